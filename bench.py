@@ -6,8 +6,8 @@
       bench.py --gpus N --steps K --warmup W
 
 Workloads (`--config`; default `auto`: `value` = c4 for EVERY N -- the workload BASELINE.json's metric is quoted on at
-1 / 2 / 4 / 8 GPUs, strong scaling, K steps = K whole maps with upload, fit, llh / rss, download and the gather inside -- and
-the c3 legs (inputs resident / streamed, one plan in flight for the kernel's roofline figures) run beside it on
+1 / 2 / 4 / 8 GPUs, strong scaling, K steps = K whole maps with upload, fit, llh / rss, download and the gather inside -- and,
+with `--full`, the c3 legs (inputs resident / streamed, one plan in flight for the kernel's roofline figures) run beside it on
 min(K, 8) steps and are reported as `value_resident`, `value_streamed`, `single_stream`, `single_caller` in the same line):
   c3  BASELINE configs[2]: `--batch` (1024) synthetic 2-ZARC spectra per GPU, shared 256-point frequency grid, 512-point
       tau grid.  A step = one full QPHB fit (DRT._qphb_fit_core: scaling, initial-weights QP, hyper-parameter loop to
@@ -16,6 +16,15 @@ min(K, 8) steps and are reported as `value_resident`, `value_streamed`, `single_
       fits its share on one plan that cuts it into side-by-side ranges, or on `--inflight` plans), a step = upload + fit + download on every rank + one gather of the
       results on rank 0, all inside the timed region.  Strong scaling.
 Rank 0 prints ONE JSON line.  `value` is always whole-job fits per second.
+
+A plain run measures the headline alone: for `auto`, set-up, W warm-up maps (at least one: it builds the plans), K timed maps
+and the result line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = one timed map, the workload);
+for `c3` / `c4`, their first timed leg alone.  `--full` adds everything else the line has held: the c3 legs beside the map,
+the rooflines and phase split, the single-spectrum and configs[4] timings, the matrix-build roofline and the CPU baselines
+(the `--no-*` options switch single legs of a `--full` run off).
+`--dump-outputs DIR` writes, after the timed steps, what the headline's last step returned to its caller as DIR/<name>.npy
+(float64; integer and boolean fields converted, at most 64 MB: a larger output is cut to a fixed, seeded sample of its
+rows, listed in DIR/rows.npy).  The inputs are seeded: the same arguments give the same inputs in every run.
 """
 import argparse
 import hashlib
@@ -263,6 +272,46 @@ def self_launch(n):
     return 1 if bad else 0
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def map_outputs(got):
+    """the triple mapping.fit_observations_sharded returns on rank 0, as one flat dict of arrays"""
+    obs_x, obs_special, res = got
+    outputs = {"obs_x": obs_x}
+    outputs.update({f"special_{k}": v for k, v in obs_special.items()})
+    outputs.update({k: v for k, v in res.items() if k != "obs_fit_errors"})
+    return outputs
+
+
+def dump_outputs(dirname, outputs):
+    """--dump-outputs: every numeric array of `outputs` as DIR/<name>.npy in float64 (complex as <name>_real / <name>_imag);
+    dicts (timings) and non-numeric fields are left out.  Above DUMP_LIMIT_BYTES the arrays whose first axis is the batch
+    keep a fixed, seeded sample of its rows (DIR/rows.npy), the others are written whole."""
+    arrays = {}
+    for name, v in outputs.items():
+        if isinstance(v, dict):
+            continue
+        a = np.asarray(v)
+        if a.dtype == object or a.dtype.kind not in "biufc":
+            continue
+        if a.dtype.kind == "c":
+            arrays[name + "_real"], arrays[name + "_imag"] = a.real.astype(np.float64), a.imag.astype(np.float64)
+        else:
+            arrays[name] = a.astype(np.float64)
+    rows = max((a.shape[0] for a in arrays.values() if a.ndim), default=0)
+    total = sum(a.size * 8 for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES and rows:
+        batched = sum(a.size * 8 for a in arrays.values() if a.ndim and a.shape[0] == rows)
+        keep = max(1, int(rows * (DUMP_LIMIT_BYTES - (total - batched) - 8 * rows) / batched))
+        idx = np.sort(np.random.default_rng(0).choice(rows, size=min(keep, rows), replace=False))
+        arrays = {k: a[idx] if a.ndim and a.shape[0] == rows else a for k, a in arrays.items()}
+        arrays["rows"] = idx.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def _flush_c_stdio():
     import ctypes
     try:
@@ -279,7 +328,7 @@ def main():
     ap.add_argument("--config", choices=("auto", "c3", "c4"), default="auto",
                     help="c3 = configs[2] (1024 spectra per GPU, weak), c4 = configs[3] (one 10 000-spectrum map sharded "
                          "over the ranks, strong); auto = `value` is the c4 map (K steps = K maps, transfers and gather inside) "
-                         "on every N, with the c3 legs (resident / streamed / one plan for the roofline) beside it on min(K, 8) steps")
+                         "on every N, with --full the c3 legs (resident / streamed / one plan for the roofline) beside it on min(K, 8) steps")
     ap.add_argument("--no-scale-reference", action="store_true", help="c3: skip the configs[3] map leg")
     ap.add_argument("--scale-steps", type=int, default=2, help="maps timed by the `scale_reference` leg (one warm-up map before)")
     ap.add_argument("--force-dist", action="store_true",
@@ -302,6 +351,10 @@ def main():
     ap.add_argument("--no-single-caller", action="store_true",
                     help="skip the sub-batched one-caller leg (its launches are half-size: a rocprofv3 --stats average over a run "
                          "with it is not the one-range launch's)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, every other leg: c3 legs, rooflines, other configs, matrix build, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline's last timed step returned as DIR/<name>.npy (float64, at most 64 MB)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # launched without torch.distributed.run: this process -- which has not touched the GPU and never will -- starts
@@ -332,7 +385,7 @@ def main():
 
     # ---- CPU legs first: the process pool forks, so it must run before anything in this process has opened the GPU ----
     cpu = None
-    if rank_env == 0 and world_env == 1 and not args.no_cpu_baseline:
+    if args.full and rank_env == 0 and world_env == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(freq, tau, synth.zarc2_batch(freq, 64, first_seed=0), procs=args.cpu_procs)
 
     import threading
@@ -362,25 +415,18 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
     _flush_c_stdio()                                         # (RCCL's start-up banner leaves every rank's buffer now)
 
-    if config == "c3":
-        B = args.batch
-        z = synth.zarc2_batch(freq, B, first_seed=rank * B)
-        nfl = max(1, min(4 if args.inflight in (None, "auto") else args.inflight, max(c3_steps, 1)))
-        chunks = [np.arange(B)] * nfl                        # every plan holds the whole batch
-        job_fits = world * B
-    else:
-        total = args.total
-        mine = shard_indices(total, world, rank, args.shard)
-        z_all = None
-        # every rank generates its own rows only (seed = global observation index)
-        z = np.concatenate([synth.zarc2_batch(freq, 1, first_seed=int(i)) for i in mine]) if len(mine) else \
-            np.zeros((0, len(freq)), dtype=complex)
-        from hipdrt.mapping.drtmd import auto_inflight
-        nfl = auto_inflight(len(mine)) if args.inflight in (None, "auto") else args.inflight
-        nfl = max(1, min(nfl, max(len(mine), 1)))
-        chunks = np.array_split(np.arange(len(mine)), nfl)
-        B = len(mine)
-        job_fits = total
+    def finish(out, outputs=None, code=0):
+        if rank == 0 and args.dump_outputs and outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
+        # the JSON line is the LAST thing this job writes to stdout: RCCL prints its banner through C stdio, which is block-buffered
+        # on a pipe and would otherwise be flushed at exit, behind the line
+        hd.barrier()
+        hd.destroy()
+        _flush_c_stdio()
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if code:
+            raise SystemExit(code)
 
     # ---- BASELINE configs[3] on this N: the headline (`value`) with --config auto, `scale_reference` beside a c3 headline --------
     # (Until round 6 it mattered by 4 % WHERE in the process this ran -- the runtime's placement of the plans' streams on hardware
@@ -388,8 +434,8 @@ def main():
     # csrc/api.hip: StreamPool, and the order of the legs no longer decides anything.  The map's default is ONE plan, which cuts
     # every rank's share into ranges itself: mapping.auto_inflight.)
     def run_scale_reference():
-        scale_ref = None
-        if config == "c3" and not args.no_scale_reference:
+        scale_ref = got4 = None
+        if config == "c3":
             from hipdrt.mapping.drtmd import auto_inflight, fit_observations_sharded
             mine4 = shard_indices(args.total, world, rank, args.shard)
             z4 = np.zeros((args.total, len(freq)), dtype=complex)          # every rank holds its own rows only
@@ -432,11 +478,53 @@ def main():
                     d_._context.close()
             del d4, z4
             gc.collect()
+        return scale_ref, got4
 
+    if promote and not args.full:
+        # a plain run: the headline alone -- the configs[3] map, K maps timed; its result is also what --dump-outputs writes
+        scale_ref, got4 = run_scale_reference()
+        out = None
+        if rank == 0:
+            out = {"metric": "DRT fits/sec (256 freq x 512 tau, batched)", "value": scale_ref["value"], "unit": "fits/s",
+                   "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                   "ms_per_step": scale_ref["seconds_per_map"] * 1e3, "higher_is_better": True, "scaling": "strong",
+                   "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+                   "config": {"workload": scale_ref["workload"] + f" -- a step = one whole map; TRANSFERS ARE INSIDE: the {args.total} "
+                                          f"x 256 complex spectra start in host memory, the results ({len(tau) + 9} doubles per "
+                                          f"spectrum) are downloaded and gathered on rank 0 in every step",
+                              "nf": len(freq), "ntau": len(tau), "spectra_per_map": args.total,
+                              "spectra_per_rank": scale_ref["spectra_per_rank"],
+                              "batches_in_flight_per_gpu": scale_ref["batches_in_flight_per_gpu"]},
+                   "scale_reference": scale_ref,
+                   "collectives": {"backend": hd.backend(), "forced_one_rank_group": bool(hd.forced()),
+                                   "torch_imported": "torch" in sys.modules},
+                   "full": False}
+        # (an incomplete map is the headline's own failure here: the line says so and the run exits non-zero)
+        bad = rank == 0 and "error" in scale_ref
+        finish(out, map_outputs(got4) if rank == 0 else None, code=1 if bad else 0)
+        return
 
-        return scale_ref
+    if config == "c3":
+        B = args.batch
+        z = synth.zarc2_batch(freq, B, first_seed=rank * B)
+        nfl = max(1, min(4 if args.inflight in (None, "auto") else args.inflight, max(c3_steps, 1)))
+        chunks = [np.arange(B)] * nfl                        # every plan holds the whole batch
+        job_fits = world * B
+    else:
+        total = args.total
+        mine = shard_indices(total, world, rank, args.shard)
+        z_all = None
+        # every rank generates its own rows only (seed = global observation index)
+        z = np.concatenate([synth.zarc2_batch(freq, 1, first_seed=int(i)) for i in mine]) if len(mine) else \
+            np.zeros((0, len(freq)), dtype=complex)
+        from hipdrt.mapping.drtmd import auto_inflight
+        nfl = auto_inflight(len(mine)) if args.inflight in (None, "auto") else args.inflight
+        nfl = max(1, min(nfl, max(len(mine), 1)))
+        chunks = np.array_split(np.arange(len(mine)), nfl)
+        B = len(mine)
+        job_fits = total
 
-    scale_ref = None
+    scale_ref = got4 = None
 
     # one DRT + plan + HIP stream per in-flight batch
     if config == "c3":
@@ -531,16 +619,18 @@ def main():
     single_elapsed = transfer_elapsed = one_caller_elapsed = None
     if config == "c3":
         elapsed = timed_c3(nfl, worker_resident)
-        reset()
-        transfer_elapsed = timed_c3(nfl, worker_transfers)          # same steps with upload and download inside
-        reset()
-        single_elapsed = timed_c3(1, worker_resident)               # one batch in flight: un-overlapped launches
+        if args.full:
+            reset()
+            transfer_elapsed = timed_c3(nfl, worker_transfers)      # same steps with upload and download inside
+            reset()
+            single_elapsed = timed_c3(1, worker_resident)           # one batch in flight: un-overlapped launches
         qp_ms, qp_launch = stats[0]["qp_ms"], stats[0]["qp_launch"]
         phase = dict(stats[0]["phase"])
         # the configs[3] map: behind the four configs[2] plans' streams (queues 0..3: its three land on 4, 5, 6) and in front of
         # the one-caller leg, whose ranges make two more streams
-        scale_ref = run_scale_reference() if not args.no_scale_reference else None
-        if not args.no_single_caller:
+        if args.full and not args.no_scale_reference:
+            scale_ref, got4 = run_scale_reference()
+        if args.full and not args.no_single_caller:
             plans[0].set_subbatches(0)                              # one caller, one plan, the library cuts the batch into ranges
             one_caller_elapsed = timed_c3(1, worker_resident)
             plans[0].set_subbatches(1)
@@ -673,7 +763,7 @@ def main():
                 "value": world * B * c3_steps / transfer_elapsed, "ms_per_step": transfer_elapsed / c3_steps * 1e3,
                 "note": "same K steps with the upload of the spectra and the download of all results inside every step"},
         }
-        if not args.no_matrix_build:
+        if args.full and not args.no_matrix_build:
             # secondary roofline (north_star): batched Z'/Z'' build with per-spectrum frequency grids
             Bm = 512
             fb = np.sort(10 ** np.random.default_rng(0).uniform(-1, 6, size=(Bm, 256)), axis=1)[:, ::-1].copy()
@@ -691,7 +781,7 @@ def main():
                                             "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                             "frac": gbs / HBM_PEAK_GBS, "bytes_per_launch": byts,
                                             "avg_launch_ms": ms / reps}
-        if world == 1 and not args.no_other_configs:
+        if args.full and world == 1 and not args.no_other_configs:
             # the other BASELINE configs as measured here (parity cases, not the bench metric): configs[1] one spectrum
             # 256 x 512, configs[4] one joint chrono + EIS fit with DOP (512 f + 4096 t x 1024 tau); wall time of the
             # second call (plans and lookup tables warm), inputs handed over as host arrays
@@ -797,13 +887,19 @@ def main():
             cpu["gpu_over_reference_structure"] = value / cpu["reference_structure"]["value"]
         else:
             out["cpu_baseline"] = None
-    # the JSON line is the LAST thing this job writes to stdout: RCCL prints its banner through C stdio, which is block-buffered
-    # on a pipe and would otherwise be flushed at exit, behind the line
-    hd.barrier()
-    hd.destroy()
-    _flush_c_stdio()
+        out["full"] = args.full
+        if not args.full:                                   # a plain c3 / c4 run: its first leg's headline alone
+            out = {k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+                                       "scaling", "vs_baseline", "dtype", "data", "config", "collectives", "full")}
+    outputs = None
     if rank == 0:
-        print(json.dumps(out), flush=True)
+        if promote and scale_ref is not None and "error" not in scale_ref:
+            outputs = map_outputs(got4)                     # the headline is the map
+        elif config == "c3":
+            outputs = res                                   # one plan's batch (every plan fits the same spectra)
+        else:
+            outputs = map_outputs(gathered)
+    finish(out, outputs)
 
 
 if __name__ == "__main__":

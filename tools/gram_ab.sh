@@ -3,7 +3,7 @@
 cd /tmp; export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT; O=gpurun_out; T=${1:-gram_ab}; shift; mkdir -p $O; : > $O/${T}_kernels.txt
 one() {
   rm -rf $O/prof_$T
-  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$T -- python3 bench.py --inflight 1 --steps ${STEPS:-2} --warmup ${WARM:-1} --no-cpu-baseline --no-other-configs --no-matrix-build > $O/prof_${T}.log 2>&1
+  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$T -- python3 bench.py --full --inflight 1 --steps ${STEPS:-2} --warmup ${WARM:-1} --no-cpu-baseline --no-other-configs --no-matrix-build > $O/prof_${T}.log 2>&1
   echo "== $1" >> $O/${T}_kernels.txt
   python3 - $O/prof_$T/*/*kernel_stats.csv >> $O/${T}_kernels.txt <<'PY'
 import csv, sys

@@ -3,7 +3,7 @@
 cd /tmp; export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT; O=gpurun_out
 for ns in "$@"; do
   export HIPDRT_GRAM_NS=$ns
-  rocprofv3 --kernel-trace --output-format csv -d $O/prof_gns$ns -- python3 bench.py --inflight 1 --steps 1 --warmup 0 --no-cpu-baseline --no-other-configs --no-matrix-build > $O/prof_gns$ns.log 2>&1
+  rocprofv3 --kernel-trace --output-format csv -d $O/prof_gns$ns -- python3 bench.py --full --inflight 1 --steps 1 --warmup 0 --no-cpu-baseline --no-other-configs --no-matrix-build > $O/prof_gns$ns.log 2>&1
   echo "== HIPDRT_GRAM_NS=$ns"
   python3 -c "
 import csv, glob

@@ -50,7 +50,7 @@ def main():
         "fetch_bytes_per_launch_x2": 2.0 * fetch_raw,
         "write_bytes_per_launch": write_b,
         "hbm_bytes_per_launch": 2.0 * fetch_raw + write_b,
-        "note": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `bench.py --steps 1 "
+        "note": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `bench.py --full --steps 1 "
                 "--warmup 0 --inflight 1 --no-cpu-baseline --no-single-caller` (every launch = the 1024-spectrum batch of ONE plan, ONE range: "
                 "the launches `roofline.avg_launch_ms` averages over; only full-batch launches are counted.  CORRECTION: the figures of "
                 "rounds 4-5 (26.1 ... 26.4 GB) were averages that included the one-caller leg's half-size launches -- per full-batch "

@@ -1,5 +1,5 @@
 P='import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print(sys.argv[1], round(d["value_resident"],1), round(d["value_streamed"],1), round(d["single_stream"]["value"],1), d["c3"]["steps"] if d.get("c3") else d["steps"])'
-F="--no-cpu-baseline --no-other-configs --no-matrix-build --no-scale-reference --no-single-caller"
+F="--full --no-cpu-baseline --no-other-configs --no-matrix-build --no-scale-reference --no-single-caller"
 python bench.py $F --steps 8 2>/dev/null | python -c "$P" auto8
 python bench.py $F --steps 4 2>/dev/null | python -c "$P" auto4
 python bench.py $F --config c3 --steps 8 2>/dev/null | python -c "$P" c3_8
