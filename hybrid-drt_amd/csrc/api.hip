@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -116,6 +117,52 @@ struct hipdrt_subfit {
     // (ctx.stream is borrowed from the library's pool for the duration of one fit: hipdrt_plan_fit)
 };
 hipdrt_plan::~hipdrt_plan() = default;
+
+// ---- the buffers a plan holds once per staged spectrum, sized by its capacity --------------------------------------------
+// plan_alloc_batch allocates them, make_view cuts a sub-batch range's windows out of them, hipdrt_plan_bytes_per_spectrum adds
+// them up for the map driver.  Buffers that only some plans use (outlier_t, w_eff, wrow, wfac, dop_rho, dop_xmx, vz_entry, the
+// history) stay outside the table and are never windowed: a plan which may use a buffer outside the table fits as one range
+// (subbatch_count).
+struct SpecDims { size_t n, m, nf; int qp_G; };
+struct PerSpectrumBuf {
+    DevBuf hipdrt_plan::*buf;
+    size_t (*bytes)(const SpecDims&);      // per spectrum
+    bool lazy;                             // allocated where it is first needed, not by plan_alloc_batch
+};
+static const PerSpectrumBuf kPerSpectrum[] = {
+    {&hipdrt_plan::z_re, [](const SpecDims& d) { return d.nf * sizeof(double); }},
+    {&hipdrt_plan::z_im, [](const SpecDims& d) { return d.nf * sizeof(double); }},
+    {&hipdrt_plan::rv, [](const SpecDims& d) { return d.m * sizeof(double); }},
+    {&hipdrt_plan::w, [](const SpecDims& d) { return d.m * sizeof(double); }},
+    {&hipdrt_plan::est_w, [](const SpecDims& d) { return d.m * sizeof(double); }},
+    {&hipdrt_plan::x, [](const SpecDims& d) { return d.n * sizeof(double); }},
+    {&hipdrt_plan::x_in, [](const SpecDims& d) { return d.n * sizeof(double); }},
+    {&hipdrt_plan::q, [](const SpecDims& d) { return d.n * sizeof(double); }},
+    {&hipdrt_plan::s, [](const SpecDims& d) { return 3 * d.n * sizeof(double); }},
+    {&hipdrt_plan::rho, [](const SpecDims&) { return 3 * sizeof(double); }},
+    {&hipdrt_plan::xmx, [](const SpecDims&) { return 3 * sizeof(double); }},
+    {&hipdrt_plan::coef_scale, [](const SpecDims&) { return sizeof(double); }},
+    {&hipdrt_plan::var_floor, [](const SpecDims&) { return sizeof(double); }},
+    {&hipdrt_plan::pcost, [](const SpecDims&) { return sizeof(double); }},
+    {&hipdrt_plan::active, [](const SpecDims&) { return sizeof(int); }},
+    {&hipdrt_plan::outer_iters, [](const SpecDims&) { return sizeof(int); }},
+    {&hipdrt_plan::fit_status, [](const SpecDims&) { return sizeof(int); }},
+    {&hipdrt_plan::qp_iters_total, [](const SpecDims&) { return sizeof(int); }},
+    {&hipdrt_plan::qp_status, [](const SpecDims&) { return sizeof(int); }},
+    {&hipdrt_plan::qp_iters, [](const SpecDims&) { return sizeof(int); }},
+    {&hipdrt_plan::L, [](const SpecDims& d) { return qp_scratch_doubles((int)d.n, d.qp_G) * sizeof(double); }},
+    {&hipdrt_plan::qpstate, [](const SpecDims& d) { return (d.qp_G > 1 ? d.qp_G : 1) * qp_state_doubles((int)d.n) * sizeof(double); }},
+    {&hipdrt_plan::gsync, [](const SpecDims&) { return qp_gsync_ints() * sizeof(int); }},
+    {&hipdrt_plan::Ppk, [](const SpecDims& d) { return qp_ppk_doubles((int)d.n) * sizeof(double); }},
+    {&hipdrt_plan::order, [](const SpecDims&) { return sizeof(int); }},
+    // [3][capacity][m], a range's window its own [3][nb][m]: plan_hyper's batched products, allocated by plan_hyper / hipdrt_plan_fit
+    {&hipdrt_plan::premv, [](const SpecDims& d) { return 3 * d.m * sizeof(double); }, true},
+};
+
+// (prepared plans have no frequency grid: nf = 0, the impedance buffers keep one entry per spectrum)
+static SpecDims spec_dims(const hipdrt_plan* p) {
+    return {(size_t)p->n, (size_t)p->m, (size_t)(p->nf > 0 ? p->nf : 1), p->qp_G};
+}
 
 static int upload(DevBuf& buf, const void* src, size_t bytes, hipStream_t st) {
     HIPDRT_CHECK(buf.alloc(bytes));
@@ -810,27 +857,14 @@ static int plan_build_matrices(hipdrt_plan* p, bool build_lookup) {
 // work space for `capacity` spectra
 static int plan_alloc_batch(hipdrt_plan* p) {
     const size_t cap = (size_t)p->capacity;
-    const int n = p->n, m = p->m, nf = p->nf > 0 ? p->nf : 1;
-    HIPDRT_CHECK(p->z_re.alloc(cap * nf * sizeof(double))); HIPDRT_CHECK(p->z_im.alloc(cap * nf * sizeof(double)));
-    HIPDRT_CHECK(p->rv.alloc(cap * m * sizeof(double))); HIPDRT_CHECK(p->w.alloc(cap * m * sizeof(double)));
-    HIPDRT_CHECK(p->est_w.alloc(cap * m * sizeof(double)));
-    HIPDRT_CHECK(p->x.alloc(cap * n * sizeof(double))); HIPDRT_CHECK(p->x_in.alloc(cap * n * sizeof(double)));
-    HIPDRT_CHECK(p->q.alloc(cap * n * sizeof(double)));
-    HIPDRT_CHECK(p->s.alloc(cap * 3 * n * sizeof(double)));
-    HIPDRT_CHECK(p->rho.alloc(cap * 3 * sizeof(double))); HIPDRT_CHECK(p->xmx.alloc(cap * 3 * sizeof(double)));
-    HIPDRT_CHECK(p->coef_scale.alloc(cap * sizeof(double))); HIPDRT_CHECK(p->var_floor.alloc(cap * sizeof(double)));
-    HIPDRT_CHECK(p->pcost.alloc(cap * sizeof(double)));
-    for (DevBuf* ib : {&p->active, &p->outer_iters, &p->fit_status, &p->qp_iters_total, &p->qp_status, &p->qp_iters})
-        HIPDRT_CHECK(ib->alloc(cap * sizeof(int)));
-    HIPDRT_CHECK(p->n_active.alloc(sizeof(int)));
+    const int n = p->n, m = p->m;
     p->qp_G = qp_group_size(p->capacity, n, p->ctx->qp_force_group);
     HIPDRT_REQUIRE(p->qp_G >= 0, "n too large for the QP kernels");
-    HIPDRT_CHECK(p->L.alloc(cap * qp_scratch_doubles(n, p->qp_G) * sizeof(double)));
+    const SpecDims d = spec_dims(p);
+    for (const PerSpectrumBuf& e : kPerSpectrum)
+        if (!e.lazy) HIPDRT_CHECK((p->*e.buf).alloc(cap * e.bytes(d)));
+    HIPDRT_CHECK(p->n_active.alloc(sizeof(int)));
     HIPDRT_CHECK(p->Ptmp.alloc((size_t)n * p->ldp * sizeof(double)));
-    HIPDRT_CHECK(p->qpstate.alloc(cap * (p->qp_G > 1 ? p->qp_G : 1) * qp_state_doubles(n) * sizeof(double)));
-    HIPDRT_CHECK(p->gsync.alloc(cap * qp_gsync_ints() * sizeof(int)));
-    HIPDRT_CHECK(p->Ppk.alloc(cap * qp_ppk_doubles(n) * sizeof(double)));
-    HIPDRT_CHECK(p->order.alloc(cap * sizeof(int)));
     if (p->opts.outlier_p > 0.0) {
         HIPDRT_CHECK(p->vmm_base.alloc((size_t)m * m * sizeof(double)));
         HIPDRT_CHECK(p->outlier_t.alloc(cap * m * sizeof(double)));
@@ -1107,6 +1141,21 @@ static GramL2 plan_l2(const hipdrt_plan* p, double l2_lambda_0, const double* de
     return g;
 }
 
+// What the posterior entry points call "the final P": calculate_pq with the final weights / s / rho (drt1d.py:1006), from
+// calculate_pq's scaled_weights -- w_eff whenever the plan has weight factors.  b >= 0: s, rho, dop_rho and the weights of
+// spectrum b alone.
+struct FinalP { GramL2 g; const double* w; };
+static FinalP plan_final_p(const hipdrt_plan* p, int b) {
+    FinalP f{plan_l2(p, p->opts.l2_lambda_0, p->opts.derivative_weights, p->prepared ? p->desc.dop_l2_lambda_0 : 0.0),
+             p->has_weight_factors() ? p->w_eff.d() : p->w.d()};
+    if (b >= 0) {
+        f.g.s += (size_t)b * 3 * p->n; f.g.rho += (size_t)b * 3;
+        if (f.g.dop_size > 0) f.g.dop_rho += (size_t)b * 3;
+        f.w += (size_t)b * p->m;
+    }
+    return f;
+}
+
 // Reach of the penalty matrices on a log-uniform grid: the largest distance from the diagonal at which the first row of the DRT
 // block of any order is not exactly zero (Gaussian basis: e^(-a^2 / 2) underflows ~39 grid points out at 10 points per decade,
 // whatever the matrix size).  The Gram kernel's L2 epilogue skips tiles that lie wholly beyond it.  Once per plan.
@@ -1186,6 +1235,70 @@ struct PhaseTimer {
 };
 }  // namespace
 
+// QP arguments of the outer loop: one P per spectrum in the packed tile layout, the loop's constraint vector
+static QpArgs loop_qp_args(hipdrt_plan* p, const hipdrt_qp_opts& qpo) {
+    const int n = p->n;
+    QpArgs qa{};
+    qa.B = p->B; qa.n = n; qa.ldp = p->ldp; qa.q = p->q.d(); qa.h = p->h.d(); qa.h_stride = 0;
+    qa.L = p->L.d(); qa.ldl = p->ldl;
+    p->qp_layout(p->B, qa);
+    qa.x = p->x.d(); qa.iters = p->qp_iters.i(); qa.pcost = p->pcost.d(); qa.status = p->qp_status.i();
+    qa.iters_accum = p->qp_iters_total.i(); qa.opts = qpo;
+    qa.state = p->qpstate.d(); qa.state_ld = qp_state_ld(n); qa.state_stride = (long long)qp_state_doubles(n);
+    qa.P = nullptr; qa.p_stride = (long long)n * p->ldp; qa.active = p->active.i();
+    qa.Ppk = p->Ppk.d(); qa.ppk_stride = (long long)qp_ppk_doubles(n); qa.nchp = qp_nchp(n);
+    return qa;
+}
+
+// One outer iteration of the staged batch on the weights `wq` the QP sees: P and q (phase 1, opened by the caller), the QP
+// (phase 2; workgroups dispatched longest first when an `order` buffer is given), the hyper-parameter step (phase 3)
+static int outer_iteration(hipdrt_plan* p, hipStream_t st, PhaseTimer& tm, const FitState& fs, const GramL2& g, QpArgs qa,
+                           const double* wq, int* order, int it) {
+    const int B = p->B, n = p->n, m = p->m;
+    launch_gram_l2(st, B, m, n, p->rm.d(), p->ldrm, wq, g, nullptr, p->ldp, (long long)n * p->ldp, p->active.i(),
+                   p->Ppk.d(), (long long)qp_ppk_doubles(n), qp_nchp(n), p->rm_stride);
+    launch_qvec(st, B, m, n, p->rm.d(), p->ldrm, wq, p->rv.d(), p->l1.d(), 0.0, p->q.d(), p->active.i(), p->rm_stride);
+    LAUNCH_OK();
+    tm.mark(2);
+    if (order && B * sizeof(int) <= 48 * 1024) {     // dispatch order from the previous QP's iteration counts
+        launch_lpt_order(st, B, p->qp_iters.i(), p->active.i(), order);
+        qa.order = order;
+    }
+    TRY(launch_qp(st, qa));
+    tm.mark(3);
+    TRY(plan_hyper(p, st, fs, B, it));
+    LAUNCH_OK();
+    return HIPDRT_OK;
+}
+
+// The outer loop (drt1d.py:877-988) with the options of `fs`: until no spectrum is active, at most max_iter iterations.
+// `weights(it)` applies the caller's weight scaling of iteration `it` and returns the weights the QP sees.
+static int outer_loop(hipdrt_plan* p, hipStream_t st, PhaseTimer& tm, const FitState& fs,
+                      const std::function<const double*(int)>& weights) {
+    const GramL2 g = plan_l2(p, fs.opts.l2_lambda_0, fs.opts.derivative_weights, p->prepared ? p->desc.dop_l2_lambda_0 : 0.0);
+    const QpArgs qa = loop_qp_args(p, fs.opts.qp);
+    for (int it = 0; it < fs.opts.max_iter; ++it) {
+        tm.mark(1);
+        HIPDRT_CHECK(hipMemsetAsync(p->n_active.p, 0, sizeof(int), st));
+        TRY(outer_iteration(p, st, tm, fs, g, qa, weights(it), p->order.i(), it));
+        int n_active = 0;
+        HIPDRT_CHECK(hipMemcpyAsync(&n_active, p->n_active.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPDRT_CHECK(hipStreamSynchronize(st));
+        if (n_active == 0) break;
+    }
+    return HIPDRT_OK;
+}
+
+// calculate_pq's q with the final weights `wfin` (qphb.py:1154-1183), then the phase record of the call
+static int outer_finish(hipdrt_plan* p, hipStream_t st, PhaseTimer& tm, const double* wfin) {
+    launch_qvec(st, p->B, p->m, p->n, p->rm.d(), p->ldrm, wfin, p->rv.d(), p->l1.d(), 0.0, p->q.d(), nullptr, p->rm_stride);
+    LAUNCH_OK();
+    tm.mark(-1);
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    tm.collect(p->t_ms, p->launches);
+    return HIPDRT_OK;
+}
+
 // the whole fit of the plan's staged spectra on the plan's stream (hipdrt_plan_fit; also run per sub-batch view)
 static int plan_fit_one(hipdrt_plan* p) {
     HIPDRT_REQUIRE(p, "plan is NULL");
@@ -1203,18 +1316,16 @@ static int plan_fit_one(hipdrt_plan* p) {
 
     // initialize_weights runs with iw_l2_lambda_0 and the DOP / DRT ratio kept (drt1d.py:640-646)
     const double dop_l2 = p->prepared ? p->desc.dop_l2_lambda_0 : 0.0;
-    GramL2 g = plan_l2(p, p->opts.iw_l2_lambda_0, p->opts.derivative_weights,
-                       dop_l2 / p->opts.l2_lambda_0 * p->opts.iw_l2_lambda_0);
+    const GramL2 g = plan_l2(p, p->opts.iw_l2_lambda_0, p->opts.derivative_weights,
+                             dop_l2 / p->opts.l2_lambda_0 * p->opts.iw_l2_lambda_0);
     const long long astr = p->rm_stride;
     const bool shared_rm = astr == 0;
-
-    QpArgs qa{};
-    qa.B = B; qa.n = n; qa.ldp = p->ldp; qa.q = p->q.d(); qa.h = p->h.d(); qa.h_stride = 0;
-    qa.L = p->L.d(); qa.ldl = p->ldl;
-    p->qp_layout(B, qa);
-    qa.x = p->x.d(); qa.iters = p->qp_iters.i(); qa.pcost = p->pcost.d(); qa.status = p->qp_status.i();
-    qa.iters_accum = p->qp_iters_total.i(); qa.opts = p->opts.qp;
-    qa.state = p->qpstate.d(); qa.state_ld = qp_state_ld(n); qa.state_stride = (long long)qp_state_doubles(n);
+    // initialize_weights' QPs: the loop's arguments, but one P for the whole batch when the response matrix is shared, every
+    // spectrum taking part, and initialize_weights' own constraint vector
+    QpArgs qa = loop_qp_args(p, p->opts.qp);
+    if (shared_rm) qa.p_stride = qa.ppk_stride = 0;
+    qa.active = nullptr;
+    if (p->h_init.p) qa.h = p->h_init.d();
 
     // ---- initialize_weights (qphb.py:1609-1681): one un-weighted, weakly penalised QP; P is the same for
     //      every spectrum (weights = 1, s = s_0, rho = rho_0), only q differs -------------------------------
@@ -1227,9 +1338,6 @@ static int plan_fit_one(hipdrt_plan* p) {
     if (separately) {
         // drt1d.py:648-672: initialize_weights once for the chrono rows and once for the impedance rows.  A QP that sees
         // only one block = unit weights on its rows and zero on the others (the zero rows add exact zeros to P and q)
-        qa.P = Prow; qa.p_stride = shared_rm ? 0 : pstr; qa.active = nullptr;
-        qa.Ppk = p->Ppk.d(); qa.ppk_stride = shared_rm ? 0 : pkstr; qa.nchp = qp_nchp(n);
-        if (p->h_init.p) qa.h = p->h_init.d();
         const int bounds[3] = {0, nc, m};
         for (int blk = 0; blk < 2; ++blk) {
             tm.mark(1);
@@ -1255,9 +1363,6 @@ static int plan_fit_one(hipdrt_plan* p) {
                 astr);
     LAUNCH_OK();
     tm.mark(2);
-    qa.P = Prow; qa.p_stride = shared_rm ? 0 : pstr; qa.active = nullptr;
-    qa.Ppk = p->Ppk.d(); qa.ppk_stride = shared_rm ? 0 : pkstr; qa.nchp = qp_nchp(n);
-    if (p->h_init.p) qa.h = p->h_init.d();          // initialize_weights' own constraint vector
     TRY(launch_qp(st, qa));
     tm.mark(3);
     if (p->opts.outlier_p > 0.0) {
@@ -1272,7 +1377,7 @@ static int plan_fit_one(hipdrt_plan* p) {
                     nullptr, astr);
         LAUNCH_OK();
         tm.mark(2);
-        qa.p_stride = (long long)n * p->ldp; qa.ppk_stride = (long long)qp_ppk_doubles(n);
+        qa.p_stride = pstr; qa.ppk_stride = pkstr;
         TRY(launch_qp(st, qa));
         tm.mark(3);
     }
@@ -1290,38 +1395,13 @@ static int plan_fit_one(hipdrt_plan* p) {
     }
 
     // ---- outer loop (drt1d.py:877-988) ----------------------------------------------------------------------
-    g = plan_l2(p, p->opts.l2_lambda_0, p->opts.derivative_weights, dop_l2);
-    qa.h = p->h.d();
-    qa.p_stride = (long long)n * p->ldp; qa.active = p->active.i();
-    qa.ppk_stride = (long long)qp_ppk_doubles(n);
-    int it = 0;
-    for (; it < p->opts.max_iter; ++it) {
-        tm.mark(1);
-        HIPDRT_CHECK(hipMemsetAsync(p->n_active.p, 0, sizeof(int), st));
-        const double* wq = p->w.d();
-        if (p->has_weight_factors()) {           // drt1d.py:889-901: row factors every iteration, weight_factor from the second
-            launch_scale_rows(st, B, m, p->w.d(), (p->wrow_late && it == 0) ? nullptr : p->wrow.d(), p->wrow_batched,
-                              it > 0 ? p->weight_factor : 1.0, p->active.i(), p->w_eff.d());
-            wq = p->w_eff.d();
-        }
-        launch_gram_l2(st, B, m, n, p->rm.d(), p->ldrm, wq, g, Prow, p->ldp, (long long)n * p->ldp, p->active.i(),
-                       p->Ppk.d(), (long long)qp_ppk_doubles(n), qp_nchp(n), astr);
-        launch_qvec(st, B, m, n, p->rm.d(), p->ldrm, wq, p->rv.d(), p->l1.d(), 0.0, p->q.d(), p->active.i(), astr);
-        LAUNCH_OK();
-        tm.mark(2);
-        if (B * sizeof(int) <= 48 * 1024) {     // dispatch order from the previous QP's iteration counts
-            launch_lpt_order(st, B, p->qp_iters.i(), p->active.i(), p->order.i());
-            qa.order = p->order.i();
-        }
-        TRY(launch_qp(st, qa));
-        tm.mark(3);
-        TRY(plan_hyper(p, st, fs, B, it));
-        LAUNCH_OK();
-        int n_active = 0;
-        HIPDRT_CHECK(hipMemcpyAsync(&n_active, p->n_active.p, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPDRT_CHECK(hipStreamSynchronize(st));
-        if (n_active == 0) break;
-    }
+    TRY(outer_loop(p, st, tm, fs, [&](int it) {
+        if (!p->has_weight_factors()) return p->w.d();
+        // drt1d.py:889-901: row factors every iteration, weight_factor from the second
+        launch_scale_rows(st, B, m, p->w.d(), (p->wrow_late && it == 0) ? nullptr : p->wrow.d(), p->wrow_batched,
+                          it > 0 ? p->weight_factor : 1.0, p->active.i(), p->w_eff.d());
+        return p->w_eff.d();
+    }));
     // ---- calculate_pq's q with the final weights (qphb.py:1154-1183) ---------------------------------------
     tm.mark(4);
     const double* wfin = p->w.d();
@@ -1336,12 +1416,7 @@ static int plan_fit_one(hipdrt_plan* p) {
         }
         wfin = p->w_eff.d();
     }
-    launch_qvec(st, B, m, n, p->rm.d(), p->ldrm, wfin, p->rv.d(), p->l1.d(), 0.0, p->q.d(), nullptr, astr);
-    LAUNCH_OK();
-    tm.mark(-1);
-    HIPDRT_CHECK(hipStreamSynchronize(st));
-    tm.collect(p->t_ms, p->launches);
-    return HIPDRT_OK;
+    return outer_finish(p, st, tm, wfin);
 }
 
 // ---- sub-batches ---------------------------------------------------------------------------------------------------------
@@ -1400,37 +1475,23 @@ static int make_view(hipdrt_plan* p, hipdrt_subfit& sf, int idx, int b0, int nb)
     for (int k = 0; k < 3; ++k) whole(v.mk[k], p->mk[k]);
     whole(v.vmm, p->vmm); whole(v.h, p->h); whole(v.l1, p->l1); whole(v.h_init, p->h_init); whole(v.vmm_base, p->vmm_base);
     whole(v.Ptmp, p->Ptmp);
-    // per spectrum: `per` bytes each
-    auto rows = [&](DevBuf& d, const DevBuf& s_, size_t per) { d.alias(s_, (size_t)b0 * per, (size_t)nb * per); };
-    const size_t D = sizeof(double), I = sizeof(int), nn = (size_t)p->n, mm = (size_t)p->m;
-    rows(v.z_re, p->z_re, p->nf * D); rows(v.z_im, p->z_im, p->nf * D);
-    rows(v.rv, p->rv, mm * D); rows(v.w, p->w, mm * D); rows(v.est_w, p->est_w, mm * D);
-    rows(v.x, p->x, nn * D); rows(v.x_in, p->x_in, nn * D); rows(v.q, p->q, nn * D); rows(v.s, p->s, 3 * nn * D);
-    rows(v.rho, p->rho, 3 * D); rows(v.xmx, p->xmx, 3 * D); rows(v.coef_scale, p->coef_scale, D); rows(v.var_floor, p->var_floor, D);
-    rows(v.pcost, p->pcost, D);
-    rows(v.active, p->active, I); rows(v.outer_iters, p->outer_iters, I); rows(v.fit_status, p->fit_status, I);
-    rows(v.qp_iters_total, p->qp_iters_total, I); rows(v.qp_status, p->qp_status, I); rows(v.qp_iters, p->qp_iters, I);
-    rows(v.order, p->order, I);
-    rows(v.L, p->L, qp_scratch_doubles(p->n, p->qp_G) * D);
-    rows(v.qpstate, p->qpstate, (size_t)(p->qp_G > 1 ? p->qp_G : 1) * qp_state_doubles(p->n) * D);
-    rows(v.gsync, p->gsync, qp_gsync_ints() * I);
-    rows(v.Ppk, p->Ppk, qp_ppk_doubles(p->n) * D);
-    rows(v.premv, p->premv, 3 * mm * D);                   // [3][nb][m] of this range (plan_hyper: batched products)
-    v.n_active.alias(p->n_active_sub, (size_t)idx * I, I);
+    // per spectrum: this range's window of every buffer of the table
+    const SpecDims d = spec_dims(p);
+    for (const PerSpectrumBuf& e : kPerSpectrum) {
+        const size_t per = e.bytes(d);
+        (v.*e.buf).alias(p->*e.buf, (size_t)b0 * per, (size_t)nb * per);
+    }
+    v.n_active.alias(p->n_active_sub, (size_t)idx * sizeof(int), sizeof(int));
     return HIPDRT_OK;
 }
 
-// device bytes one more staged spectrum costs an EIS plan (the per-spectrum buffers plan_alloc and hipdrt_plan_fit size by the
-// capacity): what a map driver divides the device's memory by before it forms its batches
+// device bytes one more staged spectrum costs an EIS plan (the per-spectrum buffers plan_alloc_batch and hipdrt_plan_fit size
+// by the capacity, batch coneqp kernel): what a map driver divides the device's memory by before it forms its batches
 int hipdrt_plan_bytes_per_spectrum(int nf, int ntau, int ns, long long* bytes) try {
     HIPDRT_REQUIRE(bytes && nf >= 1 && ntau >= 1 && ns >= 0, "arguments");
-    const size_t n = (size_t)ntau + ns, m = 2 * (size_t)nf, D = sizeof(double), I = sizeof(int);
+    const SpecDims d{(size_t)ntau + ns, 2 * (size_t)nf, (size_t)nf, 0};
     size_t b = 0;
-    b += 2 * (size_t)nf * D;                           // z_re, z_im
-    b += 3 * m * D + 3 * m * D;                        // rv, w, est_w; the three batched products of the hyper phase
-    b += 3 * n * D + 3 * n * D;                        // x, x_in, q; s
-    b += (3 + 3 + 1 + 1 + 1) * D + 8 * I;              // rho, xmx, scales, cost; flags and counters
-    b += (qp_scratch_doubles((int)n, 0) + qp_state_doubles((int)n) + qp_ppk_doubles((int)n)) * D + qp_gsync_ints() * I;
+    for (const PerSpectrumBuf& e : kPerSpectrum) b += e.bytes(d);
     *bytes = (long long)b;
     return HIPDRT_OK;
 } HIPDRT_CATCH
@@ -1563,21 +1624,6 @@ int hipdrt_plan_set_state_dop(hipdrt_plan* p, const double* dop_rho) try {
     return HIPDRT_OK;
 } HIPDRT_CATCH
 
-// QP arguments of the outer loop: one P per spectrum in the packed tile layout, the loop's constraint vector
-static QpArgs loop_qp_args(hipdrt_plan* p, const hipdrt_qp_opts& qpo) {
-    const int n = p->n;
-    QpArgs qa{};
-    qa.B = p->B; qa.n = n; qa.ldp = p->ldp; qa.q = p->q.d(); qa.h = p->h.d(); qa.h_stride = 0;
-    qa.L = p->L.d(); qa.ldl = p->ldl;
-    p->qp_layout(p->B, qa);
-    qa.x = p->x.d(); qa.iters = p->qp_iters.i(); qa.pcost = p->pcost.d(); qa.status = p->qp_status.i();
-    qa.iters_accum = p->qp_iters_total.i(); qa.opts = qpo;
-    qa.state = p->qpstate.d(); qa.state_ld = qp_state_ld(n); qa.state_stride = (long long)qp_state_doubles(n);
-    qa.P = nullptr; qa.p_stride = (long long)n * p->ldp; qa.active = p->active.i();
-    qa.Ppk = p->Ppk.d(); qa.ppk_stride = (long long)qp_ppk_doubles(n); qa.nchp = qp_nchp(n);
-    return qa;
-}
-
 // drt1d._continue_from_init (hybdrt/models/drt1d.py:1270-1365) for the fitted batch: the same outer loop re-entered from
 // the state on the device (x, s, rho [, dop_rho], weights; est_weights, xmx / dop_xmx norms and data scale stay) with updated
 // hyper-parameters.  Any data type: on prepared plans (chrono / joint fits, DOP) the plan's row factors -- chrono / eis weight
@@ -1596,7 +1642,7 @@ int hipdrt_plan_continue(hipdrt_plan* p, const hipdrt_fit_opts* opts, double wei
     HIPDRT_REQUIRE(!(p->wrow.p && p->wrow_late), "a vector-valued weight_factor belongs to the fit, not to its warm restarts");
     HIPDRT_CHECK(hipSetDevice(p->ctx->device)); (void)hipGetLastError();
     hipStream_t st = p->ctx->stream;
-    const int B = p->B, n = p->n, m = p->m;
+    const int B = p->B, m = p->m;
     TRY(plan_hist_reserve(p, opts->max_iter));
     // the row factors may be new with this call (hipdrt_plan_set_weight_factors after the fit): the buffer of the scaled final
     // weights is filled behind the loop, below
@@ -1623,35 +1669,14 @@ int hipdrt_plan_continue(hipdrt_plan* p, const hipdrt_fit_opts* opts, double wei
         HIPDRT_CHECK(hipMemsetAsync(p->qp_iters_total.p, 0, (size_t)B * sizeof(int), st));
         HIPDRT_CHECK(hipStreamSynchronize(st));
     }
-    GramL2 g = plan_l2(p, opts->l2_lambda_0, opts->derivative_weights, p->prepared ? p->desc.dop_l2_lambda_0 : 0.0);
-    QpArgs qa = loop_qp_args(p, opts->qp);
-    double* const Prow = nullptr;
-    for (int it = 0; it < opts->max_iter; ++it) {
-        tm.mark(1);
-        HIPDRT_CHECK(hipMemsetAsync(p->n_active.p, 0, sizeof(int), st));
+    TRY(outer_loop(p, st, tm, fs, [&](int) {
         // in place, like the reference's `weights[:num_chrono] *= ...; weights = weights * weight_factor`: the hyper step
         // replaces the weights with a fresh estimate afterwards
         if (p->prepared && p->wrow.p)
             launch_scale_rows(st, B, m, p->w.d(), p->wrow.d(), p->wrow_batched, weight_factor, p->active.i(), p->w.d());
         else if (weight_factor != 1.0) launch_scale_weights(st, fs, B, weight_factor);
-        launch_gram_l2(st, B, m, n, p->rm.d(), p->ldrm, p->w.d(), g, Prow, p->ldp, (long long)n * p->ldp, p->active.i(),
-                       p->Ppk.d(), (long long)qp_ppk_doubles(n), qp_nchp(n), astr);
-        launch_qvec(st, B, m, n, p->rm.d(), p->ldrm, p->w.d(), p->rv.d(), p->l1.d(), 0.0, p->q.d(), p->active.i(), astr);
-        LAUNCH_OK();
-        tm.mark(2);
-        if (B * sizeof(int) <= 48 * 1024) {
-            launch_lpt_order(st, B, p->qp_iters.i(), p->active.i(), p->order.i());
-            qa.order = p->order.i();
-        }
-        TRY(launch_qp(st, qa));
-        tm.mark(3);
-        TRY(plan_hyper(p, st, fs, B, it));
-        LAUNCH_OK();
-        int n_active = 0;
-        HIPDRT_CHECK(hipMemcpyAsync(&n_active, p->n_active.p, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPDRT_CHECK(hipStreamSynchronize(st));
-        if (n_active == 0) break;
-    }
+        return p->w.d();
+    }));
     tm.mark(4);
     // What the posterior entry points call "the final P" (hipdrt_plan_p_matrix, _param_cov, _distribution_cov, _param_var read
     // w_eff whenever the plan has weight factors): the weights this restart ended with -- the last iteration's fresh estimate --
@@ -1663,12 +1688,7 @@ int hipdrt_plan_continue(hipdrt_plan* p, const hipdrt_fit_opts* opts, double wei
         launch_scale_rows(st, B, m, p->w.d(), p->wrow.d(), p->wrow_batched, weight_factor, nullptr, p->w_eff.d());
         wfin = p->w_eff.d();
     }
-    launch_qvec(st, B, m, n, p->rm.d(), p->ldrm, wfin, p->rv.d(), p->l1.d(), 0.0, p->q.d(), nullptr, astr);
-    LAUNCH_OK();
-    tm.mark(-1);
-    HIPDRT_CHECK(hipStreamSynchronize(st));
-    tm.collect(p->t_ms, p->launches);
-    return HIPDRT_OK;
+    return outer_finish(p, st, tm, wfin);
 } HIPDRT_CATCH
 
 // qphb.iterate_qphb (hybdrt/models/qphb.py:606-972) for every staged measurement of a prepared plan: the QP on
@@ -1711,17 +1731,9 @@ int hipdrt_plan_iterate(hipdrt_plan* p, const hipdrt_iterate_state* in, int* con
         HIPDRT_CHECK(hipStreamSynchronize(st));         // `ones` and the caller's arrays may go once this returns
     }
     const GramL2 g = plan_l2(p, p->opts.l2_lambda_0, p->opts.derivative_weights, p->desc.dop_l2_lambda_0);
-    QpArgs qa = loop_qp_args(p, p->opts.qp);
+    const QpArgs qa = loop_qp_args(p, p->opts.qp);
     tm.mark(1);
-    launch_gram_l2(st, B, m, n, p->rm.d(), p->ldrm, p->w.d(), g, nullptr, p->ldp, (long long)n * p->ldp, p->active.i(),
-                   p->Ppk.d(), (long long)qp_ppk_doubles(n), qp_nchp(n), p->rm_stride);
-    launch_qvec(st, B, m, n, p->rm.d(), p->ldrm, p->w.d(), p->rv.d(), p->l1.d(), 0.0, p->q.d(), p->active.i(), p->rm_stride);
-    LAUNCH_OK();
-    tm.mark(2);
-    TRY(launch_qp(st, qa));
-    tm.mark(3);
-    TRY(plan_hyper(p, st, fs, B, 0));
-    LAUNCH_OK();
+    TRY(outer_iteration(p, st, tm, fs, g, qa, p->w.d(), nullptr, 0));      // (no dispatch order)
     tm.mark(-1);
     std::vector<int> act(B);
     HIPDRT_CHECK(hipMemcpyAsync(act.data(), p->active.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -1778,12 +1790,8 @@ int hipdrt_plan_get_p_matrix(hipdrt_plan* p, int b, double* out) try {
     HIPDRT_CHECK(hipSetDevice(p->ctx->device)); (void)hipGetLastError();
     hipStream_t st = p->ctx->stream;
     const int n = p->n, m = p->m;
-    GramL2 g = plan_l2(p, p->opts.l2_lambda_0, p->opts.derivative_weights, p->prepared ? p->desc.dop_l2_lambda_0 : 0.0);
-    g.s = p->s.d() + (size_t)b * 3 * n; g.rho = p->rho.d() + (size_t)b * 3;
-    if (g.dop_size > 0) g.dop_rho = p->dop_rho.d() + (size_t)b * 3;
-    const double* wfin = p->has_weight_factors() ? p->w_eff.d() : p->w.d();     // scaled_weights of calculate_pq
-    launch_gram_l2(st, 1, m, n, p->rm.d() + (size_t)b * p->rm_stride, p->ldrm, wfin + (size_t)b * m, g, p->Ptmp.d(),
-                   p->ldp, 0, nullptr);
+    const FinalP f = plan_final_p(p, b);
+    launch_gram_l2(st, 1, m, n, p->rm.d() + (size_t)b * p->rm_stride, p->ldrm, f.w, f.g, p->Ptmp.d(), p->ldp, 0, nullptr);
     LAUNCH_OK();
     return copy_strided(out, p->Ptmp.d(), n, n, p->ldp, st);
 } HIPDRT_CATCH
@@ -1799,10 +1807,10 @@ static int plan_quadratic_forms(hipdrt_plan* p, const double* basis_eval, int ne
     hipStream_t st = p->ctx->stream;
     const int n = p->n, m = p->m, B = p->B;
     const int nex = (neval + 15) / 16, nchp = qp_nchp(n);
-    // final P of every spectrum (calculate_pq with the final weights / s / rho, drt1d.py:1006), packed tiles only
-    GramL2 g = plan_l2(p, p->opts.l2_lambda_0, p->opts.derivative_weights, p->prepared ? p->desc.dop_l2_lambda_0 : 0.0);
-    launch_gram_l2(st, B, m, n, p->rm.d(), p->ldrm, p->has_weight_factors() ? p->w_eff.d() : p->w.d(), g, nullptr, p->ldp, 0,
-                   nullptr, p->Ppk.d(), (long long)qp_ppk_doubles(n), nchp, p->rm_stride);
+    // final P of every spectrum, packed tiles only
+    const FinalP f = plan_final_p(p, -1);
+    launch_gram_l2(st, B, m, n, p->rm.d(), p->ldrm, f.w, f.g, nullptr, p->ldp, 0, nullptr, p->Ppk.d(),
+                   (long long)qp_ppk_doubles(n), nchp, p->rm_stride);
     LAUNCH_OK();
     // evaluation rows -> packed tiles, shifted past the special-parameter slots
     DevBuf dbe, bex, scratch, dout, dstat;
@@ -1847,14 +1855,11 @@ static int plan_full_cov(hipdrt_plan* p, int b, const double* rows, int neval, i
     hipStream_t st = p->ctx->stream;
     const int n = p->n, m = p->m;
     const int nex = (neval + 15) / 16, nchp = qp_nchp(n), nch = round_up(n, 32) / 16;
-    // final P of this spectrum (calculate_pq with the final weights / s / rho), packed tiles, into its own slot of Ppk
-    GramL2 g = plan_l2(p, p->opts.l2_lambda_0, p->opts.derivative_weights, p->prepared ? p->desc.dop_l2_lambda_0 : 0.0);
-    g.s = p->s.d() + (size_t)b * 3 * n; g.rho = p->rho.d() + (size_t)b * 3;
-    if (g.dop_size > 0) g.dop_rho = p->dop_rho.d() + (size_t)b * 3;
-    const double* wfin = p->has_weight_factors() ? p->w_eff.d() : p->w.d();
+    // final P of this spectrum, packed tiles, into its own slot of Ppk
+    const FinalP f = plan_final_p(p, b);
     double* ppk = p->Ppk.d() + (size_t)b * qp_ppk_doubles(n);
-    launch_gram_l2(st, 1, m, n, p->rm.d() + (size_t)b * p->rm_stride, p->ldrm, wfin + (size_t)b * m, g, nullptr, p->ldp, 0,
-                   nullptr, ppk, 0, nchp, 0);
+    launch_gram_l2(st, 1, m, n, p->rm.d() + (size_t)b * p->rm_stride, p->ldrm, f.w, f.g, nullptr, p->ldp, 0, nullptr, ppk, 0,
+                   nchp, 0);
     LAUNCH_OK();
     DevBuf dbe, bex, scratch, dvar, dstat, dcov;
     TRY(upload(dbe, rows, (size_t)neval * ncol * sizeof(double), st));

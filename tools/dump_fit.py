@@ -1,5 +1,7 @@
 """Fits a fixed set of spectra (C1 golden-size and C2-size) with whatever library HIPDRT_LIB points to and saves the raw
-results; two dumps compared bit for bit tell whether two builds compute the same thing.
+results; two dumps compared bit for bit tell whether two builds compute the same thing.  Every path of the plan's device
+loop is taken once: EIS batch fits, a sub-batched fit, outlier_p, a warm restart, a prepared joint fit with the 'weight'
+factor rule and its restart with row factors, one iterate_qphb pass, and the posterior entry points.
 python tools/dump_fit.py out.npz   /   python tools/dump_fit.py --cmp a.npz b.npz"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,5 +39,53 @@ f = np.logspace(5.5, -0.5, 60)
 r3 = DRT(basis_tau_ppd=8).fit_eis_batch(f, synth.zarc2_batch(f, 8))      # n = 61: odd number of block columns etc.
 for k in ("x", "outer_iters", "qp_iters_total"):
     out["d_" + k] = r3[k]
+
+# the staged batch fitted as three ranges side by side (hipdrt_plan_set_subbatches)
+ds = DRT(fixed_basis_tau=c2["tau"])
+ds.stage_batch(c2["freq"], synth.zarc2_batch(c2["freq"], 384, first_seed=5000)).set_subbatches(3)
+ds.fit_staged()
+rs = ds.collect_staged()
+for k in ("x", "weights", "rho", "s_vectors", "q_vector", "outer_iters", "qp_iters_total"):
+    out["sub_" + k] = rs[k]
+out["sub_launches"] = np.array(list(rs["launches"].values()))
+
+# outlier_p: two initial QPs, outlier-aware weights in every iteration
+ro = DRT(fixed_basis_tau=c1["tau"]).fit_eis_batch(c1["freq"], z1, outlier_p=0.05)
+for k in ("x", "weights", "outer_iters", "qp_iters_total"):
+    out["outl_" + k] = ro[k]
+
+# warm restart of the C2 batch with a changed l2_lambda_0
+rc = d.continue_from_init(l2_lambda_0=142.0 / 4.0)
+for k in ("x", "weights", "rho", "q_vector", "outer_iters", "qp_iters_total"):
+    out["cont_" + k] = rc[k]
+
+# prepared joint fit: initial weights per block, row factors by the 'weight' rule; then a restart with row factors and the
+# posterior entry points on the state it leaves
+dj = DRT(warn=False)
+fj = dj.fit_hybrid(*synth.hybrid_measurement(seed=0), init_weights_separately=True, hybrid_weight_factor_method='weight')
+qp = dj.qphb_params
+out["joint_x"], out["joint_weights"], out["joint_p"] = dj.cvx_result["x"], qp["true_weights"], fj["p_matrix"]
+out["joint_factors"] = np.array([qp["chrono_weight_factor"], qp["eis_weight_factor"]])
+rj = dj.continue_from_init(weight_factor=1.3, eis_weight_factor=1.7, chrono_weight_factor=0.6, max_iter=3)
+for k in ("x", "weights", "rho", "q_vector", "outer_iters", "qp_iters_total"):
+    out["jcont_" + k] = rj[k]
+pc = dj.estimate_param_cov()
+out["jcont_param_cov"] = np.asarray(np.nan if pc is None else pc)
+dc = dj.estimate_distribution_cov(ppd=10)
+out["jcont_dist_cov"] = np.asarray(np.nan if dc is None else dc)
+v = dj.estimate_distribution_var_batch(ppd=10)
+out["jcont_var"] = np.asarray(v[0] if isinstance(v, tuple) else v)
+out["jcont_p"] = dj._plan.p_matrix(0)
+
+# one iterate_qphb pass from the start state of _qphb_fit_core on the joint fit's matrices
+from hipdrt.models import qphb
+from oracle import drt_oracle as orc
+n = qp["rm"].shape[1]
+it = qphb.iterate_qphb(np.zeros(n) + 1e-6, np.ones((3, n)), np.ones(3), None, qp["rv"], qp["true_weights"], qp["est_weights"],
+                       None, qp["rm"], qp["vmm"], qp["penalty_matrices"], "integral", qp["l1_lambda_vector"],
+                       orc.get_default_hypers(), True, np.ones(3), None, None, None, None, True, dj.special_qp_params, 1e-2, 1, None)
+for i, k in ((0, "x"), (1, "s_vectors"), (2, "rho"), (4, "weights")):
+    out["iter_" + k] = np.asarray(it[i])
+out["iter_qp"] = np.array([it[7]["iterations"], it[7]["primal objective"], it[8]], dtype=float)
 np.savez(sys.argv[1], **out)
 print("saved", sys.argv[1], {k: v.shape for k, v in out.items() if k.endswith("_x")})
