@@ -69,6 +69,13 @@ struct DevBuf {
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
+// raise kernel f's dynamic-LDS limit to `bytes` (`what` names the kernel in the error message)
+inline int set_lds_limit(const void* f, size_t bytes, const char* what) {
+    const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) { set_error(std::string("hipFuncSetAttribute(") + what + "): " + hipGetErrorString(e)); return HIPDRT_E_HIP; }
+    return HIPDRT_OK;
+}
+
 }  // namespace hipdrt
 
 struct hipdrt_ctx {

@@ -997,11 +997,8 @@ int launch_prep(hipStream_t s, const FitState& st, int B) {
     return 0;
 }
 
-static int set_lds(const void* f, size_t bytes) {
-    if (bytes <= 64 * 1024) return 0;
-    hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) { set_error(std::string("hipFuncSetAttribute: ") + hipGetErrorString(e)); return HIPDRT_E_HIP; }
-    return 0;
+static int set_lds(const void* f, size_t bytes, const char* what) {
+    return bytes <= 64 * 1024 ? 0 : set_lds_limit(f, bytes, what);
 }
 
 // w[b][i] = 1 inside [r0, r1), 0 elsewhere: the QP of init_weights_separately sees one data block at a time
@@ -1043,7 +1040,7 @@ int launch_init_weights(hipStream_t s, const FitState& st, int B, int stage, int
     // x + two row vectors, two more only for the outlier branch
     const size_t lds = ((size_t)st.n + (st.opts.outlier_p > 0.0 ? 4 : 2) * (size_t)st.m) * sizeof(double);
     if (lds > kLdsLimit) { set_error("initialize_weights: m too large for the LDS-resident kernel"); return HIPDRT_E_INVALID; }
-    if (int rc = set_lds(reinterpret_cast<const void*>(init_weights_kernel), lds)) return rc;
+    if (int rc = set_lds(reinterpret_cast<const void*>(init_weights_kernel), lds, "init_weights_kernel")) return rc;
     hipLaunchKernelGGL(init_weights_kernel, dim3(B), dim3(HT), lds, s, st, stage, r0, r1);
     if (stage == 1 || stage == 3) hipLaunchKernelGGL(record_init_qp_kernel, dim3(1), dim3(64), 0, s, st);
     return 0;
@@ -1108,7 +1105,7 @@ __global__ __launch_bounds__(HT) void llh_kernel(FitState st, double* __restrict
 
 int launch_llh(hipStream_t s, const FitState& st, int B, double* rss, double* slw, int stored, double scalar_w) {
     const size_t lds = (size_t)(st.n + 3 * st.m) * sizeof(double);
-    if (int rc = set_lds(reinterpret_cast<const void*>(llh_kernel), lds)) return rc;
+    if (int rc = set_lds(reinterpret_cast<const void*>(llh_kernel), lds, "llh_kernel")) return rc;
     hipLaunchKernelGGL(llh_kernel, dim3(B), dim3(HT), lds, s, st, rss, slw, stored, scalar_w);
     return 0;
 }
@@ -1168,7 +1165,7 @@ int launch_hyper(hipStream_t s, const FitState& st_in, int B, int it) {
         else { st.toeplitz_m = 0; lds -= cols * sizeof(double); }
     }
     if (lds > kLdsLimit) { set_error("hyper-parameter kernel: problem too large for LDS (m, n)"); return HIPDRT_E_INVALID; }
-    if (int rc = set_lds(reinterpret_cast<const void*>(hyper_kernel), lds)) return rc;
+    if (int rc = set_lds(reinterpret_cast<const void*>(hyper_kernel), lds, "hyper_kernel")) return rc;
     if (st.premv && st.premv_batched && st.opts.outlier_p <= 0.0) {
         // many fits sharing rm and vmm: both products of estimate_weights for the whole batch on the matrix pipe
         const dim3 grid((st.m + BG_TI - 1) / BG_TI, (B + BG_TB - 1) / BG_TB);

@@ -122,61 +122,37 @@ void launch_lpt_order(hipStream_t st, int B, const int* iters, const int* active
     hipLaunchKernelGGL(lpt_order_kernel, dim3(blocks), dim3(256), (size_t)B * sizeof(int), st, B, iters, active, order);
 }
 
+// every launch of a kernel with dynamic LDS beyond the default: its LDS limit, the launch, the launch error (`what` names the
+// kernel in both error messages)
+template <typename K, typename... A>
+static int launch_lds(K kernel, const char* what, dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
+    if (int rc = set_lds_limit(reinterpret_cast<const void*>(kernel), lds, what)) return rc;
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error(std::string(what) + " launch: " + hipGetErrorString(e)); return HIPDRT_E_HIP; }
+    return HIPDRT_OK;
+}
+
 static int launch_qp_resident(hipStream_t st, const QpArgs& a) {
     const int NP = round_up(a.n, 32);
     if (!a.Ppk) { set_error("qp resident: packed copy of P missing"); return HIPDRT_E_INVALID; }
     const bool gu = a.n > RNP_MAX;                      // inverse diagonal blocks in global memory: any n <= 2048
-    if (!gu && a.waves == 4) {
-        // the fat form: four wavefronts with 512 registers each (qp_resident.hpp), n <= 528
-        const size_t ldsf = resident_fat_lds_bytes(NP);
-        const void* ff = reinterpret_cast<const void*>(qp_kernel_resident<false, 256, 1, kFatPanel64, 2>);
-        hipError_t ef = hipFuncSetAttribute(ff, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsf);
-        if (ef != hipSuccess) { set_error(std::string("hipFuncSetAttribute(qp fat): ") + hipGetErrorString(ef)); return HIPDRT_E_HIP; }
-        hipLaunchKernelGGL((qp_kernel_resident<false, 256, 1, kFatPanel64, 2>), dim3(a.B), dim3(256), ldsf, st, a, NP);
-        ef = hipGetLastError();
-        if (ef != hipSuccess) { set_error(std::string("qp fat launch: ") + hipGetErrorString(ef)); return HIPDRT_E_HIP; }
-        return HIPDRT_OK;
-    }
-    const size_t lds = gu ? resident_gu_lds_bytes(true) : resident_lds_bytes(NP, true);
-    const void* fn = gu ? reinterpret_cast<const void*>(qp_kernel_resident<true>) : reinterpret_cast<const void*>(qp_kernel_resident<false>);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { set_error(std::string("hipFuncSetAttribute(qp resident): ") + hipGetErrorString(e)); return HIPDRT_E_HIP; }
-    if (gu) hipLaunchKernelGGL(qp_kernel_resident<true>, dim3(a.B), dim3(RT), lds, st, a, NP);
-    else hipLaunchKernelGGL(qp_kernel_resident<false>, dim3(a.B), dim3(RT), lds, st, a, NP);
-    e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("qp launch: ") + hipGetErrorString(e)); return HIPDRT_E_HIP; }
-    return HIPDRT_OK;
+    if (!gu && a.waves == 4)                            // the fat form: four wavefronts with 512 registers each (qp_resident.hpp)
+        return launch_lds(qp_kernel_resident<false, 256, 1, 2>, "qp fat", dim3(a.B), dim3(256), qp_resident_lds_bytes<false, 256, 2>(NP),
+                          st, a, NP);
+    if (gu) return launch_lds(qp_kernel_resident<true>, "qp resident", dim3(a.B), dim3(RT), qp_resident_lds_bytes<true>(NP), st, a, NP);
+    return launch_lds(qp_kernel_resident<false>, "qp resident", dim3(a.B), dim3(RT), qp_resident_lds_bytes<false>(NP), st, a, NP);
 }
 
 int launch_dist_var(hipStream_t st, int B, int n, const double* Ppk, long long ppk_stride, const double* Bex, int nex,
                     double* L, long long l_stride, double* out, long long out_stride, int* status) {
     if (n > GRP_NMAX) { set_error("posterior variance: n > 4096 not supported"); return HIPDRT_E_INVALID; }
-    if (n > RNP_MAX) {
-        const int NP = round_up(n, 32);
-        const size_t lds = resident_gu_lds_bytes();
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(cov_kernel_resident<true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { set_error(std::string("hipFuncSetAttribute(cov): ") + hipGetErrorString(e)); return HIPDRT_E_HIP; }
-        CovArgs a;
-        a.B = B; a.n = n; a.Ppk = Ppk; a.ppk_stride = ppk_stride; a.nchp = qp_nchp(n); a.Bex = Bex; a.nex = nex;
-        a.L = L; a.l_stride = l_stride; a.out = out; a.out_stride = out_stride; a.status = status;
-        hipLaunchKernelGGL(cov_kernel_resident<true>, dim3(B), dim3(RT), lds, st, a, NP);
-        e = hipGetLastError();
-        if (e != hipSuccess) { set_error(std::string("cov launch: ") + hipGetErrorString(e)); return HIPDRT_E_HIP; }
-        return HIPDRT_OK;
-    }
     const int NP = round_up(n, 32);
-    const size_t lds = resident_lds_bytes(NP);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(cov_kernel_resident<false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { set_error(std::string("hipFuncSetAttribute(cov): ") + hipGetErrorString(e)); return HIPDRT_E_HIP; }
     CovArgs a;
     a.B = B; a.n = n; a.Ppk = Ppk; a.ppk_stride = ppk_stride; a.nchp = qp_nchp(n); a.Bex = Bex; a.nex = nex;
     a.L = L; a.l_stride = l_stride; a.out = out; a.out_stride = out_stride; a.status = status;
-    hipLaunchKernelGGL(cov_kernel_resident<false>, dim3(B), dim3(RT), lds, st, a, NP);
-    e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("cov launch: ") + hipGetErrorString(e)); return HIPDRT_E_HIP; }
-    return HIPDRT_OK;
+    if (n > RNP_MAX) return launch_lds(cov_kernel_resident<true>, "cov", dim3(B), dim3(RT), cov_lds_bytes<true>(NP), st, a, NP);
+    return launch_lds(cov_kernel_resident<false>, "cov", dim3(B), dim3(RT), cov_lds_bytes<false>(NP), st, a, NP);
 }
 
 // doubles of factor scratch per spectrum for the posterior-variance kernel: (nch + nex) x nch tiles
@@ -192,10 +168,10 @@ int qp_occupancy(int threads, int n) {
     hipError_t e;
     if (threads != 512) return -1;
     if (n > RNP_MAX) {
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, qp_kernel_resident<true, 512>, 512, resident_gu_lds_bytes(true));
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, qp_kernel_resident<true, 512>, 512, qp_resident_lds_bytes<true>(NP));
     } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(qp_kernel_resident<false, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)resident_lds_bytes(NP, true));
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, qp_kernel_resident<false, 512>, 512, resident_lds_bytes(NP, true));
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(qp_kernel_resident<false, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)qp_resident_lds_bytes<false>(NP));
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, qp_kernel_resident<false, 512>, 512, qp_resident_lds_bytes<false>(NP));
     }
     return e == hipSuccess ? nb : -1;
 }
@@ -206,10 +182,7 @@ int qp_occupancy(int threads, int n) {
 static int launch_qp_group(hipStream_t st, const QpArgs& a, int G) {
     const int NP = round_up(a.n, 32);
     if (!a.Ppk || !a.gsync) { set_error("qp group: packed copy of P or sync words missing"); return HIPDRT_E_INVALID; }
-    const size_t lds = group_lds_bytes(NP);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(qp_kernel_group), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { set_error(std::string("hipFuncSetAttribute(qp group): ") + hipGetErrorString(e)); return HIPDRT_E_HIP; }
-    e = hipMemsetAsync(a.gsync, 0, (size_t)a.B * GRP_WORDS * sizeof(int), st);
+    hipError_t e = hipMemsetAsync(a.gsync, 0, (size_t)a.B * GRP_WORDS * sizeof(int), st);
     if (e != hipSuccess) { set_error(std::string("qp group sync reset: ") + hipGetErrorString(e)); return HIPDRT_E_HIP; }
     const int blocks = 8 * G * ((a.B + 7) / 8);
     static std::mutex mtx;
@@ -227,9 +200,7 @@ static int launch_qp_group(hipStream_t st, const QpArgs& a, int G) {
             if (e != hipSuccess) { ev = nullptr; set_error(std::string("qp group event: ") + hipGetErrorString(e)); return HIPDRT_E_HIP; }
         }
     }
-    hipLaunchKernelGGL(qp_kernel_group, dim3(blocks), dim3(512), lds, st, a, NP, G);
-    e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("qp group launch: ") + hipGetErrorString(e)); return HIPDRT_E_HIP; }
+    if (int rc = launch_lds(qp_kernel_group, "qp group", dim3(blocks), dim3(512), group_lds_bytes(NP), st, a, NP, G)) return rc;
     if (G > 1) {
         e = hipEventRecord(ev, st);
         if (e != hipSuccess) { set_error(std::string("qp group record: ") + hipGetErrorString(e)); return HIPDRT_E_HIP; }

@@ -422,7 +422,7 @@ __device__ __forceinline__ void ipm_solve(const QpArgs& a, int b, Ops& ops, cons
         };
         __syncthreads();
         FOR_E if (VALID) sm.dvec[i] = di[i] * di[i];
-        if (Ops::kFusedForward) set_rhs(0);     // the factorisation also forward-substitutes the first rhs
+        set_rhs(0);                             // the factorisation also forward-substitutes the first rhs
         __syncthreads();
         if (!ops.factor()) {
             status = (start || iters == 0) ? HIPDRT_QP_SINGULAR : HIPDRT_QP_SINGULAR_LATE;
@@ -431,7 +431,7 @@ __device__ __forceinline__ void ipm_solve(const QpArgs& a, int b, Ops& ops, cons
 
 #pragma nounroll
         for (int pc = 0; pc < nsolve; ++pc) {
-            if (Ops::kFusedForward && pc == 0) {
+            if (pc == 0) {
                 ops.backward();
             } else {
                 set_rhs(pc);

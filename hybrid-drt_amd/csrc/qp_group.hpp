@@ -101,7 +101,6 @@ struct OpsGroup : OpsResidentT<true, 512> {
     // update itself, as it does for the tiles.  Every member's chain then computes every y_j from identical bits, and at the end
     // of the factorisation every member's vector holds the whole substituted right-hand side.  Per row the block columns'
     // contributions arrive in ascending order whoever owns the row: the result does not depend on G.
-    static constexpr bool kFusedForward = true;
     static constexpr int kRedSlots = 4;
     static constexpr int kSpinLimit = 1 << 24;
     static constexpr int kRendezvousLimit = 1 << 22;       // polls of the start rendezvous (~0.5 s) before the launch gives up cleanly
@@ -585,23 +584,21 @@ struct OpsGroup : OpsResidentT<true, 512> {
                 w21 = __builtin_amdgcn_mfma_f64_16x16x4f64(-U[(size_t)(j0 + 16 + li) * PLD + 16 + 4 * s_ + kq], y[s_], w21, 0, 0, 0);
 #pragma unroll
             for (int rg = 0; rg < 4; ++rg) U[(size_t)(j0 + 16 + kq + 4 * rg) * PLD + li] = w21[rg];
-            if (fwd) {
-                // fused forward substitution: y_j = M_j b_j (b_j: published by the rows' owner, last update by wavefront 1)
-                __builtin_amdgcn_wave_barrier();
-                const int r = lane & 31;
-                const double* Mr = U + (size_t)(j0 + r) * PLD;
-                double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+            // fused forward substitution: y_j = M_j b_j (b_j: published by the rows' owner, last update by wavefront 1)
+            __builtin_amdgcn_wave_barrier();
+            const int r = lane & 31;
+            const double* Mr = U + (size_t)(j0 + r) * PLD;
+            double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
 #pragma unroll
-                for (int c = 0; c < NB; c += 4) {
-                    s0 += Mr[c] * sm.vec[j0 + c];
-                    s1 += Mr[c + 1] * sm.vec[j0 + c + 1];
-                    s2 += Mr[c + 2] * sm.vec[j0 + c + 2];
-                    s3 += Mr[c + 3] * sm.vec[j0 + c + 3];
-                }
-                const double yv = (s0 + s1) + (s2 + s3);
-                __builtin_amdgcn_wave_barrier();
-                if (lane < NB) sm.vec[j0 + lane] = yv;
+            for (int c = 0; c < NB; c += 4) {
+                s0 += Mr[c] * sm.vec[j0 + c];
+                s1 += Mr[c + 1] * sm.vec[j0 + c + 1];
+                s2 += Mr[c + 2] * sm.vec[j0 + c + 2];
+                s3 += Mr[c + 3] * sm.vec[j0 + c + 3];
             }
+            const double yv = (s0 + s1) + (s2 + s3);
+            __builtin_amdgcn_wave_barrier();
+            if (lane < NB) sm.vec[j0 + lane] = yv;
             // (A2): separates this block column's readers of the L21 scratch block from its next writer, and publishes y_j
             TS(8);
             lds_barrier();                                      // (A2)
@@ -691,7 +688,7 @@ struct OpsGroup : OpsResidentT<true, 512> {
                             dst[0] = p20; dst[64] = p21; dst[128] = p30; dst[192] = p31; dst[256] = e11; dst[320] = e21; dst[384] = e22;
                             // ... and the rows' right-hand-side entries as this member's row wavefronts left them (block columns
                             // 0 .. jb - 1 applied: la_new_range waited for those rows)
-                            if (fwd && lane < 32) labuf[(size_t)jb * GRP_LA_SLOT + 7 * 256 + lane] = sm.vec[R2 * 16 + lane];
+                            if (lane < 32) labuf[(size_t)jb * GRP_LA_SLOT + 7 * 256 + lane] = sm.vec[R2 * 16 + lane];
                             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                             if (lane == 0) __hip_atomic_store(&gs[3], prog_value(jb + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         }
@@ -721,7 +718,7 @@ struct OpsGroup : OpsResidentT<true, 512> {
                         for (int q = 0; q < 14; ++q) asm volatile("" : "+v"(t_[q]));
                         auto cat = [&](int q) { return (v4d){t_[2 * q].x, t_[2 * q].y, t_[2 * q + 1].x, t_[2 * q + 1].y}; };
                         p20 = cat(0); p21 = cat(1); p30 = cat(2); p31 = cat(3); e11 = cat(4); e21 = cat(5); e22 = cat(6);
-                        if (fwd && lane < 32) {
+                        if (lane < 32) {
                             // the owner's right-hand-side entries of rows R2, R3 replace this member's stale ones (agent-scope load:
                             // past the L1, like the accumulators)
                             unsigned long long* rp_ = reinterpret_cast<unsigned long long*>(labuf + (size_t)jb * GRP_LA_SLOT + 7 * 256 + lane);
@@ -796,11 +793,9 @@ struct OpsGroup : OpsResidentT<true, 512> {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 if (lane == 0) *(volatile int*)&sm.flag[1] = jb + 1;      // diagonal block jb + 1 staged: the chain may start
                 lds_barrier();                                  // (A2)
-                if (fwd) {
-                    // block column jb's update of the right-hand side of rows R2, R3 (every member, identical bits)
-                    fwd_update(x20, x21_, R2, j0, li, kq);
-                    if (v3) fwd_update(x30, x31, R3, j0, li, kq);
-                }
+                // block column jb's update of the right-hand side of rows R2, R3 (every member, identical bits)
+                fwd_update(x20, x21_, R2, j0, li, kq);
+                if (v3) fwd_update(x30, x31, R3, j0, li, kq);
             } else {
                 lds_barrier();                                  // (A2)
             }
@@ -929,11 +924,9 @@ struct OpsGroup : OpsResidentT<true, 512> {
                         }
                     }
                     if (ps == 0) lds_barrier();                 // (A2): y_j is in vec
-                    if (fwd) {
 #pragma unroll
-                        for (int u = 0; u < GRP_RMAXT; ++u)
-                            if (act[u] && T[u] < nch) fwd_update(x1[u], x2[u], T[u], j0, li, kq);
-                    }
+                    for (int u = 0; u < GRP_RMAXT; ++u)
+                        if (act[u] && T[u] < nch) fwd_update(x1[u], x2[u], T[u], j0, li, kq);
                 } else if (ps == 0) {
                     lds_barrier();                              // (A2)
                 }

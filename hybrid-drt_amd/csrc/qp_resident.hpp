@@ -24,13 +24,13 @@
 //    [[W1, 0], [-W2 L21 W1, W2]], so the triangular solves do one 32x32 mat-vec per block instead of a 32-step
 //    substitution chain and never fetch diagonal blocks from HBM (the diagonal-block tiles of L are not even
 //    written to HBM).
-//  * The predictor's forward substitution is fused into the factorisation (a block column's tiles update the
-//    right-hand side while they are still in registers).  Separate solves: per 32-block the mat-vec by wavefront 0, which
+//  * The predictor's forward substitution is fused into the QP's factorisation (factor64: a block column's tiles update
+//    the right-hand side while they are still in registers).  Separate solves: per 32-block the mat-vec by wavefront 0, which
 //    also applies the two tiles of the rank-32 update its next step needs; wavefronts 1..7 apply the rest meanwhile (tiles
 //    fetched two blocks ahead, one LDS-only barrier per block: forward() / backward()).
 //  * P x from the packed lower tiles: every tile is read once and used for y_T += tile x_C and y_C += tile' x_T.
-//  * Optional extra tile rows appended below the matrix turn the same factorisation into a multi-right-hand-side
-//    triangular solve (posterior variance, cov_kernel_resident).
+//  * Optional extra tile rows appended below the matrix turn the 32-column factorisation (factor()) into a multi-right-
+//    hand-side triangular solve (posterior variance, cov_kernel_resident).
 #pragma once
 #include "qp_common.hpp"
 
@@ -56,12 +56,10 @@ static constexpr int DLD = 17;           // row stride of the 16x16 LDS scratch 
 // LDS: the only structure of this kernel whose size grows with n^1 x 33, i.e. what limits the LDS-resident form to
 // n <= 528.  With U outside, the same kernel serves every n <= 2048 (LDS then holds the two n-vectors and the small
 // fixed buffers: 39 kB).
-#ifndef HIPDRT_QP_PANEL64
-#define HIPDRT_QP_PANEL64 1      // the QP kernel's factorisation walks the finished part of L once per 64 columns (factor64)
-#endif
-// P64 = LDS layout of the 64-column factorisation (factor64, the QP kernel with 8 wavefronts): L21 of BOTH 32-blocks of a super
-// column in operand-fragment layout (t21: [2][4][64]), two reduction slots instead of four, dvec without the 32 padding
-// entries, a schedule table per super column -- at n = 514 the workgroup's 160 KB are used to the last 32 bytes.
+// P64 = LDS layout of the 64-column factorisation (factor64, the QP kernel): L21 of BOTH 32-blocks of a super column in
+// operand-fragment layout (t21: [2][4][64]), two reduction slots instead of four, dvec without the 32 padding entries, a
+// schedule table per super column -- at n = 514 the workgroup's 160 KB are used to the last 32 bytes.  P64 = false: the layout
+// of the 32-column factorisation (cov_kernel_resident, and the group kernel's base); its schedule rows are not read.
 // VT = virtual threads per thread of the interior-point driver (qp_common.hpp: Reducer): the reduction slots are per VIRTUAL wavefront
 template <bool GU, int RTT = 512, bool P64 = false, int VT = 1>
 struct ResSmemT {
@@ -73,7 +71,7 @@ struct ResSmemT {
     double* dsc;     // [16][DLD]   diagonal block being factored
     double* img;     // [2][64][4]  register images of -D21', -D22' of the next diagonal block
     int* flag;       // [4]
-    unsigned char* sched;   // [nblk][SROW] owner wavefront of every tile row below a block column (build_schedule)
+    unsigned char* sched;   // [nsup][SROW] owner wavefront of every tile row below a super column (build_schedule64)
 
     // fixed offsets for everything but U, so that the small buffers have compile-time LDS addresses
     // NP + 32: NP <= 544 with U in LDS; with U outside the QP kernel (P64: n <= 2048) needs 2112, the posterior-variance kernel
@@ -99,9 +97,8 @@ struct ResSmemT {
     }
 };
 static_assert((ResSmemT<false, 512, true>::FIXED + 544 * 33) * 8 <= 160 * 1024, "n = 514 must fit one CU's LDS");
+static_assert((ResSmemT<false, 256, true, 2>::FIXED + 544 * 33) * 8 <= 160 * 1024, "n = 514 must fit one CU's LDS (fat form)");
 static_assert((ResSmemT<false, 512, true>::RED + ResSmemT<false, 512, true>::T21 + 16 * 17 + 8) % 4 == 0, "img must be 32-byte aligned");
-
-using ResSmem = ResSmemT<false>;
 
 // RTT = threads per workgroup.  512 (8 wavefronts: chain, look-ahead, six row wavefronts; one workgroup per CU) is what
 // is built.  256 (chain, look-ahead, two row wavefronts, U in global memory, two workgroups per CU so that one's sequential
@@ -125,54 +122,6 @@ struct OpsResidentT {
     // Bex[nex][nchp][256]): the factorisation treats them as more panel rows, so they come out as Bex * L^-T --
     // the multi-right-hand-side triangular solve of the posterior-variance kernel at the price of a taller panel.
     int nex = 0; const double* Bex = nullptr;
-    // The factorisation also forward-substitutes the right-hand side waiting in sm.vec (column by column, as soon as
-    // a block column's tiles sit in registers): the predictor's forward sweep costs no pass over L in HBM.
-    static constexpr bool kFusedForward = true;
-    bool fwd = true;
-
-    // Which row wavefront owns which tile row below block column jb.  The rank-k phase is bound by the busiest SIMD's FP64
-    // MFMA pipe: wavefront w sits on SIMD w % 4, the look-ahead wavefront (1) carries a fixed 14 MFMAs per half-chunk
-    // whatever the number of rows left, and a plain round-robin gives its SIMD partner (5) as many rows as everyone else
-    // (sum over the block columns of the busiest SIMD at n = 514: 657k cycles, 417k if perfectly balanced).  The table gives
-    // every row to the least-loaded SIMD instead -- one thread per block column, once per launch; results do not depend on
-    // who computes a row.  Only for the plain factorisation (no appended rows) with 8 wavefronts.
-    bool balanced = false;
-    __device__ __forceinline__ void build_schedule() {
-        if constexpr (P64) { build_schedule64(); return; }
-        balanced = (RNW == 8) && nex == 0;
-        if (!balanced) return;
-        const int ntr = (n + 15) >> 4, nblk = (n + NB - 1) / NB;
-        constexpr int SROW = Smem::SROW;
-        for (int jb = threadIdx.x; jb < nblk; jb += RT) {
-            const int tb = 2 * jb, nk2 = 4 * jb;
-            const int nsq = ntr - (tb + 4) > 0 ? ntr - (tb + 4) : 0;
-            const int c = 4 * nk2 + 12;                               // MFMAs of one row: rank-k + triangular solve
-            // no more passes than the round-robin needs: a wavefront's rows beyond its first RMAXT are streamed after
-            // barrier (A), i.e. in series with the diagonal chain
-            const int cap = RMAXT * (nsq > 6 * RMAXT ? (nsq + 6 * RMAXT - 1) / (6 * RMAXT) : 1);
-            // SIMD 0 also runs the diagonal chain (~21k cycles per block column = ~300 MFMA slots of FP64 vector work that a
-            // partner's FP64 MFMAs slow down by 40 %, profiles/r02d_chain_partner.txt): wavefront 4 is charged with it
-            int l0 = 150, l1 = (tb + 2 < ntr) ? 14 * nk2 + 24 : 0, l2 = 0, l3 = 0;      // MFMAs per SIMD
-            int c2 = 0, c3 = 0, c4 = 0, c5 = 0, c6 = 0, c7 = 0;                          // rows per wavefront
-            for (int r = 0; r < nsq; ++r) {
-                // candidate of each SIMD: its row wavefront with fewer rows (SIMD 0: 4, SIMD 1: 5, SIMD 2: 2|6, SIMD 3: 3|7)
-                const int w2 = c2 <= c6 ? 2 : 6, n2 = c2 <= c6 ? c2 : c6;
-                const int w3 = c3 <= c7 ? 3 : 7, n3 = c3 <= c7 ? c3 : c7;
-                int best = -1, bl = 0x7fffffff;
-                if (c4 < cap && l0 < bl) { best = 4; bl = l0; }
-                if (n2 < cap && l2 < bl) { best = w2; bl = l2; }
-                if (n3 < cap && l3 < bl) { best = w3; bl = l3; }
-                if (c5 < cap && l1 < bl) { best = 5; bl = l1; }
-                sm.sched[jb * SROW + r] = (unsigned char)best;
-                if (best == 4) { ++c4; l0 += c; }
-                else if (best == 5) { ++c5; l1 += c; }
-                else if (best == 2) { ++c2; l2 += c; }
-                else if (best == 6) { ++c6; l2 += c; }
-                else if (best == 3) { ++c3; l3 += c; }
-                else { ++c7; l3 += c; }
-            }
-        }
-    }
 
     // tile (t, c) starts at ((t*nch + c) * TSZ) doubles; returned in double2 units
     __device__ __forceinline__ const double2* tile2(int t, int c) const {
@@ -341,9 +290,11 @@ struct OpsResidentT {
 
     // operand fragments of a tile held in its register image (rg <-> column kq + 4 rg): k-half h = (x[2h], x[2h+1])
     //
-    // One loop over the block columns PER ROLE (the barrier sequences of the three loops match: (A), (A2) when the forward
-    // substitution is fused, (B)): state carried from one block column to the next -- the source tiles requested a column
-    // ahead -- is then live in its own role's loop only and costs the other roles no registers.
+    // factor(): the QP kernel's layout (P64) runs factor64 below; the 32-column form here is the posterior-variance kernel's
+    // (cov_kernel_resident: appended rows, no right-hand side, row wavefronts dealt the rows round-robin).
+    // One loop over the block columns PER ROLE (the barrier sequences of the three loops match: (A), (B)): state carried from
+    // one block column to the next -- the source tiles requested a column ahead -- is then live in its own role's loop only and
+    // costs the other roles no registers.
     __device__ __forceinline__ bool factor() {
         if constexpr (P64) return factor64();
         const int tid = opaque_u32(threadIdx.x), lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -411,24 +362,6 @@ struct OpsResidentT {
                 w21 = __builtin_amdgcn_mfma_f64_16x16x4f64(-U[(size_t)(j0 + 16 + li) * PLD + 16 + 4 * s_ + kq], y[s_], w21, 0, 0, 0);
 #pragma unroll
             for (int rg = 0; rg < 4; ++rg) U[(size_t)(j0 + 16 + kq + 4 * rg) * PLD + li] = w21[rg];
-            if (fwd) {
-                // fused forward substitution: y_j = M_j b_j (b_j has received every earlier column's update)
-                __builtin_amdgcn_wave_barrier();
-                const int r = lane & 31;
-                const double* Mr = U + (size_t)(j0 + r) * PLD;
-                double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-#pragma unroll
-                for (int c = 0; c < NB; c += 4) {
-                    s0 += Mr[c] * sm.vec[j0 + c];
-                    s1 += Mr[c + 1] * sm.vec[j0 + c + 1];
-                    s2 += Mr[c + 2] * sm.vec[j0 + c + 2];
-                    s3 += Mr[c + 3] * sm.vec[j0 + c + 3];
-                }
-                const double yv = (s0 + s1) + (s2 + s3);
-                __builtin_amdgcn_wave_barrier();
-                if (lane < NB) sm.vec[j0 + lane] = yv;
-                lds_barrier();                                  // (A2) y_j published
-            }
             PROF(3);
             __syncthreads();                                    // (B) block column visible to everyone
             PROF(4);
@@ -584,13 +517,6 @@ struct OpsResidentT {
                 stage_dsc(e11);
                 img21[lane] = e21;
                 img22[lane] = e22;
-                if (fwd) {
-                    lds_barrier();                              // (A2)
-                    fwd_update(x20, x21_, R2, j0, li, kq);
-                    if (v3) fwd_update(x30, x31, R3, j0, li, kq);
-                }
-            } else if (fwd) {
-                lds_barrier();                                  // (A2)
             }
             __syncthreads();                                    // (B) block column visible to everyone
         }
@@ -598,32 +524,17 @@ struct OpsResidentT {
     }
 
     // ======== wavefronts 2..7: the rows below ==========================================================================
-    // rows of pass 0 of block column jb for this wavefront (balanced schedule: the first RMAXT set bits of its mask)
-    __device__ __forceinline__ void first_rows(int jb, int wv, int lane, int ntr, int (&T)[RMAXT], bool (&act)[RMAXT]) const {
+    // rows of pass 0 of block column jb for this wavefront (round-robin: the square matrix's rows, then the appended ones)
+    __device__ __forceinline__ void first_rows(int jb, int wv, int ntr, int (&T)[RMAXT], bool (&act)[RMAXT]) const {
         constexpr int OW = RNW - 2;
         const int tb = 2 * jb;
         const int nsq = ntr - (tb + 4) > 0 ? ntr - (tb + 4) : 0;
         const int nothers = nsq + nex;
-        if (balanced) {
-            constexpr int SROW = Smem::SROW;
-            const unsigned char* row = sm.sched + jb * SROW;
-            unsigned long long m0 = __ballot(lane < nsq && row[lane] == wv), m1 = 0;
-            if (SROW > 64) m1 = __ballot(lane + 64 < nsq && row[lane + 64] == wv);
 #pragma unroll
-            for (int u = 0; u < RMAXT; ++u) {
-                int r = -1;
-                if (m0) { r = __builtin_ctzll(m0); m0 &= m0 - 1; }
-                else if (m1) { r = 64 + __builtin_ctzll(m1); m1 &= m1 - 1; }
-                T[u] = r >= 0 ? tb + 4 + r : nch;
-                act[u] = r >= 0;
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < RMAXT; ++u) {
-                const int slot = (wv - 2) + u * OW;
-                T[u] = slot < nsq ? tb + 4 + slot : nch + (slot - nsq);
-                act[u] = slot < nothers;
-            }
+        for (int u = 0; u < RMAXT; ++u) {
+            const int slot = (wv - 2) + u * OW;
+            T[u] = slot < nsq ? tb + 4 + slot : nch + (slot - nsq);
+            act[u] = slot < nothers;
         }
     }
 
@@ -644,37 +555,16 @@ struct OpsResidentT {
             const int nsq = ntr - (tb + 4) > 0 ? ntr - (tb + 4) : 0;   // rows of the square matrix below R3
             const int nothers = nsq + nex;                               // ... followed by the appended rows
             const bool two = (tb + 1) < ntr;                             // second tile column is not pure padding
-            int npass = nothers > OW * RMAXT ? (nothers + OW * RMAXT - 1) / (OW * RMAXT) : 1;
-            // balanced schedule (build_schedule): bit r of (m0, m1) = tile row tb + 4 + r is this wavefront's
-            unsigned long long m0 = 0, m1 = 0;
-            if (balanced) {
-                constexpr int SROW = Smem::SROW;
-                const unsigned char* row = sm.sched + jb * SROW;
-                m0 = __ballot(lane < nsq && row[lane] == wv);
-                if (SROW > 64) m1 = __ballot(lane + 64 < nsq && row[lane + 64] == wv);
-                const int mine = __builtin_popcountll(m0) + __builtin_popcountll(m1);
-                npass = mine > RMAXT ? (mine + RMAXT - 1) / RMAXT : 1;
-            }
+            const int npass = nothers > OW * RMAXT ? (nothers + OW * RMAXT - 1) / (OW * RMAXT) : 1;
 #pragma unroll 1
             for (int ps = 0; ps < npass; ++ps) {
                 int T[RMAXT];
                 bool act[RMAXT];
-                if (balanced) {
 #pragma unroll
-                    for (int u = 0; u < RMAXT; ++u) {
-                        int r = -1;
-                        if (m0) { r = __builtin_ctzll(m0); m0 &= m0 - 1; }
-                        else if (m1) { r = 64 + __builtin_ctzll(m1); m1 &= m1 - 1; }
-                        T[u] = r >= 0 ? tb + 4 + r : nch;
-                        act[u] = r >= 0;
-                    }
-                } else {
-#pragma unroll
-                    for (int u = 0; u < RMAXT; ++u) {
-                        const int slot = (wv - 2) + u * OW + ps * OW * RMAXT;
-                        T[u] = slot < nsq ? tb + 4 + slot : nch + (slot - nsq);
-                        act[u] = slot < nothers;
-                    }
+                for (int u = 0; u < RMAXT; ++u) {
+                    const int slot = (wv - 2) + u * OW + ps * OW * RMAXT;
+                    T[u] = slot < nsq ? tb + 4 + slot : nch + (slot - nsq);
+                    act[u] = slot < nothers;
                 }
                 // ---- (1) accT = -(S' tile) + sum_c L(Cc, c) L(T, c)' --------------------------------------
                 v4d acc[RMAXT][2];
@@ -792,7 +682,7 @@ struct OpsResidentT {
                         // the source tiles of the next block column's first pass: in flight while the stores above drain
                         int Tn[RMAXT];
                         bool an[RMAXT];
-                        first_rows(jb + 1, wv, lane, ntr, Tn, an);
+                        first_rows(jb + 1, wv, ntr, Tn, an);
                         if (an[0]) {
 #pragma unroll
                             for (int u = 0; u < RMAXT; ++u)
@@ -802,14 +692,6 @@ struct OpsResidentT {
                             have_pre = true;
                         }
                     }
-                    if (fwd) {
-                        if (ps == 0) lds_barrier();             // (A2) y_j published by wavefront 0
-#pragma unroll
-                        for (int u = 0; u < RMAXT; ++u)
-                            if (act[u] && T[u] < nch) fwd_update(x1[u], x2[u], T[u], j0, li, kq);
-                    }
-                } else if (fwd && ps == 0) {
-                    lds_barrier();                              // (A2)
                 }
             }
             __syncthreads();                                        // (B) block column visible to everyone
@@ -857,7 +739,8 @@ struct OpsResidentT {
     // shorter chain path returns, and the two-row look-ahead wavefronts are what the busiest SIMD carries either way.
     // Two barriers per 64 columns instead of six.  Every tile receives exactly the MFMA sequence it receives in factor()
     // (history chunks ascending, x then y half of every half-chunk, the same operand order), so the factor, U and the forward-
-    // substituted right-hand side are bit for bit those of the 32-column form (tools/dump_fit.py --cmp).
+    // substituted right-hand side are bit for bit those of the 32-column form (tools/dump_fit.py --cmp against the 32-column QP
+    // build, tools/experiments/qp_factor32_qp_variant.patch).
     // kFat: the four-wavefront form (one wavefront per SIMD, 512 registers each: 32 accumulator tiles in AccVGPRs).  Wavefront 0
     // is the chain + look-ahead of block b exactly as with eight wavefronts -- alone on its SIMD, so no row wavefront's MFMA
     // stream stretches the chains --, wavefront 1 carries tile rows tA+4, tA+5 (11 tiles) plus up to RM1 ordinary rows,
@@ -2255,7 +2138,7 @@ __global__ __launch_bounds__(RTT) void cov_kernel_resident(CovArgs a, int NP) {
     OpsResidentT<GU, RTT> ops;
     ops.L = a.L + (size_t)b * a.l_stride; ops.nch = NP / 16; ops.n = a.n;
     ops.Ppk = a.Ppk + (size_t)b * a.ppk_stride; ops.nchp = a.nchp;
-    ops.nex = a.nex; ops.Bex = a.Bex; ops.fwd = false;
+    ops.nex = a.nex; ops.Bex = a.Bex;
     constexpr int VEC = ResSmemT<GU, RTT>::VEC;
     ops.sm.carve(smem);
     // with U outside LDS it sits behind the (nch + nex) x nch tiles of this spectrum's scratch
@@ -2284,27 +2167,25 @@ __global__ __launch_bounds__(RTT) void cov_kernel_resident(CovArgs a, int NP) {
     }
 }
 
-// the QP kernel's factorisation: 64-column passes over the history (factor64) with eight wavefronts
-template <int RTT> static constexpr bool kQpPanel64 = (HIPDRT_QP_PANEL64 != 0) && RTT == 512;
-
+// The QP kernel: 64-column passes over the history (factor64), in both forms below.
 // (the second launch-bound argument is waves per SIMD: 2 in both forms, i.e. one 512-thread or two 256-thread workgroups per
 // CU and at most 256 registers per lane; without it hipcc gives the 256-thread form 393 registers and one workgroup per CU)
 // The FAT form (RTT = 256, WPS = 1, VT = 2): four wavefronts, one per SIMD, with the whole register file of their SIMD -- 256
 // architectural registers for operand rings and 256 accumulation registers (AccVGPRs: hipcc puts every MFMA result there once
 // a kernel may use more than 256 registers) = 32 accumulator tiles per wavefront.  The interior-point vectors run as two
 // virtual threads per thread (qp_common.hpp), so its results are bit for bit the eight-wavefront kernel's.
-template <bool GU, int RTT = 512, int WPS = 2, bool P64 = kQpPanel64<RTT>, int VT = 1>
+template <bool GU, int RTT = 512, int WPS = 2, int VT = 1>
 __global__ __launch_bounds__(RTT, WPS) void qp_kernel_resident(QpArgs a, int NP) {
     constexpr int RT = RTT;
     const int b = a.order ? a.order[blockIdx.x] : blockIdx.x;
     if (a.active && !a.active[b]) return;
     extern __shared__ double smem[];
-    OpsResidentT<GU, RTT, P64, VT> ops;
+    OpsResidentT<GU, RTT, true, VT> ops;
     ops.L = a.L + (size_t)b * a.l_stride; ops.nch = NP / 16; ops.n = a.n;
     ops.Ppk = a.Ppk ? a.Ppk + (size_t)b * a.ppk_stride : nullptr; ops.nchp = a.nchp;
     ops.sm.carve(smem);
     if (GU) ops.sm.U = resident_u_ptr<GU>(ops.L, NP);
-    ops.build_schedule();
+    ops.build_schedule64();
     // zero U (the upper-right quarter of every inverse block stays zero) and the padding of vec (read by the
     // updates of the last, partial block)
     for (int i = threadIdx.x; i < NP * PLD; i += RT) ops.sm.U[i] = 0.0;
@@ -2315,19 +2196,14 @@ __global__ __launch_bounds__(RTT, WPS) void qp_kernel_resident(QpArgs a, int NP)
     ipm_solve<RT, GU ? (2048 + VTH - 1) / VTH : (RNP_MAX + VTH - 1) / VTH, decltype(ops), VT>(a, b, ops, is);
 }
 
-// LDS bytes: everything for n <= 528, only the fixed part when U lives in global memory
-// (qp = the QP kernel's layout, which differs from the posterior-variance kernel's when it runs factor64)
-static size_t resident_lds_bytes(int NP, bool qp = false) {
-    return ((size_t)NP * PLD + (qp ? ResSmemT<false, 512, kQpPanel64<512>>::FIXED : ResSmem::FIXED)) * sizeof(double);
+// LDS bytes of the two kernels: everything for n <= 528, only the fixed part when U lives in global memory (GU)
+template <bool GU, int RTT = 512, int VT = 1>
+static size_t qp_resident_lds_bytes(int NP) {
+    return ((GU ? 0 : (size_t)NP * PLD) + ResSmemT<GU, RTT, true, VT>::FIXED) * sizeof(double);
 }
-// the fat four-wavefront form of the QP kernel
-static constexpr bool kFatPanel64 = true;
-using FatSmem = ResSmemT<false, 256, kFatPanel64, 2>;
-static size_t resident_fat_lds_bytes(int NP) { return ((size_t)NP * PLD + FatSmem::FIXED) * sizeof(double); }
-static_assert((FatSmem::FIXED + 544 * 33) * 8 <= 160 * 1024, "n = 514 must fit one CU's LDS (fat form)");
-template <int RTT = 512>
-static size_t resident_gu_lds_bytes(bool qp = false) {
-    return (size_t)(qp ? ResSmemT<true, RTT, kQpPanel64<RTT>>::FIXED : ResSmemT<true, RTT>::FIXED) * sizeof(double);
+template <bool GU>
+static size_t cov_lds_bytes(int NP) {
+    return ((GU ? 0 : (size_t)NP * PLD) + ResSmemT<GU, 512, false>::FIXED) * sizeof(double);
 }
 // per-problem scratch doubles of the U-outside form: the tile-packed factor (NP^2) followed by U (NP x 33)
 static size_t resident_gu_doubles(int n) {

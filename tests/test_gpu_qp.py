@@ -326,7 +326,7 @@ def test_group_launches_beside_a_batch_launch_that_fills_the_chip():
 @pytest.mark.parametrize("n", [1, 17, 33, 64, 65, 93, 123, 129, 257, 400, 497, 513, 514, 528])
 def test_fat_four_wavefront_kernel_same_bits(n):
     """The fat form of the batch coneqp kernel (four wavefronts, one per SIMD, 512 registers each: accumulators in AccVGPRs,
-    qp_kernel_resident<false, 256, 1, true, 2>; debug switch hipdrt_debug_qp_waves) against the eight-wavefront kernel: every
+    qp_kernel_resident<false, 256, 1, 2>; debug switch hipdrt_debug_qp_waves) against the eight-wavefront kernel: every
     tile receives the same MFMA sequence whoever owns it, the sweeps apply the blocks' contributions in the same order, and the
     interior-point reductions run over two VIRTUAL threads per thread -- the results are the same bits, the failure statuses too."""
     from hipdrt import _ffi

@@ -30,6 +30,15 @@ for k in ("x", "weights", "rho", "outer_iters", "qp_iters_total"):
     out["c2_" + k] = r[k]
 v = d.estimate_distribution_var_batch(c2["tau"][::4])
 out["c2_var"] = np.asarray(v[0] if isinstance(v, tuple) else v)
+# the same range on a finer tau grid: n > 528, the posterior variance with the inverse diagonal blocks in global memory (four
+# spectra: their QPs run on the group kernel)
+tf = np.geomspace(c2["tau"][0], c2["tau"][-1], 600)
+df = DRT(fixed_basis_tau=tf)
+rf = df.fit_eis_batch(c2["freq"], z[:4])
+for k in ("x", "outer_iters", "qp_iters_total"):
+    out["fine_" + k] = rf[k]
+v = df.estimate_distribution_var_batch(tf[::4])
+out["fine_var"] = np.asarray(v[0] if isinstance(v, tuple) else v)
 c1 = synth.config_c1()
 z1 = synth.zarc2_batch(c1["freq"], 16)
 r1 = DRT(fixed_basis_tau=c1["tau"]).fit_eis_batch(c1["freq"], z1)
