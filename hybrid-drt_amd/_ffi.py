@@ -67,6 +67,20 @@ class IterateState(C.Structure):
 
 _vp = C.c_void_p
 
+
+class DebugGramArgs(C.Structure):
+    """hipdrt_debug_gram_args (include/hipdrt_debug.h)"""
+    _fields_ = [
+        ("B", C.c_int), ("m", C.c_int), ("n", C.c_int), ("A", _dp), ("a_batched", C.c_int), ("lda", C.c_int),
+        ("w", _dp), ("y", _dp), ("l1", _dp), ("l1_scalar", C.c_double),
+        ("l2", _dp), ("l2_batched", C.c_int), ("ldl2", C.c_int),
+        ("mk", _dp * 3), ("ldm", C.c_int), ("s", _dp), ("rho", _dp), ("dfac", C.c_double * 3),
+        ("ns", C.c_int), ("sym", C.c_int), ("toep", C.c_int), ("toep_maxd", C.c_int), ("spec_zero", C.c_int),
+        ("dop_start", C.c_int), ("dop_size", C.c_int), ("dop_rho", _dp), ("dop_dfac", C.c_double * 3),
+        ("active", _ip), ("P", _dp), ("ldp", C.c_int), ("Ppk", _dp), ("q", _dp),
+    ]
+
+
 # name -> argtypes (all return int unless listed in _RESTYPES).  Mirrors include/hipdrt.h one-to-one;
 # tests/test_cabi_symbols.py checks the header and this table against the built library.
 SIGNATURES = {
@@ -101,6 +115,8 @@ SIGNATURES = {
     "hipdrt_debug_exact_zero_shortcuts": [_vp, C.c_int],
     "hipdrt_debug_qp_waves": [_vp, C.c_int],
     "hipdrt_debug_stream_pool": [_vp, C.c_int, C.POINTER(C.c_void_p), _ip, _ip, _ip],
+    "hipdrt_debug_gram_l2": [_vp, C.POINTER(DebugGramArgs)],
+    "hipdrt_debug_pack_p": [_vp, C.c_int, C.c_int, _dp, C.c_int, _dp],
     "hipdrt_comm_unique_id": [C.c_char_p],
     "hipdrt_comm_create": [C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(_vp)],
     "hipdrt_comm_destroy": [_vp],
@@ -472,6 +488,94 @@ class Context:
         """tests: with on = False this context's fits visit the penalty matrices' exact zeros as well (same bits, slower)
         (hipdrt_debug_exact_zero_shortcuts, include/hipdrt_debug.h)"""
         _check(self._lib.hipdrt_debug_exact_zero_shortcuts(self._h, int(bool(on))))
+
+    def debug_gram_l2(self, A, w, y=None, l1=None, l1_scalar=0.0, l2=None, mk=None, s=None, rho=None, dfac=(0.0, 0.0, 0.0),
+                      ns=0, sym=False, toep=False, toep_maxd=-1, spec_zero=False, dop_start=0, dop_size=0, dop_rho=None,
+                      dop_dfac=(0.0, 0.0, 0.0), active=None, n=None, P=None, Ppk=None, q=None):
+        """tests: the fit loop's Gram / q launchers on host arrays (hipdrt_debug_gram_l2, include/hipdrt_debug.h).
+        A [m][lda] (shared) or [B][m][lda], w [B][m], y [B][m] or None (no q); `n` = the number of unknowns when A's rows are
+        padded (lda = A.shape[-1] > n).  Either l2 ([n][ldl2] or [B][n][ldl2]) or the hyper-parameter form mk (three [n][ldm]
+        matrices) + s [B][3][n] (+ rho [B][3]); see GramL2 in csrc/common.hpp for the rest.  P [B][n][ldp], Ppk [B][nchp^2 * 256]
+        and q [B][n] are float64 C-contiguous arrays the CALLER fills beforehand (poison): they are uploaded, the kernels
+        run, and they are overwritten in place with what the device holds afterwards.  P=None runs the kernel form without the
+        row-major copy.  Returns (P, Ppk, q)."""
+        A, w = _f64(A), _f64(w)
+        B, m = w.shape
+        a = DebugGramArgs()
+        a.B, a.m, a.lda = B, m, A.shape[-1]
+        a.n = n = A.shape[-1] if n is None else int(n)
+        a.a_batched = int(A.ndim == 3)
+        if A.shape[-2] != m or (A.ndim == 3 and A.shape[0] != B):
+            raise ValueError("A does not match w")
+        keep = [A, w]
+
+        def arr(v, shape, what):
+            if v is None:
+                return None
+            v = _f64(v)
+            if v.shape != tuple(shape):
+                raise ValueError(f"{what}: shape {v.shape}, expected {tuple(shape)}")
+            keep.append(v)
+            return _p(v)
+
+        def out(v, shape, what):
+            if v is None:
+                return None
+            if not (isinstance(v, np.ndarray) and v.dtype == np.float64 and v.flags.c_contiguous and v.flags.writeable):
+                raise ValueError(f"{what}: a writeable C-contiguous float64 array")
+            if v.shape != tuple(shape):
+                raise ValueError(f"{what}: shape {v.shape}, expected {tuple(shape)}")
+            return _p(v)
+
+        a.A, a.w = _p(A), _p(w)
+        a.y = arr(y, (B, m), "y")
+        a.l1 = arr(l1, (n,), "l1")
+        a.l1_scalar = float(l1_scalar)
+        if s is not None:
+            if mk is None or len(mk) != 3 or l2 is not None:
+                raise ValueError("hyper-parameter form: three penalty matrices and no explicit l2")
+            mk = [_f64(v) for v in mk]
+            a.ldm = mk[0].shape[-1]
+            for k in range(3):
+                a.mk[k] = arr(mk[k], (n, a.ldm), "mk")
+            a.s = arr(s, (B, 3, n), "s")
+            a.rho = arr(rho, (B, 3), "rho")
+            a.dop_rho = arr(dop_rho, (B, 3), "dop_rho")
+        elif l2 is not None:
+            l2 = _f64(l2)
+            a.l2_batched, a.ldl2 = int(l2.ndim == 3), l2.shape[-1]
+            a.l2 = arr(l2, ((B, n, a.ldl2) if l2.ndim == 3 else (n, a.ldl2)), "l2")
+        for k in range(3):
+            a.dfac[k], a.dop_dfac[k] = float(dfac[k]), float(dop_dfac[k])
+        a.ns, a.sym, a.toep, a.toep_maxd, a.spec_zero = int(ns), int(bool(sym)), int(bool(toep)), int(toep_maxd), int(bool(spec_zero))
+        a.dop_start, a.dop_size = int(dop_start), int(dop_size)
+        if active is not None:
+            active = np.ascontiguousarray(active, dtype=np.int32)
+            if active.shape != (B,):
+                raise ValueError("active: one flag per spectrum")
+            keep.append(active)
+            a.active = _pi(active)
+        if P is not None:
+            a.ldp = P.shape[-1]
+            a.P = out(P, (B, n, a.ldp), "P")
+        nchp = (n + 31) // 32 * 2
+        a.Ppk = out(Ppk, (B, nchp * nchp * 256), "Ppk")
+        a.q = out(q, (B, n), "q")
+        _check(self._lib.hipdrt_debug_gram_l2(self._h, C.byref(a)))
+        return P, Ppk, q
+
+    def debug_pack_p(self, P, n=None):
+        """tests: launch_pack_p on row-major symmetric P [B][n][ldp] -> Ppk [B][nchp^2 * 256]; slots the kernel does not write
+        come back as NaN (hipdrt_debug_pack_p, include/hipdrt_debug.h)"""
+        P = _f64(P)
+        B, rows, ldp = P.shape
+        n = rows if n is None else int(n)
+        if rows != n:
+            raise ValueError("P: [B][n][ldp]")
+        nchp = (n + 31) // 32 * 2
+        Ppk = np.full((B, nchp * nchp * 256), np.nan)
+        _check(self._lib.hipdrt_debug_pack_p(self._h, B, n, _p(P), ldp, _p(Ppk)))
+        return Ppk
 
     def qp_profile(self, reset=True):
         buf = (C.c_ulonglong * 64)()        # 0..47 the QP kernel's phases, 48..63 hyper_kernel's (PROFILE=1 builds)

@@ -809,6 +809,91 @@ int hipdrt_weighted_gram(hipdrt_ctx* ctx, int B, int m, int n, const double* A, 
     return HIPDRT_OK;
 } HIPDRT_CATCH
 
+// test hook (include/hipdrt_debug.h): launch_gram_l2 / launch_qvec exactly as the fit loop calls them, on host arrays.  Every
+// extent a kernel derives an address from is checked here: the kernels themselves trust their caller.
+int hipdrt_debug_gram_l2(hipdrt_ctx* ctx, const hipdrt_debug_gram_args* a) try {
+    HIPDRT_REQUIRE(ctx && a && a->A && a->w, "NULL pointer");
+    const int B = a->B, m = a->m, n = a->n;
+    HIPDRT_REQUIRE(B >= 1 && B <= 4096 && m >= 1 && m <= 8192 && n >= 1 && n <= 4096, "1 <= B <= 4096, 1 <= m <= 8192, 1 <= n <= 4096");
+    HIPDRT_REQUIRE(a->lda >= n, "lda >= n");
+    HIPDRT_REQUIRE(a->P || a->Ppk, "at least one of P / Ppk");
+    HIPDRT_REQUIRE(!a->P || a->ldp >= n, "ldp >= n");
+    HIPDRT_REQUIRE(!a->y || a->q, "y without q");
+    const bool hyper = a->s != nullptr;
+    if (hyper) {
+        HIPDRT_REQUIRE(a->mk[0] && a->mk[1] && a->mk[2], "hyper-parameter form: three penalty matrices");
+        HIPDRT_REQUIRE(a->ldm >= n, "ldm >= n");
+        HIPDRT_REQUIRE(a->ns >= 0 && a->ns <= n, "0 <= ns <= n");
+        HIPDRT_REQUIRE(a->dop_size >= 0 && (a->dop_size == 0 || (a->dop_start >= 0 && a->dop_start + a->dop_size <= a->ns)),
+                       "x_dop block outside the special block [0, ns)");
+        HIPDRT_REQUIRE(a->dop_size == 0 || !a->rho || a->dop_rho, "dop_rho missing");
+        HIPDRT_REQUIRE(a->toep_maxd >= -1 && a->toep_maxd < n, "-1 <= toep_maxd < n");
+        HIPDRT_REQUIRE(!a->toep || n - a->ns >= 1, "Toeplitz form needs a DRT block (n - ns >= 1)");
+    } else if (a->l2) {
+        HIPDRT_REQUIRE(a->ldl2 >= n, "ldl2 >= n");
+    }
+    HIPDRT_CHECK(hipSetDevice(ctx->device)); (void)hipGetLastError();
+    hipStream_t st = ctx->stream;
+    const size_t D = sizeof(double);
+    const int nchp = qp_nchp(n);
+    const size_t ppk = qp_ppk_doubles(n);
+    DevBuf dA, dw, dy, dl1, dl2, dmk[3], ds, drho, ddrho, dact, dP, dPpk, dq;
+    TRY(upload(dA, a->A, (size_t)(a->a_batched ? B : 1) * m * a->lda * D, st));
+    TRY(upload(dw, a->w, (size_t)B * m * D, st));
+    if (a->y) TRY(upload(dy, a->y, (size_t)B * m * D, st));
+    if (a->l1) TRY(upload(dl1, a->l1, (size_t)n * D, st));
+    if (a->active) TRY(upload(dact, a->active, (size_t)B * sizeof(int), st));
+    GramL2 g{};
+    if (hyper) {
+        for (int k = 0; k < 3; ++k) {
+            TRY(upload(dmk[k], a->mk[k], (size_t)n * a->ldm * D, st));
+            g.mk[k] = dmk[k].d(); g.dfac[k] = a->dfac[k]; g.dop_dfac[k] = a->dop_dfac[k];
+        }
+        TRY(upload(ds, a->s, (size_t)B * 3 * n * D, st));
+        if (a->rho) TRY(upload(drho, a->rho, (size_t)B * 3 * D, st));
+        if (a->rho && a->dop_size > 0) TRY(upload(ddrho, a->dop_rho, (size_t)B * 3 * D, st));
+        g.ldm = a->ldm; g.s = ds.d(); g.rho = a->rho ? drho.d() : nullptr; g.use_rho = a->rho ? 1 : 0;
+        g.ns = a->ns; g.sym = a->sym ? 1 : 0; g.toep = a->toep ? 1 : 0; g.toep_maxd = a->toep_maxd; g.spec_zero = a->spec_zero ? 1 : 0;
+        g.dop_start = a->dop_start; g.dop_size = a->dop_size; g.dop_rho = ddrho.d();
+    } else if (a->l2) {
+        TRY(upload(dl2, a->l2, (size_t)(a->l2_batched ? B : 1) * n * a->ldl2 * D, st));
+        g.l2 = dl2.d(); g.l2_stride = a->l2_batched ? (long long)n * a->ldl2 : 0; g.ldl2 = a->ldl2;
+    }
+    if (a->P) TRY(upload(dP, a->P, (size_t)B * n * a->ldp * D, st));
+    if (a->Ppk) TRY(upload(dPpk, a->Ppk, (size_t)B * ppk * D, st));
+    if (a->y) TRY(upload(dq, a->q, (size_t)B * n * D, st));
+    const long long astr = a->a_batched ? (long long)m * a->lda : 0;
+    launch_gram_l2(st, B, m, n, dA.d(), a->lda, dw.d(), g, a->P ? dP.d() : nullptr, a->ldp, (long long)n * a->ldp,
+                   a->active ? dact.i() : nullptr, a->Ppk ? dPpk.d() : nullptr, (long long)ppk, nchp, astr);
+    LAUNCH_OK();
+    if (a->y) {
+        launch_qvec(st, B, m, n, dA.d(), a->lda, dw.d(), dy.d(), a->l1 ? dl1.d() : nullptr, a->l1_scalar, dq.d(),
+                    a->active ? dact.i() : nullptr, astr);
+        LAUNCH_OK();
+    }
+    if (a->P) HIPDRT_CHECK(hipMemcpyAsync(a->P, dP.p, (size_t)B * n * a->ldp * D, hipMemcpyDeviceToHost, st));
+    if (a->Ppk) HIPDRT_CHECK(hipMemcpyAsync(a->Ppk, dPpk.p, (size_t)B * ppk * D, hipMemcpyDeviceToHost, st));
+    if (a->y) HIPDRT_CHECK(hipMemcpyAsync(a->q, dq.p, (size_t)B * n * D, hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+int hipdrt_debug_pack_p(hipdrt_ctx* ctx, int B, int n, const double* P, int ldp, double* Ppk) try {
+    HIPDRT_REQUIRE(ctx && P && Ppk, "NULL pointer");
+    HIPDRT_REQUIRE(B >= 1 && B <= 4096 && n >= 1 && n <= 4096 && ldp >= n, "1 <= B <= 4096, 1 <= n <= 4096, ldp >= n");
+    HIPDRT_CHECK(hipSetDevice(ctx->device)); (void)hipGetLastError();
+    hipStream_t st = ctx->stream;
+    const size_t ppk = qp_ppk_doubles(n);
+    DevBuf dP, dPpk;
+    TRY(upload(dP, P, (size_t)B * n * ldp * sizeof(double), st));
+    TRY(upload(dPpk, Ppk, (size_t)B * ppk * sizeof(double), st));
+    launch_pack_p(st, B, n, dP.d(), ldp, (long long)n * ldp, dPpk.d(), (long long)ppk, qp_nchp(n));
+    LAUNCH_OK();
+    HIPDRT_CHECK(hipMemcpyAsync(Ppk, dPpk.p, (size_t)B * ppk * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
 // ---- plan ---------------------------------------------------------------------------------------------------
 
 void hipdrt_default_fit_opts(hipdrt_fit_opts* o) {

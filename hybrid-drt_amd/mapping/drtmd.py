@@ -69,6 +69,12 @@ def drt_siblings(drt, count):
         c = copy.copy(drt)                     # configuration only: the arrays it refers to are read-only
         c._plan = c._plan_key = c._last_batch = None
         c._context = _ffi.Context(drt.device)
+        # a sibling made while the parent's coneqp kernel choice is switched (_one_kernel: a reproducible map in flight) fits
+        # under the same choice
+        held = getattr(getattr(drt, '_context', None), '_qp_group_override', -1)
+        if held != -1:
+            c._context.debug_qp_group(held)
+            c._context._qp_group_override = held
         c._sibling_clones = None
         clones.append(c)
     drt._sibling_clones = clones
@@ -589,12 +595,16 @@ def _unpack_block(block):
 
 def _one_kernel(drt, members, saved=None):
     """pin (members = 0: one workgroup per problem, the batch kernel) the coneqp kernel choice of `drt` and its sibling clones,
-    or give back what each context held before (``saved`` = the list a pinning call returned).  Only plans made under ANOTHER
-    choice are dropped (their scratch layout follows the kernel); the contexts are the instances' own -- an instance on the
-    process-wide default context gets a private one first, so that no other DRT object or thread sees the switch."""
+    or give back what each context held before (``saved`` = what a pinning call returned: (context, its choice before) pairs,
+    the caller's own first).  Siblings that did not exist when the choice was pinned were made under it (drt_siblings hands it
+    on): they go back to what the caller's own context held, which is what they would have started from.  Only plans made
+    under ANOTHER choice are dropped (their scratch layout follows the kernel); the contexts are the instances' own -- an
+    instance on the process-wide default context gets a private one first, so that no other DRT object or thread sees the
+    switch."""
     from .. import _ffi
+    before_of = {} if saved is None else {id(ctx): before for ctx, before in saved}
     held = []
-    for k, d in enumerate([drt] + list(getattr(drt, '_sibling_clones', None) or [])):
+    for d in [drt] + list(getattr(drt, '_sibling_clones', None) or []):
         if d._context is None:                       # never switch the shared default context under other users' feet
             d._context = _ffi.Context(d.device)
             if getattr(d, '_plan', None) is not None:
@@ -602,8 +612,8 @@ def _one_kernel(drt, members, saved=None):
                 d._plan = d._plan_key = None
         ctx = d._context
         before = getattr(ctx, '_qp_group_override', -1)
-        want = members if saved is None else saved[k]
-        held.append(before)
+        want = members if saved is None else before_of.get(id(ctx), saved[0][1])
+        held.append((ctx, before))
         if want != before:
             ctx.debug_qp_group(want)
             ctx._qp_group_override = want

@@ -40,6 +40,43 @@ int hipdrt_debug_exact_zero_shortcuts(hipdrt_ctx* ctx, int on);
  * the number of device loops running on it right now.  Any of the three arrays may be NULL.                               */
 int hipdrt_debug_stream_pool(hipdrt_ctx* ctx, int cap, void** streams, int* holders, int* running, int* size);
 
+/* test hook (tests/test_gpu_gram.py): the fit loop's Gram and q launchers on host arrays, in every form the loop, the posterior
+ * entry points and the stand-alone API run them -- P_b = (W_b A_b)'(W_b A_b) + L2_b and q_b = -(W_b A_b)'(W_b y_b) + l1 (csrc/gram.hip).
+ * All arrays are host memory, row-major; a NULL pointer means "absent".                                                     */
+typedef struct hipdrt_debug_gram_args {
+    int B, m, n;
+    const double* A;        /* [a_batched ? B : 1][m][lda], lda >= n                                                    */
+    int a_batched, lda;
+    const double* w;        /* [B][m]                                                                                   */
+    const double* y;        /* [B][m] or NULL: no q                                                                     */
+    const double* l1;       /* [n] or NULL: l1_scalar                                                                   */
+    double l1_scalar;
+    /* explicit L2 (used when s is NULL; may be NULL as well: no L2 term) ...                                           */
+    const double* l2;       /* [l2_batched ? B : 1][n][ldl2], ldl2 >= n                                                 */
+    int l2_batched, ldl2;
+    /* ... or the hyper-parameter form, selected by s != NULL (fields as GramL2, csrc/common.hpp)                       */
+    const double* mk[3];    /* each [n][ldm], ldm >= n                                                                  */
+    int ldm;
+    const double* s;        /* [B][3][n]                                                                                */
+    const double* rho;      /* [B][3] or NULL: use_rho = 0 (dop_rho is then not used either)                            */
+    double dfac[3];
+    int ns, sym, toep, toep_maxd, spec_zero;
+    int dop_start, dop_size;       /* dop_size > 0: the block lies inside [0, ns)                                       */
+    const double* dop_rho;  /* [B][3], required when dop_size > 0 and rho is given                                      */
+    double dop_dfac[3];
+    const int* active;      /* [B] or NULL                                                                              */
+    /* in/out: the host contents are uploaded first, so what comes back differs from them only where a kernel wrote     */
+    double* P;              /* [B][n][ldp], ldp >= n, or NULL: the kernel form without the row-major copy               */
+    int ldp;
+    double* Ppk;            /* [B][nchp * nchp * 256] with nchp = round_up(n, 32) / 16, or NULL                         */
+    double* q;              /* [B][n] (with y)                                                                          */
+} hipdrt_debug_gram_args;
+/* uploads, calls launch_gram_l2 and (with y) launch_qvec as they are, downloads.  Refuses every combination that could make a
+ * kernel read or write out of bounds.                                                                                   */
+int hipdrt_debug_gram_l2(hipdrt_ctx* ctx, const hipdrt_debug_gram_args* a);
+/* test hook: launch_pack_p -- row-major symmetric P [B][n][ldp] (host) -> Ppk [B][nchp * nchp * 256] (host, in/out as above) */
+int hipdrt_debug_pack_p(hipdrt_ctx* ctx, int B, int n, const double* P, int ldp, double* Ppk);
+
 #ifdef __cplusplus
 }
 #endif

@@ -392,6 +392,34 @@ def test_reproducible_map_is_bit_identical_however_it_is_sharded():
     parity_close("reproducible_map.group_vs_batch_kernel", lx, whole[0], 2e-9)      # measured 1.1e-10 (a fit of 27 outer iterations, two kernels)
 
 
+def test_reproducible_map_is_bit_identical_with_two_batches_in_flight_on_a_fresh_drt():
+    """fit_observations_sharded(reproducible=True, inflight=2) on a DRT that has no sibling yet: the sibling is made inside the
+    call, after the kernel choice was pinned -- it has to fit its twelve spectra (which alone would take the several-workgroups
+    kernel) under the same choice, and the map has the bits of the inflight=1 map.  Afterwards every context involved is back at
+    the library's choice: the Python-side record says so, and a small share fitted on either of them takes the other kernel again."""
+    from hipdrt import synth
+    from hipdrt.mapping import fit_observations, fit_observations_sharded
+    from hipdrt.models import DRT
+    c2 = synth.config_c2()
+    z = synth.zarc2_batch(c2["freq"], 24, first_seed=700)
+    whole = fit_observations_sharded(DRT(fixed_basis_tau=c2["tau"]), c2["freq"], z, rank=0, world=1, reproducible=True)
+    drt = DRT(fixed_basis_tau=c2["tau"])
+    assert not getattr(drt, "_sibling_clones", None)
+    two = fit_observations_sharded(drt, c2["freq"], z, rank=0, world=1, reproducible=True, inflight=2)
+    np.testing.assert_array_equal(two[0], whole[0])
+    for key in ("R_inf", "inductance"):
+        np.testing.assert_array_equal(two[1][key], whole[1][key])
+    for key in ("outer_iters", "qp_iters_total", "obs_llh", "obs_rss"):
+        np.testing.assert_array_equal(two[2][key], whole[2][key])
+    sibs = [drt] + list(drt._sibling_clones)
+    assert len(sibs) == 2 and sibs[1]._context is not None and sibs[1]._context is not drt._context
+    assert [getattr(d._context, "_qp_group_override", -1) for d in sibs] == [-1, -1]
+    fresh = fit_observations(DRT(fixed_basis_tau=c2["tau"]), c2["freq"], z[:8])       # never pinned: the several-workgroups kernel
+    assert not np.array_equal(fresh[0], whole[0][:8])                           # (rounding apart from the pinned map)
+    for d in sibs:
+        np.testing.assert_array_equal(fit_observations(d, c2["freq"], z[:8])[0], fresh[0])
+
+
 def test_store_fit_all_resumes_where_it_stopped_and_matches_the_reference_map():
     """mapping.DRTMD (observation store, drtmd.py:186-329): ten observations of the reference's 16-observation map are added and
     fitted, six more are added, fit_all(refit=False) sends exactly those six to the device (drtmd.py:321-329) -- and the store

@@ -143,3 +143,65 @@ def test_a_map_larger_than_one_batch_is_fitted_in_consecutive_batches():
     np.testing.assert_array_equal(res["obs_llh"], ref["obs_llh"])
     assert len(res["obs_fit_errors"]) == 25 and res["obs_fit_status"].all()
     assert drtmd.max_batch_for(fake, freq) is None
+
+
+class _FakeContext:
+    """stands in for _ffi.Context: remembers the coneqp kernel choice it was given, as the real one does"""
+    made = []
+
+    def __init__(self, device=0):
+        self.device = device
+        self.calls = []
+        _FakeContext.made.append(self)
+
+    def debug_qp_group(self, members):
+        self.calls.append(int(members))
+        self._qp_group_override = int(members)
+
+
+class _FakeDeviceDRT(_FakeDRT):
+    """a _FakeDRT with what _one_kernel and drt_siblings touch; its fits record the kernel choice they ran under"""
+    device = 0
+    tau_epsilon = None
+    integrate_method = 'interp'
+
+    def __init__(self):
+        super().__init__()
+        self._context = self._plan = self._plan_key = None
+        self.under = []
+
+    def fit_eis_batch(self, frequencies, z, **kw):
+        self.under.append(getattr(self._context, '_qp_group_override', -1))
+        return super().fit_eis_batch(frequencies, z, **kw)
+
+
+@pytest.mark.parametrize("parent_choice", [-1, 3])
+def test_reproducible_map_pins_and_restores_siblings_made_during_the_fit(monkeypatch, parent_choice):
+    """fit_observations_sharded(reproducible=True, inflight=2) on a DRT that has no siblings yet: the sibling made inside the call
+    fits under the pinned kernel choice as well, and giving the choices back afterwards does not trip over it (it used to raise
+    IndexError: the saved list was indexed by position and had one entry); a second call, siblings in place, leaves the same state"""
+    from hipdrt import _ffi
+    from hipdrt.mapping import drtmd
+    monkeypatch.setattr(_ffi, "Context", _FakeContext)
+    _FakeContext.made = []
+    drt = _FakeDeviceDRT()
+    if parent_choice != -1:                       # the caller switched its own context before (a test, a tool)
+        drt._context = _FakeContext(0)
+        drt._context.debug_qp_group(parent_choice)
+    freq, z = np.logspace(3, 0, 9), _data(24)
+    one = drtmd.fit_observations_sharded(_FakeDeviceDRT(), freq, z, rank=0, world=1, reproducible=True, fit=drtmd.fit_observations)
+    for _ in range(2):
+        two = drtmd.fit_observations_sharded(drt, freq, z, rank=0, world=1, reproducible=True, inflight=2, fit=drtmd.fit_observations)
+        np.testing.assert_array_equal(two[0], one[0])
+        sibs = [drt] + list(drt._sibling_clones)
+        assert len(sibs) == 2 and sibs[1]._context is not drt._context
+        assert [d.under[-1] for d in sibs] == [0, 0]                            # both chunks ran on the pinned kernel
+        assert [getattr(d._context, '_qp_group_override', -1) for d in sibs] == [parent_choice] * 2     # and both are back
+    # three in flight next: one sibling known to the pin, one made under it
+    drtmd.fit_observations_sharded(drt, freq, z, rank=0, world=1, reproducible=True, inflight=3, fit=drtmd.fit_observations)
+    sibs = [drt] + list(drt._sibling_clones)
+    assert len(sibs) == 3 and [d.under[-1] for d in sibs] == [0, 0, 0]
+    assert [getattr(d._context, '_qp_group_override', -1) for d in sibs] == [parent_choice] * 3
+    # a sibling made outside a reproducible map starts from the library's choice unless the parent holds one
+    drtmd.drt_siblings(drt, 4)
+    assert getattr(drt._sibling_clones[2]._context, '_qp_group_override', -1) == parent_choice
