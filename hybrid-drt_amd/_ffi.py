@@ -68,6 +68,13 @@ class IterateState(C.Structure):
 _vp = C.c_void_p
 
 
+class KkOpts(C.Structure):
+    """hipdrt_kk_opts (include/hipdrt.h)"""
+    _fields_ = [("n_outlier_iter", C.c_int), ("p_thresh", C.c_double), ("n_sigma", C.c_double),
+                ("std_sample_fraction", C.c_double), ("n_std", C.c_double), ("max_num_outliers", C.c_int),
+                ("outlier_weight", C.c_double)]
+
+
 class DebugGramArgs(C.Structure):
     """hipdrt_debug_gram_args (include/hipdrt_debug.h)"""
     _fields_ = [
@@ -117,6 +124,9 @@ SIGNATURES = {
     "hipdrt_debug_stream_pool": [_vp, C.c_int, C.POINTER(C.c_void_p), _ip, _ip, _ip],
     "hipdrt_debug_gram_l2": [_vp, C.POINTER(DebugGramArgs)],
     "hipdrt_debug_pack_p": [_vp, C.c_int, C.c_int, _dp, C.c_int, _dp],
+    "hipdrt_debug_kk_stats": [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(KkOpts), _dp, _ip, _dp, _ip, _ip],
+    "hipdrt_default_kk_opts": [C.POINTER(KkOpts)],
+    "hipdrt_plan_kk_screen": [_vp, C.POINTER(KkOpts), C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _ip, _ip],
     "hipdrt_comm_unique_id": [C.c_char_p],
     "hipdrt_comm_create": [C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(_vp)],
     "hipdrt_comm_destroy": [_vp],
@@ -167,7 +177,8 @@ SIGNATURES = {
                              C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.POINTER(FitOpts), _dp, _dp, _dp, _dp,
                              _dp, _dp, _dp, _dp, _ip, _ip],
 }
-_RESTYPES = {"hipdrt_last_error": C.c_char_p, "hipdrt_stream": C.c_void_p, "hipdrt_default_fit_opts": None}
+_RESTYPES = {"hipdrt_last_error": C.c_char_p, "hipdrt_stream": C.c_void_p, "hipdrt_default_fit_opts": None,
+             "hipdrt_default_kk_opts": None}
 
 _lib = None
 _lock = threading.Lock()
@@ -233,6 +244,28 @@ def default_fit_opts() -> FitOpts:
     o = FitOpts()
     load_library().hipdrt_default_fit_opts(C.byref(o))
     return o
+
+
+def kk_opts(n_outlier_iter=2, p_thresh=1e-4, n_sigma=None, std_sample_fraction=0.6, n_std=None, max_num_outliers=2,
+            outlier_weight=1e-10) -> KkOpts:
+    """hipdrt_kk_opts from the keywords of DRT.kk_test (None <-> -1 for n_sigma); n_std=None: the library's default for a
+    std_sample_fraction of 0.6, otherwise the caller supplies the quantile that goes with its fraction"""
+    o = KkOpts()
+    load_library().hipdrt_default_kk_opts(C.byref(o))
+    o.n_outlier_iter, o.p_thresh = int(n_outlier_iter), float(p_thresh)
+    o.n_sigma = -1.0 if n_sigma is None else float(n_sigma)
+    if n_std is None and float(std_sample_fraction) != o.std_sample_fraction:
+        raise ValueError("n_std must be given with a std_sample_fraction other than the default")
+    o.std_sample_fraction = float(std_sample_fraction)
+    if n_std is not None:
+        o.n_std = float(n_std)
+    o.max_num_outliers, o.outlier_weight = int(max_num_outliers), float(outlier_weight)
+    return o
+
+
+def _kk_outputs(B, nf):
+    return dict(std=np.empty(B), outlier_mask=np.empty((B, nf), dtype=np.int32), f_lim=np.empty((B, 2)),
+                i_lim=np.empty((B, 2), dtype=np.int32), status=np.empty(B, dtype=np.int32))
 
 
 class Context:
@@ -564,6 +597,21 @@ class Context:
         _check(self._lib.hipdrt_debug_gram_l2(self._h, C.byref(a)))
         return P, Ppk, q
 
+    def debug_kk_stats(self, freq, err, opts: KkOpts | None = None):
+        """tests: the statistics stage of the KK screen kernel on host residuals err (B, nf) complex
+        (hipdrt_debug_kk_stats, include/hipdrt_debug.h) -> dict(std, outlier_mask, f_lim, i_lim, status)"""
+        freq = _f64(freq)
+        err = np.atleast_2d(np.asarray(err, dtype=complex))
+        if err.shape[1] != freq.size:
+            raise ValueError("err must have shape (B, len(freq))")
+        e_re, e_im = _f64(err.real), _f64(err.imag)
+        out = _kk_outputs(err.shape[0], freq.size)
+        _check(self._lib.hipdrt_debug_kk_stats(self._h, err.shape[0], freq.size, _p(freq), _p(e_re), _p(e_im),
+                                               C.byref(opts) if opts is not None else None, _p(out["std"]),
+                                               _pi(out["outlier_mask"]), _p(out["f_lim"]), _pi(out["i_lim"]),
+                                               _pi(out["status"])))
+        return out
+
     def debug_pack_p(self, P, n=None):
         """tests: launch_pack_p on row-major symmetric P [B][n][ldp] -> Ppk [B][nchp^2 * 256]; slots the kernel does not write
         come back as NaN (hipdrt_debug_pack_p, include/hipdrt_debug.h)"""
@@ -664,7 +712,8 @@ class Plan:
                   "a_im": (self.nf, self.ntau), "rm": (self.m, self.n), "m0": (self.n, self.n),
                   "m1": (self.n, self.n), "m2": (self.n, self.n), "vmm": (self.m, self.m), "h": (self.n,),
                   "est_weights": (self.batch, self.m), "rv": (self.batch, self.m), "xmx": (self.batch, 3),
-                  "outlier_t": (self.batch, self.m)}
+                  "outlier_t": (self.batch, self.m), "row_factors": (self.batch, self.m), "x": (self.batch, self.n),
+                  "coef_scale": (self.batch,)}
         out = np.empty(shapes[which])
         _check(self._lib.hipdrt_plan_get(self._h, which.encode(), _p(out), out.size))
         return out
@@ -726,6 +775,25 @@ class Plan:
             rf = _f64(np.vstack([rf, np.ones((self.capacity - rf.shape[0], rf.shape[1]))]))
         _check(self._lib.hipdrt_plan_set_weight_factors(self._h, float(weight_factor), _p(rf),
                                                         int(rf is not None and rf.ndim == 2) | (2 if late else 0)))
+
+    def kk_screen(self, opts: KkOpts | None = None, set_row_factors=False, z_hat=True, residuals=True):
+        """hipdrt_plan_kk_screen: prediction at the fit frequencies, residuals in percent of |Z|, outlier mask and clean window
+        of every spectrum of the fitted batch, on the device.  Returns dict(z_hat (B, nf) complex, residuals (B, nf) complex,
+        std (B,), outlier_mask (B, nf) int32, f_lim (B, 2) = f_min, f_max, i_lim (B, 2), status (B,)); z_hat / residuals are
+        left out on request.  set_row_factors: the next fit's row factors (outlier_weight on the rows of masked frequencies)
+        are written on the device and the plan is left as set_weight_factors(1.0, rows, late=True) would leave it."""
+        B, nf = self.B, self.nf
+        out = _kk_outputs(B, nf)
+        zr, zi = (np.empty((B, nf)), np.empty((B, nf))) if z_hat else (None, None)
+        er, ei = (np.empty((B, nf)), np.empty((B, nf))) if residuals else (None, None)
+        _check(self._lib.hipdrt_plan_kk_screen(self._h, C.byref(opts) if opts is not None else None, int(bool(set_row_factors)),
+                                               _p(zr), _p(zi), _p(er), _p(ei), _p(out["std"]), _pi(out["outlier_mask"]),
+                                               _p(out["f_lim"]), _pi(out["i_lim"]), _pi(out["status"])))
+        if z_hat:
+            out["z_hat"] = zr + 1j * zi
+        if residuals:
+            out["residuals"] = er + 1j * ei
+        return out
 
     def set_init_h(self, h_init):
         h = None if h_init is None else _f64(h_init)

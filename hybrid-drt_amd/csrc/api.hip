@@ -27,6 +27,7 @@ struct hipdrt_plan {
     hipdrt_ctx* ctx = nullptr;
     int nf = 0, ntau = 0, n = 0, m = 0, ns = 0, ngrid = 0, ny = 0, mode = 0, toeplitz_a = 0, toeplitz_m = 0;
     int idx_rinf = -1, idx_induc = -1;
+    int freq_order = 0;        // +1: the frequency grid is strictly descending, -1: strictly ascending, 0: neither (kk_screen refuses)
     int ldrm = 0, ldm = 0, ldp = 0, ldl = 0;
     int capacity = 0, B = 0;
     double eps = 0;
@@ -958,6 +959,15 @@ static int plan_alloc_batch(hipdrt_plan* p) {
     return 0;
 }
 
+// +1: strictly descending, -1: strictly ascending, 0: neither
+static int freq_monotone(const double* f, int nf) {
+    if (nf < 2) return 1;
+    const int dir = f[0] > f[1] ? 1 : -1;
+    for (int i = 0; i + 1 < nf; ++i)
+        if (!(dir > 0 ? f[i] > f[i + 1] : f[i] < f[i + 1])) return 0;
+    return dir;
+}
+
 int hipdrt_plan_create(hipdrt_ctx* ctx, const double* freq, int nf, const double* tau, int ntau, double epsilon,
                        int mode, int toeplitz_a, int toeplitz_m, int ngrid, int ny, const double* wt_re,
                        const double* wt_im, const double* log_wt_re, const double* log_wt_im,
@@ -988,6 +998,7 @@ int hipdrt_plan_create(hipdrt_ctx* ctx, const double* freq, int nf, const double
     for (int i = 0; i < ntau; ++i) ln_tau[i] = std::log(tau[i]);
     TRY(upload(p->freq, freq, (size_t)nf * sizeof(double), st));
     TRY(upload(p->tau, tau, (size_t)ntau * sizeof(double), st));
+    p->freq_order = freq_monotone(freq, nf);
     const size_t gb = (size_t)(ngrid > 0 ? ngrid : 1) * sizeof(double);
     if (mode == HIPDRT_MODE_INTERP) {
         TRY(upload(p->wt_re, wt_re, gb, st)); TRY(upload(p->wt_im, wt_im, gb, st));
@@ -1119,6 +1130,123 @@ int hipdrt_plan_set_weight_factors(hipdrt_plan* p, double weight_factor, const d
     return HIPDRT_OK;
 } HIPDRT_CATCH
 
+// ---- Kramers-Kronig screening (csrc/kk.hip) ---------------------------------------------------------------------------------
+void hipdrt_default_kk_opts(hipdrt_kk_opts* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->n_outlier_iter = 2; o->p_thresh = 1e-4; o->n_sigma = -1.0; o->std_sample_fraction = 0.6;
+    o->n_std = 0.8416212335729143; o->max_num_outliers = 2; o->outlier_weight = 1e-10;
+}
+
+static int kk_check_opts(const hipdrt_kk_opts& o) {
+    HIPDRT_REQUIRE(o.n_outlier_iter >= 0 && o.n_outlier_iter <= 100, "0 <= n_outlier_iter <= 100");
+    HIPDRT_REQUIRE(o.n_sigma > 0.0 || (o.p_thresh > 0.0 && o.p_thresh < 1.0), "0 < p_thresh < 1");
+    HIPDRT_REQUIRE(o.std_sample_fraction > 0.0 && o.std_sample_fraction <= 1.0, "0 < std_sample_fraction <= 1");
+    HIPDRT_REQUIRE(o.n_std > 0.0 && std::isfinite(o.n_std), "n_std > 0");
+    HIPDRT_REQUIRE(o.max_num_outliers >= 0, "max_num_outliers >= 0");
+    HIPDRT_REQUIRE(o.outlier_weight > 0.0 && std::isfinite(o.outlier_weight), "outlier_weight > 0");
+    return HIPDRT_OK;
+}
+
+// device outputs of one kk launch for B spectra of nf frequencies, and their way back to the host
+extern "C++" {
+namespace {
+struct KkOut {
+    DevBuf zr, zi, er, ei, sd, mask, flim, ilim, status;
+    int alloc(KkArgs& a, int B, int nf, bool z, bool zi_, bool e, bool ei_, bool sd_, bool mask_, bool fl, bool il, bool stt) {
+        const size_t bn = (size_t)B * nf;
+        if (z) { HIPDRT_CHECK(zr.alloc(bn * sizeof(double))); a.z_re = zr.d(); }
+        if (zi_) { HIPDRT_CHECK(zi.alloc(bn * sizeof(double))); a.z_im = zi.d(); }
+        if (e) { HIPDRT_CHECK(er.alloc(bn * sizeof(double))); a.e_re = er.d(); }
+        if (ei_) { HIPDRT_CHECK(ei.alloc(bn * sizeof(double))); a.e_im = ei.d(); }
+        if (sd_) { HIPDRT_CHECK(sd.alloc((size_t)B * sizeof(double))); a.std = sd.d(); }
+        if (mask_) { HIPDRT_CHECK(mask.alloc(bn * sizeof(int))); a.mask = mask.i(); }
+        if (fl) { HIPDRT_CHECK(flim.alloc((size_t)B * 2 * sizeof(double))); a.f_lim = flim.d(); }
+        if (il) { HIPDRT_CHECK(ilim.alloc((size_t)B * 2 * sizeof(int))); a.i_lim = ilim.i(); }
+        if (stt) { HIPDRT_CHECK(status.alloc((size_t)B * sizeof(int))); a.status = status.i(); }
+        return HIPDRT_OK;
+    }
+    static int back(void* host, const DevBuf& d, hipStream_t st) {
+        if (host && d.p) HIPDRT_CHECK(hipMemcpyAsync(host, d.p, d.bytes, hipMemcpyDeviceToHost, st));
+        return HIPDRT_OK;
+    }
+};
+}  // namespace
+}
+
+int hipdrt_plan_kk_screen(hipdrt_plan* p, const hipdrt_kk_opts* opts, int set_row_factors, double* z_hat_re, double* z_hat_im,
+                          double* err_re, double* err_im, double* std_out, int* outlier_mask, double* f_lim, int* i_lim,
+                          int* status) try {
+    HIPDRT_REQUIRE(p, "plan is NULL");
+    HIPDRT_REQUIRE(p->B >= 1 && p->prepped, "no fitted batch in the plan");
+    // every check comes before the first launch and the first change of the plan
+    HIPDRT_REQUIRE(!p->prepared, "the KK screen is built for plain EIS plans (hipdrt_plan_create)");
+    HIPDRT_REQUIRE(p->nf >= 1 && p->m == 2 * p->nf, "the KK screen needs EIS-only data (m = 2 nf)");
+    HIPDRT_REQUIRE(p->freq_order != 0, "the KK screen needs a strictly ascending or descending frequency grid");
+    hipdrt_kk_opts o;
+    if (opts) o = *opts; else hipdrt_default_kk_opts(&o);
+    TRY(kk_check_opts(o));
+    HIPDRT_REQUIRE(kk_lds_bytes(p->nf, p->n, 1) <= 160 * 1024 - 256, "KK screen: nf and n too large for one workgroup's LDS");
+    HIPDRT_CHECK(hipSetDevice(p->ctx->device)); (void)hipGetLastError();
+    hipStream_t st = p->ctx->stream;
+    const int B = p->B, nf = p->nf, m = p->m;
+    KkArgs a{};
+    a.nf = nf; a.desc = p->freq_order > 0 ? 1 : 0; a.freq = p->freq.d(); a.o = o;
+    KkOut out;
+    TRY(out.alloc(a, B, nf, z_hat_re, z_hat_im, err_re, err_im, std_out, outlier_mask, f_lim, i_lim, status));
+    if (set_row_factors) {
+        const size_t need = (size_t)p->capacity * m * sizeof(double);
+        if (p->wrow.bytes < need || !p->wrow_batched) {
+            // (rows past the staged batch are never read by a fit of this batch; ones all the same)
+            std::vector<double> ones((size_t)p->capacity * m, 1.0);
+            TRY(upload(p->wrow, ones.data(), need, st));
+            HIPDRT_CHECK(hipStreamSynchronize(st));
+        }
+        if (!p->w_eff.p) HIPDRT_CHECK(p->w_eff.alloc(need));
+        a.wrow = p->wrow.d();
+    }
+    const FitState fs = p->state();
+    TRY(launch_kk(st, &fs, a, B));
+    LAUNCH_OK();
+    if (set_row_factors) { p->weight_factor = 1.0; p->wrow_batched = 1; p->wrow_late = 1; }
+    TRY(KkOut::back(z_hat_re, out.zr, st)); TRY(KkOut::back(z_hat_im, out.zi, st));
+    TRY(KkOut::back(err_re, out.er, st)); TRY(KkOut::back(err_im, out.ei, st));
+    TRY(KkOut::back(std_out, out.sd, st)); TRY(KkOut::back(outlier_mask, out.mask, st));
+    TRY(KkOut::back(f_lim, out.flim, st)); TRY(KkOut::back(i_lim, out.ilim, st)); TRY(KkOut::back(status, out.status, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+// test hook (include/hipdrt_debug.h): stage B of kk_kernel as it is, on host residuals
+int hipdrt_debug_kk_stats(hipdrt_ctx* ctx, int B, int nf, const double* freq, const double* err_re, const double* err_im,
+                          const hipdrt_kk_opts* opts, double* std_out, int* outlier_mask, double* f_lim, int* i_lim,
+                          int* status) try {
+    HIPDRT_REQUIRE(ctx && freq && err_re && err_im, "NULL pointer");
+    HIPDRT_REQUIRE(B >= 1 && B <= 65535 && nf >= 1 && nf <= 4096, "1 <= B <= 65535, 1 <= nf <= 4096");
+    const int order = freq_monotone(freq, nf);
+    HIPDRT_REQUIRE(order != 0, "the frequency grid must be strictly ascending or descending");
+    hipdrt_kk_opts o;
+    if (opts) o = *opts; else hipdrt_default_kk_opts(&o);
+    TRY(kk_check_opts(o));
+    HIPDRT_REQUIRE(kk_lds_bytes(nf, 0, 0) <= 160 * 1024 - 256, "KK statistics: nf too large for one workgroup's LDS");
+    HIPDRT_CHECK(hipSetDevice(ctx->device)); (void)hipGetLastError();
+    hipStream_t st = ctx->stream;
+    DevBuf dfreq, dre, dim;
+    TRY(upload(dfreq, freq, (size_t)nf * sizeof(double), st));
+    TRY(upload(dre, err_re, (size_t)B * nf * sizeof(double), st));
+    TRY(upload(dim, err_im, (size_t)B * nf * sizeof(double), st));
+    KkArgs a{};
+    a.nf = nf; a.desc = order > 0 ? 1 : 0; a.freq = dfreq.d(); a.o = o; a.in_re = dre.d(); a.in_im = dim.d();
+    KkOut out;
+    TRY(out.alloc(a, B, nf, false, false, false, false, std_out, outlier_mask, f_lim, i_lim, status));
+    TRY(launch_kk(st, nullptr, a, B));
+    LAUNCH_OK();
+    TRY(KkOut::back(std_out, out.sd, st)); TRY(KkOut::back(outlier_mask, out.mask, st));
+    TRY(KkOut::back(f_lim, out.flim, st)); TRY(KkOut::back(i_lim, out.ilim, st)); TRY(KkOut::back(status, out.status, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
 int hipdrt_plan_set_init_h(hipdrt_plan* p, const double* h_init) try {
     HIPDRT_REQUIRE(p, "plan is NULL");
     HIPDRT_CHECK(hipSetDevice(p->ctx->device)); (void)hipGetLastError();
@@ -1172,6 +1300,9 @@ int hipdrt_plan_get(hipdrt_plan* p, const char* which, double* out, long long co
     else if (w == "xmx") { src = p->xmx.d(); rows = p->B; cols = ld = 3; }
     else if (w == "outlier_t" && p->outlier_t.p) { src = p->outlier_t.d(); rows = p->B; cols = ld = p->m; }
     else if (w == "weight_factors" && p->wfac.p) { src = p->wfac.d(); rows = p->B; cols = ld = 2; }
+    else if (w == "row_factors" && p->wrow.p && p->wrow_batched) { src = p->wrow.d(); rows = p->B; cols = ld = p->m; }   // [B][m]
+    else if (w == "x") { src = p->x.d(); rows = p->B; cols = ld = p->n; }
+    else if (w == "coef_scale") { src = p->coef_scale.d(); rows = p->B; cols = ld = 1; }
     else if (w == "dop_rho" && p->prepared) { src = p->dop_rho.d(); rows = p->B; cols = ld = 3; }
     else if (w == "dop_xmx" && p->prepared) { src = p->dop_xmx.d(); rows = p->B; cols = ld = 3; }
     else if (w == "rzm") { src = p->rm.d(); rows = (p->rm_stride ? p->B : 1) * p->m; cols = p->n; ld = p->ldrm; }

@@ -243,6 +243,26 @@ void launch_special_penalty(hipStream_t s, double* m0, double* m1, double* m2, i
                             double pen_r, double pen_l);
 void launch_make_h(hipStream_t s, double* h, int n, int ns, int nonneg);
 
+// kk.hip: Kramers-Kronig screening, one workgroup per spectrum (all pointers device memory; an output may be null)
+struct KkArgs {
+    int nf, p2;                   // frequencies; power of two >= 2 nf (set by launch_kk)
+    int desc;                     // 1: freq is descending, 0: ascending
+    const double* freq;           // [nf]
+    hipdrt_kk_opts o;
+    const double *in_re, *in_im;  // [B][nf] residuals for the stage-B-only launch
+    double *z_re, *z_im;          // [B][nf] prediction in data units
+    double *e_re, *e_im;          // [B][nf] residuals, percent of |Z|
+    double* std;                  // [B]
+    int* mask;                    // [B][nf]
+    double* f_lim;                // [B][2] f_min, f_max
+    int* i_lim;                   // [B][2] positions in descending-frequency order
+    int* status;                  // [B]
+    double* wrow;                 // [B][2 nf] or null: row factors of the next fit
+};
+size_t kk_lds_bytes(int nf, int n, int stage_a);
+// st != null: both stages on the plan's state; null: stage B alone on a.in_re / a.in_im.  HIPDRT_E_INVALID when LDS cannot hold the shape.
+int launch_kk(hipStream_t s, const FitState* st, KkArgs a, int B);
+
 // qp.hip
 struct QpArgs {
     int B, n;

@@ -12,7 +12,7 @@ import numpy as np
 from .. import _ffi, preprocessing as pp
 from ..matrices import mat1d
 from ..utils.array import is_uniform
-from . import qphb
+from . import kk, qphb
 from .prepared import PreparedFitMixin, combine_status
 
 _FIT_KW_DEFAULTS = dict(  # DRT._qphb_fit_core keyword defaults (drt1d.py:102-137) that the device loop honours
@@ -631,3 +631,148 @@ class DRT(PreparedFitMixin):
         self.stage_batch(frequencies, z_batch, history_of=history_of, **kw)
         self.fit_staged()
         return self.collect_staged()
+
+    # ---- Kramers-Kronig test (drt1d.py:1370-1491) ------------------------------------------------------------------------
+    def get_fit_frequencies(self):
+        """DRTBase.get_fit_frequencies for an EIS fit: the frequencies of the last fit"""
+        return np.asarray(self.f_fit, dtype=float)
+
+    def _kk_plan(self):
+        if self._plan is None or self._last_batch is None or isinstance(self._plan, _ffi.PreparedPlan):
+            raise NotImplementedError('the Kramers-Kronig screen needs a finished plain EIS fit (fit_eis / fit_eis_batch '
+                                      'without fit_dop, fit_capacitance, solve_rp or outlier removal)')
+        return self._plan
+
+    @staticmethod
+    def _kk_opts(n_outlier_iter=2, p_thresh=1e-4, n_sigma=None, std_sample_fraction=0.6, max_num_outliers=2):
+        if std_sample_fraction > 1 or std_sample_fraction <= 0:
+            raise ValueError('sample_fraction must be no greater than 1')              # stats.robust_std
+        return _ffi.kk_opts(n_outlier_iter=n_outlier_iter, p_thresh=p_thresh, n_sigma=n_sigma,
+                            std_sample_fraction=std_sample_fraction,
+                            n_std=kk.std_normal_quantile(0.5 + std_sample_fraction / 2), max_num_outliers=max_num_outliers)
+
+    def predict_z(self, frequencies):
+        """DRT.predict_z at the FIT frequencies only: rm @ x of the fitted spectrum, in data units, formed on the device
+        (hipdrt_plan_kk_screen).  Any other frequencies raise NotImplementedError."""
+        plan = self._kk_plan()
+        f = np.asarray(frequencies, dtype=float)
+        if f.shape != np.shape(self.f_fit) or not np.array_equal(f, self.f_fit):
+            raise NotImplementedError('predict_z is built for the fit frequencies only (get_fit_frequencies())')
+        return plan.kk_screen(self._kk_opts(), residuals=False)['z_hat'][0]
+
+    def eval_kk_residuals(self, norm='modulus'):
+        """DRT.eval_kk_residuals (drt1d.py:1472-1481): 100 (z - z_hat) / |z| at the fit frequencies, from the device"""
+        if norm != 'modulus':
+            raise ValueError(f'norm must be "modulus", got {norm!r}')
+        return self._kk_plan().kk_screen(self._kk_opts(), z_hat=False)['residuals'][0]
+
+    def get_kk_outliers(self, norm='modulus', n_iter=2, p_thresh=1e-4, n_sigma=None, std_sample_fraction=0.6):
+        """DRT.get_kk_outliers (drt1d.py:1483-1486): indices of the outliers of the last fit's residuals, from the device"""
+        if norm != 'modulus':
+            raise ValueError(f'norm must be "modulus", got {norm!r}')
+        self._kk_last = dict(n_outlier_iter=n_iter, p_thresh=p_thresh, n_sigma=n_sigma, std_sample_fraction=std_sample_fraction)
+        res = self._kk_plan().kk_screen(self._kk_opts(**self._kk_last), z_hat=False, residuals=False)
+        if res['status'][0] < 0:
+            raise ValueError('the fit of this spectrum failed: there are no residuals to screen')
+        return np.where(res['outlier_mask'][0] != 0)[0]
+
+    def get_kk_limits(self, outlier_index, max_num_outliers=2):
+        """DRT.get_kk_limits (drt1d.py:1488-1491): (f_min, f_max) of the clean window.  For the index set get_kk_outliers
+        returned for this fit -- what kk_test passes -- the window is the device's; an index set of the caller's own making is
+        handed to models.kk.get_limits.  IndexError when no point is clean with clean neighbours, as upstream."""
+        plan = self._kk_plan()
+        res = plan.kk_screen(self._kk_opts(max_num_outliers=max_num_outliers, **getattr(self, '_kk_last', {})),
+                             z_hat=False, residuals=False)
+        own = np.where(res['outlier_mask'][0] != 0)[0]
+        if not np.array_equal(np.sort(np.asarray(outlier_index, dtype=int)), own):
+            return kk.get_limits(self.get_fit_frequencies(), outlier_index, max_num_outliers=max_num_outliers)
+        if res['status'][0] == 1:
+            raise IndexError('no clean point with clean neighbours: the frequency limits are undefined')
+        return float(res['f_lim'][0, 0]), float(res['f_lim'][0, 1])
+
+    @staticmethod
+    def _kk_weight_factor(num_freq, outlier_index, outlier_weight=1e-10):
+        """the vector-valued weight_factor of kk_fit (drt1d.py:1399-1404): outliers stay in the data with (almost) no weight"""
+        weight_factor = np.ones(2 * num_freq)
+        outlier_index = np.asarray(outlier_index, dtype=int)
+        weight_factor[outlier_index] = outlier_weight
+        weight_factor[outlier_index + num_freq] = outlier_weight
+        return weight_factor
+
+    def kk_fit(self, frequencies, z, nonneg=False, l2_lambda_0=1e-2, extend_basis_decades=2, outlier_index=None):
+        """DRT.kk_fit (drt1d.py:1393-1411): a weakly regularised fit without the sign constraint on a basis extended by
+        ``extend_basis_decades`` (the instance's own setting is restored afterwards)."""
+        extend_basis_orig = self.extend_basis_decades
+        self.extend_basis_decades = extend_basis_decades
+        try:
+            weight_factor = 1 if outlier_index is None else self._kk_weight_factor(len(frequencies), outlier_index)
+            self.fit_eis(frequencies, z, nonneg=nonneg, l2_lambda_0=l2_lambda_0, weight_factor=weight_factor)
+            self.z_fit = np.asarray(z, dtype=complex)
+        finally:
+            self.extend_basis_decades = extend_basis_orig
+
+    def kk_test(self, frequencies, z, nonneg=False, l2_lambda_0=1e-2, extend_basis_decades=2, norm='modulus',
+                max_num_outliers=2, p_thresh=1e-4, n_sigma=None, std_sample_fraction=0.6, n_iter=2, n_outlier_iter=2,
+                show_plot=True):
+        """DRT.kk_test (drt1d.py:1370-1391): n_iter rounds of kk_fit -> outliers -> limits, each fit with the previous round's
+        outliers weighted out.  Returns (outlier_index, (f_min, f_max), (f_clean, z_clean))."""
+        if n_iter < 1:
+            raise ValueError('n_iter must be at least 1')
+        frequencies, z = np.asarray(frequencies, dtype=float), np.asarray(z, dtype=complex)
+        outlier_index = None
+        for _ in range(n_iter):
+            self.kk_fit(frequencies, z, nonneg=nonneg, l2_lambda_0=l2_lambda_0, extend_basis_decades=extend_basis_decades,
+                        outlier_index=outlier_index)
+            outlier_index = self.get_kk_outliers(norm=norm, p_thresh=p_thresh, n_iter=n_outlier_iter, n_sigma=n_sigma,
+                                                 std_sample_fraction=std_sample_fraction)
+            f_min, f_max = self.get_kk_limits(outlier_index, max_num_outliers=max_num_outliers)
+            fz_clean = kk.trim_data(frequencies, z, f_min, f_max)
+        if show_plot:
+            warnings.warn('plotting is outside this package: kk_test(show_plot=True) returns its results without a figure')
+        return outlier_index, (f_min, f_max), fz_clean
+
+    def kk_test_batch(self, frequencies, z_batch, nonneg=False, l2_lambda_0=1e-2, extend_basis_decades=2, norm='modulus',
+                      max_num_outliers=2, p_thresh=1e-4, n_sigma=None, std_sample_fraction=0.6, n_iter=2, n_outlier_iter=2):
+        """kk_test for B spectra on one frequency grid (a map): the batch is staged once, then n_iter rounds of fit -> screen run
+        on one plan.  Every screen but the last writes the next fit's row factors on the device (nothing but the results crosses
+        to the host), and the later rounds fit the staged data again without staging anew, which would reset them.  Fits with
+        row factors run in one range (hipdrt_plan_set_subbatches), so the second and later fits do not overlap ranges.
+        Returns a dict: outlier_mask (B, nf) bool, f_min / f_max (B,), clean_mask (B, nf) bool (the points trim_data keeps),
+        residuals (B, nf) complex in percent of |Z|, std (B,), status (B,) (0 ok, 1 no clean point: limits NaN, -1 fit failed),
+        z_hat (B, nf) complex -- all of the last round -- and passes, the same entries for every round.  The plan's weight
+        factors are cleared afterwards."""
+        if norm != 'modulus':
+            raise ValueError(f'norm must be "modulus", got {norm!r}')
+        if n_iter < 1:
+            raise ValueError('n_iter must be at least 1')
+        if self.fit_dop or self.fit_capacitance:
+            raise NotImplementedError('kk_test_batch is built for plain EIS plans')
+        frequencies = np.asarray(frequencies, dtype=float)
+        z_batch = np.asarray(z_batch, dtype=complex)
+        if z_batch.ndim != 2 or z_batch.shape[1] != len(frequencies):
+            raise ValueError('z_batch must have shape (B, len(frequencies))')
+        opts = self._kk_opts(n_outlier_iter=n_outlier_iter, p_thresh=p_thresh, n_sigma=n_sigma,
+                             std_sample_fraction=std_sample_fraction, max_num_outliers=max_num_outliers)
+        extend_basis_orig = self.extend_basis_decades
+        self.extend_basis_decades = extend_basis_decades
+        plan, passes = None, []
+        try:
+            plan = self.stage_batch(frequencies, z_batch, nonneg=nonneg, l2_lambda_0=l2_lambda_0)
+            for i in range(n_iter):
+                plan.fit()
+                res = plan.kk_screen(opts, set_row_factors=i < n_iter - 1)
+                res['timings_ms'], res['launches'] = plan.timings()
+                ok = res['status'] == 0
+                f_min, f_max = res['f_lim'][:, 0], res['f_lim'][:, 1]
+                with np.errstate(invalid='ignore'):
+                    clean = (frequencies[None, :] <= f_max[:, None]) & (frequencies[None, :] >= f_min[:, None]) & ok[:, None]
+                passes.append(dict(outlier_mask=res['outlier_mask'] != 0, f_min=f_min, f_max=f_max, clean_mask=clean,
+                                   residuals=res['residuals'], std=res['std'], status=res['status'], z_hat=res['z_hat'],
+                                   i_lim=res['i_lim'], timings_ms=res['timings_ms']))
+        finally:
+            self.extend_basis_decades = extend_basis_orig
+            if plan is not None:
+                plan.set_weight_factors(1.0)
+        out = dict(passes[-1])
+        out['passes'] = passes
+        return out

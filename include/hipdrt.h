@@ -227,7 +227,8 @@ int hipdrt_plan_destroy(hipdrt_plan* plan);
 /* dimensions: n = ns + ntau unknowns, m = 2 nf rows, ns special parameters */
 int hipdrt_plan_dims(hipdrt_plan* plan, int* n, int* m, int* ns);
 /* copy a shared matrix of the plan back to the host: which = "lut_z_re","lut_z_im" [ngrid],
- * "a_re","a_im" [nf][ntau], "rm" [m][n], "m0","m1","m2" [n][n] (padded), "vmm" [m][m]                  */
+ * "a_re","a_im" [nf][ntau], "rm" [m][n], "m0","m1","m2" [n][n] (padded), "vmm" [m][m]; of the staged batch:
+ * "rv" [B][m] scaled data, "x" [B][n] current solution, "coef_scale" [B], "row_factors" [B][m] (batched row factors only) */
 int hipdrt_plan_get(hipdrt_plan* plan, const char* which, double* out, long long count);
 /* replace the plan's lookup tables with externally supplied ones (multi-GPU: rank 0 builds them, RCCL
  * broadcasts, the other ranks install them) and rebuild the dependent matrices            */
@@ -410,6 +411,42 @@ int hipdrt_plan_set_weight_factors(hipdrt_plan* plan, double weight_factor, cons
  * negative coefficients only inside a tau window, initialize_weights everywhere; hybdrt/models/drt1d.py:467, 657-660 vs
  * 944, hybdrt/models/qphb.py:521-557).  h_init[n]; NULL restores the plan's single h.                                   */
 int hipdrt_plan_set_init_h(hipdrt_plan* plan, const double* h_init);
+
+/* ---- Kramers-Kronig screening of the fitted batch ---------------------------------------------------------------------
+ * Options of DRT.kk_test's screening step (hybdrt/models/drt1d.py:1370-1391): n_outlier_iter / p_thresh / n_sigma /
+ * std_sample_fraction are the arguments of kk.get_outliers (hybdrt/models/kk.py:21-53), max_num_outliers that of kk.get_limits
+ * (kk.py:56-123), outlier_weight the row factor kk_fit gives an outlier (drt1d.py:1403-1404).  n_std is the standard-normal
+ * quantile of 0.5 + std_sample_fraction / 2 (stats.robust_std, hybdrt/utils/stats.py:124-134), supplied by the caller.      */
+typedef struct {
+    int n_outlier_iter;           /* 2 */
+    double p_thresh;              /* 1e-4 */
+    double n_sigma;               /* -1; <= 0 means None: the chi-squared test with p_thresh, else |e| > n_sigma * std */
+    double std_sample_fraction;   /* 0.6 */
+    double n_std;                 /* 0.8416212335729143 */
+    int max_num_outliers;         /* 2 */
+    double outlier_weight;        /* 1e-10 */
+} hipdrt_kk_opts;
+void hipdrt_default_kk_opts(hipdrt_kk_opts* o);
+/* DRT.eval_kk_residuals + get_kk_outliers + get_kk_limits (drt1d.py:1472-1491) for every spectrum of the fitted batch, on the
+ * device, one workgroup per spectrum: the prediction at the fit frequencies yh = rm x (predict_z, in data units:
+ * z_hat = coef_scale * yh), residuals e = 100 (z - z_hat) / |z| (kk.normalize_residuals, norm="modulus", kk.py:9-19), the outlier
+ * mask of kk.get_outliers -- robust std from numpy's linear percentiles 50 -/+ 100 fraction / 2 of the unmasked Re and Im
+ * residuals, then exp(-|e|^2 / (2 std^2)) < p_thresh (= 1 - chi2.cdf(|e|^2, 2, scale=std^2)) or |e| > n_sigma std, n_outlier_iter
+ * times; fewer than two values left, or a std that is zero or not finite, masks nothing -- and the clean window of kk.get_limits.
+ * Plain EIS plans (hipdrt_plan_create) whose frequency grid is strictly ascending or descending; anything else, or a shape whose
+ * residuals, sort buffer, x and prediction do not fit one workgroup's LDS (nf <= 2048 with n <= 4096 fits), is HIPDRT_E_INVALID
+ * before any launch.
+ * out (host; any may be NULL): z_hat_re, z_hat_im [B][nf]; err_re, err_im [B][nf] percent of |Z|; std [B] of the last outlier
+ * iteration; outlier_mask [B][nf]; f_lim [B][2] = f_min, f_max; i_lim [B][2] = i_left, i_right, positions in descending-frequency
+ * order; status [B]: 0 ok, 1 no clean point (the reference raises IndexError; limits NaN, indices -1), -1 the spectrum's fit
+ * failed (outputs NaN, mask empty, row factors 1).
+ * set_row_factors != 0: the next fit's row factors are written on the device into the plan's batched row-factor buffer -- rows k and
+ * nf + k get outlier_weight for masked k and 1 elsewhere (drt1d.py:1399-1404) -- and the plan is left as
+ * hipdrt_plan_set_weight_factors(plan, 1.0, rows, 3) would leave it.  Fits with row factors run in one range
+ * (hipdrt_plan_set_subbatches).                                                                                              */
+int hipdrt_plan_kk_screen(hipdrt_plan* plan, const hipdrt_kk_opts* opts, int set_row_factors,
+                          double* z_hat_re, double* z_hat_im, double* err_re, double* err_im,
+                          double* std, int* outlier_mask, double* f_lim, int* i_lim, int* status);
 
 /* kernel-time breakdown of the last hipdrt_plan_fit in ms (HIP events on the ctx stream):
  * t[0]=total, t[1]=gram, t[2]=qp, t[3]=hyper, t[4]=setup/other; launches[5] same order                 */

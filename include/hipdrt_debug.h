@@ -77,6 +77,12 @@ int hipdrt_debug_gram_l2(hipdrt_ctx* ctx, const hipdrt_debug_gram_args* a);
 /* test hook: launch_pack_p -- row-major symmetric P [B][n][ldp] (host) -> Ppk [B][nchp * nchp * 256] (host, in/out as above) */
 int hipdrt_debug_pack_p(hipdrt_ctx* ctx, int B, int n, const double* P, int ldp, double* Ppk);
 
+/* test hook (tests/test_gpu_kk.py): the statistics stage of hipdrt_plan_kk_screen's kernel as it is, on host residuals --
+ * freq [nf] strictly ascending or descending, err_re / err_im [B][nf]; out (any may be NULL): std [B], outlier_mask [B][nf],
+ * f_lim [B][2], i_lim [B][2], status [B] as documented there.  Refuses sizes the kernel's LDS cannot hold.                  */
+int hipdrt_debug_kk_stats(hipdrt_ctx* ctx, int B, int nf, const double* freq, const double* err_re, const double* err_im,
+                          const hipdrt_kk_opts* opts, double* std, int* outlier_mask, double* f_lim, int* i_lim, int* status);
+
 #ifdef __cplusplus
 }
 #endif
