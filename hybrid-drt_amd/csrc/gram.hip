@@ -5,10 +5,12 @@
 //     q_b = -(W_b A)' (W_b y_b) + l1
 //
 // FP64 only.  The contraction runs on v_mfma_f64_16x16x4_f64: a 256-thread workgroup
-// (4 wavefronts as 2x2) owns a 64x64 tile of the lower triangle of P_b, stages 16-row slabs of A (already
-// multiplied by w_b) through LDS and mirrors the tile into the upper triangle on store.  The reference forms
+// (4 wavefronts; who owns which 16x16 sub-tile: "Tile decomposition" below) owns a 64x64 tile of the lower triangle
+// of P_b, stages 16-row slabs of A (already multiplied by w_b) through LDS and mirrors the tile into the upper
+// triangle on store.  The reference forms
 // L2 with two dense n^3 products per derivative order; here it is the O(n^2) elementwise epilogue of the tile.
 #include "common.hpp"
+#include <type_traits>
 
 namespace hipdrt {
 
@@ -18,6 +20,43 @@ static constexpr int GT = 64;        // tile edge
 static constexpr int GK = 16;        // K slab
 static constexpr int GLD = 80;       // LDS row stride in doubles (k-rows land 32 banks apart: conflict-free b64 reads)
 
+
+// Tile decomposition.  The lower triangle is cut into 64 x 64 tiles, one workgroup each, and every tile into 16 x 16 sub-tiles, one
+// MFMA accumulator each.  Whoever owns a sub-tile gives it the same MFMA sequence (k ascending, the same operands), so the deal
+// below does not move a bit of P.
+//   off-diagonal workgroup: wavefront wv owns the 32 x 32 quadrant (wv >> 1, wv & 1), four sub-tiles that share their operands.
+//   diagonal workgroup: its 10 lower sub-tiles are dealt round-robin over the four wavefronts (the quadrant deal gives 3 / 0 / 4 / 3),
+//     the turn starting at wavefront 0 or 2 with the parity of the tile, so that the short shares even out over a spectrum.
+//   the strip: with nt16 = ceil(n / 16) sub-tile rows and nt16 % 4 == 1 (n = 514: 512 tau + R_inf + L, nt16 = 33) the last sub-tile
+//     row R gets no 64-tile row of its own -- nine workgroups that would fetch full slabs for an eighth of a tile's MFMAs.  Diagonal
+//     workgroup t takes the sub-tiles (R, 4t ... 4t+3) instead: their column operand is the slab it has staged anyway, their row
+//     operand -- columns 16R ... 16R+15 of A -- is staged into the columns 64 ... 79 of sI that the row stride leaves free (one
+//     double per thread, in a vj register a diagonal tile does not use).  The last diagonal workgroup also takes the corner (R, R).
+//     That is 14 (15) sub-tiles, at most four per wavefront; at n = 514 36 workgroups instead of 45 and 140 / 141 sub-tiles per
+//     wavefront index and spectrum instead of 153 / 128 / 144 / 136.
+__host__ __device__ inline bool gram_strip_folds(int n) { const int nt16 = (n + 15) >> 4; return (nt16 & 3) == 1 && nt16 > 1; }
+
+struct GramSub { int r, c; };
+__host__ __device__ constexpr GramSub gram_diag_sub(int e) {
+    const int r = e >= 10 ? 4 : e >= 6 ? 3 : e >= 3 ? 2 : e >= 1 ? 1 : 0;
+    return GramSub{r, e >= 14 ? 4 : e >= 10 ? e - 10 : e - r * (r + 1) / 2};
+}
+
+// one slab of a diagonal workgroup for the wavefront whose turn is TURN: sl = the lane's (k row, column) base in the slab
+template <int TURN>
+__device__ __forceinline__ void gram_diag_slab(const double* sl, v4d (&acc)[4], int needm) {
+#pragma unroll
+    for (int kk = 0; kk < GK; kk += 4) {
+        double x[5];
+#pragma unroll
+        for (int c = 0; c < 5; ++c) x[c] = sl[kk * GLD + c * 16];  // (the reads no sub-tile of this turn uses fall away)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const GramSub sub = gram_diag_sub(TURN + 4 * s);
+            if (needm & (1 << s)) acc[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(x[sub.c], x[sub.r], acc[s], 0, 0, 0);
+        }
+    }
+}
 
 // ROWP: also write the row-major copy P (stand-alone entry points); the fit loop reads the packed tiles only
 template <bool DOP, bool ROWP>
@@ -35,28 +74,52 @@ __global__ __launch_bounds__(256, 5) void gram_kernel(int m, int n, const double
     const int tj = t;
     const int i0 = ti * GT, j0 = tj * GT;
     const bool diag = (ti == tj);
+    const int nt16 = (n + 15) >> 4;
+    const bool strip = diag && gram_strip_folds(n);         // this workgroup carries four sub-tiles of the strip ...
+    const int s0 = (nt16 - 1) * 16;                          // ... whose first row this is
+    const bool last = strip && i0 + GT == s0;                // ... and the corner
 
     __shared__ double sI[GK * GLD];
     __shared__ double sJ[GK * GLD];
 
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int wi = (wv >> 1) * 32, wj = (wv & 1) * 32;     // wave's 32x32 sub-tile
+    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const double* wb = w + (size_t)b * m;
+    double* Pk = Ppk ? Ppk + (size_t)b * ppk_stride : nullptr;
 
-    v4d acc[2][2];
+    // Sub-tile e of a diagonal workgroup, row-major over its lower sub-tiles, then the strip's four, then the corner:
+    // e = 0 ... 9 -> (r, c) with c <= r <= 3, 10 ... 13 -> (4, e - 10), 14 -> (4, 4), row / column 4 being the strip's.
+    // Wavefront wv owns e = turn + 4 s, s = 0 ... 3, as far as they exist (nown) and hold data to multiply (nneed: the rest
+    // is padding of the packed layout, written as zeros).
+    int nown = 0, needm = 0;                                 // needm: bit s = sub-tile turn + 4 s is multiplied
+    const int turn = (wv + 2 * (ti & 1)) & 3;
+    if (diag) {
+        const int rows_all = (Pk && nchp > nt16 ? nchp : nt16) - 4 * ti, rows_data = nt16 - 4 * ti;
+        const int nr = rows_all < 4 ? rows_all : 4, nd = rows_data < 4 ? rows_data : 4;
+        nown = nr * (nr + 1) / 2 + (strip ? 4 : 0) + (last ? 1 : 0);
+        const int nneed = strip ? nown : nd * (nd + 1) / 2;
 #pragma unroll
-    for (int a = 0; a < 2; ++a)
+        for (int s = 0; s < 4; ++s) needm |= (turn + 4 * s < nneed) << s;
+    }
+    // the quadrant of an off-diagonal workgroup: sub-tile s = 2 a + c is (2 (wv >> 1) + a, 2 (wv & 1) + c) of the tile
+    const int qr = 4 * ti + 2 * (wv >> 1), qc = 4 * tj + 2 * (wv & 1);
+    const bool need00 = qr < nt16 && qc < nt16, need01 = qr < nt16 && qc + 1 < nt16;
+    const bool need10 = qr + 1 < nt16 && qc < nt16, need11 = qr + 1 < nt16 && qc + 1 < nt16;
+
+    v4d acc[4];
 #pragma unroll
-        for (int c = 0; c < 2; ++c) acc[a][c] = (v4d){0.0, 0.0, 0.0, 0.0};
+    for (int s = 0; s < 4; ++s) acc[s] = (v4d){0.0, 0.0, 0.0, 0.0};
 
     // staging map: thread -> (k = tid/16, 4 consecutive columns), fetched as two 16-byte loads when the
-    // leading dimension and n are even (always true for the plan's matrices)
+    // leading dimension and n are even (always true for the plan's matrices); the strip: (k = tid/16, column tid%16)
     const int sk = tid >> 4, sc = (tid & 15) * 4;
     const bool vec2 = ((lda | n) & 1) == 0;
     // slab k0+GK is fetched (global -> registers) while slab k0 is multiplied out of LDS; the products with w are
     // formed only when the slab is written to LDS, so nothing waits on the loads inside the MFMA loop
     double vi[4], vj[4], wkr = 0.0;
-    auto fetch = [&](int k0) {
+    // (DIAG, TURN are the workgroup's `diag` and the wavefront's `turn` as types: the K loop is compiled once per kind, each with
+    // the registers it needs)
+    auto fetch = [&](auto DIAG, int k0) {
+        constexpr bool D = decltype(DIAG)::value;
         const int k = k0 + sk;
 #pragma unroll
         for (int e = 0; e < 4; ++e) { vi[e] = 0.0; vj[e] = 0.0; }
@@ -69,69 +132,90 @@ __global__ __launch_bounds__(256, 5) void gram_kernel(int m, int n, const double
                 for (int e = 0; e < 4; e += 2) {
                     const int ci = i0 + sc + e, cj = j0 + sc + e;
                     if (ci < n) { const double2 t = *reinterpret_cast<const double2*>(row + ci); vi[e] = t.x; vi[e + 1] = t.y; }
-                    if (!diag && cj < n) { const double2 t = *reinterpret_cast<const double2*>(row + cj); vj[e] = t.x; vj[e + 1] = t.y; }
+                    if (!D && cj < n) { const double2 t = *reinterpret_cast<const double2*>(row + cj); vj[e] = t.x; vj[e + 1] = t.y; }
                 }
             } else {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int ci = i0 + sc + e, cj = j0 + sc + e;
                     if (ci < n) vi[e] = row[ci];
-                    if (!diag && cj < n) vj[e] = row[cj];
+                    if (!D && cj < n) vj[e] = row[cj];
                 }
             }
+            if (D && strip && s0 + (tid & 15) < n) vj[0] = row[s0 + (tid & 15)];
         }
     };
     // 16x16 sub-tiles that are pure padding (beyond n) or lie above the diagonal (the epilogue takes those elements
     // from the mirror) are not multiplied at all
-    const int nt16 = (n + 15) >> 4;
-    const int tr0 = __builtin_amdgcn_readfirstlane((i0 + wi) >> 4), tc0 = __builtin_amdgcn_readfirstlane((j0 + wj) >> 4);
-    const bool need00 = tr0 < nt16 && tc0 < nt16 && tr0 >= tc0;
-    const bool need01 = tr0 < nt16 && tc0 + 1 < nt16 && tr0 >= tc0 + 1;
-    const bool need10 = tr0 + 1 < nt16 && tc0 < nt16 && tr0 + 1 >= tc0;
-    const bool need11 = tr0 + 1 < nt16 && tc0 + 1 < nt16 && tr0 + 1 >= tc0 + 1;
-    fetch(0);
-    for (int k0 = 0; k0 < m; k0 += GK) {
-        __syncthreads();   // previous slab fully consumed
-        *reinterpret_cast<double2*>(&sI[sk * GLD + sc]) = make_double2(wkr * vi[0], wkr * vi[1]);
-        *reinterpret_cast<double2*>(&sI[sk * GLD + sc + 2]) = make_double2(wkr * vi[2], wkr * vi[3]);
-        if (!diag) {
-            *reinterpret_cast<double2*>(&sJ[sk * GLD + sc]) = make_double2(wkr * vj[0], wkr * vj[1]);
-            *reinterpret_cast<double2*>(&sJ[sk * GLD + sc + 2]) = make_double2(wkr * vj[2], wkr * vj[3]);
-        }
-        __syncthreads();
-        if (k0 + GK < m) fetch(k0 + GK);
-        const double* sj = diag ? sI : sJ;
+    auto kloop = [&](auto DIAG, auto TURN) {
+        constexpr bool D = decltype(DIAG)::value;
+        fetch(DIAG, 0);
+        for (int k0 = 0; k0 < m; k0 += GK) {
+            __syncthreads();   // previous slab fully consumed
+            *reinterpret_cast<double2*>(&sI[sk * GLD + sc]) = make_double2(wkr * vi[0], wkr * vi[1]);
+            *reinterpret_cast<double2*>(&sI[sk * GLD + sc + 2]) = make_double2(wkr * vi[2], wkr * vi[3]);
+            if (!D) {
+                *reinterpret_cast<double2*>(&sJ[sk * GLD + sc]) = make_double2(wkr * vj[0], wkr * vj[1]);
+                *reinterpret_cast<double2*>(&sJ[sk * GLD + sc + 2]) = make_double2(wkr * vj[2], wkr * vj[3]);
+            } else if (strip) {
+                sI[sk * GLD + GT + (tid & 15)] = wkr * vj[0];
+            }
+            __syncthreads();
+            if (k0 + GK < m) fetch(DIAG, k0 + GK);
+            if (!D) {
+                const int wi = (wv >> 1) * 32, wj = (wv & 1) * 32;     // four sub-tiles from four operand reads
 #pragma unroll
-        for (int kk = 0; kk < GK; kk += 4) {
-            const int kr = kk + (lane >> 4);
-            double a0 = sI[kr * GLD + wi + (lane & 15)];
-            double a1 = sI[kr * GLD + wi + 16 + (lane & 15)];
-            double b0 = sj[kr * GLD + wj + (lane & 15)];
-            double b1 = sj[kr * GLD + wj + 16 + (lane & 15)];
-            if (need00) acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(b0, a0, acc[0][0], 0, 0, 0);
-            if (need01) acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(b1, a0, acc[0][1], 0, 0, 0);
-            if (need10) acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(b0, a1, acc[1][0], 0, 0, 0);
-            if (need11) acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(b1, a1, acc[1][1], 0, 0, 0);
+                for (int kk = 0; kk < GK; kk += 4) {
+                    const int kr = kk + (lane >> 4);
+                    double a0 = sI[kr * GLD + wi + (lane & 15)];
+                    double a1 = sI[kr * GLD + wi + 16 + (lane & 15)];
+                    double b0 = sJ[kr * GLD + wj + (lane & 15)];
+                    double b1 = sJ[kr * GLD + wj + 16 + (lane & 15)];
+                    if (need00) acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(b0, a0, acc[0], 0, 0, 0);
+                    if (need01) acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(b1, a0, acc[1], 0, 0, 0);
+                    if (need10) acc[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(b0, a1, acc[2], 0, 0, 0);
+                    if (need11) acc[3] = __builtin_amdgcn_mfma_f64_16x16x4f64(b1, a1, acc[3], 0, 0, 0);
+                }
+            } else {
+                // any wavefront reads any 16 columns of the slab (the strip's are columns 64 ... 79); one loop per turn, so
+                // that every operand address is the lane's base plus a constant
+                const double* sl = sI + (lane >> 4) * GLD + (lane & 15);
+                gram_diag_slab<decltype(TURN)::value>(sl, acc, needm);
+            }
         }
-    }
+    };
+    if (!diag) kloop(std::false_type{}, std::integral_constant<int, 0>{});
+    else if (turn == 0) kloop(std::true_type{}, std::integral_constant<int, 0>{});
+    else if (turn == 1) kloop(std::true_type{}, std::integral_constant<int, 1>{});
+    else if (turn == 2) kloop(std::true_type{}, std::integral_constant<int, 2>{});
+    else kloop(std::true_type{}, std::integral_constant<int, 3>{});
 
     // sqrt(s_k) of the tile's rows / columns once per workgroup (the L2 epilogue needs them per element); they take
     // over the slab buffers, so the kernel needs 20 kB of LDS and eight workgroups fit a CU
-    double (*sqI)[GT] = reinterpret_cast<double (*)[GT]>(sI);
-    double (*sqJ)[GT] = reinterpret_cast<double (*)[GT]>(sJ);
+    double* sqI = sI;                                                // [3][GT]
+    double* sqJ = sJ;                                                // [3][GT]
     // On a log-uniform tau grid the DRT block of every penalty matrix is symmetric Toeplitz, M_k[i][j] = t_k[|i - j|]
     // with t_k = its first row: the tile needs the 127 differences around i0 - j0 only, staged behind the sqrt tables,
     // and no dense matrix is read in the epilogue (three 2 MB matrices per spectrum and outer iteration otherwise).
     constexpr int TW = 2 * GT;                                      // window slots per order (127 used)
-    double (*tw)[TW] = reinterpret_cast<double (*)[TW]>(sI + 3 * GT);
+    double* tw = sI + 3 * GT;                                        // [3][TW]
     const int dbase = i0 - j0 - (GT - 1);                           // difference of window slot 0
+    // the strip's tables, in the sJ region a diagonal tile leaves free: sqrt(s_k) of its 16 rows and a window of its own for the
+    // 79 differences 16R + r - (j0 + c) (the corner's differences -15 ... 15 are in the tile's window)
+    constexpr int SW = GT + 16;
+    double* sqS = sJ + 3 * GT;                                       // [3][16]
+    double* tws = sJ + 4 * GT;                                       // [3][SW]
+    const int dbase_s = s0 - j0 - (GT - 1);
     double fac[3] = {0, 0, 0};
     // Tiles of the DRT block that lie wholly beyond the reach of the penalty matrices -- every |i - j| of the tile larger than the
     // last non-zero entry of the Toeplitz first rows -- would add (sqrt(s_i) * 0) * sqrt(s_j) = 0 to every element: no tables,
-    // no epilogue arithmetic, the same bits (28 of the 45 tiles of a 514 x 514 matrix lie two or more tile diagonals out; the 7
+    // no epilogue arithmetic, the same bits (21 of the 36 tiles of a 514 x 514 matrix lie two or more tile diagonals out; the 6
     // of them that touch the special-parameter columns qualify when those columns of the penalty matrices are zero outside the
-    // special block, which the plan checks once)
-    const bool l2on = g.s && !(!DOP && g.toep && g.toep_maxd >= 0 && (j0 >= g.ns || g.spec_zero) && i0 >= g.ns && dbase > g.toep_maxd);
+    // special block, which the plan checks once).  The strip part of a diagonal tile is judged by its own differences (at
+    // n = 514 it is within reach of the last diagonal tiles only).
+    const bool reach_known = !DOP && g.toep && g.toep_maxd >= 0 && (j0 >= g.ns || g.spec_zero);
+    const bool l2on = g.s && !(reach_known && i0 >= g.ns && dbase > g.toep_maxd);
+    const bool l2on_s = strip && g.s && !(reach_known && s0 >= g.ns && dbase_s > g.toep_maxd);
     if (l2on) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) fac[k] = g.dfac[k] * (g.use_rho ? g.rho[(size_t)b * 3 + k] : 1.0);
@@ -139,8 +223,12 @@ __global__ __launch_bounds__(256, 5) void gram_kernel(int m, int n, const double
         const double* sb_ = g.s + (size_t)b * 3 * n;
         for (int e = tid; e < 3 * GT; e += 256) {
             const int k = e / GT, c = e % GT;
-            sqI[k][c] = (i0 + c < n) ? sqrt(sb_[k * n + i0 + c]) : 0.0;
-            sqJ[k][c] = (j0 + c < n) ? sqrt(sb_[k * n + j0 + c]) : 0.0;
+            sqI[e] = (i0 + c < n) ? sqrt(sb_[k * n + i0 + c]) : 0.0;
+            sqJ[e] = (j0 + c < n) ? sqrt(sb_[k * n + j0 + c]) : 0.0;
+        }
+        if (strip && tid < 3 * 16) {
+            const int k = tid >> 4, c = tid & 15;
+            sqS[tid] = (s0 + c < n) ? sqrt(sb_[k * n + s0 + c]) : 0.0;
         }
         if (g.toep) {
             // (the window holds M_k[|i - j|] * fac[k]: the product the epilogue used to form per element)
@@ -149,7 +237,11 @@ __global__ __launch_bounds__(256, 5) void gram_kernel(int m, int n, const double
                 const int k = e / TW, sl = e % TW;
                 int dd = dbase + sl;
                 dd = dd < 0 ? -dd : dd;
-                tw[k][sl] = (g.dfac[k] > 0.0 && dd < nd) ? g.mk[k][(size_t)g.ns * g.ldm + g.ns + dd] * fac[k] : 0.0;
+                tw[e] = (g.dfac[k] > 0.0 && dd < nd) ? g.mk[k][(size_t)g.ns * g.ldm + g.ns + dd] * fac[k] : 0.0;
+            }
+            if (l2on_s && tid < 3 * SW) {
+                const int k = tid / SW, dd = dbase_s + tid % SW;    // > 0
+                tws[tid] = (g.dfac[k] > 0.0 && dd < nd) ? g.mk[k][(size_t)g.ns * g.ldm + g.ns + dd] * fac[k] : 0.0;
             }
         }
         __syncthreads();
@@ -165,60 +257,88 @@ __global__ __launch_bounds__(256, 5) void gram_kernel(int m, int n, const double
         }
     }
     const int dop_lo = DOP ? g.dop_start : 0, dop_hi = DOP ? g.dop_start + g.dop_size : 0;
-    double* Pk = Ppk ? Ppk + (size_t)b * ppk_stride : nullptr;
 #pragma unroll
-    for (int a = 0; a < 2; ++a)
+    for (int s = 0; s < 4; ++s) {
+        // one owned sub-tile (r16, c16): tables of the tile or of the strip, everything else keyed on the absolute (i, j)
+        int r16 = qr + (s >> 1), c16 = qc + (s & 1);
+        bool srow = false, scol = false;
+        if (diag) {
+            const int e = turn + 4 * s;
+            if (e >= nown) continue;
+            const GramSub sub = gram_diag_sub(e);
+            srow = sub.r == 4;
+            scol = sub.c == 4;
+            r16 = srow ? nt16 - 1 : 4 * ti + sub.r;
+            c16 = scol ? nt16 - 1 : 4 * ti + sub.c;
+        }
+        const bool sw = srow && !scol;                               // a strip sub-tile left of the corner
+        const bool on = sw ? l2on_s : l2on;
+        const double* sqr = srow ? sqS - s0 : sqI - i0;              // [k * rstr + i]
+        const double* sqc = scol ? sqS - s0 : sqJ - j0;              // [k * cstr + j]
+        const int rstr = srow ? 16 : GT, cstr = scol ? 16 : GT;
+        const double* win = sw ? tws - dbase_s : tw - dbase;         // [k * wstr + (i - j)]
+        const int wstr = sw ? SW : TW;
+        double vals[4];
 #pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            double vals[4];
+        for (int r = 0; r < 4; ++r) {
+            const int i = r16 * 16 + (lane & 15);
+            const int j = c16 * 16 + (lane >> 4) + 4 * r;
+            double v = 0.0;
+            if (i < n && j < n) {
+                v = acc[s][r];
+                if (on) {
+                    double l2 = 0.0;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int i = i0 + wi + a * 16 + (lane & 15);
-                const int j = j0 + wj + c * 16 + (lane >> 4) + 4 * r;
-                double v = 0.0;
-                if (i < n && j < n) {
-                    v = acc[a][c][r];
-                    if (l2on) {
-                        double l2 = 0.0;
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) {
-                            if (g.dfac[k] > 0.0) {
-                                // (i, j) = (lane&15, lane>>4 + 4r): reading the mirror element keeps the wave's
-                                // addresses contiguous when the matrices are bitwise symmetric
-                                double mv;
-                                if (g.toep && i >= g.ns && j >= g.ns) {
-                                    mv = tw[k][(i - j) - dbase];
-                                } else {
-                                    mv = g.sym ? g.mk[k][(size_t)j * g.ldm + i] : g.mk[k][(size_t)i * g.ldm + j];
-                                    if (i >= g.ns && j >= g.ns) mv *= fac[k];
-                                    else if (DOP && i >= dop_lo && i < dop_hi && j >= dop_lo && j < dop_hi) mv *= dfac2[k];
-                                }
-                                l2 += (sqI[k][i - i0] * mv) * sqJ[k][j - j0];
+                    for (int k = 0; k < 3; ++k) {
+                        if (g.dfac[k] > 0.0) {
+                            // (i, j) = (lane&15, lane>>4 + 4r): reading the mirror element keeps the wave's
+                            // addresses contiguous when the matrices are bitwise symmetric
+                            double mv;
+                            if (g.toep && i >= g.ns && j >= g.ns) {
+                                mv = win[k * wstr + (i - j)];
+                            } else {
+                                mv = g.sym ? g.mk[k][(size_t)j * g.ldm + i] : g.mk[k][(size_t)i * g.ldm + j];
+                                if (i >= g.ns && j >= g.ns) mv *= fac[k];
+                                else if (DOP && i >= dop_lo && i < dop_hi && j >= dop_lo && j < dop_hi) mv *= dfac2[k];
                             }
+                            l2 += (sqr[k * rstr + i] * mv) * sqc[k * cstr + j];
                         }
-                        v += l2;
-                    } else if (!g.s && g.l2) {
-                        v += g.l2[(size_t)b * g.l2_stride + (size_t)i * g.ldl2 + j];
                     }
-                    if (ROWP && Pb && !(diag && j > i)) {      // upper part of a diagonal tile comes from the mirror
-                        Pb[(size_t)i * ldp + j] = v;
-                        if (i != j) Pb[(size_t)j * ldp + i] = v;
-                    }
+                    v += l2;
+                } else if (!g.s && g.l2) {
+                    v += g.l2[(size_t)b * g.l2_stride + (size_t)i * g.ldl2 + j];
                 }
-                vals[r] = v;
+                if (ROWP && Pb && j <= i) {                // upper part of a diagonal sub-tile comes from the mirror
+                    Pb[(size_t)i * ldp + j] = v;
+                    if (i != j) Pb[(size_t)j * ldp + i] = v;
+                }
             }
-            // second copy for the Cholesky in the factor's tile layout (qp_resident.hpp): double2 h*64 + i*4 + q holds
-            // columns q + 8h, q + 8h + 4 of row i -- two 16-byte stores per lane, 2 KB contiguous per tile
-            if (Pk) {
-                const int tr = ((i0 + wi) >> 4) + a, tc = ((j0 + wj) >> 4) + c;
-                if (tr < nchp && tc < nchp && tr >= tc) {
-                    double2* tile = reinterpret_cast<double2*>(Pk + ((size_t)tr * nchp + tc) * 256);
-                    const int fo = (lane & 15) * 4 + (lane >> 4);
-                    tile[fo] = make_double2(vals[0], vals[1]);
-                    tile[64 + fo] = make_double2(vals[2], vals[3]);
-                }
+            vals[r] = v;
+        }
+        // second copy for the Cholesky in the factor's tile layout (qp_resident.hpp): double2 h*64 + i*4 + q holds
+        // columns q + 8h, q + 8h + 4 of row i -- two 16-byte stores per lane, 2 KB contiguous per tile
+        if (Pk && r16 < nchp && c16 < nchp && r16 >= c16) {
+            double2* tile = reinterpret_cast<double2*>(Pk + ((size_t)r16 * nchp + c16) * 256);
+            const int fo = (lane & 15) * 4 + (lane >> 4);
+            tile[fo] = make_double2(vals[0], vals[1]);
+            tile[64 + fo] = make_double2(vals[2], vals[3]);
+        }
+    }
+    // the packed layout's pure-padding tile rows below the strip (n = 514: tile row 33 of nchp = 34), which a 64-tile row of
+    // the strip's own would have covered: zeros, beneath this workgroup's columns
+    if (Pk && strip) {
+        const int pe = nchp < nt16 + 3 ? nchp : nt16 + 3;
+        for (int pr = nt16; pr < pe; ++pr) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int pc = h ? nt16 - 1 + wv : 4 * ti + wv;
+                if (h && !(last && pc <= pr)) continue;
+                double2* tile = reinterpret_cast<double2*>(Pk + ((size_t)pr * nchp + pc) * 256);
+                tile[lane] = make_double2(0.0, 0.0);
+                tile[64 + lane] = make_double2(0.0, 0.0);
             }
         }
+    }
 }
 
 // row-major symmetric P -> lower tiles in the factor's tile layout; one wavefront per tile, grid (tiles, B)
@@ -332,7 +452,8 @@ void launch_pack_p(hipStream_t st, int B, int n, const double* P, int ldp, long 
 void launch_gram_l2(hipStream_t st, int B, int m, int n, const double* A, int lda, const double* w, const GramL2& g,
                     double* P, int ldp, long long p_stride, const int* active, double* Ppk, long long ppk_stride,
                     int nchp, long long a_stride) {
-    const int nt = (n + GT - 1) / GT;
+    // tile rows: the last sub-tile row rides on the diagonal tiles when it would be a 64-tile row's only one
+    const int nt = gram_strip_folds(n) ? ((n + 15) / 16) / 4 : (n + GT - 1) / GT;
     const int ntile = nt * (nt + 1) / 2;
     const bool dop = g.s && g.dop_size > 0;
 #define HIPDRT_GRAM(D, R) hipLaunchKernelGGL((gram_kernel<D, R>), dim3(ntile, B), dim3(256), 0, st, m, n, A, lda, w, g, P, ldp, \

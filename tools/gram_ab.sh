@@ -1,9 +1,11 @@
 # per-kernel times (rocprofv3 --kernel-trace --stats, one batch in flight) of the working library and of variant libraries:
 #   bash tools/gram_ab.sh <tag> [variant.so ...]  -> gpurun_out/<tag>_kernels.txt
+# BENCH_FLAGS="--no-scale-reference --no-single-caller" leaves the one-plan, one-range legs alone in the trace: every launch a
+# full batch with nothing beside it (the map and the one-caller leg run ranges side by side, whose kernels overlap)
 cd /tmp; export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT; O=gpurun_out; T=${1:-gram_ab}; shift; mkdir -p $O; : > $O/${T}_kernels.txt
 one() {
   rm -rf $O/prof_$T
-  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$T -- python3 bench.py --full --inflight 1 --steps ${STEPS:-2} --warmup ${WARM:-1} --no-cpu-baseline --no-other-configs --no-matrix-build > $O/prof_${T}.log 2>&1
+  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$T -- python3 bench.py --full --inflight 1 --steps ${STEPS:-2} --warmup ${WARM:-1} --no-cpu-baseline --no-other-configs --no-matrix-build ${BENCH_FLAGS:-} > $O/prof_${T}.log 2>&1
   echo "== $1" >> $O/${T}_kernels.txt
   python3 - $O/prof_$T/*/*kernel_stats.csv >> $O/${T}_kernels.txt <<'PY'
 import csv, sys
