@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("HIPDRT_LIB", os.path.join(_HERE, "libhipdrt.so"))
 MODE_INTERP, MODE_TRAPZ = 0, 1
 RESPONSE_POT, RESPONSE_EXPDECAY = 0, 1
 QP_OPTIMAL, QP_MAXITER, QP_SINGULAR_LATE, QP_SINGULAR, QP_ABORTED = 0, 1, 2, -1, -2
+PREDICT_NOT_PD = -3          # HIPDRT_PREDICT_NOT_PD: the band of a spectrum whose P is not positive definite
 
 
 class HipDrtError(RuntimeError):
@@ -127,6 +128,13 @@ SIGNATURES = {
     "hipdrt_debug_kk_stats": [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(KkOpts), _dp, _ip, _dp, _ip, _ip],
     "hipdrt_default_kk_opts": [C.POINTER(KkOpts)],
     "hipdrt_plan_kk_screen": [_vp, C.POINTER(KkOpts), C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _ip, _ip],
+    "hipdrt_func_eval_matrix": [_vp, _dp, C.c_int, _dp, C.c_int, C.c_double, C.c_int, _dp],
+    "hipdrt_plan_set_tau_basis": [_vp, _dp, C.c_int, C.c_double],
+    "hipdrt_plan_predict_drt": [_vp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _dp, _dp, _dp, _ip],
+    "hipdrt_plan_predict_z": [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _ip],
+    "hipdrt_plan_predict_resistances": [_vp, _dp, _dp, _dp, C.c_int],
+    "hipdrt_debug_last_predict_ms": [_vp, C.POINTER(C.c_float)],
+    "hipdrt_debug_apply_rows": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp],
     "hipdrt_comm_unique_id": [C.c_char_p],
     "hipdrt_comm_create": [C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(_vp)],
     "hipdrt_comm_destroy": [_vp],
@@ -612,6 +620,35 @@ class Context:
                                                _pi(out["status"])))
         return out
 
+    def func_eval_matrix(self, basis_grid, eval_grid, epsilon, order=0):
+        """hipdrt_func_eval_matrix: E[i, j] = phi^(order)(eval_i - basis_j; epsilon) of the gaussian basis, orders 0-2, on the
+        device (natural-log grids) -> (len(eval_grid), len(basis_grid))"""
+        basis_grid, eval_grid = _f64(basis_grid).ravel(), _f64(eval_grid).ravel()
+        out = np.empty((eval_grid.size, basis_grid.size))
+        _check(self._lib.hipdrt_func_eval_matrix(self._h, _p(basis_grid), basis_grid.size, _p(eval_grid), eval_grid.size,
+                                                 float(epsilon), int(order), _p(out)))
+        return out
+
+    def debug_apply_rows(self, X, E, col_offset=0, scale=None):
+        """tests: the row-application kernel of the predictions on host arrays (hipdrt_debug_apply_rows, include/hipdrt_debug.h):
+        out[b, i] = scale[b] * sum_j E[i, j] X[b, col_offset + j]; X (B, ldx), E (r, K).  Raises when the kernel wrote outside
+        its B x r block of the padded device output."""
+        X, E = _f64(X), _f64(E)
+        B, ldx = X.shape
+        r, K = E.shape
+        sc = None if scale is None else _f64(scale)
+        if sc is not None and sc.shape != (B,):
+            raise ValueError("scale must have shape (B,)")
+        out = np.empty((B, r))
+        _check(self._lib.hipdrt_debug_apply_rows(self._h, B, K, ldx, int(col_offset), _p(X), r, _p(E), _p(sc), _p(out)))
+        return out
+
+    def debug_last_predict_ms(self):
+        """tools: kernel time in ms of the last predict_drt / predict_z of a plan of this context -> (mean or impedance, with band)"""
+        ms = (C.c_float * 2)()
+        _check(self._lib.hipdrt_debug_last_predict_ms(self._h, ms))
+        return float(ms[0]), float(ms[1])
+
     def debug_pack_p(self, P, n=None):
         """tests: launch_pack_p on row-major symmetric P [B][n][ldp] -> Ppk [B][nchp^2 * 256]; slots the kernel does not write
         come back as NaN (hipdrt_debug_pack_p, include/hipdrt_debug.h)"""
@@ -795,6 +832,43 @@ class Plan:
             out["residuals"] = er + 1j * ei
         return out
 
+    def set_tau_basis(self, ln_basis_tau, epsilon):
+        """prepared plans: the tau basis the DRT block stands on (hipdrt_plan_set_tau_basis), needed by predict_drt"""
+        ln_tau = _f64(ln_basis_tau)
+        _check(self._lib.hipdrt_plan_set_tau_basis(self._h, _p(ln_tau), ln_tau.size, float(epsilon)))
+
+    def predict_drt(self, ln_tau_eval, order=0, sign=1, normalize=0, n_sigma=None):
+        """hipdrt_plan_predict_drt for the fitted batch: mu (B, neval) = scale_b E x_b on the device; normalize 0 / 1 (by R_p) /
+        2 (by absolute R_p); n_sigma = (s_lo, s_hi) adds the band.  Returns (mu, lo, hi, status) with lo = hi = None without
+        n_sigma; status (B,): the fit's status, or PREDICT_NOT_PD."""
+        ev = _f64(ln_tau_eval).ravel()
+        B = self.B
+        mu = np.empty((B, ev.size))
+        lo, hi = (np.empty((B, ev.size)), np.empty((B, ev.size))) if n_sigma is not None else (None, None)
+        s_lo, s_hi = (0.0, 0.0) if n_sigma is None else (float(n_sigma[0]), float(n_sigma[1]))
+        status = np.empty(B, dtype=np.int32)
+        _check(self._lib.hipdrt_plan_predict_drt(self._h, _p(ev), ev.size, int(order), int(sign), int(normalize), s_lo, s_hi,
+                                                 _p(mu), _p(lo), _p(hi), _pi(status)))
+        return mu, lo, hi, status
+
+    def predict_z(self, frequencies, include_drt=True, include_ohmic=True, include_inductance=True):
+        """hipdrt_plan_predict_z: complex (B, nf) impedance of the fitted batch at any frequencies, and the status (B,)"""
+        f = _f64(frequencies).ravel()
+        B = self.B
+        zr, zi = np.empty((B, f.size)), np.empty((B, f.size))
+        status = np.empty(B, dtype=np.int32)
+        mask = int(bool(include_drt)) | (int(bool(include_ohmic)) << 1) | (int(bool(include_inductance)) << 2)
+        _check(self._lib.hipdrt_plan_predict_z(self._h, _p(f), f.size, mask, _p(zr), _p(zi), _pi(status)))
+        return zr + 1j * zi, status
+
+    def predict_resistances(self, absolute=False, r_p_only=False):
+        """hipdrt_plan_predict_resistances: (r_p, r_inf, r_tot), each (B,); r_p_only (prepared plans): (r_p, None, None)"""
+        B = self.B
+        r_p = np.empty(B)
+        r_inf, r_tot = (None, None) if r_p_only else (np.empty(B), np.empty(B))
+        _check(self._lib.hipdrt_plan_predict_resistances(self._h, _p(r_p), _p(r_inf), _p(r_tot), int(bool(absolute))))
+        return r_p, r_inf, r_tot
+
     def set_init_h(self, h_init):
         h = None if h_init is None else _f64(h_init)
         _check(self._lib.hipdrt_plan_set_init_h(self._h, _p(h)))
@@ -935,7 +1009,7 @@ class PreparedPlan(Plan):
         shapes = {"m0": (self.n, self.n), "m1": (self.n, self.n), "m2": (self.n, self.n), "vmm": (self.m, self.m),
                   "h": (self.n,), "est_weights": (B, self.m), "rv": (B, self.m), "xmx": (B, 3), "dop_rho": (B, 3),
                   "dop_xmx": (B, 3), "hist_dop_rho": (int(self.opts.max_iter), 3), "outlier_t": (B, self.m),
-                  "weight_factors": (B, 2),
+                  "weight_factors": (B, 2), "x": (B, self.n),
                   "rzm": (B, self.m, self.n) if self.rm_batched else (self.m, self.n)}
         out = np.empty(shapes[which])
         _check(self._lib.hipdrt_plan_get(self._h, which.encode(), _p(out), out.size))

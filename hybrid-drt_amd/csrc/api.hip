@@ -51,6 +51,10 @@ struct hipdrt_plan {
     DevBuf active, outer_iters, fit_status, qp_iters_total, qp_status, qp_iters, n_active, pcost;
     DevBuf premv;          // [3][capacity][m]: hyper-parameter step of few, large fits (hyper.hip, premv_kernel)
     DevBuf L, Ptmp, qpstate, Ppk, order, vmm_base, gsync;
+    // tau basis of a prepared plan (hipdrt_plan_set_tau_basis): ln(basis_tau) [basis_nb] and its epsilon, for hipdrt_plan_predict_drt
+    DevBuf basis_ln_tau;
+    int basis_nb = 0;
+    double basis_eps = 0;
     int toep_maxd = -1;     // reach of the Toeplitz penalty blocks in grid points (plan_toep_reach), -1 = not determined
     int spec_zero = 0;      // the special-parameter rows / columns of the penalty matrices are zero outside the special block
     int qp_G = 0;           // workgroups per QP when the plan is full (qp_group_size at its capacity): 0 = the batch kernel
@@ -2012,10 +2016,10 @@ int hipdrt_plan_get_p_matrix(hipdrt_plan* p, int b, double* out) try {
     return copy_strided(out, p->Ptmp.d(), n, n, p->ldp, st);
 } HIPDRT_CATCH
 
-// out[b][i] = rows_i' P_b^-1 rows_i * cs_b^2 for the fitted batch; rows[nrow][ncol] sits at columns col_offset.. of the
-// unknown vector (zero elsewhere)
-static int plan_quadratic_forms(hipdrt_plan* p, const double* basis_eval, int neval, int ncol, int col_offset, double* out,
-                                int* status) {
+// rows_dev[neval][ncol] in device memory (it sits at columns col_offset.. of the unknown vector, zero elsewhere) ->
+// dout[B][nex * 16] = rows_i' P_b^-1 rows_i (not yet scaled by cs_b^2), dstat[B]
+static int plan_quadratic_forms_dev(hipdrt_plan* p, const double* rows_dev, int neval, int ncol, int col_offset, DevBuf& dout,
+                                    DevBuf& dstat) {
     HIPDRT_REQUIRE(p->B > 0, "no fitted batch in the plan");
     HIPDRT_REQUIRE(neval >= 1, "neval >= 1");
     HIPDRT_REQUIRE(p->n <= 4096, "posterior variance: n <= 4096");
@@ -2029,10 +2033,9 @@ static int plan_quadratic_forms(hipdrt_plan* p, const double* basis_eval, int ne
                    (long long)qp_ppk_doubles(n), nchp, p->rm_stride);
     LAUNCH_OK();
     // evaluation rows -> packed tiles, shifted past the special-parameter slots
-    DevBuf dbe, bex, scratch, dout, dstat;
-    TRY(upload(dbe, basis_eval, (size_t)neval * ncol * sizeof(double), st));
+    DevBuf bex, scratch;
     HIPDRT_CHECK(bex.alloc((size_t)nex * nchp * 256 * sizeof(double)));
-    launch_pack_rows(st, neval, ncol, col_offset, dbe.d(), ncol, nex, bex.d(), nchp);
+    launch_pack_rows(st, neval, ncol, col_offset, rows_dev, ncol, nex, bex.d(), nchp);
     LAUNCH_OK();
     const int chunk = B < 256 ? B : 256;
     const size_t lsz = dist_var_scratch_doubles(n, nex);
@@ -2045,6 +2048,21 @@ static int plan_quadratic_forms(hipdrt_plan* p, const double* basis_eval, int ne
                             nex, scratch.d(), (long long)lsz, dout.d() + (size_t)b0 * nex * 16, (long long)nex * 16,
                             dstat.i() + b0));
     }
+    HIPDRT_CHECK(hipStreamSynchronize(st));      // bex and scratch are released on return
+    return HIPDRT_OK;
+}
+
+// out[b][i] = rows_i' P_b^-1 rows_i * cs_b^2 for the fitted batch, host rows in, host results out
+static int plan_quadratic_forms(hipdrt_plan* p, const double* basis_eval, int neval, int ncol, int col_offset, double* out,
+                                int* status) {
+    HIPDRT_REQUIRE(p->B > 0, "no fitted batch in the plan");
+    HIPDRT_REQUIRE(neval >= 1, "neval >= 1");
+    HIPDRT_CHECK(hipSetDevice(p->ctx->device)); (void)hipGetLastError();
+    hipStream_t st = p->ctx->stream;
+    const int B = p->B, nex = (neval + 15) / 16;
+    DevBuf dbe, dout, dstat;
+    TRY(upload(dbe, basis_eval, (size_t)neval * ncol * sizeof(double), st));
+    TRY(plan_quadratic_forms_dev(p, dbe.d(), neval, ncol, col_offset, dout, dstat));
     std::vector<double> hv((size_t)B * nex * 16), cs(B);
     std::vector<int> hs(B);
     HIPDRT_CHECK(hipMemcpyAsync(hv.data(), dout.p, hv.size() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -2129,6 +2147,244 @@ int hipdrt_plan_param_var(hipdrt_plan* p, double* out, int* status) try {
     std::vector<double> eye((size_t)n * n, 0.0);
     for (int i = 0; i < n; ++i) eye[(size_t)i * n + i] = 1.0;
     return plan_quadratic_forms(p, eye.data(), n, n, 0, out, status);
+} HIPDRT_CATCH
+
+// ---- model evaluation for the fitted batch (csrc/predict.hip) ----------------------------------------------------------------
+static int func_eval_dev(hipStream_t st, const double* basis_dev, int nb, const double* ev_dev, int ne, double eps, int order,
+                         double fac, double* out_dev, int ld) {
+    // the two constants as Python forms them in basis.get_basis_func_derivative: -2 * epsilon ** 2 and 4 * epsilon ** 4
+    const double c1 = -2.0 * std::pow(eps, 2.0), c2 = 4.0 * std::pow(eps, 4.0);
+    launch_func_eval(st, basis_dev, nb, ev_dev, ne, eps, order, c1, c2, fac, out_dev, ld);
+    LAUNCH_OK();
+    return HIPDRT_OK;
+}
+
+int hipdrt_func_eval_matrix(hipdrt_ctx* ctx, const double* basis_grid, int nb, const double* eval_grid, int ne, double epsilon,
+                            int order, double* out) try {
+    HIPDRT_REQUIRE(ctx && basis_grid && eval_grid && out, "NULL pointer");
+    HIPDRT_REQUIRE(nb >= 1 && ne >= 1, "nb, ne >= 1");
+    HIPDRT_REQUIRE(order >= 0 && order <= 2, "order must be 0, 1 or 2");
+    HIPDRT_CHECK(hipSetDevice(ctx->device)); (void)hipGetLastError();
+    hipStream_t st = ctx->stream;
+    DevBuf db, de, dout;
+    TRY(upload(db, basis_grid, (size_t)nb * sizeof(double), st));
+    TRY(upload(de, eval_grid, (size_t)ne * sizeof(double), st));
+    HIPDRT_CHECK(dout.alloc((size_t)ne * nb * sizeof(double)));
+    TRY(func_eval_dev(st, db.d(), nb, de.d(), ne, epsilon, order, 1.0, dout.d(), nb));
+    HIPDRT_CHECK(hipMemcpyAsync(out, dout.p, (size_t)ne * nb * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+int hipdrt_plan_set_tau_basis(hipdrt_plan* p, const double* ln_basis_tau, int nb, double epsilon) try {
+    HIPDRT_REQUIRE(p && ln_basis_tau, "NULL pointer");
+    HIPDRT_REQUIRE(p->prepared, "a plan made by hipdrt_plan_create holds its tau basis already");
+    const int width = p->n - p->ns;
+    HIPDRT_REQUIRE(nb >= 1 && (width == nb || width == 2 * nb), "the DRT block must hold one or two copies of the basis");
+    HIPDRT_REQUIRE(epsilon > 0.0 && std::isfinite(epsilon), "epsilon > 0");
+    HIPDRT_CHECK(hipSetDevice(p->ctx->device)); (void)hipGetLastError();
+    TRY(upload(p->basis_ln_tau, ln_basis_tau, (size_t)nb * sizeof(double), p->ctx->stream));
+    HIPDRT_CHECK(hipStreamSynchronize(p->ctx->stream));
+    p->basis_nb = nb; p->basis_eps = epsilon;
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+// kernel time of the last prediction on a context (hipdrt_debug_last_predict_ms): HIP events around the launches
+struct PredictTimer {
+    hipdrt_ctx* ctx; hipStream_t st; hipEvent_t e[3] = {nullptr, nullptr, nullptr}; int n = 0;
+    PredictTimer(hipdrt_ctx* c, hipStream_t s) : ctx(c), st(s) { mark(); }
+    void mark() { if (n < 3 && hipEventCreate(&e[n]) == hipSuccess) { (void)hipEventRecord(e[n], st); ++n; } }
+    // (destroyed after the stream has been synchronised) [0] up to the second mark, [1] up to the last one
+    ~PredictTimer() {
+        float a = 0.f, b = 0.f;
+        if (n >= 2 && hipEventElapsedTime(&a, e[0], e[1]) == hipSuccess && hipEventElapsedTime(&b, e[0], e[n - 1]) == hipSuccess) {
+            ctx->predict_ms[0] = a; ctx->predict_ms[1] = b;
+        }
+        for (int i = 0; i < n; ++i) (void)hipEventDestroy(e[i]);
+        (void)hipGetLastError();
+    }
+};
+
+// the tau basis a prediction evaluates: the plan's own grid, or what hipdrt_plan_set_tau_basis gave a prepared plan
+struct PredictBasis { const double* ln_tau; int nb, copies; double eps; };
+static int predict_basis(const hipdrt_plan* p, PredictBasis& pb) {
+    HIPDRT_REQUIRE(p->B >= 1 && p->prepped, "no fitted batch in the plan");
+    if (p->prepared) {
+        HIPDRT_REQUIRE(p->basis_nb > 0, "a prepared plan needs hipdrt_plan_set_tau_basis before a DRT prediction");
+        pb = {p->basis_ln_tau.d(), p->basis_nb, (p->n - p->ns) / p->basis_nb, p->basis_eps};
+    } else {
+        pb = {p->ln_tau.d(), p->ntau, 1, p->eps};
+    }
+    return HIPDRT_OK;
+}
+
+int hipdrt_plan_predict_drt(hipdrt_plan* p, const double* ln_tau_eval, int neval, int order, int sign, int normalize, double s_lo,
+                            double s_hi, double* mu, double* lo, double* hi, int* status) try {
+    HIPDRT_REQUIRE(p && ln_tau_eval && mu, "NULL pointer");
+    PredictBasis pb;
+    TRY(predict_basis(p, pb));
+    HIPDRT_REQUIRE(neval >= 1, "neval >= 1");
+    HIPDRT_REQUIRE(order >= 0 && order <= 2, "order must be 0, 1 or 2");
+    HIPDRT_REQUIRE(sign == 1 || (pb.copies == 2 && (sign == 0 || sign == -1)),
+                   "sign must be 1, or 1, -1 or 0 when the DRT block holds a positive and a negative copy");
+    HIPDRT_REQUIRE(normalize >= 0 && normalize <= 2, "normalize must be 0, 1 (by R_p) or 2 (by absolute R_p)");
+    const bool band = lo || hi;
+    HIPDRT_REQUIRE(!band || (std::isfinite(s_lo) && std::isfinite(s_hi)), "s_lo and s_hi must be finite");
+    HIPDRT_CHECK(hipSetDevice(p->ctx->device)); (void)hipGetLastError();
+    hipStream_t st = p->ctx->stream;
+    const int B = p->B, n = p->n, ns = p->ns, width = n - ns, nb = pb.nb;
+    // E[neval][width]: the signed evaluation rows over the whole DRT block (+E | 0), (0 | -E) or (+E | -E)
+    DevBuf dev, dE, dsum, dabs, dnorm, dscale, dmu, dlo, dhi, dvar, dvstat;
+    TRY(upload(dev, ln_tau_eval, (size_t)neval * sizeof(double), st));
+    HIPDRT_CHECK(dE.alloc((size_t)neval * width * sizeof(double)));
+    HIPDRT_CHECK(dmu.alloc((size_t)B * neval * sizeof(double)));
+    PredictTimer tm(p->ctx, st);
+    if (pb.copies == 2 && sign != 0) HIPDRT_CHECK(hipMemsetAsync(dE.p, 0, dE.bytes, st));
+    if (sign != -1) TRY(func_eval_dev(st, pb.ln_tau, nb, dev.d(), neval, pb.eps, order, 1.0, dE.d(), width));
+    if (pb.copies == 2 && sign != 1) TRY(func_eval_dev(st, pb.ln_tau, nb, dev.d(), neval, pb.eps, order, -1.0, dE.d() + nb, width));
+    const double* scale = p->coef_scale.d();
+    if (normalize) {
+        HIPDRT_CHECK(dsum.alloc((size_t)B * sizeof(double))); HIPDRT_CHECK(dabs.alloc((size_t)B * sizeof(double)));
+        HIPDRT_CHECK(dnorm.alloc((size_t)B * sizeof(double))); HIPDRT_CHECK(dscale.alloc((size_t)B * sizeof(double)));
+        launch_drt_sums(st, B, p->x.d(), n, ns, nb, pb.copies, sign, dsum.d(), dabs.d());
+        launch_drt_scalars(st, B, dsum.d(), dabs.d(), p->coef_scale.d(), 1.7724538509055159 / pb.eps, 1, normalize == 2,
+                           p->x.d(), n, -1, nullptr, nullptr, nullptr, dnorm.d(), dscale.d());
+        LAUNCH_OK();
+        scale = dscale.d();
+    }
+    launch_apply_rows(st, B, width, p->x.d(), n, ns, neval, dE.d(), width, scale, p->fit_status.i(), dmu.d(), neval);
+    LAUNCH_OK();
+    tm.mark();
+    std::vector<int> hs(B), hv;
+    if (band) {
+        // sigma^2 = diag(E inv(P) E') from the variance path, fed the evaluation rows where they are
+        TRY(plan_quadratic_forms_dev(p, dE.d(), neval, width, ns, dvar, dvstat));
+        if (lo) HIPDRT_CHECK(dlo.alloc((size_t)B * neval * sizeof(double)));
+        if (hi) HIPDRT_CHECK(dhi.alloc((size_t)B * neval * sizeof(double)));
+        launch_drt_band(st, B, neval, dmu.d(), dvar.d(), (long long)((neval + 15) / 16) * 16, p->coef_scale.d(),
+                        normalize ? dnorm.d() : nullptr, s_lo, s_hi, dvstat.i(), p->fit_status.i(), dlo.d(), dhi.d());
+        LAUNCH_OK();
+        tm.mark();
+        if (lo) HIPDRT_CHECK(hipMemcpyAsync(lo, dlo.p, dlo.bytes, hipMemcpyDeviceToHost, st));
+        if (hi) HIPDRT_CHECK(hipMemcpyAsync(hi, dhi.p, dhi.bytes, hipMemcpyDeviceToHost, st));
+        hv.resize(B);
+        HIPDRT_CHECK(hipMemcpyAsync(hv.data(), dvstat.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+    }
+    HIPDRT_CHECK(hipMemcpyAsync(mu, dmu.p, dmu.bytes, hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipMemcpyAsync(hs.data(), p->fit_status.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    if (status)
+        for (int b = 0; b < B; ++b) status[b] = (hs[b] >= 0 && band && hv[b] != 0) ? HIPDRT_PREDICT_NOT_PD : hs[b];
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+int hipdrt_plan_predict_z(hipdrt_plan* p, const double* freq, int nf, int include_mask, double* z_re, double* z_im,
+                          int* status) try {
+    HIPDRT_REQUIRE(p && freq && z_re && z_im, "NULL pointer");
+    if (p->prepared) {
+        set_error("not supported: impedance prediction is built for plain EIS plans (hipdrt_plan_create); a prepared plan holds "
+                  "neither lookup tables nor a tau grid");
+        return HIPDRT_E_UNSUPPORTED;
+    }
+    HIPDRT_REQUIRE(p->B >= 1 && p->prepped, "no fitted batch in the plan");
+    HIPDRT_REQUIRE(nf >= 1, "nf >= 1");
+    HIPDRT_REQUIRE(include_mask >= 0 && include_mask <= 7, "include_mask: bit 0 DRT, bit 1 ohmic, bit 2 inductance");
+    for (int i = 0; i < nf; ++i) HIPDRT_REQUIRE(freq[i] > 0.0 && std::isfinite(freq[i]), "frequencies must be positive and finite");
+    HIPDRT_CHECK(hipSetDevice(p->ctx->device)); (void)hipGetLastError();
+    hipStream_t st = p->ctx->stream;
+    const int B = p->B, n = p->n, ntau = p->ntau;
+    DevBuf dfreq, dA, cr, dy, dzr, dzi;
+    TRY(upload(dfreq, freq, (size_t)nf * sizeof(double), st));
+    HIPDRT_CHECK(dzr.alloc((size_t)B * nf * sizeof(double))); HIPDRT_CHECK(dzi.alloc((size_t)B * nf * sizeof(double)));
+    if (include_mask & 1) {
+        HIPDRT_CHECK(dA.alloc((size_t)2 * nf * ntau * sizeof(double)));
+        HIPDRT_CHECK(cr.alloc(((size_t)nf + 2 * (size_t)(nf + ntau)) * sizeof(double)));
+        HIPDRT_CHECK(dy.alloc((size_t)B * 2 * nf * sizeof(double)));
+    }
+    PredictTimer tm(p->ctx, st);
+    if (include_mask & 1) {
+        // [A'; A''] at the requested frequencies from the plan's own tables, tau grid and integration mode (no Toeplitz shortcut:
+        // every entry is evaluated where it stands), then both parts as the two row blocks of one product
+        launch_impedance_matrix(st, 1, 0, dfreq.d(), nf, p->tau.d(), ntau, p->mode, 0, p->eps, p->ngrid, p->lut6.d(), p->ny,
+                                dA.d(), dA.d() + (size_t)nf * ntau, cr.d());
+        LAUNCH_OK();
+        launch_apply_rows(st, B, ntau, p->x.d(), n, p->ns, 2 * nf, dA.d(), ntau, p->coef_scale.d(), nullptr, dy.d(), 2 * nf);
+        LAUNCH_OK();
+    }
+    launch_z_assemble(st, B, nf, dy.d(), p->x.d(), n, p->idx_rinf, p->idx_induc, p->coef_scale.d(), p->opts.inductance_scale,
+                      dfreq.d(), include_mask, p->fit_status.i(), dzr.d(), dzi.d());
+    LAUNCH_OK();
+    tm.mark();
+    HIPDRT_CHECK(hipMemcpyAsync(z_re, dzr.p, dzr.bytes, hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipMemcpyAsync(z_im, dzi.p, dzi.bytes, hipMemcpyDeviceToHost, st));
+    if (status) HIPDRT_CHECK(hipMemcpyAsync(status, p->fit_status.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+int hipdrt_plan_predict_resistances(hipdrt_plan* p, double* r_p, double* r_inf, double* r_tot, int abs_norm) try {
+    HIPDRT_REQUIRE(p, "plan is NULL");
+    PredictBasis pb;
+    TRY(predict_basis(p, pb));
+    if (p->prepared && (r_inf || r_tot)) {
+        set_error("not supported: a prepared plan does not know which special parameter is R_inf (pass NULL for r_inf and r_tot)");
+        return HIPDRT_E_UNSUPPORTED;
+    }
+    HIPDRT_CHECK(hipSetDevice(p->ctx->device)); (void)hipGetLastError();
+    hipStream_t st = p->ctx->stream;
+    const int B = p->B, n = p->n;
+    DevBuf dsum, dabs, drp, dri, drt;
+    for (DevBuf* d : {&dsum, &dabs, &drp, &dri, &drt}) HIPDRT_CHECK(d->alloc((size_t)B * sizeof(double)));
+    // predict_r_p's default sign: the net distribution of a two-copy block, else the block itself
+    launch_drt_sums(st, B, p->x.d(), n, p->ns, pb.nb, pb.copies, pb.copies == 2 ? 0 : 1, dsum.d(), dabs.d());
+    launch_drt_scalars(st, B, dsum.d(), dabs.d(), p->coef_scale.d(), 1.7724538509055159 / pb.eps, 0, abs_norm != 0, p->x.d(), n,
+                       p->idx_rinf, drp.d(), dri.d(), drt.d(), nullptr, nullptr);
+    LAUNCH_OK();
+    if (r_p) HIPDRT_CHECK(hipMemcpyAsync(r_p, drp.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (r_inf) HIPDRT_CHECK(hipMemcpyAsync(r_inf, dri.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (r_tot) HIPDRT_CHECK(hipMemcpyAsync(r_tot, drt.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+// test hook (include/hipdrt_debug.h): apply_rows_kernel as it is, on host arrays.  The device output carries one extra row and
+// five extra columns filled with a marker; a marker that changed means the kernel wrote outside its B x r block.
+int hipdrt_debug_apply_rows(hipdrt_ctx* ctx, int B, int K, int ldx, int col_offset, const double* X, int r, const double* E,
+                            const double* scale, double* out) try {
+    HIPDRT_REQUIRE(ctx && X && E && out, "NULL pointer");
+    HIPDRT_REQUIRE(B >= 1 && K >= 1 && r >= 1 && col_offset >= 0, "B, K, r >= 1, col_offset >= 0");
+    HIPDRT_REQUIRE(ldx >= col_offset + K, "ldx >= col_offset + K");
+    HIPDRT_CHECK(hipSetDevice(ctx->device)); (void)hipGetLastError();
+    hipStream_t st = ctx->stream;
+    const int ldo = r + 5, rows = B + 1;
+    const double marker = -7.0e77;
+    DevBuf dx, de, ds, dout;
+    TRY(upload(dx, X, (size_t)B * ldx * sizeof(double), st));
+    TRY(upload(de, E, (size_t)r * K * sizeof(double), st));
+    if (scale) TRY(upload(ds, scale, (size_t)B * sizeof(double), st));
+    std::vector<double> ho((size_t)rows * ldo, marker);
+    TRY(upload(dout, ho.data(), ho.size() * sizeof(double), st));
+    launch_apply_rows(st, B, K, dx.d(), ldx, col_offset, r, de.d(), K, scale ? ds.d() : nullptr, nullptr, dout.d(), ldo);
+    LAUNCH_OK();
+    HIPDRT_CHECK(hipMemcpyAsync(ho.data(), dout.p, ho.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    for (int b = 0; b < rows; ++b)
+        for (int i = 0; i < ldo; ++i) {
+            const double v = ho[(size_t)b * ldo + i];
+            if (b < B && i < r) out[(size_t)b * r + i] = v;
+            else if (!(v == marker)) {
+                set_error("apply_rows wrote outside its B x r block (row " + std::to_string(b) + ", column " + std::to_string(i) + ")");
+                return HIPDRT_E_NUMERIC;
+            }
+        }
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+// tools hook: kernel time of the last hipdrt_plan_predict_drt or hipdrt_plan_predict_z on this context
+int hipdrt_debug_last_predict_ms(hipdrt_ctx* ctx, float* ms) try {
+    HIPDRT_REQUIRE(ctx && ms, "NULL pointer");
+    ms[0] = ctx->predict_ms[0]; ms[1] = ctx->predict_ms[1];
+    return HIPDRT_OK;
 } HIPDRT_CATCH
 
 // history buffers for `rows` outer iterations (grown when a later call asks for more than the first one did)

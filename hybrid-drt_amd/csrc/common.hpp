@@ -98,6 +98,8 @@ struct hipdrt_ctx {
     // hipdrt_debug_qp_waves (tests, tools): wavefronts per workgroup of this context's batch coneqp launches at n <= 528 --
     // 4 = the fat form, 8 = eight wavefronts, -1 = the library chooses.  Initialised from HIPDRT_QP_WAVES when the context is made.
     int qp_waves = -1;
+    // hipdrt_debug_last_predict_ms (tools): kernel time of the last prediction, ms -- [0] up to the mean / the impedance, [1] band included
+    float predict_ms[2] = {0.f, 0.f};
 };
 
 // ---- launchers implemented in the .hip files (all asynchronous on `st`) ---------------------------------
@@ -262,6 +264,27 @@ struct KkArgs {
 size_t kk_lds_bytes(int nf, int n, int stage_a);
 // st != null: both stages on the plan's state; null: stage B alone on a.in_re / a.in_im.  HIPDRT_E_INVALID when LDS cannot hold the shape.
 int launch_kk(hipStream_t s, const FitState* st, KkArgs a, int B);
+
+// matrices.hip: out[i * ld + j] = fac * phi^(order)(ev_i - basis_j), c1 = -2 eps^2, c2 = 4 eps^4 (formed by the caller)
+void launch_func_eval(hipStream_t st, const double* basis, int nb, const double* ev, int ne, double eps, int order, double c1,
+                      double c2, double fac, double* out, int ld);
+
+// predict.hip: model evaluation for the fitted batch (all pointers device memory)
+// out[b * ldo + i] = scale[b] * sum_j E[i * lde + j] * X[b * ldx + col_offset + j]; scale may be null (1), fit_status may be null
+// (otherwise rows with a negative status become NaN)
+void launch_apply_rows(hipStream_t st, int B, int K, const double* X, long long ldx, int col_offset, int r, const double* E,
+                       int lde, const double* scale, const int* fit_status, double* out, long long ldo);
+void launch_drt_sums(hipStream_t st, int B, const double* X, long long ldx, int col_offset, int nb, int copies, int sign,
+                     double* sum_x, double* sum_abs);
+void launch_drt_scalars(hipStream_t st, int B, const double* sum_x, const double* sum_abs, const double* cs, double area,
+                        int normalize, int absolute, const double* X, long long ldx, int idx_rinf, double* r_p, double* r_inf,
+                        double* r_tot, double* norm, double* scale);
+void launch_drt_band(hipStream_t st, int B, int r, const double* mu, const double* var, long long ldv, const double* cs,
+                     const double* norm, double s_lo, double s_hi, const int* var_status, const int* fit_status, double* lo,
+                     double* hi);
+void launch_z_assemble(hipStream_t st, int B, int nf, const double* y, const double* X, long long ldx, int idx_rinf,
+                       int idx_induc, const double* cs, double inductance_scale, const double* freq, int mask,
+                       const int* fit_status, double* z_re, double* z_im);
 
 // qp.hip
 struct QpArgs {

@@ -809,4 +809,29 @@ void launch_nonuniform_gauss(hipStream_t st, const double* y, int n, const doubl
                        node_delta, weights, woff, radius, out);
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// basis.construct_func_eval_matrix (hybdrt/matrices/basis.py:488-514) with get_basis_func_derivative (218-228), gaussian basis:
+// out[i * ld + j] = fac * phi^(order)(e_i - b_j), evaluated in numpy's order of operations -- y = e - b, (eps y)^2, exp, then
+// ((-2 eps^2) y) phi or ((-2 eps^2) + (4 eps^4) y^2) phi with the two constants formed on the host as Python forms them.
+// ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void func_eval_kernel(const double* __restrict__ basis, int nb, const double* __restrict__ ev,
+                                                        int ne, double eps, int order, double c1, double c2, double fac,
+                                                        double* __restrict__ out, int ld) {
+    const int j = blockIdx.x * 64 + (threadIdx.x & 63), i = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (i >= ne || j >= nb) return;
+    const double y = ev[i] - basis[j];
+    const double ey = eps * y;
+    const double phi = exp(-(ey * ey));
+    double v = phi;
+    if (order == 1) v = (c1 * y) * phi;
+    else if (order == 2) v = (c1 + c2 * (y * y)) * phi;
+    out[(size_t)i * ld + j] = fac * v;
+}
+
+void launch_func_eval(hipStream_t st, const double* basis, int nb, const double* ev, int ne, double eps, int order, double c1,
+                      double c2, double fac, double* out, int ld) {
+    hipLaunchKernelGGL(func_eval_kernel, dim3((nb + 63) / 64, (ne + 3) / 4), dim3(256), 0, st, basis, nb, ev, ne, eps, order, c1,
+                       c2, fac, out, ld);
+}
+
 }  // namespace hipdrt

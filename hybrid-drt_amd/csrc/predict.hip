@@ -1,0 +1,220 @@
+// Model evaluation for a fitted batch (hybdrt/models/drt1d.py:2965-3061 predict_drt, 3209-3231 predict_drt_ci, 3500-3542
+// predict_z, 3552-3584 the resistances): every prediction is "rows of an evaluation matrix applied to each spectrum's x",
+//
+//     Y[b][i] = scale_b * sum_j E[i][j] * x[b][col_offset + j]            (a B x r x K product, x resident on the device)
+//
+// followed by a per-element epilogue (credible band, impedance assembly).  FP64 only; the contraction runs on
+// v_mfma_f64_16x16x4_f64.  hipdrt/models/predict.py is the same arithmetic in numpy.
+//
+// Layout.  A 256-thread workgroup (4 wavefronts) owns 32 spectra x 64 evaluation rows.  Per 64-wide slab of k it stages
+// x[32][64] and E[64][64] through LDS (both k-contiguous, leading dimension 68: the operand reads below then hit every bank
+// pair exactly twice per 64 lanes, the minimum for 8-byte words).  Wavefront w owns evaluation rows 16 w .. 16 w + 15 and two
+// accumulators (spectra 0-15 and 16-31), so the two MFMA chains of a wavefront are independent.  MFMA operands: A[l & 15][l >> 4] =
+// x (rows = spectra), B[l >> 4][l & 15] = E' (columns = evaluation rows); C/D: col = lane & 15, row = (lane >> 4) + 4 reg.
+//
+// Accumulation order.  Every output element has ONE accumulator and receives its k-blocks of four in ascending order, from k = 0,
+// whatever the batch size and wherever the spectrum sits in the batch or the tile (no split-K, no atomics; the MFMA's internal
+// order over its four k is a property of the instruction).  So a spectrum predicted alone and the same spectrum inside a batch
+// give the same bits.  Tails in B, r and K are staged as zeros; nothing outside the arrays is read, nothing outside
+// out[B][r] is written.  x + col_offset need not be 16-byte aligned: the slab is fetched with 8-byte loads.
+#include "common.hpp"
+
+namespace hipdrt {
+
+typedef double v4d __attribute__((ext_vector_type(4)));
+
+constexpr int PB = 32, PR = 64, PK = 64, PLD = 68;
+
+__global__ __launch_bounds__(256) void apply_rows_kernel(int B, int K, const double* __restrict__ X, long long ldx,
+                                                         int col_offset, int r, const double* __restrict__ E, int lde,
+                                                         const double* __restrict__ scale, const int* __restrict__ fit_status,
+                                                         double* __restrict__ out, long long ldo) {
+    __shared__ double sX[PB * PLD];
+    __shared__ double sE[PR * PLD];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int b0 = blockIdx.x * PB, i0 = blockIdx.y * PR;
+    const int srow = tid >> 4, skc = tid & 15;                  // staging map: 16 lanes along k (128 contiguous bytes per row)
+    const bool live = i0 + wv * 16 < r;                         // (a wavefront whose 16 evaluation rows are all padding only stages)
+    v4d acc0 = (v4d){0.0, 0.0, 0.0, 0.0}, acc1 = (v4d){0.0, 0.0, 0.0, 0.0};
+    // slab k0 + PK is fetched (global -> registers) while slab k0 is multiplied out of LDS; tails come in as zeros
+    double vx[(PB / 16) * (PK / 16)], ve[(PR / 16) * (PK / 16)];
+    auto fetch = [&](int k0) {
+#pragma unroll
+        for (int rr = 0; rr < PB / 16; ++rr) {
+            const int b = b0 + srow + 16 * rr;
+#pragma unroll
+            for (int j = 0; j < PK / 16; ++j) {
+                const int k = k0 + skc + 16 * j;
+                vx[rr * (PK / 16) + j] = (b < B && k < K) ? X[(size_t)b * ldx + col_offset + k] : 0.0;
+            }
+        }
+#pragma unroll
+        for (int rr = 0; rr < PR / 16; ++rr) {
+            const int i = i0 + srow + 16 * rr;
+#pragma unroll
+            for (int j = 0; j < PK / 16; ++j) {
+                const int k = k0 + skc + 16 * j;
+                ve[rr * (PK / 16) + j] = (i < r && k < K) ? E[(size_t)i * lde + k] : 0.0;
+            }
+        }
+    };
+    fetch(0);
+    for (int k0 = 0; k0 < K; k0 += PK) {
+        __syncthreads();                                        // previous slab fully consumed
+#pragma unroll
+        for (int rr = 0; rr < PB / 16; ++rr)
+#pragma unroll
+            for (int j = 0; j < PK / 16; ++j) sX[(srow + 16 * rr) * PLD + skc + 16 * j] = vx[rr * (PK / 16) + j];
+#pragma unroll
+        for (int rr = 0; rr < PR / 16; ++rr)
+#pragma unroll
+            for (int j = 0; j < PK / 16; ++j) sE[(srow + 16 * rr) * PLD + skc + 16 * j] = ve[rr * (PK / 16) + j];
+        __syncthreads();
+        if (k0 + PK < K) fetch(k0 + PK);
+        if (live) {
+            const int left = K - k0;
+            const int kend = left >= PK ? PK : (left + 3) & ~3;  // whole blocks of four; the zeros past K are staged above
+            for (int kk = 0; kk < kend; kk += 4) {
+                const int kr = kk + (lane >> 4);
+                const double a0 = sX[(lane & 15) * PLD + kr];
+                const double a1 = sX[(16 + (lane & 15)) * PLD + kr];
+                const double e = sE[(wv * 16 + (lane & 15)) * PLD + kr];
+                acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, e, acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, e, acc1, 0, 0, 0);
+            }
+        }
+    }
+    const int i = i0 + wv * 16 + (lane & 15);
+    if (!live || i >= r) return;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const v4d acc = h ? acc1 : acc0;
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            const int b = b0 + 16 * h + (lane >> 4) + 4 * reg;
+            if (b >= B) continue;
+            double v = acc[reg];
+            if (scale) v = scale[b] * v;
+            if (fit_status && fit_status[b] < 0) v = NAN;
+            out[(size_t)b * ldo + i] = v;
+        }
+    }
+}
+
+void launch_apply_rows(hipStream_t st, int B, int K, const double* X, long long ldx, int col_offset, int r, const double* E,
+                       int lde, const double* scale, const int* fit_status, double* out, long long ldo) {
+    hipLaunchKernelGGL(apply_rows_kernel, dim3((B + PB - 1) / PB, (r + PR - 1) / PR), dim3(256), 0, st, B, K, X, ldx, col_offset,
+                       r, E, lde, scale, fit_status, out, ldo);
+}
+
+// Signed coefficient sums of every spectrum's DRT block (get_drt_params, drt1d.py:2965-2987, inside predict_r_p, 3552-3571):
+// one wavefront per spectrum, a fixed lane-strided order and a fixed shuffle tree, so the sums do not depend on the batch either.
+// sum_x[b] = sum_j s_j, sum_abs[b] = sum_j |s_j| with s = x+ (sign 1), -x- (sign -1), x+ - x- (sign 0); copies = 1: s = x.
+__global__ __launch_bounds__(64) void drt_sums_kernel(int B, const double* __restrict__ X, long long ldx, int col_offset, int nb,
+                                                      int copies, int sign, double* __restrict__ sum_x,
+                                                      double* __restrict__ sum_abs) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const double* x = X + (size_t)b * ldx + col_offset;
+    double s = 0.0, a = 0.0;
+    for (int j = lane; j < nb; j += 64) {
+        double v;
+        if (copies == 1 || sign == 1) v = x[j];
+        else if (sign == -1) v = -x[nb + j];
+        else v = x[j] - x[nb + j];
+        s += v; a += fabs(v);
+    }
+    for (int o = 32; o > 0; o >>= 1) { s += __shfl_down(s, o); a += __shfl_down(a, o); }
+    if (lane == 0) { sum_x[b] = s; sum_abs[b] = a; }
+}
+
+void launch_drt_sums(hipStream_t st, int B, const double* X, long long ldx, int col_offset, int nb, int copies, int sign,
+                     double* sum_x, double* sum_abs) {
+    hipLaunchKernelGGL(drt_sums_kernel, dim3(B), dim3(64), 0, st, B, X, ldx, col_offset, nb, copies, sign, sum_x, sum_abs);
+}
+
+// Per-spectrum scalars from the sums: r_p = (sum * area) * cs (predict_r_p in data units), and the factor predict_drt applies to
+// E x: cs, or cs / r_p with normalize (get_drt_norm, drt1d.py:3020-3031; abs_norm takes sum |x|).  Any output may be null.
+__global__ void drt_scalars_kernel(int B, const double* __restrict__ sum_x, const double* __restrict__ sum_abs,
+                                   const double* __restrict__ cs, double area, int normalize, int absolute,
+                                   const double* __restrict__ X, long long ldx, int idx_rinf, double* __restrict__ r_p,
+                                   double* __restrict__ r_inf, double* __restrict__ r_tot, double* __restrict__ norm,
+                                   double* __restrict__ scale) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const double c = cs[b];
+    const double rp = ((absolute ? sum_abs[b] : sum_x[b]) * area) * c;
+    const double rp_signed = (sum_x[b] * area) * c;
+    const double ri = idx_rinf >= 0 ? X[(size_t)b * ldx + idx_rinf] * c : 0.0;
+    if (r_p) r_p[b] = rp;
+    if (r_inf) r_inf[b] = ri;
+    if (r_tot) r_tot[b] = ri + rp_signed;                      // predict_r_tot adds predict_r_p() with its defaults
+    if (norm) norm[b] = normalize ? rp : 1.0;
+    if (scale) scale[b] = normalize ? c / rp : c;
+}
+
+void launch_drt_scalars(hipStream_t st, int B, const double* sum_x, const double* sum_abs, const double* cs, double area,
+                        int normalize, int absolute, const double* X, long long ldx, int idx_rinf, double* r_p, double* r_inf,
+                        double* r_tot, double* norm, double* scale) {
+    hipLaunchKernelGGL(drt_scalars_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, sum_x, sum_abs, cs, area, normalize,
+                       absolute, X, ldx, idx_rinf, r_p, r_inf, r_tot, norm, scale);
+}
+
+// predict_drt_ci (drt1d.py:3209-3231): sigma = sqrt(diag(E cov E') / norm^2) with cov = inv(P) cs^2 (estimate_param_cov,
+// 4116-4138), lo = mu + s_lo sigma, hi = mu + s_hi sigma.  var[b][i] = e_i' inv(P_b) e_i comes from the variance kernel
+// (qp_resident.hpp: cov_kernel_resident); a P that is not positive definite (var_status != 0) or a failed fit gives NaN rows.
+__global__ void drt_band_kernel(int B, int r, const double* __restrict__ mu, const double* __restrict__ var, long long ldv,
+                                const double* __restrict__ cs, const double* __restrict__ norm, double s_lo, double s_hi,
+                                const int* __restrict__ var_status, const int* __restrict__ fit_status, double* __restrict__ lo,
+                                double* __restrict__ hi) {
+    const int i = blockIdx.y * blockDim.x + threadIdx.x, b = blockIdx.x;
+    if (i >= r) return;
+    const size_t o = (size_t)b * r + i;
+    double l = NAN, h = NAN;
+    if (var_status[b] == 0 && fit_status[b] >= 0) {
+        double v = var[(size_t)b * ldv + i] * (cs[b] * cs[b]);
+        if (norm) v = v / (norm[b] * norm[b]);
+        const double sg = sqrt(v), m = mu[o];
+        l = m + s_lo * sg;
+        h = m + s_hi * sg;
+    }
+    if (lo) lo[o] = l;
+    if (hi) hi[o] = h;
+}
+
+void launch_drt_band(hipStream_t st, int B, int r, const double* mu, const double* var, long long ldv, const double* cs,
+                     const double* norm, double s_lo, double s_hi, const int* var_status, const int* fit_status, double* lo,
+                     double* hi) {
+    hipLaunchKernelGGL(drt_band_kernel, dim3(B, (r + 255) / 256), dim3(256), 0, st, B, r, mu, var, ldv, cs, norm, s_lo, s_hi,
+                       var_status, fit_status, lo, hi);
+}
+
+// predict_z (drt1d.py:3500-3542) from y[b] = cs_b [A'; A''] x_b: Z = y' + j y'' + R_inf + j 2 pi f L in data units, every term
+// switchable (mask bit 0 DRT, 1 ohmic, 2 inductance).  R_inf and L are rescaled like extract_qphb_parameters (6228-6289); the
+// inductive term is formed as numpy forms `induc * 2j * np.pi * frequencies`.  y may be null when the DRT term is off.
+__global__ void z_assemble_kernel(int B, int nf, const double* __restrict__ y, const double* __restrict__ X, long long ldx,
+                                  int idx_rinf, int idx_induc, const double* __restrict__ cs, double inductance_scale,
+                                  const double* __restrict__ freq, int mask, const int* __restrict__ fit_status,
+                                  double* __restrict__ z_re, double* __restrict__ z_im) {
+    const int i = blockIdx.y * blockDim.x + threadIdx.x, b = blockIdx.x;
+    if (i >= nf) return;
+    const double c = cs[b];
+    double re = 0.0, im = 0.0;
+    if (mask & 1) { re = y[(size_t)b * 2 * nf + i]; im = y[(size_t)b * 2 * nf + nf + i]; }
+    if ((mask & 2) && idx_rinf >= 0) re += X[(size_t)b * ldx + idx_rinf] * c;
+    if ((mask & 4) && idx_induc >= 0) {
+        const double induc = X[(size_t)b * ldx + idx_induc] * (c * inductance_scale);
+        im += ((induc * 2.0) * 3.141592653589793) * freq[i];
+    }
+    if (fit_status[b] < 0) { re = NAN; im = NAN; }
+    z_re[(size_t)b * nf + i] = re;
+    z_im[(size_t)b * nf + i] = im;
+}
+
+void launch_z_assemble(hipStream_t st, int B, int nf, const double* y, const double* X, long long ldx, int idx_rinf,
+                       int idx_induc, const double* cs, double inductance_scale, const double* freq, int mask,
+                       const int* fit_status, double* z_re, double* z_im) {
+    hipLaunchKernelGGL(z_assemble_kernel, dim3(B, (nf + 255) / 256), dim3(256), 0, st, B, nf, y, X, ldx, idx_rinf, idx_induc, cs,
+                       inductance_scale, freq, mask, fit_status, z_re, z_im);
+}
+
+}  // namespace hipdrt

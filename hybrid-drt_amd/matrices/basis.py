@@ -37,12 +37,19 @@ def generate_response_lookup(basis_type, op_mode, step_model, epsilon, grid_poin
 
 
 def construct_func_eval_matrix(basis_grid, eval_grid=None, basis_type='gaussian', epsilon=1, order=0, zga_params=None):
-    """basis.construct_func_eval_matrix (hybdrt/matrices/basis.py:488-514) for the gaussian basis, order 0:
-    em[i, j] = exp(-(epsilon (eval_i - basis_j))^2); a (neval x nbasis) host array (it is an input of the device
-    posterior-variance kernel, not a hot loop)."""
-    if basis_type != 'gaussian' or order != 0:
-        raise NotImplementedError("only the gaussian basis, order 0, is built")
+    """basis.construct_func_eval_matrix (hybdrt/matrices/basis.py:488-514) for the gaussian basis, orders 0, 1 and 2
+    (get_basis_func_derivative, basis.py:218-228): em[i, j] = phi^(order)(eval_i - basis_j) with phi(y) =
+    exp(-(epsilon y)^2); a (neval x nbasis) host array.  It mirrors the reference at the boundary and states what the device
+    kernel computes (hipdrt_func_eval_matrix); the predictions of a fitted batch build their rows on the device."""
+    if basis_type != 'gaussian' or order not in (0, 1, 2):
+        raise NotImplementedError("only the gaussian basis, orders 0, 1 and 2, is built")
     basis_grid = np.asarray(basis_grid, dtype=float)
     eval_grid = basis_grid.copy() if eval_grid is None else np.asarray(eval_grid, dtype=float)
     xx_basis, xx_eval = np.meshgrid(basis_grid, eval_grid)
-    return np.exp(-(epsilon * (xx_eval - xx_basis)) ** 2)
+    if order == 0:
+        return np.exp(-(epsilon * (xx_eval - xx_basis)) ** 2)
+    y = xx_eval - xx_basis
+    phi = np.exp(-(epsilon * y) ** 2)
+    if order == 1:
+        return -2 * epsilon ** 2 * y * phi
+    return (-2 * epsilon ** 2 + 4 * epsilon ** 4 * y ** 2) * phi

@@ -12,7 +12,7 @@ import numpy as np
 from .. import _ffi, preprocessing as pp
 from ..matrices import mat1d
 from ..utils.array import is_uniform
-from . import kk, qphb
+from . import kk, predict, qphb
 from .prepared import PreparedFitMixin, combine_status
 
 _FIT_KW_DEFAULTS = dict(  # DRT._qphb_fit_core keyword defaults (drt1d.py:102-137) that the device loop honours
@@ -631,6 +631,154 @@ class DRT(PreparedFitMixin):
         self.stage_batch(frequencies, z_batch, history_of=history_of, **kw)
         self.fit_staged()
         return self.collect_staged()
+
+    # ---- model evaluation (drt1d.py:2959-3584), acting on the last fitted batch --------------------------------------------
+    def _predict_plan(self, what, x=None, p_matrix=None):
+        """(plan, per-member coefficient scales or None) for a prediction.  The x= / p_matrix= overrides of the reference would
+        bypass the state on the device and are not taken."""
+        if x is not None:
+            raise NotImplementedError(f'{what}: the x= override is not taken (predictions use the coefficients on the device)')
+        if p_matrix is not None:
+            raise NotImplementedError(f'{what}: the p_matrix= override is not taken (the band uses the fit\'s own P on the device)')
+        prepared = isinstance(self._plan, _ffi.PreparedPlan)
+        if self._plan is None or (self._last_batch is None and not prepared) or (prepared and not self._plan.batch):
+            raise RuntimeError(f'{what} needs a finished qphb fit')
+        if not prepared:
+            return self._plan, None
+        # the device loop of a prepared plan runs at unit scale: the coefficient scale is applied here
+        preps = self._last_prepared[0] if getattr(self, '_last_prepared', None) and \
+            len(self._last_prepared[0]) == self._plan.batch else [self._prep]
+        self._plan.set_tau_basis(np.log(self.basis_tau), self.tau_epsilon)
+        return self._plan, np.array([pr['coefficient_scale'] for pr in preps], dtype=float)
+
+    def _drt_sign(self, plan, sign):
+        two_copies = plan.n - plan.ns == 2 * len(self.basis_tau)
+        if sign is None:
+            return predict.default_sign(two_copies)              # DRT.default_dist_sign
+        if sign not in (-1, 0, 1):
+            raise ValueError(f'Invalid sign {sign}. Options: -1, 0, 1')
+        return sign if two_copies else 1                         # get_drt_params ignores the sign of a one-copy fit
+
+    def _predict_drt_device(self, what, tau, ppd, order, sign, normalize, normalize_by, abs_norm, quantiles, x=None, p_matrix=None):
+        if order not in (0, 1, 2):
+            raise ValueError(f'Invalid order {order}. Options: 0, 1, 2')
+        if normalize_by is not None and not normalize_by > 0:
+            raise ValueError('normalize_by must be positive')
+        plan, scales = self._predict_plan(what, x=x, p_matrix=p_matrix)
+        sign = self._drt_sign(plan, sign)
+        if tau is None:
+            tau = self.get_tau_eval(ppd)
+        by_rp = bool(normalize) and normalize_by is None
+        n_sig = None if quantiles is None else predict.n_sigma(quantiles)
+        mu, lo, hi, status = plan.predict_drt(np.log(np.asarray(tau, dtype=float)), order=order, sign=sign,
+                                              normalize=(2 if abs_norm else 1) if by_rp else 0, n_sigma=n_sig)
+        f = None
+        if scales is not None and not by_rp:                     # (a ratio to the spectrum's own R_p carries no scale)
+            f = scales[:, None]
+        if normalize_by is not None:
+            f = (1.0 if f is None else f) / normalize_by
+        if f is not None:
+            mu = mu * f
+            lo, hi = (None, None) if lo is None else (lo * f, hi * f)
+        return mu, lo, hi, status
+
+    def predict_drt_batch(self, tau=None, ppd=20, order=0, sign=None, normalize=False, normalize_by=None, abs_norm=False,
+                          x=None):
+        """DRT.predict_drt (drt1d.py:3040-3061) for every spectrum of the last fitted batch -> (B, len(tau)): the evaluation
+        matrix is built and applied to the resident coefficients on the device (hipdrt_plan_predict_drt); nothing is downloaded
+        but the result.  order 0, 1, 2; sign=None is the reference's default (0 for series_neg fits, else 1); tau=None is
+        get_tau_eval(ppd); normalize divides every spectrum by its own R_p (abs_norm: of |x|), normalize_by by a given positive
+        number.  Rows of failed fits are NaN.  A map cut into several device batches (max_batch) predicts for the last batch."""
+        return self._predict_drt_device('predict_drt_batch', tau, ppd, order, sign, normalize, normalize_by, abs_norm, None, x=x)[0]
+
+    def predict_drt_ci_batch(self, tau=None, ppd=20, order=0, sign=None, normalize=False, normalize_by=None, abs_norm=False,
+                             quantiles=(0.025, 0.975), x=None, p_matrix=None):
+        """DRT.predict_drt_ci (drt1d.py:3209-3231) for every spectrum of the last fitted batch -> (lo, hi, ok): mean +/- the
+        quantiles' numbers of posterior standard deviations (stats.std_normal_quantile), sigma^2 = diag(E inv(P) E') from the
+        Cholesky factor of every final P on the device, fed the device-resident evaluation rows.  ok (B,) bool is False where
+        the fit failed or P is not positive definite (rows NaN; the reference returns (None, None)).  Last device batch only."""
+        _, lo, hi, status = self._predict_drt_device('predict_drt_ci_batch', tau, ppd, order, sign, normalize, normalize_by,
+                                                     abs_norm, quantiles, x=x, p_matrix=p_matrix)
+        return lo, hi, status >= 0
+
+    def predict_z_batch(self, frequencies=None, include_drt=True, include_ohmic=True, include_inductance=True, x=None):
+        """DRT.predict_z(include_vz_offset=False) (drt1d.py:3500-3542) for every spectrum of the last fitted batch, at ANY
+        frequencies -> complex (B, nf); frequencies=None: the fit frequencies.  Z' / Z'' matrices are built on the device at the
+        requested frequencies from the plan's own lookup tables (clamped outside them like np.interp), tau grid and integration
+        mode, and applied to the resident coefficients (hipdrt_plan_predict_z).  This is the any-grid impedance prediction:
+        ``predict_z_batch(f)[b]``; DRT.predict_z itself serves the fit frequencies only.  Plain EIS fits only (no fit_dop,
+        fit_capacitance, solve_rp, series_neg, chrono or joint data).  Rows of failed fits are NaN.  Last device batch only."""
+        if self.fit_dop:
+            raise NotImplementedError('predict_z_batch is built for plain EIS fits, not for fit_dop fits')
+        plan, scales = self._predict_plan('predict_z_batch', x=x)
+        if scales is not None:
+            raise NotImplementedError('predict_z_batch is built for plain EIS plans (fit_eis / fit_eis_batch without '
+                                      'fit_dop, fit_capacitance, solve_rp, series_neg or outlier removal)')
+        f = self.get_fit_frequencies() if frequencies is None else np.asarray(frequencies, dtype=float)
+        return plan.predict_z(f, include_drt=include_drt, include_ohmic=include_ohmic, include_inductance=include_inductance)[0]
+
+    def predict_r_p_batch(self, absolute=False):
+        """DRT.predict_r_p (drt1d.py:3552-3571; default sign) of every spectrum of the last fitted batch, summed on the device"""
+        plan, scales = self._predict_plan('predict_r_p_batch')
+        r_p = plan.predict_resistances(absolute=absolute, r_p_only=scales is not None)[0]
+        return r_p if scales is None else r_p * scales
+
+    def _r_inf_prepared(self, scales):
+        sp = self.special_qp_params
+        if 'R_inf' not in sp:
+            return np.zeros(len(scales))
+        return self._plan.get('x')[:, sp['R_inf']['index']] * scales
+
+    def predict_r_inf_batch(self):
+        """DRT.predict_r_inf (drt1d.py:3573-3581) of every spectrum of the last fitted batch"""
+        plan, scales = self._predict_plan('predict_r_inf_batch')
+        return plan.predict_resistances()[1] if scales is None else self._r_inf_prepared(scales)
+
+    def predict_r_tot_batch(self):
+        """DRT.predict_r_tot (drt1d.py:3583-3584): R_inf + R_p of every spectrum of the last fitted batch"""
+        plan, scales = self._predict_plan('predict_r_tot_batch')
+        if scales is None:
+            return plan.predict_resistances()[2]
+        return self._r_inf_prepared(scales) + plan.predict_resistances(r_p_only=True)[0] * scales
+
+    # single-spectrum forms with the reference's signatures; ``b`` picks a member of the last batch
+    def predict_drt(self, tau=None, ppd=20, x=None, order=0, sign=1, normalize=False, normalize_by=None, abs_norm=False, b=0):
+        """DRT.predict_drt (drt1d.py:3040-3061) of member ``b`` of the last fit, from the device"""
+        return self._predict_drt_device('predict_drt', tau, ppd, order, sign, normalize, normalize_by, abs_norm, None, x=x)[0][b]
+
+    def predict_distribution(self, tau=None, ppd=20, x=None, order=0, sign=1, normalize=False, normalize_by=None,
+                             abs_norm=False, b=0):
+        """DRT.predict_distribution (drt1d.py:3033-3038): the deprecated name of predict_drt"""
+        warnings.warn("predict_distribution is deprecated and will be removed in the future. Please use predict_drt instead",
+                      DeprecationWarning)
+        return self.predict_drt(tau=tau, ppd=ppd, x=x, order=order, sign=sign, normalize=normalize, normalize_by=normalize_by,
+                                abs_norm=abs_norm, b=b)
+
+    def predict_drt_ci(self, tau=None, ppd=20, x=None, order=0, sign=1, normalize=False, normalize_by=None,
+                       quantiles=(0.025, 0.975), p_matrix=None, b=0):
+        """DRT.predict_drt_ci (drt1d.py:3209-3231) of member ``b`` of the last fit: (lo, hi), or (None, None) with upstream's
+        warning when P is not positive definite"""
+        _, lo, hi, status = self._predict_drt_device('predict_drt_ci', tau, ppd, order, sign, normalize, normalize_by, False,
+                                                     quantiles, x=x, p_matrix=p_matrix)
+        if status[b] < 0:
+            warnings.warn('Singular P matrix - could not obtain covariance estimate')
+            return None, None
+        return lo[b], hi[b]
+
+    def predict_r_p(self, sign=None, absolute=False, x=None, raw=False, b=0):
+        """DRT.predict_r_p (drt1d.py:3552-3571) of member ``b`` of the last fit; the default sign only"""
+        plan, _ = self._predict_plan('predict_r_p', x=x)
+        if raw or (sign is not None and self._drt_sign(plan, sign) != self._drt_sign(plan, None)):
+            raise NotImplementedError('predict_r_p: only the default sign of the fitted coefficients is built')
+        return float(self.predict_r_p_batch(absolute=absolute)[b])
+
+    def predict_r_inf(self, b=0):
+        """DRT.predict_r_inf (drt1d.py:3573-3581) of member ``b`` of the last fit"""
+        return float(self.predict_r_inf_batch()[b])
+
+    def predict_r_tot(self, b=0):
+        """DRT.predict_r_tot (drt1d.py:3583-3584) of member ``b`` of the last fit"""
+        return float(self.predict_r_tot_batch()[b])
 
     # ---- Kramers-Kronig test (drt1d.py:1370-1491) ------------------------------------------------------------------------
     def get_fit_frequencies(self):

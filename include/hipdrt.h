@@ -23,6 +23,7 @@ extern "C" {
 #define HIPDRT_E_HIP (-2)       /* HIP runtime error (text in hipdrt_last_error)         */
 #define HIPDRT_E_NODEVICE (-3)  /* no usable gfx950 device                              */
 #define HIPDRT_E_NUMERIC (-4)   /* numerical breakdown for the whole call               */
+#define HIPDRT_E_UNSUPPORTED (-5) /* the call is not built for this kind of plan         */
 
 /* per-problem status codes written to status[] arrays */
 #define HIPDRT_QP_OPTIMAL 0     /* coneqp stopping test met                                        */
@@ -447,6 +448,45 @@ void hipdrt_default_kk_opts(hipdrt_kk_opts* o);
 int hipdrt_plan_kk_screen(hipdrt_plan* plan, const hipdrt_kk_opts* opts, int set_row_factors,
                           double* z_hat_re, double* z_hat_im, double* err_re, double* err_im,
                           double* std, int* outlier_mask, double* f_lim, int* i_lim, int* status);
+
+/* ---- model evaluation: what a user does first with a finished fit ---------------------------------------------------------
+ * basis.construct_func_eval_matrix (hybdrt/matrices/basis.py:488-514) with get_basis_func_derivative (218-228), gaussian basis:
+ * out[ne][nb], out[i][j] = phi^(order)(eval_grid[i] - basis_grid[j]; epsilon) for natural-log grids; order 0: exp(-(eps y)^2),
+ * 1: -2 eps^2 y phi, 2: (-2 eps^2 + 4 eps^4 y^2) phi, evaluated in numpy's order of operations.                              */
+int hipdrt_func_eval_matrix(hipdrt_ctx* ctx, const double* basis_grid, int nb, const double* eval_grid, int ne, double epsilon,
+                            int order, double* out);
+/* A prepared plan holds no tau grid: give it ln(basis_tau)[nb] and the basis epsilon before hipdrt_plan_predict_drt /
+ * hipdrt_plan_predict_resistances.  Its DRT block (n - ns columns) must hold one copy of the basis, or two (series_neg: positive
+ * copy, then negative copy; drt1d.py:2961-2963).  Plans made by hipdrt_plan_create know their basis: the call is refused there. */
+int hipdrt_plan_set_tau_basis(hipdrt_plan* plan, const double* ln_basis_tau, int nb, double epsilon);
+/* per-spectrum status of hipdrt_plan_predict_drt when the band was asked for and P is not positive definite (the reference's
+ * LinAlgError -> (None, None), drt1d.py:3229-3231): mu is valid, lo and hi are NaN                                             */
+#define HIPDRT_PREDICT_NOT_PD (-3)
+/* DRT.predict_drt (hybdrt/models/drt1d.py:3040-3061) and DRT.predict_drt_ci (3209-3231) for every spectrum of the fitted batch:
+ * mu[b][i] = scale_b * sum_j E[i][j] x_b[j] with E the evaluation matrix above at ln_tau_eval[neval], x_b the DRT block of the
+ * solution on the device, scale_b the coefficient scale -- divided by that spectrum's own R_p (normalize = 1; 2: by R_p of |x|,
+ * abs_norm; get_drt_norm, 3020-3031).  sign is get_drt_params' (2965-2987): 1 = +x+, -1 = -x-, 0 = x+ - x-; a one-copy block takes
+ * 1 only.  lo, hi (may be NULL: then nothing is factorised) = mu + s_lo sigma, mu + s_hi sigma with
+ * sigma^2 = diag(E inv(P) E') scale_b^2 (estimate_distribution_cov, 3063-3151, before extend_var) from the same Cholesky kernel
+ * as hipdrt_plan_distribution_var, fed the device-resident E; s_lo, s_hi are the caller's numbers of standard deviations
+ * (stats.std_normal_quantile of the quantiles).  mu, lo, hi: [B][neval].  status[B] (may be NULL): the fit's status (0, 1; < 0
+ * failed: the row is NaN), or HIPDRT_PREDICT_NOT_PD.  Plain and prepared plans; a prepared plan runs at unit scale
+ * (coefficient scale 1: the caller rescales) and needs hipdrt_plan_set_tau_basis.  Every output element is accumulated in one
+ * fixed order that depends neither on B nor on the spectrum's position: alone or in a batch, a spectrum gives the same bits.   */
+int hipdrt_plan_predict_drt(hipdrt_plan* plan, const double* ln_tau_eval, int neval, int order, int sign, int normalize,
+                            double s_lo, double s_hi, double* mu, double* lo, double* hi, int* status);
+/* DRT.predict_z (drt1d.py:3500-3542; include_vz_offset / include_dop / include_cap do not apply to a plain EIS fit) at ANY
+ * frequencies freq[nf]: Z = cs (A' x + j A'' x) + R_inf + j 2 pi f L in data units, A', A'' built on the device at freq from the
+ * plan's own lookup tables, tau grid and integration mode (mat1d.construct_impedance_matrix, hybdrt/matrices/mat1d.py:212-374,
+ * with np.interp's clamp outside the tables, 353-372).  include_mask: bit 0 the DRT term, bit 1 R_inf, bit 2 the inductance
+ * (include_drt / include_ohmic / include_inductance).  z_re, z_im [B][nf]; status[B] (may be NULL) the fit's status, rows of a
+ * failed fit are NaN.  Plain EIS plans only: a prepared plan returns HIPDRT_E_UNSUPPORTED.                                      */
+int hipdrt_plan_predict_z(hipdrt_plan* plan, const double* freq, int nf, int include_mask, double* z_re, double* z_im,
+                          int* status);
+/* DRT.predict_r_p (drt1d.py:3552-3571; abs_norm != 0: absolute=True), predict_r_inf (3573-3581) and predict_r_tot (3583-3584) of
+ * every fitted spectrum, in data units; each output [B], any may be NULL.  A prepared plan gives r_p only (unit scale;
+ * HIPDRT_E_UNSUPPORTED when r_inf or r_tot is asked for).                                                                       */
+int hipdrt_plan_predict_resistances(hipdrt_plan* plan, double* r_p, double* r_inf, double* r_tot, int abs_norm);
 
 /* kernel-time breakdown of the last hipdrt_plan_fit in ms (HIP events on the ctx stream):
  * t[0]=total, t[1]=gram, t[2]=qp, t[3]=hyper, t[4]=setup/other; launches[5] same order                 */

@@ -83,6 +83,18 @@ int hipdrt_debug_pack_p(hipdrt_ctx* ctx, int B, int n, const double* P, int ldp,
 int hipdrt_debug_kk_stats(hipdrt_ctx* ctx, int B, int nf, const double* freq, const double* err_re, const double* err_im,
                           const hipdrt_kk_opts* opts, double* std, int* outlier_mask, double* f_lim, int* i_lim, int* status);
 
+/* test hook (tests/test_gpu_predict.py): the row-application kernel of the prediction entry points (csrc/predict.hip) as it is,
+ * on host arrays: out[b][i] = scale[b] * sum_j E[i][j] X[b][col_offset + j]; X [B][ldx] with ldx >= col_offset + K, E [r][K],
+ * scale [B] or NULL (1), out [B][r].  The device output is allocated one row and five columns larger and filled with a marker:
+ * HIPDRT_E_NUMERIC when the kernel changed anything outside its B x r block.                                                */
+int hipdrt_debug_apply_rows(hipdrt_ctx* ctx, int B, int K, int ldx, int col_offset, const double* X, int r, const double* E,
+                            const double* scale, double* out);
+
+/* tools hook (tools/bench_predict.py): kernel time in ms of the last hipdrt_plan_predict_drt / hipdrt_plan_predict_z of a plan of
+ * this context, by HIP events around its launches (allocations and copies excluded): ms[0] up to the mean (predict_z: the whole
+ * prediction), ms[1] with the credible band's factorisation included (equal to ms[0] without a band).                         */
+int hipdrt_debug_last_predict_ms(hipdrt_ctx* ctx, float* ms);
+
 #ifdef __cplusplus
 }
 #endif
