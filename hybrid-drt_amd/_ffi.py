@@ -89,6 +89,19 @@ class DebugGramArgs(C.Structure):
     ]
 
 
+class DebugHyperArgs(C.Structure):
+    """hipdrt_debug_hyper_args (include/hipdrt_debug.h)"""
+    _fields_ = [
+        ("B", C.c_int), ("m", C.c_int), ("n", C.c_int), ("ns", C.c_int), ("ldrm", C.c_int), ("ldm", C.c_int),
+        ("rm", _dp), ("rm_batched", C.c_int), ("vmm", _dp), ("mk", _dp * 3), ("toeplitz", C.c_int), ("toep_reach", C.c_int),
+        ("x", _dp), ("x_in", _dp), ("s", _dp), ("rho", _dp), ("xmx", _dp), ("rv", _dp), ("est_w", _dp), ("w", _dp),
+        ("var_floor", _dp), ("coef_scale", _dp), ("qp_status", _ip), ("active", _ip), ("fit_status", _ip), ("outer_iters", _ip),
+        ("n_active", _ip), ("outlier_t", _dp), ("opts", C.POINTER(FitOpts)), ("it", C.c_int), ("continue_mode", C.c_int),
+        ("min_iter", C.c_int), ("basis_area", C.c_double), ("desc", C.POINTER(PreparedDesc)), ("dop_rho", _dp), ("dop_xmx", _dp),
+        ("vz_strength", _dp), ("vz_entry", _dp), ("rm_col", _dp), ("products", C.c_int),
+    ]
+
+
 # name -> argtypes (all return int unless listed in _RESTYPES).  Mirrors include/hipdrt.h one-to-one;
 # tests/test_cabi_symbols.py checks the header and this table against the built library.
 SIGNATURES = {
@@ -125,6 +138,8 @@ SIGNATURES = {
     "hipdrt_debug_stream_pool": [_vp, C.c_int, C.POINTER(C.c_void_p), _ip, _ip, _ip],
     "hipdrt_debug_gram_l2": [_vp, C.POINTER(DebugGramArgs)],
     "hipdrt_debug_pack_p": [_vp, C.c_int, C.c_int, _dp, C.c_int, _dp],
+    "hipdrt_debug_hyper_step": [_vp, C.POINTER(DebugHyperArgs)],
+    "hipdrt_debug_hyper_form": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.POINTER(C.c_longlong)],
     "hipdrt_debug_kk_stats": [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(KkOpts), _dp, _ip, _dp, _ip, _ip],
     "hipdrt_default_kk_opts": [C.POINTER(KkOpts)],
     "hipdrt_plan_kk_screen": [_vp, C.POINTER(KkOpts), C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _ip, _ip],
@@ -604,6 +619,92 @@ class Context:
         a.q = out(q, (B, n), "q")
         _check(self._lib.hipdrt_debug_gram_l2(self._h, C.byref(a)))
         return P, Ppk, q
+
+    def debug_hyper_form(self, n, m, ns, toeplitz=True, outlier=False):
+        """tests: (form, lds_bytes) of the LDS layout launch_hyper picks -- 1: Toeplitz columns beside the two m-vectors, 2: inside
+        the second one, 0: the general row-streaming form; raises when none fits (hipdrt_debug_hyper_form, include/hipdrt_debug.h)"""
+        form, lds = C.c_int(-1), C.c_longlong(0)
+        _check(self._lib.hipdrt_debug_hyper_form(self._h, int(n), int(m), int(ns), int(bool(toeplitz)), int(bool(outlier)),
+                                                 C.byref(form), C.byref(lds)))
+        return form.value, lds.value
+
+    def debug_hyper_step(self, rm, vmm, mk, x, x_in, s, rho, xmx, rv, est_w, w, var_floor, coef_scale, opts: FitOpts, ns=0, n=None,
+                         toeplitz=False, toep_reach=-1, qp_status=None, active=None, fit_status=None, outer_iters=None, n_active=0,
+                         outlier_t=None, it=0, continue_mode=0, min_iter=1, basis_area=1.0, desc: PreparedDesc | None = None,
+                         dop_rho=None, dop_xmx=None, vz_strength=None, vz_entry=None, products=0):
+        """tests: one hyper-parameter step (launch_hyper as it is) on host arrays (hipdrt_debug_hyper_step, include/hipdrt_debug.h).
+        rm [m][ldrm] (shared) or [B][m][ldrm], vmm [m][m], mk three [n][ldm]; `n` = the number of unknowns when the rows of rm are
+        padded.  x [B][n] is the QP's result; the other per-spectrum arrays are the state BEFORE the step (poison where the step is
+        to write without reading).  Nothing passed in is modified.  Returns a dict of the state AFTER the step: s, rho, xmx, dop_rho,
+        dop_xmx, w, x_in, outlier_t, active, fit_status, outer_iters, n_active, rv, est_w, coef_scale, var_floor, rm_col."""
+        rm, vmm, x = _f64(rm), _f64(vmm), _f64(x)
+        B = x.shape[0]
+        m = vmm.shape[0]
+        a = DebugHyperArgs()
+        a.B, a.m, a.ldrm = B, m, rm.shape[-1]
+        a.n = n = x.shape[1] if n is None else int(n)
+        a.ns, a.rm_batched = int(ns), int(rm.ndim == 3)
+        if rm.shape[-2] != m or (rm.ndim == 3 and rm.shape[0] != B) or vmm.shape != (m, m) or x.shape != (B, n):
+            raise ValueError("rm, vmm and x do not match")
+        mk = [_f64(v) for v in mk]
+        if len(mk) != 3 or any(v.shape != (n, mk[0].shape[-1]) for v in mk):
+            raise ValueError("mk: three [n][ldm] matrices")
+        a.ldm = mk[0].shape[-1]
+        keep = [rm, vmm, x] + mk
+        a.rm, a.vmm, a.x = _p(rm), _p(vmm), _p(x)
+        for k in range(3):
+            a.mk[k] = _p(mk[k])
+        a.toeplitz, a.toep_reach = int(bool(toeplitz)), int(toep_reach)
+        out = {}
+
+        def state(name, v, shape, dtype=np.float64, required=True):
+            if v is None:
+                if required:
+                    raise ValueError(f"{name} is required")
+                return None
+            v = np.array(v, dtype=dtype, order="C")           # a copy: the caller's array stays as it is
+            if v.shape != tuple(shape):
+                raise ValueError(f"{name}: shape {v.shape}, expected {tuple(shape)}")
+            out[name] = v
+            return _p(v) if dtype == np.float64 else _pi(v)
+
+        a.x_in = state("x_in", x_in, (B, n))
+        a.s = state("s", s, (B, 3, n))
+        a.rho, a.xmx = state("rho", rho, (B, 3)), state("xmx", xmx, (B, 3))
+        a.rv, a.est_w, a.w = state("rv", rv, (B, m)), state("est_w", est_w, (B, m)), state("w", w, (B, m))
+        a.var_floor, a.coef_scale = state("var_floor", var_floor, (B,)), state("coef_scale", coef_scale, (B,))
+        qs = np.ascontiguousarray(np.zeros(B) if qp_status is None else qp_status, dtype=np.int32)
+        if qs.shape != (B,):
+            raise ValueError("qp_status: one per spectrum")
+        keep.append(qs)
+        a.qp_status = _pi(qs)
+        a.active = state("active", np.ones(B) if active is None else active, (B,), np.int32)
+        a.fit_status = state("fit_status", np.full(B, -77) if fit_status is None else fit_status, (B,), np.int32)
+        a.outer_iters = state("outer_iters", np.full(B, -77) if outer_iters is None else outer_iters, (B,), np.int32)
+        a.n_active = state("n_active", np.array([n_active]), (1,), np.int32)
+        a.outlier_t = state("outlier_t", outlier_t, (B, m), required=False)
+        a.opts = C.pointer(opts)
+        a.it, a.continue_mode, a.min_iter, a.basis_area = int(it), int(continue_mode), int(min_iter), float(basis_area)
+        a.products = int(products)
+        if desc is not None:
+            a.desc = C.pointer(desc)
+            a.dop_rho, a.dop_xmx = state("dop_rho", dop_rho, (B, 3)), state("dop_xmx", dop_xmx, (B, 3))
+            if desc.vz_index >= 0:
+                vs = _f64(vz_strength)
+                if vs.shape != (m,):
+                    raise ValueError("vz_strength: [m]")
+                keep.append(vs)
+                a.vz_strength = _p(vs)
+                a.rm_col = state("rm_col", np.full((B if rm.ndim == 3 else 1, m), np.nan), (B if rm.ndim == 3 else 1, m))
+        if vz_entry is not None:
+            ve = _f64(vz_entry)
+            if ve.shape != (B, m):
+                raise ValueError("vz_entry: [B][m]")
+            keep.append(ve)
+            a.vz_entry = _p(ve)
+        _check(self._lib.hipdrt_debug_hyper_step(self._h, C.byref(a)))
+        out["n_active"] = int(out["n_active"][0])
+        return out
 
     def debug_kk_stats(self, freq, err, opts: KkOpts | None = None):
         """tests: the statistics stage of the KK screen kernel on host residuals err (B, nf) complex

@@ -899,6 +899,186 @@ int hipdrt_debug_pack_p(hipdrt_ctx* ctx, int B, int n, const double* P, int ldp,
     return HIPDRT_OK;
 } HIPDRT_CATCH
 
+// test hook (include/hipdrt_debug.h): launch_hyper as the fit loop calls it, on host arrays.  Every extent a kernel derives an
+// address from is checked here.  In/out arrays live on the device between two borders of marker bytes.
+namespace {
+struct Guarded {
+    static constexpr size_t G = 128;           // border bytes on either side
+    static constexpr unsigned char MARK = 0xA5;
+    DevBuf buf;
+    void* host = nullptr;
+    size_t bytes = 0;
+    const char* name = "";
+    std::vector<unsigned char> stage;
+    int up(const char* what, void* h, size_t nbytes, hipStream_t st) {
+        name = what; host = h; bytes = nbytes;
+        stage.assign(nbytes + 2 * G, MARK);
+        if (h) std::memcpy(stage.data() + G, h, nbytes);
+        HIPDRT_CHECK(buf.alloc(stage.size()));
+        HIPDRT_CHECK(hipMemcpyAsync(buf.p, stage.data(), stage.size(), hipMemcpyHostToDevice, st));
+        return 0;
+    }
+    double* dd() const { return reinterpret_cast<double*>(static_cast<unsigned char*>(buf.p) + G); }
+    int* di() const { return reinterpret_cast<int*>(static_cast<unsigned char*>(buf.p) + G); }
+    int fetch(hipStream_t st) { HIPDRT_CHECK(hipMemcpyAsync(stage.data(), buf.p, stage.size(), hipMemcpyDeviceToHost, st)); return 0; }
+    int check() {
+        for (size_t i = 0; i < G; ++i)
+            if (stage[i] != MARK || stage[G + bytes + i] != MARK) {
+                set_error(std::string("hyper step wrote outside ") + name);
+                return HIPDRT_E_NUMERIC;
+            }
+        if (host) std::memcpy(host, stage.data() + G, bytes);
+        return 0;
+    }
+};
+}  // namespace
+
+int hipdrt_debug_hyper_form(hipdrt_ctx* ctx, int n, int m, int ns, int toeplitz, int outlier, int* form, long long* lds_bytes) try {
+    HIPDRT_REQUIRE(ctx && form && lds_bytes, "NULL pointer");
+    HIPDRT_REQUIRE(m >= 1 && m <= 8192 && n >= 1 && n <= 4096 && ns >= 0 && ns < n, "1 <= m <= 8192, 0 <= ns < n <= 4096");
+    size_t lds = 0;
+    const bool ok = hyper_lds_form(n, m, ns, toeplitz ? 1 : 0, outlier != 0, form, &lds);
+    *lds_bytes = (long long)lds;
+    if (!ok) { set_error("hyper-parameter kernel: problem too large for LDS (m, n)"); return HIPDRT_E_INVALID; }
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+int hipdrt_debug_hyper_step(hipdrt_ctx* ctx, const hipdrt_debug_hyper_args* a) try {
+    HIPDRT_REQUIRE(ctx && a, "NULL pointer");
+    const int B = a->B, m = a->m, n = a->n, ns = a->ns, nd = n - ns;
+    HIPDRT_REQUIRE(B >= 1 && B <= 4096 && m >= 1 && m <= 8192 && n >= 1 && n <= 4096, "1 <= B <= 4096, 1 <= m <= 8192, 1 <= n <= 4096");
+    HIPDRT_REQUIRE(ns >= 0 && nd >= 1, "0 <= ns < n: the step needs a DRT block");
+    HIPDRT_REQUIRE(a->ldrm >= n && a->ldm >= n, "ldrm >= n, ldm >= n");
+    HIPDRT_REQUIRE(a->rm && a->vmm && a->mk[0] && a->mk[1] && a->mk[2] && a->opts, "rm, vmm, three penalty matrices, opts");
+    HIPDRT_REQUIRE(a->x && a->x_in && a->s && a->rho && a->xmx && a->rv && a->est_w && a->w && a->var_floor && a->coef_scale,
+                   "per-spectrum state: x, x_in, s, rho, xmx, rv, est_w, w, var_floor, coef_scale");
+    HIPDRT_REQUIRE(a->qp_status && a->active && a->fit_status && a->outer_iters && a->n_active, "qp_status, active, fit_status, outer_iters, n_active");
+    HIPDRT_REQUIRE(a->continue_mode >= 0 && a->continue_mode <= 2 && a->it >= 0, "continue_mode 0, 1 or 2; it >= 0");
+    HIPDRT_REQUIRE(a->products >= 0 && a->products <= 2, "products 0, 1 or 2");
+    HIPDRT_REQUIRE(a->toep_reach >= -1, "toep_reach >= -1");
+    const bool outl = a->opts->outlier_p > 0.0;
+    const bool prep = a->desc != nullptr;
+    hipdrt_prepared_desc desc{};
+    desc.vz_index = -1;
+    if (prep) {
+        desc = *a->desc;
+        HIPDRT_REQUIRE(a->dop_rho && a->dop_xmx, "a prepared step needs dop_rho and dop_xmx");
+        HIPDRT_REQUIRE(desc.dop_size >= 0 && (desc.dop_size == 0 || (desc.dop_start >= 0 && desc.dop_start + desc.dop_size <= ns)),
+                       "x_dop block outside the special block [0, ns)");
+        HIPDRT_REQUIRE(desc.dop_size <= nd, "x_dop block larger than the DRT block (the kernel's LDS vectors hold n - ns entries)");
+        HIPDRT_REQUIRE(desc.vz_index >= -1 && desc.vz_index < n, "-1 <= vz_index < n");
+        HIPDRT_REQUIRE(desc.vb_start >= 0 && desc.vb_size >= 0 && desc.vb_start + desc.vb_size <= n, "v_baseline columns outside [0, n)");
+        HIPDRT_REQUIRE(desc.num_chrono >= 0 && desc.num_chrono <= m, "0 <= num_chrono <= m");
+        if (desc.vz_index >= 0) {
+            HIPDRT_REQUIRE(a->vz_strength && a->rm_col, "vz_offset column: vz_strength and rm_col");
+            HIPDRT_REQUIRE(a->rm_batched || B == 1, "vz_offset column: one response matrix per spectrum");
+        }
+        desc.m = m; desc.n = n; desc.ns = ns; desc.toeplitz_m = a->toeplitz ? 1 : 0;
+    }
+    const bool vz = prep && desc.vz_index >= 0;
+    HIPDRT_REQUIRE(!a->vz_entry || vz, "vz_entry without a vz_offset column");
+    if (a->products == 1) HIPDRT_REQUIRE(!outl, "products = 1: outlier_p <= 0");
+    if (a->products == 2) HIPDRT_REQUIRE(!a->rm_batched && !outl && !vz, "products = 2: a shared rm, no vz_offset column, outlier_p <= 0");
+    // the Toeplitz claim and the reach, on the host
+    if (a->toeplitz) {
+        int reach = 0;
+        for (int k = 0; k < 3; ++k) {
+            const double* blk = a->mk[k] + (size_t)ns * a->ldm + ns;
+            for (int i = 0; i < nd; ++i)
+                for (int j = 0; j < nd; ++j) {
+                    const int d = i > j ? i - j : j - i;
+                    const double v = blk[(size_t)i * a->ldm + j];
+                    HIPDRT_REQUIRE(v == blk[d] || (v != v && blk[d] != blk[d]), "toeplitz = 1, but a DRT block is not symmetric Toeplitz");
+                }
+            for (int d = nd - 1; d > reach; --d)
+                if (blk[d] != 0.0) { reach = d; break; }
+        }
+        HIPDRT_REQUIRE(a->toep_reach < 0 || a->toep_reach >= reach, "toep_reach is smaller than the reach of the penalty blocks");
+    }
+    int form = 0;
+    size_t lds = 0;
+    if (!hyper_lds_form(n, m, ns, a->toeplitz ? 1 : 0, outl, &form, &lds)) {
+        set_error("hyper-parameter kernel: problem too large for LDS (m, n)");
+        return HIPDRT_E_INVALID;
+    }
+    HIPDRT_CHECK(hipSetDevice(ctx->device)); (void)hipGetLastError();
+    hipStream_t st = ctx->stream;
+    const size_t D = sizeof(double), I = sizeof(int);
+    const size_t nrm = (size_t)(a->rm_batched ? B : 1) * m * a->ldrm;
+    DevBuf dvmm, dmk[3], dx, dqs, dvs, dve, dpremv;
+    Guarded grm, gxin, gs, grho, gxmx, grv, gew, gw, gvf, gcs, gact, gfs, goi, gna, got, gdr, gdx;
+    std::vector<double> rm_copy(a->rm, a->rm + nrm);
+    TRY(grm.up("rm", rm_copy.data(), nrm * D, st));
+    TRY(upload(dvmm, a->vmm, (size_t)m * m * D, st));
+    for (int k = 0; k < 3; ++k) TRY(upload(dmk[k], a->mk[k], (size_t)n * a->ldm * D, st));
+    TRY(upload(dx, a->x, (size_t)B * n * D, st));
+    TRY(upload(dqs, a->qp_status, (size_t)B * I, st));
+    if (vz) TRY(upload(dvs, a->vz_strength, (size_t)m * D, st));
+    if (a->vz_entry) TRY(upload(dve, a->vz_entry, (size_t)B * m * D, st));
+    TRY(gxin.up("x_in", a->x_in, (size_t)B * n * D, st));
+    TRY(gs.up("s", a->s, (size_t)B * 3 * n * D, st));
+    TRY(grho.up("rho", a->rho, (size_t)B * 3 * D, st));
+    TRY(gxmx.up("xmx", a->xmx, (size_t)B * 3 * D, st));
+    TRY(grv.up("rv", a->rv, (size_t)B * m * D, st));
+    TRY(gew.up("est_w", a->est_w, (size_t)B * m * D, st));
+    TRY(gw.up("w", a->w, (size_t)B * m * D, st));
+    TRY(gvf.up("var_floor", a->var_floor, (size_t)B * D, st));
+    TRY(gcs.up("coef_scale", a->coef_scale, (size_t)B * D, st));
+    TRY(gact.up("active", a->active, (size_t)B * I, st));
+    TRY(gfs.up("fit_status", a->fit_status, (size_t)B * I, st));
+    TRY(goi.up("outer_iters", a->outer_iters, (size_t)B * I, st));
+    TRY(gna.up("n_active", a->n_active, I, st));
+    if (a->outlier_t) TRY(got.up("outlier_t", a->outlier_t, (size_t)B * m * D, st));
+    if (prep) {
+        TRY(gdr.up("dop_rho", a->dop_rho, (size_t)B * 3 * D, st));
+        TRY(gdx.up("dop_xmx", a->dop_xmx, (size_t)B * 3 * D, st));
+    }
+    FitState fs{};
+    fs.nf = 0; fs.m = m; fs.n = n; fs.ns = ns; fs.ldrm = a->ldrm; fs.ldm = a->ldm;
+    fs.toeplitz_m = a->toeplitz ? 1 : 0; fs.toep_reach = a->toeplitz ? a->toep_reach : -1;
+    fs.continue_mode = a->continue_mode; fs.min_iter = a->min_iter; fs.basis_area = a->basis_area; fs.opts = *a->opts;
+    fs.prepared = prep ? 1 : 0; fs.desc = desc;
+    fs.rm_stride = a->rm_batched ? (long long)m * a->ldrm : 0;
+    fs.rm = grm.dd(); fs.rm_rw = grm.dd();
+    fs.vz_strength = vz ? dvs.d() : nullptr; fs.vz_entry = a->vz_entry ? dve.d() : nullptr;
+    fs.dop_rho = prep ? gdr.dd() : nullptr; fs.dop_xmx = prep ? gdx.dd() : nullptr;
+    fs.outlier_t = a->outlier_t ? got.dd() : nullptr;
+    fs.vmm = dvmm.d(); fs.vmm_iw = dvmm.d();
+    for (int k = 0; k < 3; ++k) fs.mk[k] = dmk[k].d();
+    fs.rv = grv.dd(); fs.w = gw.dd(); fs.est_w = gew.dd();
+    fs.x = dx.d(); fs.x_in = gxin.dd(); fs.s = gs.dd(); fs.rho = grho.dd(); fs.xmx = gxmx.dd();
+    fs.coef_scale = gcs.dd(); fs.var_floor = gvf.dd();
+    fs.active = gact.di(); fs.outer_iters = goi.di(); fs.fit_status = gfs.di();
+    fs.qp_status = dqs.i(); fs.n_active = gna.di();
+    fs.hist_b = -1; fs.hist_cap = 0;
+    if (a->products) {
+        HIPDRT_CHECK(dpremv.alloc(3 * (size_t)B * m * D));
+        HIPDRT_CHECK(hipMemsetAsync(dpremv.p, 0xFF, 3 * (size_t)B * m * D, st));       // NaN where no product kernel wrote
+        fs.premv = dpremv.d();
+        fs.premv_batched = a->products == 2 ? 1 : 0;
+    }
+    TRY(launch_hyper(st, fs, B, a->it));
+    LAUNCH_OK();
+    Guarded* all[] = {&grm, &gxin, &gs, &grho, &gxmx, &grv, &gew, &gw, &gvf, &gcs, &gact, &gfs, &goi, &gna, &got, &gdr, &gdx};
+    for (Guarded* g : all) if (g->buf.p) TRY(g->fetch(st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    for (Guarded* g : all) if (g->buf.p) TRY(g->check());
+    // the response matrix: nothing but the vz_offset column may differ from what was uploaded
+    const int nmat = a->rm_batched ? B : 1;
+    for (int b = 0; b < nmat; ++b)
+        for (int i = 0; i < m; ++i) {
+            const size_t row = ((size_t)b * m + i) * a->ldrm;
+            for (int j = 0; j < a->ldrm; ++j) {
+                if (vz && j == desc.vz_index) { a->rm_col[(size_t)b * m + i] = rm_copy[row + j]; continue; }
+                if (std::memcmp(&rm_copy[row + j], &a->rm[row + j], D) != 0) {
+                    set_error("hyper step changed rm outside the vz_offset column (row " + std::to_string(i) + ", column " + std::to_string(j) + ")");
+                    return HIPDRT_E_NUMERIC;
+                }
+            }
+        }
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
 // ---- plan ---------------------------------------------------------------------------------------------------
 
 void hipdrt_default_fit_opts(hipdrt_fit_opts* o) {

@@ -224,6 +224,7 @@ struct FitState {
     int *hist_qp, *hist_rows;
 };
 size_t hyper_lds_bytes(int n, int m, int ns);
+bool hyper_lds_form(int n, int m, int ns, int toeplitz, bool outlier, int* form, size_t* lds_bytes);
 int launch_prep(hipStream_t s, const FitState& st, int B);
 // stage 0: weights from the first overfit only (outlier branch); stage 1: final est_weights -> init weights, x reset
 // stage 2: est_weights of rows [r0, r1) only (init_weights_separately); stage 3: final step only

@@ -1019,21 +1019,37 @@ void launch_scale_weights(hipStream_t s, const FitState& st, int B, double facto
     hipLaunchKernelGGL(scale_weights_kernel, dim3((st.m + 255) / 256, B), dim3(256), 0, s, st, factor);
 }
 
-int launch_hyper(hipStream_t s, const FitState& st_in, int B, int it) {
-    FitState st = st_in;
-    const size_t extra = st.opts.outlier_p > 0.0 ? 2 * (size_t)st.m * sizeof(double) : 0;
-    size_t lds = hyper_lds_bytes(st.n, st.m, st.ns) + extra;
-    if (lds > kLdsLimit && st.toeplitz_m && extra == 0) {
+// which of hyper_kernel's three LDS layouts a problem gets, and its dynamic LDS: form 1 = the mirrored Toeplitz columns beside the
+// two m-vectors, 2 = the columns inside the second m-vector (toeplitz_m == 2), 0 = the general row-streaming form (no columns in
+// LDS).  false: no layout fits.  The one place this is decided: launch_hyper and hipdrt_debug_hyper_form both ask here.
+bool hyper_lds_form(int n, int m, int ns, int toeplitz, bool outlier, int* form, size_t* lds_bytes) {
+    const size_t extra = outlier ? 2 * (size_t)m * sizeof(double) : 0;
+    size_t lds = hyper_lds_bytes(n, m, ns) + extra;
+    int f = toeplitz ? 1 : 0;
+    if (lds > kLdsLimit && toeplitz && extra == 0) {
         // large joint fits (config 5: m = 5120, n = 1078): no room for the mirrored Toeplitz columns NEXT to the two
         // m-vectors -- they share the second one's space (see hyper_kernel); if even that does not fit, the general
         // row-streaming form of the same updates reads the penalty blocks from L2 instead
-        const size_t nd = (size_t)(st.n - st.ns), tl = (size_t)st.m > nd ? (size_t)st.m : nd, cols = 3 * (2 * nd - 1);
+        const size_t nd = (size_t)(n - ns), tl = (size_t)m > nd ? (size_t)m : nd, cols = 3 * (2 * nd - 1);
         const size_t second = tl > nd + cols ? tl : nd + cols;
-        const size_t compact = ((size_t)st.n + 4 * nd + tl + second) * sizeof(double);
-        if (compact <= kLdsLimit) { st.toeplitz_m = 2; lds = compact; }
-        else { st.toeplitz_m = 0; lds -= cols * sizeof(double); }
+        const size_t compact = ((size_t)n + 4 * nd + tl + second) * sizeof(double);
+        if (compact <= kLdsLimit) { f = 2; lds = compact; }
+        else { f = 0; lds -= cols * sizeof(double); }
     }
-    if (lds > kLdsLimit) { set_error("hyper-parameter kernel: problem too large for LDS (m, n)"); return HIPDRT_E_INVALID; }
+    *form = f;
+    *lds_bytes = lds;
+    return lds <= kLdsLimit;
+}
+
+int launch_hyper(hipStream_t s, const FitState& st_in, int B, int it) {
+    FitState st = st_in;
+    int form = 0;
+    size_t lds = 0;
+    if (!hyper_lds_form(st.n, st.m, st.ns, st.toeplitz_m, st.opts.outlier_p > 0.0, &form, &lds)) {
+        set_error("hyper-parameter kernel: problem too large for LDS (m, n)");
+        return HIPDRT_E_INVALID;
+    }
+    if (st.toeplitz_m && form != 1) st.toeplitz_m = form;
     if (int rc = set_lds(reinterpret_cast<const void*>(hyper_kernel), lds, "hyper_kernel")) return rc;
     if (st.premv && st.premv_batched && st.opts.outlier_p <= 0.0) {
         // many fits sharing rm and vmm: both products of estimate_weights for the whole batch on the matrix pipe

@@ -3,7 +3,9 @@
  * NOT part of the drop-in boundary (include/hipdrt.h): nothing here replaces a reference interface, and the Python host
  * layer's product path never calls these.  They exist for tests/ (kernel-choice independence of the results) and tools/
  * (in-kernel phase counters of a PROFILE build, occupancy queries).  Every hook takes a context: there is no process-wide
- * switch.
+ * switch.  The kernels of the fit loop each have a hook that runs their launcher as it is on host arrays: hipdrt_debug_gram_l2
+ * (Gram, q), hipdrt_debug_hyper_step (the hyper-parameter step in its three product forms), hipdrt_debug_kk_stats,
+ * hipdrt_debug_apply_rows.
  */
 #ifndef HIPDRT_DEBUG_H
 #define HIPDRT_DEBUG_H
@@ -76,6 +78,49 @@ typedef struct hipdrt_debug_gram_args {
 int hipdrt_debug_gram_l2(hipdrt_ctx* ctx, const hipdrt_debug_gram_args* a);
 /* test hook: launch_pack_p -- row-major symmetric P [B][n][ldp] (host) -> Ppk [B][nchp * nchp * 256] (host, in/out as above) */
 int hipdrt_debug_pack_p(hipdrt_ctx* ctx, int B, int n, const double* P, int ldp, double* Ppk);
+
+/* test hook (tests/test_gpu_hyper.py): one hyper-parameter step -- launch_hyper (csrc/hyper.hip) as it is: hyper_kernel, with the
+ * products of estimate_weights inside it, from premv_kernel or from batch_products_kernel<0> / <1> -- on host arrays.  The hook
+ * fills a FitState (csrc/common.hpp) from this struct.  Arrays are host memory, row-major.  The per-spectrum arrays are in/out:
+ * their host contents are uploaded, so what comes back differs from them only where a kernel wrote.  On the device every one of
+ * them has a border of marker bytes on either side; HIPDRT_E_NUMERIC when a border changed, or when any entry of a per-spectrum rm
+ * other than the vz_offset column did.                                                                                        */
+typedef struct hipdrt_debug_hyper_args {
+    int B, m, n, ns, ldrm, ldm;    /* ns < n: there is a DRT block; ldrm, ldm >= n                                             */
+    const double* rm;       /* [rm_batched ? B : 1][m][ldrm]                                                                */
+    int rm_batched;
+    const double* vmm;      /* [m][m]                                                                                       */
+    const double* mk[3];    /* each [n][ldm]                                                                                */
+    int toeplitz;           /* 1: the DRT blocks are symmetric Toeplitz (verified on the host, refused when they are not)      */
+    int toep_reach;         /* -1, or a distance beyond which every DRT block is exactly zero (refused when it is too small)   */
+    const double* x;        /* [B][n] the QP's result                                                                       */
+    double* x_in;           /* [B][n]                                                                                       */
+    double* s;              /* [B][3][n]                                                                                    */
+    double *rho, *xmx;      /* [B][3]                                                                                       */
+    double *rv, *est_w, *w; /* [B][m]                                                                                       */
+    double *var_floor, *coef_scale;        /* [B]                                                                          */
+    const int* qp_status;   /* [B]                                                                                          */
+    int *active, *fit_status, *outer_iters;   /* [B]                                                                       */
+    int* n_active;          /* [1]: incremented by every spectrum that goes on                                              */
+    double* outlier_t;      /* [B][m] or NULL                                                                               */
+    const hipdrt_fit_opts* opts;
+    int it, continue_mode, min_iter;       /* continue_mode 0, 1 or 2 (FitState)                                           */
+    double basis_area;
+    const hipdrt_prepared_desc* desc;      /* or NULL: not a prepared plan.  Used: ns-independent fields dop_*, vz_index, vb_*,
+                                              num_chrono, chrono_vmm_uniform                                                */
+    double *dop_rho, *dop_xmx;             /* [B][3], required with desc                                                    */
+    const double* vz_strength;             /* [m], required when desc->vz_index >= 0                                        */
+    const double* vz_entry;                /* [B][m] or NULL                                                                */
+    double* rm_col;         /* out [rm_batched ? B : 1][m]: column vz_index of rm after the step (desc->vz_index >= 0)        */
+    int products;           /* 0: inside hyper_kernel, 1: premv_kernel, 2: batch_products_kernel (needs a shared rm, no vz
+                               column and outlier_p <= 0, as the fit loop's own choice does)                                */
+} hipdrt_debug_hyper_args;
+/* Refuses every combination that could make a kernel read or write out of bounds, and a problem no LDS form holds (nothing is
+ * launched then).                                                                                                           */
+int hipdrt_debug_hyper_step(hipdrt_ctx* ctx, const hipdrt_debug_hyper_args* a);
+/* test hook: the LDS form launch_hyper picks for a problem -- *form 1: Toeplitz columns beside the two m-vectors, 2: inside the
+ * second m-vector, 0: the general row-streaming form -- and its dynamic LDS in bytes; HIPDRT_E_INVALID when none fits.        */
+int hipdrt_debug_hyper_form(hipdrt_ctx* ctx, int n, int m, int ns, int toeplitz, int outlier, int* form, long long* lds_bytes);
 
 /* test hook (tests/test_gpu_kk.py): the statistics stage of hipdrt_plan_kk_screen's kernel as it is, on host residuals --
  * freq [nf] strictly ascending or descending, err_re / err_im [B][nf]; out (any may be NULL): std [B], outlier_mask [B][nf],
