@@ -109,47 +109,76 @@ __global__ __launch_bounds__(256, 5) void gram_kernel(int m, int n, const double
 #pragma unroll
     for (int s = 0; s < 4; ++s) acc[s] = (v4d){0.0, 0.0, 0.0, 0.0};
 
-    // staging map: thread -> (k = tid/16, 4 consecutive columns), fetched as two 16-byte loads when the
-    // leading dimension and n are even (always true for the plan's matrices); the strip: (k = tid/16, column tid%16)
+    // staging map: thread -> (k = tid/16, 4 consecutive columns); the strip: (k = tid/16, column tid%16).  How a slab is fetched is
+    // decided here, once per workgroup, and compiled into the K loop as FORM (a choice made inside the loop is a join at which
+    // the compiler waits for every load in flight -- a memory round trip per slab in front of the MFMAs):
+    //   FORM 0, full: every staged column lies inside n (the strip's 16 apart), m is a multiple of the slab and the rows are
+    //     16-byte aligned -- every workgroup of the plan's matrices.  Unconditional 16-byte loads from two per-thread pointers that
+    //     advance a slab at a time; the strip's operand is read from a column clamped into the row and masked when it is used.
+    //   FORM 1, general with 16-byte loads (even lda and n, aligned rows), FORM 2, general with 8-byte loads: edge tiles, slab
+    //     tails, odd sizes; every load under its own bounds test.
     const int sk = tid >> 4, sc = (tid & 15) * 4;
-    const bool vec2 = ((lda | n) & 1) == 0;
-    // slab k0+GK is fetched (global -> registers) while slab k0 is multiplied out of LDS; the products with w are
-    // formed only when the slab is written to LDS, so nothing waits on the loads inside the MFMA loop
+    const bool vec2 = ((lda | n) & 1) == 0 && (reinterpret_cast<size_t>(A) & 15) == 0;
+    const bool full = vec2 && m >= GK && (m & (GK - 1)) == 0 && i0 + GT <= n && (diag || j0 + GT <= n);
+    const bool smask = strip && s0 + (tid & 15) < n;         // the strip's column of this thread holds data
+    // slab k0+GK is fetched (global -> registers) while slab k0 is multiplied out of LDS; the products with w are formed only
+    // when the slab is written to LDS, so the loads are waited for at the head of the next slab and nowhere else
     double vi[4], vj[4], wkr = 0.0;
-    // (DIAG, TURN are the workgroup's `diag` and the wavefront's `turn` as types: the K loop is compiled once per kind, each with
-    // the registers it needs)
-    auto fetch = [&](auto DIAG, int k0) {
+    const double *pI = nullptr, *pJ = nullptr;               // FORM 0: the thread's columns in the row of the slab to fetch next
+    // (DIAG, TURN, FORM are the workgroup's `diag`, the wavefront's `turn` and the fetch form as types: the K loop is compiled
+    // once per kind, each with the registers it needs)
+    auto fetch = [&](auto DIAG, auto FORM, int k0) {
         constexpr bool D = decltype(DIAG)::value;
-        const int k = k0 + sk;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { vi[e] = 0.0; vj[e] = 0.0; }
-        wkr = 0.0;
-        if (k < m) {
-            wkr = wb[k];
-            const double* row = A + (size_t)k * lda;
-            if (vec2) {
-#pragma unroll
-                for (int e = 0; e < 4; e += 2) {
-                    const int ci = i0 + sc + e, cj = j0 + sc + e;
-                    if (ci < n) { const double2 t = *reinterpret_cast<const double2*>(row + ci); vi[e] = t.x; vi[e + 1] = t.y; }
-                    if (!D && cj < n) { const double2 t = *reinterpret_cast<const double2*>(row + cj); vj[e] = t.x; vj[e + 1] = t.y; }
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int ci = i0 + sc + e, cj = j0 + sc + e;
-                    if (ci < n) vi[e] = row[ci];
-                    if (!D && cj < n) vj[e] = row[cj];
-                }
+        constexpr int F = decltype(FORM)::value;
+        if constexpr (F == 0) {
+            wkr = wb[k0 + sk];
+            const double2 t0 = *reinterpret_cast<const double2*>(pI), t1 = *reinterpret_cast<const double2*>(pI + 2);
+            vi[0] = t0.x; vi[1] = t0.y; vi[2] = t1.x; vi[3] = t1.y;
+            if constexpr (!D) {
+                const double2 u0 = *reinterpret_cast<const double2*>(pJ), u1 = *reinterpret_cast<const double2*>(pJ + 2);
+                vj[0] = u0.x; vj[1] = u0.y; vj[2] = u1.x; vj[3] = u1.y;
+            } else if (strip) {
+                vj[0] = *pJ;
             }
-            if (D && strip && s0 + (tid & 15) < n) vj[0] = row[s0 + (tid & 15)];
+            pI += (size_t)GK * lda;
+            pJ += (size_t)GK * lda;
+        } else {
+            const int k = k0 + sk;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { vi[e] = 0.0; vj[e] = 0.0; }
+            wkr = 0.0;
+            if (k < m) {
+                wkr = wb[k];
+                const double* row = A + (size_t)k * lda;
+                if constexpr (F == 1) {
+#pragma unroll
+                    for (int e = 0; e < 4; e += 2) {
+                        const int ci = i0 + sc + e, cj = j0 + sc + e;
+                        if (ci < n) { const double2 t = *reinterpret_cast<const double2*>(row + ci); vi[e] = t.x; vi[e + 1] = t.y; }
+                        if (!D && cj < n) { const double2 t = *reinterpret_cast<const double2*>(row + cj); vj[e] = t.x; vj[e + 1] = t.y; }
+                    }
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int ci = i0 + sc + e, cj = j0 + sc + e;
+                        if (ci < n) vi[e] = row[ci];
+                        if (!D && cj < n) vj[e] = row[cj];
+                    }
+                }
+                if (D && smask) vj[0] = row[s0 + (tid & 15)];
+            }
         }
     };
     // 16x16 sub-tiles that are pure padding (beyond n) or lie above the diagonal (the epilogue takes those elements
     // from the mirror) are not multiplied at all
-    auto kloop = [&](auto DIAG, auto TURN) {
+    auto kloop = [&](auto DIAG, auto TURN, auto FORM) {
         constexpr bool D = decltype(DIAG)::value;
-        fetch(DIAG, 0);
+        constexpr bool FULL = decltype(FORM)::value == 0;
+        if constexpr (FULL) {
+            pI = A + (size_t)sk * lda + i0 + sc;
+            pJ = A + (size_t)sk * lda + (D ? (smask ? s0 + (tid & 15) : n - 1) : j0 + sc);
+        }
+        fetch(DIAG, FORM, 0);
         for (int k0 = 0; k0 < m; k0 += GK) {
             __syncthreads();   // previous slab fully consumed
             *reinterpret_cast<double2*>(&sI[sk * GLD + sc]) = make_double2(wkr * vi[0], wkr * vi[1]);
@@ -158,10 +187,10 @@ __global__ __launch_bounds__(256, 5) void gram_kernel(int m, int n, const double
                 *reinterpret_cast<double2*>(&sJ[sk * GLD + sc]) = make_double2(wkr * vj[0], wkr * vj[1]);
                 *reinterpret_cast<double2*>(&sJ[sk * GLD + sc + 2]) = make_double2(wkr * vj[2], wkr * vj[3]);
             } else if (strip) {
-                sI[sk * GLD + GT + (tid & 15)] = wkr * vj[0];
+                sI[sk * GLD + GT + (tid & 15)] = wkr * (FULL && !smask ? 0.0 : vj[0]);
             }
             __syncthreads();
-            if (k0 + GK < m) fetch(DIAG, k0 + GK);
+            if (k0 + GK < m) fetch(DIAG, FORM, k0 + GK);
             if (!D) {
                 const int wi = (wv >> 1) * 32, wj = (wv & 1) * 32;     // four sub-tiles from four operand reads
 #pragma unroll
@@ -171,10 +200,11 @@ __global__ __launch_bounds__(256, 5) void gram_kernel(int m, int n, const double
                     double a1 = sI[kr * GLD + wi + 16 + (lane & 15)];
                     double b0 = sJ[kr * GLD + wj + (lane & 15)];
                     double b1 = sJ[kr * GLD + wj + 16 + (lane & 15)];
-                    if (need00) acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(b0, a0, acc[0], 0, 0, 0);
-                    if (need01) acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(b1, a0, acc[1], 0, 0, 0);
-                    if (need10) acc[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(b0, a1, acc[2], 0, 0, 0);
-                    if (need11) acc[3] = __builtin_amdgcn_mfma_f64_16x16x4f64(b1, a1, acc[3], 0, 0, 0);
+                    // (a full workgroup has no padding sub-tile)
+                    if (FULL || need00) acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(b0, a0, acc[0], 0, 0, 0);
+                    if (FULL || need01) acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(b1, a0, acc[1], 0, 0, 0);
+                    if (FULL || need10) acc[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(b0, a1, acc[2], 0, 0, 0);
+                    if (FULL || need11) acc[3] = __builtin_amdgcn_mfma_f64_16x16x4f64(b1, a1, acc[3], 0, 0, 0);
                 }
             } else {
                 // any wavefront reads any 16 columns of the slab (the strip's are columns 64 ... 79); one loop per turn, so
@@ -184,11 +214,16 @@ __global__ __launch_bounds__(256, 5) void gram_kernel(int m, int n, const double
             }
         }
     };
-    if (!diag) kloop(std::false_type{}, std::integral_constant<int, 0>{});
-    else if (turn == 0) kloop(std::true_type{}, std::integral_constant<int, 0>{});
-    else if (turn == 1) kloop(std::true_type{}, std::integral_constant<int, 1>{});
-    else if (turn == 2) kloop(std::true_type{}, std::integral_constant<int, 2>{});
-    else kloop(std::true_type{}, std::integral_constant<int, 3>{});
+    auto kform = [&](auto DIAG, auto TURN) {
+        if (full) kloop(DIAG, TURN, std::integral_constant<int, 0>{});
+        else if (vec2) kloop(DIAG, TURN, std::integral_constant<int, 1>{});
+        else kloop(DIAG, TURN, std::integral_constant<int, 2>{});
+    };
+    if (!diag) kform(std::false_type{}, std::integral_constant<int, 0>{});
+    else if (turn == 0) kform(std::true_type{}, std::integral_constant<int, 0>{});
+    else if (turn == 1) kform(std::true_type{}, std::integral_constant<int, 1>{});
+    else if (turn == 2) kform(std::true_type{}, std::integral_constant<int, 2>{});
+    else kform(std::true_type{}, std::integral_constant<int, 3>{});
 
     // sqrt(s_k) of the tile's rows / columns once per workgroup (the L2 epilogue needs them per element); they take
     // over the slab buffers, so the kernel needs 20 kB of LDS and eight workgroups fit a CU
