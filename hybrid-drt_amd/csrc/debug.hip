@@ -1,0 +1,370 @@
+// Test and diagnostic hooks of include/hipdrt_debug.h: context switches, and single launchers run on host arrays exactly as
+// the fit loop runs them.  (hipdrt_debug_stream_pool sits with the pool in api.hip.)
+#include <cstring>
+
+#include "plan.hpp"
+
+extern "C" {
+
+int hipdrt_debug_qp_group(hipdrt_ctx* ctx, int members) try {
+    HIPDRT_REQUIRE(ctx, "NULL pointer");
+    ctx->qp_force_group = members;
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+int hipdrt_debug_qp_waves(hipdrt_ctx* ctx, int waves) try {
+    HIPDRT_REQUIRE(ctx, "NULL pointer");
+    HIPDRT_REQUIRE(waves == -1 || waves == 4 || waves == 8, "waves: 4, 8 or -1");
+    ctx->qp_waves = waves;
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+int hipdrt_debug_exact_zero_shortcuts(hipdrt_ctx* ctx, int on) try {
+    HIPDRT_REQUIRE(ctx, "NULL pointer");
+    ctx->zero_shortcuts = on ? 1 : 0;
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+int hipdrt_debug_qp_occupancy(hipdrt_ctx* ctx, int threads, int n) try {
+    if (!ctx || hipSetDevice(ctx->device) != hipSuccess) return -1;
+    return qp_occupancy(threads, n);
+} HIPDRT_CATCH
+
+int hipdrt_qp_profile(hipdrt_ctx* ctx, unsigned long long* cycles, int n, int reset) try {
+    HIPDRT_REQUIRE(ctx && cycles, "NULL pointer");
+    TRY(enter(ctx));
+    HIPDRT_CHECK(hipStreamSynchronize(ctx->stream));
+    return qp_profile_read(cycles, n, reset) < 0 ? HIPDRT_E_HIP : HIPDRT_OK;
+} HIPDRT_CATCH
+
+// test hook (include/hipdrt_debug.h): launch_gram_l2 / launch_qvec exactly as the fit loop calls them, on host arrays.  Every
+// extent a kernel derives an address from is checked here: the kernels themselves trust their caller.
+int hipdrt_debug_gram_l2(hipdrt_ctx* ctx, const hipdrt_debug_gram_args* a) try {
+    HIPDRT_REQUIRE(ctx && a && a->A && a->w, "NULL pointer");
+    const int B = a->B, m = a->m, n = a->n;
+    HIPDRT_REQUIRE(B >= 1 && B <= 4096 && m >= 1 && m <= 8192 && n >= 1 && n <= 4096, "1 <= B <= 4096, 1 <= m <= 8192, 1 <= n <= 4096");
+    HIPDRT_REQUIRE(a->lda >= n, "lda >= n");
+    HIPDRT_REQUIRE(a->P || a->Ppk, "at least one of P / Ppk");
+    HIPDRT_REQUIRE(!a->P || a->ldp >= n, "ldp >= n");
+    HIPDRT_REQUIRE(!a->y || a->q, "y without q");
+    const bool hyper = a->s != nullptr;
+    if (hyper) {
+        HIPDRT_REQUIRE(a->mk[0] && a->mk[1] && a->mk[2], "hyper-parameter form: three penalty matrices");
+        HIPDRT_REQUIRE(a->ldm >= n, "ldm >= n");
+        HIPDRT_REQUIRE(a->ns >= 0 && a->ns <= n, "0 <= ns <= n");
+        HIPDRT_REQUIRE(a->dop_size >= 0 && (a->dop_size == 0 || (a->dop_start >= 0 && a->dop_start + a->dop_size <= a->ns)),
+                       "x_dop block outside the special block [0, ns)");
+        HIPDRT_REQUIRE(a->dop_size == 0 || !a->rho || a->dop_rho, "dop_rho missing");
+        HIPDRT_REQUIRE(a->toep_maxd >= -1 && a->toep_maxd < n, "-1 <= toep_maxd < n");
+        HIPDRT_REQUIRE(!a->toep || n - a->ns >= 1, "Toeplitz form needs a DRT block (n - ns >= 1)");
+    } else if (a->l2) {
+        HIPDRT_REQUIRE(a->ldl2 >= n, "ldl2 >= n");
+    }
+    hipStream_t st; TRY(enter(ctx, &st));
+    const size_t D = sizeof(double);
+    const int nchp = qp_nchp(n);
+    const size_t ppk = qp_ppk_doubles(n);
+    DevBuf dA, dw, dy, dl1, dl2, dmk[3], ds, drho, ddrho, dact, dP, dPpk, dq;
+    TRY(upload(dA, a->A, (size_t)(a->a_batched ? B : 1) * m * a->lda * D, st));
+    TRY(upload(dw, a->w, (size_t)B * m * D, st));
+    if (a->y) TRY(upload(dy, a->y, (size_t)B * m * D, st));
+    if (a->l1) TRY(upload(dl1, a->l1, (size_t)n * D, st));
+    if (a->active) TRY(upload(dact, a->active, (size_t)B * sizeof(int), st));
+    GramL2 g{};
+    if (hyper) {
+        for (int k = 0; k < 3; ++k) {
+            TRY(upload(dmk[k], a->mk[k], (size_t)n * a->ldm * D, st));
+            g.mk[k] = dmk[k].d(); g.dfac[k] = a->dfac[k]; g.dop_dfac[k] = a->dop_dfac[k];
+        }
+        TRY(upload(ds, a->s, (size_t)B * 3 * n * D, st));
+        if (a->rho) TRY(upload(drho, a->rho, (size_t)B * 3 * D, st));
+        if (a->rho && a->dop_size > 0) TRY(upload(ddrho, a->dop_rho, (size_t)B * 3 * D, st));
+        g.ldm = a->ldm; g.s = ds.d(); g.rho = a->rho ? drho.d() : nullptr; g.use_rho = a->rho ? 1 : 0;
+        g.ns = a->ns; g.sym = a->sym ? 1 : 0; g.toep = a->toep ? 1 : 0; g.toep_maxd = a->toep_maxd; g.spec_zero = a->spec_zero ? 1 : 0;
+        g.dop_start = a->dop_start; g.dop_size = a->dop_size; g.dop_rho = ddrho.d();
+    } else if (a->l2) {
+        TRY(upload(dl2, a->l2, (size_t)(a->l2_batched ? B : 1) * n * a->ldl2 * D, st));
+        g.l2 = dl2.d(); g.l2_stride = a->l2_batched ? (long long)n * a->ldl2 : 0; g.ldl2 = a->ldl2;
+    }
+    if (a->P) TRY(upload(dP, a->P, (size_t)B * n * a->ldp * D, st));
+    if (a->Ppk) TRY(upload(dPpk, a->Ppk, (size_t)B * ppk * D, st));
+    if (a->y) TRY(upload(dq, a->q, (size_t)B * n * D, st));
+    const long long astr = a->a_batched ? (long long)m * a->lda : 0;
+    launch_gram_l2(st, B, m, n, dA.d(), a->lda, dw.d(), g, a->P ? dP.d() : nullptr, a->ldp, (long long)n * a->ldp,
+                   a->active ? dact.i() : nullptr, a->Ppk ? dPpk.d() : nullptr, (long long)ppk, nchp, astr);
+    LAUNCH_OK();
+    if (a->y) {
+        launch_qvec(st, B, m, n, dA.d(), a->lda, dw.d(), dy.d(), a->l1 ? dl1.d() : nullptr, a->l1_scalar, dq.d(),
+                    a->active ? dact.i() : nullptr, astr);
+        LAUNCH_OK();
+    }
+    if (a->P) HIPDRT_CHECK(hipMemcpyAsync(a->P, dP.p, (size_t)B * n * a->ldp * D, hipMemcpyDeviceToHost, st));
+    if (a->Ppk) HIPDRT_CHECK(hipMemcpyAsync(a->Ppk, dPpk.p, (size_t)B * ppk * D, hipMemcpyDeviceToHost, st));
+    if (a->y) HIPDRT_CHECK(hipMemcpyAsync(a->q, dq.p, (size_t)B * n * D, hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+int hipdrt_debug_pack_p(hipdrt_ctx* ctx, int B, int n, const double* P, int ldp, double* Ppk) try {
+    HIPDRT_REQUIRE(ctx && P && Ppk, "NULL pointer");
+    HIPDRT_REQUIRE(B >= 1 && B <= 4096 && n >= 1 && n <= 4096 && ldp >= n, "1 <= B <= 4096, 1 <= n <= 4096, ldp >= n");
+    hipStream_t st; TRY(enter(ctx, &st));
+    const size_t ppk = qp_ppk_doubles(n);
+    DevBuf dP, dPpk;
+    TRY(upload(dP, P, (size_t)B * n * ldp * sizeof(double), st));
+    TRY(upload(dPpk, Ppk, (size_t)B * ppk * sizeof(double), st));
+    launch_pack_p(st, B, n, dP.d(), ldp, (long long)n * ldp, dPpk.d(), (long long)ppk, qp_nchp(n));
+    LAUNCH_OK();
+    HIPDRT_CHECK(hipMemcpyAsync(Ppk, dPpk.p, (size_t)B * ppk * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+// test hook (include/hipdrt_debug.h): launch_hyper as the fit loop calls it, on host arrays.  Every extent a kernel derives an
+// address from is checked here.  In/out arrays live on the device between two borders of marker bytes.
+namespace {
+struct Guarded {
+    static constexpr size_t G = 128;           // border bytes on either side
+    static constexpr unsigned char MARK = 0xA5;
+    DevBuf buf;
+    void* host = nullptr;
+    size_t bytes = 0;
+    const char* name = "";
+    std::vector<unsigned char> stage;
+    int up(const char* what, void* h, size_t nbytes, hipStream_t st) {
+        name = what; host = h; bytes = nbytes;
+        stage.assign(nbytes + 2 * G, MARK);
+        if (h) std::memcpy(stage.data() + G, h, nbytes);
+        HIPDRT_CHECK(buf.alloc(stage.size()));
+        HIPDRT_CHECK(hipMemcpyAsync(buf.p, stage.data(), stage.size(), hipMemcpyHostToDevice, st));
+        return 0;
+    }
+    double* dd() const { return reinterpret_cast<double*>(static_cast<unsigned char*>(buf.p) + G); }
+    int* di() const { return reinterpret_cast<int*>(static_cast<unsigned char*>(buf.p) + G); }
+    int fetch(hipStream_t st) { HIPDRT_CHECK(hipMemcpyAsync(stage.data(), buf.p, stage.size(), hipMemcpyDeviceToHost, st)); return 0; }
+    int check() {
+        for (size_t i = 0; i < G; ++i)
+            if (stage[i] != MARK || stage[G + bytes + i] != MARK) {
+                set_error(std::string("hyper step wrote outside ") + name);
+                return HIPDRT_E_NUMERIC;
+            }
+        if (host) std::memcpy(host, stage.data() + G, bytes);
+        return 0;
+    }
+};
+}  // namespace
+
+int hipdrt_debug_hyper_form(hipdrt_ctx* ctx, int n, int m, int ns, int toeplitz, int outlier, int* form, long long* lds_bytes) try {
+    HIPDRT_REQUIRE(ctx && form && lds_bytes, "NULL pointer");
+    HIPDRT_REQUIRE(m >= 1 && m <= 8192 && n >= 1 && n <= 4096 && ns >= 0 && ns < n, "1 <= m <= 8192, 0 <= ns < n <= 4096");
+    size_t lds = 0;
+    const bool ok = hyper_lds_form(n, m, ns, toeplitz ? 1 : 0, outlier != 0, form, &lds);
+    *lds_bytes = (long long)lds;
+    if (!ok) { set_error("hyper-parameter kernel: problem too large for LDS (m, n)"); return HIPDRT_E_INVALID; }
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+int hipdrt_debug_hyper_step(hipdrt_ctx* ctx, const hipdrt_debug_hyper_args* a) try {
+    HIPDRT_REQUIRE(ctx && a, "NULL pointer");
+    const int B = a->B, m = a->m, n = a->n, ns = a->ns, nd = n - ns;
+    HIPDRT_REQUIRE(B >= 1 && B <= 4096 && m >= 1 && m <= 8192 && n >= 1 && n <= 4096, "1 <= B <= 4096, 1 <= m <= 8192, 1 <= n <= 4096");
+    HIPDRT_REQUIRE(ns >= 0 && nd >= 1, "0 <= ns < n: the step needs a DRT block");
+    HIPDRT_REQUIRE(a->ldrm >= n && a->ldm >= n, "ldrm >= n, ldm >= n");
+    HIPDRT_REQUIRE(a->rm && a->vmm && a->mk[0] && a->mk[1] && a->mk[2] && a->opts, "rm, vmm, three penalty matrices, opts");
+    HIPDRT_REQUIRE(a->x && a->x_in && a->s && a->rho && a->xmx && a->rv && a->est_w && a->w && a->var_floor && a->coef_scale,
+                   "per-spectrum state: x, x_in, s, rho, xmx, rv, est_w, w, var_floor, coef_scale");
+    HIPDRT_REQUIRE(a->qp_status && a->active && a->fit_status && a->outer_iters && a->n_active, "qp_status, active, fit_status, outer_iters, n_active");
+    HIPDRT_REQUIRE(a->continue_mode >= 0 && a->continue_mode <= 2 && a->it >= 0, "continue_mode 0, 1 or 2; it >= 0");
+    HIPDRT_REQUIRE(a->products >= 0 && a->products <= 2, "products 0, 1 or 2");
+    HIPDRT_REQUIRE(a->toep_reach >= -1, "toep_reach >= -1");
+    const bool outl = a->opts->outlier_p > 0.0;
+    const bool prep = a->desc != nullptr;
+    hipdrt_prepared_desc desc{};
+    desc.vz_index = -1;
+    if (prep) {
+        desc = *a->desc;
+        HIPDRT_REQUIRE(a->dop_rho && a->dop_xmx, "a prepared step needs dop_rho and dop_xmx");
+        HIPDRT_REQUIRE(desc.dop_size >= 0 && (desc.dop_size == 0 || (desc.dop_start >= 0 && desc.dop_start + desc.dop_size <= ns)),
+                       "x_dop block outside the special block [0, ns)");
+        HIPDRT_REQUIRE(desc.dop_size <= nd, "x_dop block larger than the DRT block (the kernel's LDS vectors hold n - ns entries)");
+        HIPDRT_REQUIRE(desc.vz_index >= -1 && desc.vz_index < n, "-1 <= vz_index < n");
+        HIPDRT_REQUIRE(desc.vb_start >= 0 && desc.vb_size >= 0 && desc.vb_start + desc.vb_size <= n, "v_baseline columns outside [0, n)");
+        HIPDRT_REQUIRE(desc.num_chrono >= 0 && desc.num_chrono <= m, "0 <= num_chrono <= m");
+        if (desc.vz_index >= 0) {
+            HIPDRT_REQUIRE(a->vz_strength && a->rm_col, "vz_offset column: vz_strength and rm_col");
+            HIPDRT_REQUIRE(a->rm_batched || B == 1, "vz_offset column: one response matrix per spectrum");
+        }
+        desc.m = m; desc.n = n; desc.ns = ns; desc.toeplitz_m = a->toeplitz ? 1 : 0;
+    }
+    const bool vz = prep && desc.vz_index >= 0;
+    HIPDRT_REQUIRE(!a->vz_entry || vz, "vz_entry without a vz_offset column");
+    if (a->products == 1) HIPDRT_REQUIRE(!outl, "products = 1: outlier_p <= 0");
+    if (a->products == 2) HIPDRT_REQUIRE(!a->rm_batched && !outl && !vz, "products = 2: a shared rm, no vz_offset column, outlier_p <= 0");
+    // the Toeplitz claim and the reach, on the host
+    if (a->toeplitz) {
+        int reach = 0;
+        for (int k = 0; k < 3; ++k) {
+            const double* blk = a->mk[k] + (size_t)ns * a->ldm + ns;
+            for (int i = 0; i < nd; ++i)
+                for (int j = 0; j < nd; ++j) {
+                    const int d = i > j ? i - j : j - i;
+                    const double v = blk[(size_t)i * a->ldm + j];
+                    HIPDRT_REQUIRE(v == blk[d] || (v != v && blk[d] != blk[d]), "toeplitz = 1, but a DRT block is not symmetric Toeplitz");
+                }
+            for (int d = nd - 1; d > reach; --d)
+                if (blk[d] != 0.0) { reach = d; break; }
+        }
+        HIPDRT_REQUIRE(a->toep_reach < 0 || a->toep_reach >= reach, "toep_reach is smaller than the reach of the penalty blocks");
+    }
+    int form = 0;
+    size_t lds = 0;
+    if (!hyper_lds_form(n, m, ns, a->toeplitz ? 1 : 0, outl, &form, &lds)) {
+        set_error("hyper-parameter kernel: problem too large for LDS (m, n)");
+        return HIPDRT_E_INVALID;
+    }
+    hipStream_t st; TRY(enter(ctx, &st));
+    const size_t D = sizeof(double), I = sizeof(int);
+    const size_t nrm = (size_t)(a->rm_batched ? B : 1) * m * a->ldrm;
+    DevBuf dvmm, dmk[3], dx, dqs, dvs, dve, dpremv;
+    Guarded grm, gxin, gs, grho, gxmx, grv, gew, gw, gvf, gcs, gact, gfs, goi, gna, got, gdr, gdx;
+    std::vector<double> rm_copy(a->rm, a->rm + nrm);
+    TRY(grm.up("rm", rm_copy.data(), nrm * D, st));
+    TRY(upload(dvmm, a->vmm, (size_t)m * m * D, st));
+    for (int k = 0; k < 3; ++k) TRY(upload(dmk[k], a->mk[k], (size_t)n * a->ldm * D, st));
+    TRY(upload(dx, a->x, (size_t)B * n * D, st));
+    TRY(upload(dqs, a->qp_status, (size_t)B * I, st));
+    if (vz) TRY(upload(dvs, a->vz_strength, (size_t)m * D, st));
+    if (a->vz_entry) TRY(upload(dve, a->vz_entry, (size_t)B * m * D, st));
+    TRY(gxin.up("x_in", a->x_in, (size_t)B * n * D, st));
+    TRY(gs.up("s", a->s, (size_t)B * 3 * n * D, st));
+    TRY(grho.up("rho", a->rho, (size_t)B * 3 * D, st));
+    TRY(gxmx.up("xmx", a->xmx, (size_t)B * 3 * D, st));
+    TRY(grv.up("rv", a->rv, (size_t)B * m * D, st));
+    TRY(gew.up("est_w", a->est_w, (size_t)B * m * D, st));
+    TRY(gw.up("w", a->w, (size_t)B * m * D, st));
+    TRY(gvf.up("var_floor", a->var_floor, (size_t)B * D, st));
+    TRY(gcs.up("coef_scale", a->coef_scale, (size_t)B * D, st));
+    TRY(gact.up("active", a->active, (size_t)B * I, st));
+    TRY(gfs.up("fit_status", a->fit_status, (size_t)B * I, st));
+    TRY(goi.up("outer_iters", a->outer_iters, (size_t)B * I, st));
+    TRY(gna.up("n_active", a->n_active, I, st));
+    if (a->outlier_t) TRY(got.up("outlier_t", a->outlier_t, (size_t)B * m * D, st));
+    if (prep) {
+        TRY(gdr.up("dop_rho", a->dop_rho, (size_t)B * 3 * D, st));
+        TRY(gdx.up("dop_xmx", a->dop_xmx, (size_t)B * 3 * D, st));
+    }
+    FitState fs{};
+    fs.nf = 0; fs.m = m; fs.n = n; fs.ns = ns; fs.ldrm = a->ldrm; fs.ldm = a->ldm;
+    fs.toeplitz_m = a->toeplitz ? 1 : 0; fs.toep_reach = a->toeplitz ? a->toep_reach : -1;
+    fs.continue_mode = a->continue_mode; fs.min_iter = a->min_iter; fs.basis_area = a->basis_area; fs.opts = *a->opts;
+    fs.prepared = prep ? 1 : 0; fs.desc = desc;
+    fs.rm_stride = a->rm_batched ? (long long)m * a->ldrm : 0;
+    fs.rm = grm.dd(); fs.rm_rw = grm.dd();
+    fs.vz_strength = vz ? dvs.d() : nullptr; fs.vz_entry = a->vz_entry ? dve.d() : nullptr;
+    fs.dop_rho = prep ? gdr.dd() : nullptr; fs.dop_xmx = prep ? gdx.dd() : nullptr;
+    fs.outlier_t = a->outlier_t ? got.dd() : nullptr;
+    fs.vmm = dvmm.d(); fs.vmm_iw = dvmm.d();
+    for (int k = 0; k < 3; ++k) fs.mk[k] = dmk[k].d();
+    fs.rv = grv.dd(); fs.w = gw.dd(); fs.est_w = gew.dd();
+    fs.x = dx.d(); fs.x_in = gxin.dd(); fs.s = gs.dd(); fs.rho = grho.dd(); fs.xmx = gxmx.dd();
+    fs.coef_scale = gcs.dd(); fs.var_floor = gvf.dd();
+    fs.active = gact.di(); fs.outer_iters = goi.di(); fs.fit_status = gfs.di();
+    fs.qp_status = dqs.i(); fs.n_active = gna.di();
+    fs.hist_b = -1; fs.hist_cap = 0;
+    if (a->products) {
+        HIPDRT_CHECK(dpremv.alloc(3 * (size_t)B * m * D));
+        HIPDRT_CHECK(hipMemsetAsync(dpremv.p, 0xFF, 3 * (size_t)B * m * D, st));       // NaN where no product kernel wrote
+        fs.premv = dpremv.d();
+        fs.premv_batched = a->products == 2 ? 1 : 0;
+    }
+    TRY(launch_hyper(st, fs, B, a->it));
+    LAUNCH_OK();
+    Guarded* all[] = {&grm, &gxin, &gs, &grho, &gxmx, &grv, &gew, &gw, &gvf, &gcs, &gact, &gfs, &goi, &gna, &got, &gdr, &gdx};
+    for (Guarded* g : all) if (g->buf.p) TRY(g->fetch(st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    for (Guarded* g : all) if (g->buf.p) TRY(g->check());
+    // the response matrix: nothing but the vz_offset column may differ from what was uploaded
+    const int nmat = a->rm_batched ? B : 1;
+    for (int b = 0; b < nmat; ++b)
+        for (int i = 0; i < m; ++i) {
+            const size_t row = ((size_t)b * m + i) * a->ldrm;
+            for (int j = 0; j < a->ldrm; ++j) {
+                if (vz && j == desc.vz_index) { a->rm_col[(size_t)b * m + i] = rm_copy[row + j]; continue; }
+                if (std::memcmp(&rm_copy[row + j], &a->rm[row + j], D) != 0) {
+                    set_error("hyper step changed rm outside the vz_offset column (row " + std::to_string(i) + ", column " + std::to_string(j) + ")");
+                    return HIPDRT_E_NUMERIC;
+                }
+            }
+        }
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+// test hook (include/hipdrt_debug.h): stage B of kk_kernel as it is, on host residuals
+int hipdrt_debug_kk_stats(hipdrt_ctx* ctx, int B, int nf, const double* freq, const double* err_re, const double* err_im,
+                          const hipdrt_kk_opts* opts, double* std_out, int* outlier_mask, double* f_lim, int* i_lim,
+                          int* status) try {
+    HIPDRT_REQUIRE(ctx && freq && err_re && err_im, "NULL pointer");
+    HIPDRT_REQUIRE(B >= 1 && B <= 65535 && nf >= 1 && nf <= 4096, "1 <= B <= 65535, 1 <= nf <= 4096");
+    const int order = freq_monotone(freq, nf);
+    HIPDRT_REQUIRE(order != 0, "the frequency grid must be strictly ascending or descending");
+    hipdrt_kk_opts o;
+    if (opts) o = *opts; else hipdrt_default_kk_opts(&o);
+    TRY(kk_check_opts(o));
+    HIPDRT_REQUIRE(kk_lds_bytes(nf, 0, 0) <= 160 * 1024 - 256, "KK statistics: nf too large for one workgroup's LDS");
+    hipStream_t st; TRY(enter(ctx, &st));
+    DevBuf dfreq, dre, dim;
+    TRY(upload(dfreq, freq, (size_t)nf * sizeof(double), st));
+    TRY(upload(dre, err_re, (size_t)B * nf * sizeof(double), st));
+    TRY(upload(dim, err_im, (size_t)B * nf * sizeof(double), st));
+    KkArgs a{};
+    a.nf = nf; a.desc = order > 0 ? 1 : 0; a.freq = dfreq.d(); a.o = o; a.in_re = dre.d(); a.in_im = dim.d();
+    KkOut out;
+    TRY(out.alloc(a, B, nf, false, false, false, false, std_out, outlier_mask, f_lim, i_lim, status));
+    TRY(launch_kk(st, nullptr, a, B));
+    LAUNCH_OK();
+    TRY(KkOut::back(std_out, out.sd, st)); TRY(KkOut::back(outlier_mask, out.mask, st));
+    TRY(KkOut::back(f_lim, out.flim, st)); TRY(KkOut::back(i_lim, out.ilim, st)); TRY(KkOut::back(status, out.status, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+// test hook (include/hipdrt_debug.h): apply_rows_kernel as it is, on host arrays.  The device output carries one extra row and
+// five extra columns filled with a marker; a marker that changed means the kernel wrote outside its B x r block.
+int hipdrt_debug_apply_rows(hipdrt_ctx* ctx, int B, int K, int ldx, int col_offset, const double* X, int r, const double* E,
+                            const double* scale, double* out) try {
+    HIPDRT_REQUIRE(ctx && X && E && out, "NULL pointer");
+    HIPDRT_REQUIRE(B >= 1 && K >= 1 && r >= 1 && col_offset >= 0, "B, K, r >= 1, col_offset >= 0");
+    HIPDRT_REQUIRE(ldx >= col_offset + K, "ldx >= col_offset + K");
+    hipStream_t st; TRY(enter(ctx, &st));
+    const int ldo = r + 5, rows = B + 1;
+    const double marker = -7.0e77;
+    DevBuf dx, de, ds, dout;
+    TRY(upload(dx, X, (size_t)B * ldx * sizeof(double), st));
+    TRY(upload(de, E, (size_t)r * K * sizeof(double), st));
+    if (scale) TRY(upload(ds, scale, (size_t)B * sizeof(double), st));
+    std::vector<double> ho((size_t)rows * ldo, marker);
+    TRY(upload(dout, ho.data(), ho.size() * sizeof(double), st));
+    launch_apply_rows(st, B, K, dx.d(), ldx, col_offset, r, de.d(), K, scale ? ds.d() : nullptr, nullptr, dout.d(), ldo);
+    LAUNCH_OK();
+    HIPDRT_CHECK(hipMemcpyAsync(ho.data(), dout.p, ho.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    for (int b = 0; b < rows; ++b)
+        for (int i = 0; i < ldo; ++i) {
+            const double v = ho[(size_t)b * ldo + i];
+            if (b < B && i < r) out[(size_t)b * r + i] = v;
+            else if (!(v == marker)) {
+                set_error("apply_rows wrote outside its B x r block (row " + std::to_string(b) + ", column " + std::to_string(i) + ")");
+                return HIPDRT_E_NUMERIC;
+            }
+        }
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+// tools hook: kernel time of the last hipdrt_plan_predict_drt or hipdrt_plan_predict_z on this context
+int hipdrt_debug_last_predict_ms(hipdrt_ctx* ctx, float* ms) try {
+    HIPDRT_REQUIRE(ctx && ms, "NULL pointer");
+    ms[0] = ctx->predict_ms[0]; ms[1] = ctx->predict_ms[1];
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+}  // extern "C"

@@ -1,0 +1,212 @@
+// Internal declarations shared by the host-side translation units of the C-ABI (api.hip, operators.hip, debug.hip, plan.hip,
+// plan_fit.hip, plan_post.hip): the plan itself, the entry points' error handling, and the few functions that cross those
+// files.  Never included by a kernel file: what those see is common.hpp.
+#pragma once
+#include <memory>
+#include <mutex>
+#include <new>
+#include <stdexcept>
+
+#include "common.hpp"
+
+using namespace hipdrt;
+
+#define TRY(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
+#define LAUNCH_OK() HIPDRT_CHECK(hipGetLastError())
+
+// No exception may cross the C ABI: every entry point is a function-try-block.  (Host-side std::vector buffers -- an
+// n x n identity of 134 MB at n = 4096, download staging, the Toeplitz reach scan of plan creation -- can throw std::bad_alloc.)
+#define HIPDRT_CATCH                                                                                              \
+    catch (const std::bad_alloc&) { hipdrt::set_error("out of host memory"); return HIPDRT_E_HIP; }                \
+    catch (const std::exception& e) { hipdrt::set_error(std::string("internal error: ") + e.what()); return HIPDRT_E_HIP; } \
+    catch (...) { hipdrt::set_error("internal error"); return HIPDRT_E_HIP; }
+
+// every entry point that touches the device starts here: the context's device current, no sticky error left over from an
+// earlier call, and (when asked for) the context's stream
+inline int enter(hipdrt_ctx* ctx, hipStream_t* st = nullptr) {
+    HIPDRT_CHECK(hipSetDevice(ctx->device)); (void)hipGetLastError();
+    if (st) *st = ctx->stream;
+    return HIPDRT_OK;
+}
+
+inline int upload(DevBuf& buf, const void* src, size_t bytes, hipStream_t st) {
+    HIPDRT_CHECK(buf.alloc(bytes));
+    if (src) HIPDRT_CHECK(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, st));
+    return 0;
+}
+
+inline int copy_strided(double* out, const double* dev, int rows, int cols, int ld, hipStream_t st) {
+    HIPDRT_CHECK(hipMemcpy2DAsync(out, (size_t)cols * sizeof(double), dev, (size_t)ld * sizeof(double),
+                                  (size_t)cols * sizeof(double), rows, hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
+// +1: strictly descending, -1: strictly ascending, 0: neither
+inline int freq_monotone(const double* f, int nf) {
+    if (nf < 2) return 1;
+    const int dir = f[0] > f[1] ? 1 : -1;
+    for (int i = 0; i + 1 < nf; ++i)
+        if (!(dir > 0 ? f[i] > f[i + 1] : f[i] < f[i + 1])) return 0;
+    return dir;
+}
+
+namespace hipdrt {
+// ---- api.hip: the library's own streams (StreamPool) and the life cycle of contexts -----------------------------------------
+// k streams for the ranges of one fit, the least busy first (more ranges than streams: they repeat), and their return
+void pool_borrow(int device, int k, int* idx, hipStream_t* st);
+void pool_return(int device, int k, const int* idx);
+int pool_size(int device);
+struct LoopOnContextStream {       // RAII: "a device loop runs on this context's stream" for the ranges of other fits to avoid
+    hipdrt_ctx* c;
+    explicit LoopOnContextStream(hipdrt_ctx* c_);
+    ~LoopOnContextStream();
+};
+extern std::mutex g_life;          // context / plan creation and destruction (any thread, e.g. a garbage collector's)
+void free_ctx(hipdrt_ctx* ctx);    // (under g_life) a released context whose last plan is gone
+
+// ---- operators.hip --------------------------------------------------------------------------------------------------------
+hipdrt_qp_opts default_qp_opts();
+// out_dev[i * ld + j] = fac * phi^(order)(ev_i - basis_j) (launch_func_eval with the two constants as Python forms them)
+int func_eval_dev(hipStream_t st, const double* basis_dev, int nb, const double* ev_dev, int ne, double eps, int order,
+                  double fac, double* out_dev, int ld);
+}  // namespace hipdrt
+
+// ---- the plan ---------------------------------------------------------------------------------------------------------------
+// What a sub-batch view shares with its parent, copied whole (plan.hip: make_view): dimensions and leading dimensions, mode and
+// structure flags, options.  A scalar that every range of a fit must see the same belongs HERE, not beside it in hipdrt_plan.
+struct PlanShape {
+    int nf = 0, ntau = 0, n = 0, m = 0, ns = 0, ngrid = 0, ny = 0, mode = 0, toeplitz_a = 0, toeplitz_m = 0;
+    int idx_rinf = -1, idx_induc = -1;
+    int ldrm = 0, ldm = 0, ldp = 0, ldl = 0;
+    double eps = 0;
+    hipdrt_fit_opts opts{};
+    int toep_maxd = -1;     // reach of the Toeplitz penalty blocks in grid points (plan_toep_reach), -1 = not determined
+    int spec_zero = 0;      // the special-parameter rows / columns of the penalty matrices are zero outside the special block
+    int qp_G = 0;           // workgroups per QP when the plan is full (qp_group_size at its capacity): 0 = the batch kernel
+};
+
+struct hipdrt_plan : PlanShape {
+    hipdrt_ctx* ctx = nullptr;
+    int freq_order = 0;        // +1: the frequency grid is strictly descending, -1: strictly ascending, 0: neither (kk_screen refuses)
+    int capacity = 0, B = 0;
+    // prepared-matrix plans (hipdrt_plan_create_prepared)
+    int prepared = 0;
+    int prepped = 0;           // launch_prep has run on the staged batch (hipdrt_plan_iterate runs it once)
+    hipdrt_prepared_desc desc{};
+    long long rm_stride = 0;
+    DevBuf vz_strength, dop_rho, dop_xmx, hist_dop_rho, outlier_t, vz_entry;
+    // weight factors (hipdrt_plan_set_weight_factors): w_eff = w * row factor * weight_factor is what the QP sees
+    double weight_factor = 1.0;
+    int wrow_batched = 0;
+    int wrow_late = 0;      // row factors are a vector-valued weight_factor: applied from the second iteration on only
+    DevBuf wrow, w_eff, h_init, wfac;
+    bool has_weight_factors() const { return weight_factor != 1.0 || wrow.p != nullptr; }
+    // shared
+    DevBuf freq, tau, ln_tau, wt_re, wt_im, lut6, a_re, a_im, cr, rm, mk[3], vmm, h, l1;
+    // per spectrum
+    DevBuf z_re, z_im, rv, w, est_w, x, x_in, q, s, rho, xmx, coef_scale, var_floor;
+    DevBuf active, outer_iters, fit_status, qp_iters_total, qp_status, qp_iters, n_active, pcost;
+    DevBuf premv;          // [3][capacity][m]: hyper-parameter step of few, large fits (hyper.hip, premv_kernel)
+    DevBuf L, Ptmp, qpstate, Ppk, order, vmm_base, gsync;
+    // tau basis of a prepared plan (hipdrt_plan_set_tau_basis): ln(basis_tau) [basis_nb] and its epsilon, for hipdrt_plan_predict_drt
+    DevBuf basis_ln_tau;
+    int basis_nb = 0;
+    double basis_eps = 0;
+    // The kernel is chosen per fit from the number of spectra actually staged: a plan sized for a thousand spectra that is
+    // handed one or a handful runs them on several workgroups each, inside the scratch it already has.
+    void qp_layout(int B, QpArgs& qa) const {
+        int G = qp_group_size(B, n, ctx ? ctx->qp_force_group : -1);
+        const size_t have_l = L.bytes / sizeof(double), have_s = qpstate.bytes / sizeof(double);
+        if (G >= 1 && G != qp_G) {
+            const bool fits = gsync.p && (size_t)B * qp_scratch_doubles(n, G) <= have_l &&
+                              (size_t)B * G * qp_state_doubles(n) <= have_s && (size_t)B * qp_gsync_ints() * sizeof(int) <= gsync.bytes;
+            if (!fits) G = qp_G;
+        } else if (G < 1) {
+            G = qp_G;            // (a plan created for few spectra keeps its group layout when it is full)
+        }
+        qa.G = G; qa.gsync = gsync.i(); qa.l_stride = (long long)qp_scratch_doubles(n, G);
+        qa.waves = ctx ? ctx->qp_waves : -1;
+    }
+    // history
+    int hist_b = -1, hist_cap = 0;
+    DevBuf hist_x, hist_w, hist_rho, hist_qp, hist_rows;
+    // timings of the last fit
+    float t_ms[5] = {0, 0, 0, 0, 0};
+    int launches[5] = {0, 0, 0, 0, 0};
+    // sub-batches of one fit (hipdrt_plan_set_subbatches): the staged spectra split into `k` contiguous ranges, every range
+    // fitted by the same device loop on its own stream, all inside ONE hipdrt_plan_fit call and the plan's own buffers
+    int subbatches = 0;                                   // 0 = automatic (subbatch_count), >= 1 fixed
+    std::vector<std::unique_ptr<struct hipdrt_subfit>> subs;
+    DevBuf n_active_sub;                                  // one "still active" counter per sub-batch
+    hipdrt_plan() = default;
+    ~hipdrt_plan();
+
+    FitState state() const {
+        FitState st{};
+        st.nf = nf; st.m = m; st.n = n; st.ns = ns; st.ldrm = ldrm; st.ldm = ldm; st.toeplitz_m = toeplitz_m;
+        st.toep_reach = (toeplitz_m && !(ctx && !ctx->zero_shortcuts)) ? toep_maxd : -1;
+        st.opts = opts; st.continue_mode = 0; st.min_iter = 1;
+        st.basis_area = prepared ? desc.basis_area : (eps > 0 ? 1.7724538509055159 / eps : 0.0);   // sqrt(pi) / epsilon
+        st.prepared = prepared; st.desc = desc; st.rm_stride = rm_stride; st.rm_rw = rm.d();
+        st.vz_strength = vz_strength.d(); st.vz_entry = nullptr; st.dop_rho = dop_rho.d(); st.dop_xmx = dop_xmx.d();
+        st.hist_dop_rho = hist_dop_rho.d(); st.outlier_t = outlier_t.d();
+        st.rm = rm.d(); st.vmm = vmm.d(); st.vmm_iw = vmm_base.p ? vmm_base.d() : vmm.d();
+        for (int k = 0; k < 3; ++k) st.mk[k] = mk[k].d();
+        st.z_re = z_re.d(); st.z_im = z_im.d();
+        st.rv = rv.d(); st.w = w.d(); st.est_w = est_w.d();
+        st.x = x.d(); st.x_in = x_in.d(); st.s = s.d(); st.rho = rho.d(); st.xmx = xmx.d();
+        st.coef_scale = coef_scale.d(); st.var_floor = var_floor.d();
+        st.active = active.i(); st.outer_iters = outer_iters.i(); st.fit_status = fit_status.i();
+        st.qp_iters_total = qp_iters_total.i(); st.qp_status = qp_status.i(); st.qp_iters = qp_iters.i();
+        st.n_active = n_active.i();
+        st.hist_b = hist_b; st.hist_cap = hist_cap;
+        st.hist_x = hist_x.d(); st.hist_w = hist_w.d(); st.hist_rho = hist_rho.d();
+        st.hist_qp = hist_qp.i(); st.hist_rows = hist_rows.i();
+        st.premv = nullptr; st.premv_batched = 0;
+        return st;
+    }
+};
+
+// one sub-batch of a plan: a plan object whose buffers are windows into the parent's, with a stream of its own
+struct hipdrt_subfit {
+    hipdrt_ctx ctx;
+    hipdrt_plan view;
+    int rc = 0;
+    std::string err;
+    // (ctx.stream is borrowed from the library's pool for the duration of one fit: hipdrt_plan_fit)
+};
+inline hipdrt_plan::~hipdrt_plan() = default;
+
+namespace hipdrt {
+// plan.hip: one range of a plan's staged batch as a plan of its own; history buffers for `rows` outer iterations
+int make_view(hipdrt_plan* p, hipdrt_subfit& sf, int idx, int b0, int nb);
+int plan_hist_reserve(hipdrt_plan* p, int rows);
+// plan_fit.hip: L2 part of P in hyper-parameter form for the plan's current state
+GramL2 plan_l2(const hipdrt_plan* p, double l2_lambda_0, const double* derivative_weights, double dop_l2_lambda_0);
+
+// ---- Kramers-Kronig screening: plan_post.hip (hipdrt_plan_kk_screen) and its stage-B test hook in debug.hip --------------------
+int kk_check_opts(const hipdrt_kk_opts& o);
+}  // namespace hipdrt
+
+// device outputs of one kk launch for B spectra of nf frequencies, and their way back to the host
+struct KkOut {
+    DevBuf zr, zi, er, ei, sd, mask, flim, ilim, status;
+    int alloc(KkArgs& a, int B, int nf, bool z, bool zi_, bool e, bool ei_, bool sd_, bool mask_, bool fl, bool il, bool stt) {
+        const size_t bn = (size_t)B * nf;
+        if (z) { HIPDRT_CHECK(zr.alloc(bn * sizeof(double))); a.z_re = zr.d(); }
+        if (zi_) { HIPDRT_CHECK(zi.alloc(bn * sizeof(double))); a.z_im = zi.d(); }
+        if (e) { HIPDRT_CHECK(er.alloc(bn * sizeof(double))); a.e_re = er.d(); }
+        if (ei_) { HIPDRT_CHECK(ei.alloc(bn * sizeof(double))); a.e_im = ei.d(); }
+        if (sd_) { HIPDRT_CHECK(sd.alloc((size_t)B * sizeof(double))); a.std = sd.d(); }
+        if (mask_) { HIPDRT_CHECK(mask.alloc(bn * sizeof(int))); a.mask = mask.i(); }
+        if (fl) { HIPDRT_CHECK(flim.alloc((size_t)B * 2 * sizeof(double))); a.f_lim = flim.d(); }
+        if (il) { HIPDRT_CHECK(ilim.alloc((size_t)B * 2 * sizeof(int))); a.i_lim = ilim.i(); }
+        if (stt) { HIPDRT_CHECK(status.alloc((size_t)B * sizeof(int))); a.status = status.i(); }
+        return HIPDRT_OK;
+    }
+    static int back(void* host, const DevBuf& d, hipStream_t st) {
+        if (host && d.p) HIPDRT_CHECK(hipMemcpyAsync(host, d.p, d.bytes, hipMemcpyDeviceToHost, st));
+        return HIPDRT_OK;
+    }
+};

@@ -1,0 +1,425 @@
+// What reads a finished fit of a plan (include/hipdrt.h): log-likelihood terms, the posterior covariance and variance,
+// Kramers-Kronig screening (csrc/kk.hip) and model evaluation (csrc/predict.hip).
+#include <cmath>
+#include <cstring>
+
+#include "plan.hpp"
+
+namespace hipdrt {
+int kk_check_opts(const hipdrt_kk_opts& o) {
+    HIPDRT_REQUIRE(o.n_outlier_iter >= 0 && o.n_outlier_iter <= 100, "0 <= n_outlier_iter <= 100");
+    HIPDRT_REQUIRE(o.n_sigma > 0.0 || (o.p_thresh > 0.0 && o.p_thresh < 1.0), "0 < p_thresh < 1");
+    HIPDRT_REQUIRE(o.std_sample_fraction > 0.0 && o.std_sample_fraction <= 1.0, "0 < std_sample_fraction <= 1");
+    HIPDRT_REQUIRE(o.n_std > 0.0 && std::isfinite(o.n_std), "n_std > 0");
+    HIPDRT_REQUIRE(o.max_num_outliers >= 0, "max_num_outliers >= 0");
+    HIPDRT_REQUIRE(o.outlier_weight > 0.0 && std::isfinite(o.outlier_weight), "outlier_weight > 0");
+    return HIPDRT_OK;
+}
+}  // namespace hipdrt
+
+extern "C" {
+
+static int plan_llh_terms(hipdrt_plan* p, double* rss, double* sum_log_w, int stored, double scalar_w = 1.0);
+
+int hipdrt_plan_llh_terms(hipdrt_plan* p, double* rss, double* sum_log_w) { return plan_llh_terms(p, rss, sum_log_w, 0); }
+
+int hipdrt_plan_obs_llh_terms(hipdrt_plan* p, double* rss, double* sum_log_w) { return plan_llh_terms(p, rss, sum_log_w, 1); }
+
+int hipdrt_plan_obs_llh_terms_w(hipdrt_plan* p, int weights_mode, double scalar_weight, double* rss, double* sum_log_w) try {
+    HIPDRT_REQUIRE(weights_mode == HIPDRT_LLH_W_EST || weights_mode == HIPDRT_LLH_W_UNIFORM || weights_mode == HIPDRT_LLH_W_SCALAR,
+                   "weights_mode");
+    HIPDRT_REQUIRE(weights_mode != HIPDRT_LLH_W_SCALAR || scalar_weight > 0.0, "scalar weight must be positive");
+    return plan_llh_terms(p, rss, sum_log_w, weights_mode, scalar_weight);
+} HIPDRT_CATCH
+
+static int plan_llh_terms(hipdrt_plan* p, double* rss, double* sum_log_w, int stored, double scalar_w) {
+    HIPDRT_REQUIRE(p && rss && sum_log_w, "NULL pointer");
+    HIPDRT_REQUIRE(p->B >= 1, "no fitted batch in the plan");
+    hipStream_t st; TRY(enter(p->ctx, &st));
+    const size_t bb = (size_t)p->B * sizeof(double);
+    DevBuf d1, d2;
+    HIPDRT_CHECK(d1.alloc(bb)); HIPDRT_CHECK(d2.alloc(bb));
+    TRY(launch_llh(st, p->state(), p->B, d1.d(), d2.d(), stored, scalar_w));
+    LAUNCH_OK();
+    HIPDRT_CHECK(hipMemcpyAsync(rss, d1.p, bb, hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipMemcpyAsync(sum_log_w, d2.p, bb, hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    return HIPDRT_OK;
+}
+
+// What the posterior entry points call "the final P": calculate_pq with the final weights / s / rho (drt1d.py:1006), from
+// calculate_pq's scaled_weights -- w_eff whenever the plan has weight factors.  b >= 0: s, rho, dop_rho and the weights of
+// spectrum b alone.
+struct FinalP { GramL2 g; const double* w; };
+static FinalP plan_final_p(const hipdrt_plan* p, int b) {
+    FinalP f{plan_l2(p, p->opts.l2_lambda_0, p->opts.derivative_weights, p->prepared ? p->desc.dop_l2_lambda_0 : 0.0),
+             p->has_weight_factors() ? p->w_eff.d() : p->w.d()};
+    if (b >= 0) {
+        f.g.s += (size_t)b * 3 * p->n; f.g.rho += (size_t)b * 3;
+        if (f.g.dop_size > 0) f.g.dop_rho += (size_t)b * 3;
+        f.w += (size_t)b * p->m;
+    }
+    return f;
+}
+
+int hipdrt_plan_get_p_matrix(hipdrt_plan* p, int b, double* out) try {
+    HIPDRT_REQUIRE(p && out, "NULL pointer");
+    HIPDRT_REQUIRE(b >= 0 && b < p->B, "spectrum index out of range");
+    hipStream_t st; TRY(enter(p->ctx, &st));
+    const int n = p->n, m = p->m;
+    const FinalP f = plan_final_p(p, b);
+    launch_gram_l2(st, 1, m, n, p->rm.d() + (size_t)b * p->rm_stride, p->ldrm, f.w, f.g, p->Ptmp.d(), p->ldp, 0, nullptr);
+    LAUNCH_OK();
+    return copy_strided(out, p->Ptmp.d(), n, n, p->ldp, st);
+} HIPDRT_CATCH
+
+// rows_dev[neval][ncol] in device memory (it sits at columns col_offset.. of the unknown vector, zero elsewhere) ->
+// dout[B][nex * 16] = rows_i' P_b^-1 rows_i (not yet scaled by cs_b^2), dstat[B]
+static int plan_quadratic_forms_dev(hipdrt_plan* p, const double* rows_dev, int neval, int ncol, int col_offset, DevBuf& dout,
+                                    DevBuf& dstat) {
+    HIPDRT_REQUIRE(p->B > 0, "no fitted batch in the plan");
+    HIPDRT_REQUIRE(neval >= 1, "neval >= 1");
+    HIPDRT_REQUIRE(p->n <= 4096, "posterior variance: n <= 4096");
+    hipStream_t st; TRY(enter(p->ctx, &st));
+    const int n = p->n, m = p->m, B = p->B;
+    const int nex = (neval + 15) / 16, nchp = qp_nchp(n);
+    // final P of every spectrum, packed tiles only
+    const FinalP f = plan_final_p(p, -1);
+    launch_gram_l2(st, B, m, n, p->rm.d(), p->ldrm, f.w, f.g, nullptr, p->ldp, 0, nullptr, p->Ppk.d(),
+                   (long long)qp_ppk_doubles(n), nchp, p->rm_stride);
+    LAUNCH_OK();
+    // evaluation rows -> packed tiles, shifted past the special-parameter slots
+    DevBuf bex, scratch;
+    HIPDRT_CHECK(bex.alloc((size_t)nex * nchp * 256 * sizeof(double)));
+    launch_pack_rows(st, neval, ncol, col_offset, rows_dev, ncol, nex, bex.d(), nchp);
+    LAUNCH_OK();
+    const int chunk = B < 256 ? B : 256;
+    const size_t lsz = dist_var_scratch_doubles(n, nex);
+    HIPDRT_CHECK(scratch.alloc((size_t)chunk * lsz * sizeof(double)));
+    HIPDRT_CHECK(dout.alloc((size_t)B * nex * 16 * sizeof(double)));
+    HIPDRT_CHECK(dstat.alloc((size_t)B * sizeof(int)));
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+        const int nb = (B - b0) < chunk ? (B - b0) : chunk;
+        TRY(launch_dist_var(st, nb, n, p->Ppk.d() + (size_t)b0 * qp_ppk_doubles(n), (long long)qp_ppk_doubles(n), bex.d(),
+                            nex, scratch.d(), (long long)lsz, dout.d() + (size_t)b0 * nex * 16, (long long)nex * 16,
+                            dstat.i() + b0));
+    }
+    HIPDRT_CHECK(hipStreamSynchronize(st));      // bex and scratch are released on return
+    return HIPDRT_OK;
+}
+
+// out[b][i] = rows_i' P_b^-1 rows_i * cs_b^2 for the fitted batch, host rows in, host results out
+static int plan_quadratic_forms(hipdrt_plan* p, const double* basis_eval, int neval, int ncol, int col_offset, double* out,
+                                int* status) {
+    HIPDRT_REQUIRE(p->B > 0, "no fitted batch in the plan");
+    HIPDRT_REQUIRE(neval >= 1, "neval >= 1");
+    hipStream_t st; TRY(enter(p->ctx, &st));
+    const int B = p->B, nex = (neval + 15) / 16;
+    DevBuf dbe, dout, dstat;
+    TRY(upload(dbe, basis_eval, (size_t)neval * ncol * sizeof(double), st));
+    TRY(plan_quadratic_forms_dev(p, dbe.d(), neval, ncol, col_offset, dout, dstat));
+    std::vector<double> hv((size_t)B * nex * 16), cs(B);
+    std::vector<int> hs(B);
+    HIPDRT_CHECK(hipMemcpyAsync(hv.data(), dout.p, hv.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipMemcpyAsync(cs.data(), p->coef_scale.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipMemcpyAsync(hs.data(), dstat.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    // estimate_param_cov scales the inverse by coefficient_scale^2 (drt1d.py:4133)
+    for (int b = 0; b < B; ++b) {
+        const double c2 = cs[b] * cs[b];
+        for (int i = 0; i < neval; ++i) out[(size_t)b * neval + i] = hv[((size_t)b * nex) * 16 + i] * c2;
+        if (status) status[b] = hs[b];
+    }
+    return HIPDRT_OK;
+}
+
+// out[neval][neval] = rows P_b^-1 rows' * cs_b^2 for ONE fitted spectrum: the variance kernel leaves Y = rows L^-T behind the
+// factor (one more panel of the same factorisation), rows_outer_kernel forms Y Y'
+static int plan_full_cov(hipdrt_plan* p, int b, const double* rows, int neval, int ncol, int col_offset, double* out, int* status) {
+    HIPDRT_REQUIRE(p->B > 0, "no fitted batch in the plan");
+    HIPDRT_REQUIRE(b >= 0 && b < p->B, "spectrum index out of range");
+    HIPDRT_REQUIRE(neval >= 1, "neval >= 1");
+    HIPDRT_REQUIRE(p->n <= 4096, "posterior covariance: n <= 4096");
+    hipStream_t st; TRY(enter(p->ctx, &st));
+    const int n = p->n, m = p->m;
+    const int nex = (neval + 15) / 16, nchp = qp_nchp(n), nch = round_up(n, 32) / 16;
+    // final P of this spectrum, packed tiles, into its own slot of Ppk
+    const FinalP f = plan_final_p(p, b);
+    double* ppk = p->Ppk.d() + (size_t)b * qp_ppk_doubles(n);
+    launch_gram_l2(st, 1, m, n, p->rm.d() + (size_t)b * p->rm_stride, p->ldrm, f.w, f.g, nullptr, p->ldp, 0, nullptr, ppk, 0,
+                   nchp, 0);
+    LAUNCH_OK();
+    DevBuf dbe, bex, scratch, dvar, dstat, dcov;
+    TRY(upload(dbe, rows, (size_t)neval * ncol * sizeof(double), st));
+    HIPDRT_CHECK(bex.alloc((size_t)nex * nchp * 256 * sizeof(double)));
+    launch_pack_rows(st, neval, ncol, col_offset, dbe.d(), ncol, nex, bex.d(), nchp);
+    LAUNCH_OK();
+    HIPDRT_CHECK(scratch.alloc(dist_var_scratch_doubles(n, nex) * sizeof(double)));
+    HIPDRT_CHECK(dvar.alloc((size_t)nex * 16 * sizeof(double)));
+    HIPDRT_CHECK(dstat.alloc(sizeof(int)));
+    HIPDRT_CHECK(dcov.alloc((size_t)neval * neval * sizeof(double)));
+    TRY(launch_dist_var(st, 1, n, ppk, 0, bex.d(), nex, scratch.d(), 0, dvar.d(), 0, dstat.i()));
+    double cs = 1.0;
+    int hs = 0;
+    HIPDRT_CHECK(hipMemcpyAsync(&cs, p->coef_scale.d() + b, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipMemcpyAsync(&hs, dstat.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    if (status) *status = hs;
+    if (hs != 0) {                               // P not positive definite (np.linalg.inv would still return something; the
+        for (size_t i = 0; i < (size_t)neval * neval; ++i) out[i] = __builtin_nan("");      // reference warns and returns None)
+        return HIPDRT_OK;
+    }
+    // Y = rows L^-T sits in tile rows nch .. nch + nex - 1 of the scratch; only the first ceil(n / 16) tile columns are non-zero
+    launch_rows_outer(st, scratch.d() + (size_t)nch * nch * 256, nch, nch, nex, neval, cs * cs, dcov.d(), neval);
+    LAUNCH_OK();
+    HIPDRT_CHECK(hipMemcpyAsync(out, dcov.p, (size_t)neval * neval * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    return HIPDRT_OK;
+}
+
+int hipdrt_plan_distribution_cov(hipdrt_plan* p, int b, const double* basis_eval, int neval, double* out, int* status) try {
+    HIPDRT_REQUIRE(p && basis_eval && out, "NULL pointer");
+    return plan_full_cov(p, b, basis_eval, neval, p->ntau, p->ns, out, status);
+} HIPDRT_CATCH
+
+int hipdrt_plan_param_cov(hipdrt_plan* p, int b, double* out, int* status) try {
+    HIPDRT_REQUIRE(p && out, "NULL pointer");
+    const int n = p->n;
+    std::vector<double> eye((size_t)n * n, 0.0);
+    for (int i = 0; i < n; ++i) eye[(size_t)i * n + i] = 1.0;
+    return plan_full_cov(p, b, eye.data(), n, n, 0, out, status);
+} HIPDRT_CATCH
+
+int hipdrt_plan_distribution_var(hipdrt_plan* p, const double* basis_eval, int neval, double* out, int* status) try {
+    HIPDRT_REQUIRE(p && basis_eval && out, "NULL pointer");
+    return plan_quadratic_forms(p, basis_eval, neval, p->ntau, p->ns, out, status);
+} HIPDRT_CATCH
+
+int hipdrt_plan_param_var(hipdrt_plan* p, double* out, int* status) try {
+    HIPDRT_REQUIRE(p && out, "NULL pointer");
+    const int n = p->n;
+    std::vector<double> eye((size_t)n * n, 0.0);
+    for (int i = 0; i < n; ++i) eye[(size_t)i * n + i] = 1.0;
+    return plan_quadratic_forms(p, eye.data(), n, n, 0, out, status);
+} HIPDRT_CATCH
+
+// ---- Kramers-Kronig screening (csrc/kk.hip) ---------------------------------------------------------------------------------
+void hipdrt_default_kk_opts(hipdrt_kk_opts* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->n_outlier_iter = 2; o->p_thresh = 1e-4; o->n_sigma = -1.0; o->std_sample_fraction = 0.6;
+    o->n_std = 0.8416212335729143; o->max_num_outliers = 2; o->outlier_weight = 1e-10;
+}
+
+int hipdrt_plan_kk_screen(hipdrt_plan* p, const hipdrt_kk_opts* opts, int set_row_factors, double* z_hat_re, double* z_hat_im,
+                          double* err_re, double* err_im, double* std_out, int* outlier_mask, double* f_lim, int* i_lim,
+                          int* status) try {
+    HIPDRT_REQUIRE(p, "plan is NULL");
+    HIPDRT_REQUIRE(p->B >= 1 && p->prepped, "no fitted batch in the plan");
+    // every check comes before the first launch and the first change of the plan
+    HIPDRT_REQUIRE(!p->prepared, "the KK screen is built for plain EIS plans (hipdrt_plan_create)");
+    HIPDRT_REQUIRE(p->nf >= 1 && p->m == 2 * p->nf, "the KK screen needs EIS-only data (m = 2 nf)");
+    HIPDRT_REQUIRE(p->freq_order != 0, "the KK screen needs a strictly ascending or descending frequency grid");
+    hipdrt_kk_opts o;
+    if (opts) o = *opts; else hipdrt_default_kk_opts(&o);
+    TRY(kk_check_opts(o));
+    HIPDRT_REQUIRE(kk_lds_bytes(p->nf, p->n, 1) <= 160 * 1024 - 256, "KK screen: nf and n too large for one workgroup's LDS");
+    hipStream_t st; TRY(enter(p->ctx, &st));
+    const int B = p->B, nf = p->nf, m = p->m;
+    KkArgs a{};
+    a.nf = nf; a.desc = p->freq_order > 0 ? 1 : 0; a.freq = p->freq.d(); a.o = o;
+    KkOut out;
+    TRY(out.alloc(a, B, nf, z_hat_re, z_hat_im, err_re, err_im, std_out, outlier_mask, f_lim, i_lim, status));
+    if (set_row_factors) {
+        const size_t need = (size_t)p->capacity * m * sizeof(double);
+        if (p->wrow.bytes < need || !p->wrow_batched) {
+            // (rows past the staged batch are never read by a fit of this batch; ones all the same)
+            std::vector<double> ones((size_t)p->capacity * m, 1.0);
+            TRY(upload(p->wrow, ones.data(), need, st));
+            HIPDRT_CHECK(hipStreamSynchronize(st));
+        }
+        if (!p->w_eff.p) HIPDRT_CHECK(p->w_eff.alloc(need));
+        a.wrow = p->wrow.d();
+    }
+    const FitState fs = p->state();
+    TRY(launch_kk(st, &fs, a, B));
+    LAUNCH_OK();
+    if (set_row_factors) { p->weight_factor = 1.0; p->wrow_batched = 1; p->wrow_late = 1; }
+    TRY(KkOut::back(z_hat_re, out.zr, st)); TRY(KkOut::back(z_hat_im, out.zi, st));
+    TRY(KkOut::back(err_re, out.er, st)); TRY(KkOut::back(err_im, out.ei, st));
+    TRY(KkOut::back(std_out, out.sd, st)); TRY(KkOut::back(outlier_mask, out.mask, st));
+    TRY(KkOut::back(f_lim, out.flim, st)); TRY(KkOut::back(i_lim, out.ilim, st)); TRY(KkOut::back(status, out.status, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+// ---- model evaluation for the fitted batch (csrc/predict.hip) ----------------------------------------------------------------
+int hipdrt_plan_set_tau_basis(hipdrt_plan* p, const double* ln_basis_tau, int nb, double epsilon) try {
+    HIPDRT_REQUIRE(p && ln_basis_tau, "NULL pointer");
+    HIPDRT_REQUIRE(p->prepared, "a plan made by hipdrt_plan_create holds its tau basis already");
+    const int width = p->n - p->ns;
+    HIPDRT_REQUIRE(nb >= 1 && (width == nb || width == 2 * nb), "the DRT block must hold one or two copies of the basis");
+    HIPDRT_REQUIRE(epsilon > 0.0 && std::isfinite(epsilon), "epsilon > 0");
+    TRY(enter(p->ctx));
+    TRY(upload(p->basis_ln_tau, ln_basis_tau, (size_t)nb * sizeof(double), p->ctx->stream));
+    HIPDRT_CHECK(hipStreamSynchronize(p->ctx->stream));
+    p->basis_nb = nb; p->basis_eps = epsilon;
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+// kernel time of the last prediction on a context (hipdrt_debug_last_predict_ms): HIP events around the launches
+struct PredictTimer {
+    hipdrt_ctx* ctx; hipStream_t st; hipEvent_t e[3] = {nullptr, nullptr, nullptr}; int n = 0;
+    PredictTimer(hipdrt_ctx* c, hipStream_t s) : ctx(c), st(s) { mark(); }
+    void mark() { if (n < 3 && hipEventCreate(&e[n]) == hipSuccess) { (void)hipEventRecord(e[n], st); ++n; } }
+    // (destroyed after the stream has been synchronised) [0] up to the second mark, [1] up to the last one
+    ~PredictTimer() {
+        float a = 0.f, b = 0.f;
+        if (n >= 2 && hipEventElapsedTime(&a, e[0], e[1]) == hipSuccess && hipEventElapsedTime(&b, e[0], e[n - 1]) == hipSuccess) {
+            ctx->predict_ms[0] = a; ctx->predict_ms[1] = b;
+        }
+        for (int i = 0; i < n; ++i) (void)hipEventDestroy(e[i]);
+        (void)hipGetLastError();
+    }
+};
+
+// the tau basis a prediction evaluates: the plan's own grid, or what hipdrt_plan_set_tau_basis gave a prepared plan
+struct PredictBasis { const double* ln_tau; int nb, copies; double eps; };
+static int predict_basis(const hipdrt_plan* p, PredictBasis& pb) {
+    HIPDRT_REQUIRE(p->B >= 1 && p->prepped, "no fitted batch in the plan");
+    if (p->prepared) {
+        HIPDRT_REQUIRE(p->basis_nb > 0, "a prepared plan needs hipdrt_plan_set_tau_basis before a DRT prediction");
+        pb = {p->basis_ln_tau.d(), p->basis_nb, (p->n - p->ns) / p->basis_nb, p->basis_eps};
+    } else {
+        pb = {p->ln_tau.d(), p->ntau, 1, p->eps};
+    }
+    return HIPDRT_OK;
+}
+
+int hipdrt_plan_predict_drt(hipdrt_plan* p, const double* ln_tau_eval, int neval, int order, int sign, int normalize, double s_lo,
+                            double s_hi, double* mu, double* lo, double* hi, int* status) try {
+    HIPDRT_REQUIRE(p && ln_tau_eval && mu, "NULL pointer");
+    PredictBasis pb;
+    TRY(predict_basis(p, pb));
+    HIPDRT_REQUIRE(neval >= 1, "neval >= 1");
+    HIPDRT_REQUIRE(order >= 0 && order <= 2, "order must be 0, 1 or 2");
+    HIPDRT_REQUIRE(sign == 1 || (pb.copies == 2 && (sign == 0 || sign == -1)),
+                   "sign must be 1, or 1, -1 or 0 when the DRT block holds a positive and a negative copy");
+    HIPDRT_REQUIRE(normalize >= 0 && normalize <= 2, "normalize must be 0, 1 (by R_p) or 2 (by absolute R_p)");
+    const bool band = lo || hi;
+    HIPDRT_REQUIRE(!band || (std::isfinite(s_lo) && std::isfinite(s_hi)), "s_lo and s_hi must be finite");
+    hipStream_t st; TRY(enter(p->ctx, &st));
+    const int B = p->B, n = p->n, ns = p->ns, width = n - ns, nb = pb.nb;
+    // E[neval][width]: the signed evaluation rows over the whole DRT block (+E | 0), (0 | -E) or (+E | -E)
+    DevBuf dev, dE, dsum, dabs, dnorm, dscale, dmu, dlo, dhi, dvar, dvstat;
+    TRY(upload(dev, ln_tau_eval, (size_t)neval * sizeof(double), st));
+    HIPDRT_CHECK(dE.alloc((size_t)neval * width * sizeof(double)));
+    HIPDRT_CHECK(dmu.alloc((size_t)B * neval * sizeof(double)));
+    PredictTimer tm(p->ctx, st);
+    if (pb.copies == 2 && sign != 0) HIPDRT_CHECK(hipMemsetAsync(dE.p, 0, dE.bytes, st));
+    if (sign != -1) TRY(func_eval_dev(st, pb.ln_tau, nb, dev.d(), neval, pb.eps, order, 1.0, dE.d(), width));
+    if (pb.copies == 2 && sign != 1) TRY(func_eval_dev(st, pb.ln_tau, nb, dev.d(), neval, pb.eps, order, -1.0, dE.d() + nb, width));
+    const double* scale = p->coef_scale.d();
+    if (normalize) {
+        HIPDRT_CHECK(dsum.alloc((size_t)B * sizeof(double))); HIPDRT_CHECK(dabs.alloc((size_t)B * sizeof(double)));
+        HIPDRT_CHECK(dnorm.alloc((size_t)B * sizeof(double))); HIPDRT_CHECK(dscale.alloc((size_t)B * sizeof(double)));
+        launch_drt_sums(st, B, p->x.d(), n, ns, nb, pb.copies, sign, dsum.d(), dabs.d());
+        launch_drt_scalars(st, B, dsum.d(), dabs.d(), p->coef_scale.d(), 1.7724538509055159 / pb.eps, 1, normalize == 2,
+                           p->x.d(), n, -1, nullptr, nullptr, nullptr, dnorm.d(), dscale.d());
+        LAUNCH_OK();
+        scale = dscale.d();
+    }
+    launch_apply_rows(st, B, width, p->x.d(), n, ns, neval, dE.d(), width, scale, p->fit_status.i(), dmu.d(), neval);
+    LAUNCH_OK();
+    tm.mark();
+    std::vector<int> hs(B), hv;
+    if (band) {
+        // sigma^2 = diag(E inv(P) E') from the variance path, fed the evaluation rows where they are
+        TRY(plan_quadratic_forms_dev(p, dE.d(), neval, width, ns, dvar, dvstat));
+        if (lo) HIPDRT_CHECK(dlo.alloc((size_t)B * neval * sizeof(double)));
+        if (hi) HIPDRT_CHECK(dhi.alloc((size_t)B * neval * sizeof(double)));
+        launch_drt_band(st, B, neval, dmu.d(), dvar.d(), (long long)((neval + 15) / 16) * 16, p->coef_scale.d(),
+                        normalize ? dnorm.d() : nullptr, s_lo, s_hi, dvstat.i(), p->fit_status.i(), dlo.d(), dhi.d());
+        LAUNCH_OK();
+        tm.mark();
+        if (lo) HIPDRT_CHECK(hipMemcpyAsync(lo, dlo.p, dlo.bytes, hipMemcpyDeviceToHost, st));
+        if (hi) HIPDRT_CHECK(hipMemcpyAsync(hi, dhi.p, dhi.bytes, hipMemcpyDeviceToHost, st));
+        hv.resize(B);
+        HIPDRT_CHECK(hipMemcpyAsync(hv.data(), dvstat.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+    }
+    HIPDRT_CHECK(hipMemcpyAsync(mu, dmu.p, dmu.bytes, hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipMemcpyAsync(hs.data(), p->fit_status.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    if (status)
+        for (int b = 0; b < B; ++b) status[b] = (hs[b] >= 0 && band && hv[b] != 0) ? HIPDRT_PREDICT_NOT_PD : hs[b];
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+int hipdrt_plan_predict_z(hipdrt_plan* p, const double* freq, int nf, int include_mask, double* z_re, double* z_im,
+                          int* status) try {
+    HIPDRT_REQUIRE(p && freq && z_re && z_im, "NULL pointer");
+    if (p->prepared) {
+        set_error("not supported: impedance prediction is built for plain EIS plans (hipdrt_plan_create); a prepared plan holds "
+                  "neither lookup tables nor a tau grid");
+        return HIPDRT_E_UNSUPPORTED;
+    }
+    HIPDRT_REQUIRE(p->B >= 1 && p->prepped, "no fitted batch in the plan");
+    HIPDRT_REQUIRE(nf >= 1, "nf >= 1");
+    HIPDRT_REQUIRE(include_mask >= 0 && include_mask <= 7, "include_mask: bit 0 DRT, bit 1 ohmic, bit 2 inductance");
+    for (int i = 0; i < nf; ++i) HIPDRT_REQUIRE(freq[i] > 0.0 && std::isfinite(freq[i]), "frequencies must be positive and finite");
+    hipStream_t st; TRY(enter(p->ctx, &st));
+    const int B = p->B, n = p->n, ntau = p->ntau;
+    DevBuf dfreq, dA, cr, dy, dzr, dzi;
+    TRY(upload(dfreq, freq, (size_t)nf * sizeof(double), st));
+    HIPDRT_CHECK(dzr.alloc((size_t)B * nf * sizeof(double))); HIPDRT_CHECK(dzi.alloc((size_t)B * nf * sizeof(double)));
+    if (include_mask & 1) {
+        HIPDRT_CHECK(dA.alloc((size_t)2 * nf * ntau * sizeof(double)));
+        HIPDRT_CHECK(cr.alloc(((size_t)nf + 2 * (size_t)(nf + ntau)) * sizeof(double)));
+        HIPDRT_CHECK(dy.alloc((size_t)B * 2 * nf * sizeof(double)));
+    }
+    PredictTimer tm(p->ctx, st);
+    if (include_mask & 1) {
+        // [A'; A''] at the requested frequencies from the plan's own tables, tau grid and integration mode (no Toeplitz shortcut:
+        // every entry is evaluated where it stands), then both parts as the two row blocks of one product
+        launch_impedance_matrix(st, 1, 0, dfreq.d(), nf, p->tau.d(), ntau, p->mode, 0, p->eps, p->ngrid, p->lut6.d(), p->ny,
+                                dA.d(), dA.d() + (size_t)nf * ntau, cr.d());
+        LAUNCH_OK();
+        launch_apply_rows(st, B, ntau, p->x.d(), n, p->ns, 2 * nf, dA.d(), ntau, p->coef_scale.d(), nullptr, dy.d(), 2 * nf);
+        LAUNCH_OK();
+    }
+    launch_z_assemble(st, B, nf, dy.d(), p->x.d(), n, p->idx_rinf, p->idx_induc, p->coef_scale.d(), p->opts.inductance_scale,
+                      dfreq.d(), include_mask, p->fit_status.i(), dzr.d(), dzi.d());
+    LAUNCH_OK();
+    tm.mark();
+    HIPDRT_CHECK(hipMemcpyAsync(z_re, dzr.p, dzr.bytes, hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipMemcpyAsync(z_im, dzi.p, dzi.bytes, hipMemcpyDeviceToHost, st));
+    if (status) HIPDRT_CHECK(hipMemcpyAsync(status, p->fit_status.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+int hipdrt_plan_predict_resistances(hipdrt_plan* p, double* r_p, double* r_inf, double* r_tot, int abs_norm) try {
+    HIPDRT_REQUIRE(p, "plan is NULL");
+    PredictBasis pb;
+    TRY(predict_basis(p, pb));
+    if (p->prepared && (r_inf || r_tot)) {
+        set_error("not supported: a prepared plan does not know which special parameter is R_inf (pass NULL for r_inf and r_tot)");
+        return HIPDRT_E_UNSUPPORTED;
+    }
+    hipStream_t st; TRY(enter(p->ctx, &st));
+    const int B = p->B, n = p->n;
+    DevBuf dsum, dabs, drp, dri, drt;
+    for (DevBuf* d : {&dsum, &dabs, &drp, &dri, &drt}) HIPDRT_CHECK(d->alloc((size_t)B * sizeof(double)));
+    // predict_r_p's default sign: the net distribution of a two-copy block, else the block itself
+    launch_drt_sums(st, B, p->x.d(), n, p->ns, pb.nb, pb.copies, pb.copies == 2 ? 0 : 1, dsum.d(), dabs.d());
+    launch_drt_scalars(st, B, dsum.d(), dabs.d(), p->coef_scale.d(), 1.7724538509055159 / pb.eps, 0, abs_norm != 0, p->x.d(), n,
+                       p->idx_rinf, drp.d(), dri.d(), drt.d(), nullptr, nullptr);
+    LAUNCH_OK();
+    if (r_p) HIPDRT_CHECK(hipMemcpyAsync(r_p, drp.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (r_inf) HIPDRT_CHECK(hipMemcpyAsync(r_inf, dri.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (r_tot) HIPDRT_CHECK(hipMemcpyAsync(r_tot, drt.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 """GPU: the fit loop's Gram and q kernels (csrc/gram.hip: gram_kernel in its four template forms, qvec_kernel; csrc/hyper.hip:
 batch_products_kernel<2, true>) in isolation, through the test hook hipdrt_debug_gram_l2 (include/hipdrt_debug.h), which calls
-launch_gram_l2 / launch_qvec exactly as the loop does (csrc/api.hip: outer_iteration).
+launch_gram_l2 / launch_qvec exactly as the loop does (csrc/plan_fit.hip: outer_iteration).
 
 The reference is the numpy restatement of tests/gram_util.py (checked on the CPU by tests/test_gram_util.py).  Operands are small
 integers (and powers of two, and squares under the roots), so every product and every sum is exact in binary64 whatever its

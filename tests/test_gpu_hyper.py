@@ -1,7 +1,7 @@
 """GPU: the hyper-parameter step of the fit loop (csrc/hyper.hip: hyper_kernel -- solve_s, solve_rho, the xmx freeze,
 estimate_weights, the convergence rule, the vz_offset column, update_scale -- with the products of estimate_weights inside it, from
 premv_kernel, or from batch_products_kernel<0> / <1> on the matrix pipe) in isolation, through the test hook hipdrt_debug_hyper_step
-(include/hipdrt_debug.h), which calls launch_hyper exactly as the loop does (csrc/api.hip: plan_hyper).
+(include/hipdrt_debug.h), which calls launch_hyper exactly as the loop does (csrc/plan_fit.hip: plan_hyper).
 
 The reference is the extended-precision restatement of tests/hyper_util.py, and every tolerance is the forward error bound derived in
 its docstring for a float64 evaluation in any summation order (checked from both sides on the CPU, on these very inputs, by

@@ -1,7 +1,8 @@
 """Fits a fixed set of spectra (C1 golden-size and C2-size) with whatever library HIPDRT_LIB points to and saves the raw
 results; two dumps compared bit for bit tell whether two builds compute the same thing.  Every path of the plan's device
 loop is taken once: EIS batch fits, a sub-batched fit, outlier_p, a warm restart, a prepared joint fit with the 'weight'
-factor rule and its restart with row factors, one iterate_qphb pass, and the posterior entry points.
+factor rule and its restart with row factors, one iterate_qphb pass, the posterior entry points, the Kramers-Kronig screen
+and the predictions of a fitted batch.
 python tools/dump_fit.py out.npz   /   python tools/dump_fit.py --cmp a.npz b.npz"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,6 +31,11 @@ for k in ("x", "weights", "rho", "outer_iters", "qp_iters_total"):
     out["c2_" + k] = r[k]
 v = d.estimate_distribution_var_batch(c2["tau"][::4])
 out["c2_var"] = np.asarray(v[0] if isinstance(v, tuple) else v)
+# model evaluation of the fitted C2 batch on the device: DRT and its first derivative, credible band, impedance, R_p
+for o in (0, 1):
+    out[f"c2_drt{o}"] = d.predict_drt_batch(order=o)
+out["c2_ci_lo"], out["c2_ci_hi"], out["c2_ci_ok"] = d.predict_drt_ci_batch()
+out["c2_z"], out["c2_r_p"] = d.predict_z_batch(), d.predict_r_p_batch()
 # the same range on a finer tau grid: n > 528, the posterior variance with the inverse diagonal blocks in global memory (four
 # spectra: their QPs run on the group kernel)
 tf = np.geomspace(c2["tau"][0], c2["tau"][-1], 600)
@@ -44,6 +50,10 @@ z1 = synth.zarc2_batch(c1["freq"], 16)
 r1 = DRT(fixed_basis_tau=c1["tau"]).fit_eis_batch(c1["freq"], z1)
 for k in ("x", "weights", "outer_iters", "qp_iters_total"):
     out["c1_" + k] = r1[k]
+# Kramers-Kronig screen of the C1 spectra: two rounds of fit -> screen, the second fit with the first screen's row factors
+kk = DRT(fixed_basis_tau=c1["tau"]).kk_test_batch(c1["freq"], z1)
+for k in ("outlier_mask", "clean_mask", "f_min", "f_max", "residuals", "std", "status", "z_hat"):
+    out["kk_" + k] = kk[k]
 f = np.logspace(5.5, -0.5, 60)
 r3 = DRT(basis_tau_ppd=8).fit_eis_batch(f, synth.zarc2_batch(f, 8))      # n = 61: odd number of block columns etc.
 for k in ("x", "outer_iters", "qp_iters_total"):
