@@ -76,6 +76,13 @@ class KkOpts(C.Structure):
                 ("outlier_weight", C.c_double)]
 
 
+class PeakOpts(C.Structure):
+    """hipdrt_peak_opts (include/hipdrt.h)"""
+    _fields_ = [("eval_sign", C.c_int), ("search", C.c_int), ("normalize", C.c_int), ("method", C.c_int),
+                ("height", C.c_double), ("prominence", C.c_double), ("prob_thresh", C.c_double), ("num_peaks", C.c_int),
+                ("fxx_var_floor", C.c_double), ("ext_left", C.c_int), ("ext_right", C.c_int)]
+
+
 class DebugGramArgs(C.Structure):
     """hipdrt_debug_gram_args (include/hipdrt_debug.h)"""
     _fields_ = [
@@ -148,6 +155,11 @@ SIGNATURES = {
     "hipdrt_plan_predict_drt": [_vp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _dp, _dp, _dp, _ip],
     "hipdrt_plan_predict_z": [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _ip],
     "hipdrt_plan_predict_resistances": [_vp, _dp, _dp, _dp, C.c_int],
+    "hipdrt_peak_opts_default": [C.POINTER(PeakOpts)],
+    "hipdrt_plan_find_peaks": [_vp, _dp, C.c_int, C.POINTER(PeakOpts), _dp, _ip, _ip, _dp, _dp, _dp, _ip, _ip, _ip, _dp, _dp, _dp,
+                               _ip],
+    "hipdrt_debug_find_peaks": [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.POINTER(PeakOpts), _ip, _ip, _dp, _dp, _dp, _ip, _ip,
+                                _ip, _dp, _dp, _dp],
     "hipdrt_debug_last_predict_ms": [_vp, C.POINTER(C.c_float)],
     "hipdrt_debug_apply_rows": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp],
     "hipdrt_comm_unique_id": [C.c_char_p],
@@ -201,7 +213,7 @@ SIGNATURES = {
                              _dp, _dp, _dp, _dp, _ip, _ip],
 }
 _RESTYPES = {"hipdrt_last_error": C.c_char_p, "hipdrt_stream": C.c_void_p, "hipdrt_default_fit_opts": None,
-             "hipdrt_default_kk_opts": None}
+             "hipdrt_default_kk_opts": None, "hipdrt_peak_opts_default": None}
 
 _lib = None
 _lock = threading.Lock()
@@ -284,6 +296,47 @@ def kk_opts(n_outlier_iter=2, p_thresh=1e-4, n_sigma=None, std_sample_fraction=0
         o.n_std = float(n_std)
     o.max_num_outliers, o.outlier_weight = int(max_num_outliers), float(outlier_weight)
     return o
+
+
+PEAK_METHODS = {'thresh': 0, 'prob': 1, 'map': 2}
+
+
+def peak_opts(eval_sign=1, search=1, normalize=1, method='thresh', height=None, prominence=None, prob_thresh=0.25, num_peaks=None,
+              fxx_var_floor=1e-5, ext_left=-1, ext_right=-1) -> PeakOpts:
+    """hipdrt_peak_opts from the keywords of DRT.find_peaks (None <-> NaN for the automatic thresholds, None <-> 0 for num_peaks);
+    method 'thresh', 'prob' or 'map' (the peak_prob / curv_prob rows), or its number"""
+    o = PeakOpts()
+    load_library().hipdrt_peak_opts_default(C.byref(o))
+    o.eval_sign, o.search, o.normalize = int(eval_sign), int(search), int(normalize)
+    o.method = PEAK_METHODS[method] if isinstance(method, str) else int(method)
+    o.height = float('nan') if height is None else float(height)
+    o.prominence = float('nan') if prominence is None else float(prominence)
+    o.prob_thresh, o.num_peaks, o.fxx_var_floor = float(prob_thresh), int(num_peaks or 0), float(fxx_var_floor)
+    o.ext_left, o.ext_right = int(ext_left), int(ext_right)
+    return o
+
+
+_PEAK_INT = ("peak_sign", "keep", "left_bases", "right_bases")
+_PEAK_F64 = ("heights", "prominences", "probs", "peak_prob", "curv_prob")
+
+
+def _peak_outputs(B, n, method, want=None):
+    """host arrays of the peak entry points, poisoned so that anything a kernel leaves unwritten shows; want: the names to
+    allocate (None: all the method has) -- what is left out is passed as NULL and neither formed nor downloaded"""
+    names = _PEAK_INT + _PEAK_F64[:3] + (_PEAK_F64[3:] if method == 2 else ()) + ("count", "used_prominence")
+    out = {}
+    for k in names:
+        if want is not None and k not in want:
+            continue
+        shape = B if k in ("count", "used_prominence") else (B, n)
+        out[k] = np.full(shape, -77, dtype=np.int32) if k in _PEAK_INT + ("count",) else np.full(shape, np.nan)
+    return out
+
+
+def _peak_out_args(out):
+    g = out.get
+    return (_pi(g("peak_sign")), _pi(g("keep")), _p(g("heights")), _p(g("prominences")), _p(g("probs")), _pi(g("left_bases")),
+            _pi(g("right_bases")), _pi(g("count")), _p(g("used_prominence")), _p(g("peak_prob")), _p(g("curv_prob")))
 
 
 def _kk_outputs(B, nf):
@@ -744,6 +797,19 @@ class Context:
         _check(self._lib.hipdrt_debug_apply_rows(self._h, B, K, ldx, int(col_offset), _p(X), r, _p(E), _p(sc), _p(out)))
         return out
 
+    def debug_find_peaks(self, fxx, f=None, var_fxx=None, var_f=None, opts: PeakOpts | None = None):
+        """tests: peaks_kernel on host rows (B, neval) (hipdrt_debug_find_peaks, include/hipdrt_debug.h) -> dict(peak_sign, keep,
+        heights, prominences, probs, left_bases, right_bases, count, used_prominence[, peak_prob, curv_prob]).  Raises when the
+        kernel wrote outside an output."""
+        rows = [None if r is None else np.atleast_2d(_f64(r)) for r in (fxx, f, var_fxx, var_f)]
+        B, n = rows[0].shape
+        if any(r is not None and r.shape != (B, n) for r in rows):
+            raise ValueError("all rows must have the shape of fxx")
+        opts = opts if opts is not None else peak_opts()
+        out = _peak_outputs(B, n, opts.method)
+        _check(self._lib.hipdrt_debug_find_peaks(self._h, B, n, *[_p(r) for r in rows], C.byref(opts), *_peak_out_args(out)))
+        return out
+
     def debug_last_predict_ms(self):
         """tools: kernel time in ms of the last predict_drt / predict_z of a plan of this context -> (mean or impedance, with band)"""
         ms = (C.c_float * 2)()
@@ -951,6 +1017,21 @@ class Plan:
         _check(self._lib.hipdrt_plan_predict_drt(self._h, _p(ev), ev.size, int(order), int(sign), int(normalize), s_lo, s_hi,
                                                  _p(mu), _p(lo), _p(hi), _pi(status)))
         return mu, lo, hi, status
+
+    def find_peaks(self, ln_tau_eval, opts: PeakOpts, row_scale=None, want=None):
+        """hipdrt_plan_find_peaks for the fitted batch -> dict of dense (B, neval) rows peak_sign, keep, heights, prominences,
+        probs, left_bases, right_bases (and peak_prob, curv_prob for method 2), count (B,), used_prominence (B,), status (B,).
+        row_scale (B,): per-spectrum factor on the coefficient scale (prepared plans, normalize = 0).  want: the names to
+        download (None: all); status always comes."""
+        ev = _f64(ln_tau_eval).ravel()
+        out = _peak_outputs(self.B, ev.size, opts.method, want)
+        out["status"] = np.empty(self.B, dtype=np.int32)
+        rs = None if row_scale is None else _f64(row_scale)
+        if rs is not None and rs.shape != (self.B,):
+            raise ValueError("row_scale must have shape (B,)")
+        _check(self._lib.hipdrt_plan_find_peaks(self._h, _p(ev), ev.size, C.byref(opts), _p(rs), *_peak_out_args(out),
+                                                _pi(out["status"])))
+        return out
 
     def predict_z(self, frequencies, include_drt=True, include_ohmic=True, include_inductance=True):
         """hipdrt_plan_predict_z: complex (B, nf) impedance of the fitted batch at any frequencies, and the status (B,)"""

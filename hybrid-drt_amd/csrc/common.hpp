@@ -287,6 +287,28 @@ void launch_z_assemble(hipStream_t st, int B, int nf, const double* y, const dou
                        int idx_induc, const double* cs, double inductance_scale, const double* freq, int mask,
                        const int* fit_status, double* z_re, double* z_im);
 
+// peaks.hip: peak finding on evaluated rows, one workgroup per spectrum (all pointers device memory; an output may be null)
+struct PeakArgs {
+    int neval, p2;                       // p2: power of two >= neval (set by launch_peaks)
+    hipdrt_peak_opts o;
+    const double *fxx, *f;               // [B][neval]; f may be null unless search = 0 or method = 2
+    const double *var_fxx, *var_f;       // [B][ldv] e' inv(P) e (methods 1, 2 / method 2), scaled by cs^2 / norm^2 while staged
+    long long ldv;
+    const double *cs, *norm;             // [B] or null (1)
+    const int *fit_status, *var_status;  // [B] or null: a negative fit status / a non-zero variance status empties the spectrum
+    int *peak_sign, *keep;               // [B][neval]
+    double *heights, *prominences, *probs;
+    int *left_bases, *right_bases;
+    int* count;                          // [B]
+    double* used_prominence;             // [B]
+    double *peak_prob, *curv_prob;       // [B][neval], method 2
+};
+int peak_check_opts(const hipdrt_peak_opts& o, int neval);
+size_t peaks_lds_bytes(int neval, int method, int need_f, int num_peaks);    // need_f: search = 0 or method = 2
+// HIPDRT_E_INVALID when the options are out of range, a row the mode reads is missing, or LDS cannot hold the rows; nothing is launched then
+int launch_peaks(hipStream_t s, PeakArgs a, int B);
+void launch_scale_mul(hipStream_t s, int B, const double* x, const double* y, double* out);
+
 // qp.hip
 struct QpArgs {
     int B, n;

@@ -1,5 +1,6 @@
 // Test and diagnostic hooks of include/hipdrt_debug.h: context switches, and single launchers run on host arrays exactly as
 // the fit loop runs them.  (hipdrt_debug_stream_pool sits with the pool in api.hip.)
+#include <cmath>
 #include <cstring>
 
 #include "plan.hpp"
@@ -145,7 +146,7 @@ struct Guarded {
     int check() {
         for (size_t i = 0; i < G; ++i)
             if (stage[i] != MARK || stage[G + bytes + i] != MARK) {
-                set_error(std::string("hyper step wrote outside ") + name);
+                set_error(std::string("the kernel under test wrote outside ") + name);
                 return HIPDRT_E_NUMERIC;
             }
         if (host) std::memcpy(host, stage.data() + G, bytes);
@@ -357,6 +358,52 @@ int hipdrt_debug_apply_rows(hipdrt_ctx* ctx, int B, int K, int ldx, int col_offs
                 return HIPDRT_E_NUMERIC;
             }
         }
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+// test hook (include/hipdrt_debug.h): peaks_kernel as it is, on host rows.  Every output sits between two borders of marker bytes.
+int hipdrt_debug_find_peaks(hipdrt_ctx* ctx, int B, int neval, const double* fxx, const double* f, const double* var_fxx,
+                            const double* var_f, const hipdrt_peak_opts* opts, int* peak_sign, int* keep, double* heights,
+                            double* prominences, double* probs, int* left_bases, int* right_bases, int* count,
+                            double* used_prominence, double* peak_prob, double* curv_prob) try {
+    HIPDRT_REQUIRE(ctx && fxx, "NULL pointer");
+    HIPDRT_REQUIRE(B >= 1 && B <= 65535 && neval >= 1 && neval <= (1 << 20), "1 <= B <= 65535, 1 <= neval <= 2^20");
+    hipdrt_peak_opts o;
+    if (opts) o = *opts; else hipdrt_peak_opts_default(&o);
+    TRY(peak_check_opts(o, neval));
+    const bool need_f = o.search == 0 || o.method == 2;
+    HIPDRT_REQUIRE(!need_f || f, "a two-pass search and the map probabilities need the f rows");
+    HIPDRT_REQUIRE(o.method == 0 || var_fxx, "methods 1 and 2 need var_fxx");
+    HIPDRT_REQUIRE(o.method != 2 || var_f, "method 2 needs var_f");
+    HIPDRT_REQUIRE(peaks_lds_bytes(neval, o.method, need_f, o.num_peaks) <= 160 * 1024 - 256,
+                   "find_peaks: neval too large for one workgroup's LDS");
+    const size_t bn = (size_t)B * neval;
+    const double* rows[4] = {fxx, need_f ? f : nullptr, o.method >= 1 ? var_fxx : nullptr, o.method == 2 ? var_f : nullptr};
+    for (const double* r : rows)
+        if (r) for (size_t i = 0; i < bn; ++i) HIPDRT_REQUIRE(std::isfinite(r[i]), "non-finite input row");
+    hipStream_t st; TRY(enter(ctx, &st));
+    DevBuf din[4];
+    for (int k = 0; k < 4; ++k) if (rows[k]) TRY(upload(din[k], rows[k], bn * sizeof(double), st));
+    PeakArgs a{};
+    a.neval = neval; a.o = o; a.fxx = din[0].d(); a.f = din[1].d(); a.var_fxx = din[2].d(); a.var_f = din[3].d(); a.ldv = neval;
+    Guarded g[11];
+    const size_t D = sizeof(double), I = sizeof(int);
+    if (peak_sign) { TRY(g[0].up("peak_sign", peak_sign, bn * I, st)); a.peak_sign = g[0].di(); }
+    if (keep) { TRY(g[1].up("keep", keep, bn * I, st)); a.keep = g[1].di(); }
+    if (heights) { TRY(g[2].up("heights", heights, bn * D, st)); a.heights = g[2].dd(); }
+    if (prominences) { TRY(g[3].up("prominences", prominences, bn * D, st)); a.prominences = g[3].dd(); }
+    if (probs) { TRY(g[4].up("probs", probs, bn * D, st)); a.probs = g[4].dd(); }
+    if (left_bases) { TRY(g[5].up("left_bases", left_bases, bn * I, st)); a.left_bases = g[5].di(); }
+    if (right_bases) { TRY(g[6].up("right_bases", right_bases, bn * I, st)); a.right_bases = g[6].di(); }
+    if (count) { TRY(g[7].up("count", count, (size_t)B * I, st)); a.count = g[7].di(); }
+    if (used_prominence) { TRY(g[8].up("used_prominence", used_prominence, (size_t)B * D, st)); a.used_prominence = g[8].dd(); }
+    if (peak_prob && o.method == 2) { TRY(g[9].up("peak_prob", peak_prob, bn * D, st)); a.peak_prob = g[9].dd(); }
+    if (curv_prob && o.method == 2) { TRY(g[10].up("curv_prob", curv_prob, bn * D, st)); a.curv_prob = g[10].dd(); }
+    TRY(launch_peaks(st, a, B));
+    LAUNCH_OK();
+    for (Guarded& q : g) if (q.buf.p) TRY(q.fetch(st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    for (Guarded& q : g) if (q.buf.p) TRY(q.check());
     return HIPDRT_OK;
 } HIPDRT_CATCH
 

@@ -1,5 +1,6 @@
-// Device helpers shared by the one-workgroup-per-spectrum kernels (hyper.hip, kk.hip): 512-thread workgroups, wavefront and
-// block reductions, the row-slab matrix-vector product, and the dynamic-LDS limit of their launchers.
+// Device helpers shared by the one-workgroup-per-spectrum kernels (hyper.hip, kk.hip, peaks.hip): 512-thread workgroups (peaks.hip:
+// 256, through the template argument), wavefront and block reductions, the bitonic sort, the row-slab matrix-vector product, and
+// the dynamic-LDS limit of their launchers.
 #pragma once
 #include "common.hpp"
 
@@ -41,7 +42,8 @@ __device__ __forceinline__ double hw_min(double v) {
     return v;
 }
 
-// block-wide reductions over HT threads; red = LDS [HNW]; two syncs so `red` is immediately reusable
+// block-wide reductions over NT threads; red = LDS [NT / 64]; two syncs so `red` is immediately reusable
+template <int NT = HT>
 __device__ __forceinline__ double blk_sum(double v, double* red) {
     v = hw_sum(v);
     __syncthreads();
@@ -49,7 +51,7 @@ __device__ __forceinline__ double blk_sum(double v, double* red) {
     __syncthreads();
     double t = 0.0;
 #pragma unroll
-    for (int w = 0; w < HNW; ++w) t += red[w];
+    for (int w = 0; w < NT / 64; ++w) t += red[w];
     return t;
 }
 __device__ __forceinline__ double blk_max(double v, double* red) {
@@ -71,6 +73,24 @@ __device__ __forceinline__ double blk_min(double v, double* red) {
 #pragma unroll
     for (int w = 1; w < HNW; ++w) t = fmin(t, red[w]);
     return t;
+}
+
+// ascending bitonic network over p2 (a power of two) doubles in LDS, NT threads
+template <int NT = HT>
+__device__ __forceinline__ void lds_sort(double* __restrict__ v, int p2) {
+    for (int k = 2; k <= p2; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = threadIdx.x; i < p2; i += NT) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const double a = v[i], c = v[l];
+                    const bool up = (i & k) == 0;
+                    if (up ? (a > c) : (a < c)) { v[i] = c; v[l] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    }
 }
 
 // y[i] = sum_j M[i][j] * v[j] for the rows owned by this wavefront; v in LDS; result to LDS out.  Four rows per

@@ -12,23 +12,6 @@
 
 namespace hipdrt {
 
-// ascending bitonic network over p2 (a power of two) doubles in LDS
-__device__ __forceinline__ void lds_sort(double* __restrict__ v, int p2) {
-    for (int k = 2; k <= p2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < p2; i += HT) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const double a = v[i], c = v[l];
-                    const bool up = (i & k) == 0;
-                    if (up ? (a > c) : (a < c)) { v[i] = c; v[l] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
-
 // np.percentile(method='linear') on the first N entries of the sorted array: virtual index q / 100 * (N - 1), numpy's _lerp
 __device__ __forceinline__ double lds_percentile(const double* __restrict__ v, int N, double q) {
     const double vi = q / 100.0 * (double)(N - 1);

@@ -1,0 +1,303 @@
+// Peak finding on the curvature rows of a fitted batch, one 256-thread workgroup per spectrum, rows in LDS:
+//
+//   DRT.find_peaks                 hybdrt/models/drt1d.py:3753-3947 (method 'thresh' and 'prob', num_peaks)
+//   curvature.peak_prob_1d         hybdrt/mapping/curvature.py:12-58, times sign(f) (hybdrt/mapping/drtmd.py:1064)
+//   DRTMD.predict_curv_prob        drtmd.py:1097-1104, elementwise
+//
+// scipy.signal.find_peaks(v, height=, prominence=) is restated: a local maximum is the middle (i + a - 1) / 2 of a plateau
+// [i, a) that rises at its left edge and falls at its right one, never the first or last sample; the prominence walks outwards
+// from the peak while v <= v[p], keeps the FIRST lowest sample on each side (the one nearest the peak) as the base, and is
+// v[p] - max(left minimum, right minimum).  hipdrt/models/peaks.py is the same arithmetic in numpy.
+//
+// Every plateau start is taken by one thread, which walks its plateau, applies the height (and, in a two-pass search, the f)
+// test, walks out for the bases and applies the prominence test: all of it reads LDS only and every decision is a comparison of
+// staged values, so the result does not depend on which thread takes which start.  The automatic threshold of 'thresh' is
+// np.std: the mean, then the mean squared deviation, each summed per thread over i = tid, tid + 256, ... and then across the
+// workgroup in one fixed tree -- the order depends on neval alone, never on B or on the spectrum's position.  Results go to
+// LDS rows and are written once, dense, by the loop at the end of the kernel: that loop (i < neval, offset b * neval + i) and the
+// two per-spectrum scalars are the only global stores.  Compiled with -ffp-contract=off: thresholds and probabilities round as
+// written.
+#include <cmath>
+
+#include "hyper_dev.hpp"
+
+namespace hipdrt {
+
+static constexpr int PKT = 256;
+static constexpr double PK_SQRT2 = 1.4142135623730951;      // 2 ** 0.5
+
+// numpy's sign, maximum and minimum (NaN goes through)
+__device__ __forceinline__ double np_sign(double x) { return x > 0.0 ? 1.0 : (x < 0.0 ? -1.0 : (x == 0.0 ? 0.0 : x)); }
+__device__ __forceinline__ double np_max(double a, double c) { return (a != a) ? a : ((c != c) ? c : (a > c ? a : c)); }
+__device__ __forceinline__ double np_min(double a, double c) { return (a != a) ? a : ((c != c) ? c : (a < c ? a : c)); }
+// 1 - Phi(0; mu, sigma)
+__device__ __forceinline__ double upper_prob(double mu, double sigma) { return 1.0 - 0.5 * erfc(mu / (sigma * PK_SQRT2)); }
+
+// one search pass on v = -s * fxx: peaks that pass height, the f test (two: s * f[p] > 0) and prominence are entered at their index
+__device__ __forceinline__ void peaks_pass(const double* __restrict__ fxx, const double* __restrict__ f, int n, int s, bool two,
+                                           double height, double prominence, int* __restrict__ sgn, double* __restrict__ prom,
+                                           int* __restrict__ lb, int* __restrict__ rb) {
+    auto V = [&](int i) { return s > 0 ? -fxx[i] : fxx[i]; };
+    for (int i = 1 + (int)threadIdx.x; i < n - 1; i += PKT) {
+        const double vi = V(i);
+        if (!(V(i - 1) < vi)) continue;
+        int e = i + 1;
+        while (e < n - 1 && V(e) == vi) ++e;               // e <= n - 1
+        if (!(V(e) < vi)) continue;
+        const int p = (i + e - 1) / 2;
+        if (!(vi >= height)) continue;
+        if (two && !((s > 0 ? f[p] : -f[p]) > 0.0)) continue;
+        double lmin = vi, rmin = vi;
+        int lbi = p, rbi = p;
+        for (int j = p; j >= 0; --j) {
+            const double vj = V(j);
+            if (!(vj <= vi)) break;
+            if (vj < lmin) { lmin = vj; lbi = j; }
+        }
+        for (int j = p; j < n; ++j) {
+            const double vj = V(j);
+            if (!(vj <= vi)) break;
+            if (vj < rmin) { rmin = vj; rbi = j; }
+        }
+        const double pr = vi - (lmin > rmin ? lmin : rmin);
+        if (!(pr >= prominence)) continue;
+        sgn[p] = s; prom[p] = pr; lb[p] = lbi; rb[p] = rbi;
+    }
+}
+
+// LDS rows of one spectrum: doubles fxx, prom, [f], [vxx, prob], [vf], [srt p2]; ints sgn, lb, rb
+struct PeakLds { int f, var, varf, sort; };
+static __host__ __device__ inline PeakLds peak_lds(int method, int need_f, int num_peaks) {
+    PeakLds l;
+    l.f = need_f; l.var = method >= 1; l.varf = method == 2; l.sort = method == 1 && num_peaks > 0;
+    return l;
+}
+
+// grid = B
+__global__ __launch_bounds__(PKT) void peaks_kernel(PeakArgs a) {
+    extern __shared__ double sm[];
+    __shared__ double red[PKT / 64];
+    const int b = blockIdx.x, tid = threadIdx.x, n = a.neval, method = a.o.method;
+    const PeakLds l = peak_lds(method, a.f != nullptr, a.o.num_peaks);
+    double* fxx = sm;
+    double* prom = fxx + n;
+    double* p_ = prom + n;
+    double* f = p_;      p_ += l.f ? n : 0;
+    double* vxx = p_;    p_ += l.var ? n : 0;
+    double* prob = p_;   p_ += l.var ? n : 0;
+    double* vf = p_;     p_ += l.varf ? n : 0;
+    double* srt = p_;    p_ += l.sort ? a.p2 : 0;
+    int* sgn = reinterpret_cast<int*>(p_);
+    int* lb = sgn + n;
+    int* rb = lb + n;
+    const size_t row = (size_t)b * n;
+
+    const bool dead = (a.fit_status && a.fit_status[b] < 0) || (l.var && a.var_status && a.var_status[b] != 0);
+    if (dead) {                                          // a failed fit, or sigma asked of a P that is not positive definite
+        for (int i = tid; i < n; i += PKT) {
+            const size_t o = row + i;
+            if (a.peak_sign) a.peak_sign[o] = 0;
+            if (a.keep) a.keep[o] = 0;
+            if (a.heights) a.heights[o] = NAN;
+            if (a.prominences) a.prominences[o] = NAN;
+            if (a.probs) a.probs[o] = NAN;
+            if (a.left_bases) a.left_bases[o] = -1;
+            if (a.right_bases) a.right_bases[o] = -1;
+            if (a.peak_prob) a.peak_prob[o] = NAN;
+            if (a.curv_prob) a.curv_prob[o] = NAN;
+        }
+        if (tid == 0) {
+            if (a.count) a.count[b] = 0;
+            if (a.used_prominence) a.used_prominence[b] = NAN;
+        }
+        return;
+    }
+
+    // ---- stage the rows; the variances scaled as drt_band_kernel scales them ----
+    double c2 = 1.0, n2 = 1.0;
+    if (l.var) {
+        if (a.cs) c2 = a.cs[b] * a.cs[b];
+        if (a.norm) n2 = a.norm[b] * a.norm[b];
+    }
+    for (int i = tid; i < n; i += PKT) {
+        fxx[i] = a.fxx[row + i];
+        if (l.f) f[i] = a.f[row + i];
+        if (l.var) {
+            double v = a.var_fxx[(size_t)b * a.ldv + i];
+            if (a.cs) v = v * c2;
+            if (a.norm) v = v / n2;
+            vxx[i] = v;
+        }
+        if (l.varf) {
+            double v = a.var_f[(size_t)b * a.ldv + i];
+            if (a.cs) v = v * c2;
+            if (a.norm) v = v / n2;
+            vf[i] = v;
+        }
+        prom[i] = 0.0; sgn[i] = 0; lb[i] = -1; rb[i] = -1;
+        if (l.var) prob[i] = 0.0;
+    }
+    __syncthreads();
+    // extend_var's clamp (drt1d.py:3123-3140: the left part first, so the right bound may already be a clamped value), then the floor
+    if (l.var) {
+        const int li = a.o.ext_left, ri = a.o.ext_right;
+        const double floor_v = a.o.fxx_var_floor;
+        for (int k = 0; k < (l.varf ? 2 : 1); ++k) {
+            double* v = k ? vf : vxx;
+            const double vl = li >= 0 ? v[li] : 0.0;
+            double vr = ri >= 0 ? v[ri] : 0.0;
+            if (li >= 0 && ri >= 0 && ri < li) vr = np_max(vr, vl);
+            __syncthreads();
+            for (int i = tid; i < n; i += PKT) {
+                double x = v[i];
+                if (li >= 0 && i < li) x = np_max(x, vl);
+                if (ri >= 0 && i >= ri) x = np_max(x, vr);
+                if (k == 0 && floor_v > 0.0 && x < floor_v) x = floor_v;
+                v[i] = x;
+            }
+            __syncthreads();
+        }
+    }
+
+    // ---- thresholds (drt1d.py:3846-3858) ----
+    double prominence = a.o.prominence, height = a.o.height;
+    if (height != height) height = method == 0 ? 0.0 : 1e-3;
+    if (prominence != prominence) {
+        if (method == 0) {
+            double s = 0.0, c = 0.0;
+            for (int i = tid; i < n; i += PKT) if (!isinf(fxx[i])) { s += fxx[i]; c += 1.0; }
+            s = blk_sum<PKT>(s, red);
+            c = blk_sum<PKT>(c, red);
+            const double mean = s / c;
+            double d = 0.0;
+            for (int i = tid; i < n; i += PKT) if (!isinf(fxx[i])) { const double t = fabs(fxx[i] - mean); d += t * t; }
+            d = blk_sum<PKT>(d, red);
+            prominence = 0.05 * sqrt(d / c) + 5e-3;
+        } else {
+            prominence = 5e-3;
+        }
+    }
+
+    // ---- the search (drt1d.py:3886-3913): one pass, or the passes -1 and +1 with the f test ----
+    if (a.o.search != 0) {
+        peaks_pass(fxx, f, n, a.o.search, false, height, prominence, sgn, prom, lb, rb);
+    } else {
+        peaks_pass(fxx, f, n, -1, true, height, prominence, sgn, prom, lb, rb);
+        peaks_pass(fxx, f, n, 1, true, height, prominence, sgn, prom, lb, rb);   // (a maximum of fxx is no maximum of -fxx)
+    }
+    __syncthreads();
+
+    // ---- probabilities (drt1d.py:3915-3941; curvature.py:46-53) ----
+    double thresh = a.o.prob_thresh;
+    if (l.var) {
+        for (int i = tid; i < n; i += PKT) {
+            if (sgn[i] == 0) continue;
+            const double h = sgn[i] > 0 ? -fxx[i] : fxx[i];
+            const double mp = np_min(prom[i], h);
+            if (method == 1) prob[i] = 1.0 - erfc(mp / (sqrt(vxx[i]) * PK_SQRT2));
+            else prob[i] = np_min(upper_prob(mp, sqrt(vxx[i])), upper_prob(fabs(f[i]), sqrt(vf[i])));
+        }
+        __syncthreads();
+        if (l.sort) {
+            // the min(num_peaks, count)-th largest probability; two passes can put peaks on neighbouring samples, so every sample has a slot
+            double c = 0.0;
+            for (int i = tid; i < a.p2; i += PKT) {
+                const bool pk = i < n && sgn[i] != 0;
+                srt[i] = pk ? prob[i] : -INFINITY;
+                if (pk) c += 1.0;
+            }
+            c = blk_sum<PKT>(c, red);                    // (ends with a barrier: srt is complete)
+            lds_sort<PKT>(srt, a.p2);
+            const int cnt = (int)c, k = a.o.num_peaks < cnt ? a.o.num_peaks : cnt;
+            if (cnt > 0) thresh = srt[a.p2 - k];
+        }
+    }
+
+    // ---- the dense rows: the only global stores of the kernel besides the two scalars below ----
+    double kept = 0.0;
+    for (int i = tid; i < n; i += PKT) {
+        const size_t o = row + i;
+        const int s = sgn[i];
+        const int kp = s != 0 && (method != 1 || prob[i] >= thresh) ? 1 : 0;
+        kept += (double)kp;
+        if (a.peak_sign) a.peak_sign[o] = s;
+        if (a.keep) a.keep[o] = kp;
+        if (a.heights) a.heights[o] = s == 0 ? 0.0 : (s > 0 ? -fxx[i] : fxx[i]);
+        if (a.prominences) a.prominences[o] = prom[i];
+        if (a.probs) a.probs[o] = l.var ? prob[i] : 0.0;
+        if (a.left_bases) a.left_bases[o] = lb[i];
+        if (a.right_bases) a.right_bases[o] = rb[i];
+        if (method == 2) {
+            const double sf = np_sign(f[i]);
+            if (a.peak_prob) a.peak_prob[o] = prob[i] * sf;
+            if (a.curv_prob) {
+                double fp = upper_prob(-np_sign(fxx[i]) * f[i], sqrt(vf[i]));
+                double cp = upper_prob(-sf * fxx[i], sqrt(vxx[i]));
+                fp = 2.0 * np_max(fp - 0.5, 0.0);
+                cp = 2.0 * np_max(cp - 0.5, 0.0);
+                a.curv_prob[o] = np_min(fp, cp) * sf;
+            }
+        }
+    }
+    kept = blk_sum<PKT>(kept, red);
+    if (tid == 0) {
+        if (a.count) a.count[b] = (int)kept;
+        if (a.used_prominence) a.used_prominence[b] = prominence;
+    }
+}
+
+static int peaks_p2(int neval) {
+    int p2 = 2;
+    while (p2 < neval) p2 <<= 1;
+    return p2;
+}
+
+size_t peaks_lds_bytes(int neval, int method, int need_f, int num_peaks) {
+    const PeakLds l = peak_lds(method, need_f, num_peaks);
+    const size_t n = (size_t)neval;
+    size_t d = 2 * n + (l.f ? n : 0) + (l.var ? 2 * n : 0) + (l.varf ? n : 0) + (l.sort ? (size_t)peaks_p2(neval) : 0);
+    return d * sizeof(double) + 3 * n * sizeof(int);
+}
+
+int peak_check_opts(const hipdrt_peak_opts& o, int neval) {
+    HIPDRT_REQUIRE(neval >= 1, "neval >= 1");
+    HIPDRT_REQUIRE(o.search >= -1 && o.search <= 1, "search must be 1, -1 or 0 (two passes)");
+    HIPDRT_REQUIRE(o.method >= 0 && o.method <= 2, "method must be 0 (thresh), 1 (prob) or 2 (map probabilities)");
+    HIPDRT_REQUIRE(!std::isinf(o.height) && !std::isinf(o.prominence), "height and prominence: finite, or NaN for automatic");
+    HIPDRT_REQUIRE(std::isfinite(o.prob_thresh), "prob_thresh must be finite");
+    HIPDRT_REQUIRE(o.num_peaks >= 0, "num_peaks >= 0 (0: off)");
+    HIPDRT_REQUIRE(std::isfinite(o.fxx_var_floor), "fxx_var_floor must be finite");
+    HIPDRT_REQUIRE(o.ext_left >= -1 && o.ext_left < neval && o.ext_right >= -1 && o.ext_right < neval,
+                   "ext_left and ext_right: an index of the evaluation grid, or -1");
+    return HIPDRT_OK;
+}
+
+int launch_peaks(hipStream_t s, PeakArgs a, int B) {
+    if (int rc = peak_check_opts(a.o, a.neval)) return rc;
+    HIPDRT_REQUIRE(B >= 1 && a.fxx, "peaks: B >= 1 and the curvature rows");
+    HIPDRT_REQUIRE(a.f || (a.o.search != 0 && a.o.method != 2), "peaks: a two-pass search and the map probabilities need the f rows");
+    HIPDRT_REQUIRE(a.o.method == 0 || a.var_fxx, "peaks: methods 1 and 2 need the curvature's variance");
+    HIPDRT_REQUIRE(a.o.method != 2 || a.var_f, "peaks: method 2 needs the variance of f");
+    if (a.o.search != 0 && a.o.method != 2) a.f = nullptr;      // not read: not staged
+    a.p2 = peaks_p2(a.neval);
+    const size_t lds = peaks_lds_bytes(a.neval, a.o.method, a.f != nullptr, a.o.num_peaks);
+    if (lds > kLdsLimit) {
+        set_error("invalid argument: peaks: " + std::to_string(lds) + " bytes of LDS needed (neval, method), " +
+                  std::to_string(kLdsLimit) + " available");
+        return HIPDRT_E_INVALID;
+    }
+    if (int rc = set_lds(reinterpret_cast<const void*>(peaks_kernel), lds, "peaks_kernel")) return rc;
+    hipLaunchKernelGGL(peaks_kernel, dim3(B), dim3(PKT), lds, s, a);
+    return 0;
+}
+
+// out[b] = x[b] * y[b]: a caller's per-spectrum factor on top of the plan's coefficient scale
+__global__ void scale_mul_kernel(int B, const double* __restrict__ x, const double* __restrict__ y, double* __restrict__ out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B) out[b] = x[b] * y[b];
+}
+void launch_scale_mul(hipStream_t s, int B, const double* x, const double* y, double* out) {
+    hipLaunchKernelGGL(scale_mul_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, x, y, out);
+}
+
+}  // namespace hipdrt

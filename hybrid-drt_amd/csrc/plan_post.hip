@@ -296,6 +296,65 @@ static int predict_basis(const hipdrt_plan* p, PredictBasis& pb) {
     return HIPDRT_OK;
 }
 
+// What a DRT prediction leaves on the device (hipdrt_plan_predict_drt, hipdrt_plan_find_peaks): for every order asked for the
+// signed evaluation rows and the mean rows of the batch, the normalisation scalars, and (want_var) e' inv(P_b) e of all rows from
+// one factorisation per spectrum, not yet scaled.
+struct DrtRows {
+    DevBuf dE, dsum, dabs, dnorm, dscale, dcs, dmu, dvar, dvstat;      // dE and dmu are allocated by the caller
+    const double* scale = nullptr;       // [B] the factor the mean rows carry
+    const double* cs = nullptr;          // [B] the coefficient scale behind it (times row_scale)
+    const double* norm = nullptr;        // [B] R_p, or null without normalisation
+    int neval = 0, B = 0, norders = 0;
+    double* mu(int k) const { return dmu.d() + (size_t)k * B * neval; }                 // [B][neval] of orders[k]
+    const double* var(int k) const { return dvar.d() + (size_t)k * neval; }             // row stride ldv()
+    long long ldv() const { return (long long)((norders * neval + 15) / 16) * 16; }
+};
+// orders[norders] (norders 1 or 2): rows k * neval .. of dE and slab k of dmu belong to orders[k].  dev: ln(tau_eval) on the
+// device.  row_scale: host [B] or null.  The timer is marked once, after the mean rows.
+static int plan_drt_rows_dev(hipdrt_plan* p, const PredictBasis& pb, int neval, const int* orders,
+                             int norders, int sign, int normalize, const double* row_scale, bool want_var, hipStream_t st,
+                             DevBuf& dev, DrtRows& R, PredictTimer& tm) {
+    const int B = p->B, n = p->n, ns = p->ns, width = n - ns, nb = pb.nb;
+    R.neval = neval; R.B = B; R.norders = norders;
+    // E[neval][width]: the signed evaluation rows over the whole DRT block (+E | 0), (0 | -E) or (+E | -E)
+    if (pb.copies == 2 && sign != 0) HIPDRT_CHECK(hipMemsetAsync(R.dE.p, 0, R.dE.bytes, st));
+    for (int k = 0; k < norders; ++k) {
+        double* E = R.dE.d() + (size_t)k * neval * width;
+        if (sign != -1) TRY(func_eval_dev(st, pb.ln_tau, nb, dev.d(), neval, pb.eps, orders[k], 1.0, E, width));
+        if (pb.copies == 2 && sign != 1) TRY(func_eval_dev(st, pb.ln_tau, nb, dev.d(), neval, pb.eps, orders[k], -1.0, E + nb, width));
+    }
+    R.cs = p->coef_scale.d();
+    if (row_scale) {
+        DevBuf drs;
+        TRY(upload(drs, row_scale, (size_t)B * sizeof(double), st));
+        HIPDRT_CHECK(R.dcs.alloc((size_t)B * sizeof(double)));
+        launch_scale_mul(st, B, p->coef_scale.d(), drs.d(), R.dcs.d());
+        LAUNCH_OK();
+        HIPDRT_CHECK(hipStreamSynchronize(st));      // drs is released on return
+        R.cs = R.dcs.d();
+    }
+    R.scale = R.cs;
+    if (normalize) {
+        HIPDRT_CHECK(R.dsum.alloc((size_t)B * sizeof(double))); HIPDRT_CHECK(R.dabs.alloc((size_t)B * sizeof(double)));
+        HIPDRT_CHECK(R.dnorm.alloc((size_t)B * sizeof(double))); HIPDRT_CHECK(R.dscale.alloc((size_t)B * sizeof(double)));
+        launch_drt_sums(st, B, p->x.d(), n, ns, nb, pb.copies, sign, R.dsum.d(), R.dabs.d());
+        launch_drt_scalars(st, B, R.dsum.d(), R.dabs.d(), R.cs, 1.7724538509055159 / pb.eps, 1, normalize == 2,
+                           p->x.d(), n, -1, nullptr, nullptr, nullptr, R.dnorm.d(), R.dscale.d());
+        LAUNCH_OK();
+        R.scale = R.dscale.d();
+        R.norm = R.dnorm.d();
+    }
+    for (int k = 0; k < norders; ++k) {
+        launch_apply_rows(st, B, width, p->x.d(), n, ns, neval, R.dE.d() + (size_t)k * neval * width, width, R.scale,
+                          p->fit_status.i(), R.mu(k), neval);
+        LAUNCH_OK();
+    }
+    tm.mark();
+    // sigma^2 = diag(E inv(P) E') from the variance path, fed the evaluation rows where they are (both orders as one row block)
+    if (want_var) TRY(plan_quadratic_forms_dev(p, R.dE.d(), norders * neval, width, ns, R.dvar, R.dvstat));
+    return HIPDRT_OK;
+}
+
 int hipdrt_plan_predict_drt(hipdrt_plan* p, const double* ln_tau_eval, int neval, int order, int sign, int normalize, double s_lo,
                             double s_hi, double* mu, double* lo, double* hi, int* status) try {
     HIPDRT_REQUIRE(p && ln_tau_eval && mu, "NULL pointer");
@@ -309,49 +368,110 @@ int hipdrt_plan_predict_drt(hipdrt_plan* p, const double* ln_tau_eval, int neval
     const bool band = lo || hi;
     HIPDRT_REQUIRE(!band || (std::isfinite(s_lo) && std::isfinite(s_hi)), "s_lo and s_hi must be finite");
     hipStream_t st; TRY(enter(p->ctx, &st));
-    const int B = p->B, n = p->n, ns = p->ns, width = n - ns, nb = pb.nb;
-    // E[neval][width]: the signed evaluation rows over the whole DRT block (+E | 0), (0 | -E) or (+E | -E)
-    DevBuf dev, dE, dsum, dabs, dnorm, dscale, dmu, dlo, dhi, dvar, dvstat;
+    const int B = p->B, width = p->n - p->ns;
+    DevBuf dev, dlo, dhi;
+    DrtRows R;
     TRY(upload(dev, ln_tau_eval, (size_t)neval * sizeof(double), st));
-    HIPDRT_CHECK(dE.alloc((size_t)neval * width * sizeof(double)));
-    HIPDRT_CHECK(dmu.alloc((size_t)B * neval * sizeof(double)));
+    HIPDRT_CHECK(R.dE.alloc((size_t)neval * width * sizeof(double)));
+    HIPDRT_CHECK(R.dmu.alloc((size_t)B * neval * sizeof(double)));
     PredictTimer tm(p->ctx, st);
-    if (pb.copies == 2 && sign != 0) HIPDRT_CHECK(hipMemsetAsync(dE.p, 0, dE.bytes, st));
-    if (sign != -1) TRY(func_eval_dev(st, pb.ln_tau, nb, dev.d(), neval, pb.eps, order, 1.0, dE.d(), width));
-    if (pb.copies == 2 && sign != 1) TRY(func_eval_dev(st, pb.ln_tau, nb, dev.d(), neval, pb.eps, order, -1.0, dE.d() + nb, width));
-    const double* scale = p->coef_scale.d();
-    if (normalize) {
-        HIPDRT_CHECK(dsum.alloc((size_t)B * sizeof(double))); HIPDRT_CHECK(dabs.alloc((size_t)B * sizeof(double)));
-        HIPDRT_CHECK(dnorm.alloc((size_t)B * sizeof(double))); HIPDRT_CHECK(dscale.alloc((size_t)B * sizeof(double)));
-        launch_drt_sums(st, B, p->x.d(), n, ns, nb, pb.copies, sign, dsum.d(), dabs.d());
-        launch_drt_scalars(st, B, dsum.d(), dabs.d(), p->coef_scale.d(), 1.7724538509055159 / pb.eps, 1, normalize == 2,
-                           p->x.d(), n, -1, nullptr, nullptr, nullptr, dnorm.d(), dscale.d());
-        LAUNCH_OK();
-        scale = dscale.d();
-    }
-    launch_apply_rows(st, B, width, p->x.d(), n, ns, neval, dE.d(), width, scale, p->fit_status.i(), dmu.d(), neval);
-    LAUNCH_OK();
-    tm.mark();
+    TRY(plan_drt_rows_dev(p, pb, neval, &order, 1, sign, normalize, nullptr, band, st, dev, R, tm));
     std::vector<int> hs(B), hv;
     if (band) {
-        // sigma^2 = diag(E inv(P) E') from the variance path, fed the evaluation rows where they are
-        TRY(plan_quadratic_forms_dev(p, dE.d(), neval, width, ns, dvar, dvstat));
         if (lo) HIPDRT_CHECK(dlo.alloc((size_t)B * neval * sizeof(double)));
         if (hi) HIPDRT_CHECK(dhi.alloc((size_t)B * neval * sizeof(double)));
-        launch_drt_band(st, B, neval, dmu.d(), dvar.d(), (long long)((neval + 15) / 16) * 16, p->coef_scale.d(),
-                        normalize ? dnorm.d() : nullptr, s_lo, s_hi, dvstat.i(), p->fit_status.i(), dlo.d(), dhi.d());
+        launch_drt_band(st, B, neval, R.mu(0), R.dvar.d(), R.ldv(), p->coef_scale.d(), R.norm, s_lo, s_hi, R.dvstat.i(),
+                        p->fit_status.i(), dlo.d(), dhi.d());
         LAUNCH_OK();
         tm.mark();
         if (lo) HIPDRT_CHECK(hipMemcpyAsync(lo, dlo.p, dlo.bytes, hipMemcpyDeviceToHost, st));
         if (hi) HIPDRT_CHECK(hipMemcpyAsync(hi, dhi.p, dhi.bytes, hipMemcpyDeviceToHost, st));
         hv.resize(B);
-        HIPDRT_CHECK(hipMemcpyAsync(hv.data(), dvstat.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPDRT_CHECK(hipMemcpyAsync(hv.data(), R.dvstat.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
     }
-    HIPDRT_CHECK(hipMemcpyAsync(mu, dmu.p, dmu.bytes, hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipMemcpyAsync(mu, R.dmu.p, R.dmu.bytes, hipMemcpyDeviceToHost, st));
     HIPDRT_CHECK(hipMemcpyAsync(hs.data(), p->fit_status.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
     HIPDRT_CHECK(hipStreamSynchronize(st));
     if (status)
         for (int b = 0; b < B; ++b) status[b] = (hs[b] >= 0 && band && hv[b] != 0) ? HIPDRT_PREDICT_NOT_PD : hs[b];
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+// ---- peak finding for the fitted batch (csrc/peaks.hip) ------------------------------------------------------------------------
+void hipdrt_peak_opts_default(hipdrt_peak_opts* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->eval_sign = 1; o->search = 1; o->normalize = 1; o->method = 0;
+    o->height = __builtin_nan(""); o->prominence = __builtin_nan("");
+    o->prob_thresh = 0.25; o->num_peaks = 0; o->fxx_var_floor = 1e-5; o->ext_left = -1; o->ext_right = -1;
+}
+
+int hipdrt_plan_find_peaks(hipdrt_plan* p, const double* ln_tau_eval, int neval, const hipdrt_peak_opts* opts,
+                           const double* row_scale, int* peak_sign, int* keep, double* heights, double* prominences, double* probs,
+                           int* left_bases, int* right_bases, int* count, double* used_prominence, double* peak_prob,
+                           double* curv_prob, int* status) try {
+    HIPDRT_REQUIRE(p && ln_tau_eval, "NULL pointer");
+    PredictBasis pb;
+    TRY(predict_basis(p, pb));
+    hipdrt_peak_opts o;
+    if (opts) o = *opts; else hipdrt_peak_opts_default(&o);
+    // every check comes before the first launch
+    TRY(peak_check_opts(o, neval));
+    const int sign = o.eval_sign, normalize = o.normalize;
+    HIPDRT_REQUIRE(sign == 1 || (pb.copies == 2 && (sign == 0 || sign == -1)),
+                   "eval_sign must be 1, or 1, -1 or 0 when the DRT block holds a positive and a negative copy");
+    HIPDRT_REQUIRE(normalize >= 0 && normalize <= 2, "normalize must be 0, 1 (by R_p) or 2 (by absolute R_p)");
+    HIPDRT_REQUIRE(!row_scale || normalize == 0, "row_scale goes with normalize = 0 (a ratio to the spectrum's own R_p carries no scale)");
+    const int B = p->B, width = p->n - p->ns;
+    if (row_scale) for (int b = 0; b < B; ++b) HIPDRT_REQUIRE(row_scale[b] > 0.0 && std::isfinite(row_scale[b]), "row_scale must be positive and finite");
+    const bool need_f = o.search == 0 || o.method == 2, need_var = o.method >= 1;
+    const int orders[2] = {2, 0}, norders = need_f ? 2 : 1;
+    PeakArgs a{};
+    a.neval = neval; a.o = o;
+    HIPDRT_REQUIRE(peaks_lds_bytes(neval, o.method, need_f, o.num_peaks) <= 160 * 1024 - 256,
+                   "find_peaks: neval too large for one workgroup's LDS");
+    hipStream_t st; TRY(enter(p->ctx, &st));
+    DevBuf dev;
+    DrtRows R;
+    TRY(upload(dev, ln_tau_eval, (size_t)neval * sizeof(double), st));
+    HIPDRT_CHECK(R.dE.alloc((size_t)norders * neval * width * sizeof(double)));
+    HIPDRT_CHECK(R.dmu.alloc((size_t)norders * B * neval * sizeof(double)));
+    const size_t bn = (size_t)B * neval;
+    DevBuf dsg, dkp, dht, dpr, dpb, dlb, drb, dct, dup, dpp, dcp;
+    if (peak_sign) { HIPDRT_CHECK(dsg.alloc(bn * sizeof(int))); a.peak_sign = dsg.i(); }
+    if (keep) { HIPDRT_CHECK(dkp.alloc(bn * sizeof(int))); a.keep = dkp.i(); }
+    if (heights) { HIPDRT_CHECK(dht.alloc(bn * sizeof(double))); a.heights = dht.d(); }
+    if (prominences) { HIPDRT_CHECK(dpr.alloc(bn * sizeof(double))); a.prominences = dpr.d(); }
+    if (probs) { HIPDRT_CHECK(dpb.alloc(bn * sizeof(double))); a.probs = dpb.d(); }
+    if (left_bases) { HIPDRT_CHECK(dlb.alloc(bn * sizeof(int))); a.left_bases = dlb.i(); }
+    if (right_bases) { HIPDRT_CHECK(drb.alloc(bn * sizeof(int))); a.right_bases = drb.i(); }
+    if (count) { HIPDRT_CHECK(dct.alloc((size_t)B * sizeof(int))); a.count = dct.i(); }
+    if (used_prominence) { HIPDRT_CHECK(dup.alloc((size_t)B * sizeof(double))); a.used_prominence = dup.d(); }
+    if (peak_prob && o.method == 2) { HIPDRT_CHECK(dpp.alloc(bn * sizeof(double))); a.peak_prob = dpp.d(); }
+    if (curv_prob && o.method == 2) { HIPDRT_CHECK(dcp.alloc(bn * sizeof(double))); a.curv_prob = dcp.d(); }
+    PredictTimer tm(p->ctx, st);
+    TRY(plan_drt_rows_dev(p, pb, neval, orders, norders, sign, normalize, row_scale, need_var, st, dev, R, tm));
+    a.fxx = R.mu(0);
+    a.f = need_f ? R.mu(1) : nullptr;
+    if (need_var) {
+        a.var_fxx = R.var(0); a.var_f = o.method == 2 ? R.var(1) : nullptr; a.ldv = R.ldv();
+        a.cs = R.cs; a.norm = R.norm; a.var_status = R.dvstat.i();
+    }
+    a.fit_status = p->fit_status.i();
+    TRY(launch_peaks(st, a, B));
+    LAUNCH_OK();
+    tm.mark();
+    // (KkOut::back: copy a device output to the host when both exist)
+    TRY(KkOut::back(peak_sign, dsg, st)); TRY(KkOut::back(keep, dkp, st)); TRY(KkOut::back(heights, dht, st));
+    TRY(KkOut::back(prominences, dpr, st)); TRY(KkOut::back(probs, dpb, st)); TRY(KkOut::back(left_bases, dlb, st));
+    TRY(KkOut::back(right_bases, drb, st)); TRY(KkOut::back(count, dct, st)); TRY(KkOut::back(used_prominence, dup, st));
+    TRY(KkOut::back(peak_prob, dpp, st)); TRY(KkOut::back(curv_prob, dcp, st));
+    std::vector<int> hs(B), hv(B, 0);
+    HIPDRT_CHECK(hipMemcpyAsync(hs.data(), p->fit_status.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (need_var) HIPDRT_CHECK(hipMemcpyAsync(hv.data(), R.dvstat.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    if (status)
+        for (int b = 0; b < B; ++b) status[b] = (hs[b] >= 0 && need_var && hv[b] != 0) ? HIPDRT_PREDICT_NOT_PD : hs[b];
     return HIPDRT_OK;
 } HIPDRT_CATCH
 

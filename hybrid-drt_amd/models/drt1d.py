@@ -12,7 +12,7 @@ import numpy as np
 from .. import _ffi, preprocessing as pp
 from ..matrices import mat1d
 from ..utils.array import is_uniform
-from . import kk, predict, qphb
+from . import kk, peaks, predict, qphb
 from .prepared import PreparedFitMixin, combine_status
 
 _FIT_KW_DEFAULTS = dict(  # DRT._qphb_fit_core keyword defaults (drt1d.py:102-137) that the device loop honours
@@ -779,6 +779,102 @@ class DRT(PreparedFitMixin):
     def predict_r_tot(self, b=0):
         """DRT.predict_r_tot (drt1d.py:3583-3584) of member ``b`` of the last fit"""
         return float(self.predict_r_tot_batch()[b])
+
+    # ---- peak finding (drt1d.py:3753-3947; mapping/curvature.py, mapping/drtmd.py:1023-1106) on the last fitted batch ------------
+    def _extend_var_indices(self, tau):
+        """the two clamp indices of estimate_distribution_cov's extend_var (drt1d.py:3125-3135) on the grid tau"""
+        if isinstance(self._plan, _ffi.PreparedPlan):
+            preps = self._last_prepared[0] if getattr(self, '_last_prepared', None) and \
+                len(self._last_prepared[0]) == self._plan.batch else [self._prep]
+            pr = preps[0]                           # (the members of a prepared batch share their sampling grids)
+            t_left, t_right = pp.get_tau_lim(pr['frequencies'], pr.get('sample_times'), pr.get('nonconsec_step_times'))
+        else:
+            t_left, t_right = 1 / (2 * np.pi * np.max(self.f_fit)), 1 / (2 * np.pi * np.min(self.f_fit))
+        return int(np.argmin(np.abs(tau - t_left))) + 1, int(np.argmin(np.abs(tau - t_right)))
+
+    def _find_peaks_device(self, what, tau, ppd, normalize, sign, method, extend_var, want=None, **opt_kw):
+        plan, scales = self._predict_plan(what)
+        if tau is None:
+            tau = self.get_tau_eval(ppd)
+        tau = np.asarray(tau, dtype=float)
+        search = sign if (self.fit_kwargs['nonneg'] and sign != 0) else 0
+        ext = self._extend_var_indices(tau) if (extend_var and method != 'thresh') else (-1, -1)
+        if ext[0] >= len(tau):
+            raise ValueError('extend_var: the measured tau range ends at the last point of the evaluation grid')
+        opts = _ffi.peak_opts(eval_sign=self._drt_sign(plan, sign), search=search, normalize=1 if normalize else 0, method=method,
+                              ext_left=ext[0], ext_right=ext[1], **opt_kw)
+        # (a ratio to the spectrum's own R_p carries no scale; otherwise a prepared plan's unit-scale rows take theirs on the device)
+        out = plan.find_peaks(np.log(tau), opts, row_scale=None if (normalize or scales is None) else scales, want=want)
+        return tau, out
+
+    def find_peaks_batch(self, tau=None, normalize=True, ppd=10, prominence=None, height=None, sign=1, return_info=False,
+                         method='thresh', prob_thresh=0.25, p_matrix=None, fxx_var_floor=1e-5, extend_var=True, num_peaks=None,
+                         **kw):
+        """DRT.find_peaks (drt1d.py:3753-3947) for every spectrum of the last fitted batch, on the device
+        (hipdrt_plan_find_peaks; models/peaks.py is the rule in numpy) -> a list of B arrays of peak tau; with return_info
+        (peak_tau, tau, peak_indices, peak_info), the last two per-spectrum lists, every info dict with scipy's peak_heights,
+        prominences, left_bases, right_bases and for method 'prob' probs (of all peaks that passed height and prominence, as
+        upstream).  Only the height and prominence conditions of scipy.signal.find_peaks are built.  Spectra whose fit failed
+        (or, for 'prob', whose P is not positive definite) have no peaks.  Last device batch only."""
+        if method not in peaks.METHODS:
+            raise ValueError(f'Invalid method {method}. Options: {list(peaks.METHODS)}')
+        for name in kw:
+            raise NotImplementedError(f'find_peaks: the {name}= argument is not taken (of scipy.signal.find_peaks\' conditions '
+                                      f'only height and prominence are built; coefficients and P are the fit\'s own, on the device)')
+        if p_matrix is not None:
+            raise NotImplementedError('find_peaks: the p_matrix= override is not taken (sigma comes from the fit\'s own P on the device)')
+        # (only what the caller asked for comes down: the kept mask alone without return_info)
+        want = None if return_info else ('keep',)
+        tau, out = self._find_peaks_device('find_peaks', tau, ppd, normalize, sign, method, extend_var, want=want, height=height,
+                                           prominence=prominence, prob_thresh=prob_thresh, num_peaks=num_peaks,
+                                           fxx_var_floor=fxx_var_floor)
+        B = out['keep'].shape[0]
+
+        def per_spectrum(mask):
+            """(column indices of the set entries, cut points) -> np.split gives one array per spectrum"""
+            rows, cols = np.nonzero(mask)
+            return cols, np.searchsorted(rows, np.arange(1, B))
+
+        kept, cut = per_spectrum(out['keep'])
+        peak_tau = np.split(tau[kept], cut)
+        if not return_info:
+            return peak_tau
+        peak_indices = np.split(kept, cut)
+        _, cut = per_spectrum(out['peak_sign'])
+        sel = out['peak_sign'] != 0
+        cols = {'peak_heights': out['heights'][sel], 'prominences': out['prominences'][sel],
+                'left_bases': out['left_bases'][sel].astype(np.intp), 'right_bases': out['right_bases'][sel].astype(np.intp)}
+        if method == 'prob':
+            cols['probs'] = out['probs'][sel]
+        parts = {k: np.split(v, cut) for k, v in cols.items()}
+        peak_info = [{k: parts[k][b] for k in parts} for b in range(B)]
+        return peak_tau, tau, peak_indices, peak_info
+
+    def find_peaks(self, tau=None, x=None, normalize=True, ppd=10, prominence=None, height=None, sign=1, return_info=False,
+                   method='thresh', prob_thresh=0.25, p_matrix=None, fxx_var_floor=1e-5, extend_var=True, num_peaks=None, b=0, **kw):
+        """DRT.find_peaks (drt1d.py:3753-3947) of member ``b`` of the last fit, from the device"""
+        if x is not None:
+            kw = dict(kw, x=x)
+        res = self.find_peaks_batch(tau=tau, normalize=normalize, ppd=ppd, prominence=prominence, height=height, sign=sign,
+                                    return_info=True, method=method, prob_thresh=prob_thresh, p_matrix=p_matrix,
+                                    fxx_var_floor=fxx_var_floor, extend_var=extend_var, num_peaks=num_peaks, **kw)
+        if return_info:
+            return res[0][b], res[1], res[2][b], res[3][b]
+        return res[0][b]
+
+    def _map_probs(self, what, which, tau, extend_var, prominence, height, sign, normalize):
+        return self._find_peaks_device(what, tau, 10, normalize, sign, 'map', extend_var, want=(which,), height=height,
+                                       prominence=prominence, fxx_var_floor=0.0)[1][which]
+
+    def peak_prob_batch(self, tau=None, extend_var=True, prominence=5e-3, height=1e-3, sign=1, normalize=True):
+        """the per-observation core of DRTMD.predict_peak_prob (drtmd.py:1023-1064: curvature.peak_prob_1d times sign(f)) for every
+        spectrum of the last fitted batch -> (B, len(tau)); tau=None is get_tau_eval(10).  No psi filtering, no peak_spread_sigma."""
+        return self._map_probs('peak_prob_batch', 'peak_prob', tau, extend_var, prominence, height, sign, normalize)
+
+    def curv_prob_batch(self, tau=None, extend_var=True, prominence=5e-3, height=1e-3, sign=1, normalize=True):
+        """the per-observation core of DRTMD.predict_curv_prob (drtmd.py:1066-1106) for every spectrum of the last fitted batch ->
+        (B, len(tau)): the probability of f > 0 with negative curvature (or the reverse), signed by f"""
+        return self._map_probs('curv_prob_batch', 'curv_prob', tau, extend_var, prominence, height, sign, normalize)
 
     # ---- Kramers-Kronig test (drt1d.py:1370-1491) ------------------------------------------------------------------------
     def get_fit_frequencies(self):

@@ -1,0 +1,191 @@
+"""Peak finding on rows of the DRT's curvature: the numpy statement of csrc/peaks.hip (as models/kk.py is of csrc/kk.hip).
+
+``find_peaks_1d`` restates scipy.signal.find_peaks(v, height=, prominence=) (_local_maxima_1d, _peak_prominences without wlen);
+on top of it sit DRT.find_peaks (hybdrt/models/drt1d.py:3753-3947), curvature.peak_prob_1d (hybdrt/mapping/curvature.py:12-58)
+and the elementwise formula of DRTMD.predict_curv_prob (hybdrt/mapping/drtmd.py:1100-1104).  Everything acts on rows that are
+already evaluated: fxx (order 2), f (order 0) and their posterior variances.  No scipy: the product layer does not depend on it.
+"""
+import math
+
+import numpy as np
+
+SQRT2 = 2 ** 0.5
+METHODS = ('thresh', 'prob')
+_erfc = np.vectorize(math.erfc, otypes=[float])
+
+
+def find_peaks_1d(v, height=None, prominence=None):
+    """scipy.signal.find_peaks(v, height=height, prominence=prominence) -> (indices, dict(peak_heights, prominences,
+    left_bases, right_bases)).  None switches a condition off (the properties are returned all the same)."""
+    v = np.asarray(v, dtype=float).tolist()          # (plain floats: the loops below are the statement, not numpy's)
+    n = len(v)
+    peaks = []
+    i = 1
+    while i < n - 1:
+        if v[i - 1] < v[i]:
+            a = i + 1
+            while a < n - 1 and v[a] == v[i]:
+                a += 1
+            if v[a] < v[i]:
+                peaks.append((i + a - 1) // 2)
+                i = a
+                continue
+        i += 1
+    idx, hts, proms, lbs, rbs = [], [], [], [], []
+    for p in peaks:
+        if height is not None and not v[p] >= height:
+            continue
+        lmin, lb, i = v[p], p, p
+        while i >= 0 and v[i] <= v[p]:
+            if v[i] < lmin:
+                lmin, lb = v[i], i
+            i -= 1
+        rmin, rb, i = v[p], p, p
+        while i < n and v[i] <= v[p]:
+            if v[i] < rmin:
+                rmin, rb = v[i], i
+            i += 1
+        prom = v[p] - max(lmin, rmin)
+        if prominence is not None and not prom >= prominence:
+            continue
+        idx.append(p); hts.append(v[p]); proms.append(prom); lbs.append(lb); rbs.append(rb)
+    return np.array(idx, dtype=np.intp), dict(peak_heights=np.array(hts, dtype=float), prominences=np.array(proms, dtype=float),
+                                              left_bases=np.array(lbs, dtype=np.intp), right_bases=np.array(rbs, dtype=np.intp))
+
+
+def auto_thresholds(fxx, method, prominence=None, height=None):
+    """drt1d.py:3846-3858 -> (prominence, height); method 'thresh', or 'prob' (also the map forms' defaults)"""
+    if prominence is None:
+        fxx = np.asarray(fxx, dtype=float)
+        prominence = 0.05 * np.std(fxx[~np.isinf(fxx)]) + 5e-3 if method == 'thresh' else 5e-3
+    if height is None:
+        height = 0 if method == 'thresh' else 1e-3
+    return prominence, height
+
+
+def search_peaks(fxx, f, search, height, prominence):
+    """drt1d.py:3886-3913 -> (indices, info, signs).  search = +1 / -1: one pass on -search * fxx; 0: the passes -1 and +1, each
+    keeping the peaks with pass * f[p] > 0, merged in ascending index.  signs: the pass every peak came from."""
+    fxx = np.asarray(fxx, dtype=float)
+    if search != 0:
+        idx, info = find_peaks_1d(-search * fxx, height, prominence)
+        return idx, info, np.full(len(idx), search, dtype=np.intp)
+    f = np.asarray(f, dtype=float)
+    parts = []
+    for s in (-1, 1):
+        idx, info = find_peaks_1d(-s * fxx, height, prominence)
+        pos = s * f[idx] > 0
+        parts.append((idx[pos], {k: w[pos] for k, w in info.items()}, np.full(int(np.sum(pos)), s, dtype=np.intp)))
+    idx = np.concatenate([q[0] for q in parts])
+    order = np.argsort(idx, kind='stable')
+    info = {k: np.concatenate([q[1][k] for q in parts])[order] for k in parts[0][1]}
+    return idx[order], info, np.concatenate([q[2] for q in parts])[order]
+
+
+def extend_var(var, ext_left=-1, ext_right=-1, floor=0.0):
+    """estimate_distribution_cov's extend_var clamp (drt1d.py:3123-3140; -1: off) and var_floor (3142-3146) on one row"""
+    var = np.array(var, dtype=float)
+    if ext_left >= 0:
+        var[:ext_left] = np.maximum(var[:ext_left], var[ext_left])
+    if ext_right >= 0:
+        var[ext_right:] = np.maximum(var[ext_right:], var[ext_right])
+    if floor > 0:
+        var[var < floor] = floor
+    return var
+
+
+def peak_probs(min_prom, sigma):
+    """drt1d.py:3927: 1 - 2 Phi(0; min_prom, sigma) = 1 - erfc(min_prom / (sigma sqrt 2))"""
+    min_prom, sigma = np.asarray(min_prom, dtype=float), np.asarray(sigma, dtype=float)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return 1.0 - _erfc(min_prom / (sigma * SQRT2))
+
+
+def _upper(mu, sigma):
+    """1 - Phi(0; mu, sigma)"""
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return 1.0 - 0.5 * _erfc(np.asarray(mu, dtype=float) / (np.asarray(sigma, dtype=float) * SQRT2))
+
+
+def find_peaks_row(fxx, f=None, var_fxx=None, search=1, method='thresh', prominence=None, height=None, prob_thresh=0.25,
+                   num_peaks=None, fxx_var_floor=1e-5, ext_left=-1, ext_right=-1):
+    """DRT.find_peaks on evaluated rows -> (kept indices, all indices, info, signs, used prominence).  info has scipy's four keys and,
+    for 'prob', 'probs'; like upstream it covers every peak that passed height and prominence (and the f test), kept or not.
+    var_fxx: the curvature's variance before extend_var and the floor ('prob' only)."""
+    if method not in METHODS:
+        raise ValueError(f'Invalid method {method}. Options: {list(METHODS)}')
+    prominence, height = auto_thresholds(fxx, method, prominence, height)
+    idx, info, signs = search_peaks(fxx, f, search, height, prominence)
+    kept = idx
+    if method == 'prob':
+        min_prom = np.minimum(info['prominences'], info['peak_heights'])
+        sigma = extend_var(var_fxx, ext_left, ext_right, fxx_var_floor) ** 0.5
+        prob = peak_probs(min_prom, sigma[idx])
+        if num_peaks is not None and len(prob):
+            prob_thresh = np.sort(prob)[::-1][min(num_peaks - 1, len(prob) - 1)]
+        kept = idx[prob >= prob_thresh]
+        info['probs'] = prob
+    return kept, idx, info, signs, prominence
+
+
+def peak_prob_row(f, fxx, var_f, var_fxx, search=1, height=1e-3, prominence=5e-3):
+    """curvature.peak_prob_1d times sign(f) (drtmd.py:1064) on one row; the variances as they enter the square root"""
+    f = np.asarray(f, dtype=float)
+    idx, probs = _peak_prob_at_peaks(f, fxx, var_f, var_fxx, search, height, prominence)
+    out = np.zeros(len(f))
+    out[idx] = probs
+    return out * np.sign(f)
+
+
+def _peak_prob_at_peaks(f, fxx, var_f, var_fxx, search, height, prominence, found=None):
+    """curvature.py:46-53 -> (indices, min(curvature probability, probability that |f| > 0)); found: search_peaks' result"""
+    f, fxx = np.asarray(f, dtype=float), np.asarray(fxx, dtype=float)
+    idx, info = found if found is not None else search_peaks(fxx, f, search, height, prominence)[:2]
+    min_prom = np.minimum(info['prominences'], info['peak_heights'])
+    curv = _upper(min_prom, np.asarray(var_fxx, dtype=float)[idx] ** 0.5)
+    fpr = _upper(np.sign(f[idx]) * f[idx], np.asarray(var_f, dtype=float)[idx] ** 0.5)
+    return idx, np.minimum(curv, fpr)
+
+
+def curv_prob_row(f, fxx, var_f, var_fxx):
+    """DRTMD.predict_curv_prob's formula (drtmd.py:1097-1104), elementwise"""
+    f, fxx = np.asarray(f, dtype=float), np.asarray(fxx, dtype=float)
+    f_prob = _upper(-np.sign(fxx) * f, np.asarray(var_f, dtype=float) ** 0.5)
+    c_prob = _upper(-np.sign(f) * fxx, np.asarray(var_fxx, dtype=float) ** 0.5)
+    f_prob = 2 * np.maximum(f_prob - 0.5, 0)
+    c_prob = 2 * np.maximum(c_prob - 0.5, 0)
+    return np.minimum(f_prob, c_prob) * np.sign(f)
+
+
+def find_peaks_dense(fxx, f=None, var_fxx=None, var_f=None, search=1, method=0, prominence=None, height=None, prob_thresh=0.25,
+                     num_peaks=0, fxx_var_floor=1e-5, ext_left=-1, ext_right=-1):
+    """What peaks_kernel writes for one row, dense on the evaluation grid: dict(peak_sign, keep, heights, prominences, probs,
+    left_bases, right_bases, count, used_prominence) and for method 2 also peak_prob and curv_prob.  method 0 'thresh', 1 'prob',
+    2 the map probabilities (the thresholds default as for 'prob'; extend_var acts on both variances, the floor on var_fxx)."""
+    fxx = np.asarray(fxx, dtype=float)
+    n = len(fxx)
+    name = 'thresh' if method == 0 else 'prob'
+    out = dict(peak_sign=np.zeros(n, dtype=np.int32), keep=np.zeros(n, dtype=np.int32), heights=np.zeros(n), prominences=np.zeros(n),
+               probs=np.zeros(n), left_bases=np.full(n, -1, dtype=np.int32), right_bases=np.full(n, -1, dtype=np.int32))
+    if method == 2:
+        prominence, height = auto_thresholds(fxx, name, prominence, height)
+        idx, info, signs = search_peaks(fxx, f, search, height, prominence)
+        vxx = extend_var(var_fxx, ext_left, ext_right, fxx_var_floor)
+        vf = extend_var(var_f, ext_left, ext_right, 0.0)
+        idx, info['probs'] = _peak_prob_at_peaks(f, fxx, vf, vxx, search, height, prominence, found=(idx, info))
+        out['peak_prob'] = np.zeros(n)
+        out['peak_prob'][idx] = info['probs']
+        out['peak_prob'] *= np.sign(f)
+        out['curv_prob'] = curv_prob_row(f, fxx, vf, vxx)
+        kept, used = idx, prominence
+    else:
+        kept, idx, info, signs, used = find_peaks_row(fxx, f, var_fxx, search, name, prominence, height, prob_thresh,
+                                                      num_peaks if num_peaks else None, fxx_var_floor, ext_left, ext_right)
+    out['peak_sign'][idx] = signs
+    out['keep'][kept] = 1
+    out['heights'][idx], out['prominences'][idx] = info['peak_heights'], info['prominences']
+    out['left_bases'][idx], out['right_bases'][idx] = info['left_bases'], info['right_bases']
+    if 'probs' in info:
+        out['probs'][idx] = info['probs']
+    out['count'], out['used_prominence'] = len(kept), float(used)
+    return out

@@ -488,6 +488,45 @@ int hipdrt_plan_predict_z(hipdrt_plan* plan, const double* freq, int nf, int inc
  * HIPDRT_E_UNSUPPORTED when r_inf or r_tot is asked for).                                                                       */
 int hipdrt_plan_predict_resistances(hipdrt_plan* plan, double* r_p, double* r_inf, double* r_tot, int abs_norm);
 
+/* ---- peak finding for the fitted batch ---------------------------------------------------------------------------------------
+ * Options of DRT.find_peaks (hybdrt/models/drt1d.py:3753-3947) and of the map's peak probabilities (curvature.peak_prob_1d,
+ * hybdrt/mapping/curvature.py:12-58; DRTMD.predict_curv_prob, hybdrt/mapping/drtmd.py:1097-1104).                              */
+typedef struct {
+    int eval_sign;         /* 1; get_drt_params' sign of the evaluated rows (as hipdrt_plan_predict_drt's sign)                 */
+    int search;            /* 1; +1 / -1: one scipy.signal.find_peaks pass on -search * fxx; 0: the passes -1 and +1, each keeping
+                              the peaks with pass * f[p] > 0 (upstream: search = sign if nonneg and sign != 0, else 0)           */
+    int normalize;         /* 1; 0, 1 (by R_p) or 2 (by absolute R_p), as hipdrt_plan_predict_drt's normalize                   */
+    int method;            /* 0; 0 'thresh', 1 'prob', 2 the map probabilities (peak_prob and curv_prob rows)                   */
+    double height;         /* NaN = automatic: 0 for method 0, else 1e-3                                                        */
+    double prominence;     /* NaN = automatic: 0.05 np.std(fxx) + 5e-3 for method 0, else 5e-3                                  */
+    double prob_thresh;    /* 0.25; method 1 keeps peaks with 1 - erfc(min(prominence, height) / (sigma sqrt 2)) >= prob_thresh  */
+    int num_peaks;         /* 0 = off; method 1: the threshold becomes the min(num_peaks, count)-th largest probability        */
+    double fxx_var_floor;  /* 1e-5; lower bound of the curvature's variance (methods 1 and 2; <= 0: none)                        */
+    int ext_left;          /* -1 = off; extend_var (drt1d.py:3123-3140): var[:ext_left] = max(var[:ext_left], var[ext_left])     */
+    int ext_right;         /* -1 = off; var[ext_right:] = max(var[ext_right:], var[ext_right])                                  */
+} hipdrt_peak_opts;
+void hipdrt_peak_opts_default(hipdrt_peak_opts* o);
+/* Peaks of every spectrum of the fitted batch on the evaluation grid ln_tau_eval[neval], found on the device: the rows fxx (order
+ * 2) and, where the options need it, f (order 0) are evaluated as hipdrt_plan_predict_drt evaluates them (same kernels, same
+ * bits), for methods 1 and 2 sigma^2 = diag(E inv(P) E') scale_b^2 / norm_b^2 comes from ONE factorisation per spectrum fed both
+ * orders' rows, then extend_var's clamp and the floor; one workgroup per spectrum then applies the rule (csrc/peaks.hip;
+ * hipdrt/models/peaks.py is its numpy statement).  row_scale[B] (may be NULL) multiplies every spectrum's coefficient scale when
+ * normalize = 0: a prepared plan runs at unit scale and its caller knows the scales; the thresholds are absolute, so here the
+ * scale cannot be applied afterwards.
+ * out (host; any may be NULL), all dense on the grid: peak_sign [B][neval] 0, or the pass (+1 / -1) of a peak that passed height,
+ * prominence and the f test; keep [B][neval] 0 / 1 (= peak_sign != 0 unless method 1 filters by probability); heights,
+ * prominences, probs [B][neval], zero where there is no peak (probs: method 1 the peak probability, 2 the unsigned peak_prob_1d
+ * value); left_bases, right_bases [B][neval], -1 where there is no peak; count [B] peaks kept; used_prominence [B]; peak_prob,
+ * curv_prob [B][neval] (method 2 only, else left untouched); status [B]: the fit's status, or HIPDRT_PREDICT_NOT_PD where sigma is
+ * needed and P is not positive definite.  A spectrum with a negative status has count 0, empty integer rows and NaN float rows.
+ * HIPDRT_E_INVALID, before any launch, for options out of range and for a neval whose rows do not fit one workgroup's LDS
+ * (neval <= 2048 fits in every mode).  Plain and prepared plans (hipdrt_plan_set_tau_basis first).  The result of a spectrum
+ * depends neither on B nor on its position in the batch.                                                                        */
+int hipdrt_plan_find_peaks(hipdrt_plan* plan, const double* ln_tau_eval, int neval, const hipdrt_peak_opts* opts,
+                           const double* row_scale, int* peak_sign, int* keep, double* heights, double* prominences, double* probs,
+                           int* left_bases, int* right_bases, int* count, double* used_prominence, double* peak_prob,
+                           double* curv_prob, int* status);
+
 /* kernel-time breakdown of the last hipdrt_plan_fit in ms (HIP events on the ctx stream):
  * t[0]=total, t[1]=gram, t[2]=qp, t[3]=hyper, t[4]=setup/other; launches[5] same order                 */
 int hipdrt_plan_timings(hipdrt_plan* plan, float* t, int* launches);

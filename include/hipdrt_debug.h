@@ -5,7 +5,7 @@
  * (in-kernel phase counters of a PROFILE build, occupancy queries).  Every hook takes a context: there is no process-wide
  * switch.  The kernels of the fit loop each have a hook that runs their launcher as it is on host arrays: hipdrt_debug_gram_l2
  * (Gram, q), hipdrt_debug_hyper_step (the hyper-parameter step in its three product forms), hipdrt_debug_kk_stats,
- * hipdrt_debug_apply_rows.
+ * hipdrt_debug_apply_rows, hipdrt_debug_find_peaks.
  */
 #ifndef HIPDRT_DEBUG_H
 #define HIPDRT_DEBUG_H
@@ -135,7 +135,19 @@ int hipdrt_debug_kk_stats(hipdrt_ctx* ctx, int B, int nf, const double* freq, co
 int hipdrt_debug_apply_rows(hipdrt_ctx* ctx, int B, int K, int ldx, int col_offset, const double* X, int r, const double* E,
                             const double* scale, double* out);
 
-/* tools hook (tools/bench_predict.py): kernel time in ms of the last hipdrt_plan_predict_drt / hipdrt_plan_predict_z of a plan of
+/* test hook (tests/test_gpu_peaks.py): peaks_kernel (csrc/peaks.hip) as it is, on host rows -- fxx [B][neval]; f [B][neval]
+ * (needed by search = 0 and method 2, else may be NULL); var_fxx [B][neval] (methods 1, 2) and var_f [B][neval] (method 2): the
+ * variances before extend_var's clamp and the floor, which the kernel applies.  eval_sign and normalize of the options are not
+ * used.  Outputs as hipdrt_plan_find_peaks, any may be NULL.  Non-finite input rows are refused.  Every device output has a
+ * border of marker bytes on either side: HIPDRT_E_NUMERIC when the kernel changed one.  HIPDRT_E_INVALID, and nothing is
+ * launched, when the rows do not fit one workgroup's LDS.                                                                      */
+int hipdrt_debug_find_peaks(hipdrt_ctx* ctx, int B, int neval, const double* fxx, const double* f, const double* var_fxx,
+                            const double* var_f, const hipdrt_peak_opts* opts, int* peak_sign, int* keep, double* heights,
+                            double* prominences, double* probs, int* left_bases, int* right_bases, int* count,
+                            double* used_prominence, double* peak_prob, double* curv_prob);
+
+/* tools hook (tools/bench_predict.py, tools/bench_peaks.py): kernel time in ms of the last hipdrt_plan_predict_drt /
+ * hipdrt_plan_predict_z / hipdrt_plan_find_peaks (ms[0]: the mean rows, ms[1]: all launches, peaks_kernel included) of a plan of
  * this context, by HIP events around its launches (allocations and copies excluded): ms[0] up to the mean (predict_z: the whole
  * prediction), ms[1] with the credible band's factorisation included (equal to ms[0] without a band).                         */
 int hipdrt_debug_last_predict_ms(hipdrt_ctx* ctx, float* ms);
