@@ -83,6 +83,34 @@ class PeakOpts(C.Structure):
                 ("fxx_var_floor", C.c_double), ("ext_left", C.c_int), ("ext_right", C.c_int)]
 
 
+class PeakResolveOpts(C.Structure):
+    """hipdrt_peak_resolve_opts (include/hipdrt.h)"""
+    _fields_ = [("sign", C.c_int), ("max_peaks", C.c_int), ("epsilon_factor", C.c_double), ("max_epsilon", C.c_double),
+                ("min_epsilon", C.c_double), ("epsilon_uniform", C.c_double)]
+
+
+class PeakResolveIn(C.Structure):
+    """hipdrt_peak_resolve_in (include/hipdrt.h)"""
+    _fields_ = [("source", C.c_int), ("peak_opts", C.POINTER(PeakOpts)), ("peak_indices", _ip), ("win_start", _ip), ("win_end", _ip),
+                ("nwin", C.c_int), ("ln_tau_find", _dp), ("nfind", C.c_int), ("ln_tau_out", _dp), ("nout", C.c_int),
+                ("row_scale", _dp)]
+
+
+class PeakResolveOut(C.Structure):
+    """hipdrt_peak_resolve_out (include/hipdrt.h)"""
+    _fields_ = [("count", _ip), ("peak_index", _ip), ("trough_index", _ip), ("eps_l", _dp), ("eps_r", _dp), ("r_peaks", _dp),
+                ("r_coef", _dp), ("x_peaks", _dp), ("peak_gammas", _dp), ("status", _ip)]
+
+
+class DebugPeakResolveArgs(C.Structure):
+    """hipdrt_debug_peak_resolve_args (include/hipdrt_debug.h)"""
+    _fields_ = [("B", C.c_int), ("nfind", C.c_int), ("nb", C.c_int), ("nout", C.c_int), ("copies", C.c_int), ("source", C.c_int),
+                ("nwin", C.c_int), ("f", _dp), ("fxx", _dp), ("keep", _ip), ("indices", _ip), ("win_start", _ip), ("win_end", _ip),
+                ("x", _dp), ("ln_tau_find", _dp), ("ln_basis", _dp), ("ln_tau_out", _dp), ("basis_eps", C.c_double),
+                ("fit_status", _ip), ("opts", C.POINTER(PeakResolveOpts)), ("out", PeakResolveOut),
+                ("lds_bytes", C.POINTER(C.c_longlong))]
+
+
 class DebugGramArgs(C.Structure):
     """hipdrt_debug_gram_args (include/hipdrt_debug.h)"""
     _fields_ = [
@@ -160,6 +188,10 @@ SIGNATURES = {
                                _ip],
     "hipdrt_debug_find_peaks": [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.POINTER(PeakOpts), _ip, _ip, _dp, _dp, _dp, _ip, _ip,
                                 _ip, _dp, _dp, _dp],
+    "hipdrt_peak_resolve_opts_default": [C.POINTER(PeakResolveOpts)],
+    "hipdrt_plan_resolve_peaks": [_vp, C.POINTER(PeakResolveIn), C.POINTER(PeakResolveOpts), C.POINTER(PeakResolveOut)],
+    "hipdrt_plan_integrate_drt": [_vp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _ip, _ip, C.c_int, _dp, _ip],
+    "hipdrt_debug_peak_resolve": [_vp, C.POINTER(DebugPeakResolveArgs)],
     "hipdrt_debug_last_predict_ms": [_vp, C.POINTER(C.c_float)],
     "hipdrt_debug_apply_rows": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp],
     "hipdrt_comm_unique_id": [C.c_char_p],
@@ -213,7 +245,8 @@ SIGNATURES = {
                              _dp, _dp, _dp, _dp, _ip, _ip],
 }
 _RESTYPES = {"hipdrt_last_error": C.c_char_p, "hipdrt_stream": C.c_void_p, "hipdrt_default_fit_opts": None,
-             "hipdrt_default_kk_opts": None, "hipdrt_peak_opts_default": None}
+             "hipdrt_default_kk_opts": None, "hipdrt_peak_opts_default": None,
+             "hipdrt_peak_resolve_opts_default": None}
 
 _lib = None
 _lock = threading.Lock()
@@ -314,6 +347,51 @@ def peak_opts(eval_sign=1, search=1, normalize=1, method='thresh', height=None, 
     o.prob_thresh, o.num_peaks, o.fxx_var_floor = float(prob_thresh), int(num_peaks or 0), float(fxx_var_floor)
     o.ext_left, o.ext_right = int(ext_left), int(ext_right)
     return o
+
+
+PEAKS_OVERFLOW, PEAKS_UNORDERED = -4, -5            # per-spectrum statuses of hipdrt_plan_resolve_peaks
+PEAKS_FROM_FIND, PEAKS_FROM_INDICES, PEAKS_FROM_WINDOWS = 0, 1, 2
+RESOLVE_OUTPUTS = ("count", "peak_index", "trough_index", "eps_l", "eps_r", "r_peaks", "r_coef", "x_peaks", "peak_gammas", "status")
+
+
+def peak_resolve_opts(sign=1, max_peaks=16, epsilon_factor=1.25, max_epsilon=1.25, min_epsilon=None,
+                      epsilon_uniform=None) -> PeakResolveOpts:
+    """hipdrt_peak_resolve_opts from the keywords of DRT.estimate_peak_coef (None <-> NaN for min_epsilon and epsilon_uniform)"""
+    o = PeakResolveOpts()
+    load_library().hipdrt_peak_resolve_opts_default(C.byref(o))
+    o.sign, o.max_peaks = int(sign), int(max_peaks)
+    o.epsilon_factor, o.max_epsilon = float(epsilon_factor), float(max_epsilon)
+    o.min_epsilon = float('nan') if min_epsilon is None else float(min_epsilon)
+    o.epsilon_uniform = float('nan') if epsilon_uniform is None else float(epsilon_uniform)
+    return o
+
+
+def _resolve_outputs(B, mp, nb, nout, want=None):
+    """host arrays of the resolve entry points, poisoned so that anything the kernel leaves unwritten shows (-77 / 7e77: NaN
+    is a legitimate padding value); want: the names to allocate (None: all) -- count and status always come"""
+    shapes = dict(count=(B,), status=(B,), peak_index=(B, mp), trough_index=(B, mp), eps_l=(B, mp), eps_r=(B, mp),
+                  r_peaks=(B, mp), r_coef=(B, mp), x_peaks=(B, mp, nb), peak_gammas=(B, mp, nout))
+    out = {}
+    for k, shape in shapes.items():
+        if want is not None and k not in want and k not in ("count", "status"):
+            continue
+        if nout == 0 and k in ("r_peaks", "peak_gammas"):
+            continue
+        integer = k in ("count", "status", "peak_index", "trough_index")
+        out[k] = np.full(shape, -77, dtype=np.int32) if integer else np.full(shape, 7e77)
+    return out
+
+
+def _resolve_out_struct(out):
+    u = PeakResolveOut()
+    for k in RESOLVE_OUTPUTS:
+        a = out.get(k)
+        setattr(u, k, None if a is None else (_pi(a) if a.dtype == np.int32 else _p(a)))
+    return u
+
+
+def _i32(a):
+    return np.ascontiguousarray(a, dtype=np.int32)
 
 
 _PEAK_INT = ("peak_sign", "keep", "left_bases", "right_bases")
@@ -810,6 +888,51 @@ class Context:
         _check(self._lib.hipdrt_debug_find_peaks(self._h, B, n, *[_p(r) for r in rows], C.byref(opts), *_peak_out_args(out)))
         return out
 
+    def debug_peak_resolve(self, f, fxx, x, ln_tau_find, ln_basis, ln_tau_out=None, basis_eps=1.0, keep=None, indices=None,
+                           windows=None, copies=1, fit_status=None, opts: PeakResolveOpts | None = None, want=None):
+        """tests: peak_resolve_kernel on host arrays (hipdrt_debug_peak_resolve, include/hipdrt_debug.h): rows f, fxx (B, nfind),
+        x (B, copies * nb) in data units, the peak source keep (B, nfind) / indices (B, max_peaks) / windows (start, end) ->
+        dict of the padded outputs of hipdrt_plan_resolve_peaks plus lds_bytes.  Raises when the kernel wrote outside an output."""
+        f, fxx, x = np.atleast_2d(_f64(f)), np.atleast_2d(_f64(fxx)), np.atleast_2d(_f64(x))
+        lt, lb = _f64(ln_tau_find).ravel(), _f64(ln_basis).ravel()
+        lo = None if ln_tau_out is None else _f64(ln_tau_out).ravel()
+        B, nfind = f.shape
+        nb, nout = lb.size, 0 if lo is None else lo.size
+        if fxx.shape != f.shape or lt.size != nfind or x.shape != (B, copies * nb):
+            raise ValueError("shapes: f, fxx (B, nfind); x (B, copies * nb)")
+        opts = opts if opts is not None else peak_resolve_opts()
+        a = DebugPeakResolveArgs()
+        a.B, a.nfind, a.nb, a.nout, a.copies = B, nfind, nb, nout, int(copies)
+        keepers = [f, fxx, x, lt, lb, lo]
+        a.f, a.fxx, a.x, a.ln_tau_find, a.ln_basis, a.ln_tau_out, a.basis_eps = _p(f), _p(fxx), _p(x), _p(lt), _p(lb), _p(lo), float(basis_eps)
+        if keep is not None:
+            k = np.atleast_2d(_i32(keep)); keepers.append(k)
+            if k.shape != f.shape:
+                raise ValueError("keep must have the shape of f")
+            a.source, a.keep = PEAKS_FROM_FIND, _pi(k)
+        elif indices is not None:
+            k = np.atleast_2d(_i32(indices)); keepers.append(k)
+            if k.shape != (B, opts.max_peaks):
+                raise ValueError("indices must have shape (B, max_peaks)")
+            a.source, a.indices = PEAKS_FROM_INDICES, _pi(k)
+        else:
+            ws, we = _i32(windows[0]).ravel(), _i32(windows[1]).ravel(); keepers += [ws, we]
+            a.source, a.win_start, a.win_end, a.nwin = PEAKS_FROM_WINDOWS, _pi(ws), _pi(we), ws.size
+        if fit_status is not None:
+            fs = _i32(fit_status); keepers.append(fs)
+            a.fit_status = _pi(fs)
+        a.opts = C.pointer(opts)
+        out = _resolve_outputs(B, opts.max_peaks, nb, nout, want)
+        a.out = _resolve_out_struct(out)
+        lds = C.c_longlong(-1)
+        a.lds_bytes = C.pointer(lds)
+        try:
+            _check(self._lib.hipdrt_debug_peak_resolve(self._h, C.byref(a)))
+        finally:
+            self.last_peak_resolve_lds = int(lds.value)
+        out["lds_bytes"] = int(lds.value)
+        return out
+
     def debug_last_predict_ms(self):
         """tools: kernel time in ms of the last predict_drt / predict_z of a plan of this context -> (mean or impedance, with band)"""
         ms = (C.c_float * 2)()
@@ -1003,6 +1126,11 @@ class Plan:
         """prepared plans: the tau basis the DRT block stands on (hipdrt_plan_set_tau_basis), needed by predict_drt"""
         ln_tau = _f64(ln_basis_tau)
         _check(self._lib.hipdrt_plan_set_tau_basis(self._h, _p(ln_tau), ln_tau.size, float(epsilon)))
+        self._basis_nb = ln_tau.size
+
+    def basis_size(self):
+        """points of the tau basis the DRT block stands on (a prepared plan: what set_tau_basis gave)"""
+        return getattr(self, '_basis_nb', None) or self.ntau
 
     def predict_drt(self, ln_tau_eval, order=0, sign=1, normalize=0, n_sigma=None):
         """hipdrt_plan_predict_drt for the fitted batch: mu (B, neval) = scale_b E x_b on the device; normalize 0 / 1 (by R_p) /
@@ -1032,6 +1160,53 @@ class Plan:
         _check(self._lib.hipdrt_plan_find_peaks(self._h, _p(ev), ev.size, C.byref(opts), _p(rs), *_peak_out_args(out),
                                                 _pi(out["status"])))
         return out
+
+    def resolve_peaks(self, ln_tau_find, ln_tau_out=None, opts: PeakResolveOpts | None = None, find_opts: PeakOpts | None = None,
+                      peak_indices=None, windows=None, row_scale=None, want=None):
+        """hipdrt_plan_resolve_peaks for the fitted batch -> dict of the padded outputs count (B,), status (B,), peak_index,
+        trough_index, eps_l, eps_r, r_peaks, r_coef (B, max_peaks), x_peaks (B, max_peaks, nb), peak_gammas (B, max_peaks,
+        nout); absent slots hold -1 / NaN.  Peak source: peak_indices (B, max_peaks) -1 padded, or windows = (start, end), else
+        find_peaks with find_opts.  want: the names to form and download (None: all)."""
+        opts = opts if opts is not None else peak_resolve_opts()
+        lt = _f64(ln_tau_find).ravel()
+        lo = None if ln_tau_out is None else _f64(ln_tau_out).ravel()
+        nb = self.basis_size()
+        i = PeakResolveIn()
+        keepers = [lt, lo]
+        i.ln_tau_find, i.nfind, i.ln_tau_out, i.nout = _p(lt), lt.size, _p(lo), 0 if lo is None else lo.size
+        if peak_indices is not None:
+            k = _i32(peak_indices); keepers.append(k)
+            if k.shape != (self.B, opts.max_peaks):
+                raise ValueError("peak_indices must have shape (B, max_peaks)")
+            i.source, i.peak_indices = PEAKS_FROM_INDICES, _pi(k)
+        elif windows is not None:
+            ws, we = _i32(windows[0]).ravel(), _i32(windows[1]).ravel(); keepers += [ws, we]
+            i.source, i.win_start, i.win_end, i.nwin = PEAKS_FROM_WINDOWS, _pi(ws), _pi(we), ws.size
+        else:
+            po = find_opts if find_opts is not None else peak_opts()
+            keepers.append(po)
+            i.source, i.peak_opts = PEAKS_FROM_FIND, C.pointer(po)
+        rs = None if row_scale is None else _f64(row_scale)
+        if rs is not None and rs.shape != (self.B,):
+            raise ValueError("row_scale must have shape (B,)")
+        i.row_scale = _p(rs)
+        out = _resolve_outputs(self.B, opts.max_peaks, nb, i.nout, want)
+        u = _resolve_out_struct(out)
+        _check(self._lib.hipdrt_plan_resolve_peaks(self._h, C.byref(i), C.byref(opts), C.byref(u)))
+        return out
+
+    def integrate_drt(self, ln_tau_eval, windows, order=0, sign=1, normalize=0, row_scale=None):
+        """hipdrt_plan_integrate_drt: the trapezoid of predict_drt's row over every window (start, end) -> ((B, nwin), status)"""
+        ev = _f64(ln_tau_eval).ravel()
+        ws, we = _i32(windows[0]).ravel(), _i32(windows[1]).ravel()
+        rs = None if row_scale is None else _f64(row_scale)
+        if rs is not None and rs.shape != (self.B,):
+            raise ValueError("row_scale must have shape (B,)")
+        out = np.empty((self.B, ws.size))
+        status = np.empty(self.B, dtype=np.int32)
+        _check(self._lib.hipdrt_plan_integrate_drt(self._h, _p(ev), ev.size, int(order), int(sign), int(normalize), _p(rs), _pi(ws),
+                                                   _pi(we), ws.size, _p(out), _pi(status)))
+        return out, status
 
     def predict_z(self, frequencies, include_drt=True, include_ohmic=True, include_inductance=True):
         """hipdrt_plan_predict_z: complex (B, nf) impedance of the fitted batch at any frequencies, and the status (B,)"""

@@ -309,6 +309,40 @@ size_t peaks_lds_bytes(int neval, int method, int need_f, int num_peaks);    // 
 int launch_peaks(hipStream_t s, PeakArgs a, int B);
 void launch_scale_mul(hipStream_t s, int B, const double* x, const double* y, double* out);
 
+// peak_resolve.hip: per-peak coefficients, distributions and resistances, one workgroup per spectrum (all pointers device memory;
+// an output may be null)
+struct PeakResolveArgs {
+    int nfind, nb, nout, max_peaks, ld;  // max_peaks and ld (leading dimension of the LDS operand) are set by the launcher
+    int source;                          // 0: the keep rows of peaks_kernel, 1: index rows, 2: one peak per window (argmin fxx)
+    int nwin, copies;                    // copies of the basis in the DRT block (1, or 2: x+ | x-)
+    hipdrt_peak_resolve_opts o;
+    const double *f, *fxx;               // [B][nfind] unnormalised rows on the find grid
+    const int* keep;                     // [B][nfind]
+    const int* indices;                  // [B][max_peaks], -1 padded, strictly increasing
+    const int *win_start, *win_end;      // [nwin] windows [start, end) of the find grid (end may pass it by one)
+    const double* X;                     // [B][ldx] the unknowns; the DRT block starts at col_offset
+    long long ldx;
+    int col_offset;
+    const double* cs;                    // [B] coefficient scale, or null (1)
+    const double *lt, *lb, *lto;         // ln of the find grid [nfind], of the basis grid [nb], of the output grid [nout]
+    const double* E0;                    // [nout][nb] order-0 evaluation matrix of the output grid
+    double basis_area;                   // sqrt(pi) / epsilon of the basis
+    const int* fit_status;               // [B] or null
+    int *count, *status;                 // [B]
+    int *peak_index, *trough_index;      // [B][max_peaks]
+    double *eps_l, *eps_r, *r_peaks, *r_coef;   // [B][max_peaks]
+    double* x_peaks;                     // [B][max_peaks][nb]
+    double* peak_gammas;                 // [B][max_peaks][nout]
+};
+int peak_resolve_check_opts(const hipdrt_peak_resolve_opts& o);
+int peak_resolve_ld(int nb);
+size_t peak_resolve_lds_bytes(int nfind, int nb, int nout, int max_peaks);
+// HIPDRT_E_INVALID, before any launch, when an option is out of range, an input the source needs is missing, or LDS cannot hold the shape
+int launch_peak_resolve(hipStream_t s, PeakResolveArgs a, int B);
+// out[b][k] = trapezoid of mu[b][start_k : end_k] over ln_tau (windows clipped to the grid)
+void launch_window_trapz(hipStream_t s, int B, int n, int nwin, const double* mu, const double* lt, const int* win_start,
+                         const int* win_end, double* out);
+
 // qp.hip
 struct QpArgs {
     int B, n;

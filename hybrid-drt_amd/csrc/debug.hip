@@ -407,6 +407,75 @@ int hipdrt_debug_find_peaks(hipdrt_ctx* ctx, int B, int neval, const double* fxx
     return HIPDRT_OK;
 } HIPDRT_CATCH
 
+// test hook (include/hipdrt_debug.h): peak_resolve_kernel as it is, on host arrays.  Every output sits between two borders of marker bytes.
+int hipdrt_debug_peak_resolve(hipdrt_ctx* ctx, const hipdrt_debug_peak_resolve_args* q) try {
+    HIPDRT_REQUIRE(ctx && q && q->f && q->fxx && q->x && q->ln_tau_find && q->ln_basis, "NULL pointer");
+    const int B = q->B, nfind = q->nfind, nb = q->nb, nout = q->nout;
+    HIPDRT_REQUIRE(B >= 1 && B <= 65535 && nfind >= 1 && nfind <= (1 << 20) && nb >= 1 && nb <= (1 << 20) && nout >= 0 && nout <= (1 << 20),
+                   "1 <= B <= 65535, 1 <= nfind, nb <= 2^20, 0 <= nout <= 2^20");
+    HIPDRT_REQUIRE(q->copies == 1 || q->copies == 2, "copies must be 1 or 2");
+    HIPDRT_REQUIRE(nout == 0 || (q->ln_tau_out && q->basis_eps > 0.0 && std::isfinite(q->basis_eps)), "an output grid needs ln_tau_out and basis_eps > 0");
+    hipdrt_peak_resolve_opts o;
+    if (q->opts) o = *q->opts; else hipdrt_peak_resolve_opts_default(&o);
+    TRY(peak_resolve_check_opts(o));
+    const int mp = o.max_peaks;
+    HIPDRT_REQUIRE(q->copies == 2 || o.sign == 1, "sign must be 1 unless the DRT block holds a positive and a negative copy");
+    const size_t lds = peak_resolve_lds_bytes(nfind, nb, nout, mp);
+    if (q->lds_bytes) *q->lds_bytes = (long long)lds;
+    HIPDRT_REQUIRE(q->source != 0 || q->keep, "source 0 needs the keep rows");
+    TRY(peak_resolve_check_source(q->source, q->indices, B, mp, q->win_start, q->win_end, q->nwin, nfind));
+    const size_t bn = (size_t)B * nfind, bx = (size_t)B * q->copies * nb;
+    for (size_t i = 0; i < bn; ++i) HIPDRT_REQUIRE(std::isfinite(q->f[i]) && std::isfinite(q->fxx[i]), "non-finite input row");
+    for (size_t i = 0; i < bx; ++i) HIPDRT_REQUIRE(std::isfinite(q->x[i]), "non-finite coefficients");
+    for (int i = 0; i < nfind; ++i) HIPDRT_REQUIRE(std::isfinite(q->ln_tau_find[i]), "non-finite find grid");
+    for (int i = 0; i < nb; ++i) HIPDRT_REQUIRE(std::isfinite(q->ln_basis[i]), "non-finite basis grid");
+    for (int i = 0; i < nout; ++i) HIPDRT_REQUIRE(std::isfinite(q->ln_tau_out[i]), "non-finite output grid");
+    hipStream_t st; TRY(enter(ctx, &st));
+    DevBuf df, dfxx, dkeep, didx, dws, dwe, dx, dlt, dlb, dlo, dE0, dfs;
+    TRY(upload(df, q->f, bn * sizeof(double), st)); TRY(upload(dfxx, q->fxx, bn * sizeof(double), st));
+    TRY(upload(dx, q->x, bx * sizeof(double), st));
+    TRY(upload(dlt, q->ln_tau_find, (size_t)nfind * sizeof(double), st)); TRY(upload(dlb, q->ln_basis, (size_t)nb * sizeof(double), st));
+    PeakResolveArgs a{};
+    a.nfind = nfind; a.nb = nb; a.nout = nout; a.source = q->source; a.nwin = q->nwin; a.copies = q->copies; a.o = o;
+    a.f = df.d(); a.fxx = dfxx.d(); a.X = dx.d(); a.ldx = (long long)q->copies * nb; a.col_offset = 0; a.cs = nullptr;
+    a.lt = dlt.d(); a.lb = dlb.d();
+    if (q->source == 0) { TRY(upload(dkeep, q->keep, bn * sizeof(int), st)); a.keep = dkeep.i(); }
+    if (q->source == 1) { TRY(upload(didx, q->indices, (size_t)B * mp * sizeof(int), st)); a.indices = didx.i(); }
+    if (q->source == 2) {
+        TRY(upload(dws, q->win_start, (size_t)q->nwin * sizeof(int), st)); TRY(upload(dwe, q->win_end, (size_t)q->nwin * sizeof(int), st));
+        a.win_start = dws.i(); a.win_end = dwe.i();
+    }
+    if (q->fit_status) { TRY(upload(dfs, q->fit_status, (size_t)B * sizeof(int), st)); a.fit_status = dfs.i(); }
+    if (nout > 0) {
+        TRY(upload(dlo, q->ln_tau_out, (size_t)nout * sizeof(double), st));
+        HIPDRT_CHECK(dE0.alloc((size_t)nout * nb * sizeof(double)));
+        TRY(func_eval_dev(st, dlb.d(), nb, dlo.d(), nout, q->basis_eps, 0, 1.0, dE0.d(), nb));
+        a.E0 = dE0.d(); a.lto = dlo.d();
+        a.basis_area = 1.7724538509055159 / q->basis_eps;
+    } else {
+        a.basis_area = q->basis_eps > 0.0 ? 1.7724538509055159 / q->basis_eps : 1.0;
+    }
+    Guarded g[10];
+    const size_t D = sizeof(double), I = sizeof(int), bm = (size_t)B * mp;
+    const hipdrt_peak_resolve_out& u = q->out;
+    if (u.count) { TRY(g[0].up("count", u.count, (size_t)B * I, st)); a.count = g[0].di(); }
+    if (u.status) { TRY(g[1].up("status", u.status, (size_t)B * I, st)); a.status = g[1].di(); }
+    if (u.peak_index) { TRY(g[2].up("peak_index", u.peak_index, bm * I, st)); a.peak_index = g[2].di(); }
+    if (u.trough_index) { TRY(g[3].up("trough_index", u.trough_index, bm * I, st)); a.trough_index = g[3].di(); }
+    if (u.eps_l) { TRY(g[4].up("eps_l", u.eps_l, bm * D, st)); a.eps_l = g[4].dd(); }
+    if (u.eps_r) { TRY(g[5].up("eps_r", u.eps_r, bm * D, st)); a.eps_r = g[5].dd(); }
+    if (u.r_peaks) { TRY(g[6].up("r_peaks", u.r_peaks, bm * D, st)); a.r_peaks = g[6].dd(); }
+    if (u.r_coef) { TRY(g[7].up("r_coef", u.r_coef, bm * D, st)); a.r_coef = g[7].dd(); }
+    if (u.x_peaks) { TRY(g[8].up("x_peaks", u.x_peaks, bm * nb * D, st)); a.x_peaks = g[8].dd(); }
+    if (u.peak_gammas && nout > 0) { TRY(g[9].up("peak_gammas", u.peak_gammas, bm * nout * D, st)); a.peak_gammas = g[9].dd(); }
+    TRY(launch_peak_resolve(st, a, B));
+    LAUNCH_OK();
+    for (Guarded& w : g) if (w.buf.p) TRY(w.fetch(st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    for (Guarded& w : g) if (w.buf.p) TRY(w.check());
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
 // tools hook: kernel time of the last hipdrt_plan_predict_drt or hipdrt_plan_predict_z on this context
 int hipdrt_debug_last_predict_ms(hipdrt_ctx* ctx, float* ms) try {
     HIPDRT_REQUIRE(ctx && ms, "NULL pointer");

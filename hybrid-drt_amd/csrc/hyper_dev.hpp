@@ -1,5 +1,5 @@
-// Device helpers shared by the one-workgroup-per-spectrum kernels (hyper.hip, kk.hip, peaks.hip): 512-thread workgroups (peaks.hip:
-// 256, through the template argument), wavefront and block reductions, the bitonic sort, the row-slab matrix-vector product, and
+// Device helpers shared by the one-workgroup-per-spectrum kernels (hyper.hip, kk.hip, peaks.hip, peak_resolve.hip): 512-thread workgroups (peaks.hip,
+// peak_resolve.hip: 256, through the template argument), wavefront and block reductions, the bitonic sort, the row-slab matrix-vector product, and
 // the dynamic-LDS limit of their launchers.
 #pragma once
 #include "common.hpp"

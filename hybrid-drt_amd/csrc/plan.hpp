@@ -187,6 +187,11 @@ GramL2 plan_l2(const hipdrt_plan* p, double l2_lambda_0, const double* derivativ
 
 // ---- Kramers-Kronig screening: plan_post.hip (hipdrt_plan_kk_screen) and its stage-B test hook in debug.hip --------------------
 int kk_check_opts(const hipdrt_kk_opts& o);
+// ---- per-peak resolution: plan_post.hip (hipdrt_plan_resolve_peaks) and its test hook in debug.hip -------------------------------
+// host checks of the caller's peak source: index rows [B][max_peaks] in range, strictly increasing, -1 only as padding at the
+// end; windows 0 <= start < min(end, nfind), starts and ends ascending
+int peak_resolve_check_source(int source, const int* indices, int B, int max_peaks, const int* win_start, const int* win_end,
+                              int nwin, int nfind);
 }  // namespace hipdrt
 
 // device outputs of one kk launch for B spectra of nf frequencies, and their way back to the host

@@ -1,5 +1,6 @@
 // What reads a finished fit of a plan (include/hipdrt.h): log-likelihood terms, the posterior covariance and variance,
-// Kramers-Kronig screening (csrc/kk.hip) and model evaluation (csrc/predict.hip).
+// Kramers-Kronig screening (csrc/kk.hip), model evaluation (csrc/predict.hip), peak finding (csrc/peaks.hip) and per-peak
+// resolution (csrc/peak_resolve.hip).
 #include <cmath>
 #include <cstring>
 
@@ -13,6 +14,35 @@ int kk_check_opts(const hipdrt_kk_opts& o) {
     HIPDRT_REQUIRE(o.n_std > 0.0 && std::isfinite(o.n_std), "n_std > 0");
     HIPDRT_REQUIRE(o.max_num_outliers >= 0, "max_num_outliers >= 0");
     HIPDRT_REQUIRE(o.outlier_weight > 0.0 && std::isfinite(o.outlier_weight), "outlier_weight > 0");
+    return HIPDRT_OK;
+}
+
+int peak_resolve_check_source(int source, const int* indices, int B, int max_peaks, const int* win_start, const int* win_end,
+                              int nwin, int nfind) {
+    HIPDRT_REQUIRE(source >= 0 && source <= 2, "source must be 0 (find_peaks), 1 (indices) or 2 (windows)");
+    if (source == 1) {
+        HIPDRT_REQUIRE(indices, "source 1 needs peak_indices");
+        for (int b = 0; b < B; ++b) {
+            int prev = -1;
+            bool ended = false;
+            for (int i = 0; i < max_peaks; ++i) {
+                const int v = indices[(size_t)b * max_peaks + i];
+                if (v == -1) { ended = true; continue; }
+                HIPDRT_REQUIRE(!ended, "peak_indices: -1 only as padding at the end of a row");
+                HIPDRT_REQUIRE(v >= 0 && v < nfind, "peak_indices out of range of the find grid");
+                HIPDRT_REQUIRE(v > prev, "peak_indices must be strictly increasing within a spectrum");
+                prev = v;
+            }
+        }
+    } else if (source == 2) {
+        HIPDRT_REQUIRE(win_start && win_end, "source 2 needs win_start and win_end");
+        HIPDRT_REQUIRE(nwin >= 1 && nwin <= max_peaks, "1 <= nwin <= max_peaks");
+        for (int k = 0; k < nwin; ++k) {
+            HIPDRT_REQUIRE(win_start[k] >= 0 && win_start[k] < nfind && win_end[k] > win_start[k] && win_end[k] <= nfind + 1,
+                           "windows: 0 <= start < end <= nfind + 1, start < nfind");
+            HIPDRT_REQUIRE(k == 0 || (win_start[k] >= win_start[k - 1] && win_end[k] >= win_end[k - 1]), "windows must be ascending");
+        }
+    }
     return HIPDRT_OK;
 }
 }  // namespace hipdrt
@@ -472,6 +502,176 @@ int hipdrt_plan_find_peaks(hipdrt_plan* p, const double* ln_tau_eval, int neval,
     HIPDRT_CHECK(hipStreamSynchronize(st));
     if (status)
         for (int b = 0; b < B; ++b) status[b] = (hs[b] >= 0 && need_var && hv[b] != 0) ? HIPDRT_PREDICT_NOT_PD : hs[b];
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+// ---- per-peak coefficients, distributions and resistances (csrc/peak_resolve.hip) ----------------------------------------------
+void hipdrt_peak_resolve_opts_default(hipdrt_peak_resolve_opts* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->sign = 1; o->max_peaks = 16; o->epsilon_factor = 1.25; o->max_epsilon = 1.25;
+    o->min_epsilon = __builtin_nan(""); o->epsilon_uniform = __builtin_nan("");
+}
+
+int hipdrt_plan_resolve_peaks(hipdrt_plan* p, const hipdrt_peak_resolve_in* in, const hipdrt_peak_resolve_opts* opts,
+                              hipdrt_peak_resolve_out* out) try {
+    HIPDRT_REQUIRE(p && in && out && in->ln_tau_find, "NULL pointer");
+    PredictBasis pb;
+    TRY(predict_basis(p, pb));
+    hipdrt_peak_resolve_opts o;
+    if (opts) o = *opts; else hipdrt_peak_resolve_opts_default(&o);
+    // every check comes before the first launch
+    TRY(peak_resolve_check_opts(o));
+    const int B = p->B, n = p->n, ns = p->ns, width = n - ns, nfind = in->nfind, mp = o.max_peaks;
+    const bool want_out = out->r_peaks || out->peak_gammas;
+    const int nout = want_out ? in->nout : 0;
+    HIPDRT_REQUIRE(nfind >= 1, "nfind >= 1");
+    HIPDRT_REQUIRE(!want_out || (in->ln_tau_out && in->nout >= 1), "r_peaks and peak_gammas need the output grid");
+    HIPDRT_REQUIRE(o.sign == 1 || (pb.copies == 2 && (o.sign == 0 || o.sign == -1)),
+                   "sign must be 1, or 1, -1 or 0 when the DRT block holds a positive and a negative copy");
+    TRY(peak_resolve_check_source(in->source, in->peak_indices, B, mp, in->win_start, in->win_end, in->nwin, nfind));
+    const double* row_scale = in->row_scale;
+    if (row_scale) for (int b = 0; b < B; ++b) HIPDRT_REQUIRE(row_scale[b] > 0.0 && std::isfinite(row_scale[b]), "row_scale must be positive and finite");
+    hipdrt_peak_opts po;
+    if (in->peak_opts) po = *in->peak_opts; else hipdrt_peak_opts_default(&po);
+    const bool find = in->source == HIPDRT_PEAKS_FROM_FIND;
+    bool need_var = false;
+    if (find) {
+        TRY(peak_check_opts(po, nfind));
+        HIPDRT_REQUIRE(po.eval_sign == o.sign, "peak_opts.eval_sign must equal opts.sign (estimate_peak_coef hands its sign to find_peaks)");
+        HIPDRT_REQUIRE(po.method == 0 || po.method == 1, "peak_opts.method must be 0 (thresh) or 1 (prob)");
+        HIPDRT_REQUIRE(po.normalize >= 0 && po.normalize <= 2, "normalize must be 0, 1 (by R_p) or 2 (by absolute R_p)");
+        HIPDRT_REQUIRE(peaks_lds_bytes(nfind, po.method, 1, po.num_peaks) <= 160 * 1024 - 256,
+                       "find_peaks: nfind too large for one workgroup's LDS");
+        need_var = po.method >= 1;
+    }
+    {
+        const size_t lds = peak_resolve_lds_bytes(nfind, pb.nb, nout, mp);
+        if (lds > 160 * 1024 - 256) {
+            set_error("invalid argument: resolve_peaks: " + std::to_string(lds) + " bytes of LDS needed (nfind, nb, nout, max_peaks), " +
+                      std::to_string(160 * 1024 - 256) + " available");
+            return HIPDRT_E_INVALID;
+        }
+    }
+    hipStream_t st; TRY(enter(p->ctx, &st));
+    const int orders[2] = {2, 0};
+    const int normalize = find ? po.normalize : 0;
+    DevBuf dev, dout_grid, dE0, dkeep, dmu2, didx, dws, dwe;
+    DrtRows R;
+    TRY(upload(dev, in->ln_tau_find, (size_t)nfind * sizeof(double), st));
+    HIPDRT_CHECK(R.dE.alloc((size_t)2 * nfind * width * sizeof(double)));
+    HIPDRT_CHECK(R.dmu.alloc((size_t)2 * B * nfind * sizeof(double)));
+    PeakResolveArgs a{};
+    a.nfind = nfind; a.nb = pb.nb; a.nout = nout; a.source = in->source; a.nwin = in->nwin; a.copies = pb.copies; a.o = o;
+    if (in->source == HIPDRT_PEAKS_FROM_INDICES) { TRY(upload(didx, in->peak_indices, (size_t)B * mp * sizeof(int), st)); a.indices = didx.i(); }
+    if (in->source == HIPDRT_PEAKS_FROM_WINDOWS) {
+        TRY(upload(dws, in->win_start, (size_t)in->nwin * sizeof(int), st)); TRY(upload(dwe, in->win_end, (size_t)in->nwin * sizeof(int), st));
+        a.win_start = dws.i(); a.win_end = dwe.i();
+    }
+    if (nout > 0) {
+        TRY(upload(dout_grid, in->ln_tau_out, (size_t)nout * sizeof(double), st));
+        HIPDRT_CHECK(dE0.alloc((size_t)nout * pb.nb * sizeof(double)));
+    }
+    const size_t bm = (size_t)B * mp;
+    DevBuf dct, dpi, dti, del, der, drp, drc, dxp, dpg, dst;
+    HIPDRT_CHECK(dct.alloc((size_t)B * sizeof(int))); a.count = dct.i();
+    HIPDRT_CHECK(dst.alloc((size_t)B * sizeof(int))); a.status = dst.i();
+    if (out->peak_index) { HIPDRT_CHECK(dpi.alloc(bm * sizeof(int))); a.peak_index = dpi.i(); }
+    if (out->trough_index) { HIPDRT_CHECK(dti.alloc(bm * sizeof(int))); a.trough_index = dti.i(); }
+    if (out->eps_l) { HIPDRT_CHECK(del.alloc(bm * sizeof(double))); a.eps_l = del.d(); }
+    if (out->eps_r) { HIPDRT_CHECK(der.alloc(bm * sizeof(double))); a.eps_r = der.d(); }
+    if (out->r_peaks) { HIPDRT_CHECK(drp.alloc(bm * sizeof(double))); a.r_peaks = drp.d(); }
+    if (out->r_coef) { HIPDRT_CHECK(drc.alloc(bm * sizeof(double))); a.r_coef = drc.d(); }
+    if (out->x_peaks) { HIPDRT_CHECK(dxp.alloc(bm * pb.nb * sizeof(double))); a.x_peaks = dxp.d(); }
+    if (out->peak_gammas) { HIPDRT_CHECK(dpg.alloc(bm * nout * sizeof(double))); a.peak_gammas = dpg.d(); }
+    PredictTimer tm(p->ctx, st);
+    TRY(plan_drt_rows_dev(p, pb, nfind, orders, 2, o.sign, normalize, row_scale, need_var, st, dev, R, tm));
+    a.fxx = R.mu(0); a.f = R.mu(1);
+    if (find) {
+        HIPDRT_CHECK(dkeep.alloc((size_t)B * nfind * sizeof(int)));
+        PeakArgs pa{};
+        pa.neval = nfind; pa.o = po; pa.fxx = R.mu(0); pa.f = R.mu(1); pa.keep = dkeep.i(); pa.fit_status = p->fit_status.i();
+        if (need_var) {
+            pa.var_fxx = R.var(0); pa.ldv = R.ldv(); pa.cs = R.cs; pa.norm = R.norm; pa.var_status = R.dvstat.i();
+        }
+        TRY(launch_peaks(st, pa, B));
+        LAUNCH_OK();
+        a.keep = dkeep.i();
+        if (normalize) {
+            // estimate_peak_coef evaluates f and fxx without normalisation whatever find_peaks used: the same evaluation rows
+            // applied once more at the coefficient scale alone -- the bits of hipdrt_plan_predict_drt(normalize = 0)
+            HIPDRT_CHECK(dmu2.alloc((size_t)2 * B * nfind * sizeof(double)));
+            for (int k = 0; k < 2; ++k) {
+                launch_apply_rows(st, B, width, p->x.d(), n, ns, nfind, R.dE.d() + (size_t)k * nfind * width, width, R.cs,
+                                  p->fit_status.i(), dmu2.d() + (size_t)k * B * nfind, nfind);
+                LAUNCH_OK();
+            }
+            a.fxx = dmu2.d(); a.f = dmu2.d() + (size_t)B * nfind;
+        }
+    }
+    if (nout > 0) {
+        TRY(func_eval_dev(st, pb.ln_tau, pb.nb, dout_grid.d(), nout, pb.eps, 0, 1.0, dE0.d(), pb.nb));
+        a.E0 = dE0.d(); a.lto = dout_grid.d();
+    }
+    a.X = p->x.d(); a.ldx = n; a.col_offset = ns; a.cs = R.cs;
+    a.lt = dev.d(); a.lb = pb.ln_tau; a.basis_area = 1.7724538509055159 / pb.eps;
+    a.fit_status = p->fit_status.i();
+    TRY(launch_peak_resolve(st, a, B));
+    LAUNCH_OK();
+    tm.mark();
+    TRY(KkOut::back(out->count, dct, st)); TRY(KkOut::back(out->peak_index, dpi, st)); TRY(KkOut::back(out->trough_index, dti, st));
+    TRY(KkOut::back(out->eps_l, del, st)); TRY(KkOut::back(out->eps_r, der, st)); TRY(KkOut::back(out->r_peaks, drp, st));
+    TRY(KkOut::back(out->r_coef, drc, st)); TRY(KkOut::back(out->x_peaks, dxp, st)); TRY(KkOut::back(out->peak_gammas, dpg, st));
+    std::vector<int> hs(B), hv(B, 0);
+    HIPDRT_CHECK(hipMemcpyAsync(hs.data(), dst.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (need_var) HIPDRT_CHECK(hipMemcpyAsync(hv.data(), R.dvstat.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    bool unordered = false;
+    for (int b = 0; b < B; ++b) {
+        if (hs[b] >= 0 && need_var && hv[b] != 0) hs[b] = HIPDRT_PREDICT_NOT_PD;
+        unordered = unordered || hs[b] == HIPDRT_PEAKS_UNORDERED;
+        if (out->status) out->status[b] = hs[b];
+    }
+    if (unordered) {
+        set_error("invalid argument: resolve_peaks: the window peaks of a spectrum are not strictly increasing (two windows chose "
+                  "their shared border sample); see status");
+        return HIPDRT_E_INVALID;
+    }
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+int hipdrt_plan_integrate_drt(hipdrt_plan* p, const double* ln_tau_eval, int neval, int order, int sign, int normalize,
+                              const double* row_scale, const int* win_start, const int* win_end, int nwin, double* out,
+                              int* status) try {
+    HIPDRT_REQUIRE(p && ln_tau_eval && win_start && win_end && out, "NULL pointer");
+    PredictBasis pb;
+    TRY(predict_basis(p, pb));
+    HIPDRT_REQUIRE(neval >= 1, "neval >= 1");
+    HIPDRT_REQUIRE(order >= 0 && order <= 2, "order must be 0, 1 or 2");
+    HIPDRT_REQUIRE(sign == 1 || (pb.copies == 2 && (sign == 0 || sign == -1)),
+                   "sign must be 1, or 1, -1 or 0 when the DRT block holds a positive and a negative copy");
+    HIPDRT_REQUIRE(normalize >= 0 && normalize <= 2, "normalize must be 0, 1 (by R_p) or 2 (by absolute R_p)");
+    HIPDRT_REQUIRE(!row_scale || normalize == 0, "row_scale goes with normalize = 0 (a ratio to the spectrum's own R_p carries no scale)");
+    HIPDRT_REQUIRE(nwin >= 1 && nwin <= 65535, "1 <= nwin <= 65535");
+    TRY(peak_resolve_check_source(2, nullptr, 0, nwin, win_start, win_end, nwin, neval));
+    const int B = p->B, width = p->n - p->ns;
+    if (row_scale) for (int b = 0; b < B; ++b) HIPDRT_REQUIRE(row_scale[b] > 0.0 && std::isfinite(row_scale[b]), "row_scale must be positive and finite");
+    hipStream_t st; TRY(enter(p->ctx, &st));
+    DevBuf dev, dws, dwe, dres;
+    DrtRows R;
+    TRY(upload(dev, ln_tau_eval, (size_t)neval * sizeof(double), st));
+    TRY(upload(dws, win_start, (size_t)nwin * sizeof(int), st)); TRY(upload(dwe, win_end, (size_t)nwin * sizeof(int), st));
+    HIPDRT_CHECK(R.dE.alloc((size_t)neval * width * sizeof(double)));
+    HIPDRT_CHECK(R.dmu.alloc((size_t)B * neval * sizeof(double)));
+    HIPDRT_CHECK(dres.alloc((size_t)B * nwin * sizeof(double)));
+    PredictTimer tm(p->ctx, st);
+    TRY(plan_drt_rows_dev(p, pb, neval, &order, 1, sign, normalize, row_scale, false, st, dev, R, tm));
+    launch_window_trapz(st, B, neval, nwin, R.mu(0), dev.d(), dws.i(), dwe.i(), dres.d());
+    LAUNCH_OK();
+    tm.mark();
+    HIPDRT_CHECK(hipMemcpyAsync(out, dres.p, (size_t)B * nwin * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (status) HIPDRT_CHECK(hipMemcpyAsync(status, p->fit_status.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
     return HIPDRT_OK;
 } HIPDRT_CATCH
 

@@ -876,6 +876,217 @@ class DRT(PreparedFitMixin):
         (B, len(tau)): the probability of f > 0 with negative curvature (or the reverse), signed by f"""
         return self._map_probs('curv_prob_batch', 'curv_prob', tau, extend_var, prominence, height, sign, normalize)
 
+    # ---- per-peak coefficients, distributions and resistances (drt1d.py:3586-3620, 3949-4111; hybdrt/peaks.py:92-217) ------------
+    def _resolve_device(self, what, tau_out, tau_find, peak_indices, sign, epsilon_factor, max_epsilon, min_epsilon,
+                        epsilon_uniform, want, windows=None, find_peaks_kw=None, peak_tau=None, trough_tau=None,
+                        squeeze_factors=None, x=None):
+        """hipdrt_plan_resolve_peaks with upstream's defaults -> (padded outputs, tau_find).  On overflow the call is repeated
+        once with max_peaks = the largest count (at most 64); spectra beyond 64 keep empty rows and a warning is given."""
+        for name, v in (('peak_tau', peak_tau), ('trough_tau', trough_tau), ('squeeze_factors', squeeze_factors)):
+            if v is not None:
+                raise NotImplementedError(f'{what}: the {name}= argument is not taken (off-grid positions and squeezing act on one '
+                                          f'spectrum; peaks and troughs live on the find grid)')
+        plan, scales = self._predict_plan(what, x=x)
+        fkw = dict(find_peaks_kw or {})
+        if peak_indices is not None and tau_find is None and windows is None:
+            raise ValueError('If peak_indices are provided, the corresponding tau grid must also be provided')
+        if tau_find is None:
+            tau_find = fkw.pop('tau', None)
+        if tau_find is None:
+            tau_find = self.get_tau_eval(fkw.pop('ppd', 10))         # find_peaks' own default; estimate_peak_coef's is the same grid
+        tau_find = np.asarray(tau_find, dtype=float)
+        dsign = self._drt_sign(plan, sign)
+        B = plan.B
+        src = {}
+        if windows is not None:
+            src['windows'] = windows
+            mp0 = max(16, len(windows[0]))
+        elif peak_indices is not None:
+            rows = [np.sort(np.asarray(r, dtype=np.int64).ravel()) for r in (peak_indices if np.ndim(peak_indices[0]) else [peak_indices] * B)] \
+                if len(peak_indices) else [np.zeros(0, dtype=np.int64)] * B
+            if len(rows) != B:
+                raise ValueError(f'{what}: peak_indices must be one row, or one row per spectrum of the batch')
+            mp0 = max([16] + [len(r) for r in rows])
+            if mp0 > 64:
+                raise ValueError(f'{what}: at most 64 peaks per spectrum')
+        else:
+            for name in ('x', 'p_matrix', 'return_info'):
+                if fkw.get(name) is not None:
+                    raise NotImplementedError(f'{what}: find_peaks\' {name}= argument is not taken')
+                fkw.pop(name, None)
+            method = fkw.pop('method', 'thresh')
+            if method not in peaks.METHODS:
+                raise ValueError(f'Invalid method {method}. Options: {list(peaks.METHODS)}')
+            normalize, extend_var = fkw.pop('normalize', True), fkw.pop('extend_var', True)
+            fsign = fkw.pop('sign', sign)
+            if self._drt_sign(plan, fsign) != dsign:
+                raise ValueError(f'{what}: find_peaks runs with the sign of the peak coefficients')
+            opt_kw = {k: fkw.pop(k) for k in ('height', 'prominence', 'prob_thresh', 'num_peaks', 'fxx_var_floor') if k in fkw}
+            for name in fkw:
+                raise NotImplementedError(f'find_peaks: the {name}= argument is not taken (of scipy.signal.find_peaks\' conditions '
+                                          f'only height and prominence are built)')
+            search = sign if (self.fit_kwargs['nonneg'] and sign != 0) else 0
+            ext = self._extend_var_indices(tau_find) if (extend_var and method != 'thresh') else (-1, -1)
+            src['find_opts'] = _ffi.peak_opts(eval_sign=dsign, search=search, normalize=1 if normalize else 0, method=method,
+                                              ext_left=ext[0], ext_right=ext[1], **opt_kw)
+            mp0 = 16
+        ln_out = None if tau_out is None else np.log(np.asarray(tau_out, dtype=float))
+
+        def call(mp):
+            if peak_indices is not None and windows is None:
+                idx = np.full((B, mp), -1, dtype=np.int32)
+                for b, r in enumerate(rows):
+                    idx[b, :len(r)] = r
+                src['peak_indices'] = idx
+            o = _ffi.peak_resolve_opts(sign=dsign, max_peaks=mp, epsilon_factor=epsilon_factor, max_epsilon=max_epsilon,
+                                       min_epsilon=min_epsilon, epsilon_uniform=epsilon_uniform)
+            return plan.resolve_peaks(np.log(tau_find), ln_out, opts=o, row_scale=scales, want=want, **src)
+
+        out = call(mp0)
+        over = out['status'] == _ffi.PEAKS_OVERFLOW
+        if np.any(over):
+            out = call(int(min(64, np.max(out['count'][over]))))
+            over = out['status'] == _ffi.PEAKS_OVERFLOW
+            if np.any(over):
+                warnings.warn(f'{what}: {int(np.sum(over))} spectra have more than 64 peaks and get empty results')
+        return out, tau_find
+
+    @staticmethod
+    def _cut(out, name):
+        """per-spectrum list cut from a padded array (empty for spectra without a result)"""
+        ok = out['status'] >= 0
+        return [out[name][b, :out['count'][b]].copy() if ok[b] else out[name][b, :0].copy() for b in range(len(ok))]
+
+    def estimate_peak_coef_batch(self, tau=None, peak_indices=None, x=None, sign=1, epsilon_factor=1.25, max_epsilon=1.25,
+                                 min_epsilon=None, epsilon_uniform=None, peak_tau=None, trough_tau=None, **find_peaks_kw):
+        """DRT.estimate_peak_coef (drt1d.py:3949-3972) for every spectrum of the last fitted batch, on the device
+        (hipdrt_plan_resolve_peaks; models/peaks.py resolve_peaks_row is the rule in numpy) -> a list of B arrays
+        (peaks, len(basis_tau)) in data units.  tau: the find grid (None: find_peaks' own, get_tau_eval(10)); peak_indices: one
+        row for all spectra or one row per spectrum, else find_peaks(**find_peaks_kw) on the device.  Spectra whose fit failed
+        have no rows.  Last device batch only."""
+        out, _ = self._resolve_device('estimate_peak_coef', None, tau, peak_indices, sign, epsilon_factor, max_epsilon, min_epsilon,
+                                      epsilon_uniform, ('x_peaks',), find_peaks_kw=find_peaks_kw, peak_tau=peak_tau,
+                                      trough_tau=trough_tau, x=x)
+        return self._cut(out, 'x_peaks')
+
+    def _default_peak_sign(self, sign):
+        return (0 if self.series_neg else 1) if sign is None else sign
+
+    def estimate_peak_drts_batch(self, tau=None, ppd=10, tau_find_peaks=None, peak_indices=None, x=None, sign=None,
+                                 epsilon_factor=1.25, max_epsilon=1.25, min_epsilon=None, epsilon_uniform=None,
+                                 squeeze_factors=None, find_peaks_kw=None, peak_tau=None, trough_tau=None):
+        """DRT.estimate_peak_drts (drt1d.py:3984-4034) for every spectrum of the last fitted batch -> a list of B arrays
+        (peaks, len(tau)): every peak's partial distribution on tau (None: get_tau_eval(ppd)), formed on the device from the
+        peak coefficients and the order-0 evaluation matrix.  sign=None: 0 for series_neg fits, else 1."""
+        if tau is None:
+            tau = self.get_tau_eval(ppd)
+        out, _ = self._resolve_device('estimate_peak_drts', tau, tau_find_peaks, peak_indices, self._default_peak_sign(sign),
+                                      epsilon_factor, max_epsilon, min_epsilon, epsilon_uniform, ('peak_gammas',),
+                                      find_peaks_kw=find_peaks_kw, peak_tau=peak_tau, trough_tau=trough_tau,
+                                      squeeze_factors=squeeze_factors, x=x)
+        return self._cut(out, 'peak_gammas')
+
+    def quantify_peaks_batch(self, tau=None, ppd=10, tau_find_peaks=None, peak_indices=None, x=None, sign=None,
+                             epsilon_factor=1.25, max_epsilon=1.25, min_epsilon=None, epsilon_uniform=None, squeeze_factors=None,
+                             find_peaks_kw=None, peak_tau=None, trough_tau=None, return_info=False):
+        """DRT.quantify_peaks (drt1d.py:4101-4111) for every spectrum of the last fitted batch -> a list of B arrays of peak
+        resistances, np.trapezoid of every peak's distribution over ln(tau); only the resistances (and with return_info the
+        peak and trough indices, the length scales and r_coef = predict_r_p of every peak's coefficients) come down."""
+        if tau is None:
+            tau = self.get_tau_eval(ppd)
+        want = ('r_peaks',) + (('peak_index', 'trough_index', 'eps_l', 'eps_r', 'r_coef') if return_info else ())
+        out, tau_find = self._resolve_device('quantify_peaks', tau, tau_find_peaks, peak_indices, self._default_peak_sign(sign),
+                                             epsilon_factor, max_epsilon, min_epsilon, epsilon_uniform, want,
+                                             find_peaks_kw=find_peaks_kw, peak_tau=peak_tau, trough_tau=trough_tau,
+                                             squeeze_factors=squeeze_factors, x=x)
+        r_peaks = self._cut(out, 'r_peaks')
+        if not return_info:
+            return r_peaks
+        info = {k: self._cut(out, k) for k in want[1:]}
+        info['trough_index'] = [t[:max(len(t) - 1, 0)] for t in info['trough_index']]
+        info['tau_find_peaks'] = tau_find
+        return r_peaks, info
+
+    def _window_kw(self, what, predict_kw):
+        kw = dict(predict_kw)
+        if kw.pop('x', None) is not None:
+            raise NotImplementedError(f'{what}: the x= override is not taken (predictions use the coefficients on the device)')
+        order, sign = kw.pop('order', 0), kw.pop('sign', 1)
+        normalize, normalize_by, abs_norm = kw.pop('normalize', False), kw.pop('normalize_by', None), kw.pop('abs_norm', False)
+        for name in kw:
+            raise TypeError(f'{what}: unexpected keyword {name}')
+        if order not in (0, 1, 2):
+            raise ValueError(f'Invalid order {order}. Options: 0, 1, 2')
+        if normalize_by is not None and not normalize_by > 0:
+            raise ValueError('normalize_by must be positive')
+        return order, sign, normalize, normalize_by, abs_norm
+
+    def _integrate_device(self, what, tau, windows, predict_kw):
+        order, sign, normalize, normalize_by, abs_norm = self._window_kw(what, predict_kw)
+        plan, scales = self._predict_plan(what)
+        by_rp = bool(normalize) and normalize_by is None
+        out, _ = plan.integrate_drt(np.log(tau), windows, order=order, sign=self._drt_sign(plan, sign),
+                                    normalize=(2 if abs_norm else 1) if by_rp else 0,
+                                    row_scale=None if (by_rp or scales is None) else scales)
+        return out if normalize_by is None else out / normalize_by
+
+    def split_r_p_batch(self, tau_splits, resolve_peaks=False, **predict_kw):
+        """DRT.split_r_p (drt1d.py:3596-3620) for every spectrum of the last fitted batch -> (B, len(tau_splits) + 1): the
+        trapezoid of predict_drt's row over the windows between the splits, or with resolve_peaks the resistance
+        predict_r_p(x = x_peak) of one resolved peak per window (the minimum of the curvature), all on the device"""
+        predict_kw = dict(predict_kw)
+        tau = predict_kw.pop('tau', None)
+        ppd = predict_kw.pop('ppd', 20)
+        tau = self.get_tau_eval(ppd) if tau is None else np.asarray(tau, dtype=float)
+        windows = peaks.split_windows(tau, tau_splits)
+        if not resolve_peaks:
+            return self._integrate_device('split_r_p', tau, windows, predict_kw)
+        order, sign, normalize, normalize_by, _ = self._window_kw('split_r_p', predict_kw)
+        if order != 0 or normalize or normalize_by is not None:
+            raise NotImplementedError('split_r_p(resolve_peaks=True): order, normalize and normalize_by are not taken (upstream '
+                                      'applies them to the curvature it searches; the peak resistances carry none)')
+        out, _ = self._resolve_device('split_r_p', None, tau, None, 1, 1.25, 1.25, None, None, ('r_coef',), windows=windows)
+        nwin = len(windows[0])
+        res = out['r_coef'][:, :nwin].copy()
+        res[out['status'] < 0] = np.nan
+        return res
+
+    def integrate_drt_batch(self, tau_min, tau_max, ppd=10, **predict_kw):
+        """DRT.integrate_drt (drt1d.py:3590-3594) for every spectrum of the last fitted batch -> (B,)"""
+        num_decades = np.log10(tau_max) - np.log10(tau_min)
+        tau = np.logspace(np.log10(tau_min), np.log10(tau_max), int(num_decades * ppd) + 1)
+        return self._integrate_device('integrate_drt', tau, ([0], [len(tau)]), predict_kw)[:, 0]
+
+    # single-member forms with the reference's signatures; ``b`` picks a member of the last batch
+    def estimate_peak_coef(self, tau=None, peak_indices=None, x=None, sign=1, epsilon_factor=1.25, max_epsilon=1.25,
+                           min_epsilon=None, epsilon_uniform=None, peak_tau=None, trough_tau=None, b=0, **find_peaks_kw):
+        """DRT.estimate_peak_coef (drt1d.py:3949-3972) of member ``b`` of the last fit, from the device"""
+        return self.estimate_peak_coef_batch(tau=tau, peak_indices=peak_indices, x=x, sign=sign, epsilon_factor=epsilon_factor,
+                                             max_epsilon=max_epsilon, min_epsilon=min_epsilon, epsilon_uniform=epsilon_uniform,
+                                             peak_tau=peak_tau, trough_tau=trough_tau, **find_peaks_kw)[b]
+
+    def estimate_peak_drts(self, tau=None, ppd=10, tau_find_peaks=None, peak_indices=None, x=None, sign=None, epsilon_factor=1.25,
+                           max_epsilon=1.25, min_epsilon=None, epsilon_uniform=None, squeeze_factors=None, find_peaks_kw=None,
+                           peak_tau=None, trough_tau=None, b=0):
+        """DRT.estimate_peak_drts (drt1d.py:3984-4034) of member ``b`` of the last fit, from the device"""
+        return self.estimate_peak_drts_batch(tau=tau, ppd=ppd, tau_find_peaks=tau_find_peaks, peak_indices=peak_indices, x=x,
+                                             sign=sign, epsilon_factor=epsilon_factor, max_epsilon=max_epsilon,
+                                             min_epsilon=min_epsilon, epsilon_uniform=epsilon_uniform,
+                                             squeeze_factors=squeeze_factors, find_peaks_kw=find_peaks_kw, peak_tau=peak_tau,
+                                             trough_tau=trough_tau)[b]
+
+    def quantify_peaks(self, tau=None, ppd=10, b=0, **estimate_peak_drts_kw):
+        """DRT.quantify_peaks (drt1d.py:4101-4111) of member ``b`` of the last fit -> a list of peak resistances"""
+        return list(self.quantify_peaks_batch(tau=tau, ppd=ppd, **estimate_peak_drts_kw)[b])
+
+    def split_r_p(self, tau_splits, resolve_peaks=False, b=0, **predict_kw):
+        """DRT.split_r_p (drt1d.py:3596-3620) of member ``b`` of the last fit"""
+        return self.split_r_p_batch(tau_splits, resolve_peaks=resolve_peaks, **predict_kw)[b]
+
+    def integrate_drt(self, tau_min, tau_max, ppd=10, b=0, **predict_kw):
+        """DRT.integrate_drt (drt1d.py:3590-3594) of member ``b`` of the last fit"""
+        return float(self.integrate_drt_batch(tau_min, tau_max, ppd=ppd, **predict_kw)[b])
+
     # ---- Kramers-Kronig test (drt1d.py:1370-1491) ------------------------------------------------------------------------
     def get_fit_frequencies(self):
         """DRTBase.get_fit_frequencies for an EIS fit: the frequencies of the last fit"""

@@ -4,6 +4,10 @@
 on top of it sit DRT.find_peaks (hybdrt/models/drt1d.py:3753-3947), curvature.peak_prob_1d (hybdrt/mapping/curvature.py:12-58)
 and the elementwise formula of DRTMD.predict_curv_prob (hybdrt/mapping/drtmd.py:1100-1104).  Everything acts on rows that are
 already evaluated: fxx (order 2), f (order 0) and their posterior variances.  No scipy: the product layer does not depend on it.
+
+The second half states csrc/peak_resolve.hip: peaks.find_troughs and peaks.estimate_peak_weight_distributions
+(hybdrt/peaks.py:92-217) under DRT.estimate_peak_coef, estimate_peak_drts, quantify_peaks (drt1d.py:3949-4111), split_r_p and
+integrate_drt (3586-3620).  Upstream's np.log(tau_i / trough) is taken as a difference of the ln grids (a rounding-level deviation).
 """
 import math
 
@@ -189,3 +193,119 @@ def find_peaks_dense(fxx, f=None, var_fxx=None, var_f=None, search=1, method=0, 
         out['probs'][idx] = info['probs']
     out['count'], out['used_prominence'] = len(kept), float(used)
     return out
+
+
+# ---- per-peak coefficients, distributions and resistances: the numpy statement of csrc/peak_resolve.hip ------------------------
+def find_troughs(f, fxx, peak_indices):
+    """peaks.find_troughs (hybdrt/peaks.py:92-136) for sorted peak indices -> one trough index per neighbouring pair"""
+    f, fxx = np.asarray(f, dtype=float), np.asarray(fxx, dtype=float)
+    f_mix = -(f - fxx)
+    pk = sorted(int(p) for p in peak_indices)
+    troughs = []
+    for s, e in zip(pk[:-1], pk[1:]):
+        ls, rs = np.sign(f[s]), np.sign(f[e])
+        if ls == rs:
+            v = ls * f[s:e]
+            if np.min(v) < min(ls * f[s], ls * f[e]):
+                t = s + int(np.argmin(v))
+            else:
+                t = s + int(np.argmax(ls * f_mix[s:e]))
+                if t in (s, e):
+                    t = int((s + e + 2 * t) / 4)
+        else:
+            t = s + int(np.argmin(np.abs(f[s:e])))
+        troughs.append(t)
+    return np.array(troughs, dtype=np.intp)
+
+
+def peak_epsilons(ln_tau, peak_indices, trough_indices, epsilon_factor=1.25, max_epsilon=1.25, min_epsilon=None,
+                  epsilon_uniform=None):
+    """the inverse length scales of every peak's weighting function (hybdrt/peaks.py:164-199) -> (eps_l, eps_r); a zero
+    distance gives +inf and hence max_epsilon, as IEEE division gives upstream"""
+    lt = np.asarray(ln_tau, dtype=float)
+    P = len(peak_indices)
+    eps_l, eps_r = np.empty(P), np.empty(P)
+    for i, p in enumerate(peak_indices):
+        if epsilon_uniform is not None:
+            eps_l[i] = eps_r[i] = epsilon_uniform
+            continue
+        prev = lt[0] if i == 0 else lt[trough_indices[i - 1]]
+        nxt = lt[-1] if i == P - 1 else lt[trough_indices[i]]
+        with np.errstate(divide='ignore'):
+            el = min(np.float64(epsilon_factor) / (lt[p] - prev), max_epsilon)
+            er = min(np.float64(epsilon_factor) / (nxt - lt[p]), max_epsilon)
+        if min_epsilon is not None:
+            el, er = max(el, min_epsilon), max(er, min_epsilon)
+        eps_l[i], eps_r[i] = el, er
+    return eps_l, eps_r
+
+
+def peak_weights(ln_basis, ln_peak, eps_l, eps_r):
+    """hybdrt/peaks.py:201-217: w[i][j] = exp(-(eps y)^2), y = ln_basis[j] - ln_peak[i], eps_l left of the peak and eps_r on it and
+    right of it, every column divided by its sum over the peaks (0 / 0 = NaN where all weights underflow: more than about 9.5
+    decades from every peak at eps = 1.25).  One peak or none: ones."""
+    lb = np.asarray(ln_basis, dtype=float)
+    P = len(ln_peak)
+    if P <= 1:
+        return np.ones((P, len(lb)))
+    w = np.empty((P, len(lb)))
+    for i in range(P):
+        y = lb - ln_peak[i]
+        w[i] = np.exp(-(np.where(y < 0, eps_l[i], eps_r[i]) * y) ** 2)
+    tot = np.zeros(len(lb))
+    for i in range(P):                                   # (ascending i)
+        tot = tot + w[i]
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return w / tot
+
+
+def trapezoid(y, x):
+    """np.trapezoid(y, x=x): the sum of the terms (dx (y1 + y0)) / 2 (the kernels add them in a fixed order of their own)"""
+    y, x = np.asarray(y, dtype=float), np.asarray(x, dtype=float)
+    if len(y) < 2:
+        return 0.0
+    return float(np.sum((np.diff(x) * (y[1:] + y[:-1])) / 2.0))
+
+
+def resolve_peaks_row(f, fxx, peak_indices, x_red, ln_tau_find, ln_basis, e0=None, ln_tau_out=None, basis_area=1.0,
+                      epsilon_factor=1.25, max_epsilon=1.25, min_epsilon=None, epsilon_uniform=None):
+    """estimate_peak_coef / estimate_peak_drts / quantify_peaks for one spectrum on evaluated rows -> dict(peak_index, troughs,
+    eps_l, eps_r, x_peaks (P, nb), peak_gammas (P, nout), r_peaks (P,), r_coef (P,)).  f, fxx: the unnormalised rows on the find
+    grid; x_red: get_drt_params in data units; e0: the order-0 evaluation matrix (nout, nb) of the output grid (None: no
+    peak_gammas / r_peaks); basis_area = sqrt(pi) / epsilon of the basis (predict_r_p)."""
+    pk = np.array(sorted(int(p) for p in peak_indices), dtype=np.intp)
+    lt, lb, x_red = np.asarray(ln_tau_find, dtype=float), np.asarray(ln_basis, dtype=float), np.asarray(x_red, dtype=float)
+    tr = find_troughs(f, fxx, pk)
+    eps_l, eps_r = peak_epsilons(lt, pk, tr, epsilon_factor, max_epsilon, min_epsilon, epsilon_uniform)
+    w = peak_weights(lb, lt[pk], eps_l, eps_r)
+    x_peaks = x_red * w
+    out = dict(peak_index=pk, troughs=tr, eps_l=eps_l, eps_r=eps_r, x_peaks=x_peaks,
+               r_coef=np.array([np.sum(xp) * basis_area for xp in x_peaks]))
+    if e0 is not None:
+        out['peak_gammas'] = x_peaks @ np.asarray(e0, dtype=float).T
+        out['r_peaks'] = np.array([trapezoid(g, ln_tau_out) for g in out['peak_gammas']])
+    return out
+
+
+def nearest_index(arr, val):
+    """utils.array.nearest_index without a constraint: the first minimum of |arr - val|"""
+    return int(np.argmin(np.abs(np.asarray(arr, dtype=float) - val)))
+
+
+def split_windows(tau, tau_splits):
+    """split_r_p's windows (drt1d.py:3606-3608) -> (start, end): [start, end) with end = split + 1, the last one len(tau) + 1
+    (numpy's slice clips it)"""
+    split = [nearest_index(tau, ts) for ts in sorted(tau_splits)]
+    return np.array([0] + split, dtype=np.intp), np.array(split + [len(tau)], dtype=np.intp) + 1
+
+
+def window_peaks(fxx, start, end):
+    """split_r_p(resolve_peaks=True): one peak per window, i + argmin(fxx[i:j])"""
+    fxx = np.asarray(fxx, dtype=float)
+    return np.array([i + int(np.argmin(fxx[i:j])) for i, j in zip(start, end)], dtype=np.intp)
+
+
+def window_integrals(gamma, ln_tau, start, end):
+    """split_r_p without resolve_peaks and integrate_drt: the trapezoid of one row over every window [start, end)"""
+    gamma, ln_tau = np.asarray(gamma, dtype=float), np.asarray(ln_tau, dtype=float)
+    return np.array([trapezoid(gamma[i:j], ln_tau[i:j]) for i, j in zip(start, end)])

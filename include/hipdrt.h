@@ -527,6 +527,71 @@ int hipdrt_plan_find_peaks(hipdrt_plan* plan, const double* ln_tau_eval, int nev
                            int* left_bases, int* right_bases, int* count, double* used_prominence, double* peak_prob,
                            double* curv_prob, int* status);
 
+/* ---- per-peak coefficients, distributions and resistances of the fitted batch ------------------------------------------------
+ * Options of DRT.estimate_peak_coef / estimate_peak_drts / quantify_peaks (hybdrt/models/drt1d.py:3949-4111) over
+ * peaks.find_troughs and peaks.estimate_peak_weight_distributions (hybdrt/peaks.py:92-217).                                    */
+typedef struct {
+    int sign;                /* 1; get_drt_params' sign of the coefficients and rows (1, or 1 / -1 / 0 for a two-copy block)      */
+    int max_peaks;           /* 16; 1 .. 64: peak slots per spectrum in every output                                             */
+    double epsilon_factor;   /* 1.25; eps = min(epsilon_factor / distance to the neighbouring trough in ln tau, max_epsilon)      */
+    double max_epsilon;      /* 1.25                                                                                             */
+    double min_epsilon;      /* NaN = none; lower bound of eps                                                                   */
+    double epsilon_uniform;  /* NaN = per peak; one inverse length scale for every peak and side                                 */
+} hipdrt_peak_resolve_opts;
+void hipdrt_peak_resolve_opts_default(hipdrt_peak_resolve_opts* o);
+/* per-spectrum statuses of hipdrt_plan_resolve_peaks: more peaks than max_peaks (count holds the true number, the rows are empty);
+ * the window peaks of source 2 are not strictly increasing (two windows chose their shared border sample: upstream fails there) */
+#define HIPDRT_PEAKS_OVERFLOW (-4)
+#define HIPDRT_PEAKS_UNORDERED (-5)
+#define HIPDRT_PEAKS_FROM_FIND 0      /* the kept peaks of find_peaks with peak_opts                                             */
+#define HIPDRT_PEAKS_FROM_INDICES 1   /* peak_indices [B][max_peaks], -1 padded                                                   */
+#define HIPDRT_PEAKS_FROM_WINDOWS 2   /* split_r_p(resolve_peaks=True): i + argmin(fxx[i:j]) of every window                      */
+typedef struct {
+    int source;                       /* HIPDRT_PEAKS_FROM_*                                                                     */
+    const hipdrt_peak_opts* peak_opts;/* source 0: find_peaks' options (NULL: defaults); eval_sign must equal opts.sign           */
+    const int* peak_indices;          /* source 1: [B][max_peaks] into the find grid, strictly increasing, -1 padded at the end   */
+    const int *win_start, *win_end;   /* source 2: [nwin] windows [start, end) of the find grid; end may pass the grid by one     */
+    int nwin;
+    const double* ln_tau_find;        /* [nfind] the grid the peaks and troughs live on                                          */
+    int nfind;
+    const double* ln_tau_out;         /* [nout] grid of peak_gammas / r_peaks; NULL with nout = 0 when neither is asked for       */
+    int nout;
+    const double* row_scale;          /* [B] or NULL: multiplies every spectrum's coefficient scale (prepared plans)              */
+} hipdrt_peak_resolve_in;
+typedef struct {                      /* host arrays, any may be NULL (it is then never formed); padded: -1 / NaN in absent slots */
+    int* count;                       /* [B] peaks of the spectrum                                                               */
+    int* peak_index;                  /* [B][max_peaks]                                                                          */
+    int* trough_index;                /* [B][max_peaks] count - 1 troughs                                                        */
+    double *eps_l, *eps_r;            /* [B][max_peaks] inverse length scales left and right of every peak                       */
+    double* r_peaks;                  /* [B][max_peaks] quantify_peaks: np.trapezoid(peak_gammas, x = ln tau_out)                 */
+    double* r_coef;                   /* [B][max_peaks] predict_r_p(x = x_peak) = sqrt(pi) / eps_basis * sum_j x_peaks[i][j]      */
+    double* x_peaks;                  /* [B][max_peaks][nb] estimate_peak_coef                                                   */
+    double* peak_gammas;              /* [B][max_peaks][nout] estimate_peak_drts                                                 */
+    int* status;                      /* [B] the fit's status, HIPDRT_PREDICT_NOT_PD (source 0, method 1), HIPDRT_PEAKS_*        */
+} hipdrt_peak_resolve_out;
+/* DRT.estimate_peak_coef (drt1d.py:3949-3972), estimate_peak_drts (3984-4034), quantify_peaks (4101-4111) and the resolve_peaks
+ * branch of split_r_p (3610-3616) for every spectrum of the fitted batch, on the device.  The rows f (order 0) and fxx (order 2)
+ * on the find grid are evaluated as hipdrt_plan_predict_drt(normalize = 0) evaluates them (same kernels, same bits); source 0
+ * first runs hipdrt_plan_find_peaks' kernel on the rows with peak_opts' normalisation and takes its keep rows where they lie.
+ * One workgroup per spectrum then finds the troughs (hybdrt/peaks.py:92-136), the inverse length scales (164-199), the
+ * normalised weights (201-213), x_peaks = x_red * w in data units, peak_gammas = x_peaks E0' with E0 the order-0 matrix of
+ * hipdrt_func_eval_matrix on the output grid, and both resistances (csrc/peak_resolve.hip; hipdrt/models/peaks.py
+ * resolve_peaks_row is its numpy statement).  A basis point so far from every peak that all its weights underflow gives 0 / 0 =
+ * NaN, as upstream.  HIPDRT_E_INVALID, before any launch: options out of range, a sign other than 1 on a one-copy block, indices
+ * or windows out of range or not strictly increasing, a shape whose rows do not fit one workgroup's LDS (nb = 1024 with 16
+ * peaks, nfind = 512 and nout = 121 fits); after the launch: a spectrum with HIPDRT_PEAKS_UNORDERED (the outputs are valid for
+ * the other spectra).  Plain and prepared plans (hipdrt_plan_set_tau_basis first; unit scale times row_scale).  The result of a
+ * spectrum depends neither on B nor on its position in the batch.                                                              */
+int hipdrt_plan_resolve_peaks(hipdrt_plan* plan, const hipdrt_peak_resolve_in* in, const hipdrt_peak_resolve_opts* opts,
+                              hipdrt_peak_resolve_out* out);
+/* DRT.integrate_drt (drt1d.py:3590-3594) and split_r_p without resolve_peaks (3596-3620): out[b][k] = np.trapezoid of
+ * predict_drt's row (order, sign, normalize as hipdrt_plan_predict_drt; row_scale [B] or NULL, normalize = 0 only) over the
+ * windows [win_start[k], win_end[k]) of ln_tau_eval[neval]; an end may pass the grid by one (numpy clips the slice).
+ * out [B][nwin]; status [B] (may be NULL) the fit's status, rows of failed fits are NaN.                                        */
+int hipdrt_plan_integrate_drt(hipdrt_plan* plan, const double* ln_tau_eval, int neval, int order, int sign, int normalize,
+                              const double* row_scale, const int* win_start, const int* win_end, int nwin, double* out,
+                              int* status);
+
 /* kernel-time breakdown of the last hipdrt_plan_fit in ms (HIP events on the ctx stream):
  * t[0]=total, t[1]=gram, t[2]=qp, t[3]=hyper, t[4]=setup/other; launches[5] same order                 */
 int hipdrt_plan_timings(hipdrt_plan* plan, float* t, int* launches);

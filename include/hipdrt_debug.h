@@ -5,7 +5,7 @@
  * (in-kernel phase counters of a PROFILE build, occupancy queries).  Every hook takes a context: there is no process-wide
  * switch.  The kernels of the fit loop each have a hook that runs their launcher as it is on host arrays: hipdrt_debug_gram_l2
  * (Gram, q), hipdrt_debug_hyper_step (the hyper-parameter step in its three product forms), hipdrt_debug_kk_stats,
- * hipdrt_debug_apply_rows, hipdrt_debug_find_peaks.
+ * hipdrt_debug_apply_rows, hipdrt_debug_find_peaks, hipdrt_debug_peak_resolve.
  */
 #ifndef HIPDRT_DEBUG_H
 #define HIPDRT_DEBUG_H
@@ -145,6 +145,28 @@ int hipdrt_debug_find_peaks(hipdrt_ctx* ctx, int B, int neval, const double* fxx
                             const double* var_f, const hipdrt_peak_opts* opts, int* peak_sign, int* keep, double* heights,
                             double* prominences, double* probs, int* left_bases, int* right_bases, int* count,
                             double* used_prominence, double* peak_prob, double* curv_prob);
+
+/* test hook (tests/test_gpu_peak_resolve.py): peak_resolve_kernel (csrc/peak_resolve.hip) as it is, on host arrays -- f, fxx
+ * [B][nfind]; keep [B][nfind] (source 0) or indices [B][max_peaks] (source 1) or windows (source 2); x [B][copies * nb] the DRT
+ * block in data units; ln_tau_find [nfind], ln_basis [nb], ln_tau_out [nout] (nout may be 0); E0 [nout][nb] is built by the
+ * library (hipdrt_func_eval_matrix's kernel, order 0, basis_eps).  fit_status [B] may be NULL.  Outputs as
+ * hipdrt_plan_resolve_peaks, any may be NULL.  Non-finite input rows are refused, as are indices and windows out of range or not
+ * strictly increasing.  Every device output has a border of marker bytes on either side: HIPDRT_E_NUMERIC when the kernel changed
+ * one.  HIPDRT_E_INVALID, and nothing is launched, when the shape does not fit one workgroup's LDS; lds_bytes (may be NULL) gets
+ * the need in every case.                                                                                                        */
+typedef struct {
+    int B, nfind, nb, nout, copies, source, nwin;
+    const double *f, *fxx;
+    const int *keep, *indices, *win_start, *win_end;
+    const double* x;
+    const double *ln_tau_find, *ln_basis, *ln_tau_out;
+    double basis_eps;
+    const int* fit_status;
+    const hipdrt_peak_resolve_opts* opts;
+    hipdrt_peak_resolve_out out;
+    long long* lds_bytes;
+} hipdrt_debug_peak_resolve_args;
+int hipdrt_debug_peak_resolve(hipdrt_ctx* ctx, const hipdrt_debug_peak_resolve_args* a);
 
 /* tools hook (tools/bench_predict.py, tools/bench_peaks.py): kernel time in ms of the last hipdrt_plan_predict_drt /
  * hipdrt_plan_predict_z / hipdrt_plan_find_peaks (ms[0]: the mean rows, ms[1]: all launches, peaks_kernel included) of a plan of
