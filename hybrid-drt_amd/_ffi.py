@@ -83,6 +83,14 @@ class PeakOpts(C.Structure):
                 ("fxx_var_floor", C.c_double), ("ext_left", C.c_int), ("ext_right", C.c_int)]
 
 
+class PfrtOpts(C.Structure):
+    """hipdrt_pfrt_opts (include/hipdrt.h)"""
+    _fields_ = [("eval_sign", C.c_int), ("search", C.c_int), ("height", C.c_double), ("prominence", C.c_double),
+                ("prior_mu", C.c_double), ("prior_sigma", C.c_double), ("n_eff_factor", C.c_double), ("fxx_var_floor", C.c_double),
+                ("ext_left", C.c_int), ("ext_right", C.c_int), ("smooth", C.c_int), ("smooth_order", C.c_double),
+                ("smooth_epsilon", C.c_double), ("integrate", C.c_int), ("integrate_threshold", C.c_double), ("normalize", C.c_int)]
+
+
 class PeakResolveOpts(C.Structure):
     """hipdrt_peak_resolve_opts (include/hipdrt.h)"""
     _fields_ = [("sign", C.c_int), ("max_peaks", C.c_int), ("epsilon_factor", C.c_double), ("max_epsilon", C.c_double),
@@ -192,6 +200,17 @@ SIGNATURES = {
     "hipdrt_plan_resolve_peaks": [_vp, C.POINTER(PeakResolveIn), C.POINTER(PeakResolveOpts), C.POINTER(PeakResolveOut)],
     "hipdrt_plan_integrate_drt": [_vp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _ip, _ip, C.c_int, _dp, _ip],
     "hipdrt_debug_peak_resolve": [_vp, C.POINTER(DebugPeakResolveArgs)],
+    "hipdrt_plan_pfrt_bytes_per_spectrum": [C.c_int, C.c_int, C.POINTER(C.c_longlong)],
+    "hipdrt_plan_pfrt_begin": [_vp, C.c_int],
+    "hipdrt_plan_pfrt_record": [_vp],
+    "hipdrt_plan_pfrt_steps": [_vp, _ip],
+    "hipdrt_plan_pfrt_get_step": [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip],
+    "hipdrt_plan_get_step_p_matrix": [_vp, C.c_int, C.c_int, _dp],
+    "hipdrt_pfrt_opts_default": [C.POINTER(PfrtOpts)],
+    "hipdrt_plan_predict_pfrt": [_vp, _dp, _dp, C.c_int, _dp, C.c_int, C.POINTER(PfrtOpts), _dp, _dp, _dp, _dp, _ip],
+    "hipdrt_debug_pfrt_step": [_vp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_double, C.c_int, C.c_int, _dp],
+    "hipdrt_debug_pfrt_combine": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.POINTER(PfrtOpts), _dp, _dp,
+                                  _dp, _dp, _dp],
     "hipdrt_debug_last_predict_ms": [_vp, C.POINTER(C.c_float)],
     "hipdrt_debug_apply_rows": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp],
     "hipdrt_comm_unique_id": [C.c_char_p],
@@ -246,7 +265,7 @@ SIGNATURES = {
 }
 _RESTYPES = {"hipdrt_last_error": C.c_char_p, "hipdrt_stream": C.c_void_p, "hipdrt_default_fit_opts": None,
              "hipdrt_default_kk_opts": None, "hipdrt_peak_opts_default": None,
-             "hipdrt_peak_resolve_opts_default": None}
+             "hipdrt_peak_resolve_opts_default": None, "hipdrt_pfrt_opts_default": None}
 
 _lib = None
 _lock = threading.Lock()
@@ -347,6 +366,25 @@ def peak_opts(eval_sign=1, search=1, normalize=1, method='thresh', height=None, 
     o.prob_thresh, o.num_peaks, o.fxx_var_floor = float(prob_thresh), int(num_peaks or 0), float(fxx_var_floor)
     o.ext_left, o.ext_right = int(ext_left), int(ext_right)
     return o
+
+
+def pfrt_opts(**kw) -> PfrtOpts:
+    """hipdrt_pfrt_opts: the library's defaults (DRT.predict_pfrt's) with the given fields replaced"""
+    o = PfrtOpts()
+    load_library().hipdrt_pfrt_opts_default(C.byref(o))
+    names = {name for name, _ in PfrtOpts._fields_}
+    for k, v in kw.items():
+        if k not in names:
+            raise TypeError(f"hipdrt_pfrt_opts has no field {k!r}")
+        setattr(o, k, type(getattr(o, k))(v))
+    return o
+
+
+def pfrt_bytes_per_spectrum(n, steps):
+    """bytes the PFRT step store takes per spectrum of the plan's capacity (hipdrt_plan_pfrt_bytes_per_spectrum)"""
+    out = C.c_longlong()
+    _check(load_library().hipdrt_plan_pfrt_bytes_per_spectrum(int(n), int(steps), C.byref(out)))
+    return int(out.value)
 
 
 PEAKS_OVERFLOW, PEAKS_UNORDERED = -4, -5            # per-spectrum statuses of hipdrt_plan_resolve_peaks
@@ -933,6 +971,37 @@ class Context:
         out["lds_bytes"] = int(lds.value)
         return out
 
+    def debug_pfrt_step(self, peak_sign, heights, prominences, f, var_f, var_fxx, var_floor=1e-5, ext_left=-1, ext_right=-1):
+        """tests: pfrt_step_kernel on host rows (B, neval) (hipdrt_debug_pfrt_step, include/hipdrt_debug.h) -> (B, neval).  Raises
+        when the kernel wrote outside its output."""
+        sg = np.atleast_2d(_i32(peak_sign))
+        rows = [np.atleast_2d(_f64(r)) for r in (heights, prominences, f, var_f, var_fxx)]
+        B, n = sg.shape
+        if any(r.shape != (B, n) for r in rows):
+            raise ValueError("all rows must have the shape of peak_sign")
+        out = np.full((B, n), 7e77)
+        _check(self._lib.hipdrt_debug_pfrt_step(self._h, B, n, _pi(sg), *[_p(r) for r in rows], float(var_floor), int(ext_left),
+                                                int(ext_right), _p(out)))
+        return out
+
+    def debug_pfrt_combine(self, step_pfrt, rss, sum_log_w, factors, m, ln_tau_pfrt, ln_tau_out=None, opts: PfrtOpts | None = None):
+        """tests: pfrt_combine_kernel on host arrays (hipdrt_debug_pfrt_combine): step_pfrt (S, B, np), rss and sum_log_w (S, B),
+        factors (S,) -> dict(pfrt (B, nout), raw_pfrt (B, np), post_prob (S, B)).  Raises when the kernel wrote outside an output."""
+        sp, rss, slw, fac = _f64(step_pfrt), _f64(rss), _f64(sum_log_w), _f64(factors).ravel()
+        S, B, npf = sp.shape
+        if rss.shape != (S, B) or slw.shape != (S, B) or fac.size != S:
+            raise ValueError("shapes: step_pfrt (S, B, np); rss, sum_log_w (S, B); factors (S,)")
+        opts = opts if opts is not None else pfrt_opts()
+        ltp = _f64(ln_tau_pfrt).ravel()
+        lto = None if ln_tau_out is None else _f64(ln_tau_out).ravel()
+        nout = npf if lto is None else lto.size
+        if ltp.size != npf:
+            raise ValueError("ln_tau_pfrt must have np points")
+        out = dict(pfrt=np.full((B, nout), 7e77), raw_pfrt=np.full((B, npf), 7e77), post_prob=np.full((S, B), 7e77))
+        _check(self._lib.hipdrt_debug_pfrt_combine(self._h, B, S, npf, nout, _p(sp), _p(rss), _p(slw), _p(fac), int(m), C.byref(opts),
+                                                   _p(ltp), _p(lto), _p(out["pfrt"]), _p(out["raw_pfrt"]), _p(out["post_prob"])))
+        return out
+
     def debug_last_predict_ms(self):
         """tools: kernel time in ms of the last predict_drt / predict_z of a plan of this context -> (mean or impedance, with band)"""
         ms = (C.c_float * 2)()
@@ -1225,6 +1294,52 @@ class Plan:
         r_inf, r_tot = (None, None) if r_p_only else (np.empty(B), np.empty(B))
         _check(self._lib.hipdrt_plan_predict_resistances(self._h, _p(r_p), _p(r_inf), _p(r_tot), int(bool(absolute))))
         return r_p, r_inf, r_tot
+
+    def pfrt_begin(self, max_steps):
+        """size and empty the PFRT step store (hipdrt_plan_pfrt_begin)"""
+        _check(self._lib.hipdrt_plan_pfrt_begin(self._h, int(max_steps)))
+
+    def pfrt_record(self):
+        """append the state the last fit / warm restart left to the PFRT step store (hipdrt_plan_pfrt_record)"""
+        _check(self._lib.hipdrt_plan_pfrt_record(self._h))
+
+    def pfrt_steps(self):
+        n = C.c_int()
+        _check(self._lib.hipdrt_plan_pfrt_steps(self._h, C.byref(n)))
+        return n.value
+
+    def pfrt_step_state(self, step):
+        """what step `step` recorded -> dict(x (B, n), rho (B, 3), s_vectors (B, 3, n), rss (B,), sum_log_w (B,), status (B,))"""
+        B, n = self.B, self.n
+        out = dict(x=np.empty((B, n)), rho=np.empty((B, 3)), s_vectors=np.empty((B, 3, n)), rss=np.empty(B), sum_log_w=np.empty(B),
+                   status=np.empty(B, dtype=np.int32))
+        _check(self._lib.hipdrt_plan_pfrt_get_step(self._h, int(step), _p(out["x"]), _p(out["rho"]), _p(out["s_vectors"]),
+                                                   _p(out["rss"]), _p(out["sum_log_w"]), _pi(out["status"])))
+        return out
+
+    def step_p_matrix(self, step, b=0):
+        """pfrt_result['step_p_mat'][step] of spectrum b (hipdrt_plan_get_step_p_matrix)"""
+        out = np.empty((self.n, self.n))
+        _check(self._lib.hipdrt_plan_get_step_p_matrix(self._h, int(step), int(b), _p(out)))
+        return out
+
+    def predict_pfrt(self, factors, ln_tau_pfrt, ln_tau_out=None, opts: PfrtOpts | None = None, want=None):
+        """hipdrt_plan_predict_pfrt over the recorded steps -> dict(pfrt (B, nout), raw_pfrt (B, np), step_pfrt (S, B, np),
+        post_prob (S, B), status (B,)); want: the names to form and download (None: all); status always comes"""
+        fac, ltp = _f64(factors).ravel(), _f64(ln_tau_pfrt).ravel()
+        lto = None if ln_tau_out is None else _f64(ln_tau_out).ravel()
+        S, B, npf = fac.size, self.B, ltp.size
+        if S != self.pfrt_steps():
+            raise ValueError(f"factors has {S} entries, the plan has recorded {self.pfrt_steps()} PFRT steps")
+        nout = npf if lto is None else lto.size
+        opts = opts if opts is not None else pfrt_opts()
+        shapes = dict(pfrt=(B, nout), raw_pfrt=(B, npf), step_pfrt=(S, B, npf), post_prob=(S, B))
+        out = {k: np.full(shape, 7e77) for k, shape in shapes.items() if want is None or k in want}
+        out["status"] = np.empty(B, dtype=np.int32)
+        g = out.get
+        _check(self._lib.hipdrt_plan_predict_pfrt(self._h, _p(fac), _p(ltp), npf, _p(lto), nout, C.byref(opts), _p(g("pfrt")),
+                                                  _p(g("raw_pfrt")), _p(g("step_pfrt")), _p(g("post_prob")), _pi(out["status"])))
+        return out
 
     def set_init_h(self, h_init):
         h = None if h_init is None else _f64(h_init)

@@ -239,7 +239,9 @@ void launch_scale_weights(hipStream_t s, const FitState& st, int B, double facto
 void launch_scale_rows(hipStream_t s, int B, int m, const double* w, const double* rows, int batched, double factor,
                        const int* active, double* out);
 void launch_copy_column(hipStream_t s, int B, int m, const double* rm, long long rm_stride, int ldrm, int col, double* out);
-int launch_llh(hipStream_t s, const FitState& st, int B, double* rss, double* slw, int stored = 0, double scalar_w = 1.0);
+// w_out ([B][m] or null): the weights the sums were formed with
+int launch_llh(hipStream_t s, const FitState& st, int B, double* rss, double* slw, int stored = 0, double scalar_w = 1.0,
+               double* w_out = nullptr);
 void launch_assemble_rm(hipStream_t s, const FitState& st, const double* a_re, const double* a_im, const double* freq,
                         double* rm, int idx_rinf, int idx_induc);
 void launch_special_penalty(hipStream_t s, double* m0, double* m1, double* m2, int ld, int idx_rinf, int idx_induc,
@@ -342,6 +344,46 @@ int launch_peak_resolve(hipStream_t s, PeakResolveArgs a, int B);
 // out[b][k] = trapezoid of mu[b][start_k : end_k] over ln_tau (windows clipped to the grid)
 void launch_window_trapz(hipStream_t s, int B, int n, int nwin, const double* mu, const double* lt, const int* win_start,
                          const int* win_end, double* out);
+
+// pfrt.hip: the probability function of relaxation times on evaluated rows, one workgroup per spectrum (all pointers device memory)
+struct PfrtStepArgs {
+    int neval;
+    double floor;                        // lower bound of both variances (<= 0: none)
+    int ext_left, ext_right;             // extend_var's clamp indices, -1 = off
+    const int* peak_sign;                // [B][neval] of peaks_kernel (method 0)
+    const double *heights, *prominences; // [B][neval] of peaks_kernel
+    const double* f;                     // [B][neval]
+    const double *var_f, *var_fxx;       // [B][ldv] e' inv(P) e, scaled by cs^2 / norm^2 as they are read
+    long long ldv;
+    const double *cs, *norm;             // [B] or null (1)
+    const int *fit_status, *var_status;  // [B] or null: a negative fit status / a non-zero variance status gives a NaN row
+    double* out;                         // [B][neval]
+    int* bad;                            // [B] or null: set to 1 where var_status is non-zero
+};
+int launch_pfrt_step(hipStream_t s, const PfrtStepArgs& a, int B);
+struct PfrtCombineArgs {
+    int S, np, nout;                     // steps, points of tau_pfrt, points of the output grid (== np without smoothing)
+    long long ld_step, ld_sum;           // doubles between consecutive steps of step_pfrt (B * np) and of rss / slw
+    const double* step_pfrt;             // [S][B][np]
+    const double *rss, *slw;             // [S][ld_sum] the two likelihood sums of every step (launch_llh, stored = 0)
+    const double* ln_factors;            // [S]
+    double c, alpha_n, beta_0;           // llh = (c - alpha_n ln(beta_0 + rss / 2)) + slw
+    double prior_mu, prior_sigma, n_eff;
+    int smooth;
+    double smooth_order, smooth_eps;
+    int integrate;
+    double thr;
+    int normalize;
+    const double *ltp, *lto;             // ln(tau_pfrt) [np], ln(tau_out) [nout] (read with smooth only)
+    const int *fit_status, *bad;         // [B] or null: a negative status / a non-zero flag gives NaN rows
+    double *pfrt, *raw, *post;           // [B][nout], [B][np], [S][B]; any may be null
+};
+size_t pfrt_combine_lds_bytes(int S, int np, int nout);
+// every check of hipdrt_plan_predict_pfrt's options and grids (HIPDRT_E_INVALID: more than 2048 points on a grid, ...)
+int pfrt_check(const hipdrt_pfrt_opts& o, int S, int np, int nout);
+int launch_pfrt_combine(hipStream_t s, const PfrtCombineArgs& a, int B);
+// c, alpha_n and beta_0 of PfrtCombineArgs for m data rows (evaluate_llh's defaults alpha_0 = 2, beta_0 = 1)
+void pfrt_llh_consts(int m, double* c, double* alpha_n, double* beta_0);
 
 // qp.hip
 struct QpArgs {

@@ -407,6 +407,73 @@ int hipdrt_debug_find_peaks(hipdrt_ctx* ctx, int B, int neval, const double* fxx
     return HIPDRT_OK;
 } HIPDRT_CATCH
 
+// test hooks (include/hipdrt_debug.h): the two kernels of pfrt.hip as they are, on host arrays; outputs between borders of marker bytes
+int hipdrt_debug_pfrt_step(hipdrt_ctx* ctx, int B, int neval, const int* peak_sign, const double* heights, const double* prominences,
+                           const double* f, const double* var_f, const double* var_fxx, double var_floor, int ext_left,
+                           int ext_right, double* out) try {
+    HIPDRT_REQUIRE(ctx && peak_sign && heights && prominences && f && var_f && var_fxx && out, "NULL pointer");
+    HIPDRT_REQUIRE(B >= 1 && B <= 65535 && neval >= 1 && neval <= (1 << 20), "1 <= B <= 65535, 1 <= neval <= 2^20");
+    const size_t bn = (size_t)B * neval;
+    hipStream_t st; TRY(enter(ctx, &st));
+    DevBuf dsg, din[5];
+    const double* rows[5] = {heights, prominences, f, var_f, var_fxx};
+    TRY(upload(dsg, peak_sign, bn * sizeof(int), st));
+    for (int k = 0; k < 5; ++k) TRY(upload(din[k], rows[k], bn * sizeof(double), st));
+    Guarded g;
+    TRY(g.up("out", out, bn * sizeof(double), st));
+    PfrtStepArgs a{};
+    a.neval = neval; a.floor = var_floor; a.ext_left = ext_left; a.ext_right = ext_right; a.peak_sign = dsg.i();
+    a.heights = din[0].d(); a.prominences = din[1].d(); a.f = din[2].d(); a.var_f = din[3].d(); a.var_fxx = din[4].d();
+    a.ldv = neval; a.out = g.dd();
+    TRY(launch_pfrt_step(st, a, B));
+    LAUNCH_OK();
+    TRY(g.fetch(st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    return g.check();
+} HIPDRT_CATCH
+
+int hipdrt_debug_pfrt_combine(hipdrt_ctx* ctx, int B, int S, int neval_pfrt, int neval_out, const double* step_pfrt,
+                              const double* rss, const double* sum_log_w, const double* factors, int m,
+                              const hipdrt_pfrt_opts* opts, const double* ln_tau_pfrt, const double* ln_tau_out, double* pfrt,
+                              double* raw_pfrt, double* post_prob) try {
+    HIPDRT_REQUIRE(ctx && step_pfrt && rss && sum_log_w && factors && ln_tau_pfrt, "NULL pointer");
+    HIPDRT_REQUIRE(B >= 1 && B <= 65535 && m >= 1, "1 <= B <= 65535, m >= 1");
+    hipdrt_pfrt_opts o;
+    if (opts) o = *opts; else hipdrt_pfrt_opts_default(&o);
+    // every check comes before the first launch (and the first upload)
+    TRY(pfrt_check(o, S, neval_pfrt, neval_out));
+    HIPDRT_REQUIRE(!o.smooth || ln_tau_out, "smoothing needs the output grid");
+    for (int i = 0; i < S; ++i) HIPDRT_REQUIRE(factors[i] > 0.0 && std::isfinite(factors[i]), "factors must be positive and finite");
+    const int np = neval_pfrt, nout = neval_out;
+    std::vector<double> lnf(S);
+    for (int i = 0; i < S; ++i) lnf[i] = std::log(factors[i]);
+    hipStream_t st; TRY(enter(ctx, &st));
+    DevBuf dstep, drss, dslw, dlnf, dltp, dlto;
+    TRY(upload(dstep, step_pfrt, (size_t)S * B * np * sizeof(double), st));
+    TRY(upload(drss, rss, (size_t)S * B * sizeof(double), st)); TRY(upload(dslw, sum_log_w, (size_t)S * B * sizeof(double), st));
+    TRY(upload(dlnf, lnf.data(), (size_t)S * sizeof(double), st));
+    TRY(upload(dltp, ln_tau_pfrt, (size_t)np * sizeof(double), st));
+    if (o.smooth) TRY(upload(dlto, ln_tau_out, (size_t)nout * sizeof(double), st));
+    PfrtCombineArgs a{};
+    a.S = S; a.np = np; a.nout = nout; a.ld_step = (long long)B * np; a.ld_sum = B;
+    a.step_pfrt = dstep.d(); a.rss = drss.d(); a.slw = dslw.d(); a.ln_factors = dlnf.d();
+    pfrt_llh_consts(m, &a.c, &a.alpha_n, &a.beta_0);
+    a.prior_mu = o.prior_mu; a.prior_sigma = o.prior_sigma; a.n_eff = o.n_eff_factor;
+    a.smooth = o.smooth != 0; a.smooth_order = o.smooth_order; a.smooth_eps = o.smooth_epsilon;
+    a.integrate = o.integrate != 0; a.thr = o.integrate_threshold; a.normalize = o.normalize != 0;
+    a.ltp = dltp.d(); a.lto = dlto.d();
+    Guarded g[3];
+    if (pfrt) { TRY(g[0].up("pfrt", pfrt, (size_t)B * nout * sizeof(double), st)); a.pfrt = g[0].dd(); }
+    if (raw_pfrt) { TRY(g[1].up("raw_pfrt", raw_pfrt, (size_t)B * np * sizeof(double), st)); a.raw = g[1].dd(); }
+    if (post_prob) { TRY(g[2].up("post_prob", post_prob, (size_t)S * B * sizeof(double), st)); a.post = g[2].dd(); }
+    TRY(launch_pfrt_combine(st, a, B));
+    LAUNCH_OK();
+    for (Guarded& q : g) if (q.buf.p) TRY(q.fetch(st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    for (Guarded& q : g) if (q.buf.p) TRY(q.check());
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
 // test hook (include/hipdrt_debug.h): peak_resolve_kernel as it is, on host arrays.  Every output sits between two borders of marker bytes.
 int hipdrt_debug_peak_resolve(hipdrt_ctx* ctx, const hipdrt_debug_peak_resolve_args* q) try {
     HIPDRT_REQUIRE(ctx && q && q->f && q->fxx && q->x && q->ln_tau_find && q->ln_basis, "NULL pointer");

@@ -922,8 +922,9 @@ int launch_init_weights(hipStream_t s, const FitState& st, int B, int stage, int
 // stored = 2: weights='uniform' (drt1d.py:4436-4441, 4465-4470): within each domain -- chrono rows [0, num_chrono), impedance
 // rows after them -- every weight is the mean of that domain's est_weights, which is what DRTMD.fit_observation records per
 // observation with its default llh_kw / rss_kw (drtmd.py:129-131, 259-260); stored = 3: one scalar weight for every row.
+// w_out (may be null): the weights themselves, [B][m] -- the raw re-estimate of a PFRT step's P matrix (drt1d.py:2619-2630).
 __global__ __launch_bounds__(HT) void llh_kernel(FitState st, double* __restrict__ rss, double* __restrict__ slw, int stored,
-                                                 double scalar_w) {
+                                                 double scalar_w, double* __restrict__ w_out) {
     extern __shared__ double sm[];
     __shared__ double red[HNW];
     const int b = blockIdx.x, tid = threadIdx.x, n = st.n, m = st.m;
@@ -965,6 +966,7 @@ __global__ __launch_bounds__(HT) void llh_kernel(FitState st, double* __restrict
             if (v < vf) v = vf;
             w = fmax(1.0 / sqrt(v), 1e-10);
         }
+        if (w_out) w_out[(size_t)b * m + i] = w;
         const double wy = w * yh[i], wr = w * rv[i];
         a += wy * wy; c2 += wr * wy; d += wr * wr; lw += log(w);
     }
@@ -972,10 +974,10 @@ __global__ __launch_bounds__(HT) void llh_kernel(FitState st, double* __restrict
     if (tid == 0) { rss[b] = a - 2.0 * c2 + d; slw[b] = lw; }
 }
 
-int launch_llh(hipStream_t s, const FitState& st, int B, double* rss, double* slw, int stored, double scalar_w) {
+int launch_llh(hipStream_t s, const FitState& st, int B, double* rss, double* slw, int stored, double scalar_w, double* w_out) {
     const size_t lds = (size_t)(st.n + 3 * st.m) * sizeof(double);
     if (int rc = set_lds(reinterpret_cast<const void*>(llh_kernel), lds, "llh_kernel")) return rc;
-    hipLaunchKernelGGL(llh_kernel, dim3(B), dim3(HT), lds, s, st, rss, slw, stored, scalar_w);
+    hipLaunchKernelGGL(llh_kernel, dim3(B), dim3(HT), lds, s, st, rss, slw, stored, scalar_w, w_out);
     return 0;
 }
 

@@ -1,0 +1,239 @@
+// The probability function of relaxation times of a fitted batch, DRT.predict_pfrt (hybdrt/models/drt1d.py:2716-2858), on rows
+// that are already evaluated; hipdrt/models/pfrt.py is the same arithmetic in numpy.
+//
+//   pfrt_step_kernel      one regularisation step: at every peak that peaks_kernel (method 0, explicit height and prominence)
+//                         found, the credibility min(P(|f| > 0), P(curvature peak)) with both two-sided probabilities
+//                         1 - erfc(mu / (sigma sqrt 2)) (drt1d.py:2811-2829); sigma^2 is e' inv(P) e scaled as drt_band_kernel
+//                         scales it, then extend_var's clamp and the floor -- on BOTH variance rows (2772-2786)
+//   pfrt_combine_kernel   the posterior weights of the steps (2730-2749), the weighted sum (2831-2834), the smoothing matrix
+//                         (2840-2848, formed on the fly), the contiguous-range integration (hybdrt/models/pfrt.py:22-46) and the
+//                         normalisation by the row's maximum
+//
+// One 256-thread workgroup per spectrum.  Every sum runs in one fixed order (over the steps ascending, over the grid ascending), so
+// a spectrum's result depends neither on B nor on its position.  Each kernel's global stores are its dense output rows (offset
+// b * n + i with i < n) and one scalar per spectrum.  Compiled with -ffp-contract=off: the probabilities round as written.
+#include <cmath>
+
+#include "hyper_dev.hpp"
+
+namespace hipdrt {
+
+static constexpr int FT = 256;
+static constexpr double PF_SQRT2 = 1.4142135623730951;      // 2 ** 0.5
+static constexpr double PF_LOG_2PI = 1.8378770664093453;    // np.log(2 * np.pi)
+
+// numpy's maximum and minimum (NaN goes through)
+__device__ __forceinline__ double pf_max(double a, double c) { return (a != a) ? a : ((c != c) ? c : (a > c ? a : c)); }
+__device__ __forceinline__ double pf_min(double a, double c) { return (a != a) ? a : ((c != c) ? c : (a < c ? a : c)); }
+
+// grid = B
+__global__ __launch_bounds__(FT) void pfrt_step_kernel(PfrtStepArgs a) {
+    const int b = blockIdx.x, tid = threadIdx.x, n = a.neval;
+    const size_t row = (size_t)b * n;
+    const bool no_var = a.var_status && a.var_status[b] != 0;
+    if ((a.fit_status && a.fit_status[b] < 0) || no_var) {     // a failed fit, or a step P that is not positive definite
+        for (int i = tid; i < n; i += FT) a.out[row + i] = NAN;
+        if (tid == 0 && a.bad && no_var) a.bad[b] = 1;
+        return;
+    }
+    double c2 = 1.0, n2 = 1.0;
+    if (a.cs) c2 = a.cs[b] * a.cs[b];
+    if (a.norm) n2 = a.norm[b] * a.norm[b];
+    auto scaled = [&](const double* var, int i) {
+        double v = var[(size_t)b * a.ldv + i];
+        if (a.cs) v = v * c2;
+        if (a.norm) v = v / n2;
+        return v;
+    };
+    // extend_var's bounds (drt1d.py:3136-3139: the left part first, so the right bound may already be a clamped value)
+    const int li = a.ext_left, ri = a.ext_right;
+    double vl[2] = {0.0, 0.0}, vr[2] = {0.0, 0.0};
+    for (int k = 0; k < 2; ++k) {
+        const double* var = k ? a.var_fxx : a.var_f;
+        if (li >= 0) vl[k] = scaled(var, li);
+        if (ri >= 0) vr[k] = scaled(var, ri);
+        if (li >= 0 && ri >= 0 && ri < li) vr[k] = pf_max(vr[k], vl[k]);
+    }
+    for (int i = tid; i < n; i += FT) {
+        double p = 0.0;
+        if (a.peak_sign[row + i] != 0) {
+            double v[2];
+            for (int k = 0; k < 2; ++k) {
+                double x = scaled(k ? a.var_fxx : a.var_f, i);
+                if (li >= 0 && i < li) x = pf_max(x, vl[k]);
+                if (ri >= 0 && i >= ri) x = pf_max(x, vr[k]);
+                if (a.floor > 0.0 && x < a.floor) x = a.floor;
+                v[k] = x;
+            }
+            const double mp = pf_min(a.prominences[row + i], a.heights[row + i]);
+            const double f_prob = 1.0 - erfc(fabs(a.f[row + i]) / (sqrt(v[0]) * PF_SQRT2));
+            const double fxx_prob = 1.0 - erfc(mp / (sqrt(v[1]) * PF_SQRT2));
+            p = pf_min(f_prob, fxx_prob);
+        }
+        a.out[row + i] = p;
+    }
+}
+
+int launch_pfrt_step(hipStream_t s, const PfrtStepArgs& a, int B) {
+    HIPDRT_REQUIRE(B >= 1 && a.neval >= 1, "pfrt_step: B, neval >= 1");
+    HIPDRT_REQUIRE(a.peak_sign && a.heights && a.prominences && a.f && a.var_f && a.var_fxx && a.out, "pfrt_step: NULL row");
+    HIPDRT_REQUIRE(std::isfinite(a.floor), "fxx_var_floor must be finite");
+    HIPDRT_REQUIRE(a.ext_left >= -1 && a.ext_left < a.neval && a.ext_right >= -1 && a.ext_right < a.neval,
+                   "ext_left and ext_right: an index of the evaluation grid, or -1");
+    hipLaunchKernelGGL(pfrt_step_kernel, dim3(B), dim3(FT), 0, s, a);
+    return HIPDRT_OK;
+}
+
+// LDS of pfrt_combine_kernel: the accumulator and ln(tau_pfrt) [np], ln(tau_out), the smoothed row and the integrated row [nout],
+// the steps' posterior weights [S]
+size_t pfrt_combine_lds_bytes(int S, int np, int nout) { return ((size_t)2 * np + (size_t)3 * nout + (size_t)S) * sizeof(double); }
+
+// grid = B
+__global__ __launch_bounds__(FT) void pfrt_combine_kernel(PfrtCombineArgs a) {
+    extern __shared__ double sm[];
+    __shared__ double red[FT];
+    const int b = blockIdx.x, B = gridDim.x, tid = threadIdx.x, S = a.S, np = a.np, nout = a.nout;
+    double* acc = sm;
+    double* ltp = acc + np;
+    double* lto = ltp + np;
+    double* v = lto + nout;
+    double* res = v + nout;
+    double* post = res + nout;
+
+    if ((a.fit_status && a.fit_status[b] < 0) || (a.bad && a.bad[b] != 0)) {
+        for (int k = tid; k < nout; k += FT) if (a.pfrt) a.pfrt[(size_t)b * nout + k] = NAN;
+        for (int j = tid; j < np; j += FT) if (a.raw) a.raw[(size_t)b * np + j] = NAN;
+        for (int i = tid; i < S; i += FT) if (a.post) a.post[(size_t)i * B + b] = NAN;
+        return;
+    }
+    for (int j = tid; j < np; j += FT) ltp[j] = a.ltp[j];
+    for (int k = tid; k < nout; k += FT) lto[k] = a.smooth ? a.lto[k] : 0.0;
+
+    // ---- posterior weights of the steps (drt1d.py:2730-2749) ----
+    for (int i = tid; i < S; i += FT) {
+        const size_t o = (size_t)i * a.ld_sum + b;
+        const double llh = (a.c - a.alpha_n * log(a.beta_0 + 0.5 * a.rss[o])) + a.slw[o];
+        const double z = (a.ln_factors[i] - a.prior_mu) / a.prior_sigma;
+        post[i] = -0.5 * (PF_LOG_2PI + 2.0 * log(a.prior_sigma) + z * z) + llh;
+    }
+    __syncthreads();
+    double mx = post[0];
+    for (int i = 1; i < S; ++i) mx = pf_max(mx, post[i]);
+    __syncthreads();
+    for (int i = tid; i < S; i += FT) post[i] = exp((post[i] - mx) * a.n_eff);
+    __syncthreads();
+    double area = post[0];
+    if (S > 1) {
+        area = 0.0;
+        for (int i = 0; i + 1 < S; ++i) area += ((a.ln_factors[i + 1] - a.ln_factors[i]) * (post[i + 1] + post[i])) / 2.0;
+    }
+    __syncthreads();
+    for (int i = tid; i < S; i += FT) post[i] = post[i] / area;
+    __syncthreads();
+    double psum = 0.0;
+    for (int i = 0; i < S; ++i) psum += post[i];
+
+    // ---- the weighted sum over the steps, ascending ----
+    for (int j = tid; j < np; j += FT) {
+        double t = 0.0;
+        for (int i = 0; i < S; ++i) t += post[i] * a.step_pfrt[(size_t)i * a.ld_step + (size_t)b * np + j];
+        acc[j] = t / psum;
+    }
+    __syncthreads();
+
+    // ---- smoothing: row k of exp(-(eps |ln tau_out_k - ln tau_pfrt_j|)^(2 order)) times the accumulator (zeros add nothing) ----
+    if (a.smooth) {
+        const double ex = 2.0 * a.smooth_order;
+        for (int k = tid; k < nout; k += FT) {
+            double t = 0.0;
+            for (int j = 0; j < np; ++j) {
+                const double r = acc[j];
+                if (r != 0.0) t += exp(-pow(a.smooth_eps * fabs(lto[k] - ltp[j]), ex)) * r;
+            }
+            v[k] = t;
+        }
+    } else {
+        for (int k = tid; k < nout; k += FT) v[k] = acc[k];
+    }
+    __syncthreads();
+
+    // ---- integrate_peaks (models/pfrt.py:22-46): every contiguous range of v >= threshold becomes one value at its maximum ----
+    if (a.integrate) {
+        const double thr = a.thr;
+        for (int k = tid; k < nout; k += FT) res[k] = 0.0;
+        __syncthreads();
+        for (int k = tid; k < nout; k += FT) {
+            if (!(v[k] >= thr) || (k > 0 && v[k - 1] >= thr)) continue;
+            int e = k, pk = k;
+            while (e < nout && v[e] >= thr) { if (v[e] > v[pk]) pk = e; ++e; }
+            // np.trapezoid(pf[start - 1:end + 1]): empty (or one sample) for a range that starts at index 0
+            double ar = 0.0;
+            if (k > 0) {
+                const int hi = e + 1 < nout ? e + 1 : nout;
+                for (int i = k - 1; i + 1 < hi; ++i) ar += (v[i + 1] + v[i]) / 2.0;
+            }
+            res[pk] = ar;
+        }
+        __syncthreads();
+        for (int k = tid; k < nout; k += FT) v[k] = res[k];
+        __syncthreads();
+    }
+
+    // ---- tot / np.max(tot): an all-zero row gives NaN, as upstream ----
+    if (a.normalize) {
+        double m = -INFINITY;
+        for (int k = tid; k < nout; k += FT) m = pf_max(m, v[k]);
+        red[tid] = m;
+        __syncthreads();
+        for (int w = FT / 2; w > 0; w >>= 1) {
+            if (tid < w) red[tid] = pf_max(red[tid], red[tid + w]);
+            __syncthreads();
+        }
+        m = red[0];
+        for (int k = tid; k < nout; k += FT) v[k] = v[k] / m;      // (every thread scales the entries it wrote or copied itself)
+    }
+
+    // ---- the dense rows: the only global stores ----
+    for (int k = tid; k < nout; k += FT) if (a.pfrt) a.pfrt[(size_t)b * nout + k] = v[k];
+    for (int j = tid; j < np; j += FT) if (a.raw) a.raw[(size_t)b * np + j] = acc[j];
+    for (int i = tid; i < S; i += FT) if (a.post) a.post[(size_t)i * B + b] = post[i];
+}
+
+// the constants of evaluate_llh(marginalize_weights=True, alpha_0=2, beta_0=1) for m data rows (drt1d.py:4457-4496):
+// llh = (c - alpha_n ln(beta_0 + rss / 2)) + sum(log w)
+void pfrt_llh_consts(int m, double* c, double* alpha_n, double* beta_0) {
+    const double a0 = 2.0, b0 = 1.0, an = a0 - 1.0 + 0.5 * (double)m;
+    *c = a0 * std::log(b0) + std::lgamma(an) - std::lgamma(a0);
+    *alpha_n = an; *beta_0 = b0;
+}
+
+int pfrt_check(const hipdrt_pfrt_opts& o, int S, int np, int nout) {
+    HIPDRT_REQUIRE(S >= 1 && S <= 1024, "1 <= steps <= 1024");
+    HIPDRT_REQUIRE(np >= 1 && nout >= 1, "neval_pfrt, neval_out >= 1");
+    HIPDRT_REQUIRE(np <= 2048 && nout <= 2048, "predict_pfrt: at most 2048 points on either grid");
+    HIPDRT_REQUIRE(o.smooth || nout == np, "without smoothing the PFRT stays on the tau_pfrt grid: neval_out == neval_pfrt");
+    HIPDRT_REQUIRE(o.search >= -1 && o.search <= 1, "search must be 1, -1 or 0 (two passes)");
+    HIPDRT_REQUIRE(std::isfinite(o.height) && std::isfinite(o.prominence), "height and prominence must be finite");
+    HIPDRT_REQUIRE(std::isfinite(o.prior_mu) && o.prior_sigma > 0.0 && std::isfinite(o.prior_sigma), "prior_mu finite, prior_sigma > 0");
+    HIPDRT_REQUIRE(std::isfinite(o.n_eff_factor), "n_eff_factor must be finite");
+    HIPDRT_REQUIRE(std::isfinite(o.fxx_var_floor), "fxx_var_floor must be finite");
+    HIPDRT_REQUIRE(o.ext_left >= -1 && o.ext_left < np && o.ext_right >= -1 && o.ext_right < np,
+                   "ext_left and ext_right: an index of the tau_pfrt grid, or -1");
+    HIPDRT_REQUIRE(!o.smooth || (o.smooth_order > 0.0 && std::isfinite(o.smooth_order) && o.smooth_epsilon > 0.0 &&
+                                 std::isfinite(o.smooth_epsilon)), "smooth_order, smooth_epsilon > 0");
+    HIPDRT_REQUIRE(!o.integrate || std::isfinite(o.integrate_threshold), "integrate_threshold must be finite");
+    return HIPDRT_OK;
+}
+
+int launch_pfrt_combine(hipStream_t s, const PfrtCombineArgs& a, int B) {
+    HIPDRT_REQUIRE(B >= 1 && a.S >= 1 && a.S <= 1024, "pfrt_combine: B >= 1, 1 <= steps <= 1024");
+    HIPDRT_REQUIRE(a.np >= 1 && a.nout >= 1 && a.np <= 2048 && a.nout <= 2048, "pfrt_combine: 1 ... 2048 points on either grid");
+    HIPDRT_REQUIRE(a.smooth || a.nout == a.np, "pfrt_combine: without smoothing neval_out == neval_pfrt");
+    HIPDRT_REQUIRE(a.step_pfrt && a.rss && a.slw && a.ln_factors && a.ltp && (a.lto || !a.smooth), "pfrt_combine: NULL input");
+    const size_t lds = pfrt_combine_lds_bytes(a.S, a.np, a.nout);
+    if (int rc = set_lds(reinterpret_cast<const void*>(pfrt_combine_kernel), lds, "pfrt_combine_kernel")) return rc;
+    hipLaunchKernelGGL(pfrt_combine_kernel, dim3(B), dim3(FT), lds, s, a);
+    return HIPDRT_OK;
+}
+
+}  // namespace hipdrt

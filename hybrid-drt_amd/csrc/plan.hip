@@ -324,6 +324,7 @@ int hipdrt_plan_upload_prepared(hipdrt_plan* p, int B, int rm_batched, const dou
     p->rm_stride = rm_batched ? (long long)m * p->ldrm : 0;
     p->B = B;
     p->prepped = 0;
+    p->pf_steps = 0;            // (recorded PFRT steps belong to the batch they were fitted on)
     return HIPDRT_OK;
 } HIPDRT_CATCH
 
@@ -425,6 +426,7 @@ int hipdrt_plan_upload(hipdrt_plan* p, int B, const double* z_re, const double* 
     HIPDRT_CHECK(hipMemcpyAsync(p->z_im.p, z_im, bytes, hipMemcpyHostToDevice, st));
     HIPDRT_CHECK(hipStreamSynchronize(st));
     p->B = B;
+    p->pf_steps = 0;            // (recorded PFRT steps belong to the batch they were fitted on)
     return HIPDRT_OK;
 } HIPDRT_CATCH
 

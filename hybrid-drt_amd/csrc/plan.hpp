@@ -8,6 +8,7 @@
 #include <stdexcept>
 
 #include "common.hpp"
+#include "pfrt_store.hpp"
 
 using namespace hipdrt;
 
@@ -131,6 +132,12 @@ struct hipdrt_plan : PlanShape {
     // history
     int hist_b = -1, hist_cap = 0;
     DevBuf hist_x, hist_w, hist_rho, hist_qp, hist_rows;
+    // PFRT step store (hipdrt_plan_pfrt_begin / _record): the state every step of a PFRT fit ended with, sized for the plan's capacity
+    // -- x [S][capacity][n], rho and dop_rho [S][capacity][3], s [S][capacity][3][n], the two likelihood sums and the fit status
+    // [S][capacity] -- and how many steps are in it
+    int pf_max = 0, pf_steps = 0;
+    DevBuf pf_x, pf_rho, pf_dop_rho, pf_s, pf_rss, pf_slw, pf_status;
+    hipdrt::PfrtStoreLayout pf_layout() const { return {(size_t)capacity, (size_t)n}; }
     // timings of the last fit
     float t_ms[5] = {0, 0, 0, 0, 0};
     int launches[5] = {0, 0, 0, 0, 0};

@@ -484,4 +484,71 @@ int hipdrt_plan_iterate(hipdrt_plan* p, const hipdrt_iterate_state* in, int* con
     return HIPDRT_OK;
 } HIPDRT_CATCH
 
+// ---- PFRT step store (include/hipdrt.h) ---------------------------------------------------------------------------------------
+int hipdrt_plan_pfrt_bytes_per_spectrum(int n, int steps, long long* bytes) try {
+    HIPDRT_REQUIRE(bytes && n >= 1 && steps >= 1, "n, steps >= 1");
+    *bytes = pfrt_store_bytes_per_spectrum(n, steps);
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+int hipdrt_plan_pfrt_begin(hipdrt_plan* p, int max_steps) try {
+    HIPDRT_REQUIRE(p, "plan is NULL");
+    HIPDRT_REQUIRE(max_steps >= 1 && max_steps <= 1024, "1 <= max_steps <= 1024");
+    TRY(enter(p->ctx));
+    p->pf_steps = 0;
+    if (max_steps <= p->pf_max) return HIPDRT_OK;
+    const PfrtStoreLayout L = p->pf_layout();
+    const size_t D = sizeof(double);
+    const bool dop = p->prepared && p->desc.dop_size > 0;
+    struct { DevBuf* buf; size_t bytes; } want[] = {
+        {&p->pf_x, L.x_elems(max_steps) * D}, {&p->pf_rho, L.rho_elems(max_steps) * D}, {&p->pf_s, L.s_elems(max_steps) * D},
+        {&p->pf_rss, L.scalar_elems(max_steps) * D}, {&p->pf_slw, L.scalar_elems(max_steps) * D},
+        {&p->pf_status, L.scalar_elems(max_steps) * sizeof(int)}, {&p->pf_dop_rho, dop ? L.rho_elems(max_steps) * D : 0}};
+    p->pf_max = 0;
+    for (auto& w : want) {
+        if (w.bytes == 0) continue;
+        const hipError_t e = w.buf->alloc(w.bytes);
+        if (e != hipSuccess) {
+            // the plan itself is untouched: the store is simply empty again
+            for (auto& v : want) v.buf->release();
+            (void)hipGetLastError();
+            set_error(std::string("PFRT step store: ") + hipGetErrorString(e));
+            return HIPDRT_E_HIP;
+        }
+    }
+    p->pf_max = max_steps;
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+int hipdrt_plan_pfrt_record(hipdrt_plan* p) try {
+    HIPDRT_REQUIRE(p, "plan is NULL");
+    HIPDRT_REQUIRE(p->B >= 1 && p->prepped, "no fitted batch in the plan");
+    HIPDRT_REQUIRE(p->pf_max >= 1, "hipdrt_plan_pfrt_begin has not been called");
+    HIPDRT_REQUIRE(p->pf_steps < p->pf_max, "the PFRT step store is full");
+    // (hipdrt_plan_fit and hipdrt_plan_continue return with every range joined and the plan's stream idle)
+    hipStream_t st; TRY(enter(p->ctx, &st));
+    const PfrtStoreLayout L = p->pf_layout();
+    const size_t B = (size_t)p->B, n = (size_t)p->n, D = sizeof(double);
+    const int step = p->pf_steps;
+    const auto d2d = [&](DevBuf& dst, size_t off, const DevBuf& src, size_t bytes) {
+        return hipMemcpyAsync(static_cast<char*>(dst.p) + off, src.p, bytes, hipMemcpyDeviceToDevice, st);
+    };
+    HIPDRT_CHECK(d2d(p->pf_x, L.x(step) * D, p->x, B * n * D));
+    HIPDRT_CHECK(d2d(p->pf_rho, L.rho(step) * D, p->rho, B * 3 * D));
+    HIPDRT_CHECK(d2d(p->pf_s, L.s(step) * D, p->s, B * 3 * n * D));
+    HIPDRT_CHECK(d2d(p->pf_status, L.scalar(step) * sizeof(int), p->fit_status, B * sizeof(int)));
+    if (p->pf_dop_rho.p) HIPDRT_CHECK(d2d(p->pf_dop_rho, L.rho(step) * D, p->dop_rho, B * 3 * D));
+    TRY(launch_llh(st, p->state(), p->B, p->pf_rss.d() + L.scalar(step), p->pf_slw.d() + L.scalar(step), 0));
+    LAUNCH_OK();
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    p->pf_steps += 1;
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+int hipdrt_plan_pfrt_steps(hipdrt_plan* p, int* steps) try {
+    HIPDRT_REQUIRE(p && steps, "NULL pointer");
+    *steps = p->pf_steps;
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
 }  // extern "C"

@@ -81,9 +81,22 @@ static int plan_llh_terms(hipdrt_plan* p, double* rss, double* sum_log_w, int st
 // calculate_pq's scaled_weights -- w_eff whenever the plan has weight factors.  b >= 0: s, rho, dop_rho and the weights of
 // spectrum b alone.
 struct FinalP { GramL2 g; const double* w; };
-static FinalP plan_final_p(const hipdrt_plan* p, int b) {
-    FinalP f{plan_l2(p, p->opts.l2_lambda_0, p->opts.derivative_weights, p->prepared ? p->desc.dop_l2_lambda_0 : 0.0),
-             p->has_weight_factors() ? p->w_eff.d() : p->w.d()};
+// Where a posterior computation reads the fitted state from: the plan's live buffers (what the last fit or warm restart left), or
+// one recorded step of the PFRT store with the raw re-estimated weights of that step (step_source).  All [B]-major with the
+// strides of the live buffers.
+struct PostSource { const double *x, *s, *rho, *dop_rho, *w; const int* fit_status; };
+static PostSource live_source(const hipdrt_plan* p) {
+    return {p->x.d(), p->s.d(), p->rho.d(), p->dop_rho.d(), p->has_weight_factors() ? p->w_eff.d() : p->w.d(), p->fit_status.i()};
+}
+static PostSource step_source(const hipdrt_plan* p, int step, const double* w, const int* fit_status) {
+    const PfrtStoreLayout L = p->pf_layout();
+    return {p->pf_x.d() + L.x(step), p->pf_s.d() + L.s(step), p->pf_rho.d() + L.rho(step),
+            p->pf_dop_rho.p ? p->pf_dop_rho.d() + L.rho(step) : nullptr, w, fit_status};
+}
+static FinalP plan_final_p(const hipdrt_plan* p, int b, const PostSource& src) {
+    FinalP f{plan_l2(p, p->opts.l2_lambda_0, p->opts.derivative_weights, p->prepared ? p->desc.dop_l2_lambda_0 : 0.0), src.w};
+    f.g.s = src.s; f.g.rho = src.rho;
+    if (f.g.dop_size > 0) f.g.dop_rho = src.dop_rho;
     if (b >= 0) {
         f.g.s += (size_t)b * 3 * p->n; f.g.rho += (size_t)b * 3;
         if (f.g.dop_size > 0) f.g.dop_rho += (size_t)b * 3;
@@ -97,7 +110,7 @@ int hipdrt_plan_get_p_matrix(hipdrt_plan* p, int b, double* out) try {
     HIPDRT_REQUIRE(b >= 0 && b < p->B, "spectrum index out of range");
     hipStream_t st; TRY(enter(p->ctx, &st));
     const int n = p->n, m = p->m;
-    const FinalP f = plan_final_p(p, b);
+    const FinalP f = plan_final_p(p, b, live_source(p));
     launch_gram_l2(st, 1, m, n, p->rm.d() + (size_t)b * p->rm_stride, p->ldrm, f.w, f.g, p->Ptmp.d(), p->ldp, 0, nullptr);
     LAUNCH_OK();
     return copy_strided(out, p->Ptmp.d(), n, n, p->ldp, st);
@@ -105,8 +118,8 @@ int hipdrt_plan_get_p_matrix(hipdrt_plan* p, int b, double* out) try {
 
 // rows_dev[neval][ncol] in device memory (it sits at columns col_offset.. of the unknown vector, zero elsewhere) ->
 // dout[B][nex * 16] = rows_i' P_b^-1 rows_i (not yet scaled by cs_b^2), dstat[B]
-static int plan_quadratic_forms_dev(hipdrt_plan* p, const double* rows_dev, int neval, int ncol, int col_offset, DevBuf& dout,
-                                    DevBuf& dstat) {
+static int plan_quadratic_forms_dev(hipdrt_plan* p, const PostSource& src, const double* rows_dev, int neval, int ncol,
+                                    int col_offset, DevBuf& dout, DevBuf& dstat) {
     HIPDRT_REQUIRE(p->B > 0, "no fitted batch in the plan");
     HIPDRT_REQUIRE(neval >= 1, "neval >= 1");
     HIPDRT_REQUIRE(p->n <= 4096, "posterior variance: n <= 4096");
@@ -114,7 +127,7 @@ static int plan_quadratic_forms_dev(hipdrt_plan* p, const double* rows_dev, int 
     const int n = p->n, m = p->m, B = p->B;
     const int nex = (neval + 15) / 16, nchp = qp_nchp(n);
     // final P of every spectrum, packed tiles only
-    const FinalP f = plan_final_p(p, -1);
+    const FinalP f = plan_final_p(p, -1, src);
     launch_gram_l2(st, B, m, n, p->rm.d(), p->ldrm, f.w, f.g, nullptr, p->ldp, 0, nullptr, p->Ppk.d(),
                    (long long)qp_ppk_doubles(n), nchp, p->rm_stride);
     LAUNCH_OK();
@@ -147,7 +160,7 @@ static int plan_quadratic_forms(hipdrt_plan* p, const double* basis_eval, int ne
     const int B = p->B, nex = (neval + 15) / 16;
     DevBuf dbe, dout, dstat;
     TRY(upload(dbe, basis_eval, (size_t)neval * ncol * sizeof(double), st));
-    TRY(plan_quadratic_forms_dev(p, dbe.d(), neval, ncol, col_offset, dout, dstat));
+    TRY(plan_quadratic_forms_dev(p, live_source(p), dbe.d(), neval, ncol, col_offset, dout, dstat));
     std::vector<double> hv((size_t)B * nex * 16), cs(B);
     std::vector<int> hs(B);
     HIPDRT_CHECK(hipMemcpyAsync(hv.data(), dout.p, hv.size() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -174,7 +187,7 @@ static int plan_full_cov(hipdrt_plan* p, int b, const double* rows, int neval, i
     const int n = p->n, m = p->m;
     const int nex = (neval + 15) / 16, nchp = qp_nchp(n), nch = round_up(n, 32) / 16;
     // final P of this spectrum, packed tiles, into its own slot of Ppk
-    const FinalP f = plan_final_p(p, b);
+    const FinalP f = plan_final_p(p, b, live_source(p));
     double* ppk = p->Ppk.d() + (size_t)b * qp_ppk_doubles(n);
     launch_gram_l2(st, 1, m, n, p->rm.d() + (size_t)b * p->rm_stride, p->ldrm, f.w, f.g, nullptr, p->ldp, 0, nullptr, ppk, 0,
                    nchp, 0);
@@ -341,14 +354,15 @@ struct DrtRows {
 };
 // orders[norders] (norders 1 or 2): rows k * neval .. of dE and slab k of dmu belong to orders[k].  dev: ln(tau_eval) on the
 // device.  row_scale: host [B] or null.  The timer is marked once, after the mean rows.
-static int plan_drt_rows_dev(hipdrt_plan* p, const PredictBasis& pb, int neval, const int* orders,
+// have_E: dE already holds the evaluation rows (a second call on the same grid, orders and sign).
+static int plan_drt_rows_dev(hipdrt_plan* p, const PostSource& src, const PredictBasis& pb, int neval, const int* orders,
                              int norders, int sign, int normalize, const double* row_scale, bool want_var, hipStream_t st,
-                             DevBuf& dev, DrtRows& R, PredictTimer& tm) {
+                             DevBuf& dev, DrtRows& R, PredictTimer& tm, bool have_E = false) {
     const int B = p->B, n = p->n, ns = p->ns, width = n - ns, nb = pb.nb;
     R.neval = neval; R.B = B; R.norders = norders;
     // E[neval][width]: the signed evaluation rows over the whole DRT block (+E | 0), (0 | -E) or (+E | -E)
-    if (pb.copies == 2 && sign != 0) HIPDRT_CHECK(hipMemsetAsync(R.dE.p, 0, R.dE.bytes, st));
-    for (int k = 0; k < norders; ++k) {
+    if (!have_E && pb.copies == 2 && sign != 0) HIPDRT_CHECK(hipMemsetAsync(R.dE.p, 0, R.dE.bytes, st));
+    for (int k = 0; k < norders && !have_E; ++k) {
         double* E = R.dE.d() + (size_t)k * neval * width;
         if (sign != -1) TRY(func_eval_dev(st, pb.ln_tau, nb, dev.d(), neval, pb.eps, orders[k], 1.0, E, width));
         if (pb.copies == 2 && sign != 1) TRY(func_eval_dev(st, pb.ln_tau, nb, dev.d(), neval, pb.eps, orders[k], -1.0, E + nb, width));
@@ -367,21 +381,21 @@ static int plan_drt_rows_dev(hipdrt_plan* p, const PredictBasis& pb, int neval, 
     if (normalize) {
         HIPDRT_CHECK(R.dsum.alloc((size_t)B * sizeof(double))); HIPDRT_CHECK(R.dabs.alloc((size_t)B * sizeof(double)));
         HIPDRT_CHECK(R.dnorm.alloc((size_t)B * sizeof(double))); HIPDRT_CHECK(R.dscale.alloc((size_t)B * sizeof(double)));
-        launch_drt_sums(st, B, p->x.d(), n, ns, nb, pb.copies, sign, R.dsum.d(), R.dabs.d());
+        launch_drt_sums(st, B, src.x, n, ns, nb, pb.copies, sign, R.dsum.d(), R.dabs.d());
         launch_drt_scalars(st, B, R.dsum.d(), R.dabs.d(), R.cs, 1.7724538509055159 / pb.eps, 1, normalize == 2,
-                           p->x.d(), n, -1, nullptr, nullptr, nullptr, R.dnorm.d(), R.dscale.d());
+                           src.x, n, -1, nullptr, nullptr, nullptr, R.dnorm.d(), R.dscale.d());
         LAUNCH_OK();
         R.scale = R.dscale.d();
         R.norm = R.dnorm.d();
     }
     for (int k = 0; k < norders; ++k) {
-        launch_apply_rows(st, B, width, p->x.d(), n, ns, neval, R.dE.d() + (size_t)k * neval * width, width, R.scale,
-                          p->fit_status.i(), R.mu(k), neval);
+        launch_apply_rows(st, B, width, src.x, n, ns, neval, R.dE.d() + (size_t)k * neval * width, width, R.scale,
+                          src.fit_status, R.mu(k), neval);
         LAUNCH_OK();
     }
     tm.mark();
     // sigma^2 = diag(E inv(P) E') from the variance path, fed the evaluation rows where they are (both orders as one row block)
-    if (want_var) TRY(plan_quadratic_forms_dev(p, R.dE.d(), norders * neval, width, ns, R.dvar, R.dvstat));
+    if (want_var) TRY(plan_quadratic_forms_dev(p, src, R.dE.d(), norders * neval, width, ns, R.dvar, R.dvstat));
     return HIPDRT_OK;
 }
 
@@ -405,7 +419,7 @@ int hipdrt_plan_predict_drt(hipdrt_plan* p, const double* ln_tau_eval, int neval
     HIPDRT_CHECK(R.dE.alloc((size_t)neval * width * sizeof(double)));
     HIPDRT_CHECK(R.dmu.alloc((size_t)B * neval * sizeof(double)));
     PredictTimer tm(p->ctx, st);
-    TRY(plan_drt_rows_dev(p, pb, neval, &order, 1, sign, normalize, nullptr, band, st, dev, R, tm));
+    TRY(plan_drt_rows_dev(p, live_source(p), pb, neval, &order, 1, sign, normalize, nullptr, band, st, dev, R, tm));
     std::vector<int> hs(B), hv;
     if (band) {
         if (lo) HIPDRT_CHECK(dlo.alloc((size_t)B * neval * sizeof(double)));
@@ -480,7 +494,7 @@ int hipdrt_plan_find_peaks(hipdrt_plan* p, const double* ln_tau_eval, int neval,
     if (peak_prob && o.method == 2) { HIPDRT_CHECK(dpp.alloc(bn * sizeof(double))); a.peak_prob = dpp.d(); }
     if (curv_prob && o.method == 2) { HIPDRT_CHECK(dcp.alloc(bn * sizeof(double))); a.curv_prob = dcp.d(); }
     PredictTimer tm(p->ctx, st);
-    TRY(plan_drt_rows_dev(p, pb, neval, orders, norders, sign, normalize, row_scale, need_var, st, dev, R, tm));
+    TRY(plan_drt_rows_dev(p, live_source(p), pb, neval, orders, norders, sign, normalize, row_scale, need_var, st, dev, R, tm));
     a.fxx = R.mu(0);
     a.f = need_f ? R.mu(1) : nullptr;
     if (need_var) {
@@ -585,7 +599,7 @@ int hipdrt_plan_resolve_peaks(hipdrt_plan* p, const hipdrt_peak_resolve_in* in, 
     if (out->x_peaks) { HIPDRT_CHECK(dxp.alloc(bm * pb.nb * sizeof(double))); a.x_peaks = dxp.d(); }
     if (out->peak_gammas) { HIPDRT_CHECK(dpg.alloc(bm * nout * sizeof(double))); a.peak_gammas = dpg.d(); }
     PredictTimer tm(p->ctx, st);
-    TRY(plan_drt_rows_dev(p, pb, nfind, orders, 2, o.sign, normalize, row_scale, need_var, st, dev, R, tm));
+    TRY(plan_drt_rows_dev(p, live_source(p), pb, nfind, orders, 2, o.sign, normalize, row_scale, need_var, st, dev, R, tm));
     a.fxx = R.mu(0); a.f = R.mu(1);
     if (find) {
         HIPDRT_CHECK(dkeep.alloc((size_t)B * nfind * sizeof(int)));
@@ -665,7 +679,7 @@ int hipdrt_plan_integrate_drt(hipdrt_plan* p, const double* ln_tau_eval, int nev
     HIPDRT_CHECK(R.dmu.alloc((size_t)B * neval * sizeof(double)));
     HIPDRT_CHECK(dres.alloc((size_t)B * nwin * sizeof(double)));
     PredictTimer tm(p->ctx, st);
-    TRY(plan_drt_rows_dev(p, pb, neval, &order, 1, sign, normalize, row_scale, false, st, dev, R, tm));
+    TRY(plan_drt_rows_dev(p, live_source(p), pb, neval, &order, 1, sign, normalize, row_scale, false, st, dev, R, tm));
     launch_window_trapz(st, B, neval, nwin, R.mu(0), dev.d(), dws.i(), dwe.i(), dres.d());
     LAUNCH_OK();
     tm.mark();
@@ -739,6 +753,165 @@ int hipdrt_plan_predict_resistances(hipdrt_plan* p, double* r_p, double* r_inf, 
     if (r_inf) HIPDRT_CHECK(hipMemcpyAsync(r_inf, dri.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
     if (r_tot) HIPDRT_CHECK(hipMemcpyAsync(r_tot, drt.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPDRT_CHECK(hipStreamSynchronize(st));
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+// ---- the probability function of relaxation times of a PFRT fit (csrc/pfrt.hip) -------------------------------------------------
+void hipdrt_pfrt_opts_default(hipdrt_pfrt_opts* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->eval_sign = 1; o->search = 1; o->height = 1e-3; o->prominence = 5e-3;
+    o->prior_mu = -4.0; o->prior_sigma = 0.5; o->n_eff_factor = 0.5; o->fxx_var_floor = 1e-5; o->ext_left = -1; o->ext_right = -1;
+    o->smooth = 1; o->smooth_order = 2.0; o->smooth_epsilon = 5.0; o->integrate = 0; o->integrate_threshold = 1e-6; o->normalize = 1;
+}
+
+// the raw weights estimate_weights(x, rv, vmm, rm) of one recorded step into dw [B][m] (the sums go to scratch)
+static int step_weights(hipdrt_plan* p, int step, hipStream_t st, DevBuf& dw, DevBuf& dscratch) {
+    const size_t B = (size_t)p->B;
+    if (dw.bytes < B * p->m * sizeof(double)) HIPDRT_CHECK(dw.alloc(B * p->m * sizeof(double)));
+    if (dscratch.bytes < 2 * B * sizeof(double)) HIPDRT_CHECK(dscratch.alloc(2 * B * sizeof(double)));
+    FitState fs = p->state();
+    fs.x = p->pf_x.d() + p->pf_layout().x(step);
+    TRY(launch_llh(st, fs, p->B, dscratch.d(), dscratch.d() + B, 0, 1.0, dw.d()));
+    LAUNCH_OK();
+    return HIPDRT_OK;
+}
+
+int hipdrt_plan_get_step_p_matrix(hipdrt_plan* p, int step, int b, double* out) try {
+    HIPDRT_REQUIRE(p && out, "NULL pointer");
+    HIPDRT_REQUIRE(p->B >= 1 && p->prepped, "no fitted batch in the plan");
+    HIPDRT_REQUIRE(step >= 0 && step < p->pf_steps, "step out of range of the recorded PFRT steps");
+    HIPDRT_REQUIRE(b >= 0 && b < p->B, "spectrum index out of range");
+    hipStream_t st; TRY(enter(p->ctx, &st));
+    const int n = p->n, m = p->m;
+    DevBuf dw, dscratch;
+    TRY(step_weights(p, step, st, dw, dscratch));
+    const FinalP f = plan_final_p(p, b, step_source(p, step, dw.d(), nullptr));
+    launch_gram_l2(st, 1, m, n, p->rm.d() + (size_t)b * p->rm_stride, p->ldrm, f.w, f.g, p->Ptmp.d(), p->ldp, 0, nullptr);
+    LAUNCH_OK();
+    return copy_strided(out, p->Ptmp.d(), n, n, p->ldp, st);      // (synchronises: dw may go)
+} HIPDRT_CATCH
+
+int hipdrt_plan_pfrt_get_step(hipdrt_plan* p, int step, double* x, double* rho, double* s, double* rss, double* sum_log_w,
+                              int* status) try {
+    HIPDRT_REQUIRE(p, "plan is NULL");
+    HIPDRT_REQUIRE(step >= 0 && step < p->pf_steps, "step out of range of the recorded PFRT steps");
+    hipStream_t st; TRY(enter(p->ctx, &st));
+    const PfrtStoreLayout L = p->pf_layout();
+    const size_t B = (size_t)p->B, n = (size_t)p->n, D = sizeof(double);
+    if (x) HIPDRT_CHECK(hipMemcpyAsync(x, p->pf_x.d() + L.x(step), B * n * D, hipMemcpyDeviceToHost, st));
+    if (rho) HIPDRT_CHECK(hipMemcpyAsync(rho, p->pf_rho.d() + L.rho(step), B * 3 * D, hipMemcpyDeviceToHost, st));
+    if (s) HIPDRT_CHECK(hipMemcpyAsync(s, p->pf_s.d() + L.s(step), B * 3 * n * D, hipMemcpyDeviceToHost, st));
+    if (rss) HIPDRT_CHECK(hipMemcpyAsync(rss, p->pf_rss.d() + L.scalar(step), B * D, hipMemcpyDeviceToHost, st));
+    if (sum_log_w) HIPDRT_CHECK(hipMemcpyAsync(sum_log_w, p->pf_slw.d() + L.scalar(step), B * D, hipMemcpyDeviceToHost, st));
+    if (status) HIPDRT_CHECK(hipMemcpyAsync(status, p->pf_status.i() + L.scalar(step), B * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+int hipdrt_plan_predict_pfrt(hipdrt_plan* p, const double* factors, const double* ln_tau_pfrt, int neval_pfrt,
+                             const double* ln_tau_out, int neval_out, const hipdrt_pfrt_opts* opts, double* pfrt, double* raw_pfrt,
+                             double* step_pfrt, double* post_prob, int* status) try {
+    HIPDRT_REQUIRE(p && factors && ln_tau_pfrt, "NULL pointer");
+    if (p->prepared) {
+        set_error("not supported: predict_pfrt is built for plain EIS plans (hipdrt_plan_create); a prepared plan records its steps "
+                  "and gives their P matrices only");
+        return HIPDRT_E_UNSUPPORTED;
+    }
+    PredictBasis pb;
+    TRY(predict_basis(p, pb));
+    hipdrt_pfrt_opts o;
+    if (opts) o = *opts; else hipdrt_pfrt_opts_default(&o);
+    const int S = p->pf_steps, B = p->B, np = neval_pfrt, nout = neval_out, width = p->n - p->ns;
+    // every check comes before the first launch
+    HIPDRT_REQUIRE(S >= 1, "no recorded PFRT steps in the plan (hipdrt_plan_pfrt_begin / _record around the fit's steps)");
+    TRY(pfrt_check(o, S, np, nout));
+    HIPDRT_REQUIRE(!o.smooth || ln_tau_out, "smoothing needs the output grid");
+    HIPDRT_REQUIRE(o.eval_sign == 1, "eval_sign must be 1 (the DRT block of a plain EIS plan holds one copy of the basis)");
+    for (int i = 0; i < S; ++i) HIPDRT_REQUIRE(factors[i] > 0.0 && std::isfinite(factors[i]), "factors must be positive and finite");
+    hipdrt_peak_opts po;
+    hipdrt_peak_opts_default(&po);
+    po.eval_sign = 1; po.search = o.search; po.normalize = 1; po.method = 0; po.height = o.height; po.prominence = o.prominence;
+    TRY(peak_check_opts(po, np));
+    HIPDRT_REQUIRE(peaks_lds_bytes(np, 0, 1, 0) <= 160 * 1024 - 256, "predict_pfrt: neval_pfrt too large for one workgroup's LDS");
+    hipStream_t st; TRY(enter(p->ctx, &st));
+
+    // a spectrum whose fit failed in any step is dead in every step
+    std::vector<int> hs((size_t)S * B), comb(B, 0), hbad(B, 0);
+    for (int i = 0; i < S; ++i)
+        HIPDRT_CHECK(hipMemcpyAsync(hs.data() + (size_t)i * B, p->pf_status.i() + p->pf_layout().scalar(i), (size_t)B * sizeof(int),
+                                    hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    for (int b = 0; b < B; ++b)
+        for (int i = 0; i < S; ++i) {
+            const int v = hs[(size_t)i * B + b];
+            if (comb[b] >= 0 && (v < 0 || v > comb[b])) comb[b] = v;
+        }
+    std::vector<double> lnf(S);
+    for (int i = 0; i < S; ++i) lnf[i] = std::log(factors[i]);
+
+    const size_t bn = (size_t)B * np;
+    DevBuf dev, dout_grid, dfs, dbad, dlnf, dw, dscratch, dnorm0, dsg, dht, dpr, dstep, dpf, draw, dpost;
+    DevBuf dE;
+    TRY(upload(dev, ln_tau_pfrt, (size_t)np * sizeof(double), st));
+    if (o.smooth) TRY(upload(dout_grid, ln_tau_out, (size_t)nout * sizeof(double), st));
+    TRY(upload(dfs, comb.data(), (size_t)B * sizeof(int), st));
+    TRY(upload(dlnf, lnf.data(), (size_t)S * sizeof(double), st));
+    HIPDRT_CHECK(dbad.alloc((size_t)B * sizeof(int)));
+    HIPDRT_CHECK(hipMemsetAsync(dbad.p, 0, (size_t)B * sizeof(int), st));
+    HIPDRT_CHECK(dnorm0.alloc((size_t)B * sizeof(double)));
+    HIPDRT_CHECK(dsg.alloc(bn * sizeof(int))); HIPDRT_CHECK(dht.alloc(bn * sizeof(double))); HIPDRT_CHECK(dpr.alloc(bn * sizeof(double)));
+    HIPDRT_CHECK(dstep.alloc((size_t)S * bn * sizeof(double)));
+    HIPDRT_CHECK(dE.alloc((size_t)2 * np * width * sizeof(double)));
+    HIPDRT_CHECK(hipStreamSynchronize(st));          // (the host vectors above may go out of use)
+    const int orders[2] = {2, 0};
+    PredictTimer tm(p->ctx, st);
+    for (int i = 0; i < S; ++i) {
+        // step P = calculate_pq with the step's s / rho and the raw re-estimated weights (drt1d.py:2611-2632)
+        TRY(step_weights(p, i, st, dw, dscratch));
+        const PostSource src = step_source(p, i, dw.d(), dfs.i());
+        // f and fxx normalised by the R_p of the step's own x; sigma^2 of both orders from one factorisation of the step P
+        DrtRows R;
+        R.dE.alias(dE, 0, dE.bytes);
+        HIPDRT_CHECK(R.dmu.alloc((size_t)2 * bn * sizeof(double)));
+        TRY(plan_drt_rows_dev(p, src, pb, np, orders, 2, 1, 1, nullptr, true, st, dev, R, tm, i > 0));
+        // ... but every step's variances are divided by the squared R_p of the FIRST step (estimate_distribution_cov takes
+        // get_drt_norm() of fit_parameters, which the warm restarts never update: drt1d.py:3081)
+        if (i == 0) HIPDRT_CHECK(hipMemcpyAsync(dnorm0.p, R.dnorm.p, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, st));
+        PeakArgs pa{};
+        pa.neval = np; pa.o = po; pa.fxx = R.mu(0); pa.f = R.mu(1); pa.fit_status = dfs.i();
+        pa.peak_sign = dsg.i(); pa.heights = dht.d(); pa.prominences = dpr.d();
+        TRY(launch_peaks(st, pa, B));
+        LAUNCH_OK();
+        PfrtStepArgs sa{};
+        sa.neval = np; sa.floor = o.fxx_var_floor; sa.ext_left = o.ext_left; sa.ext_right = o.ext_right;
+        sa.peak_sign = dsg.i(); sa.heights = dht.d(); sa.prominences = dpr.d(); sa.f = R.mu(1);
+        sa.var_fxx = R.var(0); sa.var_f = R.var(1); sa.ldv = R.ldv(); sa.cs = R.cs; sa.norm = dnorm0.d();
+        sa.fit_status = dfs.i(); sa.var_status = R.dvstat.i(); sa.out = dstep.d() + (size_t)i * bn; sa.bad = dbad.i();
+        TRY(launch_pfrt_step(st, sa, B));
+        LAUNCH_OK();
+        HIPDRT_CHECK(hipStreamSynchronize(st));      // R's buffers are released at the end of the iteration
+    }
+    PfrtCombineArgs ca{};
+    ca.S = S; ca.np = np; ca.nout = nout; ca.ld_step = (long long)bn; ca.ld_sum = p->capacity;
+    ca.step_pfrt = dstep.d(); ca.rss = p->pf_rss.d(); ca.slw = p->pf_slw.d(); ca.ln_factors = dlnf.d();
+    pfrt_llh_consts(p->m, &ca.c, &ca.alpha_n, &ca.beta_0);
+    ca.prior_mu = o.prior_mu; ca.prior_sigma = o.prior_sigma; ca.n_eff = o.n_eff_factor;
+    ca.smooth = o.smooth != 0; ca.smooth_order = o.smooth_order; ca.smooth_eps = o.smooth_epsilon;
+    ca.integrate = o.integrate != 0; ca.thr = o.integrate_threshold; ca.normalize = o.normalize != 0;
+    ca.ltp = dev.d(); ca.lto = dout_grid.d(); ca.fit_status = dfs.i(); ca.bad = dbad.i();
+    if (pfrt) { HIPDRT_CHECK(dpf.alloc((size_t)B * nout * sizeof(double))); ca.pfrt = dpf.d(); }
+    if (raw_pfrt) { HIPDRT_CHECK(draw.alloc(bn * sizeof(double))); ca.raw = draw.d(); }
+    if (post_prob) { HIPDRT_CHECK(dpost.alloc((size_t)S * B * sizeof(double))); ca.post = dpost.d(); }
+    TRY(launch_pfrt_combine(st, ca, B));
+    LAUNCH_OK();
+    tm.mark();
+    TRY(KkOut::back(pfrt, dpf, st)); TRY(KkOut::back(raw_pfrt, draw, st)); TRY(KkOut::back(post_prob, dpost, st));
+    TRY(KkOut::back(step_pfrt, dstep, st));
+    HIPDRT_CHECK(hipMemcpyAsync(hbad.data(), dbad.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    if (status)
+        for (int b = 0; b < B; ++b) status[b] = (comb[b] >= 0 && hbad[b] != 0) ? HIPDRT_PREDICT_NOT_PD : comb[b];
     return HIPDRT_OK;
 } HIPDRT_CATCH
 

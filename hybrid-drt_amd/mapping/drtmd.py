@@ -327,7 +327,7 @@ def fit_observation_list(drt, observations, tau_supergrid, drt_var=False, ignore
 
 
 def fit_observations_pfrt(drt, observations, tau_supergrid, pfrt_factors=None, drt_var=False, ignore_errors=False,
-                          llh_kw=None, rss_kw=None, **fit_kw):
+                          llh_kw=None, rss_kw=None, predict_pfrt_kw=None, **fit_kw):
     """DRTMD with fit_type='pfrt' (drtmd.py:98-100, 1136-1158, 1338-1342): every observation through _pfrt_fit_core
     (drt1d.py:2558-2700) -- one full fit at the first regularisation factor, one warm restart per further factor -- with one
     solution PER FACTOR recorded.  Factors: ``pfrt_factors`` (or ``factors=`` among the fit keywords, which is where upstream
@@ -340,7 +340,10 @@ def fit_observations_pfrt(drt, observations, tau_supergrid, pfrt_factors=None, d
     evaluate_rss of the first step's last iterate (qphb_history[-1], drt1d.py:4433-4496) and obs_drt_var the variance of the
     first step's P matrix (fit_parameters['p_matrix']); the same here.  The reference's own DRTMD stops at a joint observation
     (v_baseline arrives as (S, 1) where (S,) was allocated, drtmd.py:287); here such specials are stored (num, S, size).
-    Also returned per observation: step_llh (num, S), step_iters (num, S)."""
+    Also returned per observation: step_llh (num, S), step_iters (num, S).  ``predict_pfrt_kw`` (a dict, may be empty): EIS groups
+    also fill res['obs_pfrt'] and res['obs_raw_pfrt'] (num, len(tau_supergrid)) from DRT.predict_pfrt_batch(**predict_pfrt_kw) with
+    tau_pfrt = tau = tau_supergrid unless the dict says otherwise (rows of other groups and of failed fits are NaN); None leaves
+    every returned object as it is without it."""
     tau_supergrid = np.asarray(tau_supergrid, dtype=float)
     if 'factors' in fit_kw:
         pfrt_factors = fit_kw.pop('factors')
@@ -355,6 +358,13 @@ def fit_observations_pfrt(drt, observations, tau_supergrid, pfrt_factors=None, d
     if drt_var:
         res['obs_drt_var'] = np.zeros((num, S, nsup))
         res['obs_drt_var_ok'] = np.zeros(num, dtype=bool)
+    if predict_pfrt_kw is not None:
+        ppk = dict(predict_pfrt_kw)
+        ppk.setdefault('tau_pfrt', tau_supergrid)
+        ppk.setdefault('tau', ppk['tau_pfrt'])
+        if len(ppk['tau']) != nsup or len(ppk['tau_pfrt']) != nsup:
+            raise ValueError('predict_pfrt_kw: tau and tau_pfrt must have the length of tau_supergrid')
+        res['obs_pfrt'], res['obs_raw_pfrt'] = np.full((num, nsup), np.nan), np.full((num, nsup), np.nan)
     pf_kw = {k: fit_kw.pop(k) for k in ('max_iter_per_step', 'max_init_iter', 'xtol', 'nonneg') if k in fit_kw}
     for g, (kind, idx) in enumerate(observation_groups(observations)):
         idx = np.asarray(idx)
@@ -379,6 +389,9 @@ def fit_observations_pfrt(drt, observations, tau_supergrid, pfrt_factors=None, d
                 specials['R_inf'] = pr['step_x'][:, :, sp['R_inf']['index']] * cs[None, :]
             if 'inductance' in sp:
                 specials['inductance'] = pr['step_x'][:, :, sp['inductance']['index']] * cs[None, :] * drt.inductance_scale
+            if predict_pfrt_kw is not None:
+                tot, info = drt.predict_pfrt_batch(return_info=True, **ppk)
+                res['obs_pfrt'][idx], res['obs_raw_pfrt'][idx] = tot, info['raw_pfrt']
         else:
             meas = []
             for k in idx:

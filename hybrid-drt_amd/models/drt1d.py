@@ -434,12 +434,16 @@ class DRT(PreparedFitMixin):
         init_kw = dict(kw)
         init_kw.update(step_hypers(factors[0]))
         res = self.fit_eis_batch(frequencies, z_batch, nonneg=nonneg, max_iter=max_init_iter, xtol=xtol, **init_kw)
+        # every step's final state stays on the device for predict_pfrt_batch / step_p_matrix (hipdrt_plan_pfrt_begin / _record)
+        self._plan.pfrt_begin(len(factors))
+        self._plan.pfrt_record()
         step_x, step_llh, step_iters = [res['x'].copy()], [self.evaluate_step_llh_batch()], [res['outer_iters'].copy()]
         status = np.array(res['status']).copy()
         if after_init is not None:          # (what DRTMD reads from the FIRST step's fit: its P matrix, llh / rss -- mapping)
             after_init(res)
         for f in factors[1:]:
             res = self.continue_from_init(xtol=xtol, max_iter=max_iter_per_step, **step_hypers(f))
+            self._plan.pfrt_record()
             step_x.append(res['x'].copy())
             step_llh.append(self.evaluate_step_llh_batch())
             step_iters.append(res['outer_iters'].copy())
@@ -448,6 +452,79 @@ class DRT(PreparedFitMixin):
                             'step_iters': np.array(step_iters), 'status': status,
                             'coefficient_scale': res['coefficient_scale'], 'basis_tau': res['basis_tau']}
         return self.pfrt_result
+
+    # ---- the PFRT of a PFRT fit (drt1d.py:2716-2858), over the steps recorded on the device -----------------------------------
+    def _pfrt_plan(self, what):
+        plan = self._plan
+        if plan is None or getattr(self, 'pfrt_result', None) is None or plan.pfrt_steps() == 0:
+            raise RuntimeError(f'{what} needs a finished PFRT fit (pfrt_fit_eis_batch, fit_observations(fit_type="pfrt"))')
+        return plan
+
+    def step_p_matrix(self, step, b=0):
+        """pfrt_result['step_p_mat'][step] of member ``b`` of the last PFRT fit (drt1d.py:2611-2632): calculate_pq with the step's
+        final s / rho and the raw weights re-estimated from the step's x, formed on the device (hipdrt_plan_get_step_p_matrix)"""
+        return self._pfrt_plan('step_p_matrix').step_p_matrix(step, b)
+
+    def predict_pfrt_batch(self, tau=None, tau_pfrt=None, sign=None, prior_mu=-4, prior_sigma=0.5, find_peaks_kw=None,
+                           n_eff_factor=0.5, fxx_var_floor=1e-5, extend_var=True, smooth=True, smooth_kw=None, integrate=False,
+                           integrate_threshold=1e-6, normalize=True, return_info=False):
+        """DRT.predict_pfrt (drt1d.py:2716-2858) for every spectrum of the last PFRT fit -> (B, len(tau)), on the device over the
+        recorded steps (hipdrt_plan_predict_pfrt; models/pfrt.py is the rule in numpy).  tau_pfrt=None is get_tau_eval(10), tau=None
+        is tau_pfrt (without smooth the result stays on tau_pfrt, as upstream).  With return_info also a dict with tau_pfrt,
+        raw_pfrt (B, n), step_pfrt (S, B, n), post_prob (S, B) and status (B,), the first three also stored into pfrt_result under
+        upstream's keys.  Rows of spectra whose fit failed in any step, or whose step P is not positive definite, are NaN.  Of
+        find_peaks_kw only height and prominence are built; plain EIS fits only.  select_pfrt_candidates and the discrete-model
+        conversion stay with the reference's Python on these arrays."""
+        from .. import _ffi
+        if self.series_neg:
+            raise NotImplementedError('predict_pfrt: series_neg fits are not taken (upstream\'s normalize=True raises for them)')
+        if isinstance(self._plan, _ffi.PreparedPlan):
+            raise NotImplementedError('predict_pfrt is built for plain EIS fits; a prepared plan records its steps and gives '
+                                      'step_p_matrix only')
+        plan = self._pfrt_plan('predict_pfrt')
+        fkw = dict(find_peaks_kw or {'height': 1e-3, 'prominence': 5e-3})
+        for name in fkw:
+            if name not in ('height', 'prominence'):
+                raise NotImplementedError(f'predict_pfrt: the {name}= condition of scipy.signal.find_peaks is not built '
+                                          f'(only height and prominence)')
+        skw = dict(smooth_kw or {'order': 2, 'epsilon': 5})
+        if set(skw) - {'order', 'epsilon'}:
+            raise TypeError(f"unexpected smooth_kw {sorted(set(skw) - {'order', 'epsilon'})}")
+        sign = self._drt_sign(plan, sign)
+        tau_pfrt = self.get_tau_eval(10) if tau_pfrt is None else np.asarray(tau_pfrt, dtype=float)
+        tau_out = tau_pfrt if (tau is None or not smooth) else np.asarray(tau, dtype=float)
+        search = sign if (self.fit_kwargs['nonneg'] and sign != 0) else 0
+        ext = self._extend_var_indices(tau_pfrt) if extend_var else (-1, -1)
+        if ext[0] >= len(tau_pfrt):
+            raise ValueError('extend_var: the measured tau range ends at the last point of the evaluation grid')
+        opts = _ffi.pfrt_opts(eval_sign=sign, search=search, height=fkw.get('height', 0), prominence=fkw.get('prominence', 0),
+                              prior_mu=prior_mu, prior_sigma=prior_sigma, n_eff_factor=n_eff_factor, fxx_var_floor=fxx_var_floor,
+                              ext_left=ext[0], ext_right=ext[1], smooth=bool(smooth), smooth_order=skw.get('order', 2),
+                              smooth_epsilon=skw.get('epsilon', 5), integrate=bool(integrate),
+                              integrate_threshold=integrate_threshold, normalize=bool(normalize))
+        factors = np.asarray(self.pfrt_result['factors'], dtype=float)
+        if len(factors) != plan.pfrt_steps():
+            raise ValueError(f"pfrt_result['factors'] has {len(factors)} entries, the plan recorded {plan.pfrt_steps()} steps")
+        out = plan.predict_pfrt(factors, np.log(tau_pfrt), np.log(tau_out) if smooth else None, opts,
+                                want=None if return_info else ('pfrt',))
+        if not return_info:
+            return out['pfrt']
+        self.pfrt_result.update(tau_pfrt=tau_pfrt, raw_pfrt=out['raw_pfrt'], step_pfrt=out['step_pfrt'])
+        info = dict(tau_pfrt=tau_pfrt, raw_pfrt=out['raw_pfrt'], step_pfrt=out['step_pfrt'], post_prob=out['post_prob'],
+                    status=out['status'])
+        return out['pfrt'], info
+
+    def predict_pfrt(self, tau=None, tau_pfrt=None, sign=None, prior_mu=-4, prior_sigma=0.5, find_peaks_kw=None, n_eff_factor=0.5,
+                     fxx_var_floor=1e-5, extend_var=True, smooth=True, smooth_kw=None, integrate=False, integrate_threshold=1e-6,
+                     normalize=True, b=0):
+        """DRT.predict_pfrt (drt1d.py:2716-2858) of member ``b`` of the last PFRT fit, from the device; pfrt_result gets tau_pfrt,
+        raw_pfrt and step_pfrt of that member, as upstream"""
+        tot, info = self.predict_pfrt_batch(tau=tau, tau_pfrt=tau_pfrt, sign=sign, prior_mu=prior_mu, prior_sigma=prior_sigma,
+                                            find_peaks_kw=find_peaks_kw, n_eff_factor=n_eff_factor, fxx_var_floor=fxx_var_floor,
+                                            extend_var=extend_var, smooth=smooth, smooth_kw=smooth_kw, integrate=integrate,
+                                            integrate_threshold=integrate_threshold, normalize=normalize, return_info=True)
+        self.pfrt_result.update(raw_pfrt=info['raw_pfrt'][b], step_pfrt=info['step_pfrt'][:, b])
+        return tot[b]
 
     # ---- what DRTMD takes from a finished fit (mapping/drtmd.py:258-279) ----------------------------------------
     def _signed_basis(self, bm, sign):

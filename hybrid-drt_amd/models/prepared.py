@@ -762,6 +762,9 @@ class PreparedFitMixin:
                                ('qphb_chrono' if preps[0]['num_chrono'] else 'qphb_eis'))
         else:
             self._last_prepared = (preps, None)
+        # every step's final state stays on the device for step_p_matrix (hipdrt_plan_pfrt_begin / _record)
+        self._plan.pfrt_begin(len(factors))
+        self._plan.pfrt_record()
         step_x, step_llh, step_iters = [out['x'].copy()], [self.evaluate_step_llh_batch()], [out['outer_iters'].copy()]
         status = np.array(out['status']).copy()
         history = [self._plan.history()] if single else None
@@ -776,6 +779,7 @@ class PreparedFitMixin:
             res = self._continue_prepared(xtol=xtol, max_iter=max_iter_per_step, history_of=0 if single else -1,
                                           chrono_weight_factor=float(cf[0]), eis_weight_factor=float(ef[0]),
                                           **step_hypers(f))
+            self._plan.pfrt_record()
             step_x.append(res['x'].copy())
             step_llh.append(self.evaluate_step_llh_batch())
             step_iters.append(res['outer_iters'].copy())

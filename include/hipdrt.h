@@ -592,6 +592,65 @@ int hipdrt_plan_integrate_drt(hipdrt_plan* plan, const double* ln_tau_eval, int 
                               const double* row_scale, const int* win_start, const int* win_end, int nwin, double* out,
                               int* status);
 
+/* ---- the probability function of relaxation times (PFRT) of a PFRT fit ----------------------------------------------------------
+ * DRT.pfrt_fit_eis (hybdrt/models/drt1d.py:2558-2698) is a fit at the first regularisation factor followed by one warm restart
+ * per further factor; DRT.predict_pfrt (2716-2858) turns the S solutions into the PFRT.  The plan keeps what that needs in a step
+ * store: hipdrt_plan_pfrt_begin sizes it for max_steps steps of the plan's capacity (x, s, rho [, dop_rho], the two likelihood sums
+ * and the status of every spectrum: hipdrt_plan_pfrt_bytes_per_spectrum bytes each) and empties it; hipdrt_plan_pfrt_record, called
+ * after hipdrt_plan_fit and after every hipdrt_plan_continue, appends the state that call left (device-to-device copies) and the
+ * sums of hipdrt_plan_llh_terms; hipdrt_plan_pfrt_steps gives the count.  Staging a new batch empties the store.  Plain and
+ * prepared plans.  A failed allocation is HIPDRT_E_HIP and leaves the plan usable with an empty store.                          */
+int hipdrt_plan_pfrt_bytes_per_spectrum(int n, int steps, long long* bytes);
+int hipdrt_plan_pfrt_begin(hipdrt_plan* plan, int max_steps);
+int hipdrt_plan_pfrt_record(hipdrt_plan* plan);
+int hipdrt_plan_pfrt_steps(hipdrt_plan* plan, int* steps);
+/* what step `step` recorded, for the staged spectra: x [B][n], rho [B][3], s [B][3][n], rss [B], sum_log_w [B], status [B]; any
+ * may be NULL                                                                                                                  */
+int hipdrt_plan_pfrt_get_step(hipdrt_plan* plan, int step, double* x, double* rho, double* s, double* rss, double* sum_log_w,
+                              int* status);
+/* pfrt_result['step_p_mat'][step] of spectrum b, p[n][n]: calculate_pq with the step's final s / rho and the RAW weights
+ * estimate_weights(x, rv, vmm, rm) of the step's x (drt1d.py:2611-2632) -- not hipdrt_plan_get_p_matrix's matrix, which carries
+ * the loop's blended weights times the weight factors, and only for the last state.  Also what DRTMD reads per factor
+ * (hybdrt/mapping/drtmd.py:934-941).  Plain and prepared plans.                                                                */
+int hipdrt_plan_get_step_p_matrix(hipdrt_plan* plan, int step, int b, double* p);
+typedef struct {
+    int eval_sign;              /* 1; get_drt_params' sign of the evaluated rows (a plain EIS plan takes 1 only)                 */
+    int search;                 /* 1; as hipdrt_peak_opts.search: sign if nonneg and sign != 0, else 0 (two passes)              */
+    double height;              /* 1e-3; find_peaks_kw                                                                          */
+    double prominence;          /* 5e-3                                                                                         */
+    double prior_mu;            /* -4; log-normal prior on ln(factor)                                                           */
+    double prior_sigma;         /* 0.5                                                                                          */
+    double n_eff_factor;        /* 0.5; exponent on the normalised posterior                                                    */
+    double fxx_var_floor;       /* 1e-5; lower bound of BOTH variances (upstream hands it to both estimate_distribution_cov calls) */
+    int ext_left;               /* -1 = off; extend_var's clamp indices on the tau_pfrt grid, as hipdrt_peak_opts                */
+    int ext_right;
+    int smooth;                 /* 1; multiply by exp(-(epsilon |ln tau_out - ln tau_pfrt|)^(2 order))                           */
+    double smooth_order;        /* 2                                                                                            */
+    double smooth_epsilon;      /* 5                                                                                            */
+    int integrate;              /* 0; pfrt.integrate_peaks: every contiguous range >= integrate_threshold becomes its trapezoid
+                                   area (one sample beyond either end included) at the range's maximum; a range that starts at
+                                   index 0 gets 0, as upstream's empty slice does                                               */
+    double integrate_threshold; /* 1e-6                                                                                         */
+    int normalize;              /* 1; divide by the row's maximum (an all-zero row becomes NaN, as upstream)                     */
+} hipdrt_pfrt_opts;
+void hipdrt_pfrt_opts_default(hipdrt_pfrt_opts* o);
+/* DRT.predict_pfrt for every spectrum of the fitted batch over the S recorded steps, on the device.  factors [S] (S must be the
+ * recorded step count); ln_tau_pfrt [neval_pfrt] the peak-finding grid; ln_tau_out [neval_out] the grid of the smoothed result
+ * (without smooth: neval_out == neval_pfrt and ln_tau_out is not read).  Per step: the step P of the whole batch, one
+ * factorisation per spectrum fed the order-2 and order-0 evaluation rows, f and fxx normalised by the R_p of the step's own x,
+ * both variances divided by the squared R_p of the FIRST step (as upstream, whose estimate_distribution_cov normalises by
+ * fit_parameters), extend_var's clamp and the floor, scipy's peak rule (peaks_kernel, method 0), and at every peak
+ * min(1 - erfc(|f| / (sigma_f sqrt 2)), 1 - erfc(min(prominence, height) / (sigma_fxx sqrt 2))).  Then once: posterior weights of
+ * the steps from the recorded likelihood sums and the prior, the weighted sum, smoothing, integration, normalisation.
+ * out (host; any may be NULL): pfrt [B][neval_out], raw_pfrt [B][neval_pfrt], step_pfrt [S][B][neval_pfrt], post_prob [S][B],
+ * status [B]: the fit's status (negative when any step failed), or HIPDRT_PREDICT_NOT_PD when a step P is not positive definite;
+ * the rows of such a spectrum are NaN.  HIPDRT_E_INVALID before any launch: no recorded steps, options out of range, more than
+ * 2048 points on either grid.  HIPDRT_E_UNSUPPORTED for a prepared plan.  Callable repeatedly after one fit.  The result of a
+ * spectrum depends neither on B nor on its position.                                                                            */
+int hipdrt_plan_predict_pfrt(hipdrt_plan* plan, const double* factors, const double* ln_tau_pfrt, int neval_pfrt,
+                             const double* ln_tau_out, int neval_out, const hipdrt_pfrt_opts* opts, double* pfrt, double* raw_pfrt,
+                             double* step_pfrt, double* post_prob, int* status);
+
 /* kernel-time breakdown of the last hipdrt_plan_fit in ms (HIP events on the ctx stream):
  * t[0]=total, t[1]=gram, t[2]=qp, t[3]=hyper, t[4]=setup/other; launches[5] same order                 */
 int hipdrt_plan_timings(hipdrt_plan* plan, float* t, int* launches);

@@ -168,6 +168,22 @@ typedef struct {
 } hipdrt_debug_peak_resolve_args;
 int hipdrt_debug_peak_resolve(hipdrt_ctx* ctx, const hipdrt_debug_peak_resolve_args* a);
 
+/* test hooks (tests/test_gpu_pfrt.py): the two kernels of csrc/pfrt.hip as they are, on host arrays.
+ * pfrt_step: peak_sign, heights, prominences (what peaks_kernel writes), f, var_f, var_fxx, all [B][neval]; the variances before
+ * extend_var's clamp (ext_left, ext_right; -1 = off) and the floor, which the kernel applies; out [B][neval].
+ * pfrt_combine: step_pfrt [S][B][neval_pfrt], rss and sum_log_w [S][B], factors [S], m the number of data rows behind the sums;
+ * the options' prior, n_eff_factor, smooth, integrate and normalize fields are used; ln_tau_out may be NULL without smooth;
+ * pfrt [B][neval_out], raw_pfrt [B][neval_pfrt], post_prob [S][B], any may be NULL.  Every device output has a border of marker
+ * bytes on either side: HIPDRT_E_NUMERIC when a kernel changed one.  HIPDRT_E_INVALID, and nothing is launched, for a grid of more
+ * than 2048 points.                                                                                                            */
+int hipdrt_debug_pfrt_step(hipdrt_ctx* ctx, int B, int neval, const int* peak_sign, const double* heights, const double* prominences,
+                           const double* f, const double* var_f, const double* var_fxx, double var_floor, int ext_left,
+                           int ext_right, double* out);
+int hipdrt_debug_pfrt_combine(hipdrt_ctx* ctx, int B, int S, int neval_pfrt, int neval_out, const double* step_pfrt,
+                              const double* rss, const double* sum_log_w, const double* factors, int m,
+                              const hipdrt_pfrt_opts* opts, const double* ln_tau_pfrt, const double* ln_tau_out, double* pfrt,
+                              double* raw_pfrt, double* post_prob);
+
 /* tools hook (tools/bench_predict.py, tools/bench_peaks.py): kernel time in ms of the last hipdrt_plan_predict_drt /
  * hipdrt_plan_predict_z / hipdrt_plan_find_peaks (ms[0]: the mean rows, ms[1]: all launches, peaks_kernel included) of a plan of
  * this context, by HIP events around its launches (allocations and copies excluded): ms[0] up to the mean (predict_z: the whole

@@ -1,0 +1,25 @@
+"""CPU: the host-side bookkeeping of the PFRT step store (csrc/pfrt_store.hpp: begin / record / the step loop's offsets) under
+AddressSanitizer and UndefinedBehaviorSanitizer, as a stand-alone program with its own main (tests/c/pfrt_store_host.cpp) against a
+memcpy stub of the device copies.  Nothing of it is loaded into this process and nothing touches a GPU."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+from conftest import ROOT
+
+
+def test_step_store_bookkeeping_under_sanitizers(tmp_path):
+    cxx = next((c for c in ("g++", "c++", "clang++", "/opt/rocm/llvm/bin/clang++") if shutil.which(c)), None)
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    exe = str(tmp_path / "pfrt_store_host")
+    # (the sanitizers' runtimes are linked statically: clang's default, asked of gcc)
+    static = [] if "clang" in cxx else ["-static-libasan", "-static-libubsan"]
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", *static,
+                    "-I", os.path.join(ROOT, "hybrid-drt_amd", "csrc"), os.path.join(ROOT, "tests", "c", "pfrt_store_host.cpp"),
+                    "-o", exe], check=True)
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert "pfrt store bookkeeping ok" in run.stdout
