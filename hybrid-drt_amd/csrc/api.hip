@@ -1,6 +1,6 @@
 // C-ABI of libhipdrt.so (include/hipdrt.h): the error string, the library's own streams and the life cycle of a context.
 // The rest of the ABI: operators.hip (stand-alone operators), plan.hip (the plan), plan_fit.hip (its device fit loop),
-// plan_post.hip (what reads a finished fit), debug.hip (include/hipdrt_debug.h).
+// plan_post.hip and plan_drt.hip (what reads a finished fit), debug.hip (include/hipdrt_debug.h).
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>

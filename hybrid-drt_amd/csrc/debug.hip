@@ -5,6 +5,58 @@
 
 #include "plan.hpp"
 
+namespace {
+struct Guarded {
+    static constexpr size_t G = 128;           // border bytes on either side
+    static constexpr unsigned char MARK = 0xA5;
+    DevBuf buf;
+    void* host = nullptr;
+    size_t bytes = 0;
+    const char* name = "";
+    std::vector<unsigned char> stage;
+    int up(const char* what, void* h, size_t nbytes, hipStream_t st) {
+        name = what; host = h; bytes = nbytes;
+        stage.assign(nbytes + 2 * G, MARK);
+        if (h) std::memcpy(stage.data() + G, h, nbytes);
+        HIPDRT_CHECK(buf.alloc(stage.size()));
+        HIPDRT_CHECK(hipMemcpyAsync(buf.p, stage.data(), stage.size(), hipMemcpyHostToDevice, st));
+        return 0;
+    }
+    double* dd() const { return reinterpret_cast<double*>(static_cast<unsigned char*>(buf.p) + G); }
+    int fetch(hipStream_t st) { HIPDRT_CHECK(hipMemcpyAsync(stage.data(), buf.p, stage.size(), hipMemcpyDeviceToHost, st)); return 0; }
+    int check() {
+        for (size_t i = 0; i < G; ++i)
+            if (stage[i] != MARK || stage[G + bytes + i] != MARK) {
+                set_error(std::string("the kernel under test wrote outside ") + name);
+                return HIPDRT_E_NUMERIC;
+            }
+        if (host) std::memcpy(host, stage.data() + G, bytes);
+        return 0;
+    }
+};
+// The guarded outputs of one hook, as DevOuts (plan.hpp) holds the plain ones of an entry point: one want() per output, one
+// back() after the launch that fetches every array and then checks every border.
+struct GuardedOuts {
+    static constexpr int MAX = 17;         // hipdrt_debug_hyper_step has 17
+    Guarded g[MAX];
+    int n = 0;
+    template <class T>
+    int want(const char* name, T* host, size_t count, T*& field, hipStream_t st) {
+        if (!host) return 0;
+        HIPDRT_REQUIRE(n < MAX, "internal: more outputs than GuardedOuts holds");
+        TRY(g[n].up(name, host, count * sizeof(T), st));
+        field = reinterpret_cast<T*>(g[n++].dd());
+        return 0;
+    }
+    int back(hipStream_t st) {
+        for (int i = 0; i < n; ++i) TRY(g[i].fetch(st));
+        HIPDRT_CHECK(hipStreamSynchronize(st));
+        for (int i = 0; i < n; ++i) TRY(g[i].check());
+        return 0;
+    }
+};
+}  // namespace
+
 extern "C" {
 
 int hipdrt_debug_qp_group(hipdrt_ctx* ctx, int members) try {
@@ -122,39 +174,7 @@ int hipdrt_debug_pack_p(hipdrt_ctx* ctx, int B, int n, const double* P, int ldp,
 } HIPDRT_CATCH
 
 // test hook (include/hipdrt_debug.h): launch_hyper as the fit loop calls it, on host arrays.  Every extent a kernel derives an
-// address from is checked here.  In/out arrays live on the device between two borders of marker bytes.
-namespace {
-struct Guarded {
-    static constexpr size_t G = 128;           // border bytes on either side
-    static constexpr unsigned char MARK = 0xA5;
-    DevBuf buf;
-    void* host = nullptr;
-    size_t bytes = 0;
-    const char* name = "";
-    std::vector<unsigned char> stage;
-    int up(const char* what, void* h, size_t nbytes, hipStream_t st) {
-        name = what; host = h; bytes = nbytes;
-        stage.assign(nbytes + 2 * G, MARK);
-        if (h) std::memcpy(stage.data() + G, h, nbytes);
-        HIPDRT_CHECK(buf.alloc(stage.size()));
-        HIPDRT_CHECK(hipMemcpyAsync(buf.p, stage.data(), stage.size(), hipMemcpyHostToDevice, st));
-        return 0;
-    }
-    double* dd() const { return reinterpret_cast<double*>(static_cast<unsigned char*>(buf.p) + G); }
-    int* di() const { return reinterpret_cast<int*>(static_cast<unsigned char*>(buf.p) + G); }
-    int fetch(hipStream_t st) { HIPDRT_CHECK(hipMemcpyAsync(stage.data(), buf.p, stage.size(), hipMemcpyDeviceToHost, st)); return 0; }
-    int check() {
-        for (size_t i = 0; i < G; ++i)
-            if (stage[i] != MARK || stage[G + bytes + i] != MARK) {
-                set_error(std::string("the kernel under test wrote outside ") + name);
-                return HIPDRT_E_NUMERIC;
-            }
-        if (host) std::memcpy(host, stage.data() + G, bytes);
-        return 0;
-    }
-};
-}  // namespace
-
+// address from is checked here.  In/out arrays live on the device between two borders of marker bytes (Guarded).
 int hipdrt_debug_hyper_form(hipdrt_ctx* ctx, int n, int m, int ns, int toeplitz, int outlier, int* form, long long* lds_bytes) try {
     HIPDRT_REQUIRE(ctx && form && lds_bytes, "NULL pointer");
     HIPDRT_REQUIRE(m >= 1 && m <= 8192 && n >= 1 && n <= 4096 && ns >= 0 && ns < n, "1 <= m <= 8192, 0 <= ns < n <= 4096");
@@ -227,50 +247,35 @@ int hipdrt_debug_hyper_step(hipdrt_ctx* ctx, const hipdrt_debug_hyper_args* a) t
     const size_t D = sizeof(double), I = sizeof(int);
     const size_t nrm = (size_t)(a->rm_batched ? B : 1) * m * a->ldrm;
     DevBuf dvmm, dmk[3], dx, dqs, dvs, dve, dpremv;
-    Guarded grm, gxin, gs, grho, gxmx, grv, gew, gw, gvf, gcs, gact, gfs, goi, gna, got, gdr, gdx;
     std::vector<double> rm_copy(a->rm, a->rm + nrm);
-    TRY(grm.up("rm", rm_copy.data(), nrm * D, st));
+    const size_t bn = (size_t)B * n, bm = (size_t)B * m, b3 = (size_t)B * 3;
+    FitState fs{};
+    GuardedOuts g;
+    TRY(g.want("rm", rm_copy.data(), nrm, fs.rm_rw, st));
     TRY(upload(dvmm, a->vmm, (size_t)m * m * D, st));
     for (int k = 0; k < 3; ++k) TRY(upload(dmk[k], a->mk[k], (size_t)n * a->ldm * D, st));
-    TRY(upload(dx, a->x, (size_t)B * n * D, st));
+    TRY(upload(dx, a->x, bn * D, st));
     TRY(upload(dqs, a->qp_status, (size_t)B * I, st));
     if (vz) TRY(upload(dvs, a->vz_strength, (size_t)m * D, st));
-    if (a->vz_entry) TRY(upload(dve, a->vz_entry, (size_t)B * m * D, st));
-    TRY(gxin.up("x_in", a->x_in, (size_t)B * n * D, st));
-    TRY(gs.up("s", a->s, (size_t)B * 3 * n * D, st));
-    TRY(grho.up("rho", a->rho, (size_t)B * 3 * D, st));
-    TRY(gxmx.up("xmx", a->xmx, (size_t)B * 3 * D, st));
-    TRY(grv.up("rv", a->rv, (size_t)B * m * D, st));
-    TRY(gew.up("est_w", a->est_w, (size_t)B * m * D, st));
-    TRY(gw.up("w", a->w, (size_t)B * m * D, st));
-    TRY(gvf.up("var_floor", a->var_floor, (size_t)B * D, st));
-    TRY(gcs.up("coef_scale", a->coef_scale, (size_t)B * D, st));
-    TRY(gact.up("active", a->active, (size_t)B * I, st));
-    TRY(gfs.up("fit_status", a->fit_status, (size_t)B * I, st));
-    TRY(goi.up("outer_iters", a->outer_iters, (size_t)B * I, st));
-    TRY(gna.up("n_active", a->n_active, I, st));
-    if (a->outlier_t) TRY(got.up("outlier_t", a->outlier_t, (size_t)B * m * D, st));
-    if (prep) {
-        TRY(gdr.up("dop_rho", a->dop_rho, (size_t)B * 3 * D, st));
-        TRY(gdx.up("dop_xmx", a->dop_xmx, (size_t)B * 3 * D, st));
-    }
-    FitState fs{};
+    if (a->vz_entry) TRY(upload(dve, a->vz_entry, bm * D, st));
+    TRY(g.want("x_in", a->x_in, bn, fs.x_in, st)); TRY(g.want("s", a->s, 3 * bn, fs.s, st));
+    TRY(g.want("rho", a->rho, b3, fs.rho, st)); TRY(g.want("xmx", a->xmx, b3, fs.xmx, st));
+    TRY(g.want("rv", a->rv, bm, fs.rv, st)); TRY(g.want("est_w", a->est_w, bm, fs.est_w, st)); TRY(g.want("w", a->w, bm, fs.w, st));
+    TRY(g.want("var_floor", a->var_floor, B, fs.var_floor, st)); TRY(g.want("coef_scale", a->coef_scale, B, fs.coef_scale, st));
+    TRY(g.want("active", a->active, B, fs.active, st)); TRY(g.want("fit_status", a->fit_status, B, fs.fit_status, st));
+    TRY(g.want("outer_iters", a->outer_iters, B, fs.outer_iters, st)); TRY(g.want("n_active", a->n_active, 1, fs.n_active, st));
+    TRY(g.want("outlier_t", a->outlier_t, bm, fs.outlier_t, st));
+    TRY(g.want("dop_rho", prep ? a->dop_rho : nullptr, b3, fs.dop_rho, st)); TRY(g.want("dop_xmx", prep ? a->dop_xmx : nullptr, b3, fs.dop_xmx, st));
     fs.nf = 0; fs.m = m; fs.n = n; fs.ns = ns; fs.ldrm = a->ldrm; fs.ldm = a->ldm;
     fs.toeplitz_m = a->toeplitz ? 1 : 0; fs.toep_reach = a->toeplitz ? a->toep_reach : -1;
     fs.continue_mode = a->continue_mode; fs.min_iter = a->min_iter; fs.basis_area = a->basis_area; fs.opts = *a->opts;
     fs.prepared = prep ? 1 : 0; fs.desc = desc;
     fs.rm_stride = a->rm_batched ? (long long)m * a->ldrm : 0;
-    fs.rm = grm.dd(); fs.rm_rw = grm.dd();
+    fs.rm = fs.rm_rw;
     fs.vz_strength = vz ? dvs.d() : nullptr; fs.vz_entry = a->vz_entry ? dve.d() : nullptr;
-    fs.dop_rho = prep ? gdr.dd() : nullptr; fs.dop_xmx = prep ? gdx.dd() : nullptr;
-    fs.outlier_t = a->outlier_t ? got.dd() : nullptr;
     fs.vmm = dvmm.d(); fs.vmm_iw = dvmm.d();
     for (int k = 0; k < 3; ++k) fs.mk[k] = dmk[k].d();
-    fs.rv = grv.dd(); fs.w = gw.dd(); fs.est_w = gew.dd();
-    fs.x = dx.d(); fs.x_in = gxin.dd(); fs.s = gs.dd(); fs.rho = grho.dd(); fs.xmx = gxmx.dd();
-    fs.coef_scale = gcs.dd(); fs.var_floor = gvf.dd();
-    fs.active = gact.di(); fs.outer_iters = goi.di(); fs.fit_status = gfs.di();
-    fs.qp_status = dqs.i(); fs.n_active = gna.di();
+    fs.x = dx.d(); fs.qp_status = dqs.i();
     fs.hist_b = -1; fs.hist_cap = 0;
     if (a->products) {
         HIPDRT_CHECK(dpremv.alloc(3 * (size_t)B * m * D));
@@ -280,10 +285,7 @@ int hipdrt_debug_hyper_step(hipdrt_ctx* ctx, const hipdrt_debug_hyper_args* a) t
     }
     TRY(launch_hyper(st, fs, B, a->it));
     LAUNCH_OK();
-    Guarded* all[] = {&grm, &gxin, &gs, &grho, &gxmx, &grv, &gew, &gw, &gvf, &gcs, &gact, &gfs, &goi, &gna, &got, &gdr, &gdx};
-    for (Guarded* g : all) if (g->buf.p) TRY(g->fetch(st));
-    HIPDRT_CHECK(hipStreamSynchronize(st));
-    for (Guarded* g : all) if (g->buf.p) TRY(g->check());
+    TRY(g.back(st));
     // the response matrix: nothing but the vz_offset column may differ from what was uploaded
     const int nmat = a->rm_batched ? B : 1;
     for (int b = 0; b < nmat; ++b)
@@ -319,12 +321,12 @@ int hipdrt_debug_kk_stats(hipdrt_ctx* ctx, int B, int nf, const double* freq, co
     TRY(upload(dim, err_im, (size_t)B * nf * sizeof(double), st));
     KkArgs a{};
     a.nf = nf; a.desc = order > 0 ? 1 : 0; a.freq = dfreq.d(); a.o = o; a.in_re = dre.d(); a.in_im = dim.d();
-    KkOut out;
-    TRY(out.alloc(a, B, nf, false, false, false, false, std_out, outlier_mask, f_lim, i_lim, status));
+    DevOuts outs;
+    TRY(outs.want(std_out, (size_t)B, a.std)); TRY(outs.want(outlier_mask, (size_t)B * nf, a.mask));
+    TRY(outs.want(f_lim, (size_t)B * 2, a.f_lim)); TRY(outs.want(i_lim, (size_t)B * 2, a.i_lim)); TRY(outs.want(status, (size_t)B, a.status));
     TRY(launch_kk(st, nullptr, a, B));
     LAUNCH_OK();
-    TRY(KkOut::back(std_out, out.sd, st)); TRY(KkOut::back(outlier_mask, out.mask, st));
-    TRY(KkOut::back(f_lim, out.flim, st)); TRY(KkOut::back(i_lim, out.ilim, st)); TRY(KkOut::back(status, out.status, st));
+    TRY(outs.back(st));
     HIPDRT_CHECK(hipStreamSynchronize(st));
     return HIPDRT_OK;
 } HIPDRT_CATCH
@@ -386,25 +388,17 @@ int hipdrt_debug_find_peaks(hipdrt_ctx* ctx, int B, int neval, const double* fxx
     for (int k = 0; k < 4; ++k) if (rows[k]) TRY(upload(din[k], rows[k], bn * sizeof(double), st));
     PeakArgs a{};
     a.neval = neval; a.o = o; a.fxx = din[0].d(); a.f = din[1].d(); a.var_fxx = din[2].d(); a.var_f = din[3].d(); a.ldv = neval;
-    Guarded g[11];
-    const size_t D = sizeof(double), I = sizeof(int);
-    if (peak_sign) { TRY(g[0].up("peak_sign", peak_sign, bn * I, st)); a.peak_sign = g[0].di(); }
-    if (keep) { TRY(g[1].up("keep", keep, bn * I, st)); a.keep = g[1].di(); }
-    if (heights) { TRY(g[2].up("heights", heights, bn * D, st)); a.heights = g[2].dd(); }
-    if (prominences) { TRY(g[3].up("prominences", prominences, bn * D, st)); a.prominences = g[3].dd(); }
-    if (probs) { TRY(g[4].up("probs", probs, bn * D, st)); a.probs = g[4].dd(); }
-    if (left_bases) { TRY(g[5].up("left_bases", left_bases, bn * I, st)); a.left_bases = g[5].di(); }
-    if (right_bases) { TRY(g[6].up("right_bases", right_bases, bn * I, st)); a.right_bases = g[6].di(); }
-    if (count) { TRY(g[7].up("count", count, (size_t)B * I, st)); a.count = g[7].di(); }
-    if (used_prominence) { TRY(g[8].up("used_prominence", used_prominence, (size_t)B * D, st)); a.used_prominence = g[8].dd(); }
-    if (peak_prob && o.method == 2) { TRY(g[9].up("peak_prob", peak_prob, bn * D, st)); a.peak_prob = g[9].dd(); }
-    if (curv_prob && o.method == 2) { TRY(g[10].up("curv_prob", curv_prob, bn * D, st)); a.curv_prob = g[10].dd(); }
+    GuardedOuts outs;
+    TRY(outs.want("peak_sign", peak_sign, bn, a.peak_sign, st)); TRY(outs.want("keep", keep, bn, a.keep, st));
+    TRY(outs.want("heights", heights, bn, a.heights, st)); TRY(outs.want("prominences", prominences, bn, a.prominences, st));
+    TRY(outs.want("probs", probs, bn, a.probs, st));
+    TRY(outs.want("left_bases", left_bases, bn, a.left_bases, st)); TRY(outs.want("right_bases", right_bases, bn, a.right_bases, st));
+    TRY(outs.want("count", count, (size_t)B, a.count, st)); TRY(outs.want("used_prominence", used_prominence, (size_t)B, a.used_prominence, st));
+    TRY(outs.want("peak_prob", o.method == 2 ? peak_prob : nullptr, bn, a.peak_prob, st));
+    TRY(outs.want("curv_prob", o.method == 2 ? curv_prob : nullptr, bn, a.curv_prob, st));
     TRY(launch_peaks(st, a, B));
     LAUNCH_OK();
-    for (Guarded& q : g) if (q.buf.p) TRY(q.fetch(st));
-    HIPDRT_CHECK(hipStreamSynchronize(st));
-    for (Guarded& q : g) if (q.buf.p) TRY(q.check());
-    return HIPDRT_OK;
+    return outs.back(st);
 } HIPDRT_CATCH
 
 // test hooks (include/hipdrt_debug.h): the two kernels of pfrt.hip as they are, on host arrays; outputs between borders of marker bytes
@@ -454,24 +448,16 @@ int hipdrt_debug_pfrt_combine(hipdrt_ctx* ctx, int B, int S, int neval_pfrt, int
     TRY(upload(dlnf, lnf.data(), (size_t)S * sizeof(double), st));
     TRY(upload(dltp, ln_tau_pfrt, (size_t)np * sizeof(double), st));
     if (o.smooth) TRY(upload(dlto, ln_tau_out, (size_t)nout * sizeof(double), st));
-    PfrtCombineArgs a{};
+    PfrtCombineArgs a = pfrt_combine_args(o, m);
     a.S = S; a.np = np; a.nout = nout; a.ld_step = (long long)B * np; a.ld_sum = B;
     a.step_pfrt = dstep.d(); a.rss = drss.d(); a.slw = dslw.d(); a.ln_factors = dlnf.d();
-    pfrt_llh_consts(m, &a.c, &a.alpha_n, &a.beta_0);
-    a.prior_mu = o.prior_mu; a.prior_sigma = o.prior_sigma; a.n_eff = o.n_eff_factor;
-    a.smooth = o.smooth != 0; a.smooth_order = o.smooth_order; a.smooth_eps = o.smooth_epsilon;
-    a.integrate = o.integrate != 0; a.thr = o.integrate_threshold; a.normalize = o.normalize != 0;
     a.ltp = dltp.d(); a.lto = dlto.d();
-    Guarded g[3];
-    if (pfrt) { TRY(g[0].up("pfrt", pfrt, (size_t)B * nout * sizeof(double), st)); a.pfrt = g[0].dd(); }
-    if (raw_pfrt) { TRY(g[1].up("raw_pfrt", raw_pfrt, (size_t)B * np * sizeof(double), st)); a.raw = g[1].dd(); }
-    if (post_prob) { TRY(g[2].up("post_prob", post_prob, (size_t)S * B * sizeof(double), st)); a.post = g[2].dd(); }
+    GuardedOuts outs;
+    TRY(outs.want("pfrt", pfrt, (size_t)B * nout, a.pfrt, st)); TRY(outs.want("raw_pfrt", raw_pfrt, (size_t)B * np, a.raw, st));
+    TRY(outs.want("post_prob", post_prob, (size_t)S * B, a.post, st));
     TRY(launch_pfrt_combine(st, a, B));
     LAUNCH_OK();
-    for (Guarded& q : g) if (q.buf.p) TRY(q.fetch(st));
-    HIPDRT_CHECK(hipStreamSynchronize(st));
-    for (Guarded& q : g) if (q.buf.p) TRY(q.check());
-    return HIPDRT_OK;
+    return outs.back(st);
 } HIPDRT_CATCH
 
 // test hook (include/hipdrt_debug.h): peak_resolve_kernel as it is, on host arrays.  Every output sits between two borders of marker bytes.
@@ -522,25 +508,18 @@ int hipdrt_debug_peak_resolve(hipdrt_ctx* ctx, const hipdrt_debug_peak_resolve_a
     } else {
         a.basis_area = q->basis_eps > 0.0 ? 1.7724538509055159 / q->basis_eps : 1.0;
     }
-    Guarded g[10];
-    const size_t D = sizeof(double), I = sizeof(int), bm = (size_t)B * mp;
+    const size_t bm = (size_t)B * mp;
     const hipdrt_peak_resolve_out& u = q->out;
-    if (u.count) { TRY(g[0].up("count", u.count, (size_t)B * I, st)); a.count = g[0].di(); }
-    if (u.status) { TRY(g[1].up("status", u.status, (size_t)B * I, st)); a.status = g[1].di(); }
-    if (u.peak_index) { TRY(g[2].up("peak_index", u.peak_index, bm * I, st)); a.peak_index = g[2].di(); }
-    if (u.trough_index) { TRY(g[3].up("trough_index", u.trough_index, bm * I, st)); a.trough_index = g[3].di(); }
-    if (u.eps_l) { TRY(g[4].up("eps_l", u.eps_l, bm * D, st)); a.eps_l = g[4].dd(); }
-    if (u.eps_r) { TRY(g[5].up("eps_r", u.eps_r, bm * D, st)); a.eps_r = g[5].dd(); }
-    if (u.r_peaks) { TRY(g[6].up("r_peaks", u.r_peaks, bm * D, st)); a.r_peaks = g[6].dd(); }
-    if (u.r_coef) { TRY(g[7].up("r_coef", u.r_coef, bm * D, st)); a.r_coef = g[7].dd(); }
-    if (u.x_peaks) { TRY(g[8].up("x_peaks", u.x_peaks, bm * nb * D, st)); a.x_peaks = g[8].dd(); }
-    if (u.peak_gammas && nout > 0) { TRY(g[9].up("peak_gammas", u.peak_gammas, bm * nout * D, st)); a.peak_gammas = g[9].dd(); }
+    GuardedOuts outs;
+    TRY(outs.want("count", u.count, (size_t)B, a.count, st)); TRY(outs.want("status", u.status, (size_t)B, a.status, st));
+    TRY(outs.want("peak_index", u.peak_index, bm, a.peak_index, st)); TRY(outs.want("trough_index", u.trough_index, bm, a.trough_index, st));
+    TRY(outs.want("eps_l", u.eps_l, bm, a.eps_l, st)); TRY(outs.want("eps_r", u.eps_r, bm, a.eps_r, st));
+    TRY(outs.want("r_peaks", u.r_peaks, bm, a.r_peaks, st)); TRY(outs.want("r_coef", u.r_coef, bm, a.r_coef, st));
+    TRY(outs.want("x_peaks", u.x_peaks, bm * nb, a.x_peaks, st));
+    TRY(outs.want("peak_gammas", nout > 0 ? u.peak_gammas : nullptr, bm * nout, a.peak_gammas, st));
     TRY(launch_peak_resolve(st, a, B));
     LAUNCH_OK();
-    for (Guarded& w : g) if (w.buf.p) TRY(w.fetch(st));
-    HIPDRT_CHECK(hipStreamSynchronize(st));
-    for (Guarded& w : g) if (w.buf.p) TRY(w.check());
-    return HIPDRT_OK;
+    return outs.back(st);
 } HIPDRT_CATCH
 
 // tools hook: kernel time of the last hipdrt_plan_predict_drt or hipdrt_plan_predict_z on this context

@@ -1,5 +1,5 @@
-// The plan (include/hipdrt.h): creation, upload and the setters, what is read back from it (matrices, results, history,
-// timings), and the one-call hipdrt_fit_eis_batch.  Its device fit loop is plan_fit.hip, what reads a finished fit plan_post.hip.
+// The plan (include/hipdrt.h): creation, upload and the setters, what is read back from it (matrices, results, history, timings),
+// and the one-call hipdrt_fit_eis_batch.  Its device fit loop is plan_fit.hip, what reads a finished fit plan_post.hip and plan_drt.hip.
 #include <cmath>
 #include <cstring>
 

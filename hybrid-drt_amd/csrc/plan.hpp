@@ -1,6 +1,6 @@
 // Internal declarations shared by the host-side translation units of the C-ABI (api.hip, operators.hip, debug.hip, plan.hip,
-// plan_fit.hip, plan_post.hip): the plan itself, the entry points' error handling, and the few functions that cross those
-// files.  Never included by a kernel file: what those see is common.hpp.
+// plan_fit.hip, plan_post.hip, plan_drt.hip): the plan itself, the entry points' error handling, the table of an entry point's
+// optional outputs, and the few functions that cross those files.  Never included by a kernel file: what those see is common.hpp.
 #pragma once
 #include <memory>
 #include <mutex>
@@ -42,6 +42,30 @@ inline int copy_strided(double* out, const double* dev, int rows, int cols, int 
     HIPDRT_CHECK(hipStreamSynchronize(st));
     return 0;
 }
+
+// The device twins of the optional host outputs of one entry point.  One want() per output, in the order of the argument list;
+// one back() after the launch queues every copy to the host in that order.  (A fixed array: a DevBuf must not move.)
+struct DevOuts {
+    static constexpr int MAX = 12;         // hipdrt_plan_find_peaks has 11
+    DevBuf buf[MAX];
+    void* host[MAX] = {};
+    int n = 0;
+    // `count` elements of T on the device for the host array h, and the kernel argument that points at them; a null h does
+    // nothing and leaves the field null, unless the kernel needs the array whatever the caller asked for (force)
+    template <class T>
+    int want(T* h, size_t count, T*& field, bool force = false) {
+        if (!h && !force) return HIPDRT_OK;
+        HIPDRT_REQUIRE(n < MAX, "internal: more optional outputs than DevOuts holds");
+        HIPDRT_CHECK(buf[n].alloc(count * sizeof(T)));
+        field = buf[n].as<T>(); host[n++] = h;
+        return HIPDRT_OK;
+    }
+    int back(hipStream_t st) const {
+        for (int i = 0; i < n; ++i)
+            if (host[i]) HIPDRT_CHECK(hipMemcpyAsync(host[i], buf[i].p, buf[i].bytes, hipMemcpyDeviceToHost, st));
+        return HIPDRT_OK;
+    }
+};
 
 // +1: strictly descending, -1: strictly ascending, 0: neither
 inline int freq_monotone(const double* f, int nf) {
@@ -194,31 +218,49 @@ GramL2 plan_l2(const hipdrt_plan* p, double l2_lambda_0, const double* derivativ
 
 // ---- Kramers-Kronig screening: plan_post.hip (hipdrt_plan_kk_screen) and its stage-B test hook in debug.hip --------------------
 int kk_check_opts(const hipdrt_kk_opts& o);
-// ---- per-peak resolution: plan_post.hip (hipdrt_plan_resolve_peaks) and its test hook in debug.hip -------------------------------
+
+// ---- plan_post.hip: the fitted state and its final P, for the posterior entry points there and the DRT chain of plan_drt.hip ------
+// Where a posterior computation reads the fitted state from: the plan's live buffers (what the last fit or warm restart left), or
+// one recorded step of the PFRT store with the raw re-estimated weights of that step (step_source).  All [B]-major with the
+// strides of the live buffers.
+struct PostSource { const double *x, *s, *rho, *dop_rho, *w; const int* fit_status; };
+PostSource live_source(const hipdrt_plan* p);
+PostSource step_source(const hipdrt_plan* p, int step, const double* w, const int* fit_status);
+// What the posterior entry points call "the final P": calculate_pq with the final weights / s / rho (drt1d.py:1006), from
+// calculate_pq's scaled_weights -- w_eff whenever the plan has weight factors.  b >= 0: s, rho, dop_rho and the weights of
+// spectrum b alone.
+struct FinalP { GramL2 g; const double* w; };
+FinalP plan_final_p(const hipdrt_plan* p, int b, const PostSource& src);
+// rows_dev[neval][ncol] in device memory (it sits at columns col_offset.. of the unknown vector, zero elsewhere) ->
+// dout[nb][nex * 16] = rows_i' P^-1 rows_i (not yet scaled by cs^2) and dstat[nb], of spectrum b alone (nb = 1) or, b = -1, of
+// the batch (nb = B).  The caller owns the scratch: Y = rows L^-T of the last factorisation stays in it.
+int plan_quadratic_forms_dev(hipdrt_plan* p, const PostSource& src, int b, const double* rows_dev, int neval, int ncol,
+                             int col_offset, DevBuf& scratch, DevBuf& dout, DevBuf& dstat);
+// kernel time of the last prediction on a context (hipdrt_debug_last_predict_ms): HIP events around the launches
+struct PredictTimer {
+    hipdrt_ctx* ctx; hipStream_t st; hipEvent_t e[3] = {nullptr, nullptr, nullptr}; int n = 0;
+    PredictTimer(hipdrt_ctx* c, hipStream_t s) : ctx(c), st(s) { mark(); }
+    void mark() { if (n < 3 && hipEventCreate(&e[n]) == hipSuccess) { (void)hipEventRecord(e[n], st); ++n; } }
+    // (destroyed after the stream has been synchronised) [0] up to the second mark, [1] up to the last one
+    ~PredictTimer() {
+        float a = 0.f, b = 0.f;
+        if (n >= 2 && hipEventElapsedTime(&a, e[0], e[1]) == hipSuccess && hipEventElapsedTime(&b, e[0], e[n - 1]) == hipSuccess) {
+            ctx->predict_ms[0] = a; ctx->predict_ms[1] = b;
+        }
+        for (int i = 0; i < n; ++i) (void)hipEventDestroy(e[i]);
+        (void)hipGetLastError();
+    }
+};
+
+// ---- plan_drt.hip: the DRT chain (prediction, peaks, per-peak resolution, PFRT) and the test hooks of its kernels in debug.hip ----
+// the tau basis a prediction evaluates: the plan's own grid, or what hipdrt_plan_set_tau_basis gave a prepared plan
+struct PredictBasis { const double* ln_tau; int nb, copies; double eps; };
+int predict_basis(const hipdrt_plan* p, PredictBasis& pb);
 // host checks of the caller's peak source: index rows [B][max_peaks] in range, strictly increasing, -1 only as padding at the
 // end; windows 0 <= start < min(end, nfind), starts and ends ascending
 int peak_resolve_check_source(int source, const int* indices, int B, int max_peaks, const int* win_start, const int* win_end,
                               int nwin, int nfind);
+// what launch_pfrt_combine takes from the options and the number of data rows m; sizes, strides and pointers are the caller's
+PfrtCombineArgs pfrt_combine_args(const hipdrt_pfrt_opts& o, int m);
 }  // namespace hipdrt
 
-// device outputs of one kk launch for B spectra of nf frequencies, and their way back to the host
-struct KkOut {
-    DevBuf zr, zi, er, ei, sd, mask, flim, ilim, status;
-    int alloc(KkArgs& a, int B, int nf, bool z, bool zi_, bool e, bool ei_, bool sd_, bool mask_, bool fl, bool il, bool stt) {
-        const size_t bn = (size_t)B * nf;
-        if (z) { HIPDRT_CHECK(zr.alloc(bn * sizeof(double))); a.z_re = zr.d(); }
-        if (zi_) { HIPDRT_CHECK(zi.alloc(bn * sizeof(double))); a.z_im = zi.d(); }
-        if (e) { HIPDRT_CHECK(er.alloc(bn * sizeof(double))); a.e_re = er.d(); }
-        if (ei_) { HIPDRT_CHECK(ei.alloc(bn * sizeof(double))); a.e_im = ei.d(); }
-        if (sd_) { HIPDRT_CHECK(sd.alloc((size_t)B * sizeof(double))); a.std = sd.d(); }
-        if (mask_) { HIPDRT_CHECK(mask.alloc(bn * sizeof(int))); a.mask = mask.i(); }
-        if (fl) { HIPDRT_CHECK(flim.alloc((size_t)B * 2 * sizeof(double))); a.f_lim = flim.d(); }
-        if (il) { HIPDRT_CHECK(ilim.alloc((size_t)B * 2 * sizeof(int))); a.i_lim = ilim.i(); }
-        if (stt) { HIPDRT_CHECK(status.alloc((size_t)B * sizeof(int))); a.status = status.i(); }
-        return HIPDRT_OK;
-    }
-    static int back(void* host, const DevBuf& d, hipStream_t st) {
-        if (host && d.p) HIPDRT_CHECK(hipMemcpyAsync(host, d.p, d.bytes, hipMemcpyDeviceToHost, st));
-        return HIPDRT_OK;
-    }
-};
