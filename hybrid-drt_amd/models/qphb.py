@@ -28,6 +28,15 @@ def get_default_hypers(eff_hp=True, fit_dop=False, nu_basis_type='gaussian'):
     return hypers
 
 
+def marginal_llh(rss, m, alpha_0=2, beta_0=1):
+    """the weight-marginalised log-likelihood of qphb.evaluate_llh (hybdrt/models/qphb.py:1355-1377) without its sum of log
+    weights, from the residual sum of squares of m data rows (a scalar or one entry per spectrum)"""
+    from scipy.special import loggamma
+    alpha_n = alpha_0 - 1 + m / 2
+    beta_n = beta_0 + 0.5 * rss
+    return alpha_0 * np.log(beta_0) - alpha_n * np.log(beta_n) + loggamma(alpha_n) - loggamma(alpha_0)
+
+
 def get_num_special(special_qp_params):
     """qphb.py:44-48."""
     if len(special_qp_params) == 0:
