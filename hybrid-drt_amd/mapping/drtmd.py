@@ -1,6 +1,12 @@
-"""Batch driver: the fit-loop contract of hybdrt.mapping.drtmd.DRTMD (drtmd.py:186-329, 1136-1158) for
-observations that share one frequency grid, with optional sharding over ranks (one process per GPU)."""
+"""Mapping drivers: the fit-loop contract of hybdrt.mapping.drtmd.DRTMD (drtmd.py:186-329, 1136-1158) on device batches --
+fit_observations for spectra that share one frequency grid (one batch, consecutive chunks, or sibling plans in flight),
+fit_observation_list for any mix of data types and grids (one batch per group of like observations), fit_observations_pfrt for
+fit_type='pfrt' (one solution per regularisation factor), fit_observations_sharded for a map dealt over ranks (one process per
+GPU) and gathered on one of them.  What they keep per observation, and how a fitted group gets there, is table.py's."""
 import numpy as np
+
+from .table import GATHER_COLUMNS, ObsTable, fit_errors, merge_chunk_results, raise_first_error, zero_failed
+from .table import pack_rows as _pack_rows, unpack_block as _unpack_block  # noqa: F401  (the names the tests reach them by)
 
 
 def shard_bounds(num_obs, world_size, rank):
@@ -43,9 +49,6 @@ def shard_indices(num_obs, world_size, rank, scheme='interleave', cost=None):
         owner = np.where(rnd % 2 == 0, lane, world_size - 1 - lane)     # serpentine: 0..W-1, W-1..0, ...
         return np.sort(order[owner == rank])
     raise ValueError(f"unknown sharding scheme {scheme!r}")
-
-
-_NOT_PER_OBS = ('basis_tau', 'timings_ms', 'launches', 'obs_tau_indices', 'obs_fit_errors')
 
 
 def auto_inflight(num_obs):
@@ -126,24 +129,7 @@ def _fit_observations_inflight(drt, frequencies, z_obs, inflight, tau_supergrid,
     for exc in errs:
         if exc is not None:
             raise exc
-    return _merge_chunk_results(outs, chunks, ignore_errors)
-
-
-def _merge_chunk_results(outs, chunks, ignore_errors):
-    """results of fit_observations on consecutive chunks of one map -> the result for the whole map"""
-    obs_x = np.concatenate([o[0] for o in outs])
-    obs_special = {k: np.concatenate([o[1][k] for o in outs]) for k in outs[0][1]}
-    res = {}
-    for k, v in outs[0][2].items():
-        if k in _NOT_PER_OBS:
-            res[k] = v
-        elif isinstance(v, np.ndarray) and v.ndim >= 1 and v.shape[0] == len(chunks[0]):
-            res[k] = np.concatenate([o[2][k] for o in outs])
-        else:
-            res[k] = v
-    res['obs_fit_errors'] = [e for o in outs for e in o[2]['obs_fit_errors']]
-    _raise_first_error(res, ignore_errors)
-    return obs_x, obs_special, res
+    return merge_chunk_results(outs, chunks, ignore_errors)
 
 
 def max_batch_for(drt, frequencies):
@@ -164,14 +150,6 @@ def max_batch_for(drt, frequencies):
         return max(1, int(0.8 * ctx.device_info()['hbm_bytes'] / per))
     except (AttributeError, TypeError):
         return None
-
-
-def _raise_first_error(res, ignore_errors):
-    """fit_observation's error contract (drtmd.py:292-301): without ignore_errors the first failed observation raises"""
-    if not ignore_errors and not np.all(res['obs_fit_status']):
-        bad = int(np.flatnonzero(~np.asarray(res['obs_fit_status']))[0])
-        print(f"Error encountered at obs_index {bad}")
-        raise res['obs_fit_errors'][bad]
 
 
 def _metric_kw(llh_kw, rss_kw):
@@ -273,19 +251,11 @@ def fit_observation_list(drt, observations, tau_supergrid, drt_var=False, ignore
     tau_supergrid = np.asarray(tau_supergrid, dtype=float)
     num = len(observations)
     llh_kw, rss_kw = _metric_kw(llh_kw, rss_kw)
-    obs_x = np.zeros((num, len(tau_supergrid)))
-    obs_special = {}
-    res = dict(obs_llh=np.zeros(num), obs_rss=np.zeros(num), obs_tau_indices=[None] * num, obs_group=np.zeros(num, dtype=int),
-               obs_fit_status=np.zeros(num, dtype=bool), obs_fit_errors=[None] * num, outer_iters=np.zeros(num, dtype=np.int64),
-               qp_iters_total=np.zeros(num, dtype=np.int64), status=np.zeros(num, dtype=np.int64), groups=[])
-    if drt_var:
-        res['obs_drt_var'] = np.zeros((num, len(tau_supergrid)))
-        res['obs_drt_var_ok'] = np.zeros(num, dtype=bool)
+    table = ObsTable(num, (len(tau_supergrid),), drt_var, GATHER_COLUMNS, groups=True)
     tags, step_times = None, [None] * num
     if fit_kw.get('remove_extremes') or fit_kw.get('remove_outliers'):
         observations, fit_kw, tags, step_times = prefilter_observations(drt, observations, fit_kw)
-    for g, (kind, idx) in enumerate(observation_groups(observations, tags)):
-        idx = np.asarray(idx)
+    for kind, idx in observation_groups(observations, tags):
         if kind == 'eis':
             freq = np.asarray(observations[idx[0]][1][0], dtype=float)
             out = drt.fit_eis_batch(freq, np.array([observations[k][1][1] for k in idx]), **fit_kw)
@@ -297,33 +267,12 @@ def fit_observation_list(drt, observations, tau_supergrid, drt_var=False, ignore
                 group_kw = dict(fit_kw, step_times=step_times[idx[0]], step_sizes=None)
             out = drt._fit_prepared_batch(meas, group_kw)
             special_keys = [key for key in drt.special_qp_params if key in out]
-        basis_tau = out['basis_tau']
-        left, right = _supergrid_slots(tau_supergrid, basis_tau)
-        ok = np.asarray(out['status']) >= 0
-        obs_x[idx, left:right] = np.where(ok[:, None], out['fit_x'], 0.0)
-        for key in special_keys:
-            val = np.asarray(out[key], dtype=float)
-            if key not in obs_special:          # (initialize_obs_special / the "key is new" branch of drtmd.py:281-285)
-                obs_special[key] = np.zeros((num,) + val.shape[1:])
-            obs_special[key][idx] = np.where(ok.reshape((-1,) + (1,) * (val.ndim - 1)), val, 0.0)
+        span = _supergrid_slots(tau_supergrid, out['basis_tau'])
         llh, rss = drt.evaluate_obs_llh_rss_batch(llh_kw=llh_kw, rss_kw=rss_kw)
-        res['obs_llh'][idx], res['obs_rss'][idx] = np.where(ok, llh, 0.0), np.where(ok, rss, 0.0)
-        res['obs_fit_status'][idx] = ok
-        res['obs_group'][idx] = g
-        for key in ('outer_iters', 'qp_iters_total', 'status'):
-            res[key][idx] = out[key]
-        for j, k in enumerate(idx):
-            res['obs_tau_indices'][k] = (left, right)
-            if not ok[j]:
-                res['obs_fit_errors'][k] = ValueError("Rank(A) < p or Rank([P; A; G]) < n")
-        if drt_var:
-            var, vok = drt.estimate_distribution_var_batch(tau=tau_supergrid, extend_var=True)
-            vok = np.asarray(vok, dtype=bool) & ok
-            res['obs_drt_var'][idx] = np.where(vok[:, None], var, 0.0)
-            res['obs_drt_var_ok'][idx] = vok
-        res['groups'].append(dict(kind=kind, indices=idx, basis_tau=basis_tau, tau_indices=(left, right)))
-    _raise_first_error(res, ignore_errors)
-    return obs_x, obs_special, res
+        var, vok = drt.estimate_distribution_var_batch(tau=tau_supergrid, extend_var=True) if drt_var else (None, None)
+        table.scatter(idx, np.asarray(out['status']) >= 0, out['fit_x'], span, {key: out[key] for key in special_keys}, llh, rss,
+                      {key: out[key] for key in GATHER_COLUMNS}, var=var, vok=vok, group=(kind, out['basis_tau']))
+    return table.result(ignore_errors)          # (a failed observation raises here, after every group was fitted)
 
 
 def fit_observations_pfrt(drt, observations, tau_supergrid, pfrt_factors=None, drt_var=False, ignore_errors=False,
@@ -350,14 +299,9 @@ def fit_observations_pfrt(drt, observations, tau_supergrid, pfrt_factors=None, d
     factors = np.logspace(-1, 1, 11) if pfrt_factors is None else np.asarray(pfrt_factors, dtype=float)
     num, S, nsup = len(observations), len(factors), len(tau_supergrid)
     llh_kw, rss_kw = _metric_kw(llh_kw, rss_kw)
-    obs_x = np.zeros((num, S, nsup))
-    obs_special = {}
-    res = dict(obs_llh=np.zeros(num), obs_rss=np.zeros(num), obs_tau_indices=[None] * num, obs_group=np.zeros(num, dtype=int),
-               obs_fit_status=np.zeros(num, dtype=bool), obs_fit_errors=[None] * num, status=np.zeros(num, dtype=np.int64),
-               step_llh=np.zeros((num, S)), step_iters=np.zeros((num, S), dtype=np.int64), pfrt_factors=factors, groups=[])
-    if drt_var:
-        res['obs_drt_var'] = np.zeros((num, S, nsup))
-        res['obs_drt_var_ok'] = np.zeros(num, dtype=bool)
+    table = ObsTable(num, (S, nsup), drt_var, dict(status=np.int64, step_llh=(float, (S,)), step_iters=(np.int64, (S,))), groups=True)
+    res = table.res
+    res['pfrt_factors'] = factors
     if predict_pfrt_kw is not None:
         ppk = dict(predict_pfrt_kw)
         ppk.setdefault('tau_pfrt', tau_supergrid)
@@ -366,8 +310,7 @@ def fit_observations_pfrt(drt, observations, tau_supergrid, pfrt_factors=None, d
             raise ValueError('predict_pfrt_kw: tau and tau_pfrt must have the length of tau_supergrid')
         res['obs_pfrt'], res['obs_raw_pfrt'] = np.full((num, nsup), np.nan), np.full((num, nsup), np.nan)
     pf_kw = {k: fit_kw.pop(k) for k in ('max_iter_per_step', 'max_init_iter', 'xtol', 'nonneg') if k in fit_kw}
-    for g, (kind, idx) in enumerate(observation_groups(observations)):
-        idx = np.asarray(idx)
+    for kind, idx in observation_groups(observations):
         first = {}
 
         def after_init(out, first=first):
@@ -393,11 +336,7 @@ def fit_observations_pfrt(drt, observations, tau_supergrid, pfrt_factors=None, d
                 tot, info = drt.predict_pfrt_batch(return_info=True, **ppk)
                 res['obs_pfrt'][idx], res['obs_raw_pfrt'][idx] = tot, info['raw_pfrt']
         else:
-            meas = []
-            for k in idx:
-                chrono, eis = observations[k]
-                eis = eis if (eis is not None and eis[0] is not None) else (None, None)
-                meas.append((chrono[0], chrono[1], chrono[2], eis[0], eis[1]))
+            meas = [_as_measurement(observations[k]) for k in idx]
             preps, out, hypers, kw2, ckw = drt._pfrt_prepared(meas, factors, pf_kw.get('max_iter_per_step', 10),
                                                               pf_kw.get('max_init_iter', 20), pf_kw.get('xtol', 1e-2),
                                                               pf_kw.get('nonneg', True), dict(fit_kw), after_init=after_init)
@@ -408,30 +347,13 @@ def fit_observations_pfrt(drt, observations, tau_supergrid, pfrt_factors=None, d
             fx = np.array([[fp['x'] for fp in row] for row in fps])
             specials = {key: np.array([[np.asarray(fp[key], dtype=float) for fp in row] for row in fps])
                         for key in drt.special_qp_params if key in fps[0][0]}
-        left, right = _supergrid_slots(tau_supergrid, basis_tau)
-        ok = np.asarray(pr['status']) >= 0
-        obs_x[idx, :, left:right] = np.where(ok[:, None, None], np.swapaxes(fx, 0, 1), 0.0)
-        for key, val in specials.items():
-            val = np.swapaxes(val, 0, 1)                                                  # (B, S[, size])
-            if key not in obs_special:
-                obs_special[key] = np.zeros((num,) + val.shape[1:])
-            obs_special[key][idx] = np.where(ok.reshape((-1,) + (1,) * (val.ndim - 1)), val, 0.0)
-        res['obs_llh'][idx], res['obs_rss'][idx] = np.where(ok, first['llh'], 0.0), np.where(ok, first['rss'], 0.0)
-        res['step_llh'][idx], res['step_iters'][idx] = pr['step_llh'].T, pr['step_iters'].T
-        res['obs_fit_status'][idx] = ok
-        res['status'][idx] = pr['status']
-        res['obs_group'][idx] = g
-        for j, k in enumerate(idx):
-            res['obs_tau_indices'][k] = (left, right)
-            if not ok[j]:
-                res['obs_fit_errors'][k] = ValueError("Rank(A) < p or Rank([P; A; G]) < n")
-        if drt_var:
-            vok = np.asarray(first['vok'], dtype=bool) & ok
-            res['obs_drt_var'][idx] = np.where(vok[:, None, None], first['var'][:, None, :], 0.0)   # one variance, every factor
-            res['obs_drt_var_ok'][idx] = vok
-        res['groups'].append(dict(kind=kind, indices=idx, basis_tau=basis_tau, tau_indices=(left, right)))
-    _raise_first_error(res, ignore_errors)
-    return obs_x, obs_special, res
+        span = _supergrid_slots(tau_supergrid, basis_tau)
+        var = first['var'][:, None, :] if drt_var else None                                   # one variance, every factor
+        table.scatter(idx, np.asarray(pr['status']) >= 0, np.swapaxes(fx, 0, 1),            # (B, S, ntau), specials (B, S[, size])
+                      span, {key: np.swapaxes(val, 0, 1) for key, val in specials.items()}, first['llh'], first['rss'],
+                      dict(status=pr['status'], step_llh=pr['step_llh'].T, step_iters=pr['step_iters'].T),
+                      var=var, vok=first.get('vok'), group=(kind, basis_tau))
+    return table.result(ignore_errors)
 
 
 def fit_observations(drt, frequencies=None, z_obs=None, tau_supergrid=None, drt_var=False, ignore_errors=False, llh_kw=None,
@@ -486,36 +408,29 @@ def fit_observations(drt, frequencies=None, z_obs=None, tau_supergrid=None, drt_
         chunks = [c for c in np.array_split(np.arange(z_obs.shape[0]), parts) if len(c)]
         outs = [fit_observations(drt, frequencies, z_obs[c], tau_supergrid=tau_supergrid, drt_var=drt_var, ignore_errors=True,
                                  llh_kw=llh_kw, rss_kw=rss_kw, inflight=1, max_batch=limit, **fit_kw) for c in chunks]
-        return _merge_chunk_results(outs, chunks, ignore_errors)
+        return merge_chunk_results(outs, chunks, ignore_errors)
     llh_kw, rss_kw = _metric_kw(llh_kw, rss_kw)
     res = drt.fit_eis_batch(frequencies, z_obs, **fit_kw)
-    num = z_obs.shape[0]
     basis_tau = res['basis_tau']
-    if tau_supergrid is None:
-        tau_supergrid = basis_tau
-    tau_supergrid = np.asarray(tau_supergrid)
-    left = int(np.argmin(np.abs(np.log(tau_supergrid) - np.log(basis_tau[0]))))
+    tau_supergrid = np.asarray(basis_tau if tau_supergrid is None else tau_supergrid)
+    # (the right end is counted from the left one here, the list and PFRT forms look it up as well, _supergrid_slots: the two agree
+    # for a basis that is a contiguous slice of the supergrid and may not otherwise)
+    left = _supergrid_slots(tau_supergrid, basis_tau)[0]
     right = left + len(basis_tau)
     ok = np.asarray(res['status']) >= 0
-    errors = [None if good else ValueError("Rank(A) < p or Rank([P; A; G]) < n") for good in ok]
-    res['obs_fit_status'], res['obs_fit_errors'] = ok, errors
-    _raise_first_error(res, ignore_errors)
-    obs_x = np.zeros((num, len(tau_supergrid)))
-    obs_x[:, left:right] = np.where(ok[:, None], res['fit_x'], 0.0)
-    obs_special = {'R_inf': np.where(ok, res['R_inf'], 0.0), 'inductance': np.where(ok, res['inductance'], 0.0)}
+    res['obs_fit_status'], res['obs_fit_errors'] = ok, fit_errors(ok)
+    raise_first_error(res, ignore_errors)          # (before the llh evaluation; the list form raises after its last group)
+    obs_x = np.zeros((len(ok), len(tau_supergrid)))
+    obs_x[:, left:right] = zero_failed(ok, res['fit_x'])
+    obs_special = {key: zero_failed(ok, res[key]) for key in ('R_inf', 'inductance')}
     llh, rss = drt.evaluate_obs_llh_rss_batch(llh_kw=llh_kw, rss_kw=rss_kw)
-    res['obs_llh'], res['obs_rss'] = np.where(ok, llh, 0.0), np.where(ok, rss, 0.0)
+    res['obs_llh'], res['obs_rss'] = zero_failed(ok, llh), zero_failed(ok, rss)
     res['obs_tau_indices'] = (left, right)
     if drt_var:
         var, vok = drt.estimate_distribution_var_batch(tau=tau_supergrid, extend_var=True)
         vok = np.asarray(vok, dtype=bool) & ok
-        res['obs_drt_var'], res['obs_drt_var_ok'] = np.where(vok[:, None], var, 0.0), vok     # (failed fits keep zeros)
+        res['obs_drt_var'], res['obs_drt_var_ok'] = zero_failed(vok, var), vok     # (failed fits keep zeros)
     return obs_x, obs_special, res
-
-
-_GATHER_KEYS = ('obs_llh', 'obs_rss', 'outer_iters', 'qp_iters_total', 'status')
-# every special parameter a fit can report (x layout of drt1d.py:377-408); the gathered rows name them by position here
-_SPECIAL_REGISTRY = ('v_baseline', 'vz_offset', 'R_inf', 'inductance', 'C_inv', 'x_dop')
 
 
 def share_lookup_tables(drt, rank, world, src=0, force=False):
@@ -549,61 +464,6 @@ def share_lookup_tables(drt, rank, world, src=0, force=False):
             clone.install_lookup_tables(z_re, z_im, resp)
         clone._lut_shared_key = key
     return True
-
-
-def _pack_rows(obs_x, obs_special, res, drt_var):
-    """One rank's results as rows of doubles behind ONE header row that describes them, so that `dst` can unpack blocks from
-    ranks whose fits reported other special parameters (or none at all) without a second collective:
-        header = [nsup, drt_var, n_specials, (registry index, width, ndim) x n_specials, 0 ...]
-        row    = [obs_x (nsup) | specials at their real widths | _GATHER_KEYS | left, right | obs_drt_var (nsup), ok]"""
-    num, nsup = obs_x.shape
-    unknown = [k for k in obs_special if k not in _SPECIAL_REGISTRY]
-    if unknown:
-        raise NotImplementedError(f'special parameters {unknown} are not known to the sharded driver')
-    cols, head = [obs_x], [float(nsup), float(bool(drt_var)), 0.0]
-    for ki, key in enumerate(_SPECIAL_REGISTRY):
-        if obs_special.get(key) is None:
-            continue
-        raw = np.asarray(obs_special[key], dtype=float)
-        val = raw.reshape(num, -1)
-        cols.append(val)
-        head += [float(ki), float(val.shape[1]), float(raw.ndim)]
-        head[2] += 1
-    cols += [np.asarray(res[k], dtype=float)[:, None] for k in _GATHER_KEYS]
-    ti = res.get('obs_tau_indices', (0, nsup))
-    ti = np.array(ti, dtype=float) if isinstance(ti, list) else np.tile(np.array(ti, dtype=float), (num, 1))
-    cols.append(ti)
-    if drt_var:
-        cols += [res['obs_drt_var'], np.asarray(res['obs_drt_var_ok'], dtype=float)[:, None]]
-    body = np.concatenate(cols, axis=1)
-    width = max(body.shape[1], len(head))
-    packed = np.zeros((num + 1, width))
-    packed[0, :len(head)] = head
-    packed[1:, :body.shape[1]] = body
-    return packed
-
-
-def _unpack_block(block):
-    """inverse of _pack_rows for one rank's block (header row first): (obs_x, {special: (2-d array, ndim of the original)}, {key: column}, ti, var, vok)"""
-    head, body = block[0], block[1:]
-    nsup, drt_var, nsp = int(head[0]), bool(head[1]), int(head[2])
-    obs_x = body[:, :nsup]
-    pos = nsup
-    special = {}
-    for j in range(nsp):
-        key, w, nd = _SPECIAL_REGISTRY[int(head[3 + 3 * j])], int(head[4 + 3 * j]), int(head[5 + 3 * j])
-        special[key] = (body[:, pos:pos + w], nd)
-        pos += w
-    cols = {}
-    for k in _GATHER_KEYS:
-        cols[k] = body[:, pos]
-        pos += 1
-    ti = body[:, pos:pos + 2]
-    pos += 2
-    var = vok = None
-    if drt_var:
-        var, vok = body[:, pos:pos + nsup], body[:, pos + nsup] > 0.5
-    return obs_x, special, cols, ti, var, vok
 
 
 def _one_kernel(drt, members, saved=None):
@@ -710,52 +570,23 @@ def fit_observations_sharded(drt, frequencies=None, z_obs=None, rank=None, world
         packed = None
     # blocks: one header row + the rank's observations; a rank without observations sends nothing
     counts = [len(o) + 1 if len(o) else 0 for o in owned]
-    if min(counts) == 0 and world > 1:
-        # the row width is a function of the fit's configuration; a rank that fitted nothing learns it from the others
+    # The row width is a function of the fit's configuration.  It is agreed (one scalar all-reduce) when a rank that fitted nothing
+    # must learn it from the others, or when the ranks fitted a heterogeneous list: different sets of specials, rows of different widths
+    if (world > 1 and min(counts) == 0) or ((world > 1 or hd.forced()) and general and packed is not None):
         width = int(hd.max_over_ranks(0 if packed is None else packed.shape[1]))
         if packed is None:
             packed = np.zeros((0, width))
-        elif packed.shape[1] < width:            # (ranks whose fits report different specials: pad to the widest row)
+        elif packed.shape[1] < width:            # pad to the widest row
             packed = np.pad(packed, ((0, 0), (0, width - packed.shape[1])))
     elif packed is None:
         packed = np.zeros((0, 1))
-    elif (world > 1 or hd.forced()) and general:
-        # heterogeneous lists: ranks may report different sets of special parameters, i.e. rows of different widths
-        width = int(hd.max_over_ranks(packed.shape[1]))
-        if packed.shape[1] < width:
-            packed = np.pad(packed, ((0, 0), (0, width - packed.shape[1])))
     full = hd.gather_rows(packed, counts, dst=dst)
     if rank != dst:
         return None
     if num == 0:
         raise ValueError('no observations')
-    blocks, pos = [], 0
-    for r in range(world):
+    table = ObsTable(num, (int(full[0, 0]),), drt_var, GATHER_COLUMNS)          # (nsup: the first block's header says it)
+    for r, end in enumerate(np.cumsum(counts)):
         if counts[r]:
-            blocks.append((owned[r], _unpack_block(full[pos:pos + counts[r]])))
-            pos += counts[r]
-    nsup = blocks[0][1][0].shape[1]
-    obs_x = np.zeros((num, nsup))
-    obs_special, res = {}, {}
-    for k in _GATHER_KEYS:
-        res[k] = np.zeros(num) if k in ('obs_llh', 'obs_rss') else np.zeros(num, dtype=np.int64)
-    tis = np.zeros((num, 2), dtype=np.int64)
-    if drt_var:
-        res['obs_drt_var'], res['obs_drt_var_ok'] = np.zeros((num, nsup)), np.zeros(num, dtype=bool)
-    for idx, (bx, bspecial, bcols, bti, bvar, bvok) in blocks:
-        obs_x[idx] = bx
-        for key, (val, nd) in bspecial.items():
-            if key not in obs_special:
-                obs_special[key] = np.zeros((num, val.shape[1]) if nd > 1 else (num,))
-            obs_special[key][idx] = val if nd > 1 else val[:, 0]
-        for k in _GATHER_KEYS:
-            res[k][idx] = bcols[k] if k in ('obs_llh', 'obs_rss') else bcols[k].astype(np.int64)
-        tis[idx] = bti.astype(np.int64)
-        if drt_var:
-            res['obs_drt_var'][idx], res['obs_drt_var_ok'][idx] = bvar, bvok
-    # (shapes as fit_observations returns them: (num,) for scalar specials, (num, width) for vector-valued ones)
-    res['obs_tau_indices'] = [(int(a_), int(b_)) for a_, b_ in tis]
-    res['obs_fit_status'] = res['status'] >= 0
-    res['obs_fit_errors'] = [None if good else ValueError("Rank(A) < p or Rank([P; A; G]) < n") for good in res['obs_fit_status']]
-    _raise_first_error(res, ignore_errors)
-    return obs_x, obs_special, res
+            table.scatter_rows(owned[r], full[end - counts[r]:end])
+    return table.result(ignore_errors)

@@ -19,6 +19,7 @@ Not here (out of scope): file readers, psi interpolation / fil
 import numpy as np
 
 from . import drtmd as _driver
+from .table import new_special, tau_slots
 
 
 class DRTMD:
@@ -38,10 +39,7 @@ class DRTMD:
         self.pfrt_factors = None if pfrt_factors is None else np.asarray(pfrt_factors, dtype=float)
         n_steps = 11 if self.pfrt_factors is None else len(self.pfrt_factors)
         self.drt_var = bool(drt_var)
-        self.llh_kw, self.rss_kw = dict(llh_kw or {}), dict(rss_kw or {})
-        for kw in (self.llh_kw, self.rss_kw):                                                     # drtmd.py:127-129
-            kw.setdefault('normalize', True)
-            kw.setdefault('weights', 'uniform')
+        self.llh_kw, self.rss_kw = _driver._metric_kw(llh_kw, rss_kw)                            # drtmd.py:127-129
         self.psi_dim_names = psi_dim_names
         self.obs_psi = None if psi_dim_names is None else np.zeros((0, len(psi_dim_names)))
         self.obs_data, self.obs_group_id, self.obs_fit_errors, self.obs_tau_indices = [], [], [], []
@@ -94,42 +92,38 @@ class DRTMD:
         self.last_fit_index = idx
         if len(idx) == 0:
             return
-        observations = [self.obs_data[i] for i in idx]
-        kw = dict(self.fit_kw)
         obs_x, obs_special, res = _driver.fit_observations(
-            self.drt1d, observations=observations, tau_supergrid=self.tau_supergrid, drt_var=self.drt_var, ignore_errors=True,
-            llh_kw=self.llh_kw, rss_kw=self.rss_kw, fit_type=self.fit_type,
-            pfrt_factors=self.pfrt_factors if self.fit_type == 'pfrt' else None, **kw)
+            self.drt1d, observations=[self.obs_data[i] for i in idx], tau_supergrid=self.tau_supergrid, drt_var=self.drt_var,
+            ignore_errors=True, llh_kw=self.llh_kw, rss_kw=self.rss_kw, fit_type=self.fit_type,
+            pfrt_factors=self.pfrt_factors if self.fit_type == 'pfrt' else None, **self.fit_kw)
         ok = np.asarray(res['obs_fit_status'], dtype=bool)
-        errors = list(res['obs_fit_errors'])
         first_bad = int(np.argmin(ok)) if not ok.all() else len(idx)
         # without ignore_errors the reference's loop stops at the first failure: what came before it is stored, the rest is not
-        keep = np.arange(len(idx)) if ignore_errors else np.arange(first_bad)
-        for j in keep:
-            i = idx[j]
-            if ok[j]:
-                self.obs_x[i] = obs_x[j]
-                self.obs_llh[i], self.obs_rss[i] = res['obs_llh'][j], res['obs_rss'][j]
-                ti = res['obs_tau_indices']
-                self.obs_tau_indices[i] = tuple(ti[j]) if isinstance(ti, list) else tuple(ti)
-                if self.drt_var and 'obs_drt_var' in res:
-                    self.obs_drt_var[i] = res['obs_drt_var'][j]
-                if self.obs_special is None:                      # initialize_obs_special, drtmd.py:270-271
-                    self.obs_special = {}
-                for key, val in obs_special.items():
-                    val = np.asarray(val)
-                    if key not in self.obs_special:               # "key is new", drtmd.py:281-285
-                        self.obs_special[key] = np.zeros((self.num_obs,) + val.shape[1:])
-                    self.obs_special[key][i] = val[j]
-                self.obs_fit_status[i] = True
-                self.obs_fit_errors[i] = None
-            else:                                                 # drtmd.py:292-299
-                self.obs_fit_status[i] = False
-                self.obs_ignore_flag[i] = True
-                self.obs_fit_errors[i] = errors[j]
+        seen = np.arange(len(idx)) if ignore_errors else np.arange(first_bad)
+        good, bad = seen[ok[seen]], seen[~ok[seen]]
+        if len(good):
+            rows = idx[good]
+            self.obs_x[rows] = obs_x[good]
+            self.obs_llh[rows], self.obs_rss[rows] = res['obs_llh'][good], res['obs_rss'][good]
+            if self.drt_var and 'obs_drt_var' in res:
+                self.obs_drt_var[rows] = res['obs_drt_var'][good]
+            if self.obs_special is None:                          # initialize_obs_special, drtmd.py:270-271
+                self.obs_special = {}
+            for key, val in obs_special.items():
+                if key not in self.obs_special:
+                    self.obs_special[key] = new_special(self.num_obs, val)
+                self.obs_special[key][rows] = np.asarray(val)[good]
+            self.obs_fit_status[rows] = True
+            slots = tau_slots(res['obs_tau_indices'], len(idx))
+            for j in good:
+                self.obs_tau_indices[idx[j]] = tuple(slots[j].tolist())
+                self.obs_fit_errors[idx[j]] = None
+        self.obs_fit_status[idx[bad]], self.obs_ignore_flag[idx[bad]] = False, True          # drtmd.py:292-299
+        for j in bad:
+            self.obs_fit_errors[idx[j]] = res['obs_fit_errors'][j]
         if not ignore_errors and first_bad < len(idx):
             print(f"Error encountered at obs_index {idx[first_bad]}")
-            raise errors[first_bad]
+            raise res['obs_fit_errors'][first_bad]
 
     def fit_all(self, refit=False, ignore_errors=False):
         """drtmd.py:321-329: everything (refit=True) or only what is neither fitted nor ignored"""
