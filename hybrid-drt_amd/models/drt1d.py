@@ -5,7 +5,8 @@
 serial loop in DRTMD.fit_observations (hybdrt/mapping/drtmd.py:303-319).  All arithmetic -- lookup tables,
 Z'/Z'' and penalty matrices, the QPHB loop -- runs in libhipdrt.so on one MI355X; this module only decides
 grids and options and rescales results (host logic mirrored from the reference, cited per method).  The methods that act on a
-finished fit (prediction, peaks, PFRT, covariances) are postfit.PostFitMixin; chrono / joint / DOP fits prepared.PreparedFitMixin."""
+finished fit (prediction, peaks, PFRT, covariances) are postfit.PostFitMixin; chrono / joint / DOP fits prepared.PreparedFitMixin;
+what re-enters the device loop on a finished fit (warm restarts, candidates, the PFRT fits) restart.RestartMixin."""
 import warnings
 
 import numpy as np
@@ -15,7 +16,8 @@ from ..matrices import mat1d
 from ..utils.array import is_uniform
 from . import kk, qphb
 from .postfit import PostFitMixin
-from .prepared import PreparedFitMixin, combine_status
+from .prepared import PreparedFitMixin
+from .restart import RestartMixin
 
 _FIT_KW_DEFAULTS = dict(  # DRT._qphb_fit_core keyword defaults (drt1d.py:102-137) that the device loop honours
     nonneg=True, scale_data=True, ohmic_penalty=1e-6, inductance_penalty=1e-6, inductance_scale=1e-5,
@@ -24,7 +26,7 @@ _FIT_KW_DEFAULTS = dict(  # DRT._qphb_fit_core keyword defaults (drt1d.py:102-13
     iw_l1_lambda_0=1e-4, iw_l2_lambda_0=1e-4, eff_hp=True, weight_factor=1, xtol=1e-2, max_iter=50)
 
 
-class DRT(PreparedFitMixin, PostFitMixin):
+class DRT(PreparedFitMixin, PostFitMixin, RestartMixin):
     def __init__(self, fixed_basis_tau=None, tau_supergrid=None, tau_basis_type='gaussian', tau_epsilon=None,
                  basis_tau_ppd=10, extend_basis_decades=1, interpolate_integrals=True, fit_dop=False,
                  fit_inductance=True, fit_ohmic=True, fit_capacitance=False, frequency_precision=10,
@@ -301,79 +303,6 @@ class DRT(PreparedFitMixin, PostFitMixin):
         res['timings_ms'], res['launches'] = plan.timings()
         return res
 
-    # ---- warm restarts of the device loop (drt1d.py:1270-1365) and the candidate generators on top (1497-1632) ---
-    def continue_from_init(self, x_init=None, rho_vector=None, s_vectors=None, weights=None, weight_factor=1,
-                           xtol=1e-2, max_iter=10, min_iter=2, history_of=-1, dop_rho_vector=None, **kw):
-        """DRT._continue_from_init for the last fitted batch: the outer loop re-entered on the device from the given
-        state (arrays with a leading batch axis; None = the state left by the previous call) with ``kw`` updating the
-        hyper-parameters (e.g. s_0, l2_lambda_0).  est_weights, xmx norms and the data scale stay as fitted.
-        Returns the same dict of arrays as fit_eis_batch (outer_iters = iterations of this call)."""
-        if isinstance(self._plan, _ffi.PreparedPlan):         # chrono / joint fits, DOP: the same loop on the prepared plan
-            return self._continue_prepared(x_init=x_init, rho_vector=rho_vector, s_vectors=s_vectors, weights=weights,
-                                           dop_rho_vector=dop_rho_vector, weight_factor=weight_factor, xtol=xtol, max_iter=max_iter, min_iter=min_iter,
-                                           history_of=history_of, **kw)
-        if self._plan is None or self._last_batch is None:
-            raise Exception('continue_from_init needs a finished qphb fit')
-        fit_kw = dict(self.fit_kwargs)
-        fit_kw.update(kw)
-        fit_kw.update(xtol=xtol, max_iter=max_iter)
-        opts, _, _ = self._make_opts(fit_kw)
-        plan = self._plan
-        plan.set_state(x=x_init, rho=rho_vector, s=s_vectors, weights=weights)
-        plan.record_history(history_of)
-        plan.continue_fit(opts, weight_factor=weight_factor, min_iter=min_iter)
-        res = self.collect_staged()
-        if history_of >= 0:
-            res['history'] = plan.history()
-        return res
-
-    def _candidate_baseline(self):
-        """What the reference's candidate generators re-read from the finished fit before their first warm restart
-        (drt1d.py:1517-1525, 1587-1594): x of the last recorded iterate, rho / dop_rho and the (scaled) weights of
-        qphb_params -- NOT the s vectors, which its shallow list copies let earlier warm restarts update in place.  Single
-        fits only (a batch fit keeps no per-spectrum qphb_params: its restarts go on from the state on the device)."""
-        qp, hist = getattr(self, 'qphb_params', None), getattr(self, 'qphb_history', None)
-        if not qp or not hist or self._plan.B != 1 or len(qp['weights']) != self._plan.m:
-            return {}
-        base = dict(x_init=np.asarray(hist[-1]['x'])[None, :], rho_vector=np.asarray(qp['rho_vector'])[None, :],
-                    weights=np.asarray(qp['weights'])[None, :])
-        if qp.get('dop_rho_vector') is not None:
-            base['dop_rho_vector'] = np.asarray(qp['dop_rho_vector'])[None, :]
-        return base
-
-    def generate_candidates_s0(self, multiplier, steps, xtol=1e-2, max_iter=10, history_of=-1):
-        """DRT._generate_candidates_s0 (drt1d.py:1497-1565) for the last fit (EIS, chrono or joint; single or batch): step i
-        restarts with s_0 * multiplier^i, l2_lambda_0 / multiplier^i and (multiplier > 1) the baseline s vectors
-        scaled by multiplier^i; the first step from the fit's x / rho / weights, later ones from their predecessor's.
-        Returns the list of per-step result dicts."""
-        base = self._collect_prepared() if isinstance(self._plan, _ffi.PreparedPlan) else self.collect_staged()
-        s_base = base['s_vectors'].copy()
-        s_in = s_base.copy()
-        s_0 = np.broadcast_to(np.asarray(self.fit_kwargs['s_0'], dtype=float), (3,)).copy()
-        out = []
-        start = self._candidate_baseline()
-        for i in range(1, steps + 1):
-            f = multiplier ** i
-            s_in = s_base * f if multiplier > 1 else s_in * multiplier
-            res = self.continue_from_init(s_vectors=s_in, xtol=xtol, max_iter=max_iter, history_of=history_of,
-                                          s_0=s_0 * f, l2_lambda_0=self.fit_kwargs['l2_lambda_0'] / f, **start)
-            start = {}
-            s_in = res['s_vectors'].copy()
-            out.append(res)
-        return out
-
-    def generate_candidates_weights(self, multiplier, steps, xtol=1e-2, max_iter=10, history_of=-1):
-        """DRT._generate_candidates_weights (drt1d.py:1567-1632): step i restarts with weight_factor = multiplier^i.
-        As in the reference (whose shallow list copy lets iterate_qphb update the stored s vectors in place) every
-        step starts from the s vectors the previous step ended with."""
-        out = []
-        start = self._candidate_baseline()
-        for i in range(1, steps + 1):
-            out.append(self.continue_from_init(weight_factor=multiplier ** i, xtol=xtol, max_iter=max_iter,
-                                               history_of=history_of, **start))
-            start = {}
-        return out
-
     def evaluate_obs_llh_rss_batch(self, llh_kw=None, rss_kw=None):
         """(DRT.evaluate_llh(**llh_kw), DRT.evaluate_rss(**rss_kw)) (drt1d.py:4433-4496; x = the last iterate) for every
         spectrum of the last fitted batch -- what DRTMD.fit_observation stores as obs_llh / obs_rss (drtmd.py:259-260).
@@ -404,48 +333,6 @@ class DRT(PreparedFitMixin, PostFitMixin):
         if rss_kw.get('normalize', False):
             rss /= m
         return llh, rss
-
-    def evaluate_step_llh_batch(self, alpha_0=2, beta_0=1):
-        """evaluate_llh(weights=estimate_weights(x), x) (drt1d.py:2618-2622) for the current x of every spectrum of
-        the batch: residuals, re-estimated weights and both sums on the device, the two lgamma constants here."""
-        rss, slw = self._plan.llh_terms()
-        return qphb.marginal_llh(rss, self._plan.m, alpha_0, beta_0) + slw
-
-    def pfrt_fit_eis_batch(self, frequencies, z_batch, factors=None, max_iter_per_step=10, max_init_iter=20,
-                           xtol=1e-2, nonneg=True, after_init=None, **kw):
-        """DRT.pfrt_fit_eis (drt1d.py:2558-2690) for B spectra at once: a full fit at the first regularisation factor
-        (s_0 * f, l2_lambda_0 / f), then one warm restart per further factor on the device.  Returns
-        {'factors', 'step_x' (S, B, n) scaled-space solutions, 'step_llh' (S, B), 'step_iters' (S, B)}."""
-        base = qphb.get_default_hypers(True, False, 'gaussian')
-        base.update({k: v for k, v in kw.items() if k in base})
-        if factors is None:
-            factors = np.logspace(-1, 1, 11)
-        s_0 = np.broadcast_to(np.asarray(base['s_0'], dtype=float), (3,))
-
-        def step_hypers(f):
-            return dict(s_0=s_0 * f, l2_lambda_0=base['l2_lambda_0'] / f)
-
-        init_kw = dict(kw)
-        init_kw.update(step_hypers(factors[0]))
-        res = self.fit_eis_batch(frequencies, z_batch, nonneg=nonneg, max_iter=max_init_iter, xtol=xtol, **init_kw)
-        # every step's final state stays on the device for predict_pfrt_batch / step_p_matrix (hipdrt_plan_pfrt_begin / _record)
-        self._plan.pfrt_begin(len(factors))
-        self._plan.pfrt_record()
-        step_x, step_llh, step_iters = [res['x'].copy()], [self.evaluate_step_llh_batch()], [res['outer_iters'].copy()]
-        status = np.array(res['status']).copy()
-        if after_init is not None:          # (what DRTMD reads from the FIRST step's fit: its P matrix, llh / rss -- mapping)
-            after_init(res)
-        for f in factors[1:]:
-            res = self.continue_from_init(xtol=xtol, max_iter=max_iter_per_step, **step_hypers(f))
-            self._plan.pfrt_record()
-            step_x.append(res['x'].copy())
-            step_llh.append(self.evaluate_step_llh_batch())
-            step_iters.append(res['outer_iters'].copy())
-            status = combine_status(status, res['status'])
-        self.pfrt_result = {'factors': np.asarray(factors), 'step_x': np.array(step_x), 'step_llh': np.array(step_llh),
-                            'step_iters': np.array(step_iters), 'status': status,
-                            'coefficient_scale': res['coefficient_scale'], 'basis_tau': res['basis_tau']}
-        return self.pfrt_result
 
     series_neg = False
 
