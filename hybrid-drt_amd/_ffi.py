@@ -145,6 +145,45 @@ class DebugHyperArgs(C.Structure):
     ]
 
 
+class PredictDesc(C.Structure):
+    """hipdrt_predict_desc (include/hipdrt.h)"""
+    _fields_ = [("idx_rinf", C.c_int), ("idx_induc", C.c_int), ("idx_cinv", C.c_int), ("inductance_scale", C.c_double),
+                ("capacitance_scale", C.c_double), ("dop_scale_vector", _dp), ("dop_scale_batched", C.c_int), ("v_baseline_scale", _dp),
+                ("coefficient_scale", _dp), ("response_signal_scale", _dp), ("scaled_response_offset", _dp)]
+
+
+class ResponseArgs(C.Structure):
+    """hipdrt_response_args (include/hipdrt.h)"""
+    _fields_ = [("times", _dp), ("nt", C.c_int), ("step_times", _dp), ("nsteps", C.c_int), ("step_sizes", _dp),
+                ("sizes_batched", C.c_int), ("basis_tau", _dp), ("mode", C.c_int), ("ny", C.c_int), ("ngrid", C.c_int),
+                ("log_td", _dp), ("v", _dp), ("basis_nu", _dp), ("nu_epsilon", C.c_double), ("inf_rv", _dp),
+                ("inf_batched", C.c_int), ("cap_rv", _dp), ("cap_batched", C.c_int), ("vz_strength", _dp), ("vb_mat", _dp),
+                ("include_mask", C.c_int)]
+
+
+class ZModelArgs(C.Structure):
+    """hipdrt_z_model_args (include/hipdrt.h)"""
+    _fields_ = [("freq", _dp), ("nf", C.c_int), ("basis_tau", _dp), ("mode", C.c_int), ("ny", C.c_int), ("ngrid", C.c_int),
+                ("log_wt_re", _dp), ("z_re", _dp), ("log_wt_im", _dp), ("z_im", _dp), ("basis_nu", _dp), ("nu_epsilon", C.c_double),
+                ("vz_strength", _dp), ("include_mask", C.c_int)]
+
+
+class DebugResponseArgs(C.Structure):
+    """hipdrt_debug_response_args (include/hipdrt_debug.h)"""
+    _fields_ = [("B", C.c_int), ("S", C.c_int), ("nt", C.c_int), ("ntau", C.c_int), ("copies", C.c_int), ("ns", C.c_int),
+                ("n", C.c_int), ("X", _dp), ("U", _dp), ("Ud", _dp), ("dop_start", C.c_int), ("dop_size", C.c_int),
+                ("dop_scale_vector", _dp), ("step_sizes", _dp), ("sizes_batched", C.c_int), ("coefficient_scale", _dp), ("response_signal_scale", _dp),
+                ("scaled_response_offset", _dp), ("idx_rinf", C.c_int), ("idx_cinv", C.c_int), ("vz_index", C.c_int),
+                ("vb_start", C.c_int), ("vb_size", C.c_int), ("capacitance_scale", C.c_double), ("inf_rv", _dp),
+                ("inf_batched", C.c_int), ("cap_rv", _dp), ("cap_batched", C.c_int), ("vz_strength", _dp), ("vb_mat", _dp),
+                ("v_baseline_scale", _dp), ("fit_status", _ip), ("include_mask", C.c_int), ("out", _dp)]
+
+
+# include_mask bits of hipdrt_plan_predict_response and hipdrt_plan_predict_z_model (HIPDRT_INCLUDE_*)
+INCLUDE_DRT, INCLUDE_OHMIC, INCLUDE_CAP, INCLUDE_DOP, INCLUDE_VZ_OFFSET, INCLUDE_BASELINE, INCLUDE_INDUCTANCE = 1, 2, 4, 8, 16, 32, 64
+INCLUDE_ALL = 127
+
+
 # name -> argtypes (all return int unless listed in _RESTYPES).  Mirrors include/hipdrt.h one-to-one;
 # tests/test_cabi_symbols.py checks the header and this table against the built library.
 SIGNATURES = {
@@ -191,6 +230,11 @@ SIGNATURES = {
     "hipdrt_plan_predict_drt": [_vp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _dp, _dp, _dp, _ip],
     "hipdrt_plan_predict_z": [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _ip],
     "hipdrt_plan_predict_resistances": [_vp, _dp, _dp, _dp, C.c_int],
+    "hipdrt_plan_set_predict_desc": [_vp, C.POINTER(PredictDesc)],
+    "hipdrt_plan_predict_response": [_vp, C.POINTER(ResponseArgs), _dp, _ip],
+    "hipdrt_plan_predict_z_model": [_vp, C.POINTER(ZModelArgs), _dp, _dp, _ip],
+    "hipdrt_plan_predict_dop": [_vp, _dp, C.c_int, _dp, C.c_double, _dp, C.c_double, C.c_int, _dp, _ip],
+    "hipdrt_debug_response": [_vp, C.POINTER(DebugResponseArgs)],
     "hipdrt_peak_opts_default": [C.POINTER(PeakOpts)],
     "hipdrt_plan_find_peaks": [_vp, _dp, C.c_int, C.POINTER(PeakOpts), _dp, _ip, _ip, _dp, _dp, _dp, _ip, _ip, _ip, _dp, _dp, _dp,
                                _ip],
@@ -913,6 +957,67 @@ class Context:
         _check(self._lib.hipdrt_debug_apply_rows(self._h, B, K, ldx, int(col_offset), _p(X), r, _p(E), _p(sc), _p(out)))
         return out
 
+    def debug_response(self, X, ns, step_sizes, coefficient_scale, U=None, Ud=None, dop_start=0, copies=1, idx_rinf=-1,
+                       idx_cinv=-1, vz_index=-1, vb_start=0, capacitance_scale=1.0, response_signal_scale=None,
+                       scaled_response_offset=None, inf_rv=None, cap_rv=None, vz_strength=None, vb_mat=None,
+                       v_baseline_scale=None, fit_status=None, include_mask=INCLUDE_ALL, nt=None, dop_scale_vector=None):
+        """tests: the device chain of hipdrt_plan_predict_response behind its layer builders, on host arrays
+        (hipdrt_debug_response, include/hipdrt_debug.h) -> (B, nt).  X (B, n); U (S, nt, ntau) unit-step layers; Ud (S, nt, dop_size)
+        unit phasor layers, dop_scale_vector (B, dop_size) or None; step_sizes (S,) or (B, S); inf_rv / cap_rv (nt,) or (B, nt).  Raises when the kernel
+        wrote outside its output."""
+        a, keep = DebugResponseArgs(), []
+
+        def arr(name, v, dtype=np.float64):
+            if v is not None:
+                v = np.ascontiguousarray(v, dtype=dtype)
+                keep.append(v)
+                setattr(a, name, v.ctypes.data_as(_ip if dtype == np.int32 else _dp))
+            return v
+        X = arr('X', X)
+        sz = arr('step_sizes', step_sizes)
+        U, Ud = arr('U', U), arr('Ud', Ud)
+        a.B, a.n = X.shape
+        a.S = sz.shape[-1]
+        a.sizes_batched = int(sz.ndim == 2)
+        layers = U if U is not None else Ud
+        a.nt = int(nt) if layers is None else layers.shape[1]
+        a.ntau = U.shape[2] if U is not None else 1
+        a.copies, a.ns = int(copies), int(ns)
+        a.dop_start, a.dop_size = int(dop_start), (Ud.shape[2] if Ud is not None else 0)
+        dsv = arr('dop_scale_vector', dop_scale_vector)
+        if dsv is not None and dsv.shape != (a.B, a.dop_size):
+            raise ValueError("dop_scale_vector must have shape (B, dop_size)")
+        for name, v in (('coefficient_scale', coefficient_scale), ('response_signal_scale', response_signal_scale),
+                        ('scaled_response_offset', scaled_response_offset)):
+            v = arr(name, v)
+            if v is not None and v.shape != (a.B,):
+                raise ValueError(f"{name} must have shape (B,)")
+        a.idx_rinf, a.idx_cinv, a.vz_index, a.vb_start = int(idx_rinf), int(idx_cinv), int(vz_index), int(vb_start)
+        a.capacitance_scale = float(capacitance_scale)
+        for name, v in (('inf_rv', inf_rv), ('cap_rv', cap_rv)):
+            v = arr(name, v)
+            if v is not None:
+                if v.shape not in ((a.nt,), (a.B, a.nt)):
+                    raise ValueError(f"{name} must have shape (nt,) or (B, nt)")
+                setattr(a, name[:3] + '_batched', int(v.ndim == 2))
+        vs = arr('vz_strength', vz_strength)
+        if vs is not None and vs.shape != (a.nt,):
+            raise ValueError("vz_strength must have shape (nt,)")
+        vb, vbs = arr('vb_mat', vb_mat), arr('v_baseline_scale', v_baseline_scale)
+        a.vb_size = 0 if vb is None else vb.shape[1]
+        if vb is not None and (vb.shape[0] != a.nt or vbs is None or vbs.shape != (a.vb_size,)):
+            raise ValueError("vb_mat must have shape (nt, vb_size) and v_baseline_scale (vb_size,)")
+        for name, v in (('U', U), ('Ud', Ud)):
+            if v is not None and v.shape[:2] != (a.S, a.nt):
+                raise ValueError(f"{name} must have shape (S, nt, columns)")
+        fs = arr('fit_status', fit_status, np.int32)
+        if fs is not None and fs.shape != (a.B,):
+            raise ValueError("fit_status must have shape (B,)")
+        a.include_mask = int(include_mask)
+        out = arr('out', np.empty((a.B, a.nt)))
+        _check(self._lib.hipdrt_debug_response(self._h, C.byref(a)))
+        return out
+
     def debug_find_peaks(self, fxx, f=None, var_fxx=None, var_f=None, opts: PeakOpts | None = None):
         """tests: peaks_kernel on host rows (B, neval) (hipdrt_debug_find_peaks, include/hipdrt_debug.h) -> dict(peak_sign, keep,
         heights, prominences, probs, left_bases, right_bases, count, used_prominence[, peak_prob, curv_prob]).  Raises when the
@@ -1475,6 +1580,123 @@ class PreparedPlan(Plan):
         pobj = np.empty(B)
         _check(self._lib.hipdrt_plan_iterate(self._h, C.byref(st), _pi(conv), _pi(status), _pi(iters), _p(pobj)))
         return dict(converged=conv.astype(bool), qp_status=status, qp_iters=iters, primal_objective=pobj)
+
+    def set_predict_desc(self, idx_rinf, idx_induc, idx_cinv, inductance_scale, capacitance_scale, coefficient_scale,
+                         dop_scale_vector=None, v_baseline_scale=None, response_signal_scale=None, scaled_response_offset=None):
+        """hipdrt_plan_set_predict_desc: what the special columns mean and the post-fit scales of the fitted batch (per member:
+        coefficient_scale, response_signal_scale, scaled_response_offset, each (B,); dop_scale_vector (dop_size,) shared or (B, dop_size))"""
+        d, keep = PredictDesc(), []
+        d.idx_rinf, d.idx_induc, d.idx_cinv = int(idx_rinf), int(idx_induc), int(idx_cinv)
+        d.inductance_scale, d.capacitance_scale = float(inductance_scale), float(capacitance_scale)
+        if dop_scale_vector is not None and np.ndim(dop_scale_vector) == 2:
+            if np.shape(dop_scale_vector) != (self.batch, self.desc.dop_size):
+                raise ValueError(f"dop_scale_vector: expected shape {(self.batch, self.desc.dop_size)} or {(self.desc.dop_size,)}")
+            d.dop_scale_batched = 1
+        sizes = dict(dop_scale_vector=self.desc.dop_size * (self.batch if d.dop_scale_batched else 1),
+                     v_baseline_scale=self.desc.vb_size, coefficient_scale=self.batch,
+                     response_signal_scale=self.batch, scaled_response_offset=self.batch)
+        given = dict(dop_scale_vector=dop_scale_vector, v_baseline_scale=v_baseline_scale, coefficient_scale=coefficient_scale,
+                     response_signal_scale=response_signal_scale, scaled_response_offset=scaled_response_offset)
+        for name, v in given.items():
+            if v is None:
+                continue
+            v = _f64(v).ravel()
+            if v.size != sizes[name]:
+                raise ValueError(f"{name}: expected {sizes[name]} values, got {v.size}")
+            keep.append(v)
+            setattr(d, name, _p(v))
+        _check(self._lib.hipdrt_plan_set_predict_desc(self._h, C.byref(d)))
+
+    def predict_response(self, times, step_times, step_sizes, basis_tau=None, mode=MODE_TRAPZ, ny=1000, lookup=None,
+                         basis_nu=None, nu_epsilon=0.0, inf_rv=None, cap_rv=None, vz_strength=None, vb_mat=None,
+                         include_mask=INCLUDE_ALL):
+        """hipdrt_plan_predict_response: (B, nt) voltage response of the fitted batch at any times, and the status (B,).
+        step_sizes (S,) or (B, S); inf_rv / cap_rv (nt,) or (B, nt); lookup = (log_td, v) for MODE_INTERP; vb_mat (nt, vb_size)."""
+        a, keep = ResponseArgs(), []
+        B = self.batch
+
+        def arr(name, v, shapes=None):
+            if v is not None:
+                v = _f64(v)
+                if shapes is not None and v.shape not in shapes:
+                    raise ValueError(f"{name}: expected shape {' or '.join(map(str, shapes))}, got {v.shape}")
+                keep.append(v)
+                setattr(a, name, _p(v))
+            return v
+        t = arr('times', np.ravel(times))
+        st = arr('step_times', np.ravel(step_times))
+        a.nt, a.nsteps = t.size, st.size
+        sz = arr('step_sizes', step_sizes, [(st.size,), (B, st.size)])
+        a.sizes_batched = int(sz.ndim == 2)
+        # (without set_tau_basis the library refuses before it reads the basis)
+        arr('basis_tau', basis_tau, [(self._basis_nb,)] if getattr(self, '_basis_nb', None) else None)
+        a.mode, a.ny = int(mode), int(ny)
+        if lookup is not None:
+            ltd, v = arr('log_td', lookup[0]), arr('v', lookup[1])
+            a.ngrid = ltd.size
+        arr('basis_nu', basis_nu, [(self.desc.dop_size,)])
+        a.nu_epsilon = float(nu_epsilon)
+        for name, v in (('inf_rv', inf_rv), ('cap_rv', cap_rv)):
+            v = arr(name, v, [(t.size,), (B, t.size)])
+            if v is not None:
+                setattr(a, name[:3] + '_batched', int(v.ndim == 2))
+        arr('vz_strength', vz_strength, [(t.size,)])
+        arr('vb_mat', vb_mat, [(t.size, self.desc.vb_size)])
+        a.include_mask = int(include_mask)
+        out = np.empty((B, t.size))
+        status = np.empty(B, dtype=np.int32)
+        _check(self._lib.hipdrt_plan_predict_response(self._h, C.byref(a), _p(out), _pi(status)))
+        return out, status
+
+    def predict_z_model(self, frequencies, basis_tau=None, mode=MODE_TRAPZ, ny=1000, lookups=None, basis_nu=None, nu_epsilon=0.0,
+                        vz_strength=None, include_mask=INCLUDE_ALL):
+        """hipdrt_plan_predict_z_model: complex (B, nf) impedance of the fitted batch of a prepared plan at any frequencies, and
+        the status (B,).  lookups = ((log_wt_re, z_re), (log_wt_im, z_im)) for MODE_INTERP; vz_strength (nf,) or None."""
+        a, keep = ZModelArgs(), []
+
+        def arr(name, v, shape=None):
+            if v is not None:
+                v = _f64(v)
+                if shape is not None and v.shape != shape:
+                    raise ValueError(f"{name}: expected shape {shape}, got {v.shape}")
+                keep.append(v)
+                setattr(a, name, _p(v))
+            return v
+        f = arr('freq', np.ravel(frequencies))
+        a.nf = f.size
+        arr('basis_tau', basis_tau, (self._basis_nb,) if getattr(self, '_basis_nb', None) else None)
+        a.mode, a.ny = int(mode), int(ny)
+        if lookups is not None:
+            (lwr, zr), (lwi, zi) = lookups
+            lwr = arr('log_wt_re', lwr)
+            a.ngrid = lwr.size
+            for name, v in (('z_re', zr), ('log_wt_im', lwi), ('z_im', zi)):
+                arr(name, v, (lwr.size,))
+        arr('basis_nu', basis_nu, (self.desc.dop_size,))
+        a.nu_epsilon = float(nu_epsilon)
+        arr('vz_strength', vz_strength, (f.size,))
+        a.include_mask = int(include_mask)
+        B = self.batch
+        zr, zi = np.empty((B, f.size)), np.empty((B, f.size))
+        status = np.empty(B, dtype=np.int32)
+        _check(self._lib.hipdrt_plan_predict_z_model(self._h, C.byref(a), _p(zr), _p(zi), _pi(status)))
+        return zr + 1j * zi, status
+
+    def predict_dop(self, nu, basis_nu, nu_epsilon, normalize_by=None, nu_basis_area=1.0, include_ideal=True):
+        """hipdrt_plan_predict_dop: (B, len(nu)) distribution of phasances of the fitted batch on the ascending grid nu, and the
+        status (B,); normalize_by (len(nu),) divides it (get_dop_norm), None leaves it as it is"""
+        nu, bn = _f64(nu).ravel(), _f64(basis_nu).ravel()
+        if bn.size != self.desc.dop_size:
+            raise ValueError(f"basis_nu: expected {self.desc.dop_size} points, got {bn.size}")
+        nb = None if normalize_by is None else _f64(normalize_by).ravel()
+        if nb is not None and nb.size != nu.size:
+            raise ValueError("normalize_by must have one entry per point of nu")
+        B = self.batch
+        out = np.empty((B, nu.size))
+        status = np.empty(B, dtype=np.int32)
+        _check(self._lib.hipdrt_plan_predict_dop(self._h, _p(nu), nu.size, _p(bn), float(nu_epsilon), _p(nb), float(nu_basis_area),
+                                                 int(bool(include_ideal)), _p(out), _pi(status)))
+        return out, status
 
     def get(self, which):
         B = self.batch

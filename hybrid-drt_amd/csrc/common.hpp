@@ -288,6 +288,52 @@ void launch_drt_band(hipStream_t st, int B, int r, const double* mu, const doubl
 void launch_z_assemble(hipStream_t st, int B, int nf, const double* y, const double* X, long long ldx, int idx_rinf,
                        int idx_induc, const double* cs, double inductance_scale, const double* freq, int mask,
                        const int* fit_status, double* z_re, double* z_im);
+// response_assemble_kernel (predict.hip): the voltage response of every member from the step-wise products T = cs U x.  All
+// pointers are device memory; a null T / Tn / Td / vector leaves its term out.
+struct ResponseArgs {
+    int S, nt, mask;                       // steps, prediction times, HIPDRT_INCLUDE_* bits
+    const double *T, *Tn, *Td;             // [B][ldt], entry s * nt + i: DRT block (positive copy), negative copy, DOP block
+    long long ldt;
+    const double* sizes; int sizes_batched;    // [S] or [B][S]
+    const double* X; long long ldx;        // the scaled solutions
+    const double *cs, *rss, *sro;          // [B] coefficient scale, response signal scale, scaled response offset (null: 0)
+    int idx_rinf, idx_cinv, vz_index, vb_start, vb_size;
+    double capacitance_scale;
+    const double* inf_rv; int inf_batched;     // [nt] or [B][nt]
+    const double* cap_rv; int cap_batched;
+    const double *strength, *vb_mat, *vb_scale;    // [nt], [nt][vb_size], [vb_size]
+    const int* fit_status;
+    double* out;                           // [B][nt]
+};
+void launch_response_assemble(hipStream_t st, int B, const ResponseArgs& a);
+// z_model_assemble_kernel (predict.hip): the impedance of every member of a prepared plan from Y = cs [A'; A''] x
+struct ZModelArgs {
+    int nf, mask;                          // HIPDRT_INCLUDE_* bits
+    const double *Y, *Yn, *Yd;             // [B][2 nf]: DRT block (positive copy), negative copy, DOP block; null: term left out
+    const double* X; long long ldx;
+    const double* cs;
+    int idx_rinf, idx_induc, idx_cinv, vz_index;
+    double inductance_scale, capacitance_scale;
+    const double *freq, *strength;         // [nf]; strength null: no vz-offset factor
+    const int* fit_status;
+    double *z_re, *z_im;                   // [B][nf]
+};
+void launch_z_model_assemble(hipStream_t st, int B, const ZModelArgs& a);
+// dop_assemble_kernel (predict.hip): normalisation and ideal elements of the distribution of phasances, in place
+struct DopArgs {
+    int nn, include_ideal;
+    double* dop;                           // [B][nn]
+    const double *nu, *norm;               // [nn]; norm null: not normalised
+    double basis_area;
+    const double* X; long long ldx;
+    const double* cs;
+    int idx_rinf, idx_induc, idx_cinv;
+    double inductance_scale, capacitance_scale;
+    const int* fit_status;
+};
+void launch_dop_assemble(hipStream_t st, int B, const DopArgs& a);
+// out[b][j] = X[b][col + j] * v[b][j], out and v [B][nd]: every member's DOP block times its own dop_scale_vector
+void launch_scale_block(hipStream_t st, int B, int nd, const double* X, long long ldx, int col, const double* v, double* out);
 
 // peaks.hip: peak finding on evaluated rows, one workgroup per spectrum (all pointers device memory; an output may be null)
 struct PeakArgs {

@@ -460,6 +460,61 @@ int hipdrt_debug_pfrt_combine(hipdrt_ctx* ctx, int B, int S, int neval_pfrt, int
     return outs.back(st);
 } HIPDRT_CATCH
 
+// test hook (include/hipdrt_debug.h): response_chain (plan_response.hip) as it is, on host arrays; out between borders of marker bytes
+int hipdrt_debug_response(hipdrt_ctx* ctx, const hipdrt_debug_response_args* q) try {
+    HIPDRT_REQUIRE(ctx && q && q->X && q->step_sizes && q->coefficient_scale && q->out, "NULL pointer");
+    const int B = q->B, S = q->S, nt = q->nt, ntau = q->ntau, n = q->n, ns = q->ns, nd = q->dop_size, nvb = q->vb_size;
+    HIPDRT_REQUIRE(B >= 1 && B <= 65535 && S >= 1 && nt >= 1 && nt <= 65535 && ntau >= 1 && n >= 1, "1 <= B, nt <= 65535; S, ntau, n >= 1");
+    HIPDRT_REQUIRE((long long)S * nt <= (1 << 22) - 64, "S * nt < 2^22");
+    HIPDRT_REQUIRE(q->copies == 1 || q->copies == 2, "copies: 1 or 2");
+    HIPDRT_REQUIRE(ns >= 0 && (long long)ns + (long long)q->copies * ntau <= n, "the DRT block must lie inside [0, n)");
+    HIPDRT_REQUIRE(nd >= 0 && q->dop_start >= 0 && (long long)q->dop_start + nd <= n, "the DOP block must lie inside [0, n)");
+    HIPDRT_REQUIRE(nvb >= 0 && q->vb_start >= 0 && (long long)q->vb_start + nvb <= n, "the baseline block must lie inside [0, n)");
+    for (int idx : {q->idx_rinf, q->idx_cinv, q->vz_index}) HIPDRT_REQUIRE(idx >= -1 && idx < n, "special indices: -1 or inside [0, n)");
+    HIPDRT_REQUIRE(q->include_mask >= 0 && q->include_mask < 128, "include_mask: HIPDRT_INCLUDE_* bits");
+    HIPDRT_REQUIRE(nvb == 0 || !q->vb_mat || (q->v_baseline_scale && q->response_signal_scale),
+                   "a baseline term needs v_baseline_scale and response_signal_scale");
+    hipStream_t st; TRY(enter(ctx, &st));
+    const size_t tb = (size_t)nt * sizeof(double), bb = (size_t)B * sizeof(double);
+    DevBuf dx, du, dud, ddsv, dxd, dsz, dcs, drss, dsro, dinf, dcap, dstr, dvb, dvs, dfs, t, tn, td;
+    TRY(upload(dx, q->X, (size_t)B * n * sizeof(double), st));
+    if (q->U) TRY(upload(du, q->U, (size_t)S * ntau * tb, st));
+    const bool dop = q->Ud && nd > 0;
+    if (dop) {
+        TRY(upload(dud, q->Ud, (size_t)S * nd * tb, st));
+        std::vector<double> ones((size_t)B * nd, 1.0);
+        TRY(upload(ddsv, q->dop_scale_vector ? q->dop_scale_vector : ones.data(), ones.size() * sizeof(double), st));
+        HIPDRT_CHECK(hipStreamSynchronize(st));       // (ones leaves scope)
+        HIPDRT_CHECK(dxd.alloc(ones.size() * sizeof(double)));
+    }
+    TRY(upload(dsz, q->step_sizes, (size_t)(q->sizes_batched ? B : 1) * S * sizeof(double), st));
+    TRY(upload(dcs, q->coefficient_scale, bb, st));
+    ResponseArgs a{};
+    a.S = S; a.nt = nt; a.mask = q->include_mask; a.sizes = dsz.d(); a.sizes_batched = q->sizes_batched != 0;
+    a.X = dx.d(); a.ldx = n; a.cs = dcs.d();
+    if (q->response_signal_scale) { TRY(upload(drss, q->response_signal_scale, bb, st)); a.rss = drss.d(); }
+    if (q->scaled_response_offset) { TRY(upload(dsro, q->scaled_response_offset, bb, st)); a.sro = dsro.d(); }
+    a.idx_rinf = q->idx_rinf; a.idx_cinv = q->idx_cinv; a.vz_index = q->vz_index; a.vb_start = q->vb_start; a.vb_size = nvb;
+    a.capacitance_scale = q->capacitance_scale;
+    if (q->inf_rv) { TRY(upload(dinf, q->inf_rv, (q->inf_batched ? B : 1) * tb, st)); a.inf_rv = dinf.d(); a.inf_batched = q->inf_batched != 0; }
+    if (q->cap_rv) { TRY(upload(dcap, q->cap_rv, (q->cap_batched ? B : 1) * tb, st)); a.cap_rv = dcap.d(); a.cap_batched = q->cap_batched != 0; }
+    if (q->vz_strength) { TRY(upload(dstr, q->vz_strength, tb, st)); a.strength = dstr.d(); }
+    if (q->vb_mat && nvb > 0) {
+        TRY(upload(dvb, q->vb_mat, tb * nvb, st)); a.vb_mat = dvb.d();
+        TRY(upload(dvs, q->v_baseline_scale, (size_t)nvb * sizeof(double), st)); a.vb_scale = dvs.d();
+    }
+    if (q->fit_status) { TRY(upload(dfs, q->fit_status, (size_t)B * sizeof(int), st)); a.fit_status = dfs.i(); }
+    Guarded g;
+    TRY(g.up("out", q->out, (size_t)B * tb, st));
+    a.out = g.dd();
+    if (dop) launch_scale_block(st, B, nd, dx.d(), n, q->dop_start, ddsv.d(), dxd.d());
+    TRY(response_chain(st, B, ntau, q->copies, ns, q->U ? du.d() : nullptr, dop ? dud.d() : nullptr, dop ? dxd.d() : nullptr, nd,
+                       a, t, tn, td));
+    TRY(g.fetch(st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    return g.check();
+} HIPDRT_CATCH
+
 // test hook (include/hipdrt_debug.h): peak_resolve_kernel as it is, on host arrays.  Every output sits between two borders of marker bytes.
 int hipdrt_debug_peak_resolve(hipdrt_ctx* ctx, const hipdrt_debug_peak_resolve_args* q) try {
     HIPDRT_REQUIRE(ctx && q && q->f && q->fxx && q->x && q->ln_tau_find && q->ln_basis, "NULL pointer");

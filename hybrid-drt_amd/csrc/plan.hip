@@ -325,6 +325,7 @@ int hipdrt_plan_upload_prepared(hipdrt_plan* p, int B, int rm_batched, const dou
     p->B = B;
     p->prepped = 0;
     p->pf_steps = 0;            // (recorded PFRT steps belong to the batch they were fitted on)
+    p->pd_set = 0;              // (so do the post-fit scales of the prediction description)
     return HIPDRT_OK;
 } HIPDRT_CATCH
 

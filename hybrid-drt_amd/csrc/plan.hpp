@@ -138,6 +138,12 @@ struct hipdrt_plan : PlanShape {
     DevBuf basis_ln_tau;
     int basis_nb = 0;
     double basis_eps = 0;
+    // prediction description of a prepared plan (hipdrt_plan_set_predict_desc): what its special columns mean and the post-fit
+    // scales of the staged batch -- dop_scale_vector [B][dop_size] (solve_rp rescales it per member), v_baseline_scale [vb_size]; coefficient scale, response signal
+    // scale and scaled response offset [B]
+    int pd_set = 0, pd_idx_rinf = -1, pd_idx_induc = -1, pd_idx_cinv = -1;
+    double pd_inductance_scale = 0, pd_capacitance_scale = 0;
+    DevBuf pd_dop_scale, pd_vb_scale, pd_cs, pd_rss, pd_sro;
     // The kernel is chosen per fit from the number of spectra actually staged: a plan sized for a thousand spectra that is
     // handed one or a handful runs them on several workgroups each, inside the scratch it already has.
     void qp_layout(int B, QpArgs& qa) const {
@@ -251,6 +257,14 @@ struct PredictTimer {
         (void)hipGetLastError();
     }
 };
+
+// ---- plan_response.hip: the voltage response of a prepared plan's batch, and its test hook in debug.hip ---------------------------
+// Everything on the device: X [B][ldx] scaled solutions with the DRT block at column ns (copies = 2: positive copy, negative copy),
+// U [S nt][ntau] unit-step layers, Ud [S nt][dop_size] unit phasor layers applied to Xd [B][dop_size], every member's DOP block times
+// its own dop_scale_vector (launch_scale_block; Ud or Xd null: no DOP term).  a carries sizes, scales, vectors, mask and out; T / Tn /
+// Td / ldt are set here from the three scratch buffers, which the caller keeps until the stream has been synchronised.
+int response_chain(hipStream_t st, int B, int ntau, int copies, int ns, const double* U, const double* Ud, const double* Xd,
+                   int dop_size, ResponseArgs a, DevBuf& t, DevBuf& tn, DevBuf& td);
 
 // ---- plan_drt.hip: the DRT chain (prediction, peaks, per-peak resolution, PFRT) and the test hooks of its kernels in debug.hip ----
 // the tau basis a prediction evaluates: the plan's own grid, or what hipdrt_plan_set_tau_basis gave a prepared plan

@@ -3,7 +3,8 @@
 //
 //     Y[b][i] = scale_b * sum_j E[i][j] * x[b][col_offset + j]            (a B x r x K product, x resident on the device)
 //
-// followed by a per-element epilogue (credible band, impedance assembly).  FP64 only; the contraction runs on
+// followed by a per-element epilogue (credible band, impedance assembly; for a prepared plan the voltage response, the impedance
+// with every special term and the distribution of phasances: hipdrt/models/response.py).  FP64 only; the contraction runs on
 // v_mfma_f64_16x16x4_f64.  hipdrt/models/predict.py is the same arithmetic in numpy.
 //
 // Layout.  A 256-thread workgroup (4 wavefronts) owns 32 spectra x 64 evaluation rows.  Per 64-wide slab of k it stages
@@ -215,6 +216,135 @@ void launch_z_assemble(hipStream_t st, int B, int nf, const double* y, const dou
                        const int* fit_status, double* z_re, double* z_im) {
     hipLaunchKernelGGL(z_assemble_kernel, dim3(B, (nf + 255) / 256), dim3(256), 0, st, B, nf, y, X, ldx, idx_rinf, idx_induc, cs,
                        inductance_scale, freq, mask, fit_status, z_re, z_im);
+}
+
+// predict_response (drt1d.py:3363-3464) of every member from T = cs U x, the unit-step layers applied to the resident solution
+// (entry s * nt + i of row b): threads run along i, so T, the response vectors and out are read and written with unit stride.
+//   v = sum_s size[b][s] (T[b][s][i] - Tn[b][s][i])        one accumulator, s ascending: the same bits alone and in a batch
+//     + sum_s size[b][s] Td[b][s][i]
+//     + inf_rv[i] r_inf + c_inv cap_rv[i]
+//   v *= 1 + vz_offset strength[i];  v += vb_mat[i] . v_baseline
+// r_inf, c_inv and v_baseline in data units as extract_qphb_parameters forms them (6228-6289): the baseline coefficients lose their
+// column normalisation, the first one the scaled offset, then all take the response scale.  A failed fit gives a NaN row.
+__global__ __launch_bounds__(256) void response_assemble_kernel(int B, ResponseArgs a) {
+    const int i = blockIdx.y * blockDim.x + threadIdx.x, b = blockIdx.x;
+    if (i >= a.nt || b >= B) return;
+    const double* sz = a.sizes + (a.sizes_batched ? (size_t)b * a.S : 0);
+    const double* x = a.X + (size_t)b * a.ldx;
+    const double c = a.cs[b];
+    double v = 0.0;
+    if ((a.mask & HIPDRT_INCLUDE_DRT) && a.T) {
+        const double* t = a.T + (size_t)b * a.ldt + i;
+        const double* tn = a.Tn ? a.Tn + (size_t)b * a.ldt + i : nullptr;
+        double acc = 0.0;
+        for (int s = 0; s < a.S; ++s) {
+            double ts = t[(size_t)s * a.nt];
+            if (tn) ts = ts - tn[(size_t)s * a.nt];
+            acc += sz[s] * ts;
+        }
+        v += acc;
+    }
+    if ((a.mask & HIPDRT_INCLUDE_DOP) && a.Td) {
+        const double* t = a.Td + (size_t)b * a.ldt + i;
+        double acc = 0.0;
+        for (int s = 0; s < a.S; ++s) acc += sz[s] * t[(size_t)s * a.nt];
+        v += acc;
+    }
+    if ((a.mask & HIPDRT_INCLUDE_OHMIC) && a.idx_rinf >= 0 && a.inf_rv)
+        v += a.inf_rv[(a.inf_batched ? (size_t)b * a.nt : 0) + i] * (x[a.idx_rinf] * c);
+    if ((a.mask & HIPDRT_INCLUDE_CAP) && a.idx_cinv >= 0 && a.cap_rv)
+        v += (x[a.idx_cinv] * (c * a.capacitance_scale)) * a.cap_rv[(a.cap_batched ? (size_t)b * a.nt : 0) + i];
+    if ((a.mask & HIPDRT_INCLUDE_VZ_OFFSET) && a.vz_index >= 0 && a.strength) v *= 1.0 + x[a.vz_index] * a.strength[i];
+    if ((a.mask & HIPDRT_INCLUDE_BASELINE) && a.vb_size > 0 && a.vb_mat) {
+        double acc = 0.0;
+        for (int k = 0; k < a.vb_size; ++k) {
+            double coef = x[a.vb_start + k] * (1.0 / a.vb_scale[k]);
+            if (k == 0 && a.sro) coef -= a.sro[b];
+            acc += a.vb_mat[(size_t)i * a.vb_size + k] * (coef * a.rss[b]);
+        }
+        v += acc;
+    }
+    if (a.fit_status && a.fit_status[b] < 0) v = NAN;
+    a.out[(size_t)b * a.nt + i] = v;
+}
+
+void launch_response_assemble(hipStream_t st, int B, const ResponseArgs& a) {
+    hipLaunchKernelGGL(response_assemble_kernel, dim3(B, (a.nt + 255) / 256), dim3(256), 0, st, B, a);
+}
+
+// predict_z (drt1d.py:3500-3542) of every member of a prepared plan from Y = cs [A'; A''] x (row b: nf real parts, then nf
+// imaginary parts; Yn the negative copy of a series_neg block, Yd the phasor-Z rows of a DOP block):
+//   Z = (Y - Yn) + Yd + R_inf + j 2 pi f L + C_inv / (j 2 pi f),   Z *= 1 - vz_offset eis_strength[f]
+// every term switchable, the ideal elements rescaled like extract_qphb_parameters (6228-6289) and formed as numpy forms
+// `induc * 2j * np.pi * frequencies` and `c_inv * (2j * np.pi * frequencies) ** -1`.  A failed fit gives a NaN row.
+__global__ __launch_bounds__(256) void z_model_assemble_kernel(int B, ZModelArgs a) {
+    const int i = blockIdx.y * blockDim.x + threadIdx.x, b = blockIdx.x;
+    if (i >= a.nf || b >= B) return;
+    const double* x = a.X + (size_t)b * a.ldx;
+    const double c = a.cs[b];
+    const size_t o = (size_t)b * 2 * a.nf + i;
+    double re = 0.0, im = 0.0;
+    if ((a.mask & HIPDRT_INCLUDE_DRT) && a.Y) {
+        re = a.Y[o]; im = a.Y[o + a.nf];
+        if (a.Yn) { re = re - a.Yn[o]; im = im - a.Yn[o + a.nf]; }
+    }
+    if ((a.mask & HIPDRT_INCLUDE_OHMIC) && a.idx_rinf >= 0) re += x[a.idx_rinf] * c;
+    if ((a.mask & HIPDRT_INCLUDE_INDUCTANCE) && a.idx_induc >= 0) {
+        const double induc = x[a.idx_induc] * (c * a.inductance_scale);
+        im += ((induc * 2.0) * 3.141592653589793) * a.freq[i];
+    }
+    if ((a.mask & HIPDRT_INCLUDE_CAP) && a.idx_cinv >= 0)
+        im += (x[a.idx_cinv] * (c * a.capacitance_scale)) * -(1.0 / (6.283185307179586 * a.freq[i]));
+    if ((a.mask & HIPDRT_INCLUDE_DOP) && a.Yd) { re += a.Yd[o]; im += a.Yd[o + a.nf]; }
+    if ((a.mask & HIPDRT_INCLUDE_VZ_OFFSET) && a.vz_index >= 0 && a.strength) {
+        const double f = 1.0 - x[a.vz_index] * a.strength[i];
+        re *= f; im *= f;
+    }
+    if (a.fit_status && a.fit_status[b] < 0) { re = NAN; im = NAN; }
+    a.z_re[(size_t)b * a.nf + i] = re;
+    a.z_im[(size_t)b * a.nf + i] = im;
+}
+
+void launch_z_model_assemble(hipStream_t st, int B, const ZModelArgs& a) {
+    hipLaunchKernelGGL(z_model_assemble_kernel, dim3(B, (a.nf + 255) / 256), dim3(256), 0, st, B, a);
+}
+
+// predict_dop (drt1d.py:3273-3347) of every member from dop[b][i] = cs E (dop_scale_vector x_dop), in place: the division by
+// get_dop_norm's vector (null: none), then the ideal elements at nu = 0, 1, -1 -- R_inf, inductance and C_inv in data units, each
+// divided by norm[i] * basis_area when normalised (they are delta functions: the basis-function area does not scale them).
+__global__ __launch_bounds__(256) void dop_assemble_kernel(int B, DopArgs a) {
+    const int i = blockIdx.y * blockDim.x + threadIdx.x, b = blockIdx.x;
+    if (i >= a.nn || b >= B) return;
+    const double* x = a.X + (size_t)b * a.ldx;
+    const double c = a.cs[b], nu = a.nu[i];
+    double v = a.dop[(size_t)b * a.nn + i];
+    if (a.norm) v = v / a.norm[i];
+    if (a.include_ideal && (nu == 0.0 || nu == 1.0 || nu == -1.0)) {
+        double e = 0.0;
+        if (nu == 0.0) e = a.idx_rinf >= 0 ? x[a.idx_rinf] * c : 0.0;
+        else if (nu == 1.0) e = a.idx_induc >= 0 ? x[a.idx_induc] * (c * a.inductance_scale) : 0.0;
+        else e = a.idx_cinv >= 0 ? x[a.idx_cinv] * (c * a.capacitance_scale) : 0.0;
+        if (a.norm) e = e / (a.norm[i] * a.basis_area);
+        v += e;
+    }
+    if (a.fit_status && a.fit_status[b] < 0) v = NAN;
+    a.dop[(size_t)b * a.nn + i] = v;
+}
+
+void launch_dop_assemble(hipStream_t st, int B, const DopArgs& a) {
+    hipLaunchKernelGGL(dop_assemble_kernel, dim3(B, (a.nn + 255) / 256), dim3(256), 0, st, B, a);
+}
+
+// out[b][j] = X[b][col + j] * v[b][j]: the DOP block of every member times that member's own dop_scale_vector (solve_rp rescales
+// it per member), the operand the DOP rows are applied to
+__global__ void scale_block_kernel(int B, int nd, const double* __restrict__ X, long long ldx, int col, const double* __restrict__ v,
+                                   double* __restrict__ out) {
+    const int j = blockIdx.y * blockDim.x + threadIdx.x, b = blockIdx.x;
+    if (j < nd && b < B) out[(size_t)b * nd + j] = X[(size_t)b * ldx + col + j] * v[(size_t)b * nd + j];
+}
+
+void launch_scale_block(hipStream_t st, int B, int nd, const double* X, long long ldx, int col, const double* v, double* out) {
+    hipLaunchKernelGGL(scale_block_kernel, dim3(B, (nd + 255) / 256), dim3(256), 0, st, B, nd, X, ldx, col, v, out);
 }
 
 }  // namespace hipdrt

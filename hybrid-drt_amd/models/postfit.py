@@ -6,8 +6,8 @@ import warnings
 import numpy as np
 
 from .. import _ffi, preprocessing as pp
-from ..matrices import basis
-from . import peaks, predict
+from ..matrices import basis, mat1d
+from . import background, peaks, predict, response
 
 
 class PostFitMixin:
@@ -213,6 +213,222 @@ class PostFitMixin:
     def predict_r_tot(self, b=0):
         """DRT.predict_r_tot (drt1d.py:3583-3584) of member ``b`` of the last fit"""
         return float(self.predict_r_tot_batch()[b])
+
+    # ---- the voltage response of a chrono / hybrid fit (drt1d.py:3363-3474), on the prepared plan of the last fit ---------------
+    def _set_predict_desc(self, plan):
+        """gives the prepared plan what extract_qphb_parameters needs (hipdrt_plan_set_predict_desc): the meaning of its special
+        columns and the members' post-fit scales, as prepared.py keeps them in each prep"""
+        members, sp, kw = self._members(), self.special_qp_params, self.fit_kwargs
+        p0 = members[0]
+        idx = lambda name: sp[name]['index'] if name in sp else -1
+        chrono = p0['num_chrono'] > 0
+        plan.set_predict_desc(
+            idx('R_inf'), idx('inductance'), idx('C_inv'), kw['inductance_scale'], kw['capacitance_scale'],
+            [pr['coefficient_scale'] for pr in members],
+            # (solve_rp rescales the DOP columns of every member by that member's own factor)
+            dop_scale_vector=np.array([pr['dop_scale_vector'] for pr in members]) if p0['dop'] else None,
+            v_baseline_scale=p0['v_baseline_scale'] if chrono else None,
+            response_signal_scale=[pr['response_signal_scale'] for pr in members] if chrono else None,
+            scaled_response_offset=[pr['scaled_response_offset'] for pr in members] if chrono else None)
+
+    def _response_request(self, what, times, input_signal, step_times, step_sizes, op_mode, offset_steps, step_offset_size, x,
+                          subtract_background, y_bkg):
+        """the checks and defaults of a predict_response request (drt1d.py:3369-3387, 5994-6045) -> (plan, times, step_times,
+        step_sizes (S,) or (B, S), the input signal behind a measured ohmic response or None)"""
+        if subtract_background is False and y_bkg is None:
+            raise NotImplementedError(f'{what}: subtract_background=False without y_bkg is not taken (no chrono background is '
+                                      f'fitted here)')
+        if (op_mode if op_mode is not None else self.chrono_mode) != 'galv':
+            raise NotImplementedError(f"{what}: op_mode='pot' is not taken (galvanostatic prediction only)")
+        if self.step_model != 'ideal':
+            raise NotImplementedError(f'{what}: step_model={self.step_model!r} is not taken (ideal steps only)')
+        plan, scales = self._predict_plan(what, x=x)
+        if scales is None or self._members()[0].get('num_chrono', 0) == 0:
+            raise RuntimeError(f'{what} needs a finished chrono or hybrid fit (fit_chrono, fit_hybrid, fit_hybrid_batch)')
+        members = self._members()
+        if input_signal is not None and step_times is not None:
+            raise ValueError('Either input_signal OR (step_times and step_sizes) should be provided; '
+                             'received input_signal and step_times')
+        if step_times is not None and step_sizes is None:
+            raise ValueError('If input signal steps are provided, both step_times and step_sizes must be provided; '
+                             'received step_times only')
+        kw = self.fit_kwargs
+        offset_steps = kw['offset_steps'] if offset_steps is None else offset_steps
+        step_offset_size = kw['step_offset_size'] if step_offset_size is None else step_offset_size
+        times = members[0]['sample_times'] if times is None else np.asarray(times, dtype=float)
+        signals = None
+        if input_signal is None and step_times is None:
+            # the fitted signal: the members of one protocol share their step times, their measured step sizes differ
+            step_times = members[0]['step_times']
+            if any(not np.array_equal(pr['step_times'], step_times) for pr in members[1:]):
+                raise ValueError(f'{what}: the members of the batch do not share their step times; give step_times and step_sizes')
+            step_sizes = np.array([pr['step_sizes'] for pr in members])
+            signals = [pr['raw_input_signal'] for pr in members]
+        elif step_times is None:
+            input_signal = np.asarray(input_signal, dtype=float)
+            step_times, step_sizes, _ = pp.process_input_signal(times, input_signal, self.step_model, offset_steps, step_offset_size)
+            signals = [input_signal] * len(members)
+        step_times, step_sizes = np.asarray(step_times, dtype=float), np.asarray(step_sizes, dtype=float)
+        if step_sizes.shape not in ((len(step_times),), (len(members), len(step_times))):
+            raise ValueError(f'{what}: step_sizes must have one entry per step, or one row of them per member of the batch')
+        return plan, times, step_times, step_sizes, signals
+
+    def predict_response_batch(self, times=None, input_signal=None, step_times=None, step_sizes=None, op_mode=None,
+                               offset_steps=None, step_offset_size=None, include_dop=True, include_drt=True, include_ohmic=True,
+                               include_cap=True, smooth_inf_response=None, x=None, include_vz_offset=True,
+                               subtract_background=True, y_bkg=None, v_baseline=None, include_baseline=True):
+        """DRT.predict_response (drt1d.py:3363-3464) for every member of the last chrono / hybrid fit, at ANY times -> (B, nt);
+        times=None: the fit times, no signal and no steps: the fitted steps with every member's own step sizes.  The unit-step
+        response layers (and the phasor layers of a fit_dop fit) are built once for the batch on the device and applied to the
+        resident coefficients (hipdrt_plan_predict_response; models/response.py is the rule in numpy); the host forms only the
+        O(nt) ohmic and capacitance response vectors, the vz-offset strength at ``times`` and the baseline features.  y_bkg and
+        v_baseline, when given, are added as upstream adds them.  Rows of failed fits are NaN.  Ideal steps, galvanostatic;
+        last device batch only."""
+        what = 'predict_response'
+        plan, times, step_times, step_sizes, signals = self._response_request(
+            what, times, input_signal, step_times, step_sizes, op_mode, offset_steps, step_offset_size, x, subtract_background, y_bkg)
+        members, sp, kw = self._members(), self.special_qp_params, self.fit_kwargs
+        p0, B = members[0], len(members)
+        smooth = kw['smooth_inf_response'] if smooth_inf_response is None else smooth_inf_response
+        rows = step_sizes if step_sizes.ndim == 2 else step_sizes[None, :]
+        if not smooth and signals is None:
+            # given steps: upstream measures the ohmic response on the model signal of those steps (drt1d.py:6020-6021)
+            signals = [pp.generate_model_signal(times, step_times, rows[b if step_sizes.ndim == 2 else 0], None, self.step_model)
+                       for b in range(B)]
+        if not smooth and len(signals[0]) != len(times):
+            raise ValueError(f'{what}: smooth_inf_response=False takes the ohmic response from the input signal, which must be '
+                             f'given at the prediction times')
+        per_member = lambda fn: np.array([fn(b) for b in range(len(rows))]) if step_sizes.ndim == 2 else fn(0)
+        inf_rv = cap_rv = strength = vb_mat = None
+        if 'R_inf' in sp and include_ohmic:
+            # the ideal steps, or (smooth_inf_response=False) every member's own signal minus its pre-step mean
+            inf_of = lambda b: mat1d.construct_ohmic_response_vector(
+                times, self.step_model, step_times, rows[b if step_sizes.ndim == 2 else 0], None,
+                None if smooth else signals[b], smooth)
+            inf_rv = per_member(inf_of) if smooth else np.array([inf_of(b) for b in range(B)])
+        if 'C_inv' in sp and include_cap:
+            cap_rv = per_member(lambda b: mat1d.construct_capacitance_response_vector(times, self.step_model, step_times,
+                                                                                      rows[b], None))
+        if 'vz_offset' in sp and include_vz_offset:
+            strength = self._vz_strength(p0['sample_times'], p0['frequencies'], p0['nonconsec_step_times'], kw['vz_offset_eps'],
+                                         times=times)[0]
+        if include_baseline and v_baseline is None:
+            vb_mat = background.get_baseline_matrix(times, int(kw['v_baseline_deg']), normalize=False,
+                                                    sqrt=bool(kw['v_baseline_sqrt']))
+        mask = (_ffi.INCLUDE_DRT * bool(include_drt) | _ffi.INCLUDE_OHMIC * bool(include_ohmic) | _ffi.INCLUDE_CAP * bool(include_cap)
+                | _ffi.INCLUDE_DOP * bool(include_dop) | _ffi.INCLUDE_VZ_OFFSET * bool(include_vz_offset)
+                | _ffi.INCLUDE_BASELINE * (vb_mat is not None))
+        interp = self.integrate_method == 'interp'
+        self._set_predict_desc(plan)
+        out, _ = plan.predict_response(
+            times, step_times, step_sizes, basis_tau=self.basis_tau, mode=_ffi.MODE_INTERP if interp else _ffi.MODE_TRAPZ,
+            lookup=self._lookups(plan.ctx)['response'] if interp else None,
+            basis_nu=self.basis_nu if p0['dop'] else None, nu_epsilon=self.nu_epsilon if p0['dop'] else 0.0,
+            inf_rv=inf_rv, cap_rv=cap_rv, vz_strength=strength, vb_mat=vb_mat, include_mask=mask)
+        if v_baseline is not None:
+            out = out + np.asarray(v_baseline, dtype=float)
+        if not subtract_background:
+            if len(times) != len(y_bkg):
+                raise ValueError('Length of background does not match length of times')
+            out = out + np.asarray(y_bkg, dtype=float)
+        return out
+
+    def predict_response(self, times=None, input_signal=None, step_times=None, step_sizes=None, op_mode=None, offset_steps=None,
+                         step_offset_size=None, include_dop=True, include_drt=True, include_ohmic=True, include_cap=True,
+                         smooth_inf_response=None, x=None, include_vz_offset=True, subtract_background=True, y_bkg=None,
+                         v_baseline=None, b=0):
+        """DRT.predict_response (drt1d.py:3363-3464) of member ``b`` of the last chrono / hybrid fit, from the device.  The whole
+        batch is predicted and downloaded and row ``b`` returned: for many members call predict_response_batch once."""
+        return self.predict_response_batch(
+            times=times, input_signal=input_signal, step_times=step_times, step_sizes=step_sizes, op_mode=op_mode,
+            offset_steps=offset_steps, step_offset_size=step_offset_size, include_dop=include_dop, include_drt=include_drt,
+            include_ohmic=include_ohmic, include_cap=include_cap, smooth_inf_response=smooth_inf_response, x=x,
+            include_vz_offset=include_vz_offset, subtract_background=subtract_background, y_bkg=y_bkg, v_baseline=v_baseline)[b]
+
+    def predict_v_baseline(self, times, x_vb=None, b=0):
+        """DRT.predict_v_baseline (drt1d.py:3466-3473) of member ``b`` of the last chrono / hybrid fit: the baseline term of the
+        device prediction alone (of the whole batch, row ``b`` returned)"""
+        if x_vb is not None:
+            raise NotImplementedError('predict_v_baseline: the x_vb= override is not taken (the coefficients are the fit\'s own, '
+                                      'on the device)')
+        return self.predict_response_batch(times=times, include_dop=False, include_drt=False, include_ohmic=False,
+                                           include_cap=False, include_vz_offset=False)[b]
+
+    # ---- impedance and distribution of phasances of a prepared fit (drt1d.py:3273-3361, 3500-3542) ------------------------------
+    def predict_z_model_batch(self, frequencies=None, include_vz_offset=True, include_dop=True, include_drt=True,
+                              include_inductance=True, include_ohmic=True, include_cap=True, x=None):
+        """DRT.predict_z (drt1d.py:3500-3542) for every member of the last fit on a PREPARED plan -- hybrid, fit_dop,
+        fit_capacitance, solve_rp, series_neg and outlier-removal fits -- at ANY frequencies -> complex (B, nf);
+        frequencies=None: the fit frequencies.  The impedance matrices and the phasor-Z rows of a DOP block are built on the device
+        at the requested frequencies and applied to the resident coefficients; R_inf, the inductance, C_inv and the DOP term are
+        added in data units and the result is multiplied by 1 - vz_offset * strength(f) (hipdrt_plan_predict_z_model;
+        models/response.py is the rule in numpy).  Every term is switchable as upstream's include_* flags switch it.  Rows of
+        failed fits are NaN.  Plain EIS fits have predict_z_batch.  Last device batch only."""
+        what = 'predict_z_model_batch'
+        plan, scales = self._predict_plan(what, x=x)
+        if scales is None:
+            raise NotImplementedError(f'{what} is built for fits on a prepared plan (hybrid, fit_dop, fit_capacitance, solve_rp, '
+                                      f'series_neg); a plain EIS fit has predict_z_batch')
+        p0, sp, kw = self._members()[0], self.special_qp_params, self.fit_kwargs
+        if frequencies is None:
+            if p0['frequencies'] is None:
+                raise ValueError(f'{what}: a chrono fit has no fit frequencies; give frequencies')
+            frequencies = p0['frequencies']
+        f = np.asarray(frequencies, dtype=float)
+        strength = None
+        if 'vz_offset' in sp and include_vz_offset:
+            strength = self._vz_strength(p0['sample_times'], p0['frequencies'], p0['nonconsec_step_times'], kw['vz_offset_eps'],
+                                         predict_frequencies=f)[1]
+        mask = (_ffi.INCLUDE_DRT * bool(include_drt) | _ffi.INCLUDE_OHMIC * bool(include_ohmic) | _ffi.INCLUDE_CAP * bool(include_cap)
+                | _ffi.INCLUDE_DOP * bool(include_dop) | _ffi.INCLUDE_VZ_OFFSET * bool(include_vz_offset)
+                | _ffi.INCLUDE_INDUCTANCE * bool(include_inductance))
+        interp = self.integrate_method == 'interp'
+        self._set_predict_desc(plan)
+        return plan.predict_z_model(f, basis_tau=self.basis_tau, mode=_ffi.MODE_INTERP if interp else _ffi.MODE_TRAPZ,
+                                    lookups=self._lookups(plan.ctx)['z'] if interp else None,
+                                    basis_nu=self.basis_nu if p0['dop'] else None, nu_epsilon=self.nu_epsilon if p0['dop'] else 0.0,
+                                    vz_strength=strength, include_mask=mask)[0]
+
+    def predict_dop_batch(self, nu=None, x=None, normalize=False, normalize_tau=None, order=0, return_nu=False,
+                          normalize_quantiles=(0, 1), delta_density=False, include_ideal=True):
+        """DRT.predict_dop (drt1d.py:3273-3347) for every member of the last fit_dop fit -> (B, len(nu)), with return_nu
+        (nu, dop).  nu=None is upstream's grid: 1001 points on [-1, 1] joined with basis_nu and the ideal elements' -1, 0, 1.  The
+        evaluation rows are built on the device and applied to the resident DOP block with the member's dop_scale_vector and coefficient
+        scale (hipdrt_plan_predict_dop); normalize divides by get_dop_norm (3349-3361; normalize_tau=None: the measured tau range);
+        include_ideal adds R_inf, the inductance and C_inv at nu = 0, 1, -1 as upstream adds them.  Rows of failed fits are NaN."""
+        what = 'predict_dop'
+        if delta_density:
+            raise NotImplementedError(f'{what}: delta_density=True is not taken')
+        if order != 0:
+            raise NotImplementedError(f'{what}: order={order} is not taken (order 0 only)')
+        plan, scales = self._predict_plan(what, x=x)
+        p0 = self._members()[0]
+        if scales is None or not p0['dop']:
+            raise RuntimeError(f'{what} needs a finished fit with fit_dop=True')
+        if nu is None:
+            nu = np.unique(np.concatenate([self.basis_nu, np.linspace(-1, 1, 1001)]))
+            nu = np.unique(np.concatenate([nu, np.array([-1, 0, 1])]))
+        else:
+            nu = np.sort(np.asarray(nu, dtype=float))
+        area = np.sqrt(np.pi) / self.nu_epsilon
+        normalize_by = None
+        if normalize:
+            if normalize_tau is None:
+                normalize_tau = pp.get_tau_lim(p0['frequencies'], p0.get('sample_times'), p0.get('step_times'))
+            normalize_by = response.dop_norm(nu, normalize_tau, self.nu_epsilon, normalize_quantiles)
+        self._set_predict_desc(plan)
+        dop = plan.predict_dop(nu, self.basis_nu, self.nu_epsilon, normalize_by=normalize_by, nu_basis_area=area,
+                               include_ideal=include_ideal)[0]
+        return (nu, dop) if return_nu else dop
+
+    def predict_dop(self, nu=None, x=None, normalize=False, normalize_tau=None, order=0, return_nu=False,
+                    normalize_quantiles=(0, 1), delta_density=False, include_ideal=True, b=0):
+        """DRT.predict_dop (drt1d.py:3273-3347) of member ``b`` of the last fit_dop fit, from the device (the whole batch is
+        predicted, row ``b`` returned)"""
+        nu, dop = self.predict_dop_batch(nu=nu, x=x, normalize=normalize, normalize_tau=normalize_tau, order=order, return_nu=True,
+                                         normalize_quantiles=normalize_quantiles, delta_density=delta_density,
+                                         include_ideal=include_ideal)
+        return (nu, dop[b]) if return_nu else dop[b]
 
     # ---- peak finding (drt1d.py:3753-3947; mapping/curvature.py, mapping/drtmd.py:1023-1106) on the last fitted batch ------------
     def _find_peaks_device(self, what, tau, ppd, normalize, sign, method, extend_var, want=None, **opt_kw):

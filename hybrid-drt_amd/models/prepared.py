@@ -14,7 +14,7 @@ import numpy as np
 from .. import _ffi, preprocessing as pp
 from ..matrices import mat1d, phasance
 from ..utils.array import is_uniform
-from . import background, qphb
+from . import background, qphb, response
 
 _CHRONO_KW_DEFAULTS = dict(  # _qphb_fit_core chrono / hybrid keyword defaults (drt1d.py:102-129)
     step_times=None, step_sizes=None, offset_steps=True, step_offset_size=None, offset_baseline=True,
@@ -85,22 +85,14 @@ class PreparedFitMixin:
             memo[key] = kept[key] if key in kept else fn()
         return memo[key]
 
-    def _vz_strength(self, sample_times, frequencies, step_times, vz_offset_eps):
+    def _vz_strength(self, sample_times, frequencies, step_times, vz_offset_eps, times=None, predict_frequencies=None):
         """DRT._get_vz_strength_vec (drt1d.py:6173-6226): 1 where the two data sets overlap in time scale, Gaussian
-        decay in log time scale away from the overlap, 0 before the first step."""
-        rbf = lambda y, eps: np.exp(-(eps * y) ** 2)
-        deltas = pp.get_time_since_step(sample_times, step_times, prestep_value=-1)
-        chrono_tau_min = np.min(deltas[deltas > 0])
-        f_inv = 1 / (2 * np.pi * frequencies)
-        eis_tau_max = np.max(f_inv)
-        cs = np.ones(len(deltas))
-        far = deltas >= eis_tau_max
-        cs[far] = rbf(np.log(deltas[far] / eis_tau_max), vz_offset_eps)
-        cs[deltas == -1] = 0
-        es = np.ones(len(frequencies))
-        fast = f_inv <= chrono_tau_min
-        es[fast] = rbf(np.log(f_inv[fast] / chrono_tau_min), vz_offset_eps)
-        return cs, es
+        decay in log time scale away from the overlap, 0 before the first step -- at the fit's own samples, or at the given
+        prediction times / frequencies against the fit's overlap limits (models/response.py states the rule)."""
+        return response.vz_strength(sample_times if times is None else times,
+                                    frequencies if predict_frequencies is None else predict_frequencies,
+                                    fit_times=sample_times, step_times=step_times, fit_frequencies=frequencies,
+                                    vz_offset_eps=vz_offset_eps)
 
     # ---- _prep_for_fit + _format_qp_matrices + the set-up half of _qphb_fit_core --------------------------------------
     def _prepare_measurement(self, ctx, times, i_signal, v_signal, frequencies, z, kw, ckw, hypers):
@@ -610,21 +602,16 @@ class PreparedFitMixin:
 
     # ---- extract_qphb_parameters (drt1d.py:6228-6289) + the sigma vectors (1071-1081) -------------------------------
     def _extract(self, prep, x, weights, kw, ckw):
-        sp, ns, nc = prep['special'], prep['ns'], prep['num_chrono']
-        cs = prep['coefficient_scale']
-        fp = {'x': x[ns:] * cs,
-              'R_inf': x[sp['R_inf']['index']] * cs if 'R_inf' in sp else 0}
-        if 'v_baseline' in sp:
-            a = sp['v_baseline']['index']
-            vbx = x[a:a + sp['v_baseline']['size']] * (1.0 / prep['v_baseline_scale'])
-            vbx[0] -= prep['scaled_response_offset']
-            fp['v_baseline'] = vbx * prep['response_signal_scale']
-        if 'vz_offset' in sp:
-            fp['vz_offset'] = x[sp['vz_offset']['index']]
-        fp['inductance'] = x[sp['inductance']['index']] * (cs * kw['inductance_scale']) if 'inductance' in sp else 0
-        fp['C_inv'] = x[sp['C_inv']['index']] * (cs * kw['capacitance_scale']) if 'C_inv' in sp else 0
-        if prep['dop']:
-            fp['x_dop'] = x[prep['dop'][0]:prep['dop'][1]] * (prep['dop_scale_vector'] * cs)
+        sp, nc = prep['special'], prep['num_chrono']
+        idx = lambda name: sp[name]['index'] if name in sp else -1
+        # the rescaling itself is stated once, in models/response.py
+        fp = response.fit_parameters(
+            x, prep['ns'], prep['coefficient_scale'], idx_rinf=idx('R_inf'), idx_cinv=idx('C_inv'),
+            capacitance_scale=kw['capacitance_scale'], vz_index=idx('vz_offset'), vb_start=max(idx('v_baseline'), 0),
+            v_baseline_scale=prep['v_baseline_scale'] if 'v_baseline' in sp else None,
+            scaled_response_offset=prep.get('scaled_response_offset', 0.0), response_signal_scale=prep['response_signal_scale'],
+            dop_start=prep['dop'][0] if prep['dop'] else 0, dop_scale_vector=prep['dop_scale_vector'] if prep['dop'] else None,
+            idx_induc=idx('inductance'), inductance_scale=kw['inductance_scale'])
         sigma = 1.0 / weights
         nf = prep['num_eis']
         fp['v_sigma_tot'] = sigma[:nc] * prep['response_signal_scale'] if nc else None

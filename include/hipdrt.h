@@ -488,6 +488,89 @@ int hipdrt_plan_predict_z(hipdrt_plan* plan, const double* freq, int nf, int inc
  * HIPDRT_E_UNSUPPORTED when r_inf or r_tot is asked for).                                                                       */
 int hipdrt_plan_predict_resistances(hipdrt_plan* plan, double* r_p, double* r_inf, double* r_tot, int abs_norm);
 
+/* ---- model evaluation of a prepared plan: voltage response, impedance and distribution of phasances ---------------------------
+ * A prepared plan runs at unit scale and does not know what its special columns mean; hipdrt_prepared_desc gives it dop_start /
+ * dop_size, vz_index and vb_start / vb_size.  This is the rest of what DRT.extract_qphb_parameters (hybdrt/models/drt1d.py:
+ * 6228-6289) needs to turn the scaled solution into data units, given AFTER a fit (the per-member scales change under solve_rp and
+ * update_scale; they must be the post-fit values).  Arrays are copied; a NULL array is allowed where its block is absent.        */
+typedef struct {
+    int idx_rinf, idx_induc, idx_cinv;         /* columns of R_inf, inductance and C_inv (-1: none)                              */
+    double inductance_scale, capacitance_scale;
+    const double* dop_scale_vector;            /* [dop_size], or [B][dop_size] when dop_scale_batched != 0: solve_rp rescales the
+                                                  DOP columns of every member by that member's own factor (drt1d.py:596-606)     */
+    int dop_scale_batched;
+    const double* v_baseline_scale;            /* [vb_size]: the column normalisation of the baseline block                     */
+    const double* coefficient_scale;           /* [B]                                                                           */
+    const double* response_signal_scale;       /* [B] (NULL: a plan without chrono rows)                                        */
+    const double* scaled_response_offset;      /* [B] (NULL: 0)                                                                 */
+} hipdrt_predict_desc;
+/* B = the fitted batch.  HIPDRT_E_INVALID for a plan that is not prepared or holds no fitted batch, for an index outside the
+ * special block, a shared scale that is not finite, or a missing array of a block the plan has.  Holds until the next upload.           */
+int hipdrt_plan_set_predict_desc(hipdrt_plan* plan, const hipdrt_predict_desc* desc);
+
+/* terms of hipdrt_plan_predict_response (include_drt / include_ohmic / include_cap / include_dop / include_vz_offset of
+ * DRT.predict_response, and its v_baseline)                                                                                    */
+#define HIPDRT_INCLUDE_DRT 1
+#define HIPDRT_INCLUDE_OHMIC 2
+#define HIPDRT_INCLUDE_CAP 4
+#define HIPDRT_INCLUDE_DOP 8
+#define HIPDRT_INCLUDE_VZ_OFFSET 16
+#define HIPDRT_INCLUDE_BASELINE 32
+#define HIPDRT_INCLUDE_INDUCTANCE 64   /* hipdrt_plan_predict_z_model only: ideal steps induce nothing, the response ignores it */
+typedef struct {
+    const double* times; int nt;               /* prediction times, any                                                         */
+    const double* step_times; int nsteps;      /* [S] shared by the batch                                                       */
+    const double* step_sizes; int sizes_batched;   /* [S], or [B][S] when sizes_batched != 0                                    */
+    const double* basis_tau;                   /* [nb of hipdrt_plan_set_tau_basis]: the tau basis itself (not its logarithm)    */
+    int mode, ny;                              /* HIPDRT_MODE_INTERP / _TRAPZ and the trapezoid's points, as hipdrt_response_matrix */
+    int ngrid; const double *log_td, *v;       /* the response lookup table (INTERP)                                            */
+    const double* basis_nu; double nu_epsilon; /* [dop_size], needed when the DOP term is on and the plan has a DOP block        */
+    const double* inf_rv; int inf_batched;     /* ohmic response vector [nt] or [B][nt] (mat1d.construct_ohmic_response_vector)  */
+    const double* cap_rv; int cap_batched;     /* capacitance response vector [nt] or [B][nt]                                   */
+    const double* vz_strength;                 /* [nt] chrono strength of the vz offset at `times` (drt1d.py:6173-6226)          */
+    const double* vb_mat;                      /* [nt][vb_size] background.get_baseline_matrix(times, normalize=False)           */
+    int include_mask;                          /* HIPDRT_INCLUDE_* bits                                                        */
+} hipdrt_response_args;
+/* DRT.predict_response (drt1d.py:3363-3464; ideal steps, galvanostatic, background subtracted) for every member of the fitted
+ * batch of a prepared plan, at any times: out[b][i] in data units.  The unit-step layers U[S][nt][ntau] (and the phasor-V layers
+ * of a DOP block, applied to every member's DOP block times its own dop_scale_vector) are built once for the batch by the kernels of
+ * hipdrt_response_matrix / hipdrt_phasor_v_matrix; their S nt stacked rows are applied to every member's resident x by the kernel
+ * of hipdrt_plan_predict_drt (both copies of a series_neg block); response_assemble_kernel then forms, per (b, i),
+ *   ( sum_s size[b][s] T_drt[b][s][i] + sum_s size[b][s] T_dop[b][s][i] + r_inf inf_rv[i] + c_inv cap_rv[i] )
+ *   * (1 + vz_offset_b strength[i]) + vb_mat[i] . v_baseline_b
+ * with the sums over s ascending in one accumulator, so a member gives the same bits alone and inside a batch.  No per-member
+ * [B][nt][ntau] matrix is formed.  A term whose bit is off, or whose block or vector is absent (NULL), is left out.  status[B] (may
+ * be NULL): the fit's status; the row of a failed fit is NaN.  Needs hipdrt_plan_set_tau_basis and hipdrt_plan_set_predict_desc
+ * (HIPDRT_E_INVALID says which is missing).                                                                                     */
+int hipdrt_plan_predict_response(hipdrt_plan* plan, const hipdrt_response_args* args, double* out, int* status);
+
+typedef struct {
+    const double* freq; int nf;                /* prediction frequencies, any (positive)                                         */
+    const double* basis_tau;                   /* [nb of hipdrt_plan_set_tau_basis]                                              */
+    int mode, ny;                              /* as hipdrt_impedance_matrix                                                     */
+    int ngrid; const double *log_wt_re, *z_re, *log_wt_im, *z_im;   /* the impedance lookup tables (INTERP)                      */
+    const double* basis_nu; double nu_epsilon; /* [dop_size], needed when the DOP term is on and the plan has a DOP block        */
+    const double* vz_strength;                 /* [nf] eis strength of the vz offset at `freq` (drt1d.py:6173-6226), or NULL     */
+    int include_mask;                          /* HIPDRT_INCLUDE_DRT, _OHMIC, _CAP, _DOP, _VZ_OFFSET, _INDUCTANCE                */
+} hipdrt_z_model_args;
+/* DRT.predict_z (drt1d.py:3500-3542) for every member of the fitted batch of a PREPARED plan (hybrid, fit_dop, fit_capacitance,
+ * solve_rp, series_neg fits), at any frequencies: [A'; A''] (mat1d.construct_impedance_matrix, no Toeplitz shortcut) and the
+ * phasor-Z rows of a DOP block (phasance.construct_phasor_z_matrix; applied to x_dop times the member's dop_scale_vector) are built at freq
+ * and applied to the resident x by the kernel of hipdrt_plan_predict_drt; z_model_assemble_kernel adds R_inf, j 2 pi f L,
+ * C_inv / (j 2 pi f) and the DOP term in data units and multiplies by 1 - vz_offset strength[f].  z_re, z_im [B][nf]; status[B]
+ * (may be NULL) the fit's status, rows of a failed fit are NaN.  Needs hipdrt_plan_set_tau_basis and
+ * hipdrt_plan_set_predict_desc.  hipdrt_plan_predict_z is unchanged: it serves plain EIS plans and refuses prepared ones.        */
+int hipdrt_plan_predict_z_model(hipdrt_plan* plan, const hipdrt_z_model_args* args, double* z_re, double* z_im, int* status);
+
+/* DRT.predict_dop (drt1d.py:3273-3347; order 0, no delta_density) for every member of the fitted batch of a prepared plan with a
+ * DOP block: out[b][i] = cs_b sum_j E[i][j] dop_scale_vector_b[j] x_b[dop_start + j] with E = hipdrt_func_eval_matrix(basis_nu, nu,
+ * nu_epsilon), divided by normalize_by[i] (get_dop_norm, 3349-3361: the caller's vector, NULL = not normalised); include_ideal != 0
+ * adds R_inf at nu = 0, the inductance at nu = 1 and C_inv at nu = -1 as upstream adds them (divided by normalize_by[i] *
+ * nu_basis_area when normalised).  nu [nn] in ascending order; out [B][nn]; status[B] may be NULL; a failed fit gives a NaN row.
+ * Needs hipdrt_plan_set_predict_desc.                                                                                            */
+int hipdrt_plan_predict_dop(hipdrt_plan* plan, const double* nu, int nn, const double* basis_nu, double nu_epsilon,
+                            const double* normalize_by, double nu_basis_area, int include_ideal, double* out, int* status);
+
 /* ---- peak finding for the fitted batch ---------------------------------------------------------------------------------------
  * Options of DRT.find_peaks (hybdrt/models/drt1d.py:3753-3947) and of the map's peak probabilities (curvature.peak_prob_1d,
  * hybdrt/mapping/curvature.py:12-58; DRTMD.predict_curv_prob, hybdrt/mapping/drtmd.py:1097-1104).                              */

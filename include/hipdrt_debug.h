@@ -5,7 +5,7 @@
  * (in-kernel phase counters of a PROFILE build, occupancy queries).  Every hook takes a context: there is no process-wide
  * switch.  The kernels of the fit loop each have a hook that runs their launcher as it is on host arrays: hipdrt_debug_gram_l2
  * (Gram, q), hipdrt_debug_hyper_step (the hyper-parameter step in its three product forms), hipdrt_debug_kk_stats,
- * hipdrt_debug_apply_rows, hipdrt_debug_find_peaks, hipdrt_debug_peak_resolve.
+ * hipdrt_debug_apply_rows, hipdrt_debug_find_peaks, hipdrt_debug_peak_resolve, hipdrt_debug_response.
  */
 #ifndef HIPDRT_DEBUG_H
 #define HIPDRT_DEBUG_H
@@ -184,10 +184,37 @@ int hipdrt_debug_pfrt_combine(hipdrt_ctx* ctx, int B, int S, int neval_pfrt, int
                               const hipdrt_pfrt_opts* opts, const double* ln_tau_pfrt, const double* ln_tau_out, double* pfrt,
                               double* raw_pfrt, double* post_prob);
 
-/* tools hook (tools/bench_predict.py, tools/bench_peaks.py): kernel time in ms of the last hipdrt_plan_predict_drt /
- * hipdrt_plan_predict_z / hipdrt_plan_find_peaks (ms[0]: the mean rows, ms[1]: all launches, peaks_kernel included) of a plan of
- * this context, by HIP events around its launches (allocations and copies excluded): ms[0] up to the mean (predict_z: the whole
- * prediction), ms[1] with the credible band's factorisation included (equal to ms[0] without a band).                         */
+/* test hook (tests/test_gpu_response.py): the device chain of hipdrt_plan_predict_response behind its layer builders -- the DOP
+ * blocks times their scale vectors, the row-application kernel on the S nt stacked rows of U (both copies of a two-copy block) and
+ * of Ud, then response_assemble_kernel (csrc/predict.hip) -- on host arrays, no fit needed.  The assembly kernel is reached through
+ * the products it reads (T = cs U x is formed by the hook, as the entry point forms it); it cannot be fed a T of the caller's.
+ * X [B][n] scaled solutions, DRT block at column ns; U [S][nt][ntau] unit-step layers or NULL; Ud [S][nt][dop_size] unit phasor layers
+ * or NULL; dop_scale_vector [B][dop_size] per member, or NULL (1); the other fields as hipdrt_predict_desc and hipdrt_response_args
+ * name them (NULL leaves a term out).  out [B][nt] sits between two borders of marker bytes: HIPDRT_E_NUMERIC when the kernel
+ * changed one.  Every index and block is checked against n before anything is launched.                                         */
+typedef struct {
+    int B, S, nt, ntau, copies, ns, n;
+    const double *X, *U, *Ud;
+    int dop_start, dop_size;
+    const double* dop_scale_vector;
+    const double* step_sizes; int sizes_batched;
+    const double *coefficient_scale, *response_signal_scale, *scaled_response_offset;      /* [B]; the last two may be NULL */
+    int idx_rinf, idx_cinv, vz_index, vb_start, vb_size;
+    double capacitance_scale;
+    const double* inf_rv; int inf_batched;
+    const double* cap_rv; int cap_batched;
+    const double *vz_strength, *vb_mat, *v_baseline_scale;
+    const int* fit_status;      /* [B] or NULL */
+    int include_mask;
+    double* out;
+} hipdrt_debug_response_args;
+int hipdrt_debug_response(hipdrt_ctx* ctx, const hipdrt_debug_response_args* a);
+
+/* tools hook (tools/bench_predict.py, tools/bench_peaks.py, tools/bench_response.py): kernel time in ms of the last
+ * hipdrt_plan_predict_drt / hipdrt_plan_predict_z / hipdrt_plan_find_peaks (ms[0]: the mean rows, ms[1]: all launches, peaks_kernel
+ * included) or hipdrt_plan_predict_response / _z_model / _dop (ms[0] = ms[1]: all launches; _z_model with the upload of its grids and tables) of a plan of this context, by HIP
+ * events around its launches (allocations and copies excluded): ms[0] up to the mean (predict_z: the whole prediction), ms[1] with
+ * the credible band's factorisation included (equal to ms[0] without a band).                                                    */
 int hipdrt_debug_last_predict_ms(hipdrt_ctx* ctx, float* ms);
 
 #ifdef __cplusplus
