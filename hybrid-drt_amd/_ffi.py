@@ -110,6 +110,18 @@ class PeakResolveOut(C.Structure):
                 ("r_coef", _dp), ("x_peaks", _dp), ("peak_gammas", _dp), ("status", _ip)]
 
 
+class CandidatesIn(C.Structure):
+    """hipdrt_candidates_in (include/hipdrt.h)"""
+    _fields_ = [("source", C.c_int), ("C", C.c_int), ("x", _dp), ("ncand", _ip), ("ln_tau_find", _dp), ("nfind", C.c_int),
+                ("peak_opts", C.POINTER(PeakOpts)), ("max_peaks", C.c_int)]
+
+
+class CandidatesOut(C.Structure):
+    """hipdrt_candidates_out (include/hipdrt.h)"""
+    _fields_ = [("rss", _dp), ("sum_log_w", _dp), ("count", _ip), ("peak_index", _ip), ("heights", _dp), ("prominences", _dp),
+                ("status", _ip)]
+
+
 class DebugPeakResolveArgs(C.Structure):
     """hipdrt_debug_peak_resolve_args (include/hipdrt_debug.h)"""
     _fields_ = [("B", C.c_int), ("nfind", C.c_int), ("nb", C.c_int), ("nout", C.c_int), ("copies", C.c_int), ("source", C.c_int),
@@ -244,10 +256,14 @@ SIGNATURES = {
     "hipdrt_plan_resolve_peaks": [_vp, C.POINTER(PeakResolveIn), C.POINTER(PeakResolveOpts), C.POINTER(PeakResolveOut)],
     "hipdrt_plan_integrate_drt": [_vp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _ip, _ip, C.c_int, _dp, _ip],
     "hipdrt_debug_peak_resolve": [_vp, C.POINTER(DebugPeakResolveArgs)],
+    "hipdrt_plan_score_candidates": [_vp, C.POINTER(CandidatesIn), C.POINTER(CandidatesOut)],
+    "hipdrt_debug_candidate_llh": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp],
+    "hipdrt_debug_candidate_form": [_vp, C.c_int],
     "hipdrt_plan_pfrt_bytes_per_spectrum": [C.c_int, C.c_int, C.POINTER(C.c_longlong)],
     "hipdrt_plan_pfrt_begin": [_vp, C.c_int],
     "hipdrt_plan_pfrt_record": [_vp],
     "hipdrt_plan_pfrt_steps": [_vp, _ip],
+    "hipdrt_plan_pfrt_restore_s": [_vp, C.c_int, C.c_double],
     "hipdrt_plan_pfrt_get_step": [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip],
     "hipdrt_plan_get_step_p_matrix": [_vp, C.c_int, C.c_int, _dp],
     "hipdrt_pfrt_opts_default": [C.POINTER(PfrtOpts)],
@@ -433,6 +449,9 @@ def pfrt_bytes_per_spectrum(n, steps):
 
 PEAKS_OVERFLOW, PEAKS_UNORDERED = -4, -5            # per-spectrum statuses of hipdrt_plan_resolve_peaks
 PEAKS_FROM_FIND, PEAKS_FROM_INDICES, PEAKS_FROM_WINDOWS = 0, 1, 2
+CANDIDATES_FROM_STEPS, CANDIDATES_FROM_HOST = 0, 1
+CANDIDATE_ABSENT = -6                               # status of a slot at or past the spectrum's ncand (hipdrt_plan_score_candidates)
+CANDIDATE_OUTPUTS = ("rss", "sum_log_w", "count", "peak_index", "heights", "prominences", "status")
 RESOLVE_OUTPUTS = ("count", "peak_index", "trough_index", "eps_l", "eps_r", "r_peaks", "r_coef", "x_peaks", "peak_gammas", "status")
 
 
@@ -1107,6 +1126,24 @@ class Context:
                                                    _p(ltp), _p(lto), _p(out["pfrt"]), _p(out["raw_pfrt"]), _p(out["post_prob"])))
         return out
 
+    def debug_candidate_llh(self, x, rm, rv, vmm, var_floor):
+        """tests: the likelihood kernels of csrc/candidates.hip on host arrays (hipdrt_debug_candidate_llh): x (C, B, n), rm (m, n)
+        or (B, m, n), rv (B, m), vmm (m, m), var_floor (B,) -> (rss, sum_log_w), each (C, B).  Raises when a kernel wrote outside
+        an output."""
+        x, rm, rv, vmm, vf = _f64(x), _f64(rm), _f64(rv), _f64(vmm), _f64(var_floor).ravel()
+        Cn, B, n = x.shape
+        m = rv.shape[1]
+        if rm.shape not in ((m, n), (B, m, n)) or rv.shape != (B, m) or vmm.shape != (m, m) or vf.shape != (B,):
+            raise ValueError("shapes: x (C, B, n); rm (m, n) or (B, m, n); rv (B, m); vmm (m, m); var_floor (B,)")
+        rss, slw = np.full((Cn, B), 7e77), np.full((Cn, B), 7e77)
+        _check(self._lib.hipdrt_debug_candidate_llh(self._h, Cn, B, m, n, _p(rm), int(rm.ndim == 3), _p(rv), _p(vmm), _p(vf), _p(x),
+                                                    _p(rss), _p(slw)))
+        return rss, slw
+
+    def debug_candidate_form(self, form):
+        """tests: how candidate scoring on this context keeps rm x between its two products: 0 LDS, 1 scratch, -1 automatic"""
+        _check(self._lib.hipdrt_debug_candidate_form(self._h, int(form)))
+
     def debug_last_predict_ms(self):
         """tools: kernel time in ms of the last predict_drt / predict_z of a plan of this context -> (mean or impedance, with band)"""
         ms = (C.c_float * 2)()
@@ -1214,7 +1251,7 @@ class Plan:
                   "m1": (self.n, self.n), "m2": (self.n, self.n), "vmm": (self.m, self.m), "h": (self.n,),
                   "est_weights": (self.batch, self.m), "rv": (self.batch, self.m), "xmx": (self.batch, 3),
                   "outlier_t": (self.batch, self.m), "row_factors": (self.batch, self.m), "x": (self.batch, self.n),
-                  "coef_scale": (self.batch,)}
+                  "coef_scale": (self.batch,), "var_floor": (self.batch,)}
         out = np.empty(shapes[which])
         _check(self._lib.hipdrt_plan_get(self._h, which.encode(), _p(out), out.size))
         return out
@@ -1369,6 +1406,47 @@ class Plan:
         _check(self._lib.hipdrt_plan_resolve_peaks(self._h, C.byref(i), C.byref(opts), C.byref(u)))
         return out
 
+    def score_candidates(self, x=None, ncand=None, ln_tau_find=None, opts: PeakOpts | None = None, max_peaks=16, want=None):
+        """hipdrt_plan_score_candidates for the fitted batch: x (C, B, n) scaled candidate vectors to upload, or None for every
+        recorded step of the step store; ncand (B,) candidates per spectrum (None: all); ln_tau_find: the grid of the peak
+        search (None: likelihood sums only) -> dict of rss, sum_log_w, count, status (C, B), peak_index, heights, prominences
+        (C, B, max_peaks); absent slots hold -1 / NaN.  want: the names to form and download (None: all); status always comes."""
+        B, n = self.B, self.n
+        i = CandidatesIn()
+        keepers = []
+        if x is None:
+            Cn = self.pfrt_steps()
+            i.source, i.C = CANDIDATES_FROM_STEPS, 0
+        else:
+            xa = _f64(x); keepers.append(xa)
+            if xa.ndim != 3 or xa.shape[1:] != (B, n):
+                raise ValueError("x must have shape (C, B, n)")
+            Cn = xa.shape[0]
+            i.source, i.C, i.x = CANDIDATES_FROM_HOST, Cn, _p(xa)
+        if ncand is not None:
+            nc = _i32(ncand); keepers.append(nc)
+            if nc.shape != (B,):
+                raise ValueError("ncand must have shape (B,)")
+            i.ncand = _pi(nc)
+        lt = None if ln_tau_find is None else _f64(ln_tau_find).ravel()
+        po = opts if opts is not None else peak_opts()
+        keepers += [lt, po]
+        i.ln_tau_find, i.nfind, i.peak_opts, i.max_peaks = _p(lt), 0 if lt is None else lt.size, C.pointer(po), int(max_peaks)
+        mp = int(max_peaks) or 16
+        shapes = dict(rss=(Cn, B), sum_log_w=(Cn, B), count=(Cn, B), peak_index=(Cn, B, mp), heights=(Cn, B, mp),
+                      prominences=(Cn, B, mp), status=(Cn, B))
+        out = {}
+        for k, shape in shapes.items():
+            if (want is not None and k not in want and k != "status") or (lt is None and k in CANDIDATE_OUTPUTS[2:6]):
+                continue
+            out[k] = np.full(shape, -77, dtype=np.int32) if k in ("count", "peak_index", "status") else np.full(shape, 7e77)
+        u = CandidatesOut()
+        for k in CANDIDATE_OUTPUTS:
+            a = out.get(k)
+            setattr(u, k, None if a is None else (_pi(a) if a.dtype == np.int32 else _p(a)))
+        _check(self._lib.hipdrt_plan_score_candidates(self._h, C.byref(i), C.byref(u)))
+        return out
+
     def integrate_drt(self, ln_tau_eval, windows, order=0, sign=1, normalize=0, row_scale=None):
         """hipdrt_plan_integrate_drt: the trapezoid of predict_drt's row over every window (start, end) -> ((B, nwin), status)"""
         ev = _f64(ln_tau_eval).ravel()
@@ -1407,6 +1485,10 @@ class Plan:
     def pfrt_record(self):
         """append the state the last fit / warm restart left to the PFRT step store (hipdrt_plan_pfrt_record)"""
         _check(self._lib.hipdrt_plan_pfrt_record(self._h))
+
+    def pfrt_restore_s(self, step, factor=1.0):
+        """the live s vectors become factor times those step `step` recorded, on the device (hipdrt_plan_pfrt_restore_s)"""
+        _check(self._lib.hipdrt_plan_pfrt_restore_s(self._h, int(step), float(factor)))
 
     def pfrt_steps(self):
         n = C.c_int()
@@ -1703,7 +1785,7 @@ class PreparedPlan(Plan):
         shapes = {"m0": (self.n, self.n), "m1": (self.n, self.n), "m2": (self.n, self.n), "vmm": (self.m, self.m),
                   "h": (self.n,), "est_weights": (B, self.m), "rv": (B, self.m), "xmx": (B, 3), "dop_rho": (B, 3),
                   "dop_xmx": (B, 3), "hist_dop_rho": (int(self.opts.max_iter), 3), "outlier_t": (B, self.m),
-                  "weight_factors": (B, 2), "x": (B, self.n),
+                  "weight_factors": (B, 2), "x": (B, self.n), "var_floor": (B,),
                   "rzm": (B, self.m, self.n) if self.rm_batched else (self.m, self.n)}
         out = np.empty(shapes[which])
         _check(self._lib.hipdrt_plan_get(self._h, which.encode(), _p(out), out.size))

@@ -98,6 +98,9 @@ struct hipdrt_ctx {
     // hipdrt_debug_qp_waves (tests, tools): wavefronts per workgroup of this context's batch coneqp launches at n <= 528 --
     // 4 = the fat form, 8 = eight wavefronts, -1 = the library chooses.  Initialised from HIPDRT_QP_WAVES when the context is made.
     int qp_waves = -1;
+    // hipdrt_debug_candidate_form (tests): how this context's candidate scoring keeps yh = X rm' between its two products --
+    // 0 = in LDS, 1 = through the scratch buffer, -1 = the library chooses (LDS where 16 rows of m fit)
+    int cand_form = -1;
     // hipdrt_debug_last_predict_ms (tools): kernel time of the last prediction, ms -- [0] up to the mean / the impedance, [1] band included
     float predict_ms[2] = {0.f, 0.f};
 };
@@ -430,6 +433,39 @@ int pfrt_check(const hipdrt_pfrt_opts& o, int S, int np, int nout);
 int launch_pfrt_combine(hipStream_t s, const PfrtCombineArgs& a, int B);
 // c, alpha_n and beta_0 of PfrtCombineArgs for m data rows (evaluate_llh's defaults alpha_0 = 2, beta_0 = 1)
 void pfrt_llh_consts(int m, double* c, double* alpha_n, double* beta_0);
+
+// candidates.hip: the likelihood sums of C candidate solutions per spectrum, 16 candidates of a spectrum per workgroup on the
+// matrix pipe, and the compaction of peaks_kernel's dense rows (all pointers device memory)
+struct CandLlhArgs {
+    int C, B, m, n;
+    const double* x;                     // candidate (c, b): x + c * x_cstride + b * x_bstride, n doubles
+    long long x_cstride, x_bstride;
+    const double* rm; int ldrm; long long rm_stride;   // [m][ldrm]; doubles between consecutive spectra (0 = shared)
+    const double* rv;                    // [B][m]
+    const double* vmm;                   // [m][m]
+    const double* var_floor;             // [B]
+    const int* ncand;                    // [B] or null (C): slots at or past it get NaN
+    const int* fit_status;               // [B] or null: a negative status gives NaN in every slot
+    const int* slot_status;              // [C][B] or null: a negative entry gives NaN in that slot (a recorded step that failed)
+    double *rss, *slw;                   // [C][B]
+    double* scratch;                     // form 1: cand_llh_scratch_doubles(C, B, m) doubles
+};
+bool cand_llh_fits_lds(int m);           // 16 rows of rm x fit in LDS beside the staging slabs (form 0)
+size_t cand_llh_scratch_doubles(int C, int B, int m);
+// form 0: yh = X rm' stays in LDS; 1: it goes through a.scratch between two launches.  Same bits either way.
+int launch_cand_llh(hipStream_t st, const CandLlhArgs& a, int form);
+inline int cand_llh_form(const hipdrt_ctx* ctx, int m) { return ctx->cand_form >= 0 ? ctx->cand_form : (cand_llh_fits_lds(m) ? 0 : 1); }
+struct CandPeakArgs {
+    int B, neval, max_peaks;
+    const int* keep;                                     // [B][neval] of peaks_kernel
+    const double *dense_heights, *dense_prominences;     // [B][neval] of peaks_kernel (read only where the list is asked for)
+    const int* slot_status;                              // [B]: negative = no candidate in this slot
+    int* count;                                          // [B]; any output may be null
+    int* peak_index;                                     // [B][max_peaks], -1 padded
+    double *heights, *prominences;                       // [B][max_peaks], NaN padded
+    int* status;                                         // [B]
+};
+void launch_cand_compact(hipStream_t st, const CandPeakArgs& a);
 
 // qp.hip
 struct QpArgs {

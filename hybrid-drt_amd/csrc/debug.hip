@@ -577,6 +577,40 @@ int hipdrt_debug_peak_resolve(hipdrt_ctx* ctx, const hipdrt_debug_peak_resolve_a
     return outs.back(st);
 } HIPDRT_CATCH
 
+// test hooks (include/hipdrt_debug.h): the likelihood kernels of candidates.hip as they are, on host arrays; outputs between borders
+// of marker bytes
+int hipdrt_debug_candidate_llh(hipdrt_ctx* ctx, int C, int B, int m, int n, const double* rm, int rm_batched, const double* rv,
+                               const double* vmm, const double* var_floor, const double* x, double* rss, double* sum_log_w) try {
+    HIPDRT_REQUIRE(ctx && rm && rv && vmm && var_floor && x && rss && sum_log_w, "NULL pointer");
+    HIPDRT_REQUIRE(C >= 1 && C <= 4096 && B >= 1 && B <= 65535 && m >= 1 && m <= 16384 && n >= 1 && n <= 16384,
+                   "1 <= C <= 4096, 1 <= B <= 65535, 1 <= m, n <= 16384");
+    const int form = cand_llh_form(ctx, m);
+    HIPDRT_REQUIRE(form == 1 || cand_llh_fits_lds(m), "candidates: 16 rows of m doubles do not fit in LDS; use the scratch form");
+    hipStream_t st; TRY(enter(ctx, &st));
+    const size_t D = sizeof(double), cb = (size_t)C * B;
+    DevBuf drm, drv, dvmm, dvf, dx, dscr;
+    TRY(upload(drm, rm, (size_t)(rm_batched ? B : 1) * m * n * D, st)); TRY(upload(drv, rv, (size_t)B * m * D, st));
+    TRY(upload(dvmm, vmm, (size_t)m * m * D, st)); TRY(upload(dvf, var_floor, (size_t)B * D, st));
+    TRY(upload(dx, x, cb * n * D, st));
+    if (form == 1) HIPDRT_CHECK(dscr.alloc(cand_llh_scratch_doubles(C, B, m) * D));
+    CandLlhArgs a{};
+    a.C = C; a.B = B; a.m = m; a.n = n; a.x = dx.d(); a.x_cstride = (long long)B * n; a.x_bstride = n;
+    a.rm = drm.d(); a.ldrm = n; a.rm_stride = rm_batched ? (long long)m * n : 0; a.rv = drv.d(); a.vmm = dvmm.d();
+    a.var_floor = dvf.d(); a.scratch = dscr.d();
+    GuardedOuts outs;
+    TRY(outs.want("rss", rss, cb, a.rss, st)); TRY(outs.want("sum_log_w", sum_log_w, cb, a.slw, st));
+    TRY(launch_cand_llh(st, a, form));
+    LAUNCH_OK();
+    return outs.back(st);
+} HIPDRT_CATCH
+
+int hipdrt_debug_candidate_form(hipdrt_ctx* ctx, int form) try {
+    HIPDRT_REQUIRE(ctx, "NULL pointer");
+    HIPDRT_REQUIRE(form >= -1 && form <= 1, "form must be -1 (automatic), 0 (LDS) or 1 (scratch)");
+    ctx->cand_form = form;
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
 // tools hook: kernel time of the last hipdrt_plan_predict_drt or hipdrt_plan_predict_z on this context
 int hipdrt_debug_last_predict_ms(hipdrt_ctx* ctx, float* ms) try {
     HIPDRT_REQUIRE(ctx && ms, "NULL pointer");

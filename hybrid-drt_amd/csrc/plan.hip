@@ -395,6 +395,7 @@ int hipdrt_plan_get(hipdrt_plan* p, const char* which, double* out, long long co
     else if (w == "row_factors" && p->wrow.p && p->wrow_batched) { src = p->wrow.d(); rows = p->B; cols = ld = p->m; }   // [B][m]
     else if (w == "x") { src = p->x.d(); rows = p->B; cols = ld = p->n; }
     else if (w == "coef_scale") { src = p->coef_scale.d(); rows = p->B; cols = ld = 1; }
+    else if (w == "var_floor") { src = p->var_floor.d(); rows = p->B; cols = ld = 1; }
     else if (w == "dop_rho" && p->prepared) { src = p->dop_rho.d(); rows = p->B; cols = ld = 3; }
     else if (w == "dop_xmx" && p->prepared) { src = p->dop_xmx.d(); rows = p->B; cols = ld = 3; }
     else if (w == "rzm") { src = p->rm.d(); rows = (p->rm_stride ? p->B : 1) * p->m; cols = p->n; ld = p->ldrm; }

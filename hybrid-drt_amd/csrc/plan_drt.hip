@@ -118,8 +118,9 @@ static int plan_drt_rows_dev(hipdrt_plan* p, const PostSource& src, const Predic
     }
     R.scale = R.cs;
     if (normalize) {
-        HIPDRT_CHECK(R.dsum.alloc((size_t)B * sizeof(double))); HIPDRT_CHECK(R.dabs.alloc((size_t)B * sizeof(double)));
-        HIPDRT_CHECK(R.dnorm.alloc((size_t)B * sizeof(double))); HIPDRT_CHECK(R.dscale.alloc((size_t)B * sizeof(double)));
+        // (a DrtRows that is used again on the same stream keeps its buffers: the candidates of hipdrt_plan_score_candidates)
+        for (DevBuf* d : {&R.dsum, &R.dabs, &R.dnorm, &R.dscale})
+            if (d->bytes < (size_t)B * sizeof(double)) HIPDRT_CHECK(d->alloc((size_t)B * sizeof(double)));
         launch_drt_sums(st, B, src.x, n, ns, nb, pb.copies, sign, R.dsum.d(), R.dabs.d());
         launch_drt_scalars(st, B, R.dsum.d(), R.dabs.d(), R.cs, 1.7724538509055159 / pb.eps, 1, normalize == 2,
                            src.x, n, -1, nullptr, nullptr, nullptr, R.dnorm.d(), R.dscale.d());
@@ -550,6 +551,137 @@ int hipdrt_plan_predict_pfrt(hipdrt_plan* p, const double* factors, const double
     HIPDRT_CHECK(hipMemcpyAsync(hbad.data(), dbad.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
     HIPDRT_CHECK(hipStreamSynchronize(st));
     if (status) merge_status(B, comb.data(), hbad.data(), status);
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+// ---- candidate models of the fitted batch (csrc/candidates.hip) -------------------------------------------------------------------
+int hipdrt_plan_score_candidates(hipdrt_plan* p, const hipdrt_candidates_in* in, hipdrt_candidates_out* out) try {
+    HIPDRT_REQUIRE(p && in && out, "NULL pointer");
+    HIPDRT_REQUIRE(p->B >= 1 && p->prepped, "no fitted batch in the plan");
+    // every check comes before the first launch
+    const bool steps = in->source == HIPDRT_CANDIDATES_FROM_STEPS;
+    HIPDRT_REQUIRE(steps || in->source == HIPDRT_CANDIDATES_FROM_HOST, "source must be 0 (recorded steps) or 1 (host array)");
+    const int B = p->B, n = p->n, m = p->m, width = n - p->ns;
+    int C = in->C;
+    if (steps) {
+        HIPDRT_REQUIRE(p->pf_steps >= 1, "no recorded steps in the plan (hipdrt_plan_pfrt_begin / _record around the fit's steps)");
+        HIPDRT_REQUIRE(C == 0 || C == p->pf_steps, "C must be 0 or the number of recorded steps");
+        C = p->pf_steps;
+    } else {
+        HIPDRT_REQUIRE(in->x, "source 1 needs x");
+        HIPDRT_REQUIRE(C >= 1 && C <= 4096, "1 <= C <= 4096");
+    }
+    HIPDRT_REQUIRE(B <= 65535, "candidates: at most 65535 spectra per call");
+    if (in->ncand) for (int b = 0; b < B; ++b) HIPDRT_REQUIRE(in->ncand[b] >= 0 && in->ncand[b] <= C, "ncand: 0 <= ncand[b] <= C");
+    const bool want_llh = out->rss || out->sum_log_w;
+    const bool want_peaks = out->count || out->peak_index || out->heights || out->prominences;
+    const int nfind = in->nfind, mp = in->max_peaks == 0 ? 16 : in->max_peaks;
+    hipdrt_peak_opts o;
+    if (in->peak_opts) o = *in->peak_opts; else hipdrt_peak_opts_default(&o);
+    PredictBasis pb{};
+    if (want_peaks) {
+        HIPDRT_REQUIRE(in->ln_tau_find && nfind >= 1, "the peak outputs need the find grid");
+        HIPDRT_REQUIRE(mp >= 1 && mp <= 64, "1 <= max_peaks <= 64");
+        TRY(predict_basis(p, pb));
+        TRY(peak_check_opts(o, nfind));
+        HIPDRT_REQUIRE(o.method == 0, "method must be 0 ('thresh'): 'prob' needs a P matrix per candidate");
+        TRY(drt_check_request(pb, o.eval_sign, o.normalize, nullptr, "eval_sign"));
+        HIPDRT_REQUIRE(peaks_lds_bytes(nfind, 0, o.search == 0, 0) <= 160 * 1024 - 256, "find_peaks: nfind too large for one workgroup's LDS");
+    }
+    const int form = cand_llh_form(p->ctx, m);
+    HIPDRT_REQUIRE(!want_llh || form == 1 || cand_llh_fits_lds(m), "candidates: 16 rows of m doubles do not fit in LDS; use the scratch form");
+    hipStream_t st; TRY(enter(p->ctx, &st));
+
+    // status of every slot: the live fit's status where that is negative; else HIPDRT_CANDIDATE_ABSENT at or past ncand[b]; else
+    // the live status (uploaded candidates) or the status recorded with the step -- a step that failed for a spectrum is no
+    // candidate of it, whatever later steps did
+    std::vector<int> hs(B), slot((size_t)C * B);
+    HIPDRT_CHECK(hipMemcpyAsync(hs.data(), p->fit_status.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (steps)
+        for (int c = 0; c < C; ++c)
+            HIPDRT_CHECK(hipMemcpyAsync(slot.data() + (size_t)c * B, p->pf_status.i() + p->pf_layout().scalar(c), (size_t)B * sizeof(int),
+                                        hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    for (int c = 0; c < C; ++c)
+        for (int b = 0; b < B; ++b) {
+            int& v = slot[(size_t)c * B + b];
+            if (hs[b] < 0) v = hs[b];
+            else if (in->ncand && c >= in->ncand[b]) v = HIPDRT_CANDIDATE_ABSENT;
+            else if (!steps) v = hs[b];
+        }
+
+    DevBuf dx, dnc, dslot, dscr;
+    const double* x = nullptr;
+    long long cstride = 0;
+    if (steps) {
+        x = p->pf_x.d(); cstride = (long long)p->pf_layout().x(1);
+    } else {
+        TRY(upload(dx, in->x, (size_t)C * B * n * sizeof(double), st));
+        x = dx.d(); cstride = (long long)B * n;
+    }
+    if (in->ncand) TRY(upload(dnc, in->ncand, (size_t)B * sizeof(int), st));
+    TRY(upload(dslot, slot.data(), slot.size() * sizeof(int), st));
+    const size_t cb = (size_t)C * B;
+    DevOuts outs;
+    CandLlhArgs la{};
+    TRY(outs.want(out->rss, cb, la.rss, want_llh)); TRY(outs.want(out->sum_log_w, cb, la.slw, want_llh));
+    int *d_count = nullptr, *d_index = nullptr, *d_status = nullptr;
+    double *d_heights = nullptr, *d_prom = nullptr;
+    TRY(outs.want(out->count, cb, d_count)); TRY(outs.want(out->peak_index, cb * mp, d_index));
+    TRY(outs.want(out->heights, cb * mp, d_heights)); TRY(outs.want(out->prominences, cb * mp, d_prom));
+    TRY(outs.want(want_peaks ? out->status : nullptr, cb, d_status));
+    PredictTimer tm(p->ctx, st);
+    if (want_llh) {
+        if (form == 1) HIPDRT_CHECK(dscr.alloc(cand_llh_scratch_doubles(C, B, m) * sizeof(double)));
+        la.C = C; la.B = B; la.m = m; la.n = n; la.x = x; la.x_cstride = cstride; la.x_bstride = n;
+        la.rm = p->rm.d(); la.ldrm = p->ldrm; la.rm_stride = p->rm_stride; la.rv = p->rv.d(); la.vmm = p->vmm.d();
+        la.var_floor = p->var_floor.d(); la.ncand = in->ncand ? dnc.i() : nullptr; la.fit_status = p->fit_status.i();
+        la.slot_status = dslot.i(); la.scratch = dscr.d();
+        TRY(launch_cand_llh(st, la, form));
+        LAUNCH_OK();
+    }
+    if (want_peaks) {
+        const bool need_f = o.search == 0;
+        const int orders[2] = {2, 0}, norders = need_f ? 2 : 1;
+        const size_t bn = (size_t)B * nfind;
+        DevBuf dev, dE, dkeep, dht, dpr;
+        TRY(upload(dev, in->ln_tau_find, (size_t)nfind * sizeof(double), st));
+        HIPDRT_CHECK(dE.alloc((size_t)norders * nfind * width * sizeof(double)));
+        HIPDRT_CHECK(dkeep.alloc(bn * sizeof(int))); HIPDRT_CHECK(dht.alloc(bn * sizeof(double))); HIPDRT_CHECK(dpr.alloc(bn * sizeof(double)));
+        // one set of row buffers for all candidates: the launches of candidate c + 1 follow those of candidate c on the stream
+        DrtRows R;
+        R.dE.alias(dE, 0, dE.bytes);
+        HIPDRT_CHECK(R.dmu.alloc((size_t)norders * bn * sizeof(double)));
+        for (int c = 0; c < C; ++c) {
+            // the rows of candidate c of every spectrum, normalised by the R_p of the candidate's own x; a slot without a
+            // candidate is a dead spectrum to every kernel of the chain
+            const int* sl = dslot.i() + (size_t)c * B;
+            const PostSource src{x + (size_t)c * cstride, nullptr, nullptr, nullptr, nullptr, sl};
+            TRY(plan_drt_rows_dev(p, src, pb, nfind, orders, norders, o.eval_sign, o.normalize, nullptr, false, st, dev, R, tm, c > 0));
+            PeakArgs pa{};
+            peak_args_rows(pa, R, nfind, o, need_f, false, sl);
+            pa.keep = dkeep.i(); pa.heights = dht.d(); pa.prominences = dpr.d();
+            TRY(launch_peaks(st, pa, B));
+            LAUNCH_OK();
+            CandPeakArgs ca{};
+            ca.B = B; ca.neval = nfind; ca.max_peaks = mp; ca.keep = dkeep.i(); ca.dense_heights = dht.d(); ca.dense_prominences = dpr.d();
+            ca.slot_status = sl;
+            ca.count = d_count ? d_count + (size_t)c * B : nullptr; ca.status = d_status ? d_status + (size_t)c * B : nullptr;
+            ca.peak_index = d_index ? d_index + (size_t)c * B * mp : nullptr;
+            ca.heights = d_heights ? d_heights + (size_t)c * B * mp : nullptr;
+            ca.prominences = d_prom ? d_prom + (size_t)c * B * mp : nullptr;
+            launch_cand_compact(st, ca);
+            LAUNCH_OK();
+        }
+        tm.mark();
+        TRY(outs.back(st));
+        HIPDRT_CHECK(hipStreamSynchronize(st));          // (the row buffers are released at the end of this block)
+    } else {
+        tm.mark();
+        TRY(outs.back(st));
+        HIPDRT_CHECK(hipStreamSynchronize(st));
+    }
+    if (out->status && !want_peaks) std::memcpy(out->status, slot.data(), cb * sizeof(int));
     return HIPDRT_OK;
 } HIPDRT_CATCH
 

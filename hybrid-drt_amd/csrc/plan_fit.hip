@@ -2,6 +2,7 @@
 // staged batch, its side-by-side ranges, warm restarts and the single iterate_qphb pass.
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <functional>
 #include <thread>
 
@@ -542,6 +543,18 @@ int hipdrt_plan_pfrt_record(hipdrt_plan* p) try {
     LAUNCH_OK();
     HIPDRT_CHECK(hipStreamSynchronize(st));
     p->pf_steps += 1;
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+int hipdrt_plan_pfrt_restore_s(hipdrt_plan* p, int step, double factor) try {
+    HIPDRT_REQUIRE(p, "plan is NULL");
+    HIPDRT_REQUIRE(p->B >= 1 && p->prepped, "no fitted batch in the plan");
+    HIPDRT_REQUIRE(step >= 0 && step < p->pf_steps, "step out of range of the recorded PFRT steps");
+    HIPDRT_REQUIRE(factor > 0.0 && std::isfinite(factor), "factor must be positive and finite");
+    hipStream_t st; TRY(enter(p->ctx, &st));
+    launch_scale_rows(st, p->B, 3 * p->n, p->pf_s.d() + p->pf_layout().s(step), nullptr, 0, factor, nullptr, p->s.d());
+    LAUNCH_OK();
+    HIPDRT_CHECK(hipStreamSynchronize(st));
     return HIPDRT_OK;
 } HIPDRT_CATCH
 

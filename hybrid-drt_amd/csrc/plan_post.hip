@@ -95,8 +95,10 @@ static int plan_llh_terms(hipdrt_plan* p, double* rss, double* sum_log_w, int st
     const size_t bb = (size_t)p->B * sizeof(double);
     DevBuf d1, d2;
     HIPDRT_CHECK(d1.alloc(bb)); HIPDRT_CHECK(d2.alloc(bb));
+    PredictTimer tm(p->ctx, st);                    // (hipdrt_debug_last_predict_ms: the launch alone)
     TRY(launch_llh(st, p->state(), p->B, d1.d(), d2.d(), stored, scalar_w));
     LAUNCH_OK();
+    tm.mark();
     HIPDRT_CHECK(hipMemcpyAsync(rss, d1.p, bb, hipMemcpyDeviceToHost, st));
     HIPDRT_CHECK(hipMemcpyAsync(sum_log_w, d2.p, bb, hipMemcpyDeviceToHost, st));
     HIPDRT_CHECK(hipStreamSynchronize(st));

@@ -229,7 +229,8 @@ int hipdrt_plan_destroy(hipdrt_plan* plan);
 int hipdrt_plan_dims(hipdrt_plan* plan, int* n, int* m, int* ns);
 /* copy a shared matrix of the plan back to the host: which = "lut_z_re","lut_z_im" [ngrid],
  * "a_re","a_im" [nf][ntau], "rm" [m][n], "m0","m1","m2" [n][n] (padded), "vmm" [m][m]; of the staged batch:
- * "rv" [B][m] scaled data, "x" [B][n] current solution, "coef_scale" [B], "row_factors" [B][m] (batched row factors only) */
+ * "rv" [B][m] scaled data, "x" [B][n] current solution, "coef_scale" [B], "var_floor" [B] (the variance floor of the weight
+ * re-estimate), "row_factors" [B][m] (batched row factors only) */
 int hipdrt_plan_get(hipdrt_plan* plan, const char* which, double* out, long long count);
 /* replace the plan's lookup tables with externally supplied ones (multi-GPU: rank 0 builds them, RCCL
  * broadcasts, the other ranks install them) and rebuild the dependent matrices            */
@@ -687,6 +688,10 @@ int hipdrt_plan_pfrt_bytes_per_spectrum(int n, int steps, long long* bytes);
 int hipdrt_plan_pfrt_begin(hipdrt_plan* plan, int max_steps);
 int hipdrt_plan_pfrt_record(hipdrt_plan* plan);
 int hipdrt_plan_pfrt_steps(hipdrt_plan* plan, int* steps);
+/* the live s vectors of every staged spectrum become factor times the s vectors step `step` recorded (on the device): the start
+ * of DRT._generate_candidates_s0's restarts, "the baseline s vectors scaled by multiplier^i" (drt1d.py:1534-1537), when the
+ * baseline is a recorded step and nothing is to cross to the host                                                               */
+int hipdrt_plan_pfrt_restore_s(hipdrt_plan* plan, int step, double factor);
 /* what step `step` recorded, for the staged spectra: x [B][n], rho [B][3], s [B][3][n], rss [B], sum_log_w [B], status [B]; any
  * may be NULL                                                                                                                  */
 int hipdrt_plan_pfrt_get_step(hipdrt_plan* plan, int step, double* x, double* rho, double* s, double* rss, double* sum_log_w,
@@ -733,6 +738,47 @@ void hipdrt_pfrt_opts_default(hipdrt_pfrt_opts* o);
 int hipdrt_plan_predict_pfrt(hipdrt_plan* plan, const double* factors, const double* ln_tau_pfrt, int neval_pfrt,
                              const double* ln_tau_out, int neval_out, const hipdrt_pfrt_opts* opts, double* pfrt, double* raw_pfrt,
                              double* step_pfrt, double* post_prob, int* status);
+
+/* ---- candidate models of the fitted batch, scored on the device -----------------------------------------------------------------
+ * What DRT.generate_candidates (hybdrt/models/drt1d.py:1632-1821) computes per candidate before it ranks them (1690-1729): the
+ * log-likelihood under weights re-estimated from the candidate alone (evaluate_llh(weights=None, x=x), 4457-4496 over
+ * qphb.py:1347-1377) and the peaks of find_peaks(x=x) (3753-3947 over predict_drt(x=x, normalize=True), 3020-3061) -- for C
+ * candidates of every spectrum in one call.  The ranking itself (BIC, best per number of peaks, filling, Bayes factors) is host
+ * arithmetic on these outputs: hipdrt/models/candidates.py.                                                                      */
+#define HIPDRT_CANDIDATES_FROM_STEPS 0   /* every recorded step of the plan's step store (hipdrt_plan_pfrt_begin / _record)      */
+#define HIPDRT_CANDIDATES_FROM_HOST 1    /* x [C][B][n] in scaled units, uploaded by the call                                    */
+#define HIPDRT_CANDIDATE_ABSENT (-6)     /* status of a slot at or past the spectrum's ncand                                     */
+typedef struct {
+    int source;                       /* HIPDRT_CANDIDATES_FROM_*                                                                */
+    int C;                            /* FROM_HOST: candidates per spectrum; FROM_STEPS: 0, or the recorded step count            */
+    const double* x;                  /* FROM_HOST: [C][B][n], the unknown vectors as the fit holds them (scaled units)           */
+    const int* ncand;                 /* [B] candidates of each spectrum, 0 .. C; NULL: all C                                     */
+    const double* ln_tau_find;        /* [nfind] the grid peaks are found on; NULL with nfind = 0: no peak search                 */
+    int nfind;
+    const hipdrt_peak_opts* peak_opts;/* NULL: defaults; method must be 0 ('thresh': 'prob' needs a P matrix per candidate)       */
+    int max_peaks;                    /* 0 = 16; 1 .. 64 peak slots per candidate                                                 */
+} hipdrt_candidates_in;
+typedef struct {                      /* host arrays, any may be NULL; [C][B] leading                                            */
+    double *rss, *sum_log_w;          /* [C][B] the sums of hipdrt_plan_llh_terms for the candidate's x                           */
+    int* count;                       /* [C][B] peaks of the candidate (the true number even beyond max_peaks)                    */
+    int* peak_index;                  /* [C][B][max_peaks] positions on the find grid, ascending, -1 padded                       */
+    double *heights, *prominences;    /* [C][B][max_peaks] of those peaks, NaN padded                                            */
+    int* status;                      /* [C][B] the fit's (FROM_STEPS: the step's) status, HIPDRT_CANDIDATE_ABSENT, HIPDRT_PEAKS_OVERFLOW */
+} hipdrt_candidates_out;
+/* Likelihood sums (csrc/candidates.hip): r = rm_b x - rv_b, s = vmm r^2 floored at the spectrum's variance floor, w = max(s^-1/2,
+ * 1e-10), rss = |w r|^2 expanded as hipdrt_plan_llh_terms expands it, sum_log_w = sum log w.  A spectrum's candidates are taken 16
+ * at a time on the FP64 matrix pipe, so rm and vmm are read once per 16 candidates rather than once per candidate; where 16 rows of
+ * m do not fit in LDS (m > 896) rm x passes through a scratch buffer of C B m doubles, with the same bits.  Peaks: per candidate
+ * the curvature row (and f where the options need it) of the candidate's x on the find grid, normalised by the R_p of that x, by
+ * the kernels of hipdrt_plan_find_peaks; then that entry's peak rule (method 0) and a compaction of its dense rows.
+ * A failed fit gives NaN / -1 in every slot of the spectrum and its negative status; so does a slot at or past ncand[b], with
+ * HIPDRT_CANDIDATE_ABSENT, and (FROM_STEPS) a step whose recorded status is negative for the spectrum, with that status, whatever
+ * later steps did.  The status of a valid slot is the live fit's (FROM_HOST) or the one recorded with the step (FROM_STEPS).  More than max_peaks peaks: the true count, HIPDRT_PEAKS_OVERFLOW and empty rows.  HIPDRT_E_INVALID
+ * before any launch: no fitted batch, no recorded steps (FROM_STEPS), C out of range, ncand out of range, options out of range,
+ * method other than 0, a find grid whose rows do not fit one workgroup's LDS.  The call reads the plan's matrices, data and
+ * statuses and writes nothing the fit or a later call reads.  Plain and prepared plans (hipdrt_plan_set_tau_basis first for
+ * peaks).  The result of a candidate depends neither on C or B nor on its position among the candidates or in the batch.         */
+int hipdrt_plan_score_candidates(hipdrt_plan* plan, const hipdrt_candidates_in* in, hipdrt_candidates_out* out);
 
 /* kernel-time breakdown of the last hipdrt_plan_fit in ms (HIP events on the ctx stream):
  * t[0]=total, t[1]=gram, t[2]=qp, t[3]=hyper, t[4]=setup/other; launches[5] same order                 */

@@ -210,7 +210,18 @@ typedef struct {
 } hipdrt_debug_response_args;
 int hipdrt_debug_response(hipdrt_ctx* ctx, const hipdrt_debug_response_args* a);
 
-/* tools hook (tools/bench_predict.py, tools/bench_peaks.py, tools/bench_response.py): kernel time in ms of the last
+/* test hooks (tests/test_gpu_candidates.py): the likelihood kernels of csrc/candidates.hip alone, on host arrays, no plan needed.
+ * x [C][B][n]; rm [m][n] (rm_batched = 0) or [B][m][n]; rv [B][m]; vmm [m][m]; var_floor [B]; rss, sum_log_w [C][B] out, each
+ * between two borders of marker bytes (HIPDRT_E_NUMERIC when a kernel changed one).  hipdrt_debug_candidate_form fixes how this
+ * context's candidate scoring -- this hook and hipdrt_plan_score_candidates on its plans -- keeps rm x between its two products:
+ * 0 in LDS (HIPDRT_E_INVALID at the call when 16 rows of m do not fit), 1 through the scratch buffer, -1 the library chooses.    */
+int hipdrt_debug_candidate_llh(hipdrt_ctx* ctx, int C, int B, int m, int n, const double* rm, int rm_batched, const double* rv,
+                               const double* vmm, const double* var_floor, const double* x, double* rss, double* sum_log_w);
+int hipdrt_debug_candidate_form(hipdrt_ctx* ctx, int form);
+
+/* tools hook (tools/bench_predict.py, tools/bench_peaks.py, tools/bench_response.py, tools/bench_candidates.py): kernel time in ms
+ * of the last hipdrt_plan_llh_terms / _obs_llh_terms(_w) (ms[0] = ms[1]: its one launch), hipdrt_plan_score_candidates (ms[1]: all
+ * launches),
  * hipdrt_plan_predict_drt / hipdrt_plan_predict_z / hipdrt_plan_find_peaks (ms[0]: the mean rows, ms[1]: all launches, peaks_kernel
  * included) or hipdrt_plan_predict_response / _z_model / _dop (ms[0] = ms[1]: all launches; _z_model with the upload of its grids and tables) of a plan of this context, by HIP
  * events around its launches (allocations and copies excluded): ms[0] up to the mean (predict_z: the whole prediction), ms[1] with
