@@ -157,6 +157,13 @@ class DebugHyperArgs(C.Structure):
     ]
 
 
+class DebugPosteriorArgs(C.Structure):
+    """hipdrt_debug_posterior_args (include/hipdrt_debug.h)"""
+    _fields_ = [("B", C.c_int), ("n", C.c_int), ("P", _dp), ("p_batched", C.c_int), ("ldp", C.c_int), ("rows", _dp),
+                ("neval", C.c_int), ("ncol", C.c_int), ("col_offset", C.c_int), ("scale", _dp), ("cov_member", C.c_int),
+                ("var", _dp), ("status", _ip), ("cov", _dp), ("bex", _dp), ("tail", _dp)]
+
+
 class PredictDesc(C.Structure):
     """hipdrt_predict_desc (include/hipdrt.h)"""
     _fields_ = [("idx_rinf", C.c_int), ("idx_induc", C.c_int), ("idx_cinv", C.c_int), ("inductance_scale", C.c_double),
@@ -259,6 +266,7 @@ SIGNATURES = {
     "hipdrt_plan_score_candidates": [_vp, C.POINTER(CandidatesIn), C.POINTER(CandidatesOut)],
     "hipdrt_debug_candidate_llh": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp],
     "hipdrt_debug_candidate_form": [_vp, C.c_int],
+    "hipdrt_debug_posterior": [_vp, C.POINTER(DebugPosteriorArgs)],
     "hipdrt_plan_pfrt_bytes_per_spectrum": [C.c_int, C.c_int, C.POINTER(C.c_longlong)],
     "hipdrt_plan_pfrt_begin": [_vp, C.c_int],
     "hipdrt_plan_pfrt_record": [_vp],
@@ -1139,6 +1147,34 @@ class Context:
         _check(self._lib.hipdrt_debug_candidate_llh(self._h, Cn, B, m, n, _p(rm), int(rm.ndim == 3), _p(rv), _p(vmm), _p(vf), _p(x),
                                                     _p(rss), _p(slw)))
         return rss, slw
+
+    def debug_posterior(self, P, rows, col_offset=0, B=None, scale=None, cov_member=-1, n=None, want=("var", "status")):
+        """tests: the posterior variance and covariance chain on host arrays (hipdrt_debug_posterior, include/hipdrt_debug.h):
+        P (n, ldp) shared by B spectra or (B, n, ldp), rows (neval, ncol) at unknowns col_offset.., scale (B,) or None ->
+        dict of the outputs named in `want`: var (nb, neval), status (nb,), cov (neval, neval), bex (nex, nchp, 256),
+        tail (nb, nex, nchp, 256); nb = B, or 1 with cov_member >= 0.  Raises when a kernel wrote outside an output or outside a
+        spectrum's factor scratch."""
+        P, rows = _f64(P), np.atleast_2d(_f64(rows))
+        batched = P.ndim == 3
+        B = (P.shape[0] if batched else 1) if B is None else int(B)
+        n = P.shape[-2] if n is None else int(n)
+        if P.ndim not in (2, 3) or P.shape[-2] != n or (batched and P.shape[0] != B):
+            raise ValueError("P: (n, ldp) or (B, n, ldp)")
+        neval, ncol = rows.shape
+        sc = None if scale is None else _f64(scale).ravel()
+        if sc is not None and sc.size != B:
+            raise ValueError("scale: (B,)")
+        nb = 1 if cov_member >= 0 else max(B, 0)
+        nex, nchp = max((neval + 15) // 16, 0), (max(n, 0) + 31) // 32 * 2
+        shapes = dict(var=(nb, neval), status=(nb,), cov=(neval, neval), bex=(nex, nchp, 256), tail=(nb, nex, nchp, 256))
+        out = {k: (np.full(shapes[k], -7, dtype=np.int32) if k == "status" else np.full(shapes[k], 7e77)) for k in want}
+        a = DebugPosteriorArgs()
+        a.B, a.n, a.P, a.p_batched, a.ldp = B, n, _p(P), int(batched), P.shape[-1]
+        a.rows, a.neval, a.ncol, a.col_offset, a.scale, a.cov_member = _p(rows), neval, ncol, int(col_offset), _p(sc), int(cov_member)
+        for k in want:
+            setattr(a, k, _pi(out[k]) if k == "status" else _p(out[k]))
+        _check(self._lib.hipdrt_debug_posterior(self._h, C.byref(a)))
+        return out
 
     def debug_candidate_form(self, form):
         """tests: how candidate scoring on this context keeps rm x between its two products: 0 LDS, 1 scratch, -1 automatic"""

@@ -611,6 +611,78 @@ int hipdrt_debug_candidate_form(hipdrt_ctx* ctx, int form) try {
     return HIPDRT_OK;
 } HIPDRT_CATCH
 
+// test hook (include/hipdrt_debug.h): the posterior chain of plan_post.hip -- posterior_var_dev and posterior_cov_dev, the functions
+// the plan entry points call -- on a P and rows of the caller's.  Every device output sits between borders of marker bytes, and so
+// does every spectrum's factor scratch.
+int hipdrt_debug_posterior(hipdrt_ctx* ctx, const hipdrt_debug_posterior_args* a) try {
+    HIPDRT_REQUIRE(ctx && a && a->P && a->rows, "NULL pointer");
+    const int B = a->B, n = a->n, neval = a->neval, ncol = a->ncol, off = a->col_offset, ldp = a->ldp, cm = a->cov_member;
+    HIPDRT_REQUIRE(n >= 1 && n <= 4096 && B >= 1 && B <= 4096, "1 <= n <= 4096, 1 <= B <= 4096");
+    HIPDRT_REQUIRE(neval >= 1 && neval <= 65536, "1 <= neval <= 65536");
+    HIPDRT_REQUIRE(ncol >= 1 && off >= 0 && off <= n && ncol <= n - off, "the rows' columns must lie inside [0, n)");
+    HIPDRT_REQUIRE(ldp >= n, "ldp >= n");
+    HIPDRT_REQUIRE(cm >= -1 && cm < B, "cov_member: -1 or a spectrum index");
+    HIPDRT_REQUIRE(!a->cov || cm >= 0, "cov needs cov_member");
+    HIPDRT_REQUIRE(!a->tail || cm >= 0 || B <= 256, "tail: the spectra of one chunk only (B <= 256)");
+    const int pb = a->p_batched ? B : 1;
+    for (int b = 0; b < pb; ++b)
+        for (int i = 0; i < n; ++i)
+            for (int j = 0; j < n; ++j) HIPDRT_REQUIRE(std::isfinite(a->P[((size_t)b * n + i) * ldp + j]), "non-finite P");
+    for (size_t i = 0; i < (size_t)neval * ncol; ++i) HIPDRT_REQUIRE(std::isfinite(a->rows[i]), "non-finite rows");
+    if (a->scale) for (int b = 0; b < B; ++b) HIPDRT_REQUIRE(std::isfinite(a->scale[b]), "non-finite scale");
+    hipStream_t st; TRY(enter(ctx, &st));
+    const size_t D = sizeof(double), ppk = qp_ppk_doubles(n), G = Guarded::G / D;
+    const int nex = (neval + 15) / 16, nchp = qp_nchp(n);
+    const bool single = cm >= 0;
+    const int nb = single ? 1 : B, first = single ? cm : 0;
+    // P -> packed tiles as the stand-alone QP entry point packs it (lower triangle); tiles the kernel does not write stay zero
+    DevBuf dP, dPpk, drows, scratch;
+    TRY(upload(dP, a->P, (size_t)pb * n * ldp * D, st));
+    HIPDRT_CHECK(dPpk.alloc((size_t)pb * ppk * D));
+    HIPDRT_CHECK(hipMemsetAsync(dPpk.p, 0, dPpk.bytes, st));
+    launch_pack_p(st, pb, n, dP.d(), ldp, (long long)n * ldp, dPpk.d(), (long long)ppk, nchp);
+    LAUNCH_OK();
+    TRY(upload(drows, a->rows, (size_t)neval * ncol * D, st));
+    std::vector<double> hvar((size_t)nb * nex * 16, 0.0), hbex((size_t)nex * nchp * 256, 0.0), hcov;
+    std::vector<int> hstat(nb, 0);
+    PosteriorChain c{};
+    c.nb = nb; c.n = n; c.ppk = dPpk.d() + (a->p_batched ? (size_t)first * ppk : 0); c.pstr = (a->p_batched && !single) ? (long long)ppk : 0;
+    c.single = single; c.rows = drows.d(); c.neval = neval; c.ncol = ncol; c.col_offset = off; c.guard = G;
+    GuardedOuts outs;
+    double* dcov = nullptr;
+    TRY(outs.want("var", hvar.data(), hvar.size(), c.var, st));
+    TRY(outs.want("status", hstat.data(), hstat.size(), c.status, st));
+    TRY(outs.want("bex", hbex.data(), hbex.size(), c.bex, st));
+    if (a->cov) { hcov.assign((size_t)neval * neval, 0.0); TRY(outs.want("cov", hcov.data(), hcov.size(), dcov, st)); }
+    TRY(posterior_var_dev(st, c, scratch));
+    int bad = 0;
+    if (a->cov) {
+        HIPDRT_CHECK(hipMemcpyAsync(&bad, c.status, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPDRT_CHECK(hipStreamSynchronize(st));
+        if (!bad) { posterior_cov_dev(st, scratch.d() + G, n, neval, a->scale ? a->scale[cm] : 1.0, dcov); LAUNCH_OK(); }
+    }
+    // the factor scratch: its borders, then the rows left behind every factor
+    const size_t lsz = dist_var_scratch_doubles(n, nex), nch = (size_t)nchp, tl = (size_t)nex * nch * 256;
+    const int chunk = nb < 256 ? nb : 256;
+    std::vector<double> hs(scratch.bytes / D);
+    HIPDRT_CHECK(hipMemcpyAsync(hs.data(), scratch.p, scratch.bytes, hipMemcpyDeviceToHost, st));
+    TRY(outs.back(st));
+    const unsigned char* raw = reinterpret_cast<const unsigned char*>(hs.data());
+    for (int k = 0; k <= chunk; ++k)
+        for (size_t i = 0; i < Guarded::G; ++i)
+            if (raw[(size_t)k * (lsz + G) * D + i] != Guarded::MARK) {
+                set_error("the kernel under test wrote outside a spectrum's factor scratch");
+                return HIPDRT_E_NUMERIC;
+            }
+    if (a->var) posterior_var_host(hvar.data(), nb, neval, a->scale ? a->scale + first : nullptr, a->var);
+    if (a->status) std::memcpy(a->status, hstat.data(), (size_t)nb * sizeof(int));
+    if (a->bex) std::memcpy(a->bex, hbex.data(), hbex.size() * D);
+    if (a->cov) for (size_t i = 0; i < hcov.size(); ++i) a->cov[i] = bad ? __builtin_nan("") : hcov[i];
+    if (a->tail)
+        for (int k = 0; k < nb; ++k) std::memcpy(a->tail + (size_t)k * tl, hs.data() + G + (size_t)k * (lsz + G) + nch * nch * 256, tl * D);
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
 // tools hook: kernel time of the last hipdrt_plan_predict_drt or hipdrt_plan_predict_z on this context
 int hipdrt_debug_last_predict_ms(hipdrt_ctx* ctx, float* ms) try {
     HIPDRT_REQUIRE(ctx && ms, "NULL pointer");

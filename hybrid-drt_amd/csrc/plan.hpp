@@ -242,6 +242,31 @@ FinalP plan_final_p(const hipdrt_plan* p, int b, const PostSource& src);
 // the batch (nb = B).  The caller owns the scratch: Y = rows L^-T of the last factorisation stays in it.
 int plan_quadratic_forms_dev(hipdrt_plan* p, const PostSource& src, int b, const double* rows_dev, int neval, int ncol,
                              int col_offset, DevBuf& scratch, DevBuf& dout, DevBuf& dstat);
+// The device chain behind that, from packed P and device rows on -- what plan_quadratic_forms_dev runs once it has built P, and
+// what hipdrt_debug_posterior runs on a P of the caller's: rows -> packed tiles (bex), then cov_kernel_resident over the spectra in
+// chunks of at most 256 (one factor scratch per spectrum of a chunk).  `single`: the single-spectrum form (nb = 1, every stride 0).
+// Spectrum k of a chunk has its scratch at scratch + guard + k * (dist_var_scratch_doubles + guard) doubles; with guard > 0 (the
+// hook) the whole buffer is filled with the bytes 0xA5 first, so that what lies between the spectra's scratch shows a stray write.
+struct PosteriorChain {
+    int nb, n;
+    const double* ppk; long long pstr;          // packed final P; pstr 0: one P for every spectrum
+    bool single;
+    const double* rows; int neval, ncol, col_offset;
+    double* bex;                                // [nex][nchp][256]
+    double* var; int* status;                   // [nb][16 nex], [nb]
+    size_t guard = 0;
+    int nex() const { return (neval + 15) / 16; }
+};
+int posterior_var_dev(hipStream_t st, const PosteriorChain& c, DevBuf& scratch);
+// scale * Y Y' of the rows Y = rows L^-T that the chain left behind ONE spectrum's factor (scratch_b: that spectrum's scratch)
+// -> dcov[neval][neval] on the device
+void posterior_cov_dev(hipStream_t st, const double* scratch_b, int n, int neval, double scale, double* dcov);
+// host side of the variances: out[nb][neval] from the device's [nb][16 nex], times scale[b] (scale NULL: 1)
+inline void posterior_var_host(const double* var, int nb, int neval, const double* scale, double* out) {
+    const int nex = (neval + 15) / 16;
+    for (int b = 0; b < nb; ++b)
+        for (int i = 0; i < neval; ++i) out[(size_t)b * neval + i] = var[((size_t)b * nex) * 16 + i] * (scale ? scale[b] : 1.0);
+}
 // kernel time of the last prediction on a context (hipdrt_debug_last_predict_ms): HIP events around the launches
 struct PredictTimer {
     hipdrt_ctx* ctx; hipStream_t st; hipEvent_t e[3] = {nullptr, nullptr, nullptr}; int n = 0;

@@ -47,29 +47,43 @@ int plan_quadratic_forms_dev(hipdrt_plan* p, const PostSource& src, int b, const
     const bool one = b >= 0;
     const int n = p->n, m = p->m, nb = one ? 1 : p->B, first = one ? b : 0;
     const int nex = (neval + 15) / 16, nchp = qp_nchp(n);
-    const long long pstr = (long long)qp_ppk_doubles(n), lsz = (long long)dist_var_scratch_doubles(n, nex);
+    const long long pstr = (long long)qp_ppk_doubles(n);
     // final P, packed tiles only: of every spectrum, or of spectrum b into its own slot of Ppk (all strides 0)
     const FinalP f = plan_final_p(p, b, src);
     double* ppk = p->Ppk.d() + (size_t)first * pstr;
     launch_gram_l2(st, nb, m, n, p->rm.d() + (size_t)first * p->rm_stride, p->ldrm, f.w, f.g, nullptr, p->ldp, 0, nullptr, ppk,
                    one ? 0 : pstr, nchp, one ? 0 : p->rm_stride);
     LAUNCH_OK();
-    // evaluation rows -> packed tiles, shifted past the special-parameter slots
     DevBuf bex;
     HIPDRT_CHECK(bex.alloc((size_t)nex * nchp * 256 * sizeof(double)));
-    launch_pack_rows(st, neval, ncol, col_offset, rows_dev, ncol, nex, bex.d(), nchp);
-    LAUNCH_OK();
-    const int chunk = nb < 256 ? nb : 256;
-    HIPDRT_CHECK(scratch.alloc((size_t)chunk * lsz * sizeof(double)));
     HIPDRT_CHECK(dout.alloc((size_t)nb * nex * 16 * sizeof(double)));
     HIPDRT_CHECK(dstat.alloc((size_t)nb * sizeof(int)));
-    for (int b0 = 0; b0 < nb; b0 += chunk) {
-        const int nc = (nb - b0) < chunk ? (nb - b0) : chunk;
-        TRY(launch_dist_var(st, nc, n, ppk + (size_t)b0 * pstr, one ? 0 : pstr, bex.d(), nex, scratch.d(), one ? 0 : lsz,
-                            dout.d() + (size_t)b0 * nex * 16, one ? 0 : (long long)nex * 16, dstat.i() + b0));
-    }
+    TRY(posterior_var_dev(st, {nb, n, ppk, one ? 0 : pstr, one, rows_dev, neval, ncol, col_offset, bex.d(), dout.d(), dstat.i()}, scratch));
     HIPDRT_CHECK(hipStreamSynchronize(st));      // bex is released on return
     return HIPDRT_OK;
+}
+
+int posterior_var_dev(hipStream_t st, const PosteriorChain& c, DevBuf& scratch) {
+    const int n = c.n, nb = c.nb, nex = c.nex(), nchp = qp_nchp(n);
+    const long long lsz = (long long)(dist_var_scratch_doubles(n, nex) + c.guard);
+    // evaluation rows -> packed tiles, shifted past the special-parameter slots
+    launch_pack_rows(st, c.neval, c.ncol, c.col_offset, c.rows, c.ncol, nex, c.bex, nchp);
+    LAUNCH_OK();
+    const int chunk = nb < 256 ? nb : 256;
+    HIPDRT_CHECK(scratch.alloc(((size_t)chunk * lsz + c.guard) * sizeof(double)));
+    if (c.guard) HIPDRT_CHECK(hipMemsetAsync(scratch.p, 0xA5, scratch.bytes, st));
+    for (int b0 = 0; b0 < nb; b0 += chunk) {
+        const int nc = (nb - b0) < chunk ? (nb - b0) : chunk;
+        TRY(launch_dist_var(st, nc, n, c.ppk + (size_t)b0 * c.pstr, c.pstr, c.bex, nex, scratch.d() + c.guard, c.single ? 0 : lsz,
+                            c.var + (size_t)b0 * nex * 16, c.single ? 0 : (long long)nex * 16, c.status + b0));
+    }
+    return HIPDRT_OK;
+}
+
+void posterior_cov_dev(hipStream_t st, const double* scratch_b, int n, int neval, double scale, double* dcov) {
+    // Y = rows L^-T sits in tile rows nch .. nch + nex - 1 of the scratch; only the first ceil(n / 16) tile columns are non-zero
+    const int nex = (neval + 15) / 16, nch = qp_nchp(n);
+    launch_rows_outer(st, scratch_b + (size_t)nch * nch * 256, nch, nch, nex, neval, scale, dcov, neval);
 }
 }  // namespace hipdrt
 
@@ -133,11 +147,9 @@ static int plan_quadratic_forms(hipdrt_plan* p, const double* basis_eval, int ne
     HIPDRT_CHECK(hipMemcpyAsync(hs.data(), dstat.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
     HIPDRT_CHECK(hipStreamSynchronize(st));
     // estimate_param_cov scales the inverse by coefficient_scale^2 (drt1d.py:4133)
-    for (int b = 0; b < B; ++b) {
-        const double c2 = cs[b] * cs[b];
-        for (int i = 0; i < neval; ++i) out[(size_t)b * neval + i] = hv[((size_t)b * nex) * 16 + i] * c2;
-        if (status) status[b] = hs[b];
-    }
+    for (int b = 0; b < B; ++b) cs[b] *= cs[b];
+    posterior_var_host(hv.data(), B, neval, cs.data(), out);
+    if (status) std::memcpy(status, hs.data(), (size_t)B * sizeof(int));
     return HIPDRT_OK;
 }
 
@@ -149,7 +161,6 @@ static int plan_full_cov(hipdrt_plan* p, int b, const double* rows, int neval, i
     HIPDRT_REQUIRE(neval >= 1, "neval >= 1");
     HIPDRT_REQUIRE(p->n <= 4096, "posterior covariance: n <= 4096");
     hipStream_t st; TRY(enter(p->ctx, &st));
-    const int nex = (neval + 15) / 16, nch = round_up(p->n, 32) / 16;
     DevBuf dbe, scratch, dvar, dstat, dcov;
     TRY(upload(dbe, rows, (size_t)neval * ncol * sizeof(double), st));
     TRY(plan_quadratic_forms_dev(p, live_source(p), b, dbe.d(), neval, ncol, col_offset, scratch, dvar, dstat));
@@ -164,8 +175,7 @@ static int plan_full_cov(hipdrt_plan* p, int b, const double* rows, int neval, i
         for (size_t i = 0; i < (size_t)neval * neval; ++i) out[i] = __builtin_nan("");      // reference warns and returns None)
         return HIPDRT_OK;
     }
-    // Y = rows L^-T sits in tile rows nch .. nch + nex - 1 of the scratch; only the first ceil(n / 16) tile columns are non-zero
-    launch_rows_outer(st, scratch.d() + (size_t)nch * nch * 256, nch, nch, nex, neval, cs * cs, dcov.d(), neval);
+    posterior_cov_dev(st, scratch.d(), p->n, neval, cs * cs, dcov.d());
     LAUNCH_OK();
     HIPDRT_CHECK(hipMemcpyAsync(out, dcov.p, (size_t)neval * neval * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPDRT_CHECK(hipStreamSynchronize(st));

@@ -5,7 +5,9 @@
  * (in-kernel phase counters of a PROFILE build, occupancy queries).  Every hook takes a context: there is no process-wide
  * switch.  The kernels of the fit loop each have a hook that runs their launcher as it is on host arrays: hipdrt_debug_gram_l2
  * (Gram, q), hipdrt_debug_hyper_step (the hyper-parameter step in its three product forms), hipdrt_debug_kk_stats,
- * hipdrt_debug_apply_rows, hipdrt_debug_find_peaks, hipdrt_debug_peak_resolve, hipdrt_debug_response.
+ * hipdrt_debug_apply_rows, hipdrt_debug_find_peaks, hipdrt_debug_peak_resolve, hipdrt_debug_response; so have the kernels that read
+ * a finished fit: hipdrt_debug_pfrt_step / _combine, hipdrt_debug_candidate_llh, and hipdrt_debug_posterior (the posterior variance and
+ * covariance chain: packed rows, the 32-column factorisation with appended tile rows, the outer product).
  */
 #ifndef HIPDRT_DEBUG_H
 #define HIPDRT_DEBUG_H
@@ -218,6 +220,32 @@ int hipdrt_debug_response(hipdrt_ctx* ctx, const hipdrt_debug_response_args* a);
 int hipdrt_debug_candidate_llh(hipdrt_ctx* ctx, int C, int B, int m, int n, const double* rm, int rm_batched, const double* rv,
                                const double* vmm, const double* var_floor, const double* x, double* rss, double* sum_log_w);
 int hipdrt_debug_candidate_form(hipdrt_ctx* ctx, int form);
+
+/* test hook (tests/test_gpu_posterior.py): the posterior variance and covariance chain behind the plan entry points
+ * (hipdrt_plan_distribution_var / _cov, _param_var / _cov, the credible bands; csrc/plan_post.hip) from the packed final P on, with a P
+ * of the caller's: pack_rows_kernel, cov_kernel_resident over the spectra in chunks of 256, rows_outer_kernel.  The entry points and the
+ * hook call the same two functions (posterior_var_dev, posterior_cov_dev).  Host arrays, row-major:
+ *   P [p_batched ? B : 1][n][ldp], symmetric positive definite; only the lower triangle is read (launch_pack_p packs it);
+ *   rows [neval][ncol]: row i sits at unknowns col_offset .. col_offset + ncol - 1 and is zero elsewhere; scale [B] or NULL (1);
+ *   cov_member -1: the batched form over all B spectra.  cov_member = b: spectrum b alone in the single-spectrum form (every stride
+ *   0, as the covariance entry points run it); var, status and tail then hold that one spectrum.
+ * out, any may be NULL, nb = B or 1:  var [nb][neval] = scale_b * rows_i' P_b^-1 rows_i (NaN where status is -1);  status [nb] 0, or -1:
+ * P_b is not positive definite;  cov [neval][neval] = scale_b * rows P_b^-1 rows' (cov_member >= 0; all NaN when status is -1, and the
+ * call still returns HIPDRT_OK);  bex [nex][nchp][256] the packed rows, nex = ceil(neval / 16), nchp = round_up(n, 32) / 16;
+ * tail [nb][nex][nchp][256] the tile rows nchp .. nchp + nex - 1 behind each factor, rows L^-T, which rows_outer_kernel reads
+ * (B <= 256 in the batched form: later chunks reuse the scratch).
+ * Every device output has a border of marker bytes on either side, and so has every spectrum's factor scratch (with the inverse
+ * diagonal blocks behind it for n > 528): HIPDRT_E_NUMERIC when a kernel changed one.  HIPDRT_E_INVALID, and nothing is launched, for
+ * n or B outside 1..4096, neval < 1, col_offset < 0, col_offset + ncol > n, ldp < n, cov_member out of range, or non-finite input.   */
+typedef struct hipdrt_debug_posterior_args {
+    int B, n;
+    const double* P; int p_batched, ldp;
+    const double* rows; int neval, ncol, col_offset;
+    const double* scale;
+    int cov_member;
+    double* var; int* status; double* cov; double* bex; double* tail;
+} hipdrt_debug_posterior_args;
+int hipdrt_debug_posterior(hipdrt_ctx* ctx, const hipdrt_debug_posterior_args* a);
 
 /* tools hook (tools/bench_predict.py, tools/bench_peaks.py, tools/bench_response.py, tools/bench_candidates.py): kernel time in ms
  * of the last hipdrt_plan_llh_terms / _obs_llh_terms(_w) (ms[0] = ms[1]: its one launch), hipdrt_plan_score_candidates (ms[1]: all
