@@ -164,6 +164,14 @@ class DebugPosteriorArgs(C.Structure):
                 ("var", _dp), ("status", _ip), ("cov", _dp), ("bex", _dp), ("tail", _dp)]
 
 
+class DebugQpArgs(C.Structure):
+    """hipdrt_debug_qp_args (include/hipdrt_debug.h)"""
+    _fields_ = [("B", C.c_int), ("n", C.c_int), ("P", _dp), ("p_batched", C.c_int), ("ldp", C.c_int), ("q", _dp), ("h", _dp),
+                ("h_batched", C.c_int), ("opts", C.POINTER(QpOpts)), ("active", _ip), ("order", _ip), ("use_lpt", C.c_int),
+                ("form", _ip), ("x", _dp), ("iters", _ip), ("pcost", _dp), ("status", _ip), ("iters_accum", _ip),
+                ("s", _dp), ("z", _dp), ("order_out", _ip)]
+
+
 class PredictDesc(C.Structure):
     """hipdrt_predict_desc (include/hipdrt.h)"""
     _fields_ = [("idx_rinf", C.c_int), ("idx_induc", C.c_int), ("idx_cinv", C.c_int), ("inductance_scale", C.c_double),
@@ -267,6 +275,8 @@ SIGNATURES = {
     "hipdrt_debug_candidate_llh": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp],
     "hipdrt_debug_candidate_form": [_vp, C.c_int],
     "hipdrt_debug_posterior": [_vp, C.POINTER(DebugPosteriorArgs)],
+    "hipdrt_debug_qp": [_vp, C.POINTER(DebugQpArgs)],
+    "hipdrt_debug_lpt_order": [_vp, C.c_int, _ip, _ip, _ip],
     "hipdrt_plan_pfrt_bytes_per_spectrum": [C.c_int, C.c_int, C.POINTER(C.c_longlong)],
     "hipdrt_plan_pfrt_begin": [_vp, C.c_int],
     "hipdrt_plan_pfrt_record": [_vp],
@@ -1175,6 +1185,49 @@ class Context:
             setattr(a, k, _pi(out[k]) if k == "status" else _p(out[k]))
         _check(self._lib.hipdrt_debug_posterior(self._h, C.byref(a)))
         return out
+
+    def debug_qp(self, P, q, h, opts: QpOpts | None = None, active=None, order=None, use_lpt=False, x=None, iters=None, pcost=None,
+                 status=None, iters_accum=None):
+        """tests: launch_qp in the fit loop's form on host arrays (hipdrt_debug_qp, include/hipdrt_debug.h): P (n, ldp) shared or
+        (B, n, ldp), q (B, n), h (n,) or (B, n).  x, iters, pcost, status, iters_accum are what the in/out arrays hold before the launch
+        (sentinels by default; they are copied, not changed) -> dict with x, iterations, pcost, status, iters_accum, s, z (NaN rows
+        for inactive problems), order (the table the kernel used), form (G, inverse blocks in global memory, wavefronts).  Raises when
+        a kernel wrote outside an array, a problem's state block or factor scratch, or the sync words."""
+        P, q, h = _f64(P), np.atleast_2d(_f64(q)), _f64(h)
+        B, n = q.shape
+        if P.ndim not in (2, 3) or P.shape[-2] != n or (P.ndim == 3 and P.shape[0] != B) or h.shape not in ((n,), (B, n)):
+            raise ValueError("P: (n, ldp) or (B, n, ldp); q: (B, n); h: (n,) or (B, n)")
+
+        def inout(v, shape, dtype, fill):
+            out = np.full(shape, fill, dtype=dtype)
+            if v is not None:
+                out[...] = v
+            return out
+        out = dict(x=inout(x, (B, n), np.float64, 7e77), iterations=inout(iters, B, np.int32, -7), pcost=inout(pcost, B, np.float64, 7e77),
+                   status=inout(status, B, np.int32, -7), iters_accum=inout(iters_accum, B, np.int32, 0),
+                   s=np.full((B, n), np.nan), z=np.full((B, n), np.nan), order=np.full(B, -7, dtype=np.int32),
+                   form=np.full(3, -7, dtype=np.int32))
+        act = None if active is None else _i32(active).ravel()
+        order_in = None if order is None else _i32(order).ravel()
+        if (act is not None and act.size != B) or (order_in is not None and order_in.size != B):
+            raise ValueError("active, order: (B,)")
+        a = DebugQpArgs()
+        a.B, a.n, a.P, a.p_batched, a.ldp, a.q, a.h, a.h_batched = B, n, _p(P), int(P.ndim == 3), P.shape[-1], _p(q), _p(h), int(h.ndim == 2)
+        a.opts = C.pointer(opts) if opts is not None else None
+        a.active, a.order, a.use_lpt, a.form = _pi(act), _pi(order_in), int(bool(use_lpt)), _pi(out["form"])
+        a.x, a.iters, a.pcost, a.status, a.iters_accum = (_p(out["x"]), _pi(out["iterations"]), _p(out["pcost"]), _pi(out["status"]),
+                                                          _pi(out["iters_accum"]))
+        a.s, a.z, a.order_out = _p(out["s"]), _p(out["z"]), _pi(out["order"])
+        _check(self._lib.hipdrt_debug_qp(self._h, C.byref(a)))
+        return out
+
+    def debug_lpt_order(self, iters, active=None):
+        """tests: lpt_order_kernel alone (hipdrt_debug_lpt_order, include/hipdrt_debug.h) -> order (B,), -7 where the kernel wrote nothing"""
+        iters = _i32(iters).ravel()
+        act = None if active is None else _i32(active).ravel()
+        order = np.full(iters.size, -7, dtype=np.int32)
+        _check(self._lib.hipdrt_debug_lpt_order(self._h, iters.size, _pi(iters), _pi(act), _pi(order)))
+        return order
 
     def debug_candidate_form(self, form):
         """tests: how candidate scoring on this context keeps rm x between its two products: 0 LDS, 1 scratch, -1 automatic"""

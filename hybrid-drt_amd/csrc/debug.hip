@@ -55,6 +55,34 @@ struct GuardedOuts {
         return 0;
     }
 };
+// `count` blocks of `blk` doubles, each between two borders of marker bytes: [border][block 0][border][block 1] ... [border].  The
+// kernels take the distance between blocks as a stride, so the borders need nothing from them.
+struct GuardedBlocks {
+    static constexpr size_t GD = Guarded::G / sizeof(double);
+    DevBuf buf;
+    size_t blk = 0, count = 0;
+    int alloc(size_t block_doubles, size_t blocks, hipStream_t st) {
+        blk = block_doubles; count = blocks;
+        HIPDRT_CHECK(buf.alloc((count + 1) * stride() * sizeof(double)));
+        HIPDRT_CHECK(hipMemsetAsync(buf.p, Guarded::MARK, buf.bytes, st));
+        return 0;
+    }
+    size_t stride() const { return blk + GD; }
+    double* first() const { return buf.d() + GD; }
+    // the count + 1 borders alone come back (the blocks may be tens of megabytes)
+    int check(const char* what, hipStream_t st) {
+        std::vector<unsigned char> h((count + 1) * Guarded::G);
+        HIPDRT_CHECK(hipMemcpy2DAsync(h.data(), Guarded::G, buf.p, stride() * sizeof(double), Guarded::G, count + 1,
+                                      hipMemcpyDeviceToHost, st));
+        HIPDRT_CHECK(hipStreamSynchronize(st));
+        for (size_t i = 0; i < h.size(); ++i)
+            if (h[i] != Guarded::MARK) {
+                set_error(std::string("the kernel under test wrote outside ") + what + " (border " + std::to_string(i / Guarded::G) + ")");
+                return HIPDRT_E_NUMERIC;
+            }
+        return 0;
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -680,6 +708,120 @@ int hipdrt_debug_posterior(hipdrt_ctx* ctx, const hipdrt_debug_posterior_args* a
     if (a->cov) for (size_t i = 0; i < hcov.size(); ++i) a->cov[i] = bad ? __builtin_nan("") : hcov[i];
     if (a->tail)
         for (int k = 0; k < nb; ++k) std::memcpy(a->tail + (size_t)k * tl, hs.data() + G + (size_t)k * (lsz + G) + nch * nch * 256, tl * D);
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+// test hook (include/hipdrt_debug.h): lpt_order_kernel alone
+int hipdrt_debug_lpt_order(hipdrt_ctx* ctx, int B, const int* iters, const int* active, int* order) try {
+    HIPDRT_REQUIRE(ctx && iters && order, "NULL pointer");
+    HIPDRT_REQUIRE(B >= 1 && (size_t)B * sizeof(int) <= 48 * 1024, "B >= 1, B * sizeof(int) <= 48 KiB (the fit loop's own condition)");
+    hipStream_t st; TRY(enter(ctx, &st));
+    DevBuf dit, dact;
+    TRY(upload(dit, iters, (size_t)B * sizeof(int), st));
+    if (active) TRY(upload(dact, active, (size_t)B * sizeof(int), st));
+    Guarded g;
+    TRY(g.up("order", order, (size_t)B * sizeof(int), st));
+    launch_lpt_order(st, B, dit.i(), active ? dact.i() : nullptr, reinterpret_cast<int*>(g.dd()));
+    LAUNCH_OK();
+    TRY(g.fetch(st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    return g.check();
+} HIPDRT_CATCH
+
+// test hook (include/hipdrt_debug.h): launch_qp as the fit loop calls it (loop_qp_args, plan_fit.hip), on host arrays.  Every in/out
+// array, every problem's state block and factor scratch and the group kernel's sync words sit between borders of marker bytes.
+int hipdrt_debug_qp(hipdrt_ctx* ctx, const hipdrt_debug_qp_args* a) try {
+    HIPDRT_REQUIRE(ctx && a && a->P && a->q && a->h && a->x && a->status, "NULL pointer");
+    const int B = a->B, n = a->n, ldp = a->ldp;
+    HIPDRT_REQUIRE(n >= 1 && n <= 4096 && B >= 1 && B <= 4096, "1 <= n <= 4096, 1 <= B <= 4096");
+    HIPDRT_REQUIRE(ldp >= n, "ldp >= n");
+    HIPDRT_REQUIRE(!(a->order && a->use_lpt), "order and use_lpt exclude each other");
+    HIPDRT_REQUIRE(!a->use_lpt || a->iters, "use_lpt ranks the uploaded iters");
+    const int G = qp_group_size(B, n, ctx->qp_force_group);
+    HIPDRT_REQUIRE(G >= 0, "n not supported");
+    HIPDRT_REQUIRE(!(ctx->qp_force_group == 0 && n > 2048), "n > 2048 needs the group kernel, and this context forces the batch kernel");
+    const int pb = a->p_batched ? B : 1, hb = a->h_batched ? B : 1;
+    for (int b = 0; b < pb; ++b)
+        for (int i = 0; i < n; ++i)
+            for (int j = 0; j < n; ++j) HIPDRT_REQUIRE(std::isfinite(a->P[((size_t)b * n + i) * ldp + j]), "non-finite P");
+    for (size_t i = 0; i < (size_t)B * n; ++i) HIPDRT_REQUIRE(std::isfinite(a->q[i]), "non-finite q");
+    for (size_t i = 0; i < (size_t)hb * n; ++i) HIPDRT_REQUIRE(std::isfinite(a->h[i]), "non-finite h");
+    if (a->order) {
+        std::vector<char> seen((size_t)B, 0);
+        for (int i = 0; i < B; ++i) {
+            const int o = a->order[i];
+            HIPDRT_REQUIRE(o >= 0 && o < B && !seen[(size_t)o], "order must be a permutation of 0 .. B - 1");
+            seen[(size_t)o] = 1;
+        }
+    }
+    hipStream_t st; TRY(enter(ctx, &st));
+    const size_t D = sizeof(double), ppk = qp_ppk_doubles(n);
+    const int Gm = G > 1 ? G : 1;
+    const bool gu = G == 0 && qp_scratch_doubles(n, 0) > ppk;       // the scratch holds more than the factor's tiles: the inverse blocks
+    if (a->form) { a->form[0] = G; a->form[1] = gu ? 1 : 0; a->form[2] = (G == 0 && !gu && ctx->qp_waves == 4) ? 4 : 8; }
+    // P -> packed tiles (lower triangle); the kernel never sees the row-major copy
+    DevBuf dP, dPpk, dq, dh, dact;
+    TRY(upload(dP, a->P, (size_t)pb * n * ldp * D, st));
+    HIPDRT_CHECK(dPpk.alloc((size_t)pb * ppk * D));
+    HIPDRT_CHECK(hipMemsetAsync(dPpk.p, 0, dPpk.bytes, st));
+    launch_pack_p(st, pb, n, dP.d(), ldp, (long long)n * ldp, dPpk.d(), (long long)ppk, qp_nchp(n));
+    LAUNCH_OK();
+    TRY(upload(dq, a->q, (size_t)B * n * D, st));
+    TRY(upload(dh, a->h, (size_t)hb * n * D, st));
+    if (a->active) TRY(upload(dact, a->active, (size_t)B * sizeof(int), st));
+    QpArgs qa{};
+    qa.B = B; qa.n = n; qa.ldp = ldp; qa.q = dq.d(); qa.h = dh.d(); qa.h_stride = a->h_batched ? n : 0;
+    qa.P = nullptr; qa.p_stride = (long long)n * ldp; qa.active = a->active ? dact.i() : nullptr;
+    qa.Ppk = dPpk.d(); qa.ppk_stride = a->p_batched ? (long long)ppk : 0; qa.nchp = qp_nchp(n);
+    qa.opts = a->opts ? *a->opts : default_qp_opts();
+    qa.G = G; qa.waves = ctx->qp_waves;
+    GuardedOuts g;
+    TRY(g.want("x", a->x, (size_t)B * n, qa.x, st)); TRY(g.want("iters", a->iters, (size_t)B, qa.iters, st));
+    TRY(g.want("pcost", a->pcost, (size_t)B, qa.pcost, st)); TRY(g.want("status", a->status, (size_t)B, qa.status, st));
+    TRY(g.want("iters_accum", a->iters_accum, (size_t)B, qa.iters_accum, st));
+    std::vector<int> horder;
+    int* dorder = nullptr;
+    if (a->order || a->use_lpt) {
+        horder.assign((size_t)B, -1);
+        if (a->order) std::memcpy(horder.data(), a->order, (size_t)B * sizeof(int));
+        TRY(g.want("order", horder.data(), (size_t)B, dorder, st));
+        if (a->use_lpt) { launch_lpt_order(st, B, qa.iters, qa.active, dorder); LAUNCH_OK(); }     // as outer_iteration does
+        qa.order = dorder;
+    }
+    std::vector<int> hsync;
+    if (G >= 1) {
+        hsync.assign((size_t)B * qp_gsync_ints(), 0);
+        TRY(g.want("the sync words", hsync.data(), hsync.size(), qa.gsync, st));
+    }
+    GuardedBlocks L, S;
+    TRY(L.alloc(qp_scratch_doubles(n, G), (size_t)B, st));
+    TRY(S.alloc(qp_state_doubles(n), (size_t)B * Gm, st));
+    qa.L = L.first(); qa.ldl = (int)qp_scratch_ld(n); qa.l_stride = (long long)L.stride();
+    qa.state = S.first(); qa.state_ld = qp_state_ld(n); qa.state_stride = (long long)S.stride();
+    TRY(launch_qp(st, qa));
+    LAUNCH_OK();
+    std::vector<double> hs(S.buf.bytes / D);
+    HIPDRT_CHECK(hipMemcpyAsync(hs.data(), S.buf.p, S.buf.bytes, hipMemcpyDeviceToHost, st));
+    TRY(g.back(st));
+    TRY(L.check("a problem's factor scratch", st));
+    TRY(S.check("a problem's state block", st));
+    if (a->order_out)
+        for (int i = 0; i < B; ++i) a->order_out[i] = qa.order ? horder[(size_t)i] : i;
+    // s and z: state vectors 2 and 1 of the leader's copy, slot b * max(G, 1) -- or slot b when the launcher fell back to one member
+    // per problem (qp.hip: launch_qp); the leader's copy is the one whose vector 0 is the x that came back
+    if (a->s || a->z)
+        for (int b = 0; b < B; ++b) {
+            if (a->active && !a->active[b]) continue;
+            const int sld = qp_state_ld(n);
+            const double* blk = nullptr;
+            for (size_t slot : {(size_t)b * Gm, (size_t)b}) {
+                const double* c = hs.data() + GuardedBlocks::GD + slot * S.stride();
+                if (std::memcmp(c, a->x + (size_t)b * n, (size_t)n * D) == 0) { blk = c; break; }
+            }
+            if (!blk) { set_error("the leader's state block does not hold the x that came back"); return HIPDRT_E_NUMERIC; }
+            if (a->s) std::memcpy(a->s + (size_t)b * n, blk + (size_t)2 * sld, (size_t)n * D);
+            if (a->z) std::memcpy(a->z + (size_t)b * n, blk + (size_t)1 * sld, (size_t)n * D);
+        }
     return HIPDRT_OK;
 } HIPDRT_CATCH
 

@@ -7,7 +7,9 @@
  * (Gram, q), hipdrt_debug_hyper_step (the hyper-parameter step in its three product forms), hipdrt_debug_kk_stats,
  * hipdrt_debug_apply_rows, hipdrt_debug_find_peaks, hipdrt_debug_peak_resolve, hipdrt_debug_response; so have the kernels that read
  * a finished fit: hipdrt_debug_pfrt_step / _combine, hipdrt_debug_candidate_llh, and hipdrt_debug_posterior (the posterior variance and
- * covariance chain: packed rows, the 32-column factorisation with appended tile rows, the outer product).
+ * covariance chain: packed rows, the 32-column factorisation with appended tile rows, the outer product).  The interior-point QP has
+ * hipdrt_debug_qp (launch_qp in the fit loop's form: packed P only, active mask, dispatch order, iters_accum; s and z come back) and
+ * hipdrt_debug_lpt_order (the dispatch-order kernel alone).
  */
 #ifndef HIPDRT_DEBUG_H
 #define HIPDRT_DEBUG_H
@@ -246,6 +248,43 @@ typedef struct hipdrt_debug_posterior_args {
     double* var; int* status; double* cov; double* bex; double* tail;
 } hipdrt_debug_posterior_args;
 int hipdrt_debug_posterior(hipdrt_ctx* ctx, const hipdrt_debug_posterior_args* a);
+
+/* test hook (tests/test_gpu_qp_loop.py): launch_qp (csrc/qp.hip) as it is, on host arrays, with its arguments filled the way the fit
+ * loop fills them (loop_qp_args, csrc/plan_fit.hip) -- a form hipdrt_qp_batch cannot produce: P reaches the kernel as packed tiles only
+ * (launch_pack_p; one shared copy with stride 0 when p_batched = 0), with an active mask, a dispatch-order table and iters_accum.
+ * The kernel is chosen from this context's switches (hipdrt_debug_qp_group, hipdrt_debug_qp_waves) as every launch of the context is.
+ *   P [p_batched ? B : 1][n][ldp] (lower triangle read), q [B][n], h [h_batched ? B : 1][n]; opts NULL = the defaults;
+ *   active [B] or NULL; order [B] or NULL: workgroup i solves problem order[i], must be a permutation of 0 .. B - 1;
+ *   use_lpt != 0 (excludes order, needs iters): the hook runs lpt_order_kernel on the uploaded iters and active, as the fit loop does
+ *   in front of every coneqp launch, and hands its table to the kernel;
+ *   form [3] out or NULL: {workgroups per problem G (0 = the batch kernel), inverse diagonal blocks in global memory 0 / 1, wavefronts
+ *   per workgroup}: what the launch was sized for.
+ * In/out, host contents uploaded first, so an entry no kernel wrote comes back as it went in: x [B][n], status [B]; iters [B], pcost [B],
+ * iters_accum [B] (each may be NULL).  Out, any may be NULL: s, z [B][n], state vectors 2 and 1 of the leader's copy of the iterates
+ * (slot b * max(G, 1); rows of inactive problems are left alone); order_out [B] the table the kernel used (the identity without one).
+ * On the device every in/out array, the order table, every problem's state block (17 vectors x state_ld, one per member), every
+ * problem's factor scratch (qp_scratch_doubles) and the group kernel's sync words sit between borders of marker bytes:
+ * HIPDRT_E_NUMERIC when a border changed, or when the leader's state does not hold the x that came back.  HIPDRT_E_INVALID, and
+ * nothing is launched, for n or B outside 1..4096, ldp < n, non-finite input, an order that is no permutation, or n > 2048 with the
+ * batch kernel forced.                                                                                                             */
+typedef struct hipdrt_debug_qp_args {
+    int B, n;
+    const double* P; int p_batched, ldp;
+    const double* q;
+    const double* h; int h_batched;
+    const hipdrt_qp_opts* opts;
+    const int* active;
+    const int* order;
+    int use_lpt;
+    int* form;
+    double* x; int* iters; double* pcost; int* status; int* iters_accum;
+    double* s; double* z; int* order_out;
+} hipdrt_debug_qp_args;
+int hipdrt_debug_qp(hipdrt_ctx* ctx, const hipdrt_debug_qp_args* a);
+/* test hook: lpt_order_kernel alone -- order [B] (in/out, between borders of marker bytes) = the problems by descending iters, inactive
+ * ones (active [B], may be NULL) last, ties in index order.  HIPDRT_E_INVALID when B * sizeof(int) exceeds 48 KiB, the fit loop's own
+ * condition for using the table.                                                                                                 */
+int hipdrt_debug_lpt_order(hipdrt_ctx* ctx, int B, const int* iters, const int* active, int* order);
 
 /* tools hook (tools/bench_predict.py, tools/bench_peaks.py, tools/bench_response.py, tools/bench_candidates.py): kernel time in ms
  * of the last hipdrt_plan_llh_terms / _obs_llh_terms(_w) (ms[0] = ms[1]: its one launch), hipdrt_plan_score_candidates (ms[1]: all
