@@ -206,6 +206,33 @@ class DebugResponseArgs(C.Structure):
                 ("v_baseline_scale", _dp), ("fit_status", _ip), ("include_mask", C.c_int), ("out", _dp)]
 
 
+class FilterTable(C.Structure):
+    """hipdrt_filter_table (include/hipdrt.h): centre and right half of a symmetric table; radius < 0 skips the axis"""
+    _fields_ = [("w", _dp), ("radius", C.c_int)]
+
+
+MAP_FILTER_MAX_NODES = 16
+MAP_FILTER, MAP_SIGMAS = 0, 1
+
+
+class NodeTables(C.Structure):
+    """hipdrt_node_tables (include/hipdrt.h)"""
+    _fields_ = [("count", C.c_int), ("node", C.c_double * MAP_FILTER_MAX_NODES), ("node_delta", C.c_double), ("floor", C.c_double),
+                ("radius", C.c_int * MAP_FILTER_MAX_NODES), ("w", _dp * MAP_FILTER_MAX_NODES)]
+
+
+NODE_TABLE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(NodeTables))
+
+
+class MapFilterArgs(C.Structure):
+    """hipdrt_map_filter_args (include/hipdrt.h)"""
+    _fields_ = [("ndim", C.c_int), ("rows", C.c_int), ("cols", C.c_int), ("op", C.c_int), ("iterative", C.c_int),
+                ("adaptive", C.c_int), ("mask_nans", C.c_int), ("empty", C.c_int), ("iter", C.c_int), ("nstd", C.c_double),
+                ("box_size", C.c_int), ("init_weights", _dp), ("sigmas_in", _dp), ("gauss", FilterTable * 2), ("empty_gauss", FilterTable * 2),
+                ("box", FilterTable * 2), ("pre_gauss", FilterTable * 2), ("pre_empty", FilterTable * 2), ("curv", FilterTable),
+                ("k_factor", C.c_double * 2), ("max_sigma", C.c_double * 2), ("nodes", NODE_TABLE_FN), ("user", C.c_void_p)]
+
+
 # include_mask bits of hipdrt_plan_predict_response and hipdrt_plan_predict_z_model (HIPDRT_INCLUDE_*)
 INCLUDE_DRT, INCLUDE_OHMIC, INCLUDE_CAP, INCLUDE_DOP, INCLUDE_VZ_OFFSET, INCLUDE_BASELINE, INCLUDE_INDUCTANCE = 1, 2, 4, 8, 16, 32, 64
 INCLUDE_ALL = 127
@@ -236,6 +263,7 @@ SIGNATURES = {
                                        _dp, _dp],
     "hipdrt_nonuniform_gaussian_filter1d": [_vp, _dp, C.c_int, _dp, _ip, C.c_int, _ip, _dp, C.c_int, _dp, _dp, C.c_longlong,
                                             _ip, _ip, _dp],
+    "hipdrt_map_filter": [_vp, C.POINTER(MapFilterArgs), _dp, _dp, _dp, _dp],
     "hipdrt_penalty_matrices": [_vp, _dp, C.c_int, C.c_double, C.c_int, _dp, _dp, _dp],
     "hipdrt_eis_var_matrix": [_vp, _dp, C.c_int, C.c_double, C.c_double, C.c_int, _dp],
     "hipdrt_qp_batch": [_vp, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, C.POINTER(QpOpts), _dp, _ip, _dp, _ip],
@@ -290,6 +318,7 @@ SIGNATURES = {
     "hipdrt_debug_pfrt_combine": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.POINTER(PfrtOpts), _dp, _dp,
                                   _dp, _dp, _dp],
     "hipdrt_debug_last_predict_ms": [_vp, C.POINTER(C.c_float)],
+    "hipdrt_debug_map_filter_stats": [_vp, _dp],
     "hipdrt_debug_apply_rows": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp],
     "hipdrt_comm_unique_id": [C.c_char_p],
     "hipdrt_comm_create": [C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(_vp)],
@@ -701,6 +730,30 @@ class Context:
                                                              _pi(filtered), _p(nodes), nodes.shape[1], _p(node_delta),
                                                              _p(weights), weights.size, _pi(woff), _pi(radius), _p(out)))
         return out
+
+    def map_filter(self, a, args: MapFilterArgs, want_weights=False, want_sigmas=False):
+        """hipdrt_map_filter on a 1-D or 2-D array (NaN = missing); `args` comes filled but for the shape (hipdrt.filters builds
+        it).  Returns dict(out=, weights=, sigmas=) with the entries the call produces."""
+        a = _f64(a)
+        if a.ndim not in (1, 2):
+            raise ValueError("a 1-D or 2-D array")
+        args.ndim, args.rows, args.cols = a.ndim, a.shape[0], (a.shape[1] if a.ndim == 2 else 1)
+        res = {}
+        if args.op == MAP_FILTER:
+            res["out"] = np.empty_like(a)
+            if want_weights:
+                res["weights"] = np.empty_like(a)
+        if want_sigmas or args.op == MAP_SIGMAS:
+            res["sigmas"] = np.empty((a.ndim,) + a.shape)
+        _check(self._lib.hipdrt_map_filter(self._h, C.byref(args), _p(a), _p(res.get("out")), _p(res.get("weights")),
+                                           _p(res.get("sigmas"))))
+        return res
+
+    def debug_map_filter_stats(self):
+        """tools: (kernel launches, full-array reads + writes, device ms) of this context's last map_filter"""
+        st = (C.c_double * 3)()
+        _check(self._lib.hipdrt_debug_map_filter_stats(self._h, st))
+        return int(st[0]), int(st[1]), float(st[2])
 
     def penalty_matrices(self, ln_tau, epsilon, toeplitz):
         ln_tau = _f64(ln_tau)

@@ -103,6 +103,8 @@ struct hipdrt_ctx {
     int cand_form = -1;
     // hipdrt_debug_last_predict_ms (tools): kernel time of the last prediction, ms -- [0] up to the mean / the impedance, [1] band included
     float predict_ms[2] = {0.f, 0.f};
+    // hipdrt_debug_map_filter_stats (tools): launches, full-array reads + writes and device ms of the last hipdrt_map_filter
+    double map_filter_stats[3] = {0.0, 0.0, 0.0};
 };
 
 // ---- launchers implemented in the .hip files (all asynchronous on `st`) ---------------------------------

@@ -1,9 +1,13 @@
-"""Drop-in for the part of hybdrt/filters that the chrono down-sampling uses: the blended, per-sample-width Gaussian filter.
-The correlations run on the device (csrc/matrices.hip: nonuniform_gauss_kernel); the sigma nodes and kernel tables are
-derived here exactly as the reference / scipy derive them."""
+"""Drop-in for the parts of hybdrt/filters that run on the device: the blended, per-sample-width Gaussian filter of the chrono
+down-sampling (csrc/matrices.hip: nonuniform_gauss_kernel) and the map filters of mapping.ndx.filter_ndx (mapfilter.py,
+csrc/map_filter.hip): masked_filter, iterative_gaussian_filter, get_adaptive_sigmas, adaptive_gaussian_filter.  Sigma nodes and
+kernel tables are derived on the host exactly as the reference / scipy derive them; ndfilters.py states the map filters in numpy."""
 import numpy as np
 
 from .. import _ffi
+from . import ndfilters  # noqa: F401  (the numpy statement of the map filters)
+from .mapfilter import (adaptive_gaussian_filter, filter_array, get_adaptive_sigmas, iterative_gaussian_filter,  # noqa: F401
+                        masked_filter)
 
 
 def _gaussian_kernel_half(sigma, radius):

@@ -15,10 +15,17 @@ reference's:
                                            fitted on the device before the failed one keep their results, as in the
                                            reference's serial loop, later ones stay unfitted
 
-Not here (out of scope): file readers, psi interpolation / filtering, resolve bookkeeping, pickling."""
+Fitted observations can be smoothed across psi and tau on the device: ``filter_observations`` / ``filter_group``
+(drtmd.py:561-635) write ``obs_x_filt`` / ``obs_special_filt`` through mapping.ndx.filter_ndx.
+
+Not here (out of scope): file readers, psi interpolation, resolve bookkeeping, pickling."""
+import warnings
+
 import numpy as np
 
 from . import drtmd as _driver
+from .ndx import filter_ndx
+from .resolve import get_tau_indices
 from .table import new_special, tau_slots
 
 
@@ -48,7 +55,11 @@ class DRTMD:
         nt = len(self.tau_supergrid)
         self.obs_x = np.zeros((0, nt)) if fit_type == 'drt' else np.zeros((0, n_steps, nt))
         self.obs_drt_var = np.zeros_like(self.obs_x)
+        self.obs_x_filt = np.zeros_like(self.obs_x)
         self.obs_special = None
+        self.obs_special_filt = {}
+        # the store keeps no resolve bookkeeping: a caller that resolves (mapping.resolve) may set these for filter_observations
+        self.obs_x_resolved, self.obs_special_resolved = None, None
         self.obs_llh, self.obs_rss = np.zeros(0), np.zeros(0)
         self.last_fit_index = np.zeros(0, dtype=int)          # what the last fit_observations call sent to the device
 
@@ -72,6 +83,9 @@ class DRTMD:
         self.obs_tau_indices.append(None)
         self.obs_x = np.concatenate([self.obs_x, np.zeros((1,) + self.obs_x.shape[1:])])
         self.obs_drt_var = np.concatenate([self.obs_drt_var, np.zeros((1,) + self.obs_drt_var.shape[1:])])
+        self.obs_x_filt = np.concatenate([self.obs_x_filt, np.zeros((1,) + self.obs_x_filt.shape[1:])])
+        for key, val in self.obs_special_filt.items():
+            self.obs_special_filt[key] = np.concatenate([val, np.zeros((1,) + val.shape[1:])])
         self.obs_llh, self.obs_rss = np.append(self.obs_llh, 0.0), np.append(self.obs_rss, 0.0)
         if self.obs_special is not None:
             for key in self.obs_special:
@@ -133,3 +147,68 @@ class DRTMD:
             fit_index = np.where(~self.obs_fit_status & ~self.obs_ignore_flag)[0]
         self.fit_observations(fit_index, ignore_errors=ignore_errors)
         return fit_index
+
+    def get_group_index(self, group_id, psi_sort_dims=None, exclude_flagged=False):
+        """drtmd.py:1194-1225: observation indices of a group (a string) or of several (a list), optionally sorted by psi
+        dimensions -- within groups when several are given"""
+        ids = np.array(self.obs_group_id)
+        single = type(group_id) == str                                                           # noqa: E721 (as upstream)
+        obs_index = np.where(ids == group_id)[0] if single else np.where(np.isin(ids, group_id))[0]
+        if psi_sort_dims is not None:
+            sort_vals = [self.obs_psi[obs_index, self.psi_dim_names.index(d)] for d in psi_sort_dims]
+            if not single:
+                sort_vals = [ids[obs_index]] + sort_vals
+            obs_index = obs_index[np.lexsort(sort_vals[::-1])]
+        if exclude_flagged:
+            obs_index = obs_index[~self.obs_ignore_flag[obs_index]]
+        return obs_index
+
+    def filter_observations(self, obs_index, psi_sort_dims=None, truncate=False, resolved=True, special_kw=None, **kw):
+        """drtmd.py:561-628: smooth the fitted coefficients of the listed observations across psi (rows, in the order of
+        psi_sort_dims) and tau with mapping.ndx.filter_ndx(**kw) on the device, into obs_x_filt / obs_special_filt.  x_dop is
+        filtered with kw, the other specials with special_kw (None: kw without the tau entry of a non-scalar sigma / max_sigma);
+        vz_offset and v_baseline are data-dependent and copied."""
+        obs_index = np.asarray(obs_index, dtype=int).ravel()
+        obs_index = obs_index[self.obs_fit_status[obs_index] & ~self.obs_ignore_flag[obs_index]]
+        if psi_sort_dims is not None:
+            sort_vals = [self.obs_psi[obs_index, self.psi_dim_names.index(d)] for d in psi_sort_dims][::-1]
+            obs_index = obs_index[np.lexsort(sort_vals)]
+        if resolved and (self.obs_x_resolved is None or self.obs_special_resolved is None):
+            raise ValueError("resolved=True needs obs_x_resolved / obs_special_resolved, which this store does not fill: set them, "
+                             "or pass resolved=False to filter the fitted parameters")
+        x_drt_in = self.obs_x_resolved if resolved else self.obs_x
+        special_in = (self.obs_special_resolved if resolved else self.obs_special) or {}
+        if special_kw is None:
+            special_kw = kw.copy()
+            for key in ("max_sigma", "sigma"):
+                if key in special_kw and not np.isscalar(special_kw[key]):
+                    special_kw[key] = special_kw[key][:-1]                  # the tau axis
+        if len(obs_index) == 0:
+            warnings.warn("No valid observations included in resolution group")
+            return
+        obs_tau_indices = [self.obs_tau_indices[i] for i in obs_index]
+        if len(obs_index) == 1:
+            warnings.warn("Only one observation included in filter; raw parameters will be copied")
+            left, right = obs_tau_indices[0]
+            x_drt = x_drt_in[obs_index, left:right]
+            special = {k: v[obs_index] for k, v in special_in.items()}
+        else:
+            left, right = get_tau_indices(obs_tau_indices, truncate=truncate)
+            x_drt = filter_ndx(x_drt_in[obs_index, left:right], num_group_dims=0, **kw)
+            special = {}
+            for k, v in special_in.items():
+                if k in ("vz_offset", "v_baseline"):
+                    special[k] = v[obs_index]
+                else:
+                    special[k] = filter_ndx(v[obs_index], num_group_dims=0, **(kw if k == "x_dop" else special_kw))
+        self.obs_x_filt[obs_index, left:right] = x_drt
+        for key, val in special.items():
+            if key not in self.obs_special_filt:
+                self.obs_special_filt[key] = new_special(self.num_obs, val)
+            self.obs_special_filt[key][obs_index] = val
+
+    def filter_group(self, group_id, psi_sort_dims=None, truncate=False, resolved=True, special_kw={}, **kw):   # noqa: B006
+        """drtmd.py:630-635.  special_kw is forwarded as given: with upstream's default {} the special parameters are filtered
+        without a sigma, which fails there and here -- pass special_kw=None for the derived keywords"""
+        return self.filter_observations(self.get_group_index(group_id), psi_sort_dims, truncate=truncate, resolved=resolved,
+                                        special_kw=special_kw, **kw)

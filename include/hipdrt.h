@@ -140,6 +140,66 @@ int hipdrt_nonuniform_gaussian_filter1d(hipdrt_ctx* ctx, const double* y, int n,
                                         const double* node_delta, const double* weights, long long nweights,
                                         const int* woff, const int* radius, double* out);
 
+/* mapping.ndx.filter_ndx without groups (hybdrt/mapping/ndx.py:261-349, _filter_ndx_sub 302-349) on one (rows, cols) array --
+ * the smoothing of a fitted map across psi and tau (DRTMD.filter_observations, hybdrt/mapping/drtmd.py:561-635): the
+ * outlier-robust iterative Gaussian filter (hybdrt/filters/_filters.py: masked_filter 149-175, iterate_gaussian_weights
+ * 183-232, iterative_gaussian_filter 235-256; rms_filter 8-26), optionally with curvature-adaptive widths
+ * (nonuniform_gaussian_filter1d 261-345, get_adaptive_sigma1d 363-413, adaptive_gaussian_filter 451-475), on the 'reflect'
+ * boundary of scipy.ndimage.  `a` is uploaded once and `out` downloaded once; in between only the scalars the host needs come
+ * back (std of the curvature, min / max of a sigma field).
+ *
+ * Every table is built by the caller as scipy / _scifilters.py build it and is given as its centre and right half (all are
+ * symmetric): w[0 .. radius].  radius < 0 skips the axis (sigma <= 1e-15, as gaussian_filter does).  Axis 0 runs along the rows
+ * (stride cols), axis 1 along a row; ndim == 1 takes cols == 1 and axis 0 only. */
+typedef struct {
+    const double* w;
+    int radius;
+} hipdrt_filter_table;
+
+#define HIPDRT_MAP_FILTER_MAX_NODES 16
+/* the sigma nodes of one nonuniform_gaussian_filter1d call (_filters.py:264-295): node[k] ascending, node_delta their log
+ * spacing, floor the value smaller sigmas are raised to (0: none); w[k][0 .. radius[k]] the node's table (Gaussian, or empty
+ * Gaussian at max(node, min_sigma)), radius[k] < 0: the node returns its input (empty=False below min_sigma) */
+typedef struct {
+    int count;
+    double node[HIPDRT_MAP_FILTER_MAX_NODES];
+    double node_delta, floor;
+    int radius[HIPDRT_MAP_FILTER_MAX_NODES];
+    const double* w[HIPDRT_MAP_FILTER_MAX_NODES];
+} hipdrt_node_tables;
+/* called by hipdrt_map_filter, on the calling thread, once the extremes of a sigma field (after the floor at 1e-8) are known;
+ * the tables must stay valid until hipdrt_map_filter returns.  Non-zero return: hipdrt_map_filter fails with HIPDRT_E_INVALID. */
+typedef int (*hipdrt_node_table_fn)(void* user, int axis, int empty, double sigma_min, double sigma_max, hipdrt_node_tables* out);
+
+#define HIPDRT_MAP_FILTER 0   /* the filtered array */
+#define HIPDRT_MAP_SIGMAS 1   /* get_adaptive_sigmas(a, empty=, weights=init_weights) only: sigmas_out, nothing else */
+typedef struct {
+    int ndim, rows, cols;
+    int op;                       /* HIPDRT_MAP_FILTER / HIPDRT_MAP_SIGMAS */
+    int iterative, adaptive;      /* _filter_ndx_sub's switches */
+    int mask_nans;                /* 1: NaN entries are zero-filled and carry weight 0; 0: `a` is filtered as it stands */
+    int empty;                    /* HIPDRT_MAP_SIGMAS: get_adaptive_sigmas' empty=; with sigmas_in: adaptive_gaussian_filter's */
+    int iter;                     /* iterate_gaussian_weights: passes (2) */
+    double nstd;                  /* ... and nstd (5) */
+    int box_size;                 /* dev_rms_size (5; odd) */
+    const double* init_weights;   /* optional [rows * cols]: the mask of a non-iterative masked filter (masked_filter's mask) */
+    const double* sigmas_in;      /* optional [ndim][rows * cols], adaptive = 1, iterative = 0: adaptive_gaussian_filter(a,
+                                   * sigmas=, empty=) with these fields instead of get_adaptive_sigmas' */
+    hipdrt_filter_table gauss[2], empty_gauss[2];   /* adaptive = 0: order-0 Gaussian and empty Gaussian of sigma[axis] */
+    hipdrt_filter_table box[2];                     /* iterative: ones, radius box_size / 2, per axis */
+    hipdrt_filter_table pre_gauss[2], pre_empty[2]; /* adaptive = 1: the same pair for presmooth_sigma[axis] ... */
+    hipdrt_filter_table curv;                       /* ... and the order-2 Gaussian of curv_sigma = 1 */
+    double k_factor[2], max_sigma[2];
+    hipdrt_node_table_fn nodes;   /* adaptive = 1 */
+    void* user;
+} hipdrt_map_filter_args;
+/* a[rows * cols] row-major, NaN = missing.  out[rows * cols]: every entry filled (fill_nans=True; the caller restores NaNs per
+ * impute / impute_groups).  weights_out (optional, iterative): the final weights of iterate_gaussian_weights.  sigmas_out
+ * (optional, adaptive): [ndim][rows * cols], the sigma fields of the last get_adaptive_sigmas.  Sums behind np.std run in a
+ * fixed order: a call repeats itself bit for bit. */
+int hipdrt_map_filter(hipdrt_ctx* ctx, const hipdrt_map_filter_args* args, const double* a, double* out, double* weights_out,
+                      double* sigmas_out);
+
 /* mat1d.construct_integrated_derivative_matrix (hybdrt/matrices/mat1d.py:125-209), orders 0,1,2 of the
  * Gaussian basis (closed forms basis.py:382-395).  toeplitz != 0: first column scattered (mat1d.py:158-168).
  * out: m0, m1, m2 each [n][n]                                                                        */

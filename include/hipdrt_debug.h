@@ -295,6 +295,12 @@ int hipdrt_debug_lpt_order(hipdrt_ctx* ctx, int B, const int* iters, const int* 
  * the credible band's factorisation included (equal to ms[0] without a band).                                                    */
 int hipdrt_debug_last_predict_ms(hipdrt_ctx* ctx, float* ms);
 
+/* Tools (tools/probe_map_filter.py): what the last hipdrt_map_filter of this context did between its upload and its download --
+ * stats[0] kernel launches, stats[1] full-array reads plus writes those kernels make (in arrays of rows * cols doubles, counted
+ * by the driver as it launches), stats[2] device time in ms by HIP events around them (the scalar read-backs and the node-table
+ * callbacks of the adaptive path included).                                                                                    */
+int hipdrt_debug_map_filter_stats(hipdrt_ctx* ctx, double* stats);
+
 #ifdef __cplusplus
 }
 #endif
