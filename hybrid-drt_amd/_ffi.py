@@ -233,6 +233,19 @@ class MapFilterArgs(C.Structure):
                 ("k_factor", C.c_double * 2), ("max_sigma", C.c_double * 2), ("nodes", NODE_TABLE_FN), ("user", C.c_void_p)]
 
 
+RANK_ONE, RANK_DIFF = 0, 1
+Q_NANMEDIAN = -1.0
+E_NUMERIC, E_UNSUPPORTED = -4, -5
+
+
+class MapBadnessArgs(C.Structure):
+    """hipdrt_map_badness_args (include/hipdrt.h)"""
+    _fields_ = [("rows", C.c_int), ("cols", C.c_int), ("scale", C.c_int), ("flag_outliers", C.c_int), ("flag_size", C.c_int * 2),
+                ("median_size", C.c_int * 2), ("std_size", C.c_int * 2), ("thresh", C.c_double), ("p_prior", C.c_double),
+                ("full_std_contribution", C.c_double), ("n_std", C.c_double), ("impute", C.c_int), ("impute_gauss", FilterTable * 2), ("score", C.c_int),
+                ("filt_in", _dp)]
+
+
 # include_mask bits of hipdrt_plan_predict_response and hipdrt_plan_predict_z_model (HIPDRT_INCLUDE_*)
 INCLUDE_DRT, INCLUDE_OHMIC, INCLUDE_CAP, INCLUDE_DOP, INCLUDE_VZ_OFFSET, INCLUDE_BASELINE, INCLUDE_INDUCTANCE = 1, 2, 4, 8, 16, 32, 64
 INCLUDE_ALL = 127
@@ -264,6 +277,9 @@ SIGNATURES = {
     "hipdrt_nonuniform_gaussian_filter1d": [_vp, _dp, C.c_int, _dp, _ip, C.c_int, _ip, _dp, C.c_int, _dp, _dp, C.c_longlong,
                                             _ip, _ip, _dp],
     "hipdrt_map_filter": [_vp, C.POINTER(MapFilterArgs), _dp, _dp, _dp, _dp],
+    "hipdrt_rank_filter": [_vp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp],
+    "hipdrt_percentiles": [_vp, _dp, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp],
+    "hipdrt_map_badness": [_vp, C.POINTER(MapBadnessArgs), _dp, _dp, _dp, C.POINTER(C.c_ubyte), _dp],
     "hipdrt_penalty_matrices": [_vp, _dp, C.c_int, C.c_double, C.c_int, _dp, _dp, _dp],
     "hipdrt_eis_var_matrix": [_vp, _dp, C.c_int, C.c_double, C.c_double, C.c_int, _dp],
     "hipdrt_qp_batch": [_vp, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, C.POINTER(QpOpts), _dp, _ip, _dp, _ip],
@@ -319,6 +335,7 @@ SIGNATURES = {
                                   _dp, _dp, _dp],
     "hipdrt_debug_last_predict_ms": [_vp, C.POINTER(C.c_float)],
     "hipdrt_debug_map_filter_stats": [_vp, _dp],
+    "hipdrt_debug_map_badness_ms": [_vp, _dp],
     "hipdrt_debug_apply_rows": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp],
     "hipdrt_comm_unique_id": [C.c_char_p],
     "hipdrt_comm_create": [C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(_vp)],
@@ -754,6 +771,64 @@ class Context:
         st = (C.c_double * 3)()
         _check(self._lib.hipdrt_debug_map_filter_stats(self._h, st))
         return int(st[0]), int(st[1]), float(st[2])
+
+    def debug_map_badness_ms(self):
+        """tools: device ms of this context's last map_badness"""
+        ms = C.c_double()
+        _check(self._lib.hipdrt_debug_map_badness_ms(self._h, C.cast(C.byref(ms), _dp)))
+        return float(ms.value)
+
+    def rank_filter(self, a, size, rank_lo, rank_hi=None):
+        """hipdrt_rank_filter on a 2-D array: rank rank_lo of every size[0] x size[1] window, or (rank_hi given) the difference
+        rank_hi - rank_lo of the same window.  A window of more than 49 entries raises NotImplementedError."""
+        a = _f64(a)
+        if a.ndim != 2:
+            raise ValueError("a 2-D array")
+        out = np.empty_like(a)
+        rc = self._lib.hipdrt_rank_filter(self._h, _p(a), a.shape[0], a.shape[1], int(size[0]), int(size[1]),
+                                          RANK_ONE if rank_hi is None else RANK_DIFF, int(rank_lo),
+                                          int(rank_lo if rank_hi is None else rank_hi), _p(out))
+        if rc == E_UNSUPPORTED:
+            raise NotImplementedError(self._lib.hipdrt_last_error().decode())
+        _check(rc)
+        return out
+
+    def percentiles(self, a, q, by_row=False):
+        """hipdrt_percentiles: np.nanpercentile(a, q) over the whole array (out[nq]) or by row of a 2-D one (out[rows, nq]);
+        an entry Q_NANMEDIAN of q asks for np.nanmedian"""
+        a = _f64(a)
+        q = _f64(np.atleast_1d(q))
+        rows, cols = (a.shape if (by_row and a.ndim == 2) else (1, a.size))
+        out = np.empty((rows, q.size) if by_row else q.size)
+        _check(self._lib.hipdrt_percentiles(self._h, _p(a), rows, cols, int(bool(by_row)), _p(q), q.size, _p(out)))
+        return out
+
+    def map_badness(self, a, args: MapBadnessArgs, scale_src=None, want_flags=False, want_filt=False):
+        """hipdrt_map_badness on a 2-D array; `args` comes filled but for the shape (hipdrt.mapping.nddata builds it).  Returns
+        dict(rss=, flags=, filt=); ValueError when x_std contains NaNs, as the reference raises it."""
+        a = _f64(a)
+        if a.ndim != 2:
+            raise ValueError("a 2-D array")
+        args.rows, args.cols = a.shape
+        if scale_src is not None:
+            scale_src = _f64(scale_src)
+            if scale_src.shape != a.shape:
+                raise ValueError("scale_src must have the shape of a")
+        res = {}
+        if args.score:
+            res["rss"] = np.empty(a.shape[0])
+        if want_flags:
+            res["flags"] = np.empty(a.shape, dtype=np.uint8)
+        if want_filt:
+            res["filt"] = np.empty_like(a)
+        flags = res["flags"].ctypes.data_as(C.POINTER(C.c_ubyte)) if want_flags else None
+        rc = self._lib.hipdrt_map_badness(self._h, C.byref(args), _p(a), _p(scale_src), _p(res.get("rss")), flags, _p(res.get("filt")))
+        if rc == E_NUMERIC:
+            raise ValueError(self._lib.hipdrt_last_error().decode())
+        _check(rc)
+        if want_flags:
+            res["flags"] = res["flags"].astype(bool)
+        return res
 
     def penalty_matrices(self, ln_tau, epsilon, toeplitz):
         ln_tau = _f64(ln_tau)

@@ -105,6 +105,7 @@ struct hipdrt_ctx {
     float predict_ms[2] = {0.f, 0.f};
     // hipdrt_debug_map_filter_stats (tools): launches, full-array reads + writes and device ms of the last hipdrt_map_filter
     double map_filter_stats[3] = {0.0, 0.0, 0.0};
+    double map_badness_ms = 0.0;      // hipdrt_debug_map_badness_ms (tools): device ms of the last hipdrt_map_badness
 };
 
 // ---- launchers implemented in the .hip files (all asynchronous on `st`) ---------------------------------

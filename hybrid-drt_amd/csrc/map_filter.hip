@@ -435,6 +435,26 @@ struct MapFilter {
 };
 
 }  // namespace
+
+// map_filter_dev.hpp: masked_filter(nan_to_num(a), ~isnan(a), gaussian_filter) on device buffers -- prep_kernel and the fused
+// masked passes above, for impute_nans of the badness chain (map_rank.hip)
+int masked_gaussian_device(hipStream_t st, const double* a, int R, int C, const hipdrt_filter_table* tabs, double* out) {
+    MapFilter m;
+    m.st = st; m.g = nullptr;
+    m.R = R; m.C = C; m.nax = 2; m.phys[0] = 0; m.phys[1] = 1;
+    HIPDRT_REQUIRE((C + TILE_C - 1) / TILE_C <= 65535, "at most 65535 * 64 entries along a row");
+    m.n = (size_t)R * C; m.bytes = m.n * sizeof(double);
+    for (DevBuf* b : {&m.x, &m.w, &m.t0, &m.t1, &m.u0, &m.u1}) HIPDRT_CHECK(b->alloc(m.bytes));
+    const double one = 1.0;
+    TRY(upload(m.ident.buf, &one, sizeof(double), st)); m.ident.r = 0;
+    for (int l = 0; l < 2; ++l) TRY(m.upload_tab(m.gauss[l], tabs[l]));
+    hipLaunchKernelGGL(prep_kernel, dim3((m.n + 255) / 256), dim3(256), 0, st, a, m.n, 1, (const double*)nullptr, m.x.d(), m.w.d());
+    LAUNCH_OK();
+    TRY(m.run(m.table_steps(m.gauss), m.x.d(), m.w.d(), PRE_MUL, out, nullptr, POST_DIV));
+    HIPDRT_CHECK(hipStreamSynchronize(st));          // the work buffers and `one` go out of scope
+    return HIPDRT_OK;
+}
+
 }  // namespace hipdrt
 
 using namespace hipdrt;

@@ -8,6 +8,7 @@ from .. import _ffi
 from . import ndfilters  # noqa: F401  (the numpy statement of the map filters)
 from .mapfilter import (adaptive_gaussian_filter, filter_array, get_adaptive_sigmas, iterative_gaussian_filter,  # noqa: F401
                         masked_filter)
+from .rankfilter import iqr_filter, median_filter, percentile_filter  # noqa: F401  (csrc/map_rank.hip)
 
 
 def _gaussian_kernel_half(sigma, radius):

@@ -343,3 +343,134 @@ def adaptive_gaussian_filter(a, sigmas=None, presmooth_sigma=None, empty=False, 
             out = adaptive_gaussian_filter1d(out, sigmas[axis], axis, presmooth_sigma, empty, curv_func, curv_kw, k_factor[axis],
                                              max_sigma[axis], mode, cval, truncate, order, sigma_node_factor)
     return out
+
+
+# ---- scipy.ndimage's rank filters (median_filter, percentile_filter) and _filters.iqr_filter (43-46) --------------------------
+RANK_MAX_WINDOW = 49        # the device's window cap (csrc/map_rank.hip)
+
+
+def ni_select(buf, lo, hi, rank):
+    """scipy's NI_Select (ni_filters.c): Hoare quickselect on buf[lo .. hi], in place.  On a window without NaNs it returns the
+    rank-th smallest entry; on one with NaNs, where every comparison with a NaN is false, what it returns is a property of
+    these very steps and of the order of the entries -- which is why they are restated and not replaced by a sort."""
+    while True:
+        if lo == hi:
+            return buf[lo]
+        x = buf[lo]
+        i, j = lo - 1, hi + 1
+        while True:
+            j -= 1
+            while buf[j] > x:
+                j -= 1
+            i += 1
+            while buf[i] < x:
+                i += 1
+            if i < j:
+                buf[i], buf[j] = buf[j], buf[i]
+            else:
+                break
+        k = j - lo + 1
+        if rank < k:
+            hi = j
+        else:
+            lo, rank = j + 1, rank - k
+
+
+def _check_rank_args(input, size, footprint, output, mode, origin):
+    _check_mode(mode)
+    if footprint is not None:
+        raise NotImplementedError("footprint: only size= windows are built")
+    if output is not None:
+        raise NotImplementedError("output: the filters return a new array")
+    if np.any(np.asarray(origin) != 0):
+        raise NotImplementedError("origin: only origin 0 is built")
+    if size is None:
+        raise RuntimeError("no footprint or filter size provided")
+    a = np.asarray(input, dtype=float)
+    if a.ndim != 2:
+        raise NotImplementedError("input: the rank filters take 2-D arrays")
+    size = [int(s) for s in _normalize_sequence(size, 2)]
+    if min(size) < 1:
+        raise RuntimeError("incorrect filter size")
+    return a, size
+
+
+def percentile_rank(filter_size, percentile):
+    """scipy's rank of a percentile in a window of filter_size entries (percentile_filter, _filters.py)"""
+    percentile = float(percentile)
+    if percentile < 0.0:
+        percentile += 100.0
+    if percentile < 0 or percentile > 100:
+        raise RuntimeError('invalid percentile')
+    if percentile == 100.0:
+        return filter_size - 1
+    return int(float(filter_size) * percentile / 100.0)
+
+
+def window_values(a, size):
+    """[rows, cols, size[0] * size[1]]: every entry's window, rows outer (the order of scipy's filter buffer), starting size // 2
+    before the entry on either axis, on the 'reflect' boundary"""
+    rows = reflect_index(np.arange(a.shape[0])[:, None] - size[0] // 2 + np.arange(size[0])[None, :], a.shape[0])
+    cols = reflect_index(np.arange(a.shape[1])[:, None] - size[1] // 2 + np.arange(size[1])[None, :], a.shape[1])
+    return a[rows[:, None, :, None], cols[None, :, None, :]].reshape(a.shape + (size[0] * size[1],))
+
+
+def rank_filter(a, size, rank):
+    """entry `rank` of every sorted window; a window with a NaN goes through ni_select for 0 < rank < size - 1 and is NaN at
+    ranks 0 and size - 1 (numpy's min / max; scipy switches to its own minimum / maximum filter there)"""
+    win = window_values(a, size)
+    n = win.shape[-1]
+    if not 0 <= rank < n:
+        raise RuntimeError('rank not within filter footprint size')
+    has_nan = np.isnan(win).any(axis=-1)
+    out = np.where(has_nan, np.nan, np.sort(np.where(has_nan[..., None], 0.0, win), axis=-1)[..., rank])
+    if 0 < rank < n - 1:
+        for i, j in zip(*np.nonzero(has_nan)):
+            out[i, j] = ni_select(win[i, j].tolist(), 0, n - 1, rank)
+    return out
+
+
+def median_filter(input, size=None, footprint=None, output=None, mode="reflect", cval=0.0, origin=0):
+    """scipy.ndimage.median_filter for a 2-D array and size="""
+    a, size = _check_rank_args(input, size, footprint, output, mode, origin)
+    return rank_filter(a, size, size[0] * size[1] // 2)
+
+
+def percentile_filter(input, percentile, size=None, footprint=None, output=None, mode="reflect", cval=0.0, origin=0):
+    """scipy.ndimage.percentile_filter for a 2-D array and size="""
+    a, size = _check_rank_args(input, size, footprint, output, mode, origin)
+    return rank_filter(a, size, percentile_rank(size[0] * size[1], percentile))
+
+
+def iqr_filter(a, size, **kw):
+    """_filters.iqr_filter (43-46)"""
+    return percentile_filter(a, 75, size=size, **kw) - percentile_filter(a, 25, size=size, **kw)
+
+
+Q_NANMEDIAN = -1.0          # the entry of q that asks nan_percentiles for np.nanmedian's rule (HIPDRT_Q_NANMEDIAN)
+
+
+def nan_percentiles(a, q, by_row=False):
+    """np.nanpercentile(a, q) / np.nanpercentile(a, q, axis=1).T with numpy's 'linear' rule, written out as the device forms it
+    (csrc/map_rank.hip): among the n sorted non-NaN values, virtual index v = (n - 1) (q / 100), neighbours a = x[floor v] and
+    b = x[min(floor v + 1, n - 1)], t = v - floor v, a + (b - a) t, and b - (b - a) (1 - t) where t >= 0.5.  An entry
+    Q_NANMEDIAN of q is np.nanmedian: the mean of the middle pair.  No non-NaN value: NaN.  Returns [nq] or [rows, nq]."""
+    a = np.asarray(a, dtype=float)
+    q = np.atleast_1d(np.asarray(q, dtype=float))
+    rows = a if by_row else a.reshape(1, -1)
+    out = np.full((rows.shape[0], len(q)), np.nan)
+    for r, row in enumerate(rows):
+        x = np.sort(row[~np.isnan(row)])
+        n = len(x)
+        if n == 0:
+            continue
+        for k, p in enumerate(q):
+            if p == Q_NANMEDIAN:
+                out[r, k] = (x[(n - 1) // 2] + x[n // 2]) / 2.0
+                continue
+            v = (n - 1) * (p / 100)
+            lo = min(int(np.floor(v)), n - 1)
+            lo_v, hi_v, t = x[lo], x[min(lo + 1, n - 1)], v - lo
+            d = hi_v - lo_v
+            out[r, k] = hi_v - d * (1 - t) if t >= 0.5 else lo_v + d * t
+    return out if by_row else out[0]

@@ -16,7 +16,9 @@ reference's:
                                            reference's serial loop, later ones stay unfitted
 
 Fitted observations can be smoothed across psi and tau on the device: ``filter_observations`` / ``filter_group``
-(drtmd.py:561-635) write ``obs_x_filt`` / ``obs_special_filt`` through mapping.ndx.filter_ndx.
+(drtmd.py:561-635) write ``obs_x_filt`` / ``obs_special_filt`` through mapping.ndx.filter_ndx.  Before that, a group's raw data
+and fitted DRTs can be scored against their neighbours in psi: ``score_group_data_badness`` / ``score_group_fit_badness``
+(drtmd.py:642-783) write ``obs_data_badness`` / ``obs_fit_badness`` through mapping.nddata.score_rows.
 
 Not here (out of scope): file readers, psi interpolation, resolve bookkeeping, pickling."""
 import warnings
@@ -24,6 +26,7 @@ import warnings
 import numpy as np
 
 from . import drtmd as _driver
+from . import nddata
 from .ndx import filter_ndx
 from .resolve import get_tau_indices
 from .table import new_special, tau_slots
@@ -61,6 +64,7 @@ class DRTMD:
         # the store keeps no resolve bookkeeping: a caller that resolves (mapping.resolve) may set these for filter_observations
         self.obs_x_resolved, self.obs_special_resolved = None, None
         self.obs_llh, self.obs_rss = np.zeros(0), np.zeros(0)
+        self.obs_data_badness, self.obs_fit_badness = np.zeros(0), np.zeros(0)                   # drtmd.py:121-122
         self.last_fit_index = np.zeros(0, dtype=int)          # what the last fit_observations call sent to the device
 
     @property
@@ -87,6 +91,7 @@ class DRTMD:
         for key, val in self.obs_special_filt.items():
             self.obs_special_filt[key] = np.concatenate([val, np.zeros((1,) + val.shape[1:])])
         self.obs_llh, self.obs_rss = np.append(self.obs_llh, 0.0), np.append(self.obs_rss, 0.0)
+        self.obs_data_badness, self.obs_fit_badness = np.append(self.obs_data_badness, 0.0), np.append(self.obs_fit_badness, 0.0)
         if self.obs_special is not None:
             for key in self.obs_special:
                 val = self.obs_special[key]
@@ -212,3 +217,79 @@ class DRTMD:
         without a sigma, which fails there and here -- pass special_kw=None for the derived keywords"""
         return self.filter_observations(self.get_group_index(group_id), psi_sort_dims, truncate=truncate, resolved=resolved,
                                         special_kw=special_kw, **kw)
+
+    # ---- data / fit validation (drtmd.py:639-783) ----
+    @staticmethod
+    def _score_rows(statement, device):
+        if statement:
+            return nddata.score_rows_statement
+        return lambda *a, **kw: nddata.score_rows(*a, device=device, **kw)
+
+    def score_group_data_badness(self, group_id, psi_sort_dims, median_filter_size=(3, 1), std_size=(5, 3), ignore_outliers=True,
+                                 impute=False, statement=False, device=0):
+        """drtmd.py:642-735: the badness of every observation's raw data within a group, into obs_data_badness -- the mean
+        squared deviation of its chrono voltage (centred and scaled by its 2 % / 98 % percentiles) and of its impedance from
+        the median across neighbouring observations (rows in the order of psi_sort_dims), in units of the local robust spread;
+        with ignore_outliers, single outlier points are dropped first where they are fewer than 5 % of an observation.
+
+        Where upstream runs (every observation has EIS data, at least one has chrono data) the result is upstream's.  Beyond
+        that: a group without chrono data is scored on its EIS part alone, one without EIS data on its chrono
+        part alone, and an observation that lacks one part is a NaN row of that array.  impute=True fails upstream and is not
+        built.  statement=True evaluates the numpy statement (mapping.nddata.score_rows_statement) instead of the device chain."""
+        if impute:
+            raise NotImplementedError("impute=True is not built (upstream raises TypeError there: impute_nans without a sigma)")
+        score = self._score_rows(statement, device)
+        obs_index = self.get_group_index(group_id, psi_sort_dims=psi_sort_dims)
+        if len(obs_index) == 0:
+            return
+        data_list = [self.get_obs_data(i) for i in obs_index]
+        iv_data = [dl[0] for dl in data_list]
+        z_list = [None if dl[1] is None else dl[1][1] for dl in data_list]
+
+        v_len = np.array([0 if tup is None or tup[0] is None else len(tup[0]) for tup in iv_data])
+        has_chrono = v_len > 0
+        has_eis = np.array([z is not None for z in z_list])
+        v_len = np.unique(v_len[v_len > 0])
+        if len(v_len) > 1:
+            raise ValueError(f'Found chrono data with different lengths: {v_len}')
+        v_rss, z_rss = np.zeros(len(obs_index)), np.zeros(len(obs_index))
+        if has_chrono.any():
+            nan_row = np.full(v_len[0], np.nan)
+            i_array = np.stack([np.asarray(tup[1], dtype=float) if ok else nan_row for tup, ok in zip(iv_data, has_chrono)], axis=0)
+            v_array = np.stack([np.asarray(tup[2], dtype=float) if ok else nan_row for tup, ok in zip(iv_data, has_chrono)], axis=0)
+            v_rss = score(v_array, median_filter_size, std_size, scale_src=i_array, ignore_outliers=ignore_outliers)
+        if has_eis.any():
+            # EIS data: truncated to the shortest length (hybrid measurements)
+            z_len = min(len(z) for z in z_list if z is not None)
+            nan_row = np.full(2 * z_len, np.nan)
+            z_array = np.stack([nan_row if z is None else np.concatenate([np.real(z[:z_len]), np.imag(z[:z_len])]) for z in z_list],
+                               axis=0)
+            z_rss = score(z_array, median_filter_size, std_size, ignore_outliers=ignore_outliers)
+
+        tot_rss = np.zeros(len(obs_index))
+        hybrid_index = has_eis & has_chrono
+        eis_index = has_eis & ~has_chrono
+        chrono_index = has_chrono & ~has_eis
+        tot_rss[hybrid_index] = 0.5 * (v_rss[hybrid_index] + z_rss[hybrid_index])
+        tot_rss[eis_index] = z_rss[eis_index]
+        tot_rss[chrono_index] = v_rss[chrono_index]
+        self.obs_data_badness[obs_index] = tot_rss
+
+    def score_group_fit_badness(self, group_id, psi_sort_dims, median_size=(3, 3), std_size=(5, 3), include_special=False,
+                                statement=False, device=0):
+        """drtmd.py:737-783: the badness of every observation's fitted DRT within a group, into obs_fit_badness -- its mean
+        squared deviation from the median across neighbouring observations and tau, in units of the local robust spread.
+        Ignored and unfitted observations are NaN rows and score 0.  include_special=True fails upstream for scalar special
+        parameters and is not built."""
+        if include_special:
+            raise NotImplementedError("include_special=True is not built (upstream raises RuntimeError for any scalar special "
+                                      "parameter: a 2-D median_size on a 1-D array)")
+        obs_index = self.get_group_index(group_id, psi_sort_dims=psi_sort_dims)
+        if len(obs_index) == 0:
+            return
+        x_array = self.obs_x[obs_index].copy()
+        if x_array.ndim != 2:
+            raise NotImplementedError("fit_type='pfrt': the fit score takes one DRT per observation")
+        ignore = self.obs_ignore_flag[obs_index] | ~self.obs_fit_status[obs_index]
+        x_array[ignore] = np.nan
+        self.obs_fit_badness[obs_index] = self._score_rows(statement, device)(x_array, median_size, std_size)

@@ -200,6 +200,53 @@ typedef struct {
 int hipdrt_map_filter(hipdrt_ctx* ctx, const hipdrt_map_filter_args* args, const double* a, double* out, double* weights_out,
                       double* sigmas_out);
 
+/* scipy.ndimage.median_filter / percentile_filter with size=(size_r, size_c), mode='reflect', origin 0, on a[rows * cols]
+ * row-major, and hybdrt/filters/_filters.py:43-46 iqr_filter as the difference of two ranks of the same window.  The window of
+ * an entry starts size // 2 before it on either axis; rank r is entry r of the sorted window (the median: size_r size_c / 2; a
+ * percentile p: (int)(size_r size_c p / 100.0)).  A window that holds a NaN returns what scipy's quickselect returns on it
+ * (NaN compares false), for 0 < rank < size - 1; at ranks 0 and size - 1 such a window gives NaN.  Windows of more than 49
+ * entries: HIPDRT_E_UNSUPPORTED. */
+#define HIPDRT_RANK_ONE 0    /* out = rank rank_lo                */
+#define HIPDRT_RANK_DIFF 1   /* out = rank rank_hi - rank rank_lo */
+int hipdrt_rank_filter(hipdrt_ctx* ctx, const double* a, int rows, int cols, int size_r, int size_c, int op, int rank_lo,
+                       int rank_hi, double* out);
+
+/* np.nanpercentile(a, q, axis=1) (by_row != 0: out[rows][nq]) or np.nanpercentile(a, q) (by_row == 0: out[nq]) with numpy's
+ * 'linear' rule -- virtual index (n - 1) q / 100 among the n non-NaN values, a + (b - a) t between its neighbours, b - (b - a)
+ * (1 - t) where t >= 0.5 -- as DRTMD.score_group_data_badness (hybdrt/mapping/drtmd.py:675-678) and stats.robust_std
+ * (hybdrt/utils/stats.py:124-134) use it.  q[k] == HIPDRT_Q_NANMEDIAN: np.nanmedian's rule, the mean of the middle pair
+ * (nddata.py:194).  Exact selection with integer histograms: the result does not depend on the launch.  -0 and +0 compare equal;
+ * a segment without a number gives NaN.  1 <= nq <= 4. */
+#define HIPDRT_Q_NANMEDIAN (-1.0)
+int hipdrt_percentiles(hipdrt_ctx* ctx, const double* a, int rows, int cols, int by_row, const double* q, int nq, double* out);
+
+/* The badness score of the rows of one array (hybdrt/mapping/drtmd.py: score_group_data_badness 642-735 for one of its two
+ * arrays, score_group_fit_badness 737-747 and 783), between one upload and one download:
+ *   scale            a <- (a - 0.5 (hi + lo)) / (range of scale_src) by row, the 2 % and 98 % nanpercentiles (drtmd.py:675-679)
+ *   flag_outliers    nddata.flag_outliers(a, flag_size, thresh, p_prior, full_std_contribution) (nddata.py:152-175, with
+ *                    impute_nans 135-149 through impute_gauss and preprocessing.outlier_prob, preprocessing.py:860-876); then a
+ *                    row with fewer than (int)(0.05 cols) flagged entries has them set to NaN (drtmd.py:699-707)
+ *   always           filt = median_filter(a, median_size); rss = flag_bad_obs(a, filt, std_size, return_rss=True,
+ *                    robust_std=True) (nddata.py:178-211)
+ * n_std is stats.std_normal_quantile(0.75), the denominator constant of robust_std.  HIPDRT_E_NUMERIC with the reference's
+ * message when x_std contains NaNs (nddata.py:205-206); rss_out is filled all the same. */
+typedef struct {
+    int rows, cols;
+    int scale, flag_outliers;
+    int flag_size[2], median_size[2], std_size[2];
+    double thresh, p_prior, full_std_contribution;
+    double n_std;
+    int impute;                            /* flag_outliers' impute= (its default, and what drtmd.py:695-696 runs, is 1) */
+    hipdrt_filter_table impute_gauss[2];   /* impute: the Gaussian of impute_nans (sigma 0.5) per axis */
+    int score;                             /* 1: the whole chain; 0: stop after flag_outliers (flags_out only, no 5 % rule) */
+    const double* filt_in;                 /* optional [rows * cols]: flag_bad_obs against this array instead of the median
+                                            * filter of a (nddata.flag_bad_obs with the caller's x_filt) */
+} hipdrt_map_badness_args;
+/* a[rows * cols]; scale_src[rows * cols] (scale = 1); rss_out[rows] (score = 1); flags_out[rows * cols] (optional, flag_outliers = 1): the
+ * outlier flags; filt_out[rows * cols] (optional): the median-filtered array */
+int hipdrt_map_badness(hipdrt_ctx* ctx, const hipdrt_map_badness_args* args, const double* a, const double* scale_src,
+                       double* rss_out, unsigned char* flags_out, double* filt_out);
+
 /* mat1d.construct_integrated_derivative_matrix (hybdrt/matrices/mat1d.py:125-209), orders 0,1,2 of the
  * Gaussian basis (closed forms basis.py:382-395).  toeplitz != 0: first column scattered (mat1d.py:158-168).
  * out: m0, m1, m2 each [n][n]                                                                        */

@@ -301,6 +301,10 @@ int hipdrt_debug_last_predict_ms(hipdrt_ctx* ctx, float* ms);
  * callbacks of the adaptive path included).                                                                                    */
 int hipdrt_debug_map_filter_stats(hipdrt_ctx* ctx, double* stats);
 
+/* Tools (tools/probe_map_badness.py): device time in ms, by HIP events between the upload and the download, of this context's
+ * last hipdrt_map_badness (its internal synchronisations included).                                                             */
+int hipdrt_debug_map_badness_ms(hipdrt_ctx* ctx, double* ms);
+
 #ifdef __cplusplus
 }
 #endif
