@@ -246,6 +246,14 @@ class MapBadnessArgs(C.Structure):
                 ("filt_in", _dp)]
 
 
+class MapPredictArgs(C.Structure):
+    """hipdrt_map_predict_args (include/hipdrt.h)"""
+    _fields_ = [("rows", C.c_int), ("nsup", C.c_int), ("neval", C.c_int), ("ln_tau_sup", _dp), ("ln_tau_eval", _dp),
+                ("epsilon", C.c_double), ("basis_area", C.c_double), ("normalize", C.c_int), ("x_filter", FilterTable * 2),
+                ("f_var", _dp), ("fxx_var", _dp), ("var_stored", C.c_int), ("ext", _ip), ("search", C.c_int), ("height", C.c_double),
+                ("prominence", C.c_double), ("spread", FilterTable), ("spread_factor", C.c_double)]
+
+
 # include_mask bits of hipdrt_plan_predict_response and hipdrt_plan_predict_z_model (HIPDRT_INCLUDE_*)
 INCLUDE_DRT, INCLUDE_OHMIC, INCLUDE_CAP, INCLUDE_DOP, INCLUDE_VZ_OFFSET, INCLUDE_BASELINE, INCLUDE_INDUCTANCE = 1, 2, 4, 8, 16, 32, 64
 INCLUDE_ALL = 127
@@ -280,6 +288,7 @@ SIGNATURES = {
     "hipdrt_rank_filter": [_vp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp],
     "hipdrt_percentiles": [_vp, _dp, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp],
     "hipdrt_map_badness": [_vp, C.POINTER(MapBadnessArgs), _dp, _dp, _dp, C.POINTER(C.c_ubyte), _dp],
+    "hipdrt_map_predict": [_vp, C.POINTER(MapPredictArgs), _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp],
     "hipdrt_penalty_matrices": [_vp, _dp, C.c_int, C.c_double, C.c_int, _dp, _dp, _dp],
     "hipdrt_eis_var_matrix": [_vp, _dp, C.c_int, C.c_double, C.c_double, C.c_int, _dp],
     "hipdrt_qp_batch": [_vp, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, C.POINTER(QpOpts), _dp, _ip, _dp, _ip],
@@ -828,6 +837,67 @@ class Context:
         _check(rc)
         if want_flags:
             res["flags"] = res["flags"].astype(bool)
+        return res
+
+    def map_predict(self, x, ln_tau_sup, ln_tau_eval=None, epsilon=1.0, basis_area=1.0, normalize=False, filter_tables=None,
+                    f_var=None, fxx_var=None, var_stored=False, ext=None, search=1, height=1e-3, prominence=5e-3, spread_table=None,
+                    spread_factor=1.0, want=("x",)):
+        """hipdrt_map_predict on the rows x (rows, nsup) of a map (hipdrt.mapping.predict states it in numpy).  filter_tables: None
+        or one full symmetric table per axis (psi, tau; None skips the axis); f_var / fxx_var (rows, neval): the caller's variances,
+        or with var_stored the raw stored ones, which take the clamp ext (rows, 2) and the filter; spread_table: the full tau table of
+        peak_spread_sigma.  want: any of x, f, fxx, f_var, fxx_var, peak_prob, curv_prob -> dict.  An evaluation grid beyond what
+        LDS holds raises NotImplementedError."""
+        names = ("x", "f", "fxx", "f_var", "fxx_var", "peak_prob", "curv_prob")
+        unknown = [w for w in want if w not in names]
+        if unknown:
+            raise ValueError(f"unknown outputs {unknown}")
+        x = _f64(x)
+        if x.ndim != 2:
+            raise ValueError("x: a 2-D array (rows, nsup)")
+        a = MapPredictArgs()
+        keep = []
+
+        def table(slot, full):
+            slot.radius = -1
+            if full is not None:
+                r = len(full) // 2
+                half = np.ascontiguousarray(np.asarray(full, dtype=np.float64)[r:])
+                keep.append(half)
+                slot.w, slot.radius = _p(half), r
+
+        a.rows, a.nsup = x.shape
+        lts = _f64(ln_tau_sup).ravel()
+        if lts.size != x.shape[1]:
+            raise ValueError("ln_tau_sup must have one entry per column of x")
+        lte = _f64(ln_tau_eval).ravel() if ln_tau_eval is not None else lts
+        a.neval, a.ln_tau_sup, a.ln_tau_eval = lte.size, _p(lts), _p(lte)
+        a.epsilon, a.basis_area, a.normalize = float(epsilon), float(basis_area), int(bool(normalize))
+        tabs = list(filter_tables) if filter_tables is not None else [None, None]
+        if len(tabs) != 2:
+            raise ValueError("filter_tables: one table per axis (psi, tau)")
+        for slot, full in zip(a.x_filter, tabs):
+            table(slot, full)
+        table(a.spread, spread_table)
+        a.spread_factor = float(spread_factor)
+        shape = (x.shape[0], lte.size)
+        if (f_var is None) != (fxx_var is None):
+            raise ValueError("f_var and fxx_var: both or none")
+        if f_var is not None:
+            f_var, fxx_var = _f64(f_var), _f64(fxx_var)
+            if f_var.shape != shape or fxx_var.shape != shape:
+                raise ValueError(f"f_var and fxx_var must have the shape {shape}")
+            a.f_var, a.fxx_var, a.var_stored = _p(f_var), _p(fxx_var), int(bool(var_stored))
+        if ext is not None:
+            ext = np.ascontiguousarray(ext, dtype=np.int32)
+            if ext.shape != (x.shape[0], 2):
+                raise ValueError("ext: (rows, 2)")
+            a.ext = _pi(ext)
+        a.search, a.height, a.prominence = int(search), float(height), float(prominence)
+        res = {w: np.empty(x.shape if w == "x" else shape) for w in names if w in want}
+        rc = self._lib.hipdrt_map_predict(self._h, C.byref(a), _p(x), *[_p(res.get(w)) for w in names])
+        if rc == E_UNSUPPORTED:
+            raise NotImplementedError(self._lib.hipdrt_last_error().decode())
+        _check(rc)
         return res
 
     def penalty_matrices(self, ln_tau, epsilon, toeplitz):

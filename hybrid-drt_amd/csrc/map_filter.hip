@@ -455,6 +455,25 @@ int masked_gaussian_device(hipStream_t st, const double* a, int R, int C, const 
     return HIPDRT_OK;
 }
 
+// map_filter_dev.hpp: scipy.ndimage.gaussian_filter(a, sigma, mode='reflect') on device buffers -- the same passes without a mask: a
+// NaN spreads over the window that holds it, as scipy spreads it.  Every output element is one accumulator summed in the symmetric
+// order of filter_pass_kernel, whatever the shape of the launch.
+int plain_gaussian_device(hipStream_t st, const double* a, int R, int C, const hipdrt_filter_table* tabs, double* out) {
+    MapFilter m;
+    m.st = st; m.g = nullptr;
+    m.R = R; m.C = C; m.nax = 2; m.phys[0] = 0; m.phys[1] = 1;
+    HIPDRT_REQUIRE(R >= 1 && C >= 1 && a != out, "plain filter: rows, cols >= 1 and distinct buffers");
+    HIPDRT_REQUIRE((C + TILE_C - 1) / TILE_C <= 65535, "at most 65535 * 64 entries along a row");
+    m.n = (size_t)R * C; m.bytes = m.n * sizeof(double);
+    const double one = 1.0;
+    TRY(upload(m.ident.buf, &one, sizeof(double), st)); m.ident.r = 0;
+    for (int l = 0; l < 2; ++l) TRY(m.upload_tab(m.gauss[l], tabs[l]));
+    if (m.gauss[0].r >= 0 && m.gauss[1].r >= 0) HIPDRT_CHECK(m.u0.alloc(m.bytes));      // the intermediate of two passes
+    TRY(m.run(m.table_steps(m.gauss), a, nullptr, PRE_NONE, out, nullptr, POST_NONE));
+    HIPDRT_CHECK(hipStreamSynchronize(st));          // the work buffers and `one` go out of scope
+    return HIPDRT_OK;
+}
+
 }  // namespace hipdrt
 
 using namespace hipdrt;

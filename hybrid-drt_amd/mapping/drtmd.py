@@ -239,8 +239,18 @@ def prefilter_observations(drt, observations, fit_kw):
     return [_as_observation(m) for m in meas], fit_kw, tags, step_times
 
 
+def eval_var_columns(drt, eval_var_tau, ok):
+    """what a store with store_eval_var keeps of the batch `drt` has just fitted: the raw (unclamped) variances of the DRT and of its
+    curvature on eval_var_tau (DRTMD.predict_drt_var's input, hybdrt/mapping/drtmd.py:980-991, 1012-1015), NaN rows for failed fits"""
+    cols = {}
+    for name, order in (('obs_f_var', 0), ('obs_fxx_var', 2)):
+        var, vok = drt.estimate_distribution_var_batch(tau=eval_var_tau, order=order)
+        cols[name] = np.where((np.asarray(vok, dtype=bool) & ok)[:, None], var, np.nan)
+    return cols
+
+
 def fit_observation_list(drt, observations, tau_supergrid, drt_var=False, ignore_errors=False, llh_kw=None, rss_kw=None,
-                         **fit_kw):
+                         eval_var_tau=None, **fit_kw):
     """DRTMD.fit_observations (drtmd.py:245-319) for ANY mix of observations, each given as DRTMD.add_observation takes it:
     (chrono_data, eis_data) with chrono_data = (times, i_signal, v_signal) or None and eis_data = (frequencies, z) or None.
     Observations are grouped by (data type, sampling grids) on the host (observation_groups); every group is ONE device
@@ -251,7 +261,12 @@ def fit_observation_list(drt, observations, tau_supergrid, drt_var=False, ignore
     tau_supergrid = np.asarray(tau_supergrid, dtype=float)
     num = len(observations)
     llh_kw, rss_kw = _metric_kw(llh_kw, rss_kw)
-    table = ObsTable(num, (len(tau_supergrid),), drt_var, GATHER_COLUMNS, groups=True)
+    columns = dict(GATHER_COLUMNS)
+    if eval_var_tau is not None:
+        columns.update(obs_f_var=(float, (len(eval_var_tau),)), obs_fxx_var=(float, (len(eval_var_tau),)))
+    table = ObsTable(num, (len(tau_supergrid),), drt_var, columns, groups=True)
+    if eval_var_tau is not None:
+        table.res['obs_f_var'][:], table.res['obs_fxx_var'][:] = np.nan, np.nan
     tags, step_times = None, [None] * num
     if fit_kw.get('remove_extremes') or fit_kw.get('remove_outliers'):
         observations, fit_kw, tags, step_times = prefilter_observations(drt, observations, fit_kw)
@@ -270,8 +285,11 @@ def fit_observation_list(drt, observations, tau_supergrid, drt_var=False, ignore
         span = _supergrid_slots(tau_supergrid, out['basis_tau'])
         llh, rss = drt.evaluate_obs_llh_rss_batch(llh_kw=llh_kw, rss_kw=rss_kw)
         var, vok = drt.estimate_distribution_var_batch(tau=tau_supergrid, extend_var=True) if drt_var else (None, None)
+        cols = {key: out[key] for key in GATHER_COLUMNS}
+        if eval_var_tau is not None:
+            cols.update(eval_var_columns(drt, eval_var_tau, np.asarray(out['status']) >= 0))
         table.scatter(idx, np.asarray(out['status']) >= 0, out['fit_x'], span, {key: out[key] for key in special_keys}, llh, rss,
-                      {key: out[key] for key in GATHER_COLUMNS}, var=var, vok=vok, group=(kind, out['basis_tau']))
+                      cols, var=var, vok=vok, group=(kind, out['basis_tau']))
     return table.result(ignore_errors)          # (a failed observation raises here, after every group was fitted)
 
 
@@ -357,7 +375,8 @@ def fit_observations_pfrt(drt, observations, tau_supergrid, pfrt_factors=None, d
 
 
 def fit_observations(drt, frequencies=None, z_obs=None, tau_supergrid=None, drt_var=False, ignore_errors=False, llh_kw=None,
-                     rss_kw=None, inflight=1, observations=None, fit_type='drt', pfrt_factors=None, max_batch=None, **fit_kw):
+                     rss_kw=None, inflight=1, observations=None, fit_type='drt', pfrt_factors=None, max_batch=None,
+                     eval_var_tau=None, **fit_kw):
     """Fit every observation and scatter the coefficients into supergrid slots like DRTMD.fit_observation does
     (drtmd.py:245-301): returns obs_x (B, len(supergrid)), obs_special dict, and the raw result dict, which also
     carries what the reference keeps per observation:
@@ -377,9 +396,14 @@ def fit_observations(drt, frequencies=None, z_obs=None, tau_supergrid=None, drt_
     in flight; 'auto' = auto_inflight(number of observations).  (Afterwards `drt` itself holds the first batch only.)
     A shared-grid map that does not fit the device at once is fitted as consecutive batches of nearly equal size through the same
     plan (``max_batch`` spectra at most; default max_batch_for(drt, frequencies): 80 % of the device's memory, about 47 000 spectra
-    of 256 x 512 on 288 GB) -- same results, same order."""
+    of 256 x 512 on 288 GB) -- same results, same order.
+    ``eval_var_tau`` (the list form and the plain shared-grid form): every device batch also leaves obs_f_var / obs_fxx_var
+    (num, len(eval_var_tau)), the raw variances of the DRT and of its curvature on that grid (eval_var_columns) -- what a store with
+    store_eval_var keeps for DRTMD.predict_drt_var; NaN rows for failed fits."""
     if fit_type not in ('drt', 'pfrt'):
         raise ValueError(f"Invalid fit_type {fit_type}. Options: ['drt', 'pfrt']")          # drtmd.py:1479-1482
+    if eval_var_tau is not None and (fit_type == 'pfrt' or (observations is None and (inflight != 1 or max_batch is not None))):
+        raise NotImplementedError('eval_var_tau goes with the observation-list form and the plain shared-grid form')
     if fit_type == 'pfrt':
         # DRTMD(fit_type='pfrt') (drtmd.py:98-100, 1338-1342): one solution per regularisation factor and observation
         if observations is None:
@@ -395,7 +419,7 @@ def fit_observations(drt, frequencies=None, z_obs=None, tau_supergrid=None, drt_
         if tau_supergrid is None:
             raise ValueError('a heterogeneous observation list needs tau_supergrid')
         return fit_observation_list(drt, observations, tau_supergrid, drt_var=drt_var, ignore_errors=ignore_errors,
-                                    llh_kw=llh_kw, rss_kw=rss_kw, **fit_kw)
+                                    llh_kw=llh_kw, rss_kw=rss_kw, eval_var_tau=eval_var_tau, **fit_kw)
     z_obs = np.asarray(z_obs)
     inflight = auto_inflight(z_obs.shape[0]) if inflight == 'auto' else int(inflight)
     if inflight > 1 and z_obs.shape[0] >= 2 * inflight:
@@ -430,6 +454,8 @@ def fit_observations(drt, frequencies=None, z_obs=None, tau_supergrid=None, drt_
         var, vok = drt.estimate_distribution_var_batch(tau=tau_supergrid, extend_var=True)
         vok = np.asarray(vok, dtype=bool) & ok
         res['obs_drt_var'], res['obs_drt_var_ok'] = zero_failed(vok, var), vok     # (failed fits keep zeros)
+    if eval_var_tau is not None:
+        res.update(eval_var_columns(drt, eval_var_tau, ok))
     return obs_x, obs_special, res
 
 
@@ -498,7 +524,7 @@ def _one_kernel(drt, members, saved=None):
 
 def fit_observations_sharded(drt, frequencies=None, z_obs=None, rank=None, world=None, tau_supergrid=None, scheme='interleave',
                              drt_var=False, dst=0, fit=fit_observations, inflight=1, observations=None, ignore_errors=False,
-                             reproducible=False, **fit_kw):
+                             reproducible=False, eval_var_tau=None, **fit_kw):
     """BASELINE configs[3]: the observations of one map sharded over the ranks of a node (one process per GPU), every
     rank fitting its share as device batches, the results gathered on rank `dst` with ONE collective per map (a gather).
     The lookup tables of rank `dst` are broadcast ONCE per DRT instance (share_lookup_tables: the first map of an instance
@@ -519,8 +545,11 @@ def fit_observations_sharded(drt, frequencies=None, z_obs=None, rank=None, world
     kernels): a map re-sharded over another number of ranks reproduces to that level, not bit for bit --
     unless ``reproducible=True``, which keeps every device batch of this call on the one-workgroup-per-problem kernel whatever
     its size (n <= 2048; small shares then fit slower, ~1.2 x for a single spectrum): the gathered map is then bit-identical
-    for every world size, shard scheme and `inflight`."""
+    for every world size, shard scheme and `inflight`.  ``eval_var_tau``: as in fit_observations; the gathered rows then carry
+    obs_f_var / obs_fxx_var as well (table.pack_rows)."""
     from . import dist as hd
+    if eval_var_tau is not None:
+        fit_kw = dict(fit_kw, eval_var_tau=eval_var_tau)
     if reproducible:
         if fit is not fit_observations:
             raise ValueError("reproducible=True pins the device kernel of mapping.fit_observations; it cannot do that for another `fit`")
@@ -585,7 +614,10 @@ def fit_observations_sharded(drt, frequencies=None, z_obs=None, rank=None, world
         return None
     if num == 0:
         raise ValueError('no observations')
-    table = ObsTable(num, (int(full[0, 0]),), drt_var, GATHER_COLUMNS)          # (nsup: the first block's header says it)
+    columns = dict(GATHER_COLUMNS)
+    if eval_var_tau is not None:
+        columns.update(obs_f_var=(float, (len(eval_var_tau),)), obs_fxx_var=(float, (len(eval_var_tau),)))
+    table = ObsTable(num, (int(full[0, 0]),), drt_var, columns)          # (nsup: the first block's header says it)
     for r, end in enumerate(np.cumsum(counts)):
         if counts[r]:
             table.scatter_rows(owned[r], full[end - counts[r]:end])

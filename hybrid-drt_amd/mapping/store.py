@@ -20,6 +20,11 @@ Fitted observations can be smoothed across psi and tau on the device: ``filter_o
 and fitted DRTs can be scored against their neighbours in psi: ``score_group_data_badness`` / ``score_group_fit_badness``
 (drtmd.py:642-783) write ``obs_data_badness`` / ``obs_fit_badness`` through mapping.nddata.score_rows.
 
+The fitted map is read through the prediction block (drtmd.py:788-1106): ``predict_x``, ``predict_r_p``, ``predict_drt``,
+``predict_drt_var``, ``predict_peak_prob`` and ``predict_curv_prob`` run csrc/map_predict.hip on the store's arrays (statement=True:
+mapping.predict, the same arithmetic in numpy).  The store keeps no fits and no covariances: with ``store_eval_var=True`` every
+device batch also leaves the raw variances of the DRT and of its curvature on get_tau_eval(10) in ``obs_f_var`` / ``obs_fxx_var``.
+
 Not here (out of scope): file readers, psi interpolation, resolve bookkeeping, pickling."""
 import warnings
 
@@ -27,6 +32,7 @@ import numpy as np
 
 from . import drtmd as _driver
 from . import nddata
+from . import predict as _predict
 from .ndx import filter_ndx
 from .resolve import get_tau_indices
 from .table import new_special, tau_slots
@@ -34,7 +40,7 @@ from .table import new_special, tau_slots
 
 class DRTMD:
     def __init__(self, tau_supergrid, drt=None, fit_kw=None, fit_type='drt', pfrt_factors=None, drt_var=True, llh_kw=None,
-                 rss_kw=None, psi_dim_names=None, **drt_kw):
+                 rss_kw=None, psi_dim_names=None, store_eval_var=False, **drt_kw):
         from ..models import DRT
         self.tau_supergrid = np.asarray(tau_supergrid, dtype=float)
         self.drt1d = drt if drt is not None else DRT(tau_supergrid=self.tau_supergrid, **drt_kw)      # drtmd.py:52-58
@@ -66,6 +72,14 @@ class DRTMD:
         self.obs_llh, self.obs_rss = np.zeros(0), np.zeros(0)
         self.obs_data_badness, self.obs_fit_badness = np.zeros(0), np.zeros(0)                   # drtmd.py:121-122
         self.last_fit_index = np.zeros(0, dtype=int)          # what the last fit_observations call sent to the device
+        # the raw (unclamped) variances of f and fxx on get_tau_eval(10), NaN until the observation is fitted; only on request: a
+        # store built without the keyword has neither attribute
+        self.store_eval_var = bool(store_eval_var)
+        if self.store_eval_var:
+            if fit_type == 'pfrt':
+                raise NotImplementedError("store_eval_var with fit_type='pfrt': one variance per factor is not built")
+            neval = len(self.get_tau_eval(_predict.DEFAULT_PPD))
+            self.obs_f_var, self.obs_fxx_var = np.zeros((0, neval)), np.zeros((0, neval))
 
     @property
     def num_obs(self):
@@ -96,6 +110,9 @@ class DRTMD:
             for key in self.obs_special:
                 val = self.obs_special[key]
                 self.obs_special[key] = np.concatenate([val, np.zeros((1,) + val.shape[1:])])
+        if self.store_eval_var:
+            nan_row = np.full((1, self.obs_f_var.shape[1]), np.nan)
+            self.obs_f_var, self.obs_fxx_var = np.concatenate([self.obs_f_var, nan_row]), np.concatenate([self.obs_fxx_var, nan_row])
         if fit:
             self.fit_observation(self.num_obs - 1)
 
@@ -111,10 +128,11 @@ class DRTMD:
         self.last_fit_index = idx
         if len(idx) == 0:
             return
+        eval_kw = dict(eval_var_tau=self.get_tau_eval(_predict.DEFAULT_PPD)) if self.store_eval_var else {}
         obs_x, obs_special, res = _driver.fit_observations(
             self.drt1d, observations=[self.obs_data[i] for i in idx], tau_supergrid=self.tau_supergrid, drt_var=self.drt_var,
             ignore_errors=True, llh_kw=self.llh_kw, rss_kw=self.rss_kw, fit_type=self.fit_type,
-            pfrt_factors=self.pfrt_factors if self.fit_type == 'pfrt' else None, **self.fit_kw)
+            pfrt_factors=self.pfrt_factors if self.fit_type == 'pfrt' else None, **eval_kw, **self.fit_kw)
         ok = np.asarray(res['obs_fit_status'], dtype=bool)
         first_bad = int(np.argmin(ok)) if not ok.all() else len(idx)
         # without ignore_errors the reference's loop stops at the first failure: what came before it is stored, the rest is not
@@ -126,6 +144,8 @@ class DRTMD:
             self.obs_llh[rows], self.obs_rss[rows] = res['obs_llh'][good], res['obs_rss'][good]
             if self.drt_var and 'obs_drt_var' in res:
                 self.obs_drt_var[rows] = res['obs_drt_var'][good]
+            if self.store_eval_var:
+                self.obs_f_var[rows], self.obs_fxx_var[rows] = res['obs_f_var'][good], res['obs_fxx_var'][good]
             if self.obs_special is None:                          # initialize_obs_special, drtmd.py:270-271
                 self.obs_special = {}
             for key, val in obs_special.items():
@@ -293,3 +313,207 @@ class DRTMD:
         ignore = self.obs_ignore_flag[obs_index] | ~self.obs_fit_status[obs_index]
         x_array[ignore] = np.nan
         self.obs_fit_badness[obs_index] = self._score_rows(statement, device)(x_array, median_size, std_size)
+
+    # ---- prediction (drtmd.py:788-1106) ----
+    def validate_psi(self, psi):
+        """drtmd.py:1168-1184"""
+        if self.psi_dim_names is not None:
+            psi_len = len(self.psi_dim_names)
+        elif self.obs_psi is not None:
+            psi_len = self.obs_psi.shape[1]
+        else:
+            psi_len = None
+        psi = np.atleast_2d(psi)
+        if psi_len is not None and psi_len != np.shape(psi)[1]:
+            raise ValueError(f'Dimensions of provided psi ({np.shape(psi)[1]}) do not match shape of existing psi array '
+                             f'({None if self.obs_psi is None else self.obs_psi.shape})')
+        return psi
+
+    def get_psi_index(self, psi):
+        """drtmd.py:1186-1188: the observation index of every row of psi (8 significant digits), -1 where it was not observed"""
+        psi = np.asarray(self.validate_psi(psi), dtype=float)
+        return _predict.row_match_index(self.obs_psi, psi, precision=8)
+
+    def get_tau_eval(self, ppd, extend_decades=0):
+        """drtmd.py:1252-1263"""
+        return _predict.tau_eval(self.tau_supergrid, ppd, extend_decades)
+
+    @property
+    def tau_basis_area(self):
+        """drtmd.py:1292-1293 (gaussian basis)"""
+        return float(np.sqrt(np.pi) / self.drt1d.tau_epsilon)
+
+    def _map_rows(self, psi, percentile=None, factor_index=None):
+        """the checks every prediction shares -> (observation indices, their coefficient rows with NaN rows for what is unfitted or
+        ignored)"""
+        if self.fit_type == 'pfrt':
+            raise NotImplementedError("fit_type='pfrt': the prediction block takes one DRT per observation (factor_index is not built)")
+        if percentile is not None:
+            raise NotImplementedError("percentile= needs the parameter covariances, which the store does not keep")
+        index = self.get_psi_index(psi)
+        if len(index) == 0 or np.min(index) < 0:
+            raise NotImplementedError("psi that is not an observed coordinate: resampling between observations is not built")
+        x = self.obs_x[index].copy()
+        x[self.obs_ignore_flag[index] | ~self.obs_fit_status[index]] = np.nan
+        return index, x
+
+    def _tables(self, ndfilter, filter_func, filter_kw):
+        """the device filter's tables (None: no filter, or a callable that the host applies)"""
+        return _predict.filter_tables(ndfilter and filter_func is None, filter_kw)
+
+    @staticmethod
+    def _host_filter(a, ndfilter, filter_func, filter_kw):
+        """apply_filter (_filters.py:506-518) with a callable: filter_func(a, **filter_kw), as upstream calls it"""
+        if ndfilter and filter_func is not None:
+            return filter_func(a, **filter_kw)
+        return a
+
+    def _map_predict(self, statement, device, x, tau, want, normalize=False, tables=None, f_var=None, fxx_var=None, var_stored=False,
+                     ext=None, search=1, height=1e-3, prominence=5e-3, peak_spread_sigma=None):
+        """one pass of the chain on rows x: the device call, or with statement=True the same stages in numpy"""
+        eps, area = self.drt1d.tau_epsilon, self.tau_basis_area
+        ln_sup, ln_ev = np.log(self.tau_supergrid), np.log(tau)
+        if not statement:
+            from .. import _ffi
+            spread = {}
+            if peak_spread_sigma is not None:
+                spread = dict(spread_table=_predict.gaussian_tables((peak_spread_sigma,))[0],
+                              spread_factor=_predict.spread_factor(peak_spread_sigma))
+            return _ffi.get_context(device).map_predict(x, ln_sup, ln_ev, eps, area, normalize, tables, f_var, fxx_var, var_stored, ext,
+                                                        search, height, prominence, want=want, **spread)
+        res = {}
+        xf = _predict.map_x_statement(x, area, normalize, tables)
+        res['x'] = xf
+        if any(w in want for w in ('f', 'fxx', 'peak_prob', 'curv_prob')):
+            res['f'], res['fxx'] = (_predict.map_drt_statement(xf, ln_sup, ln_ev, eps, o) for o in (0, 2))
+        if f_var is not None:
+            vf, vxx = np.array(f_var, dtype=float), np.array(fxx_var, dtype=float)
+            if var_stored:
+                if ext is not None:
+                    vf, vxx = _predict.clamp_rows(vf, ext), _predict.clamp_rows(vxx, ext)
+                vf, vxx = _predict.correlate_tables(vf, tables), _predict.correlate_tables(vxx, tables)
+            res['f_var'], res['fxx_var'] = vf, vxx
+            with np.errstate(invalid='ignore', divide='ignore'):
+                if 'peak_prob' in want:
+                    pk = _predict.peak_rows(res['f'], res['fxx'], vf, vxx, search, height, prominence)
+                    if peak_spread_sigma is not None:
+                        pk = _predict.spread_statement(pk, peak_spread_sigma)
+                    res['peak_prob'] = pk * np.sign(res['f'])
+                if 'curv_prob' in want:
+                    from ..models import peaks
+                    res['curv_prob'] = peaks.curv_prob_row(res['f'], res['fxx'], vf, vxx)
+        return {w: res[w] for w in want}
+
+    def predict_x(self, psi, factor_index=None, percentile=None, normalize=False, ndfilter=False, filter_func=None, resample_dims=None,
+                  filter_kw=None, statement=False, device=0):
+        """drtmd.py:797-835: the coefficient rows of the observations at psi, in the order of psi -- normalised by their absolute
+        R_p first, then filtered.  filter_func=None filters on the device: gaussian_filter(sigma=(1, 0)) with no filter_kw, else
+        filter_kw={'sigma': ...}; a callable is applied on the host as apply_filter applies it.  Rows of unfitted or ignored
+        observations are NaN (and spread through a psi filter as scipy spreads them)."""
+        _, x = self._map_rows(psi, percentile, factor_index)
+        tables = self._tables(ndfilter, filter_func, filter_kw)
+        if normalize or tables is not None:
+            x = self._map_predict(statement, device, x, self.tau_supergrid, ('x',), normalize=normalize, tables=tables)['x']
+        return self._host_filter(x, ndfilter, filter_func, filter_kw)
+
+    def predict_r_p(self, psi=None, x=None, factor_index=None, absolute=False, **kw):
+        """drtmd.py:788-795"""
+        if x is None:
+            x = self.predict_x(psi, factor_index=factor_index, **kw)
+        if absolute:
+            x = np.abs(x)
+        return np.sum(x, axis=-1) * self.tau_basis_area
+
+    def predict_drt(self, psi=None, tau=None, x=None, order=0, factor_index=None, normalize=False, statement=False, device=0, **kw):
+        """drtmd.py:837-851: x E' on tau (None: the supergrid) for order 0 or 2 (statement=True: any order); normalize divides the
+        filtered x by its absolute R_p"""
+        if x is None:
+            x = self.predict_x(psi, factor_index=factor_index, normalize=False, statement=statement, device=device, **kw)
+        tau = self.tau_supergrid if tau is None else np.asarray(tau, dtype=float)
+        if statement:
+            xn = _predict.map_x_statement(x, self.tau_basis_area, normalize)
+            return _predict.map_drt_statement(xn, np.log(self.tau_supergrid), np.log(tau), self.drt1d.tau_epsilon, order)
+        if order not in (0, 2):
+            raise NotImplementedError("the device chain evaluates orders 0 and 2; pass statement=True for order 1")
+        name = 'f' if order == 0 else 'fxx'
+        return self._map_predict(False, device, np.asarray(x, dtype=float), tau, (name,), normalize=normalize)[name]
+
+    def _stored_var(self, obs_index, tau, order):
+        if not self.store_eval_var:
+            raise NotImplementedError("the store keeps no covariances: build it with store_eval_var=True to keep the variances of "
+                                      "every fit on get_tau_eval(10)")
+        stored = self.get_tau_eval(_predict.DEFAULT_PPD)
+        if tau is not None and not (np.shape(tau) == stored.shape and np.array_equal(np.asarray(tau, dtype=float), stored)):
+            raise NotImplementedError("the variances are stored on get_tau_eval(10) only: another grid needs the covariances")
+        if order not in (0, 2):
+            raise NotImplementedError("the variances are stored for orders 0 and 2 only")
+        obs_index = np.atleast_1d(np.asarray(obs_index, dtype=int))
+        return obs_index, stored, (self.obs_f_var if order == 0 else self.obs_fxx_var)[obs_index]
+
+    def predict_drt_var(self, obs_index, tau=None, x_cov=None, order=0, factor_index=None, extend_var=True, ndfilter=False,
+                        filter_func=None, filter_kw=None, statement=False, device=0):
+        """drtmd.py:1012-1021 from the stored rows (store_eval_var=True): the variance of the DRT (order 0) or of its curvature
+        (order 2) on get_tau_eval(10) -- tau=None means that grid here -- with the map clamp (extend_var) and the filter"""
+        if x_cov is not None:
+            raise NotImplementedError("x_cov=: the device chain starts from the stored variance rows, not from covariances")
+        if self.fit_type == 'pfrt':
+            raise NotImplementedError("fit_type='pfrt': the prediction block takes one DRT per observation")
+        obs_index, tau, var = self._stored_var(obs_index, tau, order)
+        ext = _predict.clamp_index_rows(tau, self.tau_supergrid, [self.obs_tau_indices[i] for i in obs_index]) if extend_var else None
+        tables = self._tables(ndfilter, filter_func, filter_kw)
+        if ext is not None or tables is not None:
+            var = self._map_predict(statement, device, self.obs_x[obs_index], tau, ('f_var',), tables=tables, f_var=var, fxx_var=var,
+                                    var_stored=True, ext=ext)['f_var']
+        return self._host_filter(var, ndfilter, filter_func, filter_kw)
+
+    def _prob_map(self, which, psi, x, f_var, fxx_var, tau, factor_index, extend_var, ndfilter, filter_func, filter_kw, normalize,
+                  statement, device, **peak_kw):
+        tau = self.get_tau_eval(_predict.DEFAULT_PPD) if tau is None else np.asarray(tau, dtype=float)
+        if self.fit_type == 'pfrt':
+            raise NotImplementedError("fit_type='pfrt': the prediction block takes one DRT per observation")
+        if x is None and f_var is None and fxx_var is None and filter_func is None:
+            # everything comes from the store: one upload, one download
+            index, xr = self._map_rows(psi, None, factor_index)
+            _, tau, vf = self._stored_var(index, tau, 0)
+            vxx = self.obs_fxx_var[index]
+            ext = _predict.clamp_index_rows(tau, self.tau_supergrid, [self.obs_tau_indices[i] for i in index]) if extend_var else None
+            return self._map_predict(statement, device, xr, tau, (which,), normalize=normalize, tables=self._tables(ndfilter, None, filter_kw),
+                                     f_var=vf, fxx_var=vxx, var_stored=True, ext=ext, **peak_kw)[which]
+        filt = dict(ndfilter=ndfilter, filter_func=filter_func, filter_kw=filter_kw, statement=statement, device=device)
+        if x is None:
+            x = self.predict_x(psi, factor_index=factor_index, normalize=normalize, **filt)
+        if f_var is None or fxx_var is None:
+            index = self.get_psi_index(psi)
+            if f_var is None:
+                f_var = self.predict_drt_var(index, tau=tau, order=0, factor_index=factor_index, extend_var=extend_var, **filt)
+            if fxx_var is None:
+                fxx_var = self.predict_drt_var(index, tau=tau, order=2, factor_index=factor_index, extend_var=extend_var, **filt)
+        return self._map_predict(statement, device, np.asarray(x, dtype=float), tau, (which,), f_var=f_var, fxx_var=fxx_var,
+                                 **peak_kw)[which]
+
+    def predict_peak_prob(self, psi, x=None, f_var=None, fxx_var=None, tau=None, factor_index=None, extend_var=True, prominence=5e-3,
+                          height=1e-3, peak_spread_sigma=None, ndfilter=False, filter_func=None, filter_kw=None, sign=1,
+                          statement=False, device=0):
+        """drtmd.py:1023-1064: the signed probability of a peak at every point of tau (None: get_tau_eval(10)) for the observations
+        at psi.  x is normalised and filtered, the variances are not divided by r_p^2; f_var / fxx_var passed here are used as given
+        (neither clamped nor filtered), otherwise the stored rows are taken (store_eval_var=True) with the map clamp and the filter."""
+        peak_kw = dict(search=_predict.search_kind(self.fit_kw['nonneg'], sign), height=height, prominence=prominence,
+                       peak_spread_sigma=peak_spread_sigma)
+        return self._prob_map('peak_prob', psi, x, f_var, fxx_var, tau, factor_index, extend_var, ndfilter, filter_func, filter_kw,
+                              True, statement, device, **peak_kw)
+
+    def predict_curv_prob(self, psi=None, x=None, f_var=None, fxx_var=None, tau=None, factor_index=None, extend_var=True,
+                          ndfilter=False, filter_func=None, filter_kw=None, statement=False, device=0):
+        """drtmd.py:1066-1106: the signed probability that the curvature is negative where f is positive (x unnormalised)"""
+        if psi is None and (x is None or f_var is None or fxx_var is None):
+            raise ValueError('If psi is not provided, all of x, f_var, and fxx_var must be provided')
+        return self._prob_map('curv_prob', psi, x, f_var, fxx_var, tau, factor_index, extend_var, ndfilter, filter_func, filter_kw,
+                              False, statement, device)
+
+    def predict_dop(self, *args, **kw):
+        raise NotImplementedError("predict_dop: the store keeps no distribution of phasances (upstream marks its x as a TODO)")
+
+    def predict_param_cov(self, *args, **kw):
+        raise NotImplementedError("predict_param_cov: the store keeps no fits and no covariances")
+
+    predict_x_cov = predict_x_var = predict_drt_cov = predict_param_cov

@@ -109,7 +109,9 @@ def pack_rows(obs_x, obs_special, res, drt_var):
     """One rank's results as rows of doubles behind ONE header row that describes them, so that `dst` can unpack blocks from
     ranks whose fits reported other special parameters (or none at all) without a second collective:
         header = [nsup, drt_var, n_specials, (registry index, width, ndim) x n_specials, 0 ...]
-        row    = [obs_x (nsup) | specials at their real widths | GATHER_KEYS | left, right | obs_drt_var (nsup), ok]"""
+        row    = [obs_x (nsup) | specials at their real widths | GATHER_KEYS | left, right | obs_drt_var (nsup), ok]
+    A result that carries obs_f_var / obs_fxx_var (fit_observations(eval_var_tau=)) adds 2 to the header's drt_var entry, their
+    width after the last special's triple and the two blocks at the end of the row; without them nothing changes."""
     num, nsup = obs_x.shape
     unknown = [k for k in obs_special if k not in SPECIAL_REGISTRY]
     if unknown:
@@ -127,6 +129,10 @@ def pack_rows(obs_x, obs_special, res, drt_var):
     cols.append(tau_slots(res.get('obs_tau_indices', (0, nsup)), num).astype(float))
     if drt_var:
         cols += [res['obs_drt_var'], np.asarray(res['obs_drt_var_ok'], dtype=float)[:, None]]
+    if res.get('obs_f_var') is not None:
+        head[1] += 2.0
+        head.append(float(res['obs_f_var'].shape[1]))
+        cols += [res['obs_f_var'], res['obs_fxx_var']]
     body = np.concatenate(cols, axis=1)
     width = max(body.shape[1], len(head))
     packed = np.zeros((num + 1, width))
@@ -138,7 +144,7 @@ def pack_rows(obs_x, obs_special, res, drt_var):
 def unpack_block(block):
     """inverse of pack_rows for one rank's block (header row first): (obs_x, {special: (2-d array, ndim of the original)}, {key: column}, ti, var, vok)"""
     head, body = block[0], block[1:]
-    nsup, drt_var, nsp = int(head[0]), bool(head[1]), int(head[2])
+    nsup, drt_var, eval_var, nsp = int(head[0]), bool(int(head[1]) & 1), bool(int(head[1]) & 2), int(head[2])
     obs_x = body[:, :nsup]
     pos = nsup
     special = {}
@@ -153,6 +159,10 @@ def unpack_block(block):
     var = vok = None
     if drt_var:
         var, vok = body[:, pos:pos + nsup], body[:, pos + nsup] > 0.5
+        pos += nsup + 1
+    if eval_var:                                   # (two more columns of the table: they travel with `cols`)
+        neval = int(head[3 + 3 * nsp])
+        cols['obs_f_var'], cols['obs_fxx_var'] = body[:, pos:pos + neval], body[:, pos + neval:pos + 2 * neval]
     return obs_x, special, cols, ti, var, vok
 
 

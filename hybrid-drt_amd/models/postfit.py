@@ -799,20 +799,21 @@ class PostFitMixin:
             return np.hstack([bm, -bm])
         raise ValueError('sign must be 1, -1 or 0')
 
-    def _cov_rows(self, tau, ppd, sign):
-        """(tau as an array, the order-0 evaluation rows of a covariance estimate on it)"""
+    def _cov_rows(self, tau, ppd, sign, order=0):
+        """(tau as an array, the evaluation rows (order 0 unless asked otherwise) of a covariance estimate on it)"""
         tau = np.asarray(self.get_tau_eval(ppd) if tau is None else tau, dtype=float)
-        bm = basis.construct_func_eval_matrix(np.log(self.basis_tau), np.log(tau), self.tau_basis_type, epsilon=self.tau_epsilon, order=0)
+        bm = basis.construct_func_eval_matrix(np.log(self.basis_tau), np.log(tau), self.tau_basis_type, epsilon=self.tau_epsilon, order=order)
         return tau, self._signed_basis(bm, sign)
 
-    def estimate_distribution_var_batch(self, tau=None, ppd=20, extend_var=False, sign=1):
-        """Diagonal of DRT.estimate_distribution_cov (drt1d.py:3063-3151; order 0, no normalisation) for every
+    def estimate_distribution_var_batch(self, tau=None, ppd=20, extend_var=False, sign=1, order=0):
+        """Diagonal of DRT.estimate_distribution_cov (drt1d.py:3063-3151; no normalisation) for every
         spectrum of the last fitted batch: diag(B P^-1 B') coefficient_scale^2, computed on the device from the
         Cholesky factor of each final P.  Returns (var (B, len(tau)), ok (B,) bool); ``extend_var`` applies the
-        reference's clamp outside the measured tau range (drt1d.py:3126-3143)."""
+        reference's clamp outside the measured tau range (drt1d.py:3126-3143).  ``order``: the derivative of the basis the rows
+        evaluate (0: the DRT; 2: its curvature, the fxx variance of DRTMD.predict_drt_var, hybdrt/mapping/drtmd.py:980-991)."""
         self._need_cov_fit()
         prepared = isinstance(self._plan, _ffi.PreparedPlan)
-        tau, bm = self._cov_rows(tau, ppd, sign)
+        tau, bm = self._cov_rows(tau, ppd, sign, order)
         var, status = self._plan.distribution_var(bm, self._plan.batch if prepared else self._last_batch)
         if prepared:     # the device loop of a prepared plan runs at unit scale: estimate_param_cov's coefficient_scale^2 is applied here
             var = var * self._member_scales()[:, None] ** 2

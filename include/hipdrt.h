@@ -247,6 +247,43 @@ typedef struct {
 int hipdrt_map_badness(hipdrt_ctx* ctx, const hipdrt_map_badness_args* args, const double* a, const double* scale_src,
                        double* rss_out, unsigned char* flags_out, double* filt_out);
 
+/* The prediction block of a DRTMD map (hybdrt/mapping/drtmd.py: predict_x 815-833, predict_drt 848-851, the clamp of
+ * predict_drt_cov 993-1008 and the filter of predict_drt_var 1017-1019 on rows that already are diag(B x_cov B'),
+ * predict_peak_prob 1023-1064 with curvature.peak_prob_1d (hybdrt/mapping/curvature.py:12-58), predict_curv_prob 1066-1106) on
+ * the rows x[rows][nsup] of a map, between one upload and one download:
+ *   x        normalize: x / (sum_j |x_j| basis_area) by row, first; then x_filter -- scipy.ndimage.gaussian_filter with 'reflect'
+ *            along psi (axis 0, the rows) and / or tau (axis 1), a plain correlation: a NaN row spreads to its neighbours
+ *   f, fxx   x E0', x E2' with the order-0 and order-2 evaluation matrices of hipdrt_func_eval_matrix
+ *   f_var, fxx_var   var_stored = 0: used as given.  var_stored = 1 (stored raw variances): the map clamp with the row's ext = (li,
+ *            ri) -- v[:li] = max(v[:li], v[li]), then v[ri:] = max(v[ri:], v[ri]); li < 0 or a NaN in the row: left alone -- and
+ *            then x_filter
+ *   peaks    search = 1 / -1: one pass on -search fxx; 0: the passes -1 and +1, each keeping peaks with pass * f > 0.  The
+ *            probability at a peak is min(P(min(prominence, height) > 0), P(|f| > 0)), zero elsewhere; spread.radius >= 0: that row
+ *            correlated along tau with the spread table, times spread_factor; then times sign(f)
+ * Sums run in a fixed order per output element and without atomics: a row's results depend on its position in the map only
+ * through the psi filter's window.  A row of x that is all NaN gives NaN rows.  neval is limited by the LDS the four staged rows of
+ * a map row take (52 bytes per evaluation point): HIPDRT_E_UNSUPPORTED beyond that, with the limit in the message. */
+typedef struct {
+    int rows, nsup, neval;
+    const double* ln_tau_sup;           /* [nsup] natural log of the supergrid  */
+    const double* ln_tau_eval;          /* [neval] natural log of the evaluation grid */
+    double epsilon, basis_area;
+    int normalize;
+    hipdrt_filter_table x_filter[2];    /* psi axis, tau axis; radius < 0 skips */
+    const double* f_var;                /* optional [rows][neval]; both or none */
+    const double* fxx_var;
+    int var_stored;
+    const int* ext;                     /* var_stored = 1: optional [rows][2], (li, ri) on the evaluation grid or (-1, -1) */
+    int search;
+    double height, prominence;
+    hipdrt_filter_table spread;         /* radius < 0: no spread */
+    double spread_factor;
+} hipdrt_map_predict_args;
+/* every output is optional: x_out[rows][nsup] the normalised and filtered x; f, fxx [rows][neval]; f_var_out, fxx_var_out
+ * [rows][neval] the variances as they enter the square root; peak_prob, curv_prob [rows][neval] (both need the variances) */
+int hipdrt_map_predict(hipdrt_ctx* ctx, const hipdrt_map_predict_args* args, const double* x, double* x_out, double* f,
+                       double* fxx, double* f_var_out, double* fxx_var_out, double* peak_prob, double* curv_prob);
+
 /* mat1d.construct_integrated_derivative_matrix (hybdrt/matrices/mat1d.py:125-209), orders 0,1,2 of the
  * Gaussian basis (closed forms basis.py:382-395).  toeplitz != 0: first column scattered (mat1d.py:158-168).
  * out: m0, m1, m2 each [n][n]                                                                        */
