@@ -345,6 +345,10 @@ SIGNATURES = {
     "hipdrt_debug_last_predict_ms": [_vp, C.POINTER(C.c_float)],
     "hipdrt_debug_map_filter_stats": [_vp, _dp],
     "hipdrt_debug_map_badness_ms": [_vp, _dp],
+    "hipdrt_debug_map_gaussian": [_vp, _dp, C.c_int, C.c_int, C.POINTER(FilterTable), C.c_int, _dp],
+    "hipdrt_debug_map_reduce": [_vp, _dp, C.c_longlong, C.c_int, _dp],
+    "hipdrt_debug_map_prob": [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _ip, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                              _dp, _dp, _dp, _dp],
     "hipdrt_debug_apply_rows": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp],
     "hipdrt_comm_unique_id": [C.c_char_p],
     "hipdrt_comm_create": [C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(_vp)],
@@ -1426,6 +1430,59 @@ class Context:
         order = np.full(iters.size, -7, dtype=np.int32)
         _check(self._lib.hipdrt_debug_lpt_order(self._h, iters.size, _pi(iters), _pi(act), _pi(order)))
         return order
+
+    def debug_map_gaussian(self, a, tables, masked=False):
+        """tests: plain_gaussian_device / masked_gaussian_device (csrc/map_filter.hip) on a 2-D host array
+        (hipdrt_debug_map_gaussian, include/hipdrt_debug.h); tables: one full symmetric table per axis, None skips the axis;
+        masked: the NaNs of `a` are the mask.  Entries no kernel wrote come back as -7e77."""
+        a = _f64(a)
+        if a.ndim != 2 or len(tables) != 2:
+            raise ValueError("a 2-D array and one table (or None) per axis")
+        tabs, keep = (FilterTable * 2)(), []
+        for slot, full in zip(tabs, tables):
+            slot.radius = -1
+            if full is not None:
+                r = len(full) // 2
+                keep.append(np.ascontiguousarray(np.asarray(full, dtype=np.float64)[r:]))
+                slot.w, slot.radius = _p(keep[-1]), r
+        out = np.full(a.shape, -7.0e77)
+        _check(self._lib.hipdrt_debug_map_gaussian(self._h, _p(a), a.shape[0], a.shape[1], tabs, int(bool(masked)), _p(out)))
+        return out
+
+    def debug_map_reduce(self, x, mode):
+        """tests: the fixed-order reductions of csrc/map_filter.hip alone (hipdrt_debug_map_reduce) on a host vector ->
+        mode 0: (mean, 0), 1: (np.std, the mean it was taken about), 2: (min, max)"""
+        x = _f64(x).ravel()
+        out = np.full(2, -7.0e77)
+        _check(self._lib.hipdrt_debug_map_reduce(self._h, _p(x), x.size, int(mode), _p(out)))
+        return float(out[0]), float(out[1])
+
+    def debug_map_prob(self, f, fxx, f_var, fxx_var, ext=None, clamp_first=False, search=1, height=1e-3, prominence=5e-3,
+                       sign_now=True, want=("pk", "curv", "f_var", "fxx_var")):
+        """tests: clamp_kernel and / or map_prob_kernel (csrc/map_predict.hip) as stage 3 of hipdrt_map_predict launches them, on
+        host rows (rows, n) (hipdrt_debug_map_prob, include/hipdrt_debug.h) -> dict of the rows in `want`; entries no kernel wrote
+        come back as -7e77.  A grid beyond what LDS holds raises NotImplementedError, as Context.map_predict does."""
+        names = ("pk", "curv", "f_var", "fxx_var")
+        unknown = [w for w in want if w not in names]
+        if unknown:
+            raise ValueError(f"unknown outputs {unknown}")
+        f_var, fxx_var = _f64(f_var), _f64(fxx_var)
+        shape = f_var.shape
+        f, fxx = (None if r is None else _f64(r) for r in (f, fxx))
+        if len(shape) != 2 or any(r is not None and r.shape != shape for r in (f, fxx, fxx_var)):
+            raise ValueError("f, fxx, f_var, fxx_var: 2-D arrays of one shape (rows, n)")
+        if ext is not None:
+            ext = np.ascontiguousarray(ext, dtype=np.int32)
+            if ext.shape != (shape[0], 2):
+                raise ValueError("ext: (rows, 2)")
+        res = {w: np.full(shape, -7.0e77) for w in names if w in want}
+        rc = self._lib.hipdrt_debug_map_prob(self._h, shape[0], shape[1], _p(f), _p(fxx), _p(f_var), _p(fxx_var), _pi(ext),
+                                             int(bool(clamp_first)), int(search), float(height), float(prominence),
+                                             int(bool(sign_now)), *[_p(res.get(w)) for w in names])
+        if rc == E_UNSUPPORTED:
+            raise NotImplementedError(self._lib.hipdrt_last_error().decode())
+        _check(rc)
+        return res
 
     def debug_candidate_form(self, form):
         """tests: how candidate scoring on this context keeps rm x between its two products: 0 LDS, 1 scratch, -1 automatic"""

@@ -1,89 +1,12 @@
 // Test and diagnostic hooks of include/hipdrt_debug.h: context switches, and single launchers run on host arrays exactly as
-// the fit loop runs them.  (hipdrt_debug_stream_pool sits with the pool in api.hip.)
+// the fit loop runs them.  (hipdrt_debug_stream_pool sits with the pool in api.hip; hipdrt_debug_map_gaussian, _map_reduce and
+// _map_prob sit in map_filter.hip and map_predict.hip, next to kernels no other file can name.  debug_guard.hpp holds the bordered
+// device arrays all of them use.)
 #include <cmath>
 #include <cstring>
 
+#include "debug_guard.hpp"
 #include "plan.hpp"
-
-namespace {
-struct Guarded {
-    static constexpr size_t G = 128;           // border bytes on either side
-    static constexpr unsigned char MARK = 0xA5;
-    DevBuf buf;
-    void* host = nullptr;
-    size_t bytes = 0;
-    const char* name = "";
-    std::vector<unsigned char> stage;
-    int up(const char* what, void* h, size_t nbytes, hipStream_t st) {
-        name = what; host = h; bytes = nbytes;
-        stage.assign(nbytes + 2 * G, MARK);
-        if (h) std::memcpy(stage.data() + G, h, nbytes);
-        HIPDRT_CHECK(buf.alloc(stage.size()));
-        HIPDRT_CHECK(hipMemcpyAsync(buf.p, stage.data(), stage.size(), hipMemcpyHostToDevice, st));
-        return 0;
-    }
-    double* dd() const { return reinterpret_cast<double*>(static_cast<unsigned char*>(buf.p) + G); }
-    int fetch(hipStream_t st) { HIPDRT_CHECK(hipMemcpyAsync(stage.data(), buf.p, stage.size(), hipMemcpyDeviceToHost, st)); return 0; }
-    int check() {
-        for (size_t i = 0; i < G; ++i)
-            if (stage[i] != MARK || stage[G + bytes + i] != MARK) {
-                set_error(std::string("the kernel under test wrote outside ") + name);
-                return HIPDRT_E_NUMERIC;
-            }
-        if (host) std::memcpy(host, stage.data() + G, bytes);
-        return 0;
-    }
-};
-// The guarded outputs of one hook, as DevOuts (plan.hpp) holds the plain ones of an entry point: one want() per output, one
-// back() after the launch that fetches every array and then checks every border.
-struct GuardedOuts {
-    static constexpr int MAX = 17;         // hipdrt_debug_hyper_step has 17
-    Guarded g[MAX];
-    int n = 0;
-    template <class T>
-    int want(const char* name, T* host, size_t count, T*& field, hipStream_t st) {
-        if (!host) return 0;
-        HIPDRT_REQUIRE(n < MAX, "internal: more outputs than GuardedOuts holds");
-        TRY(g[n].up(name, host, count * sizeof(T), st));
-        field = reinterpret_cast<T*>(g[n++].dd());
-        return 0;
-    }
-    int back(hipStream_t st) {
-        for (int i = 0; i < n; ++i) TRY(g[i].fetch(st));
-        HIPDRT_CHECK(hipStreamSynchronize(st));
-        for (int i = 0; i < n; ++i) TRY(g[i].check());
-        return 0;
-    }
-};
-// `count` blocks of `blk` doubles, each between two borders of marker bytes: [border][block 0][border][block 1] ... [border].  The
-// kernels take the distance between blocks as a stride, so the borders need nothing from them.
-struct GuardedBlocks {
-    static constexpr size_t GD = Guarded::G / sizeof(double);
-    DevBuf buf;
-    size_t blk = 0, count = 0;
-    int alloc(size_t block_doubles, size_t blocks, hipStream_t st) {
-        blk = block_doubles; count = blocks;
-        HIPDRT_CHECK(buf.alloc((count + 1) * stride() * sizeof(double)));
-        HIPDRT_CHECK(hipMemsetAsync(buf.p, Guarded::MARK, buf.bytes, st));
-        return 0;
-    }
-    size_t stride() const { return blk + GD; }
-    double* first() const { return buf.d() + GD; }
-    // the count + 1 borders alone come back (the blocks may be tens of megabytes)
-    int check(const char* what, hipStream_t st) {
-        std::vector<unsigned char> h((count + 1) * Guarded::G);
-        HIPDRT_CHECK(hipMemcpy2DAsync(h.data(), Guarded::G, buf.p, stride() * sizeof(double), Guarded::G, count + 1,
-                                      hipMemcpyDeviceToHost, st));
-        HIPDRT_CHECK(hipStreamSynchronize(st));
-        for (size_t i = 0; i < h.size(); ++i)
-            if (h[i] != Guarded::MARK) {
-                set_error(std::string("the kernel under test wrote outside ") + what + " (border " + std::to_string(i / Guarded::G) + ")");
-                return HIPDRT_E_NUMERIC;
-            }
-        return 0;
-    }
-};
-}  // namespace
 
 extern "C" {
 

@@ -16,6 +16,8 @@
 #include <cmath>
 #include <memory>
 
+#include "debug_guard.hpp"
+#include "map_filter_dev.hpp"
 #include "plan.hpp"
 
 namespace hipdrt {
@@ -564,5 +566,55 @@ extern "C" int hipdrt_map_filter(hipdrt_ctx* ctx, const hipdrt_map_filter_args* 
 extern "C" int hipdrt_debug_map_filter_stats(hipdrt_ctx* ctx, double* stats) try {
     HIPDRT_REQUIRE(ctx && stats, "NULL pointer");
     for (int k = 0; k < 3; ++k) stats[k] = ctx->map_filter_stats[k];
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+// test hook (include/hipdrt_debug.h): plain_gaussian_device / masked_gaussian_device as map_rank.hip and map_predict.hip call them,
+// on a host array; input and output between borders of marker bytes
+extern "C" int hipdrt_debug_map_gaussian(hipdrt_ctx* ctx, const double* a, int R, int C, const hipdrt_filter_table* tabs, int masked,
+                                         double* out) try {
+    HIPDRT_REQUIRE(ctx && a && tabs && out, "NULL pointer");
+    HIPDRT_REQUIRE(R >= 1 && C >= 1 && (long long)R * C < (1LL << 30), "rows, cols >= 1, rows * cols < 2^30");
+    HIPDRT_REQUIRE(masked == 0 || masked == 1, "masked: 0 or 1");
+    for (int l = 0; l < 2; ++l)
+        HIPDRT_REQUIRE(tabs[l].radius < 0 || (tabs[l].w && tabs[l].radius < (1 << 20)), "a table with 0 <= radius < 2^20 needs its weights");
+    hipStream_t st; TRY(enter(ctx, &st));
+    const size_t n = (size_t)R * C;
+    GuardedOuts g;
+    const double* din = nullptr;
+    double* dout = nullptr;
+    TRY(g.in("a", a, n, din, st));
+    TRY(g.want("out", out, n, dout, st));
+    TRY(masked ? masked_gaussian_device(st, din, R, C, tabs, dout) : plain_gaussian_device(st, din, R, C, tabs, dout));
+    return g.back(st);
+} HIPDRT_CATCH
+
+// test hook (include/hipdrt_debug.h): MapFilter::reduce / std_of alone on a host vector; x, the partials and the scalars between
+// borders of marker bytes
+extern "C" int hipdrt_debug_map_reduce(hipdrt_ctx* ctx, const double* x, long long n, int mode, double* out) try {
+    HIPDRT_REQUIRE(ctx && x && out, "NULL pointer");
+    HIPDRT_REQUIRE(n >= 1 && n < (1LL << 30), "1 <= n < 2^30");
+    HIPDRT_REQUIRE(mode >= 0 && mode <= 2, "mode: 0 (mean), 1 (std and mean), 2 (min and max)");
+    hipStream_t st; TRY(enter(ctx, &st));
+    MapFilter m;
+    m.st = st; m.g = nullptr;
+    m.R = 1; m.C = (int)n; m.nax = 1; m.phys[0] = 1; m.phys[1] = 1;
+    m.n = (size_t)n; m.bytes = m.n * sizeof(double);
+    Guarded gx, gpart, gscal;
+    std::vector<double> hscal(8, 0.0);
+    TRY(gx.up_in("x", x, m.bytes, st));
+    TRY(gpart.up_in("partial", nullptr, 2 * MapFilter::G * sizeof(double), st));
+    TRY(gscal.up("scal", hscal.data(), hscal.size() * sizeof(double), st));
+    m.partial.alias(gpart.buf, Guarded::G, gpart.bytes);
+    m.scal.alias(gscal.buf, Guarded::G, gscal.bytes);
+    if (mode == 0) TRY(m.reduce(gx.dd(), RED_SUM, nullptr, m.scal.d() + 1));
+    else if (mode == 1) TRY(m.std_of(gx.dd(), 0));
+    else TRY(m.reduce(gx.dd(), RED_MINMAX, nullptr, m.scal.d() + 4));
+    for (Guarded* g : {&gx, &gpart, &gscal}) TRY(g->fetch(st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    for (Guarded* g : {&gx, &gpart, &gscal}) TRY(g->check());
+    if (mode == 0) { out[0] = hscal[1]; out[1] = 0.0; }
+    else if (mode == 1) { out[0] = hscal[0]; out[1] = hscal[1]; }
+    else { out[0] = hscal[4]; out[1] = hscal[5]; }
     return HIPDRT_OK;
 } HIPDRT_CATCH

@@ -19,7 +19,9 @@
 // No atomics; nothing depends on where a row sits in the launch except through the psi filter's window.  Compiled with
 // -ffp-contract=off: every product and sum rounds as numpy's does.
 #include <cmath>
+#include <cstring>
 
+#include "debug_guard.hpp"
 #include "map_filter_dev.hpp"
 #include "peaks_dev.hpp"
 
@@ -135,6 +137,41 @@ __global__ __launch_bounds__(256) void spread_sign_kernel(size_t n, const double
     if (i < n) out[i] = (pk[i] * factor) * np_sign(f[i]);
 }
 
+// ---- stage 3's launches, shared by hipdrt_map_predict and its test hook hipdrt_debug_map_prob ----
+// what map_prob_kernel stages for rows of n points; HIPDRT_E_UNSUPPORTED with the limit in the message when LDS does not hold it
+int map_prob_lds(int n, size_t* lds) {
+    *lds = MP_BYTES_PER_POINT * (size_t)(n > 0 ? n : 0);
+    if (*lds > MP_LDS_LIMIT) {
+        set_error("unsupported: map_predict stages " + std::to_string(MP_BYTES_PER_POINT) + " bytes per evaluation point in LDS: neval <= " +
+                  std::to_string(MP_LDS_LIMIT / MP_BYTES_PER_POINT) + ", got " + std::to_string(n));
+        return HIPDRT_E_UNSUPPORTED;
+    }
+    return HIPDRT_OK;
+}
+// the clamp in a kernel of its own, in place on the stored rows
+int launch_clamp(hipStream_t st, int rows, int n, double* vf, double* vxx, const int* ext) {
+    hipLaunchKernelGGL(clamp_kernel, dim3(rows, 2), dim3(PKT), 0, st, n, vf, vxx, ext);
+    LAUNCH_OK();
+    return HIPDRT_OK;
+}
+int launch_map_prob(hipStream_t st, int rows, const MapProbArgs& a) {
+    size_t lds;
+    TRY(map_prob_lds(a.n, &lds));
+    if (lds > 65536) TRY(set_lds_limit(reinterpret_cast<const void*>(map_prob_kernel), lds, "map_prob_kernel"));
+    hipLaunchKernelGGL(map_prob_kernel, dim3(rows), dim3(PKT), lds, st, a);
+    LAUNCH_OK();
+    return HIPDRT_OK;
+}
+// ext: rows pairs of indices of the n-point grid, or (-1, -1)
+int check_ext(const int* ext, int rows, int n) {
+    for (int b = 0; b < rows; ++b) {
+        const int li = ext[2 * b], ri = ext[2 * b + 1];
+        HIPDRT_REQUIRE((li == -1 && ri == -1) || (li >= 0 && li < n && ri >= 0 && ri < n),
+                       "ext: a pair of indices of the evaluation grid, or (-1, -1)");
+    }
+    return HIPDRT_OK;
+}
+
 }  // namespace
 }  // namespace hipdrt
 
@@ -166,19 +203,9 @@ extern "C" int hipdrt_map_predict(hipdrt_ctx* ctx, const hipdrt_map_predict_args
         HIPDRT_REQUIRE(g->spread.radius < 0 || (g->spread.w && std::isfinite(g->spread_factor)), "the spread table and its factor");
     }
     const bool stored = have_var && g->var_stored != 0;
-    if (stored && g->ext && (want_var || want_prob)) {
-        for (int b = 0; b < rows; ++b) {
-            const int li = g->ext[2 * b], ri = g->ext[2 * b + 1];
-            HIPDRT_REQUIRE((li == -1 && ri == -1) || (li >= 0 && li < neval && ri >= 0 && ri < neval),
-                           "ext: a pair of indices of the evaluation grid, or (-1, -1)");
-        }
-    }
-    const size_t lds = MP_BYTES_PER_POINT * (size_t)(neval > 0 ? neval : 0);
-    if (want_prob && lds > MP_LDS_LIMIT) {
-        set_error("unsupported: map_predict stages " + std::to_string(MP_BYTES_PER_POINT) + " bytes per evaluation point in LDS: neval <= " +
-                  std::to_string(MP_LDS_LIMIT / MP_BYTES_PER_POINT) + ", got " + std::to_string(neval));
-        return HIPDRT_E_UNSUPPORTED;
-    }
+    if (stored && g->ext && (want_var || want_prob)) TRY(check_ext(g->ext, rows, neval));
+    size_t lds;
+    if (want_prob) TRY(map_prob_lds(neval, &lds));
     hipStream_t st; TRY(enter(ctx, &st));
 
     // ---- 1: x ----
@@ -222,10 +249,7 @@ extern "C" int hipdrt_map_predict(hipdrt_ctx* ctx, const hipdrt_map_predict_args
         vf = dvf.d(); vxx = dvxx.d();
         if (clamp) TRY(upload(dext, g->ext, (size_t)rows * 2 * sizeof(int), st));
         const bool clamp_first = stored && (filt || !want_prob);     // the clamp in a kernel of its own, then the filter
-        if (clamp_first && clamp) {
-            hipLaunchKernelGGL(clamp_kernel, dim3(rows, 2), dim3(PKT), 0, st, neval, dvf.d(), dvxx.d(), dext.i());
-            LAUNCH_OK();
-        }
+        if (clamp_first && clamp) TRY(launch_clamp(st, rows, neval, dvf.d(), dvxx.d(), dext.i()));
         if (stored && filt) {
             HIPDRT_CHECK(dvf2.alloc(ne * sizeof(double))); HIPDRT_CHECK(dvxx2.alloc(ne * sizeof(double)));
             TRY(plain_gaussian_device(st, dvf.d(), rows, neval, g->x_filter, dvf2.d()));
@@ -248,11 +272,7 @@ extern "C" int hipdrt_map_predict(hipdrt_ctx* ctx, const hipdrt_map_predict_args
             a.vf_out = dvf2.d(); a.vxx_out = dvxx2.d();
             vf = dvf2.d(); vxx = dvxx2.d();
         }
-        if (a.pk || a.curv) {
-            if (lds > 65536) TRY(set_lds_limit(reinterpret_cast<const void*>(map_prob_kernel), lds, "map_prob_kernel"));
-            hipLaunchKernelGGL(map_prob_kernel, dim3(rows), dim3(PKT), lds, st, a);
-            LAUNCH_OK();
-        }
+        if (a.pk || a.curv) TRY(launch_map_prob(st, rows, a));
         // ---- 4: spread and sign ----
         if (spread) {
             hipdrt_filter_table tabs[2] = {{nullptr, -1}, g->spread};
@@ -276,5 +296,47 @@ extern "C" int hipdrt_map_predict(hipdrt_ctx* ctx, const hipdrt_map_predict_args
     TRY(back(peak_prob, dpeak.d(), ne));
     TRY(back(curv_prob, dcurv.d(), ne));
     HIPDRT_CHECK(hipStreamSynchronize(st));
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+// test hook (include/hipdrt_debug.h): stage 3 alone -- clamp_kernel and / or map_prob_kernel through the launchers the entry point
+// uses, on host rows; every in and out array between borders of marker bytes
+extern "C" int hipdrt_debug_map_prob(hipdrt_ctx* ctx, int rows, int n, const double* f, const double* fxx, const double* vf,
+                                     const double* vxx, const int* ext, int clamp_first, int search, double height,
+                                     double prominence, int sign_now, double* pk, double* curv, double* vf_out,
+                                     double* vxx_out) try {
+    HIPDRT_REQUIRE(ctx && vf && vxx, "NULL pointer");
+    HIPDRT_REQUIRE(rows >= 1 && n >= 1 && (long long)rows * n < (1LL << 30), "rows, n >= 1, rows * n < 2^30");
+    const bool prob = pk || curv;
+    HIPDRT_REQUIRE(!prob || (f && fxx), "the probabilities need the f and fxx rows");
+    HIPDRT_REQUIRE(prob || (clamp_first && ext), "nothing to launch: no probability row and no clamp kernel");
+    HIPDRT_REQUIRE(!clamp_first || ext, "clamp_first needs ext");
+    HIPDRT_REQUIRE(search >= -1 && search <= 1, "search must be 1, -1 or 0 (two passes)");
+    HIPDRT_REQUIRE(std::isfinite(height) && std::isfinite(prominence), "height and prominence must be finite");
+    if (ext) TRY(check_ext(ext, rows, n));
+    size_t lds;
+    if (prob) TRY(map_prob_lds(n, &lds));
+    hipStream_t st; TRY(enter(ctx, &st));
+    const size_t bn = (size_t)rows * n;
+    MapProbArgs a{};
+    a.n = n; a.search = search; a.height = height; a.prominence = prominence; a.sign_now = sign_now ? 1 : 0;
+    GuardedOuts g;
+    TRY(g.in("f", f, bn, a.f, st)); TRY(g.in("fxx", fxx, bn, a.fxx, st));
+    // the variance rows are in/out when the clamp kernel runs first: it works in place, as on the entry point's uploaded rows
+    Guarded gvf, gvxx;
+    TRY(gvf.up_in("vf", vf, bn * sizeof(double), st)); TRY(gvxx.up_in("vxx", vxx, bn * sizeof(double), st));
+    a.vf = gvf.dd(); a.vxx = gvxx.dd();
+    const int* dext = nullptr;
+    TRY(g.in("ext", ext, (size_t)rows * 2, dext, st));
+    if (clamp_first) TRY(launch_clamp(st, rows, n, gvf.dd(), gvxx.dd(), dext));
+    else a.ext = dext;
+    TRY(g.want("pk", pk, bn, a.pk, st)); TRY(g.want("curv", curv, bn, a.curv, st));
+    if (!clamp_first) { TRY(g.want("vf_out", vf_out, bn, a.vf_out, st)); TRY(g.want("vxx_out", vxx_out, bn, a.vxx_out, st)); }
+    if (prob) TRY(launch_map_prob(st, rows, a));
+    TRY(gvf.fetch(st)); TRY(gvxx.fetch(st));
+    TRY(g.back(st));
+    TRY(gvf.check()); TRY(gvxx.check());
+    if (clamp_first && vf_out) std::memcpy(vf_out, gvf.data(), bn * sizeof(double));
+    if (clamp_first && vxx_out) std::memcpy(vxx_out, gvxx.data(), bn * sizeof(double));
     return HIPDRT_OK;
 } HIPDRT_CATCH

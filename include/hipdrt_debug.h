@@ -9,7 +9,9 @@
  * a finished fit: hipdrt_debug_pfrt_step / _combine, hipdrt_debug_candidate_llh, and hipdrt_debug_posterior (the posterior variance and
  * covariance chain: packed rows, the 32-column factorisation with appended tile rows, the outer product).  The interior-point QP has
  * hipdrt_debug_qp (launch_qp in the fit loop's form: packed P only, active mask, dispatch order, iters_accum; s and z come back) and
- * hipdrt_debug_lpt_order (the dispatch-order kernel alone).
+ * hipdrt_debug_lpt_order (the dispatch-order kernel alone).  The map kernels have hipdrt_debug_map_gaussian (the separable filter
+ * passes in their LDS and uncached forms), hipdrt_debug_map_reduce (the fixed-order mean, std and min / max) and hipdrt_debug_map_prob
+ * (the clamp and probability kernels of a map's rows, fed f and fxx directly); the rank filters are reached through their entry point.
  */
 #ifndef HIPDRT_DEBUG_H
 #define HIPDRT_DEBUG_H
@@ -304,6 +306,33 @@ int hipdrt_debug_map_filter_stats(hipdrt_ctx* ctx, double* stats);
 /* Tools (tools/probe_map_badness.py): device time in ms, by HIP events between the upload and the download, of this context's
  * last hipdrt_map_badness (its internal synchronisations included).                                                             */
 int hipdrt_debug_map_badness_ms(hipdrt_ctx* ctx, double* ms);
+
+/* test hooks (tests/test_gpu_map_kernels.py): the launchers of the map kernels alone, on host arrays.  On the device every in and out
+ * array sits between two borders of marker bytes: HIPDRT_E_NUMERIC when a kernel changed one.  HIPDRT_E_INVALID, and nothing is
+ * launched, for arguments that could make a kernel read or write out of bounds.
+ *
+ * map_gaussian: plain_gaussian_device (masked = 0: scipy's gaussian_filter, a NaN spreads over its window) or masked_gaussian_device
+ * (masked = 1: masked_filter(nan_to_num(a), ~isnan(a), gaussian_filter)) of csrc/map_filter.hip, the two functions csrc/map_rank.hip
+ * and csrc/map_predict.hip call and the same filter_pass_kernel launches as hipdrt_map_filter's -- a [R][C] row-major, tabs[2] the
+ * half tables of axis 0 and 1 (radius < 0 skips the axis), out [R][C].
+ *
+ * map_reduce: the fixed-order reductions of csrc/map_filter.hip (MapFilter::reduce, std_of: reduce_partial + reduce_final) on x [n],
+ * 1 <= n < 2^30 -- mode 0: out[0] = mean, out[1] = 0;  mode 1: out[0] = np.std(x), out[1] = the mean it was taken about;
+ * mode 2: out[0], out[1] = min, max.  The partial sums and the scalar slots are bordered as well.
+ *
+ * map_prob: stage 3 of hipdrt_map_predict (csrc/map_predict.hip) through the entry point's own launchers -- with clamp_first
+ * clamp_kernel in place on the variance rows, then (pk or curv given) map_prob_kernel without ext; without clamp_first map_prob_kernel
+ * alone, with the clamp inside it when ext is given; the dynamic-LDS limit is raised as the entry point raises it.  f, fxx, vf, vxx
+ * [rows][n] (f and fxx may be NULL when neither pk nor curv is asked for; non-finite values are allowed); ext [rows][2] or NULL: pairs
+ * of indices of the grid, or (-1, -1); search 1, -1 or 0; sign_now as MapProbArgs.  Out, any may be NULL: pk, curv [rows][n];
+ * vf_out, vxx_out [rows][n] the variance rows as the probabilities saw them.  HIPDRT_E_UNSUPPORTED with the entry point's message
+ * when n exceeds what LDS holds; HIPDRT_E_INVALID for an ext pair outside the grid, and when there is nothing to launch.          */
+int hipdrt_debug_map_gaussian(hipdrt_ctx* ctx, const double* a, int R, int C, const hipdrt_filter_table* tabs, int masked,
+                              double* out);
+int hipdrt_debug_map_reduce(hipdrt_ctx* ctx, const double* x, long long n, int mode, double* out);
+int hipdrt_debug_map_prob(hipdrt_ctx* ctx, int rows, int n, const double* f, const double* fxx, const double* vf, const double* vxx,
+                          const int* ext, int clamp_first, int search, double height, double prominence, int sign_now, double* pk,
+                          double* curv, double* vf_out, double* vxx_out);
 
 #ifdef __cplusplus
 }

@@ -58,12 +58,16 @@ def rank_case(G, key):
 def rank_equal(G, key, got):
     """bit for bit against scipy, NaN windows included wherever every rank involved lies strictly inside the window; at rank 0
     or size - 1 scipy switches to its minimum / maximum filter, and there only the windows without a NaN are compared"""
-    from hipdrt.filters import ndfilters
     a, kind, size = rank_case(G, key)
+    return rank_rule_equal(a, kind, size, got, G[key])
+
+
+def rank_rule_equal(a, kind, size, got, ref):
+    """the rule of rank_equal for any input a, filter kind and window size, against the reference result ref"""
+    from hipdrt.filters import ndfilters
     n = size[0] * size[1]
     ranks = {"median": [n // 2], "p25": [int(n * 25 / 100.0)], "p75": [int(n * 75 / 100.0)],
              "iqr": [int(n * 25 / 100.0), int(n * 75 / 100.0)]}[kind]
-    ref = G[key]
     if all(0 < r < n - 1 for r in ranks):
         return np.array_equal(got, ref, equal_nan=True)
     clean = ~np.isnan(ndfilters.window_values(a, list(size))).any(axis=-1)

@@ -86,9 +86,12 @@ def test_numpy_statement_matches_the_reference_run(fx, bounds, name):
 
 
 def test_bounds_table_covers_both_sections_and_keeps_its_rule(bounds):
-    assert set(bounds) == {"device", "numpy"}
+    # ("kernels": the adaptive passes of tests/test_gpu_map_kernels.py against ndfilters, under the same rule)
+    assert set(bounds) == {"device", "numpy", "kernels"}
     for name in CASES:
         assert f"{name}:out" in bounds["device"] and f"{name}:out" in bounds["numpy"]
+    import map_kernels_util
+    assert set(bounds["kernels"]) == set(map_kernels_util.ADAPTIVE_CASES)
     for rows in bounds.values():
         for label, (measured, bound) in rows.items():
             assert bound >= 10 * measured and bound >= 5e-15, label
