@@ -1,0 +1,58 @@
+"""Bound: an argument structure together with the numpy arrays its pointer fields refer to.
+
+A ctypes pointer field does not keep its array alive, so every array goes through here: converted, checked against the shapes
+the entry point takes, stored in the field and held in ``keep`` for as long as the Bound lives."""
+import numpy as np
+
+from .abi import _p, _pi
+
+
+class Bound:
+    def __init__(self, struct):
+        self.c = struct
+        self.keep = []
+
+    def hold(self, a):
+        """keep `a` alive with the structure (an array that goes into a positional argument, an options structure)"""
+        self.keep.append(a)
+        return a
+
+    def _store(self, field, v, shapes):
+        if shapes is not None:
+            allowed = [tuple(s) for s in (shapes if isinstance(shapes, list) else [shapes])]
+            if v.shape not in allowed:
+                raise ValueError(f"{field}: expected shape {' or '.join(map(str, allowed))}, got {v.shape}")
+        setattr(self.c, field, _pi(v) if v.dtype == np.int32 else _p(v))
+        return self.hold(v)
+
+    def array(self, field, v, shapes=None, dtype=np.float64, copy=False):
+        """`v` as a C-contiguous `dtype` (float64 or int32) array behind pointer field `field`; None leaves the field NULL.
+        shapes: one shape or a list of allowed ones; copy: a fresh writable copy, the caller's array stays untouched"""
+        if v is None:
+            return None
+        return self._store(field, np.array(v, dtype=dtype, order="C") if copy else np.ascontiguousarray(v, dtype=dtype), shapes)
+
+    def output(self, field, v, shape):
+        """a caller-filled in/out array: it must be writable C-contiguous float64 of `shape` already, nothing is copied"""
+        if v is None:
+            return None
+        if not (isinstance(v, np.ndarray) and v.dtype == np.float64 and v.flags.c_contiguous and v.flags.writeable):
+            raise ValueError(f"{field}: a writeable C-contiguous float64 array")
+        return self._store(field, v, shape)
+
+    def table(self, slot, full):
+        """centre and right half of the full symmetric table `full` into `slot`, a FilterTable or the (NodeTables, k) of node k;
+        None: radius -1, which skips the axis"""
+        r, w = -1, None
+        if full is not None:
+            r = len(full) // 2
+            w = _p(self.hold(np.ascontiguousarray(np.asarray(full, dtype=np.float64)[r:])))
+        if isinstance(slot, tuple):
+            tables, k = slot
+            tables.radius[k] = r
+            if w is not None:
+                tables.w[k] = w
+        else:
+            slot.radius = r
+            if w is not None:
+                slot.w = w

@@ -38,26 +38,18 @@ def _refuse(kw, adaptive):
     return kw, truncate
 
 
-class _Args:
-    """hipdrt_map_filter_args plus the numpy tables its pointers refer to"""
+class _Args(_ffi.Bound):
+    """hipdrt_map_filter_args with its defaults (every table skipped) and the numpy tables its pointers refer to"""
 
     def __init__(self, ndim):
+        super().__init__(_ffi.MapFilterArgs())
         self.ndim = ndim
-        self.keep = []
         self.error = None
-        a = self.c = _ffi.MapFilterArgs()
-        for tabs in (a.gauss, a.empty_gauss, a.box, a.pre_gauss, a.pre_empty):
+        a = self.c
+        for tabs in (a.gauss, a.empty_gauss, a.box, a.pre_gauss, a.pre_empty, [a.curv]):
             for t in tabs:
-                t.radius = -1
-        a.curv.radius = -1
+                self.table(t, None)
         a.iter, a.nstd, a.box_size = 2, 5.0, 5
-
-    def table(self, slot, full):
-        """centre and right half of a symmetric table"""
-        r = len(full) // 2
-        half = np.ascontiguousarray(full[r:], dtype=np.float64)
-        self.keep.append(half)
-        slot.w, slot.radius = _ffi._p(half), r
 
     def gaussians(self, slots, empty_slots, sigma, truncate):
         for l, s in enumerate(sigma):
@@ -94,9 +86,7 @@ class _Args:
             r = ndfilters.kernel_radius(1, truncate)
             self.table(a.curv, ndfilters.gaussian_kernel1d(1, 2, r))
         else:
-            s = np.ascontiguousarray(np.stack([np.broadcast_to(np.asarray(x, dtype=np.float64), sigmas_in[0].shape) for x in sigmas_in]))
-            self.keep.append(s)
-            a.sigmas_in = _ffi._p(s)
+            self.array("sigmas_in", np.stack([np.broadcast_to(np.asarray(x, dtype=np.float64), sigmas_in[0].shape) for x in sigmas_in]))
 
         def node_tables(user, axis, empty, smin, smax, out):
             try:
@@ -108,13 +98,11 @@ class _Args:
                 for k, node in enumerate(nodes):
                     t.node[k] = float(node)
                     if node < MIN_SIGMA and not empty:
-                        t.radius[k] = -1            # below the minimum effective width: the node returns its input
+                        self.table((t, k), None)    # below the minimum effective width: the node returns its input
                         continue
                     s = MIN_SIGMA if node < MIN_SIGMA else float(node)
                     r = ndfilters.kernel_radius(s, truncate)
-                    half = np.ascontiguousarray(ndfilters.gaussian_kernel1d(s, 0, r, empty=bool(empty))[r:])
-                    self.keep.append(half)
-                    t.radius[k], t.w[k] = r, _ffi._p(half)
+                    self.table((t, k), ndfilters.gaussian_kernel1d(s, 0, r, empty=bool(empty)))
                 return 0
             except Exception as e:             # noqa: BLE001 (no exception may cross the C frames)
                 self.error = e
@@ -132,9 +120,7 @@ class _Args:
             self.table(a.box[l], np.ones(int(dev_rms_size)))
 
     def weights(self, w, shape):
-        w = np.ascontiguousarray(np.broadcast_to(np.asarray(w, dtype=np.float64), shape))
-        self.keep.append(w)
-        self.c.init_weights = _ffi._p(w)
+        self.array("init_weights", np.broadcast_to(np.asarray(w, dtype=np.float64), shape))
 
     def run(self, a, device, **want):
         try:

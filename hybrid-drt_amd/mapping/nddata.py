@@ -159,19 +159,19 @@ def score_rows_statement(a, median_size, std_size, scale_src=None, ignore_outlie
 
 
 # ---- the device chain ----------------------------------------------------------------------------------------------------------
-class _Args:
-    """hipdrt_map_badness_args plus the numpy tables its pointers refer to"""
+class _Args(_ffi.Bound):
+    """hipdrt_map_badness_args with its defaults and the numpy tables its pointers refer to"""
 
     def __init__(self, median_size=(1, 1), std_size=(1, 1)):
-        self.keep = []
-        c = self.c = _ffi.MapBadnessArgs()
+        super().__init__(_ffi.MapBadnessArgs())
+        c = self.c
         c.median_size[:] = _size2(median_size)
         c.std_size[:] = _size2(std_size)
         c.flag_size[:] = [1, 1]
         c.n_std = kk.std_normal_quantile(0.75)          # robust_std's sample_fraction = 0.5
         c.score = 1
         for t in c.impute_gauss:
-            t.radius = -1
+            self.table(t, None)
 
     def flags(self, filter_size, thresh, p_prior, full_std_contribution, impute, impute_kw):
         c = self.c
@@ -182,15 +182,7 @@ class _Args:
             sigma, truncate = _impute_sigma(impute_kw)
             for l, s in enumerate(sigma):
                 if s > 1e-15:
-                    r = ndfilters.kernel_radius(s, truncate)
-                    half = np.ascontiguousarray(ndfilters.gaussian_kernel1d(s, 0, r)[r:])
-                    self.keep.append(half)
-                    c.impute_gauss[l].w, c.impute_gauss[l].radius = _ffi._p(half), r
-
-    def filt_in(self, x_filt):
-        x_filt = np.ascontiguousarray(x_filt, dtype=np.float64)
-        self.keep.append(x_filt)
-        self.c.filt_in = _ffi._p(x_filt)
+                    self.table(c.impute_gauss[l], ndfilters.gaussian_kernel1d(s, 0, ndfilters.kernel_radius(s, truncate)))
 
 
 def impute_nans(ndy, method='filter', filter_func=None, device=0, **filter_kw):
@@ -223,7 +215,7 @@ def flag_bad_obs(x_raw, x_filt, std_size=5, thresh=2, test_factor_correction=Fal
     if x_raw.shape != x_filt.shape:
         raise ValueError("x_raw and x_filt must have one shape")
     args = _Args(std_size=std_size)
-    args.filt_in(x_filt)
+    args.array("filt_in", x_filt)
     rss = _ffi.get_context(device).map_badness(x_raw, args.c)["rss"]
     bad = np.zeros(x_raw.shape, dtype=bool)
     bad[rss >= thresh] = 1
