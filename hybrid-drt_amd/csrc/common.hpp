@@ -168,22 +168,35 @@ struct GramL2 {
     const double* dop_rho; // [B][3]
     double dop_dfac[3];    // dop_l2_lambda_0 * dop_derivative_weight[k]
 };
-// a_stride: doubles between the response matrices of consecutive problems (0 = one shared matrix)
-void launch_gram_l2(hipStream_t st, int B, int m, int n, const double* A, int lda, const double* w, const GramL2& g,
-                    double* P, int ldp, long long p_stride, const int* active, double* Ppk = nullptr,
-                    long long ppk_stride = 0, int nchp = 0, long long a_stride = 0);
-// row-major symmetric P -> accumulator-native lower tiles
-void launch_pack_p(hipStream_t st, int B, int n, const double* P, int ldp, long long p_stride, double* Ppk,
-                   long long ppk_stride, int nchp);
+// The weighted normal equations of B problems (all pointers device memory): P_b = A_b' diag(w_b^2) A_b + L2_b for
+// launch_gram_l2, which reads the first two blocks, and q_b = -A_b' diag(w_b^2) y_b + l1 for launch_qvec, which reads the first
+// and the last.  A launcher ignores the block it does not read.
+struct PqArgs {
+    int B, m, n;          // problems, rows and columns of A
+    const double* A;      // [B or 1][m][lda]
+    int lda;
+    long long a_stride;   // doubles between the matrices of consecutive problems (0 = one shared matrix)
+    const double* w;      // [B][m]
+    const int* active;    // [B] or null: problems with active[b] == 0 are left as they are
+    // P: at least one of the two copies
+    double* P;            // [B][n][ldp] row-major, or null
+    int ldp;
+    long long p_stride;   // doubles between consecutive problems' P
+    double* Ppk;          // [B][nchp][nchp][256] lower 16 x 16 tiles in the QP factor's layout (nchp = qp_nchp(n)), or null
+    long long ppk_stride; // doubles between consecutive problems' Ppk (qp_ppk_doubles(n) when they are packed one behind the other)
+    // q
+    const double* y;      // [B][m]
+    const double* l1;     // [n] shared by all problems, or null: l1_scalar in every entry
+    double l1_scalar;
+    double* q;            // [B][n]
+};
 inline int qp_nchp(int n) { return round_up(n, 32) / 16; }
 inline size_t qp_ppk_doubles(int n) { return (size_t)qp_nchp(n) * qp_nchp(n) * 256; }
-void launch_qvec_batched(hipStream_t s, int B, int m, int n, const double* rm, int ldrm, const double* w, const double* y,
-                         const double* l1, double l1_scalar, double* q, const int* active);
-void launch_qvec(hipStream_t st, int B, int m, int n, const double* A, int lda, const double* w, const double* y,
-                 const double* l1, double l1_scalar, double* q, const int* active, long long a_stride = 0);
-void launch_weighted_gram(hipStream_t st, int B, int m, int n, const double* A, int lda, const double* w,
-                          const double* b, const double* l2, long long l2_stride, int ldl2, const double* l1,
-                          double* P, int ldp, long long p_stride, double* q, const int* active);
+void launch_gram_l2(hipStream_t st, const PqArgs& a, const GramL2& g);
+void launch_qvec(hipStream_t st, const PqArgs& a);
+void launch_qvec_batched(hipStream_t s, const PqArgs& a);     // hyper.hip: the shared-matrix form of launch_qvec
+// row-major symmetric P [B][n][ldp] -> accumulator-native lower tiles Ppk [B][qp_ppk_doubles(n)]
+void launch_pack_p(hipStream_t st, int B, int n, const double* P, int ldp, double* Ppk);
 
 // hyper.hip: device-resident state of a batched fit (passed by value to the kernels)
 struct FitState {

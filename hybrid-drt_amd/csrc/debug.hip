@@ -66,7 +66,6 @@ int hipdrt_debug_gram_l2(hipdrt_ctx* ctx, const hipdrt_debug_gram_args* a) try {
     }
     hipStream_t st; TRY(enter(ctx, &st));
     const size_t D = sizeof(double);
-    const int nchp = qp_nchp(n);
     const size_t ppk = qp_ppk_doubles(n);
     DevBuf dA, dw, dy, dl1, dl2, dmk[3], ds, drho, ddrho, dact, dP, dPpk, dq;
     TRY(upload(dA, a->A, (size_t)(a->a_batched ? B : 1) * m * a->lda * D, st));
@@ -93,13 +92,16 @@ int hipdrt_debug_gram_l2(hipdrt_ctx* ctx, const hipdrt_debug_gram_args* a) try {
     if (a->P) TRY(upload(dP, a->P, (size_t)B * n * a->ldp * D, st));
     if (a->Ppk) TRY(upload(dPpk, a->Ppk, (size_t)B * ppk * D, st));
     if (a->y) TRY(upload(dq, a->q, (size_t)B * n * D, st));
-    const long long astr = a->a_batched ? (long long)m * a->lda : 0;
-    launch_gram_l2(st, B, m, n, dA.d(), a->lda, dw.d(), g, a->P ? dP.d() : nullptr, a->ldp, (long long)n * a->ldp,
-                   a->active ? dact.i() : nullptr, a->Ppk ? dPpk.d() : nullptr, (long long)ppk, nchp, astr);
+    PqArgs pq{};
+    pq.B = B; pq.m = m; pq.n = n; pq.A = dA.d(); pq.lda = a->lda; pq.a_stride = a->a_batched ? (long long)m * a->lda : 0;
+    pq.w = dw.d(); pq.active = a->active ? dact.i() : nullptr;
+    pq.P = a->P ? dP.d() : nullptr; pq.ldp = a->ldp; pq.p_stride = (long long)n * a->ldp;
+    pq.Ppk = a->Ppk ? dPpk.d() : nullptr; pq.ppk_stride = (long long)ppk;
+    pq.y = dy.d(); pq.l1 = a->l1 ? dl1.d() : nullptr; pq.l1_scalar = a->l1_scalar; pq.q = dq.d();
+    launch_gram_l2(st, pq, g);
     LAUNCH_OK();
     if (a->y) {
-        launch_qvec(st, B, m, n, dA.d(), a->lda, dw.d(), dy.d(), a->l1 ? dl1.d() : nullptr, a->l1_scalar, dq.d(),
-                    a->active ? dact.i() : nullptr, astr);
+        launch_qvec(st, pq);
         LAUNCH_OK();
     }
     if (a->P) HIPDRT_CHECK(hipMemcpyAsync(a->P, dP.p, (size_t)B * n * a->ldp * D, hipMemcpyDeviceToHost, st));
@@ -117,7 +119,7 @@ int hipdrt_debug_pack_p(hipdrt_ctx* ctx, int B, int n, const double* P, int ldp,
     DevBuf dP, dPpk;
     TRY(upload(dP, P, (size_t)B * n * ldp * sizeof(double), st));
     TRY(upload(dPpk, Ppk, (size_t)B * ppk * sizeof(double), st));
-    launch_pack_p(st, B, n, dP.d(), ldp, (long long)n * ldp, dPpk.d(), (long long)ppk, qp_nchp(n));
+    launch_pack_p(st, B, n, dP.d(), ldp, dPpk.d());
     LAUNCH_OK();
     HIPDRT_CHECK(hipMemcpyAsync(Ppk, dPpk.p, (size_t)B * ppk * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPDRT_CHECK(hipStreamSynchronize(st));
@@ -591,7 +593,7 @@ int hipdrt_debug_posterior(hipdrt_ctx* ctx, const hipdrt_debug_posterior_args* a
     TRY(upload(dP, a->P, (size_t)pb * n * ldp * D, st));
     HIPDRT_CHECK(dPpk.alloc((size_t)pb * ppk * D));
     HIPDRT_CHECK(hipMemsetAsync(dPpk.p, 0, dPpk.bytes, st));
-    launch_pack_p(st, pb, n, dP.d(), ldp, (long long)n * ldp, dPpk.d(), (long long)ppk, nchp);
+    launch_pack_p(st, pb, n, dP.d(), ldp, dPpk.d());
     LAUNCH_OK();
     TRY(upload(drows, a->rows, (size_t)neval * ncol * D, st));
     std::vector<double> hvar((size_t)nb * nex * 16, 0.0), hbex((size_t)nex * nchp * 256, 0.0), hcov;
@@ -687,7 +689,7 @@ int hipdrt_debug_qp(hipdrt_ctx* ctx, const hipdrt_debug_qp_args* a) try {
     TRY(upload(dP, a->P, (size_t)pb * n * ldp * D, st));
     HIPDRT_CHECK(dPpk.alloc((size_t)pb * ppk * D));
     HIPDRT_CHECK(hipMemsetAsync(dPpk.p, 0, dPpk.bytes, st));
-    launch_pack_p(st, pb, n, dP.d(), ldp, (long long)n * ldp, dPpk.d(), (long long)ppk, qp_nchp(n));
+    launch_pack_p(st, pb, n, dP.d(), ldp, dPpk.d());
     LAUNCH_OK();
     TRY(upload(dq, a->q, (size_t)B * n * D, st));
     TRY(upload(dh, a->h, (size_t)hb * n * D, st));

@@ -477,47 +477,35 @@ void launch_rows_outer(hipStream_t st, const double* Y, int nch, int ncol, int n
     hipLaunchKernelGGL(rows_outer_kernel, dim3(nex, nex), dim3(256), 0, st, Y, nch, ncol, nrow, scale, out, ld);
 }
 
-void launch_pack_p(hipStream_t st, int B, int n, const double* P, int ldp, long long p_stride, double* Ppk,
-                   long long ppk_stride, int nchp) {
+void launch_pack_p(hipStream_t st, int B, int n, const double* P, int ldp, double* Ppk) {
     const int nt = (n + 15) / 16;
-    hipLaunchKernelGGL(pack_p_kernel, dim3(nt * (nt + 1) / 2, B), dim3(64), 0, st, n, P, ldp, p_stride, Ppk, ppk_stride,
-                       nchp);
+    hipLaunchKernelGGL(pack_p_kernel, dim3(nt * (nt + 1) / 2, B), dim3(64), 0, st, n, P, ldp, (long long)n * ldp, Ppk,
+                       (long long)qp_ppk_doubles(n), qp_nchp(n));
 }
 
-void launch_gram_l2(hipStream_t st, int B, int m, int n, const double* A, int lda, const double* w, const GramL2& g,
-                    double* P, int ldp, long long p_stride, const int* active, double* Ppk, long long ppk_stride,
-                    int nchp, long long a_stride) {
+void launch_gram_l2(hipStream_t st, const PqArgs& a, const GramL2& g) {
     // tile rows: the last sub-tile row rides on the diagonal tiles when it would be a 64-tile row's only one
-    const int nt = gram_strip_folds(n) ? ((n + 15) / 16) / 4 : (n + GT - 1) / GT;
+    const int nt = gram_strip_folds(a.n) ? ((a.n + 15) / 16) / 4 : (a.n + GT - 1) / GT;
     const int ntile = nt * (nt + 1) / 2;
+    const int nchp = a.Ppk ? qp_nchp(a.n) : 0;
     const bool dop = g.s && g.dop_size > 0;
-#define HIPDRT_GRAM(D, R) hipLaunchKernelGGL((gram_kernel<D, R>), dim3(ntile, B), dim3(256), 0, st, m, n, A, lda, w, g, P, ldp, \
-                                             p_stride, active, ntile, Ppk, ppk_stride, nchp, a_stride)
-    if (P) { if (dop) HIPDRT_GRAM(true, true); else HIPDRT_GRAM(false, true); }
+#define HIPDRT_GRAM(D, R) hipLaunchKernelGGL((gram_kernel<D, R>), dim3(ntile, a.B), dim3(256), 0, st, a.m, a.n, a.A, a.lda, a.w, \
+                                             g, a.P, a.ldp, a.p_stride, a.active, ntile, a.Ppk, a.ppk_stride, nchp, a.a_stride)
+    if (a.P) { if (dop) HIPDRT_GRAM(true, true); else HIPDRT_GRAM(false, true); }
     else { if (dop) HIPDRT_GRAM(true, false); else HIPDRT_GRAM(false, false); }
 #undef HIPDRT_GRAM
 }
 
-void launch_qvec(hipStream_t st, int B, int m, int n, const double* A, int lda, const double* w, const double* y,
-                 const double* l1, double l1_scalar, double* q, const int* active, long long a_stride) {
+void launch_qvec(hipStream_t st, const PqArgs& a) {
     // one matrix for the whole batch: a matrix product with a shared operand (hyper.hip: batch_products_kernel), whatever the
     // batch size -- a fit's bits do not depend on how many are fitted beside it; few fits with very large matrices keep the
     // vector kernel (a handful of workgroups would stream all of A)
-    if (a_stride == 0 && (size_t)m * n < ((size_t)1 << 20)) {
-        launch_qvec_batched(st, B, m, n, A, lda, w, y, l1, l1_scalar, q, active);
+    if (a.a_stride == 0 && (size_t)a.m * a.n < ((size_t)1 << 20)) {
+        launch_qvec_batched(st, a);
         return;
     }
-    hipLaunchKernelGGL(qvec_kernel, dim3((n + 255) / 256, B), dim3(256), 0, st, m, n, A, lda, w, y, l1, l1_scalar, q,
-                       active, a_stride);
-}
-
-void launch_weighted_gram(hipStream_t st, int B, int m, int n, const double* A, int lda, const double* w,
-                          const double* b, const double* l2, long long l2_stride, int ldl2, const double* l1,
-                          double* P, int ldp, long long p_stride, double* q, const int* active) {
-    GramL2 g{};
-    g.l2 = l2; g.l2_stride = l2_stride; g.ldl2 = ldl2; g.s = nullptr;
-    launch_gram_l2(st, B, m, n, A, lda, w, g, P, ldp, p_stride, active);
-    launch_qvec(st, B, m, n, A, lda, w, b, l1, 0.0, q, active);
+    hipLaunchKernelGGL(qvec_kernel, dim3((a.n + 255) / 256, a.B), dim3(256), 0, st, a.m, a.n, a.A, a.lda, a.w, a.y, a.l1,
+                       a.l1_scalar, a.q, a.active, a.a_stride);
 }
 
 }  // namespace hipdrt

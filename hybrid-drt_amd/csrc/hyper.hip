@@ -463,10 +463,10 @@ __global__ __launch_bounds__(256) void batch_products_kernel(int B, int ni, int 
 }
 
 // q_b = -rm' (w_b (w_b y_b)) + l1 for a batch that shares rm (row-major [m][n])
-void launch_qvec_batched(hipStream_t s, int B, int m, int n, const double* rm, int ldrm, const double* w, const double* y,
-                         const double* l1, double l1_scalar, double* q, const int* active) {
-    const dim3 grid((n + BG_TI - 1) / BG_TI, (B + BG_TB - 1) / BG_TB);
-    hipLaunchKernelGGL((batch_products_kernel<2, true>), grid, dim3(256), 0, s, B, n, m, w, m, y, rm, ldrm, active, q, l1, l1_scalar);
+void launch_qvec_batched(hipStream_t s, const PqArgs& a) {
+    const dim3 grid((a.n + BG_TI - 1) / BG_TI, (a.B + BG_TB - 1) / BG_TB);
+    hipLaunchKernelGGL((batch_products_kernel<2, true>), grid, dim3(256), 0, s, a.B, a.n, a.m, a.w, a.m, a.y, a.A, a.lda, a.active,
+                       a.q, a.l1, a.l1_scalar);
 }
 
 // ---------------------------------------------------------------------------------------------------------

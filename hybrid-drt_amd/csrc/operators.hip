@@ -351,7 +351,7 @@ int hipdrt_qp_batch(hipdrt_ctx* ctx, int B, int n, int p_batched, const double* 
         a.gsync = dgs.i();
     }
     HIPDRT_CHECK(dPpk.alloc(nmat * qp_ppk_doubles(n) * sizeof(double)));
-    launch_pack_p(st, (int)nmat, n, dP.d(), ldp, (long long)n * ldp, dPpk.d(), (long long)qp_ppk_doubles(n), qp_nchp(n));
+    launch_pack_p(st, (int)nmat, n, dP.d(), ldp, dPpk.d());
     a.Ppk = dPpk.d(); a.ppk_stride = p_batched ? (long long)qp_ppk_doubles(n) : 0; a.nchp = qp_nchp(n);
     HIPDRT_CHECK(dstate.alloc((size_t)B * (G > 1 ? G : 1) * qp_state_doubles(n) * sizeof(double)));
     a.state = dstate.d(); a.state_ld = qp_state_ld(n); a.state_stride = (long long)qp_state_doubles(n);
@@ -378,9 +378,15 @@ int hipdrt_weighted_gram(hipdrt_ctx* ctx, int B, int m, int n, const double* A, 
     if (l1) TRY(upload(dl1, l1, (size_t)n * sizeof(double), st));
     HIPDRT_CHECK(dP.alloc((size_t)B * n * n * sizeof(double)));
     HIPDRT_CHECK(dq.alloc((size_t)B * n * sizeof(double)));
-    launch_weighted_gram(st, B, m, n, dA.d(), n, dw.d(), db.d(), l2 ? dl2.d() : nullptr,
-                         l2_batched ? (long long)n * n : 0, n, l1 ? dl1.d() : nullptr, dP.d(), n, (long long)n * n,
-                         dq.d(), nullptr);
+    // one shared A, every problem, row-major P only; L2 as given (none: l2 = NULL)
+    PqArgs pq{};
+    pq.B = B; pq.m = m; pq.n = n; pq.A = dA.d(); pq.lda = n; pq.w = dw.d();
+    pq.P = dP.d(); pq.ldp = n; pq.p_stride = (long long)n * n;
+    pq.y = db.d(); pq.l1 = l1 ? dl1.d() : nullptr; pq.q = dq.d();
+    GramL2 g{};
+    g.l2 = l2 ? dl2.d() : nullptr; g.l2_stride = l2_batched ? (long long)n * n : 0; g.ldl2 = n;
+    launch_gram_l2(st, pq, g);
+    launch_qvec(st, pq);
     LAUNCH_OK();
     HIPDRT_CHECK(hipMemcpyAsync(P, dP.p, (size_t)B * n * n * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPDRT_CHECK(hipMemcpyAsync(q, dq.p, (size_t)B * n * sizeof(double), hipMemcpyDeviceToHost, st));

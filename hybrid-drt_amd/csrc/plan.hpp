@@ -159,6 +159,24 @@ struct hipdrt_plan : PlanShape {
         qa.G = G; qa.gsync = gsync.i(); qa.l_stride = (long long)qp_scratch_doubles(n, G);
         qa.waves = ctx ? ctx->qp_waves : -1;
     }
+    // The plan's own operands of the weighted normal equations, for the weights `wq` [B][m]: every staged spectrum that is
+    // still active, its P as packed tiles in its slot of Ppk, its q from rv and the plan's l1 vector.  A call site states only
+    // what differs.
+    PqArgs pq(const double* wq) const {
+        PqArgs a{};
+        a.B = B; a.m = m; a.n = n; a.A = rm.d(); a.lda = ldrm; a.a_stride = rm_stride; a.w = wq; a.active = active.i();
+        a.P = nullptr; a.ldp = ldp; a.p_stride = (long long)n * ldp; a.Ppk = Ppk.d(); a.ppk_stride = (long long)qp_ppk_doubles(n);
+        a.y = rv.d(); a.l1 = l1.d(); a.l1_scalar = 0.0; a.q = q.d();
+        return a;
+    }
+    // ... of spectrum b alone, `wb` [m] being that spectrum's weights: one problem on its own response matrix and its own slot
+    // of Ppk, every stride 0, whether it is still active or not (P only: y and q stay the batch's)
+    PqArgs pq_one(int b, const double* wb) const {
+        PqArgs a = pq(wb);
+        a.B = 1; a.A += (size_t)b * rm_stride; a.Ppk += (size_t)b * qp_ppk_doubles(n);
+        a.a_stride = a.p_stride = a.ppk_stride = 0; a.active = nullptr;
+        return a;
+    }
     // history
     int hist_b = -1, hist_cap = 0;
     DevBuf hist_x, hist_w, hist_rho, hist_qp, hist_rows;
@@ -237,6 +255,8 @@ PostSource step_source(const hipdrt_plan* p, int step, const double* w, const in
 // spectrum b alone.
 struct FinalP { GramL2 g; const double* w; };
 FinalP plan_final_p(const hipdrt_plan* p, int b, const PostSource& src);
+// out[n][n] (host) = the final P `f` of spectrum b, formed row-major in Ptmp without a packed copy; synchronises the stream
+int plan_final_p_to_host(hipdrt_plan* p, hipStream_t st, int b, const FinalP& f, double* out);
 // rows_dev[neval][ncol] in device memory (it sits at columns col_offset.. of the unknown vector, zero elsewhere) ->
 // dout[nb][nex * 16] = rows_i' P^-1 rows_i (not yet scaled by cs^2) and dstat[nb], of spectrum b alone (nb = 1) or, b = -1, of
 // the batch (nb = B).  The caller owns the scratch: Y = rows L^-T of the last factorisation stays in it.

@@ -428,13 +428,10 @@ int hipdrt_plan_get_step_p_matrix(hipdrt_plan* p, int step, int b, double* out) 
     HIPDRT_REQUIRE(step >= 0 && step < p->pf_steps, "step out of range of the recorded PFRT steps");
     HIPDRT_REQUIRE(b >= 0 && b < p->B, "spectrum index out of range");
     hipStream_t st; TRY(enter(p->ctx, &st));
-    const int n = p->n, m = p->m;
     DevBuf dw, dscratch;
     TRY(step_weights(p, step, st, dw, dscratch));
-    const FinalP f = plan_final_p(p, b, step_source(p, step, dw.d(), nullptr));
-    launch_gram_l2(st, 1, m, n, p->rm.d() + (size_t)b * p->rm_stride, p->ldrm, f.w, f.g, p->Ptmp.d(), p->ldp, 0, nullptr);
-    LAUNCH_OK();
-    return copy_strided(out, p->Ptmp.d(), n, n, p->ldp, st);      // (synchronises: dw may go)
+    // (synchronises: dw may go)
+    return plan_final_p_to_host(p, st, b, plan_final_p(p, b, step_source(p, step, dw.d(), nullptr)), out);
 } HIPDRT_CATCH
 
 int hipdrt_plan_pfrt_get_step(hipdrt_plan* p, int step, double* x, double* rho, double* s, double* rss, double* sum_log_w,

@@ -36,16 +36,15 @@ static int plan_hyper(hipdrt_plan* p, hipStream_t st, const FitState& fs_in, int
     const size_t premv_need = 3 * (size_t)(p->capacity > B ? p->capacity : B) * p->m * sizeof(double);
     // (the options of THIS loop decide -- a warm restart may switch outlier_p on or off against the plan's fit)
     const bool outl = fs_in.opts.outlier_p > 0.0;
-    if (B * 8 <= device_cus() && (size_t)p->m * p->n >= ((size_t)1 << 20) && !outl) {
-        if (p->premv.bytes < premv_need) HIPDRT_CHECK(p->premv.alloc(premv_need));
-        fs.premv = p->premv.d();
-    } else if (p->rm_stride == 0 && !outl && !(p->prepared && p->desc.vz_index >= 0)) {
-        // one response matrix and one variance matrix for the whole batch (every EIS plan, prepared plans without a vz_offset
-        // column): rm @ x and vmm @ resid^2 of all spectra as two batched products (hyper.hip: batch_products_kernel) -- for any
-        // batch size, so that a spectrum's bits do not depend on whether it is fitted alone or among a thousand
+    const bool spread = B * 8 <= device_cus() && (size_t)p->m * p->n >= ((size_t)1 << 20) && !outl;
+    // one response matrix and one variance matrix for the whole batch (every EIS plan, prepared plans without a vz_offset
+    // column): rm @ x and vmm @ resid^2 of all spectra as two batched products (hyper.hip: batch_products_kernel) -- for any
+    // batch size, so that a spectrum's bits do not depend on whether it is fitted alone or among a thousand
+    const bool batched = !spread && p->rm_stride == 0 && !outl && !(p->prepared && p->desc.vz_index >= 0);
+    if (spread || batched) {
         if (p->premv.bytes < premv_need) HIPDRT_CHECK(p->premv.alloc(premv_need));     // (a sub-batch view: a window of the parent's)
         fs.premv = p->premv.d();
-        fs.premv_batched = 1;
+        fs.premv_batched = batched;
     }
     return launch_hyper(st, fs, B, it);
 }
@@ -77,38 +76,51 @@ struct PhaseTimer {
 };
 }  // namespace
 
-// QP arguments of the outer loop: one P per spectrum in the packed tile layout, the loop's constraint vector
+// QP arguments of the loop, all but P and the active mask (pq_qp_step takes those from the normal equations it forms): the
+// plan's solution, scratch and counters, the loop's constraint vector
 static QpArgs loop_qp_args(hipdrt_plan* p, const hipdrt_qp_opts& qpo) {
     const int n = p->n;
     QpArgs qa{};
-    qa.B = p->B; qa.n = n; qa.ldp = p->ldp; qa.q = p->q.d(); qa.h = p->h.d(); qa.h_stride = 0;
+    qa.B = p->B; qa.n = n; qa.q = p->q.d(); qa.h = p->h.d(); qa.h_stride = 0;
     qa.L = p->L.d(); qa.ldl = p->ldl;
     p->qp_layout(p->B, qa);
     qa.x = p->x.d(); qa.iters = p->qp_iters.i(); qa.pcost = p->pcost.d(); qa.status = p->qp_status.i();
     qa.iters_accum = p->qp_iters_total.i(); qa.opts = qpo;
     qa.state = p->qpstate.d(); qa.state_ld = qp_state_ld(n); qa.state_stride = (long long)qp_state_doubles(n);
-    qa.P = nullptr; qa.p_stride = (long long)n * p->ldp; qa.active = p->active.i();
-    qa.Ppk = p->Ppk.d(); qa.ppk_stride = (long long)qp_ppk_doubles(n); qa.nchp = qp_nchp(n);
     return qa;
 }
 
-// One outer iteration of the staged batch on the weights `wq` the QP sees: P and q (phase 1, opened by the caller), the QP
-// (phase 2; workgroups dispatched longest first when an `order` buffer is given), the hyper-parameter step (phase 3)
-static int outer_iteration(hipdrt_plan* p, hipStream_t st, PhaseTimer& tm, const FitState& fs, const GramL2& g, QpArgs qa,
-                           const double* wq, int* order, int it) {
-    const int B = p->B, n = p->n, m = p->m;
-    launch_gram_l2(st, B, m, n, p->rm.d(), p->ldrm, wq, g, nullptr, p->ldp, (long long)n * p->ldp, p->active.i(),
-                   p->Ppk.d(), (long long)qp_ppk_doubles(n), qp_nchp(n), p->rm_stride);
-    launch_qvec(st, B, m, n, p->rm.d(), p->ldrm, wq, p->rv.d(), p->l1.d(), 0.0, p->q.d(), p->active.i(), p->rm_stride);
+// The step every QP of the fit consists of: P and q of the normal equations `pq` (phase 1, opened by the caller), then the QP
+// `qa` on them (phase 2; workgroups dispatched longest first when an `order` buffer is given); the phase of what follows (3) is
+// opened on return.  `one_p`: every problem has the same P (a shared response matrix, weights and hyper-parameters that do not
+// differ between the spectra) -- it is formed once and every QP reads that copy.
+static int pq_qp_step(hipStream_t st, PhaseTimer& tm, const PqArgs& pq, const GramL2& g, QpArgs qa, bool one_p,
+                      int* order = nullptr) {
+    PqArgs gp = pq;
+    if (one_p) { gp.B = 1; gp.p_stride = gp.ppk_stride = 0; }
+    launch_gram_l2(st, gp, g);
+    launch_qvec(st, pq);
     LAUNCH_OK();
     tm.mark(2);
-    if (order && B * sizeof(int) <= 48 * 1024) {     // dispatch order from the previous QP's iteration counts
-        launch_lpt_order(st, B, p->qp_iters.i(), p->active.i(), order);
+    // the QP reads P where and as the Gram launch has written it, and leaves out the spectra that launch left out
+    qa.P = gp.P; qa.ldp = gp.ldp; qa.p_stride = gp.p_stride;
+    qa.Ppk = gp.Ppk; qa.ppk_stride = gp.ppk_stride; qa.nchp = gp.Ppk ? qp_nchp(gp.n) : 0;
+    qa.active = pq.active;
+    if (order && pq.B * sizeof(int) <= 48 * 1024) {     // dispatch order from the previous QP's iteration counts
+        launch_lpt_order(st, pq.B, qa.iters, qa.active, order);
         qa.order = order;
     }
     TRY(launch_qp(st, qa));
     tm.mark(3);
-    TRY(plan_hyper(p, st, fs, B, it));
+    return HIPDRT_OK;
+}
+
+// One outer iteration of the staged batch on the weights `wq` the QP sees: pq_qp_step on the plan's own operands, one P per
+// spectrum, then the hyper-parameter step (phase 3)
+static int outer_iteration(hipdrt_plan* p, hipStream_t st, PhaseTimer& tm, const FitState& fs, const GramL2& g, const QpArgs& qa,
+                           const double* wq, int* order, int it) {
+    TRY(pq_qp_step(st, tm, p->pq(wq), g, qa, false, order));
+    TRY(plan_hyper(p, st, fs, p->B, it));
     LAUNCH_OK();
     return HIPDRT_OK;
 }
@@ -133,7 +145,9 @@ static int outer_loop(hipdrt_plan* p, hipStream_t st, PhaseTimer& tm, const FitS
 
 // calculate_pq's q with the final weights `wfin` (qphb.py:1154-1183), then the phase record of the call
 static int outer_finish(hipdrt_plan* p, hipStream_t st, PhaseTimer& tm, const double* wfin) {
-    launch_qvec(st, p->B, p->m, p->n, p->rm.d(), p->ldrm, wfin, p->rv.d(), p->l1.d(), 0.0, p->q.d(), nullptr, p->rm_stride);
+    PqArgs pq = p->pq(wfin);
+    pq.active = nullptr;       // every spectrum, stopped or not
+    launch_qvec(st, pq);
     LAUNCH_OK();
     tm.mark(-1);
     HIPDRT_CHECK(hipStreamSynchronize(st));
@@ -146,7 +160,7 @@ static int plan_fit_one(hipdrt_plan* p) {
     HIPDRT_REQUIRE(p, "plan is NULL");
     HIPDRT_REQUIRE(p->B >= 1, "no spectra staged (call hipdrt_plan_upload)");
     hipStream_t st; TRY(enter(p->ctx, &st));
-    const int B = p->B, n = p->n, m = p->m;
+    const int B = p->B, m = p->m;
     FitState fs = p->state();
     PhaseTimer tm(st);
     tm.mark(4);
@@ -159,20 +173,18 @@ static int plan_fit_one(hipdrt_plan* p) {
     const double dop_l2 = p->prepared ? p->desc.dop_l2_lambda_0 : 0.0;
     const GramL2 g = plan_l2(p, p->opts.iw_l2_lambda_0, p->opts.derivative_weights,
                              dop_l2 / p->opts.l2_lambda_0 * p->opts.iw_l2_lambda_0);
-    const long long astr = p->rm_stride;
-    const bool shared_rm = astr == 0;
-    // initialize_weights' QPs: the loop's arguments, but one P for the whole batch when the response matrix is shared, every
-    // spectrum taking part, and initialize_weights' own constraint vector
+    // initialize_weights' QPs: the loop's arguments with initialize_weights' own constraint vector, on the plan's normal
+    // equations with every spectrum taking part and a scalar l1
     QpArgs qa = loop_qp_args(p, p->opts.qp);
-    if (shared_rm) qa.p_stride = qa.ppk_stride = 0;
-    qa.active = nullptr;
     if (p->h_init.p) qa.h = p->h_init.d();
+    PqArgs iw = p->pq(p->w.d());
+    iw.active = nullptr; iw.l1 = nullptr; iw.l1_scalar = p->opts.iw_l1_lambda_0;
+    // with the weights launch_prep and launch_row_mask leave (the same for every spectrum, like s = s_0 and rho = rho_0) P
+    // differs between the spectra only where their response matrices do, and only q otherwise
+    const bool one_p = p->rm_stride == 0;
 
-    // ---- initialize_weights (qphb.py:1609-1681): one un-weighted, weakly penalised QP; P is the same for
-    //      every spectrum (weights = 1, s = s_0, rho = rho_0), only q differs -------------------------------
+    // ---- initialize_weights (qphb.py:1609-1681): one un-weighted, weakly penalised QP --------------------------------------
     tm.mark(1);
-    double* const Prow = nullptr;             // the QP reads P through its packed tile copy only (Ppk)
-    const long long pstr = (long long)n * p->ldp, pkstr = (long long)qp_ppk_doubles(n);
     const int nc = p->prepared ? p->desc.num_chrono : 0;
     const bool separately = p->prepared && p->desc.init_weights_separately && nc > 0 && nc < m;
     HIPDRT_REQUIRE(!(separately && p->opts.outlier_p > 0.0), "init_weights_separately with outlier_p is not built");
@@ -183,47 +195,25 @@ static int plan_fit_one(hipdrt_plan* p) {
         for (int blk = 0; blk < 2; ++blk) {
             tm.mark(1);
             launch_row_mask(st, B, m, bounds[blk], bounds[blk + 1], p->w.d());
-            launch_gram_l2(st, shared_rm ? 1 : B, m, n, p->rm.d(), p->ldrm, p->w.d(), g, Prow, p->ldp, shared_rm ? 0 : pstr,
-                           nullptr, p->Ppk.d(), shared_rm ? 0 : pkstr, qp_nchp(n), astr);
-            launch_qvec(st, B, m, n, p->rm.d(), p->ldrm, p->w.d(), p->rv.d(), nullptr, p->opts.iw_l1_lambda_0, p->q.d(),
-                        nullptr, astr);
-            LAUNCH_OK();
-            tm.mark(2);
-            TRY(launch_qp(st, qa));
-            tm.mark(3);
+            TRY(pq_qp_step(st, tm, iw, g, qa, one_p));
             TRY(launch_init_weights(st, fs, B, 2, bounds[blk], bounds[blk + 1]));
             LAUNCH_OK();
         }
         TRY(launch_init_weights(st, fs, B, 3));
         LAUNCH_OK();
     } else {
-    // one P for the whole batch when the response matrix is shared, else one per measurement
-    launch_gram_l2(st, shared_rm ? 1 : B, m, n, p->rm.d(), p->ldrm, p->w.d(), g, Prow, p->ldp, shared_rm ? 0 : pstr, nullptr,
-                   p->Ppk.d(), shared_rm ? 0 : pkstr, qp_nchp(n), astr);
-    launch_qvec(st, B, m, n, p->rm.d(), p->ldrm, p->w.d(), p->rv.d(), nullptr, p->opts.iw_l1_lambda_0, p->q.d(), nullptr,
-                astr);
-    LAUNCH_OK();
-    tm.mark(2);
-    TRY(launch_qp(st, qa));
-    tm.mark(3);
-    if (p->opts.outlier_p > 0.0) {
-        // qphb.py:1629-1656: weights from the first overfit with outlier down-weighting (variance matrix without each
-        // point's own residual), a second ridge QP weighted by them (per-spectrum P now), weights again
-        TRY(launch_init_weights(st, fs, B, 0));
+        TRY(pq_qp_step(st, tm, iw, g, qa, one_p));
+        if (p->opts.outlier_p > 0.0) {
+            // qphb.py:1629-1656: weights from the first overfit with outlier down-weighting (variance matrix without each
+            // point's own residual), a second ridge QP weighted by them (every spectrum its own P now), weights again
+            TRY(launch_init_weights(st, fs, B, 0));
+            LAUNCH_OK();
+            tm.mark(1);
+            PqArgs ow = iw; ow.w = p->est_w.d();
+            TRY(pq_qp_step(st, tm, ow, g, qa, false));
+        }
+        TRY(launch_init_weights(st, fs, B, 1));
         LAUNCH_OK();
-        tm.mark(1);
-        launch_gram_l2(st, B, m, n, p->rm.d(), p->ldrm, p->est_w.d(), g, Prow, p->ldp, (long long)n * p->ldp, nullptr,
-                       p->Ppk.d(), (long long)qp_ppk_doubles(n), qp_nchp(n), astr);
-        launch_qvec(st, B, m, n, p->rm.d(), p->ldrm, p->est_w.d(), p->rv.d(), nullptr, p->opts.iw_l1_lambda_0, p->q.d(),
-                    nullptr, astr);
-        LAUNCH_OK();
-        tm.mark(2);
-        qa.p_stride = pstr; qa.ppk_stride = pkstr;
-        TRY(launch_qp(st, qa));
-        tm.mark(3);
-    }
-    TRY(launch_init_weights(st, fs, B, 1));
-    LAUNCH_OK();
     }
     if (p->prepared && p->desc.weight_method == 1 && nc > 0 && nc < m) {
         // hybrid_weight_factor_method='weight' (drt1d.py:748-760): per-measurement row factors from the initial weights
@@ -400,10 +390,9 @@ int hipdrt_plan_continue(hipdrt_plan* p, const hipdrt_fit_opts* opts, double wei
     if (opts->outlier_p > 0.0 && !p->outlier_t.p) HIPDRT_CHECK(p->outlier_t.alloc((size_t)p->capacity * m * sizeof(double)));
     FitState fs = p->state();
     fs.opts = *opts; fs.continue_mode = 1; fs.min_iter = min_iter;
-    const long long astr = p->rm_stride;
     if (p->prepared && p->desc.vz_index >= 0) {
         if (!p->vz_entry.p) HIPDRT_CHECK(p->vz_entry.alloc((size_t)p->capacity * m * sizeof(double)));
-        launch_copy_column(st, B, m, p->rm.d(), astr, p->ldrm, p->desc.vz_index, p->vz_entry.d());
+        launch_copy_column(st, B, m, p->rm.d(), p->rm_stride, p->ldrm, p->desc.vz_index, p->vz_entry.d());
         LAUNCH_OK();
         fs.vz_entry = p->vz_entry.d();
     }

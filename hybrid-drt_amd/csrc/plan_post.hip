@@ -36,6 +36,13 @@ FinalP plan_final_p(const hipdrt_plan* p, int b, const PostSource& src) {
     }
     return f;
 }
+int plan_final_p_to_host(hipdrt_plan* p, hipStream_t st, int b, const FinalP& f, double* out) {
+    PqArgs pq = p->pq_one(b, f.w);
+    pq.P = p->Ptmp.d(); pq.Ppk = nullptr;
+    launch_gram_l2(st, pq, f.g);
+    LAUNCH_OK();
+    return copy_strided(out, p->Ptmp.d(), p->n, p->n, p->ldp, st);
+}
 
 int plan_quadratic_forms_dev(hipdrt_plan* p, const PostSource& src, int b, const double* rows_dev, int neval, int ncol,
                              int col_offset, DevBuf& scratch, DevBuf& dout, DevBuf& dstat) {
@@ -45,20 +52,19 @@ int plan_quadratic_forms_dev(hipdrt_plan* p, const PostSource& src, int b, const
     HIPDRT_REQUIRE(p->n <= 4096, "posterior variance: n <= 4096");
     hipStream_t st; TRY(enter(p->ctx, &st));
     const bool one = b >= 0;
-    const int n = p->n, m = p->m, nb = one ? 1 : p->B, first = one ? b : 0;
+    const int n = p->n, nb = one ? 1 : p->B;
     const int nex = (neval + 15) / 16, nchp = qp_nchp(n);
-    const long long pstr = (long long)qp_ppk_doubles(n);
-    // final P, packed tiles only: of every spectrum, or of spectrum b into its own slot of Ppk (all strides 0)
+    // final P, packed tiles only: of every spectrum, active or not, or of spectrum b into its own slot of Ppk (all strides 0)
     const FinalP f = plan_final_p(p, b, src);
-    double* ppk = p->Ppk.d() + (size_t)first * pstr;
-    launch_gram_l2(st, nb, m, n, p->rm.d() + (size_t)first * p->rm_stride, p->ldrm, f.w, f.g, nullptr, p->ldp, 0, nullptr, ppk,
-                   one ? 0 : pstr, nchp, one ? 0 : p->rm_stride);
+    PqArgs pq = one ? p->pq_one(b, f.w) : p->pq(f.w);
+    pq.active = nullptr;
+    launch_gram_l2(st, pq, f.g);
     LAUNCH_OK();
     DevBuf bex;
     HIPDRT_CHECK(bex.alloc((size_t)nex * nchp * 256 * sizeof(double)));
     HIPDRT_CHECK(dout.alloc((size_t)nb * nex * 16 * sizeof(double)));
     HIPDRT_CHECK(dstat.alloc((size_t)nb * sizeof(int)));
-    TRY(posterior_var_dev(st, {nb, n, ppk, one ? 0 : pstr, one, rows_dev, neval, ncol, col_offset, bex.d(), dout.d(), dstat.i()}, scratch));
+    TRY(posterior_var_dev(st, {nb, n, pq.Ppk, pq.ppk_stride, one, rows_dev, neval, ncol, col_offset, bex.d(), dout.d(), dstat.i()}, scratch));
     HIPDRT_CHECK(hipStreamSynchronize(st));      // bex is released on return
     return HIPDRT_OK;
 }
@@ -123,11 +129,7 @@ int hipdrt_plan_get_p_matrix(hipdrt_plan* p, int b, double* out) try {
     HIPDRT_REQUIRE(p && out, "NULL pointer");
     HIPDRT_REQUIRE(b >= 0 && b < p->B, "spectrum index out of range");
     hipStream_t st; TRY(enter(p->ctx, &st));
-    const int n = p->n, m = p->m;
-    const FinalP f = plan_final_p(p, b, live_source(p));
-    launch_gram_l2(st, 1, m, n, p->rm.d() + (size_t)b * p->rm_stride, p->ldrm, f.w, f.g, p->Ptmp.d(), p->ldp, 0, nullptr);
-    LAUNCH_OK();
-    return copy_strided(out, p->Ptmp.d(), n, n, p->ldp, st);
+    return plan_final_p_to_host(p, st, b, plan_final_p(p, b, live_source(p)), out);
 } HIPDRT_CATCH
 
 // out[b][i] = rows_i' P_b^-1 rows_i * cs_b^2 for the fitted batch, host rows in, host results out

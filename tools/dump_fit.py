@@ -72,11 +72,13 @@ out["sub_launches"] = np.array(list(rs["launches"].values()))
 ro = DRT(fixed_basis_tau=c1["tau"]).fit_eis_batch(c1["freq"], z1, outlier_p=0.05)
 for k in ("x", "weights", "outer_iters", "qp_iters_total"):
     out["outl_" + k] = ro[k]
+out["outl_launches"] = np.array(list(ro["launches"].values()))
 
 # warm restart of the C2 batch with a changed l2_lambda_0
 rc = d.continue_from_init(l2_lambda_0=142.0 / 4.0)
 for k in ("x", "weights", "rho", "q_vector", "outer_iters", "qp_iters_total"):
     out["cont_" + k] = rc[k]
+out["cont_launches"] = np.array(list(rc["launches"].values()))
 
 # prepared joint fit: initial weights per block, row factors by the 'weight' rule; then a restart with row factors and the
 # posterior entry points on the state it leaves
@@ -85,9 +87,11 @@ fj = dj.fit_hybrid(*synth.hybrid_measurement(seed=0), init_weights_separately=Tr
 qp = dj.qphb_params
 out["joint_x"], out["joint_weights"], out["joint_p"] = dj.cvx_result["x"], qp["true_weights"], fj["p_matrix"]
 out["joint_factors"] = np.array([qp["chrono_weight_factor"], qp["eis_weight_factor"]])
+out["joint_launches"] = np.array(list(dj._plan.timings()[1].values()))      # (fit_hybrid's result does not carry them)
 rj = dj.continue_from_init(weight_factor=1.3, eis_weight_factor=1.7, chrono_weight_factor=0.6, max_iter=3)
 for k in ("x", "weights", "rho", "q_vector", "outer_iters", "qp_iters_total"):
     out["jcont_" + k] = rj[k]
+out["jcont_launches"] = np.array(list(rj["launches"].values()))
 pc = dj.estimate_param_cov()
 out["jcont_param_cov"] = np.asarray(np.nan if pc is None else pc)
 dc = dj.estimate_distribution_cov(ppd=10)
