@@ -80,6 +80,13 @@ class PeakOpts(C.Structure):
                 ("fxx_var_floor", C.c_double), ("ext_left", C.c_int), ("ext_right", C.c_int)]
 
 
+class PeakProbOpts(C.Structure):
+    """hipdrt_peak_prob_opts (include/hipdrt.h)"""
+    _fields_ = [("bayes_cov", C.c_int), ("std_size", C.c_int), ("std_baseline", C.c_double), ("sigma_floor", C.c_int),
+                ("ext_left", C.c_int), ("ext_right", C.c_int), ("search", C.c_int), ("height", C.c_double),
+                ("prominence", C.c_double)]
+
+
 class PfrtOpts(C.Structure):
     """hipdrt_pfrt_opts (include/hipdrt.h)"""
     _fields_ = [("eval_sign", C.c_int), ("search", C.c_int), ("height", C.c_double), ("prominence", C.c_double),
@@ -324,6 +331,11 @@ SIGNATURES = {
                                _ip],
     "hipdrt_debug_find_peaks": [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.POINTER(PeakOpts), _ip, _ip, _dp, _dp, _dp, _ip, _ip,
                                 _ip, _dp, _dp, _dp],
+    "hipdrt_peak_prob_opts_default": [C.POINTER(PeakProbOpts)],
+    "hipdrt_plan_peak_trough_probs": [_vp, _dp, C.c_int, C.POINTER(PeakProbOpts), _dp, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, _dp,
+                                      _ip, _dp, _dp, _ip, _ip, _ip, _ip, _ip],
+    "hipdrt_debug_peak_trough_probs": [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(PeakProbOpts), C.c_int,
+                                       _ip, _ip, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _ip, _ip, _ip, _ip],
     "hipdrt_peak_resolve_opts_default": [C.POINTER(PeakResolveOpts)],
     "hipdrt_plan_resolve_peaks": [_vp, C.POINTER(PeakResolveIn), C.POINTER(PeakResolveOpts), C.POINTER(PeakResolveOut)],
     "hipdrt_plan_integrate_drt": [_vp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _ip, _ip, C.c_int, _dp, _ip],
@@ -405,7 +417,7 @@ SIGNATURES = {
                              _dp, _dp, _dp, _dp, _ip, _ip],
 }
 _RESTYPES = {"hipdrt_last_error": C.c_char_p, "hipdrt_stream": C.c_void_p, "hipdrt_default_fit_opts": None,
-             "hipdrt_default_kk_opts": None, "hipdrt_peak_opts_default": None,
+             "hipdrt_default_kk_opts": None, "hipdrt_peak_opts_default": None, "hipdrt_peak_prob_opts_default": None,
              "hipdrt_peak_resolve_opts_default": None, "hipdrt_pfrt_opts_default": None}
 
 _lib = None

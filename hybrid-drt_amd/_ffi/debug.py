@@ -8,7 +8,8 @@ import numpy as np
 from .abi import *            # noqa: F401,F403 (the constants and structures)
 from .abi import _check, _dp, _f64, _i32, _p, _pi
 from .args import Bound
-from .opts import _kk_outputs, _peak_out_args, _peak_outputs, _resolve_out_struct, _resolve_outputs, peak_opts, peak_resolve_opts, pfrt_opts
+from .opts import (_index_windows, _kk_outputs, _peak_out_args, _peak_outputs, _peak_prob_out_args, _peak_prob_outputs,
+                   _resolve_out_struct, _resolve_outputs, peak_opts, peak_prob_opts, peak_resolve_opts, pfrt_opts)
 
 
 class DebugHooks:
@@ -252,6 +253,26 @@ class DebugHooks:
         opts = opts if opts is not None else peak_opts()
         out = _peak_outputs(B, n, opts.method)
         _check(self._lib.hipdrt_debug_find_peaks(self._h, B, n, *[_p(r) for r in rows], C.byref(opts), *_peak_out_args(out)))
+        return out
+
+    def debug_peak_trough_probs(self, f=None, fx=None, fxx=None, var_f=None, var_fx=None, var_fxx=None, prob_in=None,
+                                opts: PeakProbOpts | None = None, ranges=None, want=None):
+        """tests: peak_trough_prob_kernel on host rows (B, neval) (hipdrt_debug_peak_trough_probs, include/hipdrt_debug.h) ->
+        dict as Plan.peak_trough_probs without status.  prob_in: the search alone on that row (no pp, tp, sigma); ranges:
+        (nranges, 2) index windows of search 2.  Raises when the kernel wrote outside an output."""
+        rows = [None if r is None else np.atleast_2d(_f64(r)) for r in (f, fx, fxx, var_f, var_fx, var_fxx, prob_in)]
+        first = next((r for r in rows if r is not None), None)
+        if first is None:
+            raise ValueError("the three mean rows, or prob_in")
+        B, n = first.shape
+        if any(r is not None and r.shape != (B, n) for r in rows):
+            raise ValueError("all rows must have one shape")
+        opts = opts if opts is not None else peak_prob_opts()
+        lo, hi = _index_windows(ranges)
+        nr = 0 if lo is None else lo.size
+        out = _peak_prob_outputs(B, n, opts.search, nr, want, given_prob=prob_in is not None)
+        _check(self._lib.hipdrt_debug_peak_trough_probs(self._h, B, n, *[_p(r) for r in rows], C.byref(opts), nr, _pi(lo), _pi(hi),
+                                                        *_peak_prob_out_args(out)))
         return out
 
     def debug_peak_resolve(self, f, fxx, x, ln_tau_find, ln_basis, ln_tau_out=None, basis_eps=1.0, keep=None, indices=None,

@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from .abi import (FitOpts, KkOpts, PeakOpts, PeakResolveOpts, PeakResolveOut, PfrtOpts, RESOLVE_OUTPUTS, _check, _p, _pi,
+from .abi import (FitOpts, KkOpts, PeakOpts, PeakProbOpts, PeakResolveOpts, PeakResolveOut, PfrtOpts, RESOLVE_OUTPUTS, _check, _p, _pi,
                   load_library)
 
 
@@ -47,6 +47,23 @@ def peak_opts(eval_sign=1, search=1, normalize=1, method='thresh', height=None, 
     o.prominence = float('nan') if prominence is None else float(prominence)
     o.prob_thresh, o.num_peaks, o.fxx_var_floor = float(prob_thresh), int(num_peaks or 0), float(fxx_var_floor)
     o.ext_left, o.ext_right = int(ext_left), int(ext_right)
+    return o
+
+
+PEAK_PROB_SEARCH = {'rows': 0, 'thresh': 1, 'ranges': 2}
+
+
+def peak_prob_opts(bayes_cov=True, std_size=5, std_baseline=0.1, sigma_floor=True, ext_left=-1, ext_right=-1, search='rows',
+                   height=None, prominence=None) -> PeakProbOpts:
+    """hipdrt_peak_prob_opts from the keywords of DRT.find_peaks_byprob (None <-> NaN: that condition is off); search 'rows'
+    (no search), 'thresh' (height and prominence) or 'ranges', or its number"""
+    o = PeakProbOpts()
+    load_library().hipdrt_peak_prob_opts_default(C.byref(o))
+    o.bayes_cov, o.std_size, o.std_baseline, o.sigma_floor = int(bool(bayes_cov)), int(std_size), float(std_baseline), int(bool(sigma_floor))
+    o.ext_left, o.ext_right = int(ext_left), int(ext_right)
+    o.search = PEAK_PROB_SEARCH[search] if isinstance(search, str) else int(search)
+    o.height = float('nan') if height is None else float(height)
+    o.prominence = float('nan') if prominence is None else float(prominence)
     return o
 
 
@@ -126,6 +143,41 @@ def _peak_out_args(out):
     g = out.get
     return (_pi(g("peak_sign")), _pi(g("keep")), _p(g("heights")), _p(g("prominences")), _p(g("probs")), _pi(g("left_bases")),
             _pi(g("right_bases")), _pi(g("count")), _p(g("used_prominence")), _p(g("peak_prob")), _p(g("curv_prob")))
+
+
+_PEAK_PROB_INT = ("keep", "left_bases", "right_bases")
+_PEAK_PROB_F64 = ("pp", "tp", "prob", "sigma", "heights", "prominences")
+
+
+def _peak_prob_outputs(B, n, search, nranges, want=None, given_prob=False):
+    """host arrays of the peak-probability entry points, poisoned like _peak_outputs'; only what the search mode writes is
+    allocated (0: the rows, 1: also the dense peak rows and count, 2: also range_peaks), and of that only `want` (None: all)"""
+    names = (() if given_prob else ("pp", "tp", "sigma")) + ("prob",)
+    if search == 1:
+        names += ("keep", "heights", "prominences", "left_bases", "right_bases", "count")
+    if search == 2:
+        names += ("range_peaks",)
+    out = {}
+    for k in names:
+        if want is not None and k not in want:
+            continue
+        shape = {"count": (B,), "range_peaks": (B, nranges), "sigma": (3, B, n)}.get(k, (B, n))
+        out[k] = np.full(shape, -77, dtype=np.int32) if k in _PEAK_PROB_INT + ("count", "range_peaks") else np.full(shape, np.nan)
+    return out
+
+
+def _peak_prob_out_args(out):
+    g = out.get
+    return (_p(g("pp")), _p(g("tp")), _p(g("prob")), _p(g("sigma")), _pi(g("keep")), _p(g("heights")), _p(g("prominences")),
+            _pi(g("left_bases")), _pi(g("right_bases")), _pi(g("count")), _pi(g("range_peaks")))
+
+
+def _index_windows(ranges):
+    """(lo, hi) int32 arrays of the index windows [lo, hi] of search 2; None: no windows"""
+    if ranges is None:
+        return None, None
+    r = np.asarray(ranges, dtype=np.int64).reshape(-1, 2)
+    return np.ascontiguousarray(r[:, 0], dtype=np.int32), np.ascontiguousarray(r[:, 1], dtype=np.int32)
 
 
 def _kk_outputs(B, nf):

@@ -9,7 +9,7 @@ import numpy as np
 from .abi import *            # noqa: F401,F403 (the constants and structures)
 from .abi import _check, _f64, _i32, _p, _pi, _vp, load_library
 from .args import Bound
-from .opts import (_kk_outputs, _peak_out_args, _peak_outputs, _resolve_out_struct, _resolve_outputs, default_fit_opts, peak_opts,
+from .opts import (_index_windows, _kk_outputs, _peak_out_args, _peak_outputs, _peak_prob_out_args, _peak_prob_outputs, _resolve_out_struct, _resolve_outputs, default_fit_opts, peak_opts,
                    peak_resolve_opts, pfrt_opts)
 
 
@@ -182,6 +182,25 @@ class Plan:
             raise ValueError("row_scale must have shape (B,)")
         _check(self._lib.hipdrt_plan_find_peaks(self._h, _p(ev), ev.size, C.byref(opts), _p(rs), *_peak_out_args(out),
                                                 _pi(out["status"])))
+        return out
+
+    def peak_trough_probs(self, ln_tau_eval, opts: PeakProbOpts, row_scale=None, ranges=None, want=None):
+        """hipdrt_plan_peak_trough_probs for the fitted batch -> dict of mu (3, B, neval) = f, fx, fxx (only when `want` names
+        it), pp, tp, prob (B, neval), sigma (3, B, neval) and, by opts.search, 1: the dense (B, neval) rows keep, heights, prominences, left_bases, right_bases and count (B,); 2:
+        range_peaks (B, nranges) for ranges = (nranges, 2) index windows [lo, hi] of the grid; status (B,) always.  row_scale
+        (B,): per-spectrum factor on the coefficient scale (prepared plans).  want: the names to download (None: all)."""
+        ev = _f64(ln_tau_eval).ravel()
+        lo, hi = _index_windows(ranges)
+        nr = 0 if lo is None else lo.size
+        out = _peak_prob_outputs(self.B, ev.size, opts.search, nr, want)
+        if want is not None and "mu" in want:
+            out["mu"] = np.full((3, self.B, ev.size), np.nan)
+        out["status"] = np.empty(self.B, dtype=np.int32)
+        rs = None if row_scale is None else _f64(row_scale)
+        if rs is not None and rs.shape != (self.B,):
+            raise ValueError("row_scale must have shape (B,)")
+        _check(self._lib.hipdrt_plan_peak_trough_probs(self._h, _p(ev), ev.size, C.byref(opts), _p(rs), nr, _pi(lo), _pi(hi),
+                                                       _p(out.get("mu")), *_peak_prob_out_args(out), _pi(out["status"])))
         return out
 
     def resolve_peaks(self, ln_tau_find, ln_tau_out=None, opts: PeakResolveOpts | None = None, find_opts: PeakOpts | None = None,

@@ -376,6 +376,31 @@ size_t peaks_lds_bytes(int neval, int method, int need_f, int num_peaks);    // 
 int launch_peaks(hipStream_t s, PeakArgs a, int B);
 void launch_scale_mul(hipStream_t s, int B, const double* x, const double* y, double* out);
 
+// peak_prob.hip: peak and trough probabilities of evaluated rows and the search on their product, one workgroup per spectrum
+// (all pointers device memory; an output may be null)
+struct PeakProbArgs {
+    int neval, p2, nranges;              // p2: power of two >= neval (set by launch_peak_prob); nranges counts for search 2 only
+    hipdrt_peak_prob_opts o;
+    const double *f, *fx, *fxx;          // [B][neval] orders 0, 1, 2
+    const double *var_f, *var_fx, *var_fxx;   // [B][ldv] e' inv(P) e (bayes_cov), scaled by cs^2 while staged
+    long long ldv;
+    const double* cs;                    // [B] or null (1)
+    const double* prob_in;               // [B][neval] or null: the search runs on this row, nothing else is read or formed
+    const int *fit_status, *var_status;  // [B] or null: a negative fit status / a non-zero variance status empties the spectrum
+    const int *range_lo, *range_hi;      // [nranges] index windows [lo, hi] of search 2
+    double *pp, *tp, *prob;              // [B][neval]
+    double* sigma;                       // [3][B][neval]
+    int* keep;                           // [B][neval]
+    double *heights, *prominences;
+    int *left_bases, *right_bases;
+    int* count;                          // [B]
+    int* range_peaks;                    // [B][nranges]
+};
+size_t peak_prob_lds_bytes(int neval);
+// the options, the windows and the LDS need of neval: HIPDRT_E_INVALID for what the kernel cannot take
+int peak_prob_check(const hipdrt_peak_prob_opts& o, int neval, int nranges, const int* range_lo, const int* range_hi);
+int launch_peak_prob(hipStream_t s, PeakProbArgs a, int B);
+
 // peak_resolve.hip: per-peak coefficients, distributions and resistances, one workgroup per spectrum (all pointers device memory;
 // an output may be null)
 struct PeakResolveArgs {

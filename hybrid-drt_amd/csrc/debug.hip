@@ -354,6 +354,49 @@ int hipdrt_debug_find_peaks(hipdrt_ctx* ctx, int B, int neval, const double* fxx
     return outs.back(st);
 } HIPDRT_CATCH
 
+// test hook (include/hipdrt_debug.h): peak_trough_prob_kernel as it is, on host rows.  Every output sits between two borders of marker bytes.
+int hipdrt_debug_peak_trough_probs(hipdrt_ctx* ctx, int B, int neval, const double* f, const double* fx, const double* fxx,
+                                   const double* var_f, const double* var_fx, const double* var_fxx, const double* prob_in,
+                                   const hipdrt_peak_prob_opts* opts, int nranges, const int* range_lo, const int* range_hi,
+                                   double* pp, double* tp, double* prob, double* sigma, int* keep, double* heights,
+                                   double* prominences, int* left_bases, int* right_bases, int* count, int* range_peaks) try {
+    HIPDRT_REQUIRE(ctx, "NULL pointer");
+    HIPDRT_REQUIRE(B >= 1 && B <= 65535 && neval >= 1 && neval <= (1 << 20), "1 <= B <= 65535, 1 <= neval <= 2^20");
+    hipdrt_peak_prob_opts o;
+    if (opts) o = *opts; else hipdrt_peak_prob_opts_default(&o);
+    TRY(peak_prob_check(o, neval, nranges, range_lo, range_hi));
+    const bool bayes = o.bayes_cov != 0;
+    HIPDRT_REQUIRE(prob_in || (f && fx && fxx), "the three mean rows, or prob_in");
+    HIPDRT_REQUIRE(prob_in || !bayes || (var_f && var_fx && var_fxx), "bayes_cov needs the three variance rows");
+    HIPDRT_REQUIRE(!prob_in || !(pp || tp || sigma), "a given prob row has no pp, tp or sigma");
+    const size_t bn = (size_t)B * neval;
+    const double* rows[7] = {prob_in, prob_in ? nullptr : f, prob_in ? nullptr : fx, prob_in ? nullptr : fxx,
+                             prob_in || !bayes ? nullptr : var_f, prob_in || !bayes ? nullptr : var_fx,
+                             prob_in || !bayes ? nullptr : var_fxx};
+    for (const double* r : rows)
+        if (r) for (size_t i = 0; i < bn; ++i) HIPDRT_REQUIRE(std::isfinite(r[i]), "non-finite input row");
+    if (o.search != 2) nranges = 0;
+    hipStream_t st; TRY(enter(ctx, &st));
+    DevBuf din[7], dlo, dhi;
+    for (int k = 0; k < 7; ++k) if (rows[k]) TRY(upload(din[k], rows[k], bn * sizeof(double), st));
+    if (nranges > 0) {
+        TRY(upload(dlo, range_lo, (size_t)nranges * sizeof(int), st)); TRY(upload(dhi, range_hi, (size_t)nranges * sizeof(int), st));
+    }
+    PeakProbArgs a{};
+    a.neval = neval; a.nranges = nranges; a.o = o; a.prob_in = din[0].d(); a.f = din[1].d(); a.fx = din[2].d(); a.fxx = din[3].d();
+    a.var_f = din[4].d(); a.var_fx = din[5].d(); a.var_fxx = din[6].d(); a.ldv = neval; a.range_lo = dlo.i(); a.range_hi = dhi.i();
+    GuardedOuts outs;
+    TRY(outs.want("pp", pp, bn, a.pp, st)); TRY(outs.want("tp", tp, bn, a.tp, st)); TRY(outs.want("prob", prob, bn, a.prob, st));
+    TRY(outs.want("sigma", sigma, 3 * bn, a.sigma, st)); TRY(outs.want("keep", keep, bn, a.keep, st));
+    TRY(outs.want("heights", heights, bn, a.heights, st)); TRY(outs.want("prominences", prominences, bn, a.prominences, st));
+    TRY(outs.want("left_bases", left_bases, bn, a.left_bases, st)); TRY(outs.want("right_bases", right_bases, bn, a.right_bases, st));
+    TRY(outs.want("count", count, (size_t)B, a.count, st));
+    TRY(outs.want("range_peaks", nranges > 0 ? range_peaks : nullptr, (size_t)B * nranges, a.range_peaks, st));
+    TRY(launch_peak_prob(st, a, B));
+    LAUNCH_OK();
+    return outs.back(st);
+} HIPDRT_CATCH
+
 // test hooks (include/hipdrt_debug.h): the two kernels of pfrt.hip as they are, on host arrays; outputs between borders of marker bytes
 int hipdrt_debug_pfrt_step(hipdrt_ctx* ctx, int B, int neval, const int* peak_sign, const double* heights, const double* prominences,
                            const double* f, const double* var_f, const double* var_fxx, double var_floor, int ext_left,

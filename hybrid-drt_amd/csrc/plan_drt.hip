@@ -1,6 +1,7 @@
 // The DRT chain on a finished fit of a plan (include/hipdrt.h): the evaluation rows of the batch and their variances (DrtRows),
-// and what is built on them -- DRT prediction and window integrals (csrc/predict.hip), peak finding (csrc/peaks.hip), per-peak
-// resolution (csrc/peak_resolve.hip) and the PFRT over the recorded steps of a PFRT fit (csrc/pfrt.hip).  The fitted state, the
+// and what is built on them -- DRT prediction and window integrals (csrc/predict.hip), peak finding (csrc/peaks.hip), the peak
+// and trough probabilities (csrc/peak_prob.hip), per-peak resolution (csrc/peak_resolve.hip) and the PFRT over the recorded
+// steps of a PFRT fit (csrc/pfrt.hip).  The fitted state, the
 // final P and the variance path come from plan_post.hip (plan.hpp).
 #include <cmath>
 #include <cstring>
@@ -78,7 +79,7 @@ static void merge_status(int B, const int* fit, const int* var, int* status) {
     for (int b = 0; b < B; ++b) status[b] = (fit[b] >= 0 && var && var[b] != 0) ? HIPDRT_PREDICT_NOT_PD : fit[b];
 }
 
-// What a DRT prediction leaves on the device (hipdrt_plan_predict_drt, hipdrt_plan_find_peaks): for every order asked for the
+// What a DRT prediction leaves on the device (hipdrt_plan_predict_drt, hipdrt_plan_find_peaks, hipdrt_plan_peak_trough_probs): for every order asked for the
 // signed evaluation rows and the mean rows of the batch, the normalisation scalars, and (want_var) e' inv(P_b) e of all rows from
 // one factorisation per spectrum, not yet scaled.
 struct DrtRows {
@@ -91,7 +92,7 @@ struct DrtRows {
     const double* var(int k) const { return dvar.d() + (size_t)k * neval; }             // row stride ldv()
     long long ldv() const { return (long long)((norders * neval + 15) / 16) * 16; }
 };
-// orders[norders] (norders 1 or 2): rows k * neval .. of dE and slab k of dmu belong to orders[k].  dev: ln(tau_eval) on the
+// orders[norders] (any number of them): rows k * neval .. of dE and slab k of dmu belong to orders[k].  dev: ln(tau_eval) on the
 // device.  row_scale: host [B] or null.  The timer is marked once, after the mean rows.
 // have_E: dE already holds the evaluation rows (a second call on the same grid, orders and sign).
 static int plan_drt_rows_dev(hipdrt_plan* p, const PostSource& src, const PredictBasis& pb, int neval, const int* orders,
@@ -134,7 +135,7 @@ static int plan_drt_rows_dev(hipdrt_plan* p, const PostSource& src, const Predic
         LAUNCH_OK();
     }
     tm.mark();
-    // sigma^2 = diag(E inv(P) E') from the variance path, fed the evaluation rows where they are (both orders as one row block)
+    // sigma^2 = diag(E inv(P) E') from the variance path, fed the evaluation rows where they are (all orders as one row block)
     DevBuf scratch;
     if (want_var) TRY(plan_quadratic_forms_dev(p, src, -1, R.dE.d(), norders * neval, width, ns, scratch, R.dvar, R.dvstat));
     return HIPDRT_OK;
@@ -239,6 +240,70 @@ int hipdrt_plan_find_peaks(hipdrt_plan* p, const double* ln_tau_eval, int neval,
     LAUNCH_OK();
     tm.mark();
     TRY(outs.back(st));
+    std::vector<int> hs(B), hv(B, 0);
+    HIPDRT_CHECK(hipMemcpyAsync(hs.data(), p->fit_status.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (need_var) HIPDRT_CHECK(hipMemcpyAsync(hv.data(), R.dvstat.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    if (status) merge_status(B, hs.data(), need_var ? hv.data() : nullptr, status);
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+// ---- peak and trough probabilities of the fitted batch (csrc/peak_prob.hip) ------------------------------------------------------
+void hipdrt_peak_prob_opts_default(hipdrt_peak_prob_opts* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->bayes_cov = 1; o->std_size = 5; o->std_baseline = 0.1; o->sigma_floor = 1; o->ext_left = -1; o->ext_right = -1;
+    o->search = 0; o->height = __builtin_nan(""); o->prominence = __builtin_nan("");
+}
+
+int hipdrt_plan_peak_trough_probs(hipdrt_plan* p, const double* ln_tau_eval, int neval, const hipdrt_peak_prob_opts* opts,
+                                  const double* row_scale, int nranges, const int* range_lo, const int* range_hi, double* mu,
+                                  double* pp, double* tp, double* prob, double* sigma, int* keep, double* heights,
+                                  double* prominences, int* left_bases, int* right_bases, int* count, int* range_peaks,
+                                  int* status) try {
+    HIPDRT_REQUIRE(p && ln_tau_eval, "NULL pointer");
+    PredictBasis pb;
+    TRY(predict_basis(p, pb));
+    hipdrt_peak_prob_opts o;
+    if (opts) o = *opts; else hipdrt_peak_prob_opts_default(&o);
+    // every check comes before the first launch
+    TRY(peak_prob_check(o, neval, nranges, range_lo, range_hi));
+    const int B = p->B, width = p->n - p->ns;
+    // predict_drt(tau, order=k) at its defaults (drt1d.py:3667): sign 1, not normalised
+    TRY(drt_check_request(pb, 1, 0, row_scale, "sign"));
+    TRY(drt_check_row_scale(row_scale, B));
+    const bool need_var = o.bayes_cov != 0;
+    const int orders[3] = {0, 1, 2};
+    if (o.search != 2) nranges = 0;
+    hipStream_t st; TRY(enter(p->ctx, &st));
+    DevBuf dev, dlo, dhi;
+    DrtRows R;
+    TRY(upload(dev, ln_tau_eval, (size_t)neval * sizeof(double), st));
+    if (nranges > 0) {
+        TRY(upload(dlo, range_lo, (size_t)nranges * sizeof(int), st)); TRY(upload(dhi, range_hi, (size_t)nranges * sizeof(int), st));
+    }
+    HIPDRT_CHECK(R.dE.alloc((size_t)3 * neval * width * sizeof(double)));
+    HIPDRT_CHECK(R.dmu.alloc((size_t)3 * B * neval * sizeof(double)));
+    const size_t bn = (size_t)B * neval;
+    PeakProbArgs a{};
+    DevOuts outs;
+    TRY(outs.want(pp, bn, a.pp)); TRY(outs.want(tp, bn, a.tp)); TRY(outs.want(prob, bn, a.prob)); TRY(outs.want(sigma, 3 * bn, a.sigma));
+    TRY(outs.want(keep, bn, a.keep)); TRY(outs.want(heights, bn, a.heights)); TRY(outs.want(prominences, bn, a.prominences));
+    TRY(outs.want(left_bases, bn, a.left_bases)); TRY(outs.want(right_bases, bn, a.right_bases)); TRY(outs.want(count, B, a.count));
+    TRY(outs.want(nranges > 0 ? range_peaks : nullptr, (size_t)B * nranges, a.range_peaks));
+    PredictTimer tm(p->ctx, st);
+    // one factorisation per spectrum, fed the rows of all three orders
+    TRY(plan_drt_rows_dev(p, live_source(p), pb, neval, orders, 3, 1, 0, row_scale, need_var, st, dev, R, tm));
+    a.neval = neval; a.nranges = nranges; a.o = o; a.f = R.mu(0); a.fx = R.mu(1); a.fxx = R.mu(2);
+    a.fit_status = p->fit_status.i(); a.range_lo = dlo.i(); a.range_hi = dhi.i();
+    if (need_var) {
+        a.var_f = R.var(0); a.var_fx = R.var(1); a.var_fxx = R.var(2); a.ldv = R.ldv(); a.cs = R.cs; a.var_status = R.dvstat.i();
+    }
+    TRY(launch_peak_prob(st, a, B));
+    LAUNCH_OK();
+    tm.mark();
+    TRY(outs.back(st));
+    if (mu) HIPDRT_CHECK(hipMemcpyAsync(mu, R.dmu.p, R.dmu.bytes, hipMemcpyDeviceToHost, st));
     std::vector<int> hs(B), hv(B, 0);
     HIPDRT_CHECK(hipMemcpyAsync(hs.data(), p->fit_status.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
     if (need_var) HIPDRT_CHECK(hipMemcpyAsync(hv.data(), R.dvstat.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));

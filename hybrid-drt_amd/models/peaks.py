@@ -5,13 +5,19 @@ on top of it sit DRT.find_peaks (hybdrt/models/drt1d.py:3753-3947), curvature.pe
 and the elementwise formula of DRTMD.predict_curv_prob (hybdrt/mapping/drtmd.py:1100-1104).  Everything acts on rows that are
 already evaluated: fxx (order 2), f (order 0) and their posterior variances.  No scipy: the product layer does not depend on it.
 
-The second half states csrc/peak_resolve.hip: peaks.find_troughs and peaks.estimate_peak_weight_distributions
+``peak_trough_probs_rows`` and its neighbours state csrc/peak_prob.hip: DRT.predict_peak_trough_probs, predict_peak_prob and
+find_peaks_byprob (drt1d.py:3655-3750) over surface.peak_prob / trough_prob (hybdrt/mapping/surface.py:265-350), filters.std_filter
+(hybdrt/filters/_filters.py:29-40) and peaks.find_peaks_byrange (hybdrt/peaks.py:423-441), on the rows of orders 0, 1, 2.
+
+The last part states csrc/peak_resolve.hip: peaks.find_troughs and peaks.estimate_peak_weight_distributions
 (hybdrt/peaks.py:92-217) under DRT.estimate_peak_coef, estimate_peak_drts, quantify_peaks (drt1d.py:3949-4111), split_r_p and
 integrate_drt (3586-3620).  Upstream's np.log(tau_i / trough) is taken as a difference of the ln grids (a rounding-level deviation).
 """
 import math
 
 import numpy as np
+
+from ..filters.ndfilters import reflect_index
 
 SQRT2 = 2 ** 0.5
 METHODS = ('thresh', 'prob')
@@ -192,6 +198,155 @@ def find_peaks_dense(fxx, f=None, var_fxx=None, var_f=None, search=1, method=0, 
     if 'probs' in info:
         out['probs'][idx] = info['probs']
     out['count'], out['used_prominence'] = len(kept), float(used)
+    return out
+
+
+# ---- peak and trough probabilities and the search on their product: the numpy statement of csrc/peak_prob.hip -------------------
+def _phi(z):
+    """scipy.stats.norm.cdf: Phi(z) = erfc(-z / sqrt 2) / 2"""
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return 0.5 * _erfc(-np.asarray(z, dtype=float) / SQRT2)
+
+
+def linear_quantile(srt, q):
+    """np.percentile(srt, 100 q) of an ascending row, numpy's default 'linear' method: the virtual index q (n - 1), interpolated
+    with numpy's _lerp -- a + (b - a) t, and b - (b - a) (1 - t) for t >= 0.5"""
+    n = len(srt)
+    vi = (n - 1) * q
+    lo = int(math.floor(vi))
+    hi = min(lo + 1, n - 1)
+    t, a, b = vi - lo, float(srt[lo]), float(srt[hi])
+    d = b - a
+    return b - d * (1.0 - t) if t >= 0.5 else a + d * t
+
+
+def sigma_floor_value(sigma):
+    """drt1d.py:3677-3678: np.median(sigma) - 1.5 * (np.percentile(sigma, 75) - np.percentile(sigma, 25)); the median is the
+    mean of the two middle samples for even n"""
+    srt = np.sort(np.asarray(sigma, dtype=float))
+    n = len(srt)
+    med = float(srt[n // 2]) if n % 2 else (float(srt[n // 2 - 1]) + float(srt[n // 2])) / 2.0
+    return med - 1.5 * (linear_quantile(srt, 0.75) - linear_quantile(srt, 0.25))
+
+
+def sigma_floor(sigma):
+    """drt1d.py:3676-3679 on one row: sigma[sigma < floor] = floor"""
+    sigma = np.array(sigma, dtype=float)
+    fl = sigma_floor_value(sigma)
+    sigma[sigma < fl] = fl
+    return sigma
+
+
+def _window_mean(row, size):
+    """scipy.ndimage.uniform_filter(row, size, mode='reflect') over masked_filter's mask of ones (whose filtered value is 1):
+    the terms of a window added in ascending offset, divided by size"""
+    n, h = len(row), size // 2
+    pos = np.arange(n)
+    tot = np.zeros(n)
+    for j in range(-h, h + 1):
+        tot = tot + row[reflect_index(pos + j, n)]
+    return tot / size
+
+
+def filtered_sigma(row, size=5, baseline=0.1):
+    """surface.py:272-274 with f_var=None: std_filter(row, size, mask=ones) + baseline * np.std(row).  std_filter
+    (_filters.py:29-40) is the windowed mean of the squared deviations from the windowed mean ROW, negatives set to 0, rooted."""
+    row = np.asarray(row, dtype=float)
+    if size < 3 or size % 2 != 1:
+        raise ValueError('size must be odd and at least 3')
+    mean = _window_mean(row, size)
+    var = _window_mean((row - mean) ** 2, size)
+    var[var < 0] = 0
+    return var ** 0.5 + baseline * np.std(row)
+
+
+def peak_trough_probs_rows(f, fx, fxx, var_f=None, var_fx=None, var_fxx=None, std_size=5, std_baseline=0.1, floor=True,
+                           ext_left=-1, ext_right=-1, sigma=None):
+    """DRT.predict_peak_trough_probs on evaluated rows -> (pp, tp, sigma (3, n)).  With the variances (bayes_cov=True; before
+    extend_var) sigma is the root after the clamp, floored per order (drt1d.py:3670-3680); without them the filtered sigma of
+    every row (surface.py:272-291); sigma (3, n): the rows as they enter the formulas, given.  surface.peak_prob
+    (constrain_sign=False) and trough_prob follow (surface.py:293-309, 336-350)."""
+    f, fx, fxx = (np.asarray(r, dtype=float) for r in (f, fx, fxx))
+    if sigma is not None:
+        sig = [np.asarray(s, dtype=float) for s in sigma]
+    elif var_f is None:
+        sig = [filtered_sigma(r, std_size, std_baseline) for r in (f, fx, fxx)]
+    else:
+        sig = [extend_var(v, ext_left, ext_right) ** 0.5 for v in (var_f, var_fx, var_fxx)]
+        if floor:
+            sig = [sigma_floor(s) for s in sig]
+    sf, sx, sxx = sig
+    sg = np.sign(f)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        fxx_prob = 1.0 - _phi(sg * fxx / sxx)
+        fx_prob = _phi((5.0 * sx - fx) / sx) - _phi((-5.0 * sx - fx) / sx)
+        f_prob = 1.0 - _phi((sf - np.abs(f)) / sf)
+        pp = f_prob * fx_prob * fxx_prob
+        tp = fx_prob * (1.0 - _phi(-sg * fxx / sxx))
+    return pp, tp, np.array(sig)
+
+
+def peak_prob_of(pp, tp):
+    """DRT.predict_peak_prob (drt1d.py:3718)"""
+    return pp * (1.0 - tp)
+
+
+def find_peaks_byrange(tau, prob, ranges):
+    """peaks.find_peaks_byrange (hybdrt/peaks.py:423-441): per range (t0, t1) np.argmax of prob with every sample outside it
+    set to zero -- the first maximum; index 0 when nothing in the window is positive"""
+    tau, prob = np.asarray(tau, dtype=float), np.asarray(prob, dtype=float)
+    out = []
+    for t0, t1 in ranges:
+        g = prob.copy()
+        g[(tau < t0) | (tau > t1)] = 0
+        out.append(int(np.argmax(g)))
+    return np.array(out, dtype=np.intp)
+
+
+def range_windows(tau, ranges):
+    """the index windows [lo, hi] (an (nranges, 2) array) that find_peaks_byrange's masks tau < t0, tau > t1 leave on a strictly
+    increasing grid; an empty window is (0, -1)"""
+    tau = np.asarray(tau, dtype=float)
+    if tau.ndim != 1 or np.any(np.diff(tau) <= 0):
+        raise ValueError('tau must be strictly increasing')
+    win = []
+    for t0, t1 in ranges:
+        lo, hi = int(np.sum(tau < t0)), len(tau) - 1 - int(np.sum(tau > t1))
+        win.append((lo, hi) if lo <= hi else (0, -1))
+    return np.array(win, dtype=np.intp).reshape(-1, 2)
+
+
+def find_peaks_byindex(prob, windows):
+    """find_peaks_byrange on index windows [lo, hi]: what peak_trough_prob_kernel's search 2 writes for one row"""
+    prob = np.asarray(prob, dtype=float)
+    out = []
+    for lo, hi in windows:
+        g = np.zeros(len(prob))
+        g[lo:hi + 1] = prob[lo:hi + 1]
+        out.append(int(np.argmax(g)))
+    return np.array(out, dtype=np.intp)
+
+
+def find_peaks_byprob_row(prob, height=None, prominence=None):
+    """find_peaks_byprob with thresholds (drt1d.py:3744): scipy.signal.find_peaks(prob, height=, prominence=) -> (indices, info);
+    like scipy, info carries peak_heights only with a height and prominences, left_bases, right_bases only with a prominence"""
+    idx, info = find_peaks_1d(prob, height, prominence)
+    keys = (('peak_heights',) if height is not None else ()) + \
+        (('prominences', 'left_bases', 'right_bases') if prominence is not None else ())
+    return idx, {k: info[k] for k in keys}
+
+
+def find_peaks_byprob_dense(prob, height=None, prominence=None):
+    """What peak_trough_prob_kernel's search 1 writes for one row, dense on the grid: dict(keep, heights, prominences, left_bases,
+    right_bases, count); heights and prominences are reported whether their condition is on or not"""
+    prob = np.asarray(prob, dtype=float)
+    n = len(prob)
+    idx, info = find_peaks_1d(prob, height, prominence)
+    out = dict(keep=np.zeros(n, dtype=np.int32), heights=np.zeros(n), prominences=np.zeros(n),
+               left_bases=np.full(n, -1, dtype=np.int32), right_bases=np.full(n, -1, dtype=np.int32), count=len(idx))
+    out['keep'][idx] = 1
+    out['heights'][idx], out['prominences'][idx] = info['peak_heights'], info['prominences']
+    out['left_bases'][idx], out['right_bases'][idx] = info['left_bases'], info['right_bases']
     return out
 
 

@@ -510,6 +510,90 @@ class PostFitMixin:
         (B, len(tau)): the probability of f > 0 with negative curvature (or the reverse), signed by f"""
         return self._map_probs('curv_prob_batch', 'curv_prob', tau, extend_var, prominence, height, sign, normalize)
 
+    # ---- peak and trough probabilities and find_peaks_byprob (drt1d.py:3655-3750; mapping/surface.py:265-350) --------------------
+    def _peak_prob_device(self, what, tau, bayes_cov, want, search='rows', height=None, prominence=None, ranges=None, x=None,
+                          p_matrix=None, prob=None):
+        """hipdrt_plan_peak_trough_probs on the grid tau (None: get_tau_eval(10)) -> (tau, outputs): f, fx, fxx as predict_drt
+        gives them at its defaults (sign 1, not normalised), with bayes_cov the clamp indices of extend_var=True; the ranges
+        become index windows here, from the very tau array (peaks.range_windows: tau must be strictly increasing).  Rows of a
+        failed fit (with bayes_cov: of a P that is not positive definite) are NaN and carry no peaks.  Last device batch only."""
+        if prob is not None:
+            raise NotImplementedError(f'{what}: the prob= override is not taken (the probability is formed on the device from the '
+                                      f'fit\'s own coefficients and P)')
+        plan, scales = self._predict_plan(what, x=x, p_matrix=p_matrix)
+        tau = self.get_tau_eval(10) if tau is None else np.asarray(tau, dtype=float)
+        windows = None if ranges is None else peaks.range_windows(tau, ranges)
+        if windows is not None and not 1 <= len(windows) <= 64:
+            raise ValueError(f'{what}: between 1 and 64 peak_tau_ranges')
+        ext = self._peak_ext(tau, bool(bayes_cov))
+        opts = _ffi.peak_prob_opts(bayes_cov=bayes_cov, ext_left=ext[0], ext_right=ext[1], search=search, height=height,
+                                   prominence=prominence)
+        return tau, plan.peak_trough_probs(np.log(tau), opts, row_scale=scales, ranges=windows, want=want)
+
+    def predict_peak_trough_probs_batch(self, tau=None, bayes_cov=True):
+        """DRT.predict_peak_trough_probs (drt1d.py:3655-3690) for every spectrum of the last fitted batch, on the device
+        (hipdrt_plan_peak_trough_probs; models/peaks.py peak_trough_probs_rows is the rule in numpy) -> (pp, tp), each (B, len(tau)).
+        bayes_cov: sigma of f, fx and fxx from ONE factorisation of every spectrum's final P, floored per order; else the windowed
+        standard deviation of every row."""
+        out = self._peak_prob_device('predict_peak_trough_probs', tau, bayes_cov, ('pp', 'tp'))[1]
+        return out['pp'], out['tp']
+
+    def predict_peak_prob_batch(self, tau=None, bayes_cov=True):
+        """DRT.predict_peak_prob (drt1d.py:3692-3718) for every spectrum of the last fitted batch -> (B, len(tau)): pp * (1 - tp)"""
+        return self._peak_prob_device('predict_peak_prob', tau, bayes_cov, ('prob',))[1]['prob']
+
+    def _find_peaks_byprob_device(self, tau, height, prominence, bayes_cov, peak_tau_ranges, return_info, **overrides):
+        what = 'find_peaks_byprob'
+        if peak_tau_ranges is not None:
+            tau, out = self._peak_prob_device(what, tau, bayes_cov, ('range_peaks',), search='ranges', ranges=peak_tau_ranges,
+                                              **overrides)
+            # (a failed fit has -1 in every slot: no peaks)
+            peak_indices = [r[r >= 0].astype(np.intp) for r in out['range_peaks']]
+            peak_info = [{} for _ in peak_indices]
+        else:
+            names = {'heights': 'peak_heights', 'prominences': 'prominences', 'left_bases': 'left_bases', 'right_bases': 'right_bases'}
+            want = ('keep',)
+            if return_info:
+                want += (('heights',) if height is not None else ()) + \
+                    (('prominences', 'left_bases', 'right_bases') if prominence is not None else ())
+            tau, out = self._peak_prob_device(what, tau, bayes_cov, want, search='thresh', height=height, prominence=prominence,
+                                              **overrides)
+            B = len(out['status'])
+            rows, cols = np.nonzero(out['keep'])
+            cut = np.searchsorted(rows, np.arange(1, B))
+            peak_indices = np.split(cols, cut)
+            sel = out['keep'] != 0
+            parts = {names[k]: np.split(out[k][sel].astype(np.intp) if k.endswith('bases') else out[k][sel], cut) for k in want[1:]}
+            peak_info = [{k: parts[k][b] for k in parts} for b in range(B)]
+        peak_tau = [tau[i] for i in peak_indices]
+        return (peak_tau, tau, peak_indices, peak_info) if return_info else peak_tau
+
+    def find_peaks_byprob_batch(self, tau=None, height=None, prominence=None, bayes_cov=True, peak_tau_ranges=None,
+                                return_info=False):
+        """DRT.find_peaks_byprob (drt1d.py:3720-3750) for every spectrum of the last fitted batch, probability and search on the
+        device -> a list of B arrays of peak tau; with return_info (peak_tau, tau, peak_indices, peak_info), the first and the
+        last two per-spectrum lists.  With peak_tau_ranges (at most 64) one peak per range (peaks.find_peaks_byrange) and empty
+        info dicts; else scipy.signal.find_peaks(prob, height=, prominence=), the info dicts with exactly scipy's keys for the
+        conditions given (peak_heights; prominences, left_bases, right_bases)."""
+        return self._find_peaks_byprob_device(tau, height, prominence, bayes_cov, peak_tau_ranges, return_info)
+
+    # single-member forms with the reference's signatures; ``b`` picks a member of the last batch
+    def predict_peak_trough_probs(self, tau=None, x=None, bayes_cov=True, p_matrix=None, b=0):
+        """DRT.predict_peak_trough_probs (drt1d.py:3655-3690) of member ``b`` of the last fit, from the device -> (pp, tp)"""
+        out = self._peak_prob_device('predict_peak_trough_probs', tau, bayes_cov, ('pp', 'tp'), x=x, p_matrix=p_matrix)[1]
+        return out['pp'][b], out['tp'][b]
+
+    def predict_peak_prob(self, tau=None, x=None, bayes_cov=True, p_matrix=None, b=0):
+        """DRT.predict_peak_prob (drt1d.py:3692-3718) of member ``b`` of the last fit, from the device"""
+        return self._peak_prob_device('predict_peak_prob', tau, bayes_cov, ('prob',), x=x, p_matrix=p_matrix)[1]['prob'][b]
+
+    def find_peaks_byprob(self, tau=None, x=None, prob=None, height=None, prominence=None, bayes_cov=True, p_matrix=None,
+                          peak_tau_ranges=None, return_info=False, b=0):
+        """DRT.find_peaks_byprob (drt1d.py:3720-3750) of member ``b`` of the last fit, from the device"""
+        res = self._find_peaks_byprob_device(tau, height, prominence, bayes_cov, peak_tau_ranges, True, x=x, p_matrix=p_matrix,
+                                             prob=prob)
+        return (res[0][b], res[1], res[2][b], res[3][b]) if return_info else res[0][b]
+
     # ---- per-peak coefficients, distributions and resistances (drt1d.py:3586-3620, 3949-4111; hybdrt/peaks.py:92-217) ------------
     def _resolve_device(self, what, tau_out, tau_find, peak_indices, sign, epsilon_factor, max_epsilon, min_epsilon,
                         epsilon_uniform, want, windows=None, find_peaks_kw=None, peak_tau=None, trough_tau=None,

@@ -755,6 +755,52 @@ int hipdrt_plan_find_peaks(hipdrt_plan* plan, const double* ln_tau_eval, int nev
                            int* left_bases, int* right_bases, int* count, double* used_prominence, double* peak_prob,
                            double* curv_prob, int* status);
 
+/* ---- peak and trough probabilities of the fitted batch and the peak search on them -------------------------------------------
+ * Options of DRT.predict_peak_trough_probs / predict_peak_prob / find_peaks_byprob (hybdrt/models/drt1d.py:3655-3750) over
+ * surface.peak_prob / trough_prob (hybdrt/mapping/surface.py:265-350, constrain_sign=False).                                   */
+typedef struct {
+    int bayes_cov;         /* 1; 1: sigma of every order from the fit's own P (drt1d.py:3670-3680), 0: the windowed standard
+                              deviation of the row itself (surface.py:272-291; no factorisation, no clamp, no floor)            */
+    int std_size;          /* 5; odd, >= 3: window of filters.std_filter (bayes_cov = 0)                                         */
+    double std_baseline;   /* 0.1; times np.std(row), added to the filtered sigma (bayes_cov = 0)                                */
+    int sigma_floor;       /* 1; bayes_cov = 1: sigma[sigma < floor] = floor with floor = np.median(sigma) - 1.5 * (np.percentile(
+                              sigma, 75) - np.percentile(sigma, 25)) per order (drt1d.py:3676-3679); 0: no floor                */
+    int ext_left;          /* -1 = off; extend_var (drt1d.py:3123-3140): var[:ext_left] = max(var[:ext_left], var[ext_left])     */
+    int ext_right;         /* -1 = off; var[ext_right:] = max(var[ext_right:], var[ext_right])                                  */
+    int search;            /* 0; 0: the rows only, 1: scipy.signal.find_peaks(prob, height, prominence) (drt1d.py:3744),
+                              2: peaks.find_peaks_byrange (hybdrt/peaks.py:423-441) on the index windows given                  */
+    double height;         /* NaN = no height condition (upstream's None)                                                       */
+    double prominence;     /* NaN = no prominence condition                                                                     */
+} hipdrt_peak_prob_opts;
+void hipdrt_peak_prob_opts_default(hipdrt_peak_prob_opts* o);
+/* pp, tp and prob = pp (1 - tp) of every spectrum of the fitted batch on the evaluation grid ln_tau_eval[neval], on the device.
+ * The rows f, fx, fxx (orders 0, 1, 2; sign 1, not normalised, as upstream's predict_drt defaults) are evaluated as
+ * hipdrt_plan_predict_drt evaluates them (same kernels, same bits); with bayes_cov sigma^2 = diag(E inv(P) E') scale_b^2 of all
+ * three orders comes from ONE factorisation per spectrum fed the three orders' rows, then extend_var's clamp, the root and the
+ * floor.  One workgroup per spectrum then forms, with Phi = scipy.stats.norm.cdf and sgn = np.sign,
+ *   pp = (1 - Phi((s_f - |f|) / s_f)) (Phi((5 s_x - fx) / s_x) - Phi((-5 s_x - fx) / s_x)) (1 - Phi(sgn(f) fxx / s_xx)),
+ *   tp = (Phi((5 s_x - fx) / s_x) - Phi((-5 s_x - fx) / s_x)) (1 - Phi(-sgn(f) fxx / s_xx))
+ * and runs the search (csrc/peak_prob.hip; hipdrt/models/peaks.py peak_trough_probs_rows, find_peaks_byprob_row and
+ * find_peaks_byrange are its numpy statement).  row_scale[B] (may be NULL) multiplies every spectrum's coefficient scale: a
+ * prepared plan runs at unit scale and its caller knows the scales (bayes_cov = 0 adds a baseline to sigma, so the scale cannot
+ * be applied afterwards).  range_lo, range_hi [nranges] (search 2; nranges <= 64): index windows [lo, hi] of the grid, lo = hi + 1
+ * an empty one; the peak of a window is np.argmax of prob with every sample outside it set to zero (the first maximum; index 0
+ * when nothing inside is positive and the window does not start at 0).
+ * out (host; any may be NULL): mu [3][B][neval] the rows f, fx, fxx (the bits of hipdrt_plan_predict_drt; NaN rows for a failed
+ * fit); pp, tp, prob [B][neval]; sigma [3][B][neval] of orders 0, 1, 2 as they enter the formulas; with
+ * search 1, dense on the grid as hipdrt_plan_find_peaks writes them: keep [B][neval] 0 / 1, heights, prominences [B][neval] zero
+ * where there is no peak, left_bases, right_bases [B][neval] -1 where there is none, count [B] (search 0, 2: no peaks);
+ * range_peaks [B][nranges] (search 2 only, else left untouched); status [B]: the fit's status, or HIPDRT_PREDICT_NOT_PD where
+ * bayes_cov needs sigma and P is not positive definite (upstream fails there).  A spectrum with a negative status has count 0,
+ * empty integer rows, NaN float rows and -1 range peaks.  HIPDRT_E_INVALID, before any launch: options out of range, a window
+ * outside the grid, nranges > 64, a neval whose rows do not fit one workgroup's LDS (neval <= 2048 fits).  Plain and prepared
+ * plans (hipdrt_plan_set_tau_basis first).  The result of a spectrum depends neither on B nor on its position in the batch.    */
+int hipdrt_plan_peak_trough_probs(hipdrt_plan* plan, const double* ln_tau_eval, int neval, const hipdrt_peak_prob_opts* opts,
+                                  const double* row_scale, int nranges, const int* range_lo, const int* range_hi, double* mu,
+                                  double* pp, double* tp, double* prob, double* sigma, int* keep, double* heights,
+                                  double* prominences, int* left_bases, int* right_bases, int* count, int* range_peaks,
+                                  int* status);
+
 /* ---- per-peak coefficients, distributions and resistances of the fitted batch ------------------------------------------------
  * Options of DRT.estimate_peak_coef / estimate_peak_drts / quantify_peaks (hybdrt/models/drt1d.py:3949-4111) over
  * peaks.find_troughs and peaks.estimate_peak_weight_distributions (hybdrt/peaks.py:92-217).                                    */

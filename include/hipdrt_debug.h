@@ -5,7 +5,8 @@
  * (in-kernel phase counters of a PROFILE build, occupancy queries).  Every hook takes a context: there is no process-wide
  * switch.  The kernels of the fit loop each have a hook that runs their launcher as it is on host arrays: hipdrt_debug_gram_l2
  * (Gram, q), hipdrt_debug_hyper_step (the hyper-parameter step in its three product forms), hipdrt_debug_kk_stats,
- * hipdrt_debug_apply_rows, hipdrt_debug_find_peaks, hipdrt_debug_peak_resolve, hipdrt_debug_response; so have the kernels that read
+ * hipdrt_debug_apply_rows, hipdrt_debug_find_peaks, hipdrt_debug_peak_trough_probs, hipdrt_debug_peak_resolve,
+ * hipdrt_debug_response; so have the kernels that read
  * a finished fit: hipdrt_debug_pfrt_step / _combine, hipdrt_debug_candidate_llh, and hipdrt_debug_posterior (the posterior variance and
  * covariance chain: packed rows, the 32-column factorisation with appended tile rows, the outer product).  The interior-point QP has
  * hipdrt_debug_qp (launch_qp in the fit loop's form: packed P only, active mask, dispatch order, iters_accum; s and z come back) and
@@ -151,6 +152,19 @@ int hipdrt_debug_find_peaks(hipdrt_ctx* ctx, int B, int neval, const double* fxx
                             const double* var_f, const hipdrt_peak_opts* opts, int* peak_sign, int* keep, double* heights,
                             double* prominences, double* probs, int* left_bases, int* right_bases, int* count,
                             double* used_prominence, double* peak_prob, double* curv_prob);
+
+/* test hook (tests/test_gpu_peak_prob.py): peak_trough_prob_kernel (csrc/peak_prob.hip) as it is, on host rows -- f, fx, fxx
+ * [B][neval]; var_f, var_fx, var_fxx [B][neval] (bayes_cov = 1; NULL with bayes_cov = 0): the variances before extend_var's
+ * clamp, the root and the floor, which the kernel applies.  prob_in [B][neval] non-NULL skips the probability stage and runs the
+ * search on the caller's row: the other input rows are then not read, and pp, tp and sigma must be NULL.  Ranges and outputs as
+ * hipdrt_plan_peak_trough_probs, any output may be NULL.  Non-finite input rows are refused.  Every device output has a border of
+ * marker bytes on either side: HIPDRT_E_NUMERIC when the kernel changed one.  HIPDRT_E_INVALID, and nothing is launched, for what
+ * the entry point refuses.                                                                                                     */
+int hipdrt_debug_peak_trough_probs(hipdrt_ctx* ctx, int B, int neval, const double* f, const double* fx, const double* fxx,
+                                   const double* var_f, const double* var_fx, const double* var_fxx, const double* prob_in,
+                                   const hipdrt_peak_prob_opts* opts, int nranges, const int* range_lo, const int* range_hi,
+                                   double* pp, double* tp, double* prob, double* sigma, int* keep, double* heights,
+                                   double* prominences, int* left_bases, int* right_bases, int* count, int* range_peaks);
 
 /* test hook (tests/test_gpu_peak_resolve.py): peak_resolve_kernel (csrc/peak_resolve.hip) as it is, on host arrays -- f, fxx
  * [B][nfind]; keep [B][nfind] (source 0) or indices [B][max_peaks] (source 1) or windows (source 2); x [B][copies * nb] the DRT
