@@ -37,7 +37,8 @@ typedef double v4d __attribute__((ext_vector_type(4)));
 static constexpr int CT = 16, CK = 64, CLD = 68, CW = 4;       // candidates per workgroup, k slab, slab leading dimension, wavefronts
 // static LDS of cand_llh_kernel: the two staging slabs and the reduction table
 static constexpr size_t kCandStaticLds = ((size_t)CT * CLD + (size_t)CW * 16 * CLD + (size_t)CW * CT * 4) * sizeof(double);
-static constexpr size_t kCandLdsTotal = 160 * 1024;           // LDS of a gfx950 CU available to one workgroup
+// LDS of a gfx950 CU available to one workgroup, static part included -- not kLdsLimit, which bounds the dynamic part alone
+static constexpr size_t kCandLdsTotal = 160 * 1024;
 
 static __host__ __device__ inline int cand_ldy(int m) { return (m + 31) / 32 * 32 + 4; }
 static inline size_t cand_dyn_lds(int m) { return (size_t)CT * cand_ldy(m) * sizeof(double); }

@@ -76,6 +76,18 @@ inline int set_lds_limit(const void* f, size_t bytes, const char* what) {
     return HIPDRT_OK;
 }
 
+// per-workgroup LDS of a gfx950 CU, less the static part; and the refusal of a launch that needs more (dims: the sizes that decide it)
+static constexpr size_t kLdsLimit = 160 * 1024 - 256;
+inline int lds_check(size_t bytes, const char* who, const char* dims) {
+    if (bytes <= kLdsLimit) return HIPDRT_OK;
+    set_error(std::string("invalid argument: ") + who + ": " + std::to_string(bytes) + " bytes of LDS needed (" + dims + "), " +
+              std::to_string(kLdsLimit) + " available");
+    return HIPDRT_E_INVALID;
+}
+
+// area of one tau basis function: sqrt(pi) / epsilon
+inline double basis_area(double eps) { return 1.7724538509055159 / eps; }
+
 }  // namespace hipdrt
 
 struct hipdrt_ctx {

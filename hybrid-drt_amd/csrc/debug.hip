@@ -8,6 +8,12 @@
 #include "debug_guard.hpp"
 #include "plan.hpp"
 
+// what the row hooks ask of every input row they upload (a null row: not read)
+static int require_finite(const double* row, size_t count) {
+    if (row) for (size_t i = 0; i < count; ++i) HIPDRT_REQUIRE(std::isfinite(row[i]), "non-finite input row");
+    return HIPDRT_OK;
+}
+
 extern "C" {
 
 int hipdrt_debug_qp_group(hipdrt_ctx* ctx, int members) try {
@@ -263,10 +269,9 @@ int hipdrt_debug_kk_stats(hipdrt_ctx* ctx, int B, int nf, const double* freq, co
     HIPDRT_REQUIRE(B >= 1 && B <= 65535 && nf >= 1 && nf <= 4096, "1 <= B <= 65535, 1 <= nf <= 4096");
     const int order = freq_monotone(freq, nf);
     HIPDRT_REQUIRE(order != 0, "the frequency grid must be strictly ascending or descending");
-    hipdrt_kk_opts o;
-    if (opts) o = *opts; else hipdrt_default_kk_opts(&o);
+    hipdrt_kk_opts o = opts_or(opts, hipdrt_default_kk_opts);
     TRY(kk_check_opts(o));
-    HIPDRT_REQUIRE(kk_lds_bytes(nf, 0, 0) <= 160 * 1024 - 256, "KK statistics: nf too large for one workgroup's LDS");
+    HIPDRT_REQUIRE(kk_lds_bytes(nf, 0, 0) <= kLdsLimit, "KK statistics: nf too large for one workgroup's LDS");
     hipStream_t st; TRY(enter(ctx, &st));
     DevBuf dfreq, dre, dim;
     TRY(upload(dfreq, freq, (size_t)nf * sizeof(double), st));
@@ -323,19 +328,17 @@ int hipdrt_debug_find_peaks(hipdrt_ctx* ctx, int B, int neval, const double* fxx
                             double* used_prominence, double* peak_prob, double* curv_prob) try {
     HIPDRT_REQUIRE(ctx && fxx, "NULL pointer");
     HIPDRT_REQUIRE(B >= 1 && B <= 65535 && neval >= 1 && neval <= (1 << 20), "1 <= B <= 65535, 1 <= neval <= 2^20");
-    hipdrt_peak_opts o;
-    if (opts) o = *opts; else hipdrt_peak_opts_default(&o);
+    hipdrt_peak_opts o = opts_or(opts, hipdrt_peak_opts_default);
     TRY(peak_check_opts(o, neval));
     const bool need_f = o.search == 0 || o.method == 2;
     HIPDRT_REQUIRE(!need_f || f, "a two-pass search and the map probabilities need the f rows");
     HIPDRT_REQUIRE(o.method == 0 || var_fxx, "methods 1 and 2 need var_fxx");
     HIPDRT_REQUIRE(o.method != 2 || var_f, "method 2 needs var_f");
-    HIPDRT_REQUIRE(peaks_lds_bytes(neval, o.method, need_f, o.num_peaks) <= 160 * 1024 - 256,
+    HIPDRT_REQUIRE(peaks_lds_bytes(neval, o.method, need_f, o.num_peaks) <= kLdsLimit,
                    "find_peaks: neval too large for one workgroup's LDS");
     const size_t bn = (size_t)B * neval;
     const double* rows[4] = {fxx, need_f ? f : nullptr, o.method >= 1 ? var_fxx : nullptr, o.method == 2 ? var_f : nullptr};
-    for (const double* r : rows)
-        if (r) for (size_t i = 0; i < bn; ++i) HIPDRT_REQUIRE(std::isfinite(r[i]), "non-finite input row");
+    for (const double* r : rows) TRY(require_finite(r, bn));
     hipStream_t st; TRY(enter(ctx, &st));
     DevBuf din[4];
     for (int k = 0; k < 4; ++k) if (rows[k]) TRY(upload(din[k], rows[k], bn * sizeof(double), st));
@@ -362,8 +365,7 @@ int hipdrt_debug_peak_trough_probs(hipdrt_ctx* ctx, int B, int neval, const doub
                                    double* prominences, int* left_bases, int* right_bases, int* count, int* range_peaks) try {
     HIPDRT_REQUIRE(ctx, "NULL pointer");
     HIPDRT_REQUIRE(B >= 1 && B <= 65535 && neval >= 1 && neval <= (1 << 20), "1 <= B <= 65535, 1 <= neval <= 2^20");
-    hipdrt_peak_prob_opts o;
-    if (opts) o = *opts; else hipdrt_peak_prob_opts_default(&o);
+    hipdrt_peak_prob_opts o = opts_or(opts, hipdrt_peak_prob_opts_default);
     TRY(peak_prob_check(o, neval, nranges, range_lo, range_hi));
     const bool bayes = o.bayes_cov != 0;
     HIPDRT_REQUIRE(prob_in || (f && fx && fxx), "the three mean rows, or prob_in");
@@ -373,8 +375,7 @@ int hipdrt_debug_peak_trough_probs(hipdrt_ctx* ctx, int B, int neval, const doub
     const double* rows[7] = {prob_in, prob_in ? nullptr : f, prob_in ? nullptr : fx, prob_in ? nullptr : fxx,
                              prob_in || !bayes ? nullptr : var_f, prob_in || !bayes ? nullptr : var_fx,
                              prob_in || !bayes ? nullptr : var_fxx};
-    for (const double* r : rows)
-        if (r) for (size_t i = 0; i < bn; ++i) HIPDRT_REQUIRE(std::isfinite(r[i]), "non-finite input row");
+    for (const double* r : rows) TRY(require_finite(r, bn));
     if (o.search != 2) nranges = 0;
     hipStream_t st; TRY(enter(ctx, &st));
     DevBuf din[7], dlo, dhi;
@@ -428,8 +429,7 @@ int hipdrt_debug_pfrt_combine(hipdrt_ctx* ctx, int B, int S, int neval_pfrt, int
                               double* raw_pfrt, double* post_prob) try {
     HIPDRT_REQUIRE(ctx && step_pfrt && rss && sum_log_w && factors && ln_tau_pfrt, "NULL pointer");
     HIPDRT_REQUIRE(B >= 1 && B <= 65535 && m >= 1, "1 <= B <= 65535, m >= 1");
-    hipdrt_pfrt_opts o;
-    if (opts) o = *opts; else hipdrt_pfrt_opts_default(&o);
+    hipdrt_pfrt_opts o = opts_or(opts, hipdrt_pfrt_opts_default);
     // every check comes before the first launch (and the first upload)
     TRY(pfrt_check(o, S, neval_pfrt, neval_out));
     HIPDRT_REQUIRE(!o.smooth || ln_tau_out, "smoothing needs the output grid");
@@ -519,8 +519,7 @@ int hipdrt_debug_peak_resolve(hipdrt_ctx* ctx, const hipdrt_debug_peak_resolve_a
                    "1 <= B <= 65535, 1 <= nfind, nb <= 2^20, 0 <= nout <= 2^20");
     HIPDRT_REQUIRE(q->copies == 1 || q->copies == 2, "copies must be 1 or 2");
     HIPDRT_REQUIRE(nout == 0 || (q->ln_tau_out && q->basis_eps > 0.0 && std::isfinite(q->basis_eps)), "an output grid needs ln_tau_out and basis_eps > 0");
-    hipdrt_peak_resolve_opts o;
-    if (q->opts) o = *q->opts; else hipdrt_peak_resolve_opts_default(&o);
+    hipdrt_peak_resolve_opts o = opts_or(q->opts, hipdrt_peak_resolve_opts_default);
     TRY(peak_resolve_check_opts(o));
     const int mp = o.max_peaks;
     HIPDRT_REQUIRE(q->copies == 2 || o.sign == 1, "sign must be 1 unless the DRT block holds a positive and a negative copy");
@@ -529,7 +528,7 @@ int hipdrt_debug_peak_resolve(hipdrt_ctx* ctx, const hipdrt_debug_peak_resolve_a
     HIPDRT_REQUIRE(q->source != 0 || q->keep, "source 0 needs the keep rows");
     TRY(peak_resolve_check_source(q->source, q->indices, B, mp, q->win_start, q->win_end, q->nwin, nfind));
     const size_t bn = (size_t)B * nfind, bx = (size_t)B * q->copies * nb;
-    for (size_t i = 0; i < bn; ++i) HIPDRT_REQUIRE(std::isfinite(q->f[i]) && std::isfinite(q->fxx[i]), "non-finite input row");
+    TRY(require_finite(q->f, bn)); TRY(require_finite(q->fxx, bn));
     for (size_t i = 0; i < bx; ++i) HIPDRT_REQUIRE(std::isfinite(q->x[i]), "non-finite coefficients");
     for (int i = 0; i < nfind; ++i) HIPDRT_REQUIRE(std::isfinite(q->ln_tau_find[i]), "non-finite find grid");
     for (int i = 0; i < nb; ++i) HIPDRT_REQUIRE(std::isfinite(q->ln_basis[i]), "non-finite basis grid");
@@ -555,9 +554,9 @@ int hipdrt_debug_peak_resolve(hipdrt_ctx* ctx, const hipdrt_debug_peak_resolve_a
         HIPDRT_CHECK(dE0.alloc((size_t)nout * nb * sizeof(double)));
         TRY(func_eval_dev(st, dlb.d(), nb, dlo.d(), nout, q->basis_eps, 0, 1.0, dE0.d(), nb));
         a.E0 = dE0.d(); a.lto = dlo.d();
-        a.basis_area = 1.7724538509055159 / q->basis_eps;
+        a.basis_area = basis_area(q->basis_eps);
     } else {
-        a.basis_area = q->basis_eps > 0.0 ? 1.7724538509055159 / q->basis_eps : 1.0;
+        a.basis_area = q->basis_eps > 0.0 ? basis_area(q->basis_eps) : 1.0;
     }
     const size_t bm = (size_t)B * mp;
     const hipdrt_peak_resolve_out& u = q->out;

@@ -28,7 +28,6 @@
 namespace hipdrt {
 namespace {
 
-constexpr size_t MP_LDS_LIMIT = 160 * 1024 - 256;      // per-workgroup LDS of a gfx950 CU, less what the runtime may keep
 constexpr size_t MP_BYTES_PER_POINT = 5 * sizeof(double) + 3 * sizeof(int);
 
 // x[b][j] /= sum_abs[b] * area (predict_r_p(absolute=True), then x / rp[:, None]: drtmd.py:816-817)
@@ -113,20 +112,10 @@ __global__ __launch_bounds__(PKT) void map_prob_kernel(MapProbArgs a) {
         if (a.vxx_out) a.vxx_out[o] = vxx[i];
         if (a.pk) {
             double p = 0.0;
-            if (sgn[i] != 0) {                                                    // curvature.py:46-53
-                const double h = sgn[i] > 0 ? -fxx[i] : fxx[i];
-                const double mp = np_min(prom[i], h);
-                p = np_min(upper_prob(mp, sqrt(vxx[i])), upper_prob(fabs(f[i]), sqrt(vf[i])));
-            }
+            if (sgn[i] != 0) p = map_peak_prob(prom[i], sgn[i] > 0 ? -fxx[i] : fxx[i], f[i], vxx[i], vf[i]);
             a.pk[o] = a.sign_now ? p * sf : p;
         }
-        if (a.curv) {                                                             // drtmd.py:1097-1104
-            double fp = upper_prob(-np_sign(fxx[i]) * f[i], sqrt(vf[i]));
-            double cp = upper_prob(-sf * fxx[i], sqrt(vxx[i]));
-            fp = 2.0 * np_max(fp - 0.5, 0.0);
-            cp = 2.0 * np_max(cp - 0.5, 0.0);
-            a.curv[o] = np_min(fp, cp) * sf;
-        }
+        if (a.curv) a.curv[o] = map_curv_prob(f[i], fxx[i], sf, vf[i], vxx[i]);
     }
 }
 
@@ -141,9 +130,9 @@ __global__ __launch_bounds__(256) void spread_sign_kernel(size_t n, const double
 // what map_prob_kernel stages for rows of n points; HIPDRT_E_UNSUPPORTED with the limit in the message when LDS does not hold it
 int map_prob_lds(int n, size_t* lds) {
     *lds = MP_BYTES_PER_POINT * (size_t)(n > 0 ? n : 0);
-    if (*lds > MP_LDS_LIMIT) {
+    if (*lds > kLdsLimit) {
         set_error("unsupported: map_predict stages " + std::to_string(MP_BYTES_PER_POINT) + " bytes per evaluation point in LDS: neval <= " +
-                  std::to_string(MP_LDS_LIMIT / MP_BYTES_PER_POINT) + ", got " + std::to_string(n));
+                  std::to_string(kLdsLimit / MP_BYTES_PER_POINT) + ", got " + std::to_string(n));
         return HIPDRT_E_UNSUPPORTED;
     }
     return HIPDRT_OK;

@@ -114,28 +114,17 @@ __global__ __launch_bounds__(PKT) void peak_trough_prob_kernel(PeakProbArgs a) {
         for (int i = tid; i < n; i += PKT)
             for (int k = 0; k < 3; ++k) {
                 m0[k * n + i] = mu[k][row + i];
-                if (bayes) {
-                    double v = var[k][(size_t)b * a.ldv + i];
-                    if (a.cs) v = v * c2;
-                    s0[k * n + i] = v;
-                }
+                if (bayes) s0[k * n + i] = var_scaled(var[k][(size_t)b * a.ldv + i], a.cs, c2, nullptr, 1.0);
             }
         __syncthreads();
         if (bayes) {
-            // extend_var's clamp (drt1d.py:3123-3140: the left part first, so the right bound may already be a clamped value), the root
+            // extend_var's clamp, then the root
             const int li = a.o.ext_left, ri = a.o.ext_right;
             for (int k = 0; k < 3; ++k) {
                 double* v = s0 + k * n;
-                const double vl = li >= 0 ? v[li] : 0.0;
-                double vr = ri >= 0 ? v[ri] : 0.0;
-                if (li >= 0 && ri >= 0 && ri < li) vr = np_max(vr, vl);
+                const ExtClamp c = ext_clamp(li, ri, li >= 0 ? v[li] : 0.0, ri >= 0 ? v[ri] : 0.0);
                 __syncthreads();
-                for (int i = tid; i < n; i += PKT) {
-                    double x = v[i];
-                    if (li >= 0 && i < li) x = np_max(x, vl);
-                    if (ri >= 0 && i >= ri) x = np_max(x, vr);
-                    v[i] = sqrt(x);
-                }
+                for (int i = tid; i < n; i += PKT) v[i] = sqrt(c.apply(v[i], i));
                 __syncthreads();
                 if (!a.o.sigma_floor) continue;
                 // the floor (drt1d.py:3676-3679) from the order statistics of the sorted row
@@ -251,15 +240,9 @@ __global__ __launch_bounds__(PKT) void peak_trough_prob_kernel(PeakProbArgs a) {
     if (tid == 0 && a.count) a.count[b] = (int)kept;
 }
 
-static int peak_prob_p2(int neval) {
-    int p2 = 2;
-    while (p2 < neval) p2 <<= 1;
-    return p2;
-}
-
 size_t peak_prob_lds_bytes(int neval) {
     const size_t n = (size_t)neval;
-    return (6 * n + (size_t)peak_prob_p2(neval)) * sizeof(double) + 3 * n * sizeof(int);
+    return (6 * n + (size_t)next_pow2(neval)) * sizeof(double) + 3 * n * sizeof(int);
 }
 
 int peak_prob_check(const hipdrt_peak_prob_opts& o, int neval, int nranges, const int* range_lo, const int* range_hi) {
@@ -276,13 +259,7 @@ int peak_prob_check(const hipdrt_peak_prob_opts& o, int neval, int nranges, cons
         for (int r = 0; r < nranges; ++r)
             HIPDRT_REQUIRE(range_lo[r] >= 0 && range_hi[r] < neval && range_lo[r] <= range_hi[r] + 1,
                            "ranges: 0 <= lo, hi < neval, lo <= hi + 1 (lo = hi + 1: an empty window)");
-    const size_t lds = peak_prob_lds_bytes(neval);
-    if (lds > kLdsLimit) {
-        set_error("invalid argument: peak_trough_probs: " + std::to_string(lds) + " bytes of LDS needed (neval), " +
-                  std::to_string(kLdsLimit) + " available");
-        return HIPDRT_E_INVALID;
-    }
-    return HIPDRT_OK;
+    return lds_check(peak_prob_lds_bytes(neval), "peak_trough_probs", "neval");
 }
 
 int launch_peak_prob(hipStream_t s, PeakProbArgs a, int B) {
@@ -291,7 +268,7 @@ int launch_peak_prob(hipStream_t s, PeakProbArgs a, int B) {
     HIPDRT_REQUIRE(a.prob_in || !a.o.bayes_cov || (a.var_f && a.var_fx && a.var_fxx), "peak_trough_probs: bayes_cov needs the three variance rows");
     HIPDRT_REQUIRE(!a.prob_in || !(a.pp || a.tp || a.sigma), "peak_trough_probs: a given prob row has no pp, tp or sigma");
     if (a.o.search != 2) a.nranges = 0;
-    a.p2 = peak_prob_p2(a.neval);
+    a.p2 = next_pow2(a.neval);
     const size_t lds = peak_prob_lds_bytes(a.neval);
     HIPDRT_REQUIRE(lds <= kLdsLimit, "peak_trough_probs: neval too large for one workgroup's LDS");
     if (int rc = set_lds(reinterpret_cast<const void*>(peak_trough_prob_kernel), lds, "peak_trough_prob_kernel")) return rc;

@@ -41,14 +41,13 @@
 #include <cmath>
 
 #include "hyper_dev.hpp"
+#include "peaks_dev.hpp"
 
 namespace hipdrt {
 
 static constexpr int RT = 256;
 static constexpr int RNW = RT / 64;
 typedef double v4d __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ double pr_sign(double x) { return x > 0.0 ? 1.0 : (x < 0.0 ? -1.0 : (x == 0.0 ? 0.0 : x)); }
 
 // (value, index) reductions over one wavefront; the smaller index wins a tie; every lane gets the result
 struct ValIdx { double v; int i; };
@@ -204,7 +203,7 @@ __global__ __launch_bounds__(RT) void peak_resolve_kernel(PeakResolveArgs a) {
     // ---- troughs (peaks.py:108-134): one wavefront per neighbouring pair ----
     for (int q = wv; q + 1 < P; q += RNW) {
         const int s = pk[q], e = pk[q + 1];
-        const double ls = pr_sign(f[s]), rs = pr_sign(f[e]);
+        const double ls = np_sign(f[s]), rs = np_sign(f[e]);
         int t;
         if (ls == rs) {
             const ValIdx m = wave_arg_range<false>(s, e, [&](int i) { return ls * f[i]; });
@@ -388,11 +387,7 @@ int launch_peak_resolve(hipStream_t s, PeakResolveArgs a, int B) {
     a.max_peaks = a.o.max_peaks;
     a.ld = peak_resolve_ld(a.nb);
     const size_t lds = peak_resolve_lds_bytes(a.nfind, a.nb, a.nout, a.max_peaks);
-    if (lds > kLdsLimit) {
-        set_error("invalid argument: peak_resolve: " + std::to_string(lds) + " bytes of LDS needed (nfind, nb, nout, max_peaks), " +
-                  std::to_string(kLdsLimit) + " available");
-        return HIPDRT_E_INVALID;
-    }
+    if (int rc = lds_check(lds, "peak_resolve", "nfind, nb, nout, max_peaks")) return rc;
     if (int rc = set_lds(reinterpret_cast<const void*>(peak_resolve_kernel), lds, "peak_resolve_kernel")) return rc;
     hipLaunchKernelGGL(peak_resolve_kernel, dim3(B), dim3(RT), lds, s, a);
     return 0;

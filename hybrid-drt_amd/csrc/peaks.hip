@@ -81,36 +81,22 @@ __global__ __launch_bounds__(PKT) void peaks_kernel(PeakArgs a) {
     for (int i = tid; i < n; i += PKT) {
         fxx[i] = a.fxx[row + i];
         if (l.f) f[i] = a.f[row + i];
-        if (l.var) {
-            double v = a.var_fxx[(size_t)b * a.ldv + i];
-            if (a.cs) v = v * c2;
-            if (a.norm) v = v / n2;
-            vxx[i] = v;
-        }
-        if (l.varf) {
-            double v = a.var_f[(size_t)b * a.ldv + i];
-            if (a.cs) v = v * c2;
-            if (a.norm) v = v / n2;
-            vf[i] = v;
-        }
+        if (l.var) vxx[i] = var_scaled(a.var_fxx[(size_t)b * a.ldv + i], a.cs, c2, a.norm, n2);
+        if (l.varf) vf[i] = var_scaled(a.var_f[(size_t)b * a.ldv + i], a.cs, c2, a.norm, n2);
         prom[i] = 0.0; sgn[i] = 0; lb[i] = -1; rb[i] = -1;
         if (l.var) prob[i] = 0.0;
     }
     __syncthreads();
-    // extend_var's clamp (drt1d.py:3123-3140: the left part first, so the right bound may already be a clamped value), then the floor
+    // extend_var's clamp, then the floor (of the curvature's variance only)
     if (l.var) {
         const int li = a.o.ext_left, ri = a.o.ext_right;
         const double floor_v = a.o.fxx_var_floor;
         for (int k = 0; k < (l.varf ? 2 : 1); ++k) {
             double* v = k ? vf : vxx;
-            const double vl = li >= 0 ? v[li] : 0.0;
-            double vr = ri >= 0 ? v[ri] : 0.0;
-            if (li >= 0 && ri >= 0 && ri < li) vr = np_max(vr, vl);
+            const ExtClamp c = ext_clamp(li, ri, li >= 0 ? v[li] : 0.0, ri >= 0 ? v[ri] : 0.0);
             __syncthreads();
             for (int i = tid; i < n; i += PKT) {
-                double x = v[i];
-                if (li >= 0 && i < li) x = np_max(x, vl);
-                if (ri >= 0 && i >= ri) x = np_max(x, vr);
+                double x = c.apply(v[i], i);
                 if (k == 0 && floor_v > 0.0 && x < floor_v) x = floor_v;
                 v[i] = x;
             }
@@ -152,9 +138,8 @@ __global__ __launch_bounds__(PKT) void peaks_kernel(PeakArgs a) {
         for (int i = tid; i < n; i += PKT) {
             if (sgn[i] == 0) continue;
             const double h = sgn[i] > 0 ? -fxx[i] : fxx[i];
-            const double mp = np_min(prom[i], h);
-            if (method == 1) prob[i] = 1.0 - erfc(mp / (sqrt(vxx[i]) * PK_SQRT2));
-            else prob[i] = np_min(upper_prob(mp, sqrt(vxx[i])), upper_prob(fabs(f[i]), sqrt(vf[i])));
+            if (method == 1) prob[i] = 1.0 - erfc(np_min(prom[i], h) / (sqrt(vxx[i]) * PK_SQRT2));
+            else prob[i] = map_peak_prob(prom[i], h, f[i], vxx[i], vf[i]);
         }
         __syncthreads();
         if (l.sort) {
@@ -189,13 +174,7 @@ __global__ __launch_bounds__(PKT) void peaks_kernel(PeakArgs a) {
         if (method == 2) {
             const double sf = np_sign(f[i]);
             if (a.peak_prob) a.peak_prob[o] = prob[i] * sf;
-            if (a.curv_prob) {
-                double fp = upper_prob(-np_sign(fxx[i]) * f[i], sqrt(vf[i]));
-                double cp = upper_prob(-sf * fxx[i], sqrt(vxx[i]));
-                fp = 2.0 * np_max(fp - 0.5, 0.0);
-                cp = 2.0 * np_max(cp - 0.5, 0.0);
-                a.curv_prob[o] = np_min(fp, cp) * sf;
-            }
+            if (a.curv_prob) a.curv_prob[o] = map_curv_prob(f[i], fxx[i], sf, vf[i], vxx[i]);
         }
     }
     kept = blk_sum<PKT>(kept, red);
@@ -205,16 +184,10 @@ __global__ __launch_bounds__(PKT) void peaks_kernel(PeakArgs a) {
     }
 }
 
-static int peaks_p2(int neval) {
-    int p2 = 2;
-    while (p2 < neval) p2 <<= 1;
-    return p2;
-}
-
 size_t peaks_lds_bytes(int neval, int method, int need_f, int num_peaks) {
     const PeakLds l = peak_lds(method, need_f, num_peaks);
     const size_t n = (size_t)neval;
-    size_t d = 2 * n + (l.f ? n : 0) + (l.var ? 2 * n : 0) + (l.varf ? n : 0) + (l.sort ? (size_t)peaks_p2(neval) : 0);
+    size_t d = 2 * n + (l.f ? n : 0) + (l.var ? 2 * n : 0) + (l.varf ? n : 0) + (l.sort ? (size_t)next_pow2(neval) : 0);
     return d * sizeof(double) + 3 * n * sizeof(int);
 }
 
@@ -238,13 +211,9 @@ int launch_peaks(hipStream_t s, PeakArgs a, int B) {
     HIPDRT_REQUIRE(a.o.method == 0 || a.var_fxx, "peaks: methods 1 and 2 need the curvature's variance");
     HIPDRT_REQUIRE(a.o.method != 2 || a.var_f, "peaks: method 2 needs the variance of f");
     if (a.o.search != 0 && a.o.method != 2) a.f = nullptr;      // not read: not staged
-    a.p2 = peaks_p2(a.neval);
+    a.p2 = next_pow2(a.neval);
     const size_t lds = peaks_lds_bytes(a.neval, a.o.method, a.f != nullptr, a.o.num_peaks);
-    if (lds > kLdsLimit) {
-        set_error("invalid argument: peaks: " + std::to_string(lds) + " bytes of LDS needed (neval, method), " +
-                  std::to_string(kLdsLimit) + " available");
-        return HIPDRT_E_INVALID;
-    }
+    if (int rc = lds_check(lds, "peaks", "neval, method")) return rc;
     if (int rc = set_lds(reinterpret_cast<const void*>(peaks_kernel), lds, "peaks_kernel")) return rc;
     hipLaunchKernelGGL(peaks_kernel, dim3(B), dim3(PKT), lds, s, a);
     return 0;

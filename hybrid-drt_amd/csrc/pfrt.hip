@@ -15,60 +15,46 @@
 #include <cmath>
 
 #include "hyper_dev.hpp"
+#include "peaks_dev.hpp"
 
 namespace hipdrt {
 
-static constexpr int FT = 256;
-static constexpr double PF_SQRT2 = 1.4142135623730951;      // 2 ** 0.5
 static constexpr double PF_LOG_2PI = 1.8378770664093453;    // np.log(2 * np.pi)
 
-// numpy's maximum and minimum (NaN goes through)
-__device__ __forceinline__ double pf_max(double a, double c) { return (a != a) ? a : ((c != c) ? c : (a > c ? a : c)); }
-__device__ __forceinline__ double pf_min(double a, double c) { return (a != a) ? a : ((c != c) ? c : (a < c ? a : c)); }
-
 // grid = B
-__global__ __launch_bounds__(FT) void pfrt_step_kernel(PfrtStepArgs a) {
+__global__ __launch_bounds__(PKT) void pfrt_step_kernel(PfrtStepArgs a) {
     const int b = blockIdx.x, tid = threadIdx.x, n = a.neval;
     const size_t row = (size_t)b * n;
     const bool no_var = a.var_status && a.var_status[b] != 0;
     if ((a.fit_status && a.fit_status[b] < 0) || no_var) {     // a failed fit, or a step P that is not positive definite
-        for (int i = tid; i < n; i += FT) a.out[row + i] = NAN;
+        for (int i = tid; i < n; i += PKT) a.out[row + i] = NAN;
         if (tid == 0 && a.bad && no_var) a.bad[b] = 1;
         return;
     }
     double c2 = 1.0, n2 = 1.0;
     if (a.cs) c2 = a.cs[b] * a.cs[b];
     if (a.norm) n2 = a.norm[b] * a.norm[b];
-    auto scaled = [&](const double* var, int i) {
-        double v = var[(size_t)b * a.ldv + i];
-        if (a.cs) v = v * c2;
-        if (a.norm) v = v / n2;
-        return v;
-    };
-    // extend_var's bounds (drt1d.py:3136-3139: the left part first, so the right bound may already be a clamped value)
+    auto scaled = [&](const double* var, int i) { return var_scaled(var[(size_t)b * a.ldv + i], a.cs, c2, a.norm, n2); };
+    // extend_var's bounds, from the scaled rows in global memory
     const int li = a.ext_left, ri = a.ext_right;
-    double vl[2] = {0.0, 0.0}, vr[2] = {0.0, 0.0};
+    ExtClamp c[2];
     for (int k = 0; k < 2; ++k) {
         const double* var = k ? a.var_fxx : a.var_f;
-        if (li >= 0) vl[k] = scaled(var, li);
-        if (ri >= 0) vr[k] = scaled(var, ri);
-        if (li >= 0 && ri >= 0 && ri < li) vr[k] = pf_max(vr[k], vl[k]);
+        c[k] = ext_clamp(li, ri, li >= 0 ? scaled(var, li) : 0.0, ri >= 0 ? scaled(var, ri) : 0.0);
     }
-    for (int i = tid; i < n; i += FT) {
+    for (int i = tid; i < n; i += PKT) {
         double p = 0.0;
         if (a.peak_sign[row + i] != 0) {
             double v[2];
             for (int k = 0; k < 2; ++k) {
-                double x = scaled(k ? a.var_fxx : a.var_f, i);
-                if (li >= 0 && i < li) x = pf_max(x, vl[k]);
-                if (ri >= 0 && i >= ri) x = pf_max(x, vr[k]);
+                double x = c[k].apply(scaled(k ? a.var_fxx : a.var_f, i), i);
                 if (a.floor > 0.0 && x < a.floor) x = a.floor;
                 v[k] = x;
             }
-            const double mp = pf_min(a.prominences[row + i], a.heights[row + i]);
-            const double f_prob = 1.0 - erfc(fabs(a.f[row + i]) / (sqrt(v[0]) * PF_SQRT2));
-            const double fxx_prob = 1.0 - erfc(mp / (sqrt(v[1]) * PF_SQRT2));
-            p = pf_min(f_prob, fxx_prob);
+            const double mp = np_min(a.prominences[row + i], a.heights[row + i]);
+            const double f_prob = 1.0 - erfc(fabs(a.f[row + i]) / (sqrt(v[0]) * PK_SQRT2));
+            const double fxx_prob = 1.0 - erfc(mp / (sqrt(v[1]) * PK_SQRT2));
+            p = np_min(f_prob, fxx_prob);
         }
         a.out[row + i] = p;
     }
@@ -80,7 +66,7 @@ int launch_pfrt_step(hipStream_t s, const PfrtStepArgs& a, int B) {
     HIPDRT_REQUIRE(std::isfinite(a.floor), "fxx_var_floor must be finite");
     HIPDRT_REQUIRE(a.ext_left >= -1 && a.ext_left < a.neval && a.ext_right >= -1 && a.ext_right < a.neval,
                    "ext_left and ext_right: an index of the evaluation grid, or -1");
-    hipLaunchKernelGGL(pfrt_step_kernel, dim3(B), dim3(FT), 0, s, a);
+    hipLaunchKernelGGL(pfrt_step_kernel, dim3(B), dim3(PKT), 0, s, a);
     return HIPDRT_OK;
 }
 
@@ -89,9 +75,9 @@ int launch_pfrt_step(hipStream_t s, const PfrtStepArgs& a, int B) {
 size_t pfrt_combine_lds_bytes(int S, int np, int nout) { return ((size_t)2 * np + (size_t)3 * nout + (size_t)S) * sizeof(double); }
 
 // grid = B
-__global__ __launch_bounds__(FT) void pfrt_combine_kernel(PfrtCombineArgs a) {
+__global__ __launch_bounds__(PKT) void pfrt_combine_kernel(PfrtCombineArgs a) {
     extern __shared__ double sm[];
-    __shared__ double red[FT];
+    __shared__ double red[PKT];
     const int b = blockIdx.x, B = gridDim.x, tid = threadIdx.x, S = a.S, np = a.np, nout = a.nout;
     double* acc = sm;
     double* ltp = acc + np;
@@ -101,16 +87,16 @@ __global__ __launch_bounds__(FT) void pfrt_combine_kernel(PfrtCombineArgs a) {
     double* post = res + nout;
 
     if ((a.fit_status && a.fit_status[b] < 0) || (a.bad && a.bad[b] != 0)) {
-        for (int k = tid; k < nout; k += FT) if (a.pfrt) a.pfrt[(size_t)b * nout + k] = NAN;
-        for (int j = tid; j < np; j += FT) if (a.raw) a.raw[(size_t)b * np + j] = NAN;
-        for (int i = tid; i < S; i += FT) if (a.post) a.post[(size_t)i * B + b] = NAN;
+        for (int k = tid; k < nout; k += PKT) if (a.pfrt) a.pfrt[(size_t)b * nout + k] = NAN;
+        for (int j = tid; j < np; j += PKT) if (a.raw) a.raw[(size_t)b * np + j] = NAN;
+        for (int i = tid; i < S; i += PKT) if (a.post) a.post[(size_t)i * B + b] = NAN;
         return;
     }
-    for (int j = tid; j < np; j += FT) ltp[j] = a.ltp[j];
-    for (int k = tid; k < nout; k += FT) lto[k] = a.smooth ? a.lto[k] : 0.0;
+    for (int j = tid; j < np; j += PKT) ltp[j] = a.ltp[j];
+    for (int k = tid; k < nout; k += PKT) lto[k] = a.smooth ? a.lto[k] : 0.0;
 
     // ---- posterior weights of the steps (drt1d.py:2730-2749) ----
-    for (int i = tid; i < S; i += FT) {
+    for (int i = tid; i < S; i += PKT) {
         const size_t o = (size_t)i * a.ld_sum + b;
         const double llh = (a.c - a.alpha_n * log(a.beta_0 + 0.5 * a.rss[o])) + a.slw[o];
         const double z = (a.ln_factors[i] - a.prior_mu) / a.prior_sigma;
@@ -118,9 +104,9 @@ __global__ __launch_bounds__(FT) void pfrt_combine_kernel(PfrtCombineArgs a) {
     }
     __syncthreads();
     double mx = post[0];
-    for (int i = 1; i < S; ++i) mx = pf_max(mx, post[i]);
+    for (int i = 1; i < S; ++i) mx = np_max(mx, post[i]);
     __syncthreads();
-    for (int i = tid; i < S; i += FT) post[i] = exp((post[i] - mx) * a.n_eff);
+    for (int i = tid; i < S; i += PKT) post[i] = exp((post[i] - mx) * a.n_eff);
     __syncthreads();
     double area = post[0];
     if (S > 1) {
@@ -128,13 +114,13 @@ __global__ __launch_bounds__(FT) void pfrt_combine_kernel(PfrtCombineArgs a) {
         for (int i = 0; i + 1 < S; ++i) area += ((a.ln_factors[i + 1] - a.ln_factors[i]) * (post[i + 1] + post[i])) / 2.0;
     }
     __syncthreads();
-    for (int i = tid; i < S; i += FT) post[i] = post[i] / area;
+    for (int i = tid; i < S; i += PKT) post[i] = post[i] / area;
     __syncthreads();
     double psum = 0.0;
     for (int i = 0; i < S; ++i) psum += post[i];
 
     // ---- the weighted sum over the steps, ascending ----
-    for (int j = tid; j < np; j += FT) {
+    for (int j = tid; j < np; j += PKT) {
         double t = 0.0;
         for (int i = 0; i < S; ++i) t += post[i] * a.step_pfrt[(size_t)i * a.ld_step + (size_t)b * np + j];
         acc[j] = t / psum;
@@ -144,7 +130,7 @@ __global__ __launch_bounds__(FT) void pfrt_combine_kernel(PfrtCombineArgs a) {
     // ---- smoothing: row k of exp(-(eps |ln tau_out_k - ln tau_pfrt_j|)^(2 order)) times the accumulator (zeros add nothing) ----
     if (a.smooth) {
         const double ex = 2.0 * a.smooth_order;
-        for (int k = tid; k < nout; k += FT) {
+        for (int k = tid; k < nout; k += PKT) {
             double t = 0.0;
             for (int j = 0; j < np; ++j) {
                 const double r = acc[j];
@@ -153,16 +139,16 @@ __global__ __launch_bounds__(FT) void pfrt_combine_kernel(PfrtCombineArgs a) {
             v[k] = t;
         }
     } else {
-        for (int k = tid; k < nout; k += FT) v[k] = acc[k];
+        for (int k = tid; k < nout; k += PKT) v[k] = acc[k];
     }
     __syncthreads();
 
     // ---- integrate_peaks (models/pfrt.py:22-46): every contiguous range of v >= threshold becomes one value at its maximum ----
     if (a.integrate) {
         const double thr = a.thr;
-        for (int k = tid; k < nout; k += FT) res[k] = 0.0;
+        for (int k = tid; k < nout; k += PKT) res[k] = 0.0;
         __syncthreads();
-        for (int k = tid; k < nout; k += FT) {
+        for (int k = tid; k < nout; k += PKT) {
             if (!(v[k] >= thr) || (k > 0 && v[k - 1] >= thr)) continue;
             int e = k, pk = k;
             while (e < nout && v[e] >= thr) { if (v[e] > v[pk]) pk = e; ++e; }
@@ -175,28 +161,28 @@ __global__ __launch_bounds__(FT) void pfrt_combine_kernel(PfrtCombineArgs a) {
             res[pk] = ar;
         }
         __syncthreads();
-        for (int k = tid; k < nout; k += FT) v[k] = res[k];
+        for (int k = tid; k < nout; k += PKT) v[k] = res[k];
         __syncthreads();
     }
 
     // ---- tot / np.max(tot): an all-zero row gives NaN, as upstream ----
     if (a.normalize) {
         double m = -INFINITY;
-        for (int k = tid; k < nout; k += FT) m = pf_max(m, v[k]);
+        for (int k = tid; k < nout; k += PKT) m = np_max(m, v[k]);
         red[tid] = m;
         __syncthreads();
-        for (int w = FT / 2; w > 0; w >>= 1) {
-            if (tid < w) red[tid] = pf_max(red[tid], red[tid + w]);
+        for (int w = PKT / 2; w > 0; w >>= 1) {
+            if (tid < w) red[tid] = np_max(red[tid], red[tid + w]);
             __syncthreads();
         }
         m = red[0];
-        for (int k = tid; k < nout; k += FT) v[k] = v[k] / m;      // (every thread scales the entries it wrote or copied itself)
+        for (int k = tid; k < nout; k += PKT) v[k] = v[k] / m;      // (every thread scales the entries it wrote or copied itself)
     }
 
     // ---- the dense rows: the only global stores ----
-    for (int k = tid; k < nout; k += FT) if (a.pfrt) a.pfrt[(size_t)b * nout + k] = v[k];
-    for (int j = tid; j < np; j += FT) if (a.raw) a.raw[(size_t)b * np + j] = acc[j];
-    for (int i = tid; i < S; i += FT) if (a.post) a.post[(size_t)i * B + b] = post[i];
+    for (int k = tid; k < nout; k += PKT) if (a.pfrt) a.pfrt[(size_t)b * nout + k] = v[k];
+    for (int j = tid; j < np; j += PKT) if (a.raw) a.raw[(size_t)b * np + j] = acc[j];
+    for (int i = tid; i < S; i += PKT) if (a.post) a.post[(size_t)i * B + b] = post[i];
 }
 
 // the constants of evaluate_llh(marginalize_weights=True, alpha_0=2, beta_0=1) for m data rows (drt1d.py:4457-4496):
@@ -232,7 +218,7 @@ int launch_pfrt_combine(hipStream_t s, const PfrtCombineArgs& a, int B) {
     HIPDRT_REQUIRE(a.step_pfrt && a.rss && a.slw && a.ln_factors && a.ltp && (a.lto || !a.smooth), "pfrt_combine: NULL input");
     const size_t lds = pfrt_combine_lds_bytes(a.S, a.np, a.nout);
     if (int rc = set_lds(reinterpret_cast<const void*>(pfrt_combine_kernel), lds, "pfrt_combine_kernel")) return rc;
-    hipLaunchKernelGGL(pfrt_combine_kernel, dim3(B), dim3(FT), lds, s, a);
+    hipLaunchKernelGGL(pfrt_combine_kernel, dim3(B), dim3(PKT), lds, s, a);
     return HIPDRT_OK;
 }
 

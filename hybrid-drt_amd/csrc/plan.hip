@@ -200,7 +200,7 @@ int hipdrt_plan_create(hipdrt_ctx* ctx, const double* freq, int nf, const double
     hipStream_t st; TRY(enter(ctx, &st));
     std::unique_ptr<hipdrt_plan> p(new hipdrt_plan());
     p->ctx = ctx;
-    if (opts) p->opts = *opts; else hipdrt_default_fit_opts(&p->opts);
+    p->opts = opts_or(opts, hipdrt_default_fit_opts);
     p->nf = nf; p->ntau = ntau; p->eps = epsilon; p->mode = mode; p->ngrid = ngrid; p->ny = ny;
     p->toeplitz_a = toeplitz_a; p->toeplitz_m = toeplitz_m; p->capacity = capacity;
     // special parameters in registration order (drt1d.py:383-388): R_inf, then inductance
@@ -278,7 +278,7 @@ int hipdrt_plan_create_prepared(hipdrt_ctx* ctx, const hipdrt_prepared_desc* d, 
     hipStream_t st; TRY(enter(ctx, &st));
     std::unique_ptr<hipdrt_plan> p(new hipdrt_plan());
     p->ctx = ctx;
-    if (opts) p->opts = *opts; else hipdrt_default_fit_opts(&p->opts);
+    p->opts = opts_or(opts, hipdrt_default_fit_opts);
     p->prepared = 1; p->desc = *d;
     p->n = d->n; p->m = d->m; p->ns = d->ns; p->ntau = d->n - d->ns; p->nf = 0; p->toeplitz_m = d->toeplitz_m;
     p->capacity = capacity;

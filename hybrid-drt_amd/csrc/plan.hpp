@@ -30,6 +30,14 @@ inline int enter(hipdrt_ctx* ctx, hipStream_t* st = nullptr) {
     return HIPDRT_OK;
 }
 
+// an entry point's options: the caller's, or the defaults of the public initialiser
+template <class O>
+O opts_or(const O* given, void (*dflt)(O*)) {
+    O o;
+    if (given) o = *given; else dflt(&o);
+    return o;
+}
+
 inline int upload(DevBuf& buf, const void* src, size_t bytes, hipStream_t st) {
     HIPDRT_CHECK(buf.alloc(bytes));
     if (src) HIPDRT_CHECK(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, st));
@@ -202,7 +210,7 @@ struct hipdrt_plan : PlanShape {
         st.nf = nf; st.m = m; st.n = n; st.ns = ns; st.ldrm = ldrm; st.ldm = ldm; st.toeplitz_m = toeplitz_m;
         st.toep_reach = (toeplitz_m && !(ctx && !ctx->zero_shortcuts)) ? toep_maxd : -1;
         st.opts = opts; st.continue_mode = 0; st.min_iter = 1;
-        st.basis_area = prepared ? desc.basis_area : (eps > 0 ? 1.7724538509055159 / eps : 0.0);   // sqrt(pi) / epsilon
+        st.basis_area = prepared ? desc.basis_area : (eps > 0 ? hipdrt::basis_area(eps) : 0.0);
         st.prepared = prepared; st.desc = desc; st.rm_stride = rm_stride; st.rm_rw = rm.d();
         st.vz_strength = vz_strength.d(); st.vz_entry = nullptr; st.dop_rho = dop_rho.d(); st.dop_xmx = dop_xmx.d();
         st.hist_dop_rho = hist_dop_rho.d(); st.outlier_t = outlier_t.d();

@@ -83,7 +83,8 @@ static void merge_status(int B, const int* fit, const int* var, int* status) {
 // signed evaluation rows and the mean rows of the batch, the normalisation scalars, and (want_var) e' inv(P_b) e of all rows from
 // one factorisation per spectrum, not yet scaled.
 struct DrtRows {
-    DevBuf dE, dsum, dabs, dnorm, dscale, dcs, dmu, dvar, dvstat;      // dE and dmu are allocated by the caller
+    DevBuf dgrid, dE, dsum, dabs, dnorm, dscale, dcs, dmu, dvar, dvstat;
+    const double* grid = nullptr;        // [neval] ln(tau_eval) on the device
     const double* scale = nullptr;       // [B] the factor the mean rows carry
     const double* cs = nullptr;          // [B] the coefficient scale behind it (times row_scale)
     const double* norm = nullptr;        // [B] R_p, or null without normalisation
@@ -91,21 +92,36 @@ struct DrtRows {
     double* mu(int k) const { return dmu.d() + (size_t)k * B * neval; }                 // [B][neval] of orders[k]
     const double* var(int k) const { return dvar.d() + (size_t)k * neval; }             // row stride ldv()
     long long ldv() const { return (long long)((norders * neval + 15) / 16) * 16; }
+    // the grid uploaded, dE [norders * neval][width] and dmu [norders][B][neval] allocated
+    int begin(const hipdrt_plan* p, const double* ln_tau_host, int neval_, int norders_, hipStream_t st) {
+        TRY(upload(dgrid, ln_tau_host, (size_t)neval_ * sizeof(double), st));
+        HIPDRT_CHECK(dE.alloc((size_t)norders_ * neval_ * (p->n - p->ns) * sizeof(double)));
+        return begin_mu(p, dgrid.d(), neval_, norders_);
+    }
+    // ... on a device grid and a dE that the caller keeps across the calls of a loop
+    int begin(const hipdrt_plan* p, const double* grid_dev, const DevBuf& dE_kept, int neval_, int norders_) {
+        dE.alias(dE_kept, 0, dE_kept.bytes);
+        return begin_mu(p, grid_dev, neval_, norders_);
+    }
+    int begin_mu(const hipdrt_plan* p, const double* grid_dev, int neval_, int norders_) {
+        grid = grid_dev; neval = neval_; B = p->B; norders = norders_;
+        HIPDRT_CHECK(dmu.alloc((size_t)norders * B * neval * sizeof(double)));
+        return HIPDRT_OK;
+    }
 };
-// orders[norders] (any number of them): rows k * neval .. of dE and slab k of dmu belong to orders[k].  dev: ln(tau_eval) on the
-// device.  row_scale: host [B] or null.  The timer is marked once, after the mean rows.
+// orders[R.norders] (any number of them): rows k * neval .. of dE and slab k of dmu belong to orders[k].  row_scale: host [B] or
+// null.  The timer is marked once, after the mean rows.
 // have_E: dE already holds the evaluation rows (a second call on the same grid, orders and sign).
-static int plan_drt_rows_dev(hipdrt_plan* p, const PostSource& src, const PredictBasis& pb, int neval, const int* orders,
-                             int norders, int sign, int normalize, const double* row_scale, bool want_var, hipStream_t st,
-                             DevBuf& dev, DrtRows& R, PredictTimer& tm, bool have_E = false) {
-    const int B = p->B, n = p->n, ns = p->ns, width = n - ns, nb = pb.nb;
-    R.neval = neval; R.B = B; R.norders = norders;
+static int plan_drt_rows_dev(hipdrt_plan* p, const PostSource& src, const PredictBasis& pb, const int* orders, int sign,
+                             int normalize, const double* row_scale, bool want_var, hipStream_t st, DrtRows& R, PredictTimer& tm,
+                             bool have_E = false) {
+    const int B = p->B, n = p->n, ns = p->ns, width = n - ns, nb = pb.nb, neval = R.neval, norders = R.norders;
     // E[neval][width]: the signed evaluation rows over the whole DRT block (+E | 0), (0 | -E) or (+E | -E)
     if (!have_E && pb.copies == 2 && sign != 0) HIPDRT_CHECK(hipMemsetAsync(R.dE.p, 0, R.dE.bytes, st));
     for (int k = 0; k < norders && !have_E; ++k) {
         double* E = R.dE.d() + (size_t)k * neval * width;
-        if (sign != -1) TRY(func_eval_dev(st, pb.ln_tau, nb, dev.d(), neval, pb.eps, orders[k], 1.0, E, width));
-        if (pb.copies == 2 && sign != 1) TRY(func_eval_dev(st, pb.ln_tau, nb, dev.d(), neval, pb.eps, orders[k], -1.0, E + nb, width));
+        if (sign != -1) TRY(func_eval_dev(st, pb.ln_tau, nb, R.grid, neval, pb.eps, orders[k], 1.0, E, width));
+        if (pb.copies == 2 && sign != 1) TRY(func_eval_dev(st, pb.ln_tau, nb, R.grid, neval, pb.eps, orders[k], -1.0, E + nb, width));
     }
     R.cs = p->coef_scale.d();
     if (row_scale) {
@@ -123,7 +139,7 @@ static int plan_drt_rows_dev(hipdrt_plan* p, const PostSource& src, const Predic
         for (DevBuf* d : {&R.dsum, &R.dabs, &R.dnorm, &R.dscale})
             if (d->bytes < (size_t)B * sizeof(double)) HIPDRT_CHECK(d->alloc((size_t)B * sizeof(double)));
         launch_drt_sums(st, B, src.x, n, ns, nb, pb.copies, sign, R.dsum.d(), R.dabs.d());
-        launch_drt_scalars(st, B, R.dsum.d(), R.dabs.d(), R.cs, 1.7724538509055159 / pb.eps, 1, normalize == 2,
+        launch_drt_scalars(st, B, R.dsum.d(), R.dabs.d(), R.cs, basis_area(pb.eps), 1, normalize == 2,
                            src.x, n, -1, nullptr, nullptr, nullptr, R.dnorm.d(), R.dscale.d());
         LAUNCH_OK();
         R.scale = R.dscale.d();
@@ -140,11 +156,25 @@ static int plan_drt_rows_dev(hipdrt_plan* p, const PostSource& src, const Predic
     if (want_var) TRY(plan_quadratic_forms_dev(p, src, -1, R.dE.d(), norders * neval, width, ns, scratch, R.dvar, R.dvstat));
     return HIPDRT_OK;
 }
+// The end of an entry point on R: the per-spectrum status on the device (the fit's, or a kernel's built on it) and, have_var, the
+// variance path's come back, the stream is synchronised, and merge_status of the two goes to status_out (host [B] or null) and to
+// *merged.
+static int drt_status_back(const DrtRows& R, const int* fit_status_dev, bool have_var, hipStream_t st, int* status_out,
+                           std::vector<int>* merged = nullptr) {
+    std::vector<int> hs(R.B), hv(R.B, 0);
+    HIPDRT_CHECK(hipMemcpyAsync(hs.data(), fit_status_dev, hs.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (have_var) HIPDRT_CHECK(hipMemcpyAsync(hv.data(), R.dvstat.p, hv.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    merge_status(R.B, hs.data(), have_var ? hv.data() : nullptr, hs.data());
+    if (status_out) std::memcpy(status_out, hs.data(), hs.size() * sizeof(int));
+    if (merged) merged->swap(hs);
+    return HIPDRT_OK;
+}
 
 // the rows launch_peaks reads, from a DrtRows of orders {2, 0}: fxx, f (need_f) and, for need_var, the variances with their scaling
-static void peak_args_rows(PeakArgs& a, const DrtRows& R, int neval, const hipdrt_peak_opts& o, bool need_f, bool need_var,
+static void peak_args_rows(PeakArgs& a, const DrtRows& R, const hipdrt_peak_opts& o, bool need_f, bool need_var,
                            const int* fit_status) {
-    a.neval = neval; a.o = o; a.fxx = R.mu(0); a.f = need_f ? R.mu(1) : nullptr; a.fit_status = fit_status;
+    a.neval = R.neval; a.o = o; a.fxx = R.mu(0); a.f = need_f ? R.mu(1) : nullptr; a.fit_status = fit_status;
     if (need_var) {
         a.var_fxx = R.var(0); a.var_f = o.method == 2 ? R.var(1) : nullptr; a.ldv = R.ldv();
         a.cs = R.cs; a.norm = R.norm; a.var_status = R.dvstat.i();
@@ -164,15 +194,11 @@ int hipdrt_plan_predict_drt(hipdrt_plan* p, const double* ln_tau_eval, int neval
     const bool band = lo || hi;
     HIPDRT_REQUIRE(!band || (std::isfinite(s_lo) && std::isfinite(s_hi)), "s_lo and s_hi must be finite");
     hipStream_t st; TRY(enter(p->ctx, &st));
-    const int B = p->B, width = p->n - p->ns;
-    DevBuf dev;
+    const int B = p->B;
     DrtRows R;
-    TRY(upload(dev, ln_tau_eval, (size_t)neval * sizeof(double), st));
-    HIPDRT_CHECK(R.dE.alloc((size_t)neval * width * sizeof(double)));
-    HIPDRT_CHECK(R.dmu.alloc((size_t)B * neval * sizeof(double)));
+    TRY(R.begin(p, ln_tau_eval, neval, 1, st));
     PredictTimer tm(p->ctx, st);
-    TRY(plan_drt_rows_dev(p, live_source(p), pb, neval, &order, 1, sign, normalize, nullptr, band, st, dev, R, tm));
-    std::vector<int> hs(B), hv;
+    TRY(plan_drt_rows_dev(p, live_source(p), pb, &order, sign, normalize, nullptr, band, st, R, tm));
     DevOuts outs;
     double *dlo = nullptr, *dhi = nullptr;
     if (band) {
@@ -182,14 +208,9 @@ int hipdrt_plan_predict_drt(hipdrt_plan* p, const double* ln_tau_eval, int neval
         LAUNCH_OK();
         tm.mark();
         TRY(outs.back(st));
-        hv.resize(B);
-        HIPDRT_CHECK(hipMemcpyAsync(hv.data(), R.dvstat.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
     }
     HIPDRT_CHECK(hipMemcpyAsync(mu, R.dmu.p, R.dmu.bytes, hipMemcpyDeviceToHost, st));
-    HIPDRT_CHECK(hipMemcpyAsync(hs.data(), p->fit_status.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPDRT_CHECK(hipStreamSynchronize(st));
-    if (status) merge_status(B, hs.data(), band ? hv.data() : nullptr, status);
-    return HIPDRT_OK;
+    return drt_status_back(R, p->fit_status.i(), band, st, status);
 } HIPDRT_CATCH
 
 // ---- peak finding for the fitted batch (csrc/peaks.hip) ------------------------------------------------------------------------
@@ -208,24 +229,20 @@ int hipdrt_plan_find_peaks(hipdrt_plan* p, const double* ln_tau_eval, int neval,
     HIPDRT_REQUIRE(p && ln_tau_eval, "NULL pointer");
     PredictBasis pb;
     TRY(predict_basis(p, pb));
-    hipdrt_peak_opts o;
-    if (opts) o = *opts; else hipdrt_peak_opts_default(&o);
+    hipdrt_peak_opts o = opts_or(opts, hipdrt_peak_opts_default);
     // every check comes before the first launch
     TRY(peak_check_opts(o, neval));
     const int sign = o.eval_sign, normalize = o.normalize;
-    const int B = p->B, width = p->n - p->ns;
+    const int B = p->B;
     TRY(drt_check_request(pb, sign, normalize, row_scale, "eval_sign"));
     TRY(drt_check_row_scale(row_scale, B));
     const bool need_f = o.search == 0 || o.method == 2, need_var = o.method >= 1;
     const int orders[2] = {2, 0}, norders = need_f ? 2 : 1;
-    HIPDRT_REQUIRE(peaks_lds_bytes(neval, o.method, need_f, o.num_peaks) <= 160 * 1024 - 256,
+    HIPDRT_REQUIRE(peaks_lds_bytes(neval, o.method, need_f, o.num_peaks) <= kLdsLimit,
                    "find_peaks: neval too large for one workgroup's LDS");
     hipStream_t st; TRY(enter(p->ctx, &st));
-    DevBuf dev;
     DrtRows R;
-    TRY(upload(dev, ln_tau_eval, (size_t)neval * sizeof(double), st));
-    HIPDRT_CHECK(R.dE.alloc((size_t)norders * neval * width * sizeof(double)));
-    HIPDRT_CHECK(R.dmu.alloc((size_t)norders * B * neval * sizeof(double)));
+    TRY(R.begin(p, ln_tau_eval, neval, norders, st));
     const size_t bn = (size_t)B * neval;
     PeakArgs a{};
     DevOuts outs;
@@ -234,18 +251,13 @@ int hipdrt_plan_find_peaks(hipdrt_plan* p, const double* ln_tau_eval, int neval,
     TRY(outs.want(right_bases, bn, a.right_bases)); TRY(outs.want(count, B, a.count)); TRY(outs.want(used_prominence, B, a.used_prominence));
     TRY(outs.want(o.method == 2 ? peak_prob : nullptr, bn, a.peak_prob)); TRY(outs.want(o.method == 2 ? curv_prob : nullptr, bn, a.curv_prob));
     PredictTimer tm(p->ctx, st);
-    TRY(plan_drt_rows_dev(p, live_source(p), pb, neval, orders, norders, sign, normalize, row_scale, need_var, st, dev, R, tm));
-    peak_args_rows(a, R, neval, o, need_f, need_var, p->fit_status.i());
+    TRY(plan_drt_rows_dev(p, live_source(p), pb, orders, sign, normalize, row_scale, need_var, st, R, tm));
+    peak_args_rows(a, R, o, need_f, need_var, p->fit_status.i());
     TRY(launch_peaks(st, a, B));
     LAUNCH_OK();
     tm.mark();
     TRY(outs.back(st));
-    std::vector<int> hs(B), hv(B, 0);
-    HIPDRT_CHECK(hipMemcpyAsync(hs.data(), p->fit_status.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (need_var) HIPDRT_CHECK(hipMemcpyAsync(hv.data(), R.dvstat.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPDRT_CHECK(hipStreamSynchronize(st));
-    if (status) merge_status(B, hs.data(), need_var ? hv.data() : nullptr, status);
-    return HIPDRT_OK;
+    return drt_status_back(R, p->fit_status.i(), need_var, st, status);
 } HIPDRT_CATCH
 
 // ---- peak and trough probabilities of the fitted batch (csrc/peak_prob.hip) ------------------------------------------------------
@@ -264,11 +276,10 @@ int hipdrt_plan_peak_trough_probs(hipdrt_plan* p, const double* ln_tau_eval, int
     HIPDRT_REQUIRE(p && ln_tau_eval, "NULL pointer");
     PredictBasis pb;
     TRY(predict_basis(p, pb));
-    hipdrt_peak_prob_opts o;
-    if (opts) o = *opts; else hipdrt_peak_prob_opts_default(&o);
+    hipdrt_peak_prob_opts o = opts_or(opts, hipdrt_peak_prob_opts_default);
     // every check comes before the first launch
     TRY(peak_prob_check(o, neval, nranges, range_lo, range_hi));
-    const int B = p->B, width = p->n - p->ns;
+    const int B = p->B;
     // predict_drt(tau, order=k) at its defaults (drt1d.py:3667): sign 1, not normalised
     TRY(drt_check_request(pb, 1, 0, row_scale, "sign"));
     TRY(drt_check_row_scale(row_scale, B));
@@ -276,14 +287,12 @@ int hipdrt_plan_peak_trough_probs(hipdrt_plan* p, const double* ln_tau_eval, int
     const int orders[3] = {0, 1, 2};
     if (o.search != 2) nranges = 0;
     hipStream_t st; TRY(enter(p->ctx, &st));
-    DevBuf dev, dlo, dhi;
+    DevBuf dlo, dhi;
     DrtRows R;
-    TRY(upload(dev, ln_tau_eval, (size_t)neval * sizeof(double), st));
+    TRY(R.begin(p, ln_tau_eval, neval, 3, st));
     if (nranges > 0) {
         TRY(upload(dlo, range_lo, (size_t)nranges * sizeof(int), st)); TRY(upload(dhi, range_hi, (size_t)nranges * sizeof(int), st));
     }
-    HIPDRT_CHECK(R.dE.alloc((size_t)3 * neval * width * sizeof(double)));
-    HIPDRT_CHECK(R.dmu.alloc((size_t)3 * B * neval * sizeof(double)));
     const size_t bn = (size_t)B * neval;
     PeakProbArgs a{};
     DevOuts outs;
@@ -293,7 +302,7 @@ int hipdrt_plan_peak_trough_probs(hipdrt_plan* p, const double* ln_tau_eval, int
     TRY(outs.want(nranges > 0 ? range_peaks : nullptr, (size_t)B * nranges, a.range_peaks));
     PredictTimer tm(p->ctx, st);
     // one factorisation per spectrum, fed the rows of all three orders
-    TRY(plan_drt_rows_dev(p, live_source(p), pb, neval, orders, 3, 1, 0, row_scale, need_var, st, dev, R, tm));
+    TRY(plan_drt_rows_dev(p, live_source(p), pb, orders, 1, 0, row_scale, need_var, st, R, tm));
     a.neval = neval; a.nranges = nranges; a.o = o; a.f = R.mu(0); a.fx = R.mu(1); a.fxx = R.mu(2);
     a.fit_status = p->fit_status.i(); a.range_lo = dlo.i(); a.range_hi = dhi.i();
     if (need_var) {
@@ -304,12 +313,7 @@ int hipdrt_plan_peak_trough_probs(hipdrt_plan* p, const double* ln_tau_eval, int
     tm.mark();
     TRY(outs.back(st));
     if (mu) HIPDRT_CHECK(hipMemcpyAsync(mu, R.dmu.p, R.dmu.bytes, hipMemcpyDeviceToHost, st));
-    std::vector<int> hs(B), hv(B, 0);
-    HIPDRT_CHECK(hipMemcpyAsync(hs.data(), p->fit_status.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (need_var) HIPDRT_CHECK(hipMemcpyAsync(hv.data(), R.dvstat.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPDRT_CHECK(hipStreamSynchronize(st));
-    if (status) merge_status(B, hs.data(), need_var ? hv.data() : nullptr, status);
-    return HIPDRT_OK;
+    return drt_status_back(R, p->fit_status.i(), need_var, st, status);
 } HIPDRT_CATCH
 
 // ---- per-peak coefficients, distributions and resistances (csrc/peak_resolve.hip) ----------------------------------------------
@@ -325,8 +329,7 @@ int hipdrt_plan_resolve_peaks(hipdrt_plan* p, const hipdrt_peak_resolve_in* in, 
     HIPDRT_REQUIRE(p && in && out && in->ln_tau_find, "NULL pointer");
     PredictBasis pb;
     TRY(predict_basis(p, pb));
-    hipdrt_peak_resolve_opts o;
-    if (opts) o = *opts; else hipdrt_peak_resolve_opts_default(&o);
+    hipdrt_peak_resolve_opts o = opts_or(opts, hipdrt_peak_resolve_opts_default);
     // every check comes before the first launch
     TRY(peak_resolve_check_opts(o));
     const int B = p->B, n = p->n, ns = p->ns, width = n - ns, nfind = in->nfind, mp = o.max_peaks;
@@ -337,8 +340,7 @@ int hipdrt_plan_resolve_peaks(hipdrt_plan* p, const hipdrt_peak_resolve_in* in, 
     TRY(drt_check_request(pb, o.sign, 0, in->row_scale, "sign"));
     TRY(peak_resolve_check_source(in->source, in->peak_indices, B, mp, in->win_start, in->win_end, in->nwin, nfind));
     TRY(drt_check_row_scale(in->row_scale, B));
-    hipdrt_peak_opts po;
-    if (in->peak_opts) po = *in->peak_opts; else hipdrt_peak_opts_default(&po);
+    hipdrt_peak_opts po = opts_or(in->peak_opts, hipdrt_peak_opts_default);
     const bool find = in->source == HIPDRT_PEAKS_FROM_FIND;
     bool need_var = false;
     if (find) {
@@ -346,26 +348,17 @@ int hipdrt_plan_resolve_peaks(hipdrt_plan* p, const hipdrt_peak_resolve_in* in, 
         HIPDRT_REQUIRE(po.eval_sign == o.sign, "peak_opts.eval_sign must equal opts.sign (estimate_peak_coef hands its sign to find_peaks)");
         HIPDRT_REQUIRE(po.method == 0 || po.method == 1, "peak_opts.method must be 0 (thresh) or 1 (prob)");
         HIPDRT_REQUIRE(po.normalize >= 0 && po.normalize <= 2, "normalize must be 0, 1 (by R_p) or 2 (by absolute R_p)");
-        HIPDRT_REQUIRE(peaks_lds_bytes(nfind, po.method, 1, po.num_peaks) <= 160 * 1024 - 256,
+        HIPDRT_REQUIRE(peaks_lds_bytes(nfind, po.method, 1, po.num_peaks) <= kLdsLimit,
                        "find_peaks: nfind too large for one workgroup's LDS");
         need_var = po.method >= 1;
     }
-    {
-        const size_t lds = peak_resolve_lds_bytes(nfind, pb.nb, nout, mp);
-        if (lds > 160 * 1024 - 256) {
-            set_error("invalid argument: resolve_peaks: " + std::to_string(lds) + " bytes of LDS needed (nfind, nb, nout, max_peaks), " +
-                      std::to_string(160 * 1024 - 256) + " available");
-            return HIPDRT_E_INVALID;
-        }
-    }
+    TRY(lds_check(peak_resolve_lds_bytes(nfind, pb.nb, nout, mp), "resolve_peaks", "nfind, nb, nout, max_peaks"));
     hipStream_t st; TRY(enter(p->ctx, &st));
     const int orders[2] = {2, 0};
     const int normalize = find ? po.normalize : 0;
-    DevBuf dev, dout_grid, dE0, dkeep, dmu2, didx, dws, dwe, dst;
+    DevBuf dout_grid, dE0, dkeep, dmu2, didx, dws, dwe, dst;
     DrtRows R;
-    TRY(upload(dev, in->ln_tau_find, (size_t)nfind * sizeof(double), st));
-    HIPDRT_CHECK(R.dE.alloc((size_t)2 * nfind * width * sizeof(double)));
-    HIPDRT_CHECK(R.dmu.alloc((size_t)2 * B * nfind * sizeof(double)));
+    TRY(R.begin(p, in->ln_tau_find, nfind, 2, st));
     PeakResolveArgs a{};
     a.nfind = nfind; a.nb = pb.nb; a.nout = nout; a.source = in->source; a.nwin = in->nwin; a.copies = pb.copies; a.o = o;
     if (in->source == HIPDRT_PEAKS_FROM_INDICES) { TRY(upload(didx, in->peak_indices, (size_t)B * mp * sizeof(int), st)); a.indices = didx.i(); }
@@ -385,12 +378,12 @@ int hipdrt_plan_resolve_peaks(hipdrt_plan* p, const hipdrt_peak_resolve_in* in, 
     TRY(outs.want(out->eps_l, bm, a.eps_l)); TRY(outs.want(out->eps_r, bm, a.eps_r)); TRY(outs.want(out->r_peaks, bm, a.r_peaks));
     TRY(outs.want(out->r_coef, bm, a.r_coef)); TRY(outs.want(out->x_peaks, bm * pb.nb, a.x_peaks)); TRY(outs.want(out->peak_gammas, bm * nout, a.peak_gammas));
     PredictTimer tm(p->ctx, st);
-    TRY(plan_drt_rows_dev(p, live_source(p), pb, nfind, orders, 2, o.sign, normalize, in->row_scale, need_var, st, dev, R, tm));
+    TRY(plan_drt_rows_dev(p, live_source(p), pb, orders, o.sign, normalize, in->row_scale, need_var, st, R, tm));
     a.fxx = R.mu(0); a.f = R.mu(1);
     if (find) {
         HIPDRT_CHECK(dkeep.alloc((size_t)B * nfind * sizeof(int)));
         PeakArgs pa{};
-        peak_args_rows(pa, R, nfind, po, true, need_var, p->fit_status.i());
+        peak_args_rows(pa, R, po, true, need_var, p->fit_status.i());
         pa.keep = dkeep.i();
         TRY(launch_peaks(st, pa, B));
         LAUNCH_OK();
@@ -412,20 +405,16 @@ int hipdrt_plan_resolve_peaks(hipdrt_plan* p, const hipdrt_peak_resolve_in* in, 
         a.E0 = dE0.d(); a.lto = dout_grid.d();
     }
     a.X = p->x.d(); a.ldx = n; a.col_offset = ns; a.cs = R.cs;
-    a.lt = dev.d(); a.lb = pb.ln_tau; a.basis_area = 1.7724538509055159 / pb.eps;
+    a.lt = R.grid; a.lb = pb.ln_tau; a.basis_area = basis_area(pb.eps);
     a.fit_status = p->fit_status.i();
     TRY(launch_peak_resolve(st, a, B));
     LAUNCH_OK();
     tm.mark();
     TRY(outs.back(st));
-    std::vector<int> hs(B), hv(B, 0);
-    HIPDRT_CHECK(hipMemcpyAsync(hs.data(), dst.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (need_var) HIPDRT_CHECK(hipMemcpyAsync(hv.data(), R.dvstat.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPDRT_CHECK(hipStreamSynchronize(st));
-    merge_status(B, hs.data(), need_var ? hv.data() : nullptr, hs.data());
+    std::vector<int> hs;
+    TRY(drt_status_back(R, dst.i(), need_var, st, out->status, &hs));
     bool unordered = false;
     for (int b = 0; b < B; ++b) unordered = unordered || hs[b] == HIPDRT_PEAKS_UNORDERED;
-    if (out->status) std::memcpy(out->status, hs.data(), (size_t)B * sizeof(int));
     if (unordered) {
         set_error("invalid argument: resolve_peaks: the window peaks of a spectrum are not strictly increasing (two windows chose "
                   "their shared border sample); see status");
@@ -445,19 +434,17 @@ int hipdrt_plan_integrate_drt(hipdrt_plan* p, const double* ln_tau_eval, int nev
     TRY(drt_check_request(pb, sign, normalize, row_scale, "sign"));
     HIPDRT_REQUIRE(nwin >= 1 && nwin <= 65535, "1 <= nwin <= 65535");
     TRY(peak_resolve_check_source(2, nullptr, 0, nwin, win_start, win_end, nwin, neval));
-    const int B = p->B, width = p->n - p->ns;
+    const int B = p->B;
     TRY(drt_check_row_scale(row_scale, B));
     hipStream_t st; TRY(enter(p->ctx, &st));
-    DevBuf dev, dws, dwe, dres;
+    DevBuf dws, dwe, dres;
     DrtRows R;
-    TRY(upload(dev, ln_tau_eval, (size_t)neval * sizeof(double), st));
+    TRY(R.begin(p, ln_tau_eval, neval, 1, st));
     TRY(upload(dws, win_start, (size_t)nwin * sizeof(int), st)); TRY(upload(dwe, win_end, (size_t)nwin * sizeof(int), st));
-    HIPDRT_CHECK(R.dE.alloc((size_t)neval * width * sizeof(double)));
-    HIPDRT_CHECK(R.dmu.alloc((size_t)B * neval * sizeof(double)));
     HIPDRT_CHECK(dres.alloc((size_t)B * nwin * sizeof(double)));
     PredictTimer tm(p->ctx, st);
-    TRY(plan_drt_rows_dev(p, live_source(p), pb, neval, &order, 1, sign, normalize, row_scale, false, st, dev, R, tm));
-    launch_window_trapz(st, B, neval, nwin, R.mu(0), dev.d(), dws.i(), dwe.i(), dres.d());
+    TRY(plan_drt_rows_dev(p, live_source(p), pb, &order, sign, normalize, row_scale, false, st, R, tm));
+    launch_window_trapz(st, B, neval, nwin, R.mu(0), R.grid, dws.i(), dwe.i(), dres.d());
     LAUNCH_OK();
     tm.mark();
     HIPDRT_CHECK(hipMemcpyAsync(out, dres.p, (size_t)B * nwin * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -527,8 +514,7 @@ int hipdrt_plan_predict_pfrt(hipdrt_plan* p, const double* factors, const double
     }
     PredictBasis pb;
     TRY(predict_basis(p, pb));
-    hipdrt_pfrt_opts o;
-    if (opts) o = *opts; else hipdrt_pfrt_opts_default(&o);
+    hipdrt_pfrt_opts o = opts_or(opts, hipdrt_pfrt_opts_default);
     const int S = p->pf_steps, B = p->B, np = neval_pfrt, nout = neval_out, width = p->n - p->ns;
     // every check comes before the first launch
     HIPDRT_REQUIRE(S >= 1, "no recorded PFRT steps in the plan (hipdrt_plan_pfrt_begin / _record around the fit's steps)");
@@ -540,7 +526,7 @@ int hipdrt_plan_predict_pfrt(hipdrt_plan* p, const double* factors, const double
     hipdrt_peak_opts_default(&po);
     po.eval_sign = 1; po.search = o.search; po.normalize = 1; po.method = 0; po.height = o.height; po.prominence = o.prominence;
     TRY(peak_check_opts(po, np));
-    HIPDRT_REQUIRE(peaks_lds_bytes(np, 0, 1, 0) <= 160 * 1024 - 256, "predict_pfrt: neval_pfrt too large for one workgroup's LDS");
+    HIPDRT_REQUIRE(peaks_lds_bytes(np, 0, 1, 0) <= kLdsLimit, "predict_pfrt: neval_pfrt too large for one workgroup's LDS");
     hipStream_t st; TRY(enter(p->ctx, &st));
 
     // a spectrum whose fit failed in any step is dead in every step
@@ -578,14 +564,13 @@ int hipdrt_plan_predict_pfrt(hipdrt_plan* p, const double* factors, const double
         const PostSource src = step_source(p, i, dw.d(), dfs.i());
         // f and fxx normalised by the R_p of the step's own x; sigma^2 of both orders from one factorisation of the step P
         DrtRows R;
-        R.dE.alias(dE, 0, dE.bytes);
-        HIPDRT_CHECK(R.dmu.alloc((size_t)2 * bn * sizeof(double)));
-        TRY(plan_drt_rows_dev(p, src, pb, np, orders, 2, 1, 1, nullptr, true, st, dev, R, tm, i > 0));
+        TRY(R.begin(p, dev.d(), dE, np, 2));
+        TRY(plan_drt_rows_dev(p, src, pb, orders, 1, 1, nullptr, true, st, R, tm, i > 0));
         // ... but every step's variances are divided by the squared R_p of the FIRST step (estimate_distribution_cov takes
         // get_drt_norm() of fit_parameters, which the warm restarts never update: drt1d.py:3081)
         if (i == 0) HIPDRT_CHECK(hipMemcpyAsync(dnorm0.p, R.dnorm.p, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, st));
         PeakArgs pa{};
-        peak_args_rows(pa, R, np, po, true, false, dfs.i());
+        peak_args_rows(pa, R, po, true, false, dfs.i());
         pa.peak_sign = dsg.i(); pa.heights = dht.d(); pa.prominences = dpr.d();
         TRY(launch_peaks(st, pa, B));
         LAUNCH_OK();
@@ -638,8 +623,7 @@ int hipdrt_plan_score_candidates(hipdrt_plan* p, const hipdrt_candidates_in* in,
     const bool want_llh = out->rss || out->sum_log_w;
     const bool want_peaks = out->count || out->peak_index || out->heights || out->prominences;
     const int nfind = in->nfind, mp = in->max_peaks == 0 ? 16 : in->max_peaks;
-    hipdrt_peak_opts o;
-    if (in->peak_opts) o = *in->peak_opts; else hipdrt_peak_opts_default(&o);
+    hipdrt_peak_opts o = opts_or(in->peak_opts, hipdrt_peak_opts_default);
     PredictBasis pb{};
     if (want_peaks) {
         HIPDRT_REQUIRE(in->ln_tau_find && nfind >= 1, "the peak outputs need the find grid");
@@ -648,7 +632,7 @@ int hipdrt_plan_score_candidates(hipdrt_plan* p, const hipdrt_candidates_in* in,
         TRY(peak_check_opts(o, nfind));
         HIPDRT_REQUIRE(o.method == 0, "method must be 0 ('thresh'): 'prob' needs a P matrix per candidate");
         TRY(drt_check_request(pb, o.eval_sign, o.normalize, nullptr, "eval_sign"));
-        HIPDRT_REQUIRE(peaks_lds_bytes(nfind, 0, o.search == 0, 0) <= 160 * 1024 - 256, "find_peaks: nfind too large for one workgroup's LDS");
+        HIPDRT_REQUIRE(peaks_lds_bytes(nfind, 0, o.search == 0, 0) <= kLdsLimit, "find_peaks: nfind too large for one workgroup's LDS");
     }
     const int form = cand_llh_form(p->ctx, m);
     HIPDRT_REQUIRE(!want_llh || form == 1 || cand_llh_fits_lds(m), "candidates: 16 rows of m doubles do not fit in LDS; use the scratch form");
@@ -712,16 +696,15 @@ int hipdrt_plan_score_candidates(hipdrt_plan* p, const hipdrt_candidates_in* in,
         HIPDRT_CHECK(dkeep.alloc(bn * sizeof(int))); HIPDRT_CHECK(dht.alloc(bn * sizeof(double))); HIPDRT_CHECK(dpr.alloc(bn * sizeof(double)));
         // one set of row buffers for all candidates: the launches of candidate c + 1 follow those of candidate c on the stream
         DrtRows R;
-        R.dE.alias(dE, 0, dE.bytes);
-        HIPDRT_CHECK(R.dmu.alloc((size_t)norders * bn * sizeof(double)));
+        TRY(R.begin(p, dev.d(), dE, nfind, norders));
         for (int c = 0; c < C; ++c) {
             // the rows of candidate c of every spectrum, normalised by the R_p of the candidate's own x; a slot without a
             // candidate is a dead spectrum to every kernel of the chain
             const int* sl = dslot.i() + (size_t)c * B;
             const PostSource src{x + (size_t)c * cstride, nullptr, nullptr, nullptr, nullptr, sl};
-            TRY(plan_drt_rows_dev(p, src, pb, nfind, orders, norders, o.eval_sign, o.normalize, nullptr, false, st, dev, R, tm, c > 0));
+            TRY(plan_drt_rows_dev(p, src, pb, orders, o.eval_sign, o.normalize, nullptr, false, st, R, tm, c > 0));
             PeakArgs pa{};
-            peak_args_rows(pa, R, nfind, o, need_f, false, sl);
+            peak_args_rows(pa, R, o, need_f, false, sl);
             pa.keep = dkeep.i(); pa.heights = dht.d(); pa.prominences = dpr.d();
             TRY(launch_peaks(st, pa, B));
             LAUNCH_OK();

@@ -229,10 +229,9 @@ int hipdrt_plan_kk_screen(hipdrt_plan* p, const hipdrt_kk_opts* opts, int set_ro
     HIPDRT_REQUIRE(!p->prepared, "the KK screen is built for plain EIS plans (hipdrt_plan_create)");
     HIPDRT_REQUIRE(p->nf >= 1 && p->m == 2 * p->nf, "the KK screen needs EIS-only data (m = 2 nf)");
     HIPDRT_REQUIRE(p->freq_order != 0, "the KK screen needs a strictly ascending or descending frequency grid");
-    hipdrt_kk_opts o;
-    if (opts) o = *opts; else hipdrt_default_kk_opts(&o);
+    hipdrt_kk_opts o = opts_or(opts, hipdrt_default_kk_opts);
     TRY(kk_check_opts(o));
-    HIPDRT_REQUIRE(kk_lds_bytes(p->nf, p->n, 1) <= 160 * 1024 - 256, "KK screen: nf and n too large for one workgroup's LDS");
+    HIPDRT_REQUIRE(kk_lds_bytes(p->nf, p->n, 1) <= kLdsLimit, "KK screen: nf and n too large for one workgroup's LDS");
     hipStream_t st; TRY(enter(p->ctx, &st));
     const int B = p->B, nf = p->nf, m = p->m;
     KkArgs a{};
@@ -334,7 +333,7 @@ int hipdrt_plan_predict_resistances(hipdrt_plan* p, double* r_p, double* r_inf, 
     for (DevBuf* d : {&dsum, &dabs, &drp, &dri, &drt}) HIPDRT_CHECK(d->alloc((size_t)B * sizeof(double)));
     // predict_r_p's default sign: the net distribution of a two-copy block, else the block itself
     launch_drt_sums(st, B, p->x.d(), n, p->ns, pb.nb, pb.copies, pb.copies == 2 ? 0 : 1, dsum.d(), dabs.d());
-    launch_drt_scalars(st, B, dsum.d(), dabs.d(), p->coef_scale.d(), 1.7724538509055159 / pb.eps, 0, abs_norm != 0, p->x.d(), n,
+    launch_drt_scalars(st, B, dsum.d(), dabs.d(), p->coef_scale.d(), basis_area(pb.eps), 0, abs_norm != 0, p->x.d(), n,
                        p->idx_rinf, drp.d(), dri.d(), drt.d(), nullptr, nullptr);
     LAUNCH_OK();
     if (r_p) HIPDRT_CHECK(hipMemcpyAsync(r_p, drp.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
