@@ -168,6 +168,12 @@ class DebugPosteriorArgs(C.Structure):
                 ("var", _dp), ("status", _ip), ("cov", _dp), ("bex", _dp), ("tail", _dp)]
 
 
+class DebugDopPosteriorArgs(C.Structure):
+    """hipdrt_debug_dop_posterior_args (include/hipdrt_debug.h)"""
+    _fields_ = [("post", DebugPosteriorArgs), ("dop_start", C.c_int), ("dop_size", C.c_int), ("dop_scale_vector", _dp),
+                ("dop_scale_batched", C.c_int), ("ppk", _dp)]
+
+
 class DebugQpArgs(C.Structure):
     """hipdrt_debug_qp_args (include/hipdrt_debug.h)"""
     _fields_ = [("B", C.c_int), ("n", C.c_int), ("P", _dp), ("p_batched", C.c_int), ("ldp", C.c_int), ("q", _dp), ("h", _dp),
@@ -181,6 +187,13 @@ class PredictDesc(C.Structure):
     _fields_ = [("idx_rinf", C.c_int), ("idx_induc", C.c_int), ("idx_cinv", C.c_int), ("inductance_scale", C.c_double),
                 ("capacitance_scale", C.c_double), ("dop_scale_vector", _dp), ("dop_scale_batched", C.c_int), ("v_baseline_scale", _dp),
                 ("coefficient_scale", _dp), ("response_signal_scale", _dp), ("scaled_response_offset", _dp)]
+
+
+class DopArgs(C.Structure):
+    """hipdrt_dop_args (include/hipdrt.h)"""
+    _fields_ = [("nu", _dp), ("nn", C.c_int), ("basis_nu", _dp), ("nu_epsilon", C.c_double), ("order", C.c_int),
+                ("normalize_by", _dp), ("nu_basis_area", C.c_double), ("include_ideal", C.c_int), ("s_lo", C.c_double),
+                ("s_hi", C.c_double)]
 
 
 class ResponseArgs(C.Structure):
@@ -325,6 +338,8 @@ SIGNATURES = {
     "hipdrt_plan_predict_response": [_vp, C.POINTER(ResponseArgs), _dp, _ip],
     "hipdrt_plan_predict_z_model": [_vp, C.POINTER(ZModelArgs), _dp, _dp, _ip],
     "hipdrt_plan_predict_dop": [_vp, _dp, C.c_int, _dp, C.c_double, _dp, C.c_double, C.c_int, _dp, _ip],
+    "hipdrt_plan_dop_posterior": [_vp, C.POINTER(DopArgs), _dp, _dp, _dp, _dp, _ip],
+    "hipdrt_plan_dop_cov": [_vp, C.c_int, C.POINTER(DopArgs), _dp, _ip],
     "hipdrt_debug_response": [_vp, C.POINTER(DebugResponseArgs)],
     "hipdrt_peak_opts_default": [C.POINTER(PeakOpts)],
     "hipdrt_plan_find_peaks": [_vp, _dp, C.c_int, C.POINTER(PeakOpts), _dp, _ip, _ip, _dp, _dp, _dp, _ip, _ip, _ip, _dp, _dp, _dp,
@@ -344,6 +359,7 @@ SIGNATURES = {
     "hipdrt_debug_candidate_llh": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp],
     "hipdrt_debug_candidate_form": [_vp, C.c_int],
     "hipdrt_debug_posterior": [_vp, C.POINTER(DebugPosteriorArgs)],
+    "hipdrt_debug_dop_posterior": [_vp, C.POINTER(DebugDopPosteriorArgs)],
     "hipdrt_debug_qp": [_vp, C.POINTER(DebugQpArgs)],
     "hipdrt_debug_lpt_order": [_vp, C.c_int, _ip, _ip, _ip],
     "hipdrt_plan_pfrt_bytes_per_spectrum": [C.c_int, C.c_int, C.POINTER(C.c_longlong)],

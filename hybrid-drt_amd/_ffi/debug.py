@@ -361,6 +361,42 @@ class DebugHooks:
                                                     _p(rss), _p(slw)))
         return rss, slw
 
+    def debug_dop_posterior(self, P, rows, dop_start, dop_scale_vector, col_offset=None, B=None, scale=None, cov_member=-1, n=None,
+                            dop_size=None, want=("var", "status")):
+        """tests: the posterior chain behind the per-member congruence scaling of the packed P (hipdrt_debug_dop_posterior,
+        include/hipdrt_debug.h).  Arguments and outputs as debug_posterior; dop_scale_vector (dop_size,) shared or (B, dop_size);
+        col_offset=None places the rows at dop_start.  One more output may be named in `want`: ppk (nb, nchp * nchp * 256), the
+        packed image of every member's P after the scaling."""
+        P, rows = _f64(P), np.atleast_2d(_f64(rows))
+        dsv = _f64(dop_scale_vector)
+        batched = P.ndim == 3
+        B = (P.shape[0] if batched else (dsv.shape[0] if dsv.ndim == 2 else 1)) if B is None else int(B)
+        n = P.shape[-2] if n is None else int(n)
+        nd = dsv.shape[-1] if dop_size is None else int(dop_size)
+        if P.ndim not in (2, 3) or P.shape[-2] != n or (batched and P.shape[0] != B):
+            raise ValueError("P: (n, ldp) or (B, n, ldp)")
+        if dsv.ndim not in (1, 2) or (dsv.ndim == 2 and dsv.shape[0] != B) or dsv.shape[-1] != max(nd, 0):
+            raise ValueError("dop_scale_vector: (dop_size,) or (B, dop_size)")
+        neval, ncol = rows.shape
+        sc = None if scale is None else _f64(scale).ravel()
+        if sc is not None and sc.size != B:
+            raise ValueError("scale: (B,)")
+        nb = 1 if cov_member >= 0 else max(B, 0)
+        nex, nchp = max((neval + 15) // 16, 0), (max(n, 0) + 31) // 32 * 2
+        shapes = dict(var=(nb, neval), status=(nb,), cov=(neval, neval), bex=(nex, nchp, 256), tail=(nb, nex, nchp, 256),
+                      ppk=(nb, nchp * nchp * 256))
+        out = {k: (np.full(shapes[k], -7, dtype=np.int32) if k == "status" else np.full(shapes[k], 7e77)) for k in want}
+        d = DebugDopPosteriorArgs()
+        a = d.post
+        a.B, a.n, a.P, a.p_batched, a.ldp = B, n, _p(P), int(batched), P.shape[-1]
+        a.rows, a.neval, a.ncol, a.scale, a.cov_member = _p(rows), neval, ncol, _p(sc), int(cov_member)
+        a.col_offset = int(dop_start if col_offset is None else col_offset)
+        d.dop_start, d.dop_size, d.dop_scale_vector, d.dop_scale_batched = int(dop_start), nd, _p(dsv), int(dsv.ndim == 2)
+        for k in want:
+            setattr(d if k == "ppk" else a, k, _pi(out[k]) if k == "status" else _p(out[k]))
+        _check(self._lib.hipdrt_debug_dop_posterior(self._h, C.byref(d)))
+        return out
+
     def debug_posterior(self, P, rows, col_offset=0, B=None, scale=None, cov_member=-1, n=None, want=("var", "status")):
         """tests: the posterior variance and covariance chain on host arrays (hipdrt_debug_posterior, include/hipdrt_debug.h):
         P (n, ldp) shared by B spectra or (B, n, ldp), rows (neval, ncol) at unknowns col_offset.., scale (B,) or None ->

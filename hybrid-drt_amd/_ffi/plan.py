@@ -569,6 +569,41 @@ class PreparedPlan(Plan):
                                                  int(bool(include_ideal)), _p(out), _pi(status)))
         return out, status
 
+    def _dop_args(self, nu, basis_nu, nu_epsilon, order, normalize_by, nu_basis_area, include_ideal=True, n_sigma=None):
+        """a Bound hipdrt_dop_args"""
+        b = Bound(DopArgs())
+        a, arr = b.c, b.array
+        nu = arr('nu', np.ravel(nu))
+        a.nn = nu.size
+        arr('basis_nu', np.ravel(basis_nu), (self.desc.dop_size,))
+        arr('normalize_by', None if normalize_by is None else np.ravel(normalize_by), (nu.size,))
+        a.nu_epsilon, a.order, a.nu_basis_area, a.include_ideal = float(nu_epsilon), int(order), float(nu_basis_area), int(bool(include_ideal))
+        if n_sigma is not None:
+            a.s_lo, a.s_hi = float(n_sigma[0]), float(n_sigma[1])
+        return b
+
+    def dop_posterior(self, nu, basis_nu, nu_epsilon, order=0, normalize_by=None, nu_basis_area=1.0, include_ideal=True,
+                      n_sigma=None, want_var=True):
+        """hipdrt_plan_dop_posterior: (mu, lo, hi, var, status) of the distribution of phasances of the fitted batch on the
+        ascending grid nu, each (B, len(nu)); n_sigma = (s_lo, s_hi) or None (lo, hi None); want_var False: var None.  Without
+        a band and a variance nothing is factorised."""
+        b = self._dop_args(nu, basis_nu, nu_epsilon, order, normalize_by, nu_basis_area, include_ideal, n_sigma)
+        B, nn = self.batch, b.c.nn
+        mu = np.empty((B, nn))
+        lo, hi = (np.empty((B, nn)), np.empty((B, nn))) if n_sigma is not None else (None, None)
+        var = np.empty((B, nn)) if want_var else None
+        status = np.empty(B, dtype=np.int32)
+        _check(self._lib.hipdrt_plan_dop_posterior(self._h, C.byref(b.c), _p(mu), _p(lo), _p(hi), _p(var), _pi(status)))
+        return mu, lo, hi, var, status
+
+    def dop_cov(self, member, nu, basis_nu, nu_epsilon, order=0, normalize_by=None, nu_basis_area=1.0):
+        """hipdrt_plan_dop_cov: (cov (len(nu), len(nu)), status) of member `member`; cov is NaN when status < 0"""
+        b = self._dop_args(nu, basis_nu, nu_epsilon, order, normalize_by, nu_basis_area)
+        out = np.empty((b.c.nn, b.c.nn))
+        status = C.c_int(0)
+        _check(self._lib.hipdrt_plan_dop_cov(self._h, int(member), C.byref(b.c), _p(out), C.byref(status)))
+        return out, int(status.value)
+
     def get(self, which):
         B = self.batch
         shapes = {"m0": (self.n, self.n), "m1": (self.n, self.n), "m2": (self.n, self.n), "vmm": (self.m, self.m),

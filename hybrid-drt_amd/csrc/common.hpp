@@ -365,6 +365,19 @@ struct DopArgs {
 void launch_dop_assemble(hipStream_t st, int B, const DopArgs& a);
 // out[b][j] = X[b][col + j] * v[b][j], out and v [B][nd]: every member's DOP block times its own dop_scale_vector
 void launch_scale_block(hipStream_t st, int B, int nd, const double* X, long long ldx, int col, const double* v, double* out);
+// The posterior of the distribution of phasances (predict.hip).  sinv[b][j] = 1.0 / dsv[b][j] (dsv_stride 0: one shared vector; an
+// entry that is not finite and positive gives 1: the caller has refused it, or the member's rows are NaN anyway)
+void launch_dop_recip(hipStream_t st, int B, int nd, const double* dsv, long long dsv_stride, double* sinv);
+// scale_p_kernel: the congruence S_b P_b S_b on the packed lower tiles Ppk [B][nchp][nchp][256] in place, S_b = diag(s) with
+// s = sinv[b] on the unknowns dop_start .. dop_start + dop_size - 1 and 1 elsewhere.  B = 1 with both strides 0: one member's image
+// and that member's own row of sinv.
+void launch_scale_p(hipStream_t st, int B, int n, int dop_start, int dop_size, const double* sinv, long long sinv_stride,
+                    double* Ppk, long long ppk_stride);
+// dop_band_kernel: lo, hi [B][nn] = mu + s sigma, sigma = sqrt(var cs^2) / norm[i], and var_out [B][nn] = var cs^2 / norm[i]^2 in
+// data units (norm null: 1; each output may be null); NaN where var_status != 0 or fit_status < 0
+void launch_dop_band(hipStream_t st, int B, int nn, const double* mu, const double* var, long long ldv, const double* cs,
+                     const double* norm, double s_lo, double s_hi, const int* var_status, const int* fit_status, double* lo,
+                     double* hi, double* var_out);
 
 // peaks.hip: peak finding on evaluated rows, one workgroup per spectrum (all pointers device memory; an output may be null)
 struct PeakArgs {

@@ -609,7 +609,8 @@ int hipdrt_debug_candidate_form(hipdrt_ctx* ctx, int form) try {
 // test hook (include/hipdrt_debug.h): the posterior chain of plan_post.hip -- posterior_var_dev and posterior_cov_dev, the functions
 // the plan entry points call -- on a P and rows of the caller's.  Every device output sits between borders of marker bytes, and so
 // does every spectrum's factor scratch.
-int hipdrt_debug_posterior(hipdrt_ctx* ctx, const hipdrt_debug_posterior_args* a) try {
+// d: the DOP form (hipdrt_debug_dop_posterior), null: the chain as it is
+static int debug_posterior_run(hipdrt_ctx* ctx, const hipdrt_debug_posterior_args* a, const hipdrt_debug_dop_posterior_args* d) {
     HIPDRT_REQUIRE(ctx && a && a->P && a->rows, "NULL pointer");
     const int B = a->B, n = a->n, neval = a->neval, ncol = a->ncol, off = a->col_offset, ldp = a->ldp, cm = a->cov_member;
     HIPDRT_REQUIRE(n >= 1 && n <= 4096 && B >= 1 && B <= 4096, "1 <= n <= 4096, 1 <= B <= 4096");
@@ -625,6 +626,13 @@ int hipdrt_debug_posterior(hipdrt_ctx* ctx, const hipdrt_debug_posterior_args* a
             for (int j = 0; j < n; ++j) HIPDRT_REQUIRE(std::isfinite(a->P[((size_t)b * n + i) * ldp + j]), "non-finite P");
     for (size_t i = 0; i < (size_t)neval * ncol; ++i) HIPDRT_REQUIRE(std::isfinite(a->rows[i]), "non-finite rows");
     if (a->scale) for (int b = 0; b < B; ++b) HIPDRT_REQUIRE(std::isfinite(a->scale[b]), "non-finite scale");
+    const int nd = d ? d->dop_size : 0;
+    if (d) {
+        HIPDRT_REQUIRE(d->dop_scale_vector, "NULL pointer");
+        HIPDRT_REQUIRE(nd >= 1 && d->dop_start >= 0 && d->dop_start <= n && nd <= n - d->dop_start, "the DOP block must lie inside [0, n) and hold a column");
+        for (size_t k = 0; k < (size_t)(d->dop_scale_batched ? B : 1) * nd; ++k)
+            HIPDRT_REQUIRE(d->dop_scale_vector[k] > 0.0 && std::isfinite(d->dop_scale_vector[k]), "dop_scale_vector must be finite and positive");
+    }
     hipStream_t st; TRY(enter(ctx, &st));
     const size_t D = sizeof(double), ppk = qp_ppk_doubles(n), G = Guarded::G / D;
     const int nex = (neval + 15) / 16, nchp = qp_nchp(n);
@@ -633,15 +641,38 @@ int hipdrt_debug_posterior(hipdrt_ctx* ctx, const hipdrt_debug_posterior_args* a
     // P -> packed tiles as the stand-alone QP entry point packs it (lower triangle); tiles the kernel does not write stay zero
     DevBuf dP, dPpk, drows, scratch;
     TRY(upload(dP, a->P, (size_t)pb * n * ldp * D, st));
-    HIPDRT_CHECK(dPpk.alloc((size_t)pb * ppk * D));
-    HIPDRT_CHECK(hipMemsetAsync(dPpk.p, 0, dPpk.bytes, st));
-    launch_pack_p(st, pb, n, dP.d(), ldp, dPpk.d());
+    // (the DOP form: every member has an image of its own, between borders; a shared P is packed into each)
+    const int ni = d ? B : pb;
+    const bool own = d || a->p_batched;
+    Guarded gpk;
+    double* images = nullptr;
+    if (d) {
+        TRY(gpk.up("ppk", nullptr, (size_t)ni * ppk * D, st));
+        images = gpk.dd();
+    } else {
+        HIPDRT_CHECK(dPpk.alloc((size_t)ni * ppk * D));
+        images = dPpk.d();
+    }
+    HIPDRT_CHECK(hipMemsetAsync(images, 0, (size_t)ni * ppk * D, st));
+    if (d && !a->p_batched) for (int b = 0; b < B; ++b) launch_pack_p(st, 1, n, dP.d(), ldp, images + (size_t)b * ppk);
+    else launch_pack_p(st, pb, n, dP.d(), ldp, images);
     LAUNCH_OK();
+    DevBuf ddsv, dsinv;
+    if (d) {
+        // 1 / dop_scale_vector of every member, then S P S on the images the chain will read: all of them, or member cm's alone in
+        // the single-member form (strides 0, its own scale row)
+        TRY(upload(ddsv, d->dop_scale_vector, (size_t)(d->dop_scale_batched ? B : 1) * nd * D, st));
+        HIPDRT_CHECK(dsinv.alloc((size_t)B * nd * D));
+        launch_dop_recip(st, B, nd, ddsv.d(), d->dop_scale_batched ? nd : 0, dsinv.d());
+        launch_scale_p(st, nb, n, d->dop_start, nd, dsinv.d() + (size_t)first * nd, single ? 0 : nd, images + (size_t)first * ppk,
+                       single ? 0 : (long long)ppk);
+        LAUNCH_OK();
+    }
     TRY(upload(drows, a->rows, (size_t)neval * ncol * D, st));
     std::vector<double> hvar((size_t)nb * nex * 16, 0.0), hbex((size_t)nex * nchp * 256, 0.0), hcov;
     std::vector<int> hstat(nb, 0);
     PosteriorChain c{};
-    c.nb = nb; c.n = n; c.ppk = dPpk.d() + (a->p_batched ? (size_t)first * ppk : 0); c.pstr = (a->p_batched && !single) ? (long long)ppk : 0;
+    c.nb = nb; c.n = n; c.ppk = images + (own ? (size_t)first * ppk : 0); c.pstr = (own && !single) ? (long long)ppk : 0;
     c.single = single; c.rows = drows.d(); c.neval = neval; c.ncol = ncol; c.col_offset = off; c.guard = G;
     GuardedOuts outs;
     double* dcov = nullptr;
@@ -675,7 +706,23 @@ int hipdrt_debug_posterior(hipdrt_ctx* ctx, const hipdrt_debug_posterior_args* a
     if (a->cov) for (size_t i = 0; i < hcov.size(); ++i) a->cov[i] = bad ? __builtin_nan("") : hcov[i];
     if (a->tail)
         for (int k = 0; k < nb; ++k) std::memcpy(a->tail + (size_t)k * tl, hs.data() + G + (size_t)k * (lsz + G) + nch * nch * 256, tl * D);
+    if (d) {
+        TRY(gpk.fetch(st));
+        HIPDRT_CHECK(hipStreamSynchronize(st));
+        TRY(gpk.check());
+        if (d->ppk) std::memcpy(d->ppk, gpk.data() + (size_t)first * ppk * D, (size_t)nb * ppk * D);
+    }
     return HIPDRT_OK;
+}
+
+int hipdrt_debug_posterior(hipdrt_ctx* ctx, const hipdrt_debug_posterior_args* a) try {
+    return debug_posterior_run(ctx, a, nullptr);
+} HIPDRT_CATCH
+
+// test hook (include/hipdrt_debug.h): the same chain behind launch_scale_p, as plan_quadratic_forms_dev runs it for the DOP posterior
+int hipdrt_debug_dop_posterior(hipdrt_ctx* ctx, const hipdrt_debug_dop_posterior_args* a) try {
+    HIPDRT_REQUIRE(a, "NULL pointer");
+    return debug_posterior_run(ctx, &a->post, a);
 } HIPDRT_CATCH
 
 // test hook (include/hipdrt_debug.h): lpt_order_kernel alone

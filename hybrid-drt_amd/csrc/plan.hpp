@@ -268,8 +268,16 @@ int plan_final_p_to_host(hipdrt_plan* p, hipStream_t st, int b, const FinalP& f,
 // rows_dev[neval][ncol] in device memory (it sits at columns col_offset.. of the unknown vector, zero elsewhere) ->
 // dout[nb][nex * 16] = rows_i' P^-1 rows_i (not yet scaled by cs^2) and dstat[nb], of spectrum b alone (nb = 1) or, b = -1, of
 // the batch (nb = B).  The caller owns the scratch: Y = rows L^-T of the last factorisation stays in it.
+// dop_sinv (null: P as it is): every member's image of P is scaled to S_b P_b S_b on the plan's DOP block first (launch_scale_p), so
+// that the forms are rows_i' D_b P_b^-1 D_b rows_i with D_b = diag(dop_scale_vector_b); dop_sinv [B][dop_size] on the device, 1 / D of
+// EVERY member of the batch, whatever b.  The image is rebuilt for every call: nothing of the fit is touched.
 int plan_quadratic_forms_dev(hipdrt_plan* p, const PostSource& src, int b, const double* rows_dev, int neval, int ncol,
-                             int col_offset, DevBuf& scratch, DevBuf& dout, DevBuf& dstat);
+                             int col_offset, DevBuf& scratch, DevBuf& dout, DevBuf& dstat, const double* dop_sinv = nullptr);
+// status[b] = the fit's status fit[b], or HIPDRT_PREDICT_NOT_PD where the fit is good and the variance factorisation failed
+// (var[b] != 0; var null: no variances were formed).  status may be fit itself.
+inline void merge_status(int B, const int* fit, const int* var, int* status) {
+    for (int b = 0; b < B; ++b) status[b] = (fit[b] >= 0 && var && var[b] != 0) ? HIPDRT_PREDICT_NOT_PD : fit[b];
+}
 // The device chain behind that, from packed P and device rows on -- what plan_quadratic_forms_dev runs once it has built P, and
 // what hipdrt_debug_posterior runs on a P of the caller's: rows -> packed tiles (bex), then cov_kernel_resident over the spectra in
 // chunks of at most 256 (one factor scratch per spectrum of a chunk).  `single`: the single-spectrum form (nb = 1, every stride 0).

@@ -73,12 +73,6 @@ static int drt_check_row_scale(const double* row_scale, int B) {
     return HIPDRT_OK;
 }
 
-// status[b] = the fit's status fit[b], or HIPDRT_PREDICT_NOT_PD where the fit is good and the variance factorisation failed
-// (var[b] != 0; var null: no variances were formed).  status may be fit itself.
-static void merge_status(int B, const int* fit, const int* var, int* status) {
-    for (int b = 0; b < B; ++b) status[b] = (fit[b] >= 0 && var && var[b] != 0) ? HIPDRT_PREDICT_NOT_PD : fit[b];
-}
-
 // What a DRT prediction leaves on the device (hipdrt_plan_predict_drt, hipdrt_plan_find_peaks, hipdrt_plan_peak_trough_probs): for every order asked for the
 // signed evaluation rows and the mean rows of the batch, the normalisation scalars, and (want_var) e' inv(P_b) e of all rows from
 // one factorisation per spectrum, not yet scaled.

@@ -45,11 +45,12 @@ int plan_final_p_to_host(hipdrt_plan* p, hipStream_t st, int b, const FinalP& f,
 }
 
 int plan_quadratic_forms_dev(hipdrt_plan* p, const PostSource& src, int b, const double* rows_dev, int neval, int ncol,
-                             int col_offset, DevBuf& scratch, DevBuf& dout, DevBuf& dstat) {
+                             int col_offset, DevBuf& scratch, DevBuf& dout, DevBuf& dstat, const double* dop_sinv) {
     HIPDRT_REQUIRE(p->B > 0, "no fitted batch in the plan");
     HIPDRT_REQUIRE(b >= -1 && b < p->B, "spectrum index out of range");
     HIPDRT_REQUIRE(neval >= 1, "neval >= 1");
     HIPDRT_REQUIRE(p->n <= 4096, "posterior variance: n <= 4096");
+    HIPDRT_REQUIRE(!dop_sinv || (p->prepared && p->desc.dop_size > 0), "internal: a DOP scaling for a plan without a DOP block");
     hipStream_t st; TRY(enter(p->ctx, &st));
     const bool one = b >= 0;
     const int n = p->n, nb = one ? 1 : p->B;
@@ -60,6 +61,11 @@ int plan_quadratic_forms_dev(hipdrt_plan* p, const PostSource& src, int b, const
     pq.active = nullptr;
     launch_gram_l2(st, pq, f.g);
     LAUNCH_OK();
+    if (dop_sinv) {
+        const int nd = p->desc.dop_size;
+        launch_scale_p(st, nb, n, p->desc.dop_start, nd, dop_sinv + (one ? (size_t)b * nd : 0), one ? 0 : nd, pq.Ppk, pq.ppk_stride);
+        LAUNCH_OK();
+    }
     DevBuf bex;
     HIPDRT_CHECK(bex.alloc((size_t)nex * nchp * 256 * sizeof(double)));
     HIPDRT_CHECK(dout.alloc((size_t)nb * nex * 16 * sizeof(double)));

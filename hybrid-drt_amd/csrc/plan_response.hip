@@ -1,7 +1,8 @@
 // Model evaluation of a prepared plan (include/hipdrt.h): the prediction description that tells the plan what its special columns
 // mean, and the voltage response of every member of its fitted batch (DRT.predict_response, hybdrt/models/drt1d.py:3363-3464) from
 // unit-step layers built once for the batch (csrc/matrices.hip), the row-application kernel and response_assemble_kernel
-// (csrc/predict.hip).
+// (csrc/predict.hip); its impedance with every special term, its distribution of phasances (DRT.predict_dop, 3273-3347) and the
+// posterior of that distribution (DRT.estimate_dop_cov, 3153-3198; DRT.predict_dop_ci, 3233-3258).
 #include <cmath>
 
 #include "plan.hpp"
@@ -32,6 +33,79 @@ int response_chain(hipStream_t st, int B, int ntau, int copies, int ns, const do
     }
     launch_response_assemble(st, B, a);
     LAUNCH_OK();
+    return HIPDRT_OK;
+}
+
+// ---- the distribution of phasances: what hipdrt_plan_predict_dop and the two posterior entry points share --------------------------
+// The grids of a request on the device, the evaluation rows dE [nn][dop_size], the scaled DOP blocks dxd [B][dop_size] and the mean
+// rows dmu [B][nn]
+struct DopRequest {
+    DevBuf dnu, dbn, dnorm, dE, dxd, dmu;
+    int nn = 0;
+    int begin(const hipdrt_plan* p, const double* nu, int nn_, const double* basis_nu, const double* normalize_by, hipStream_t st) {
+        const int nd = p->desc.dop_size;
+        nn = nn_;
+        TRY(upload(dnu, nu, (size_t)nn * sizeof(double), st));
+        TRY(upload(dbn, basis_nu, (size_t)nd * sizeof(double), st));
+        if (normalize_by) TRY(upload(dnorm, normalize_by, (size_t)nn * sizeof(double), st));
+        HIPDRT_CHECK(dE.alloc((size_t)nn * nd * sizeof(double)));
+        HIPDRT_CHECK(dmu.alloc((size_t)p->B * nn * sizeof(double)));
+        HIPDRT_CHECK(dxd.alloc((size_t)p->B * nd * sizeof(double)));
+        return HIPDRT_OK;
+    }
+};
+// predict_dop (drt1d.py:3273-3347) at derivative order `order` into R.dmu: the rows E, every member's DOP block times its own
+// dop_scale_vector, their product times the coefficient scale, then normalisation and ideal elements (dop_assemble_kernel); R.dnorm
+// decides whether it is normalised
+static int dop_mean_dev(hipdrt_plan* p, hipStream_t st, DopRequest& R, double nu_epsilon, int order, double nu_basis_area,
+                        int include_ideal) {
+    const int B = p->B, n = p->n, nd = p->desc.dop_size, nn = R.nn;
+    TRY(func_eval_dev(st, R.dbn.d(), nd, R.dnu.d(), nn, nu_epsilon, order, 1.0, R.dE.d(), nd));
+    launch_scale_block(st, B, nd, p->x.d(), n, p->desc.dop_start, p->pd_dop_scale.d(), R.dxd.d());
+    launch_apply_rows(st, B, nd, R.dxd.d(), nd, 0, nn, R.dE.d(), nd, p->pd_cs.d(), nullptr, R.dmu.d(), nn);
+    LAUNCH_OK();
+    DopArgs a{};
+    a.nn = nn; a.include_ideal = include_ideal != 0; a.dop = R.dmu.d(); a.nu = R.dnu.d(); a.norm = R.dnorm.p ? R.dnorm.d() : nullptr;
+    a.basis_area = nu_basis_area; a.X = p->x.d(); a.ldx = n; a.cs = p->pd_cs.d();
+    a.idx_rinf = p->pd_idx_rinf; a.idx_induc = p->pd_idx_induc; a.idx_cinv = p->pd_idx_cinv;
+    a.inductance_scale = p->pd_inductance_scale; a.capacitance_scale = p->pd_capacitance_scale; a.fit_status = p->fit_status.i();
+    launch_dop_assemble(st, B, a);
+    LAUNCH_OK();
+    return HIPDRT_OK;
+}
+// what the posterior entry points refuse before anything is launched
+static int dop_check_request(const hipdrt_plan* p, const hipdrt_dop_args* q) {
+    HIPDRT_REQUIRE(p->prepared && p->desc.dop_size > 0, "the DOP posterior needs a prepared plan with a DOP block");
+    HIPDRT_REQUIRE(p->B >= 1 && p->prepped, "no fitted batch in the plan");
+    HIPDRT_REQUIRE(p->pd_set, "the prediction description is missing: call hipdrt_plan_set_predict_desc after the fit");
+    HIPDRT_REQUIRE(p->n <= 4096, "the DOP posterior: n <= 4096");
+    HIPDRT_REQUIRE(q->nu && q->basis_nu, "NULL pointer");
+    HIPDRT_REQUIRE(q->nn >= 1 && q->nn <= 65536, "1 <= nn <= 65536");
+    HIPDRT_REQUIRE(q->order >= 0 && q->order <= 2, "order must be 0, 1 or 2");
+    HIPDRT_REQUIRE(q->nu_epsilon > 0.0 && std::isfinite(q->nu_epsilon), "nu_epsilon > 0");
+    for (int i = 0; i < q->nn; ++i)
+        HIPDRT_REQUIRE(std::isfinite(q->nu[i]) && (i == 0 || q->nu[i] >= q->nu[i - 1]), "nu must be finite and ascending");
+    for (int j = 0; j < p->desc.dop_size; ++j) HIPDRT_REQUIRE(std::isfinite(q->basis_nu[j]), "basis_nu must be finite");
+    if (q->normalize_by) {
+        HIPDRT_REQUIRE(q->nu_basis_area > 0.0 && std::isfinite(q->nu_basis_area), "nu_basis_area > 0");
+        for (int i = 0; i < q->nn; ++i)
+            HIPDRT_REQUIRE(q->normalize_by[i] > 0.0 && std::isfinite(q->normalize_by[i]), "normalize_by must be positive and finite");
+    }
+    return HIPDRT_OK;
+}
+// ... and of the dop_scale_vector of members b0 .. b0 + nb - 1 as hipdrt_plan_set_predict_desc left it on the device: 1 / it scales P.
+// (That of a member whose fit failed is not looked at: its data may not have been finite, and its rows are NaN anyway.)
+static int dop_check_scales(const hipdrt_plan* p, hipStream_t st, int b0, int nb) {
+    const int nd = p->desc.dop_size;
+    std::vector<double> dsv((size_t)nb * nd);
+    std::vector<int> fit(nb);
+    HIPDRT_CHECK(hipMemcpyAsync(dsv.data(), p->pd_dop_scale.d() + (size_t)b0 * nd, dsv.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipMemcpyAsync(fit.data(), p->fit_status.i() + b0, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    for (int b = 0; b < nb; ++b)
+        for (int j = 0; j < nd && fit[b] >= 0; ++j)
+            HIPDRT_REQUIRE(dsv[(size_t)b * nd + j] > 0.0 && std::isfinite(dsv[(size_t)b * nd + j]),
+                           "dop_scale_vector must be finite and positive");
     return HIPDRT_OK;
 }
 }  // namespace hipdrt
@@ -256,30 +330,98 @@ int hipdrt_plan_predict_dop(hipdrt_plan* p, const double* nu, int nn, const doub
         for (int i = 0; i < nn; ++i) HIPDRT_REQUIRE(normalize_by[i] > 0.0 && std::isfinite(normalize_by[i]), "normalize_by must be positive and finite");
     }
     hipStream_t st; TRY(enter(p->ctx, &st));
-    const int B = p->B, n = p->n, nd = p->desc.dop_size;
-    DevBuf dnu, dbn, dnorm, dE, dxd, dout;
-    TRY(upload(dnu, nu, (size_t)nn * sizeof(double), st));
-    TRY(upload(dbn, basis_nu, (size_t)nd * sizeof(double), st));
-    if (normalize_by) TRY(upload(dnorm, normalize_by, (size_t)nn * sizeof(double), st));
-    HIPDRT_CHECK(dE.alloc((size_t)nn * nd * sizeof(double)));
-    HIPDRT_CHECK(dout.alloc((size_t)B * nn * sizeof(double)));
-    HIPDRT_CHECK(dxd.alloc((size_t)B * nd * sizeof(double)));
+    DopRequest R;
+    TRY(R.begin(p, nu, nn, basis_nu, normalize_by, st));
     PredictTimer tm(p->ctx, st);
-    TRY(func_eval_dev(st, dbn.d(), nd, dnu.d(), nn, nu_epsilon, 0, 1.0, dE.d(), nd));
-    launch_scale_block(st, B, nd, p->x.d(), n, p->desc.dop_start, p->pd_dop_scale.d(), dxd.d());
-    launch_apply_rows(st, B, nd, dxd.d(), nd, 0, nn, dE.d(), nd, p->pd_cs.d(), nullptr, dout.d(), nn);
-    LAUNCH_OK();
-    DopArgs a{};
-    a.nn = nn; a.include_ideal = include_ideal != 0; a.dop = dout.d(); a.nu = dnu.d(); a.norm = normalize_by ? dnorm.d() : nullptr;
-    a.basis_area = nu_basis_area; a.X = p->x.d(); a.ldx = n; a.cs = p->pd_cs.d();
-    a.idx_rinf = p->pd_idx_rinf; a.idx_induc = p->pd_idx_induc; a.idx_cinv = p->pd_idx_cinv;
-    a.inductance_scale = p->pd_inductance_scale; a.capacitance_scale = p->pd_capacitance_scale; a.fit_status = p->fit_status.i();
-    launch_dop_assemble(st, B, a);
-    LAUNCH_OK();
+    TRY(dop_mean_dev(p, st, R, nu_epsilon, 0, nu_basis_area, include_ideal));
     tm.mark();
-    HIPDRT_CHECK(hipMemcpyAsync(out, dout.p, (size_t)B * nn * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (status) HIPDRT_CHECK(hipMemcpyAsync(status, p->fit_status.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipMemcpyAsync(out, R.dmu.p, R.dmu.bytes, hipMemcpyDeviceToHost, st));
+    if (status) HIPDRT_CHECK(hipMemcpyAsync(status, p->fit_status.p, (size_t)p->B * sizeof(int), hipMemcpyDeviceToHost, st));
     HIPDRT_CHECK(hipStreamSynchronize(st));
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+// DRT.predict_dop_ci (drt1d.py:3233-3258) and the diagonal of DRT.estimate_dop_cov (3153-3198) of every member: the mean chain above
+// at order k, then one Gram/L2 rebuild, the congruence scaling by every member's own 1 / dop_scale_vector and one factorisation per
+// member (plan_quadratic_forms_dev), then dop_band_kernel
+int hipdrt_plan_dop_posterior(hipdrt_plan* p, const hipdrt_dop_args* q, double* mu, double* lo, double* hi, double* var,
+                              int* status) try {
+    HIPDRT_REQUIRE(p && q, "NULL pointer");
+    TRY(dop_check_request(p, q));
+    const bool band = lo || hi || var;
+    HIPDRT_REQUIRE(!(lo || hi) || (std::isfinite(q->s_lo) && std::isfinite(q->s_hi)), "s_lo and s_hi must be finite");
+    hipStream_t st; TRY(enter(p->ctx, &st));
+    const int B = p->B, nn = q->nn, nd = p->desc.dop_size;
+    if (band) TRY(dop_check_scales(p, st, 0, B));
+    DopRequest R;
+    TRY(R.begin(p, q->nu, nn, q->basis_nu, q->normalize_by, st));
+    DevBuf dsinv, scratch, dvar, dvstat;
+    if (band) HIPDRT_CHECK(dsinv.alloc((size_t)B * nd * sizeof(double)));
+    PredictTimer tm(p->ctx, st);
+    TRY(dop_mean_dev(p, st, R, q->nu_epsilon, q->order, q->nu_basis_area, q->include_ideal));
+    tm.mark();
+    DevOuts outs;
+    if (band) {
+        launch_dop_recip(st, B, nd, p->pd_dop_scale.d(), nd, dsinv.d());
+        LAUNCH_OK();
+        TRY(plan_quadratic_forms_dev(p, live_source(p), -1, R.dE.d(), nn, nd, p->desc.dop_start, scratch, dvar, dvstat, dsinv.d()));
+        double *dlo = nullptr, *dhi = nullptr, *dvo = nullptr;
+        TRY(outs.want(lo, (size_t)B * nn, dlo)); TRY(outs.want(hi, (size_t)B * nn, dhi)); TRY(outs.want(var, (size_t)B * nn, dvo));
+        launch_dop_band(st, B, nn, R.dmu.d(), dvar.d(), (long long)((nn + 15) / 16) * 16, p->pd_cs.d(),
+                        q->normalize_by ? R.dnorm.d() : nullptr, q->s_lo, q->s_hi, dvstat.i(), p->fit_status.i(), dlo, dhi, dvo);
+        LAUNCH_OK();
+        tm.mark();
+        TRY(outs.back(st));
+    }
+    if (mu) HIPDRT_CHECK(hipMemcpyAsync(mu, R.dmu.p, R.dmu.bytes, hipMemcpyDeviceToHost, st));
+    std::vector<int> hs(B), hv(B, 0);
+    HIPDRT_CHECK(hipMemcpyAsync(hs.data(), p->fit_status.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (band) HIPDRT_CHECK(hipMemcpyAsync(hv.data(), dvstat.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    if (status) merge_status(B, hs.data(), band ? hv.data() : nullptr, status);
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+// DRT.estimate_dop_cov (drt1d.py:3153-3198) of member b: plan_full_cov's route (plan_post.hip) on the scaled image of that member's P
+// in the single-member form -- the factorisation leaves Y = E L^-T behind the factor, rows_outer_kernel forms Y Y' cs_b^2 -- then
+// upstream's broadcast division of column j by normalize_by[j]^2 on the host
+int hipdrt_plan_dop_cov(hipdrt_plan* p, int b, const hipdrt_dop_args* q, double* out, int* status) try {
+    HIPDRT_REQUIRE(p && q && out, "NULL pointer");
+    TRY(dop_check_request(p, q));
+    HIPDRT_REQUIRE(b >= 0 && b < p->B, "spectrum index out of range");
+    hipStream_t st; TRY(enter(p->ctx, &st));
+    const int B = p->B, nn = q->nn, nd = p->desc.dop_size;
+    const size_t cells = (size_t)nn * nn;
+    TRY(dop_check_scales(p, st, b, 1));
+    DopRequest R;
+    TRY(R.begin(p, q->nu, nn, q->basis_nu, nullptr, st));
+    DevBuf dsinv, scratch, dvar, dvstat, dcov;
+    HIPDRT_CHECK(dsinv.alloc((size_t)B * nd * sizeof(double)));
+    HIPDRT_CHECK(dcov.alloc(cells * sizeof(double)));
+    TRY(func_eval_dev(st, R.dbn.d(), nd, R.dnu.d(), nn, q->nu_epsilon, q->order, 1.0, R.dE.d(), nd));
+    launch_dop_recip(st, B, nd, p->pd_dop_scale.d(), nd, dsinv.d());
+    LAUNCH_OK();
+    TRY(plan_quadratic_forms_dev(p, live_source(p), b, R.dE.d(), nn, nd, p->desc.dop_start, scratch, dvar, dvstat, dsinv.d()));
+    double cs = 1.0;
+    int hv = 0, hf = 0;
+    HIPDRT_CHECK(hipMemcpyAsync(&cs, p->pd_cs.d() + b, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipMemcpyAsync(&hv, dvstat.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipMemcpyAsync(&hf, p->fit_status.i() + b, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    int merged = 0;
+    merge_status(1, &hf, &hv, &merged);
+    if (status) *status = merged;
+    if (merged < 0) {                            // (the reference warns and returns None)
+        for (size_t i = 0; i < cells; ++i) out[i] = __builtin_nan("");
+        return HIPDRT_OK;
+    }
+    posterior_cov_dev(st, scratch.d(), p->n, nn, cs * cs, dcov.d());
+    LAUNCH_OK();
+    HIPDRT_CHECK(hipMemcpyAsync(out, dcov.p, cells * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    if (q->normalize_by)
+        for (int i = 0; i < nn; ++i)
+            for (int j = 0; j < nn; ++j) out[(size_t)i * nn + j] /= q->normalize_by[j] * q->normalize_by[j];
     return HIPDRT_OK;
 } HIPDRT_CATCH
 

@@ -4,8 +4,8 @@
 //     Y[b][i] = scale_b * sum_j E[i][j] * x[b][col_offset + j]            (a B x r x K product, x resident on the device)
 //
 // followed by a per-element epilogue (credible band, impedance assembly; for a prepared plan the voltage response, the impedance
-// with every special term and the distribution of phasances: hipdrt/models/response.py).  FP64 only; the contraction runs on
-// v_mfma_f64_16x16x4_f64.  hipdrt/models/predict.py is the same arithmetic in numpy.
+// with every special term, the distribution of phasances and its posterior: hipdrt/models/response.py).  FP64 only (SURVEY.md
+// fact 4); the contraction runs on v_mfma_f64_16x16x4_f64.  hipdrt/models/predict.py is the same arithmetic in numpy.
 //
 // Layout.  A 256-thread workgroup (4 wavefronts) owns 32 spectra x 64 evaluation rows.  Per 64-wide slab of k it stages
 // x[32][64] and E[64][64] through LDS (both k-contiguous, leading dimension 68: the operand reads below then hit every bank
@@ -345,6 +345,95 @@ __global__ void scale_block_kernel(int B, int nd, const double* __restrict__ X, 
 
 void launch_scale_block(hipStream_t st, int B, int nd, const double* X, long long ldx, int col, const double* v, double* out) {
     hipLaunchKernelGGL(scale_block_kernel, dim3(B, (nd + 255) / 256), dim3(256), 0, st, B, nd, X, ldx, col, v, out);
+}
+
+// ---- the posterior of the distribution of phasances (drt1d.py:3153-3198 estimate_dop_cov, 3233-3258 predict_dop_ci) -----------------
+// estimate_param_cov (4126-4133) rescales inv(P) by D = diag(dop_scale_vector) on both sides of its DOP block, and under solve_rp D
+// differs from member to member.  The variance kernel takes one shared set of packed rows, so the members' scales go into P instead:
+// with S = diag(s), s = 1 / dop_scale_vector on the DOP unknowns and 1 elsewhere, inv(S P S) = D inv(P) D, and the shared rows E
+// over the DOP columns give e' D inv(P)[dop, dop] D e from the chain that serves the DRT band.
+//
+// s is formed once per member, by one correctly rounded division per entry, so every tile of a member sees the same bits.
+__global__ void dop_recip_kernel(int B, int nd, const double* __restrict__ dsv, long long dsv_stride, double* __restrict__ sinv) {
+    const int j = blockIdx.y * blockDim.x + threadIdx.x, b = blockIdx.x;
+    if (j >= nd || b >= B) return;
+    const double d = dsv[(size_t)b * dsv_stride + j];
+    sinv[(size_t)b * nd + j] = (d > 0.0 && d < INFINITY) ? 1.0 / d : 1.0;
+}
+
+void launch_dop_recip(hipStream_t st, int B, int nd, const double* dsv, long long dsv_stride, double* sinv) {
+    hipLaunchKernelGGL(dop_recip_kernel, dim3(B, (nd + 255) / 256), dim3(256), 0, st, B, nd, dsv, dsv_stride, sinv);
+}
+
+// Entry (i, j) of every lower tile becomes (P_ij s_i) s_j, in that order: two roundings, the same for a member alone and inside a
+// batch.  One wavefront per tile in pack_p_kernel's lane map (gram.hip): lane l holds row l & 15 and, as two double2, the columns
+// q, q + 4 and q + 8, q + 12 with q = l >> 4 -- 16-byte loads and stores.  Only the tiles whose row range or column range meets the
+// DOP block are visited: workgroup (k, y) takes tile row t = t0 + y up to its diagonal tile (k <= t) and tile column t below the
+// band (k > t1; the tiles (k, t) with t < k <= t1 belong to row k), so each of them is visited once.  Only entries with i or j in
+// the block are written: the zeros beyond n, the identity padding and the tiles above the diagonal stay as they were.
+__global__ __launch_bounds__(64) void scale_p_kernel(int nt, int t0, int t1, int dop_start, int dop_size,
+                                                     const double* __restrict__ sinv, long long sinv_stride,
+                                                     double* __restrict__ Ppk, long long ppk_stride, int nchp) {
+    const int b = blockIdx.x / nt, k = blockIdx.x % nt, t = t0 + blockIdx.y, lane = threadIdx.x;
+    int tr, tc;
+    if (k <= t) { tr = t; tc = k; }
+    else if (k > t1) { tr = k; tc = t; }
+    else return;
+    const double* s = sinv + (size_t)b * sinv_stride;
+    double2* tile = reinterpret_cast<double2*>(Ppk + (size_t)b * ppk_stride + ((size_t)tr * nchp + tc) * 256);
+    const int i = tr * 16 + (lane & 15) - dop_start, j0 = tc * 16 + (lane >> 4) - dop_start;
+    const bool ri = i >= 0 && i < dop_size;
+    const double si = ri ? s[i] : 1.0;
+    const int fo = (lane & 15) * 4 + (lane >> 4);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int ja = j0 + 8 * h, jb = ja + 4;
+        const bool ca = ja >= 0 && ja < dop_size, cb = jb >= 0 && jb < dop_size;
+        if (!(ri || ca || cb)) continue;
+        double2 v = tile[64 * h + fo];
+        if (ri) { v.x = v.x * si; v.y = v.y * si; }
+        if (ca) v.x = v.x * s[ja];
+        if (cb) v.y = v.y * s[jb];
+        tile[64 * h + fo] = v;
+    }
+}
+
+void launch_scale_p(hipStream_t st, int B, int n, int dop_start, int dop_size, const double* sinv, long long sinv_stride,
+                    double* Ppk, long long ppk_stride) {
+    const int nt = (n + 15) / 16, t0 = dop_start / 16, t1 = (dop_start + dop_size - 1) / 16;
+    hipLaunchKernelGGL(scale_p_kernel, dim3((unsigned)B * nt, t1 - t0 + 1), dim3(64), 0, st, nt, t0, t1, dop_start, dop_size, sinv,
+                       sinv_stride, Ppk, ppk_stride, qp_nchp(n));
+}
+
+// predict_dop_ci's band on the mean that dop_assemble_kernel left (ideal elements included: upstream adds no variance for them):
+// estimate_dop_cov divides the covariance by get_dop_norm's vector squared, so sigma = sqrt(var cs^2) / norm[i].
+__global__ void dop_band_kernel(int B, int nn, const double* __restrict__ mu, const double* __restrict__ var, long long ldv,
+                                const double* __restrict__ cs, const double* __restrict__ norm, double s_lo, double s_hi,
+                                const int* __restrict__ var_status, const int* __restrict__ fit_status, double* __restrict__ lo,
+                                double* __restrict__ hi, double* __restrict__ var_out) {
+    const int i = blockIdx.y * blockDim.x + threadIdx.x, b = blockIdx.x;
+    if (i >= nn || b >= B) return;
+    const size_t o = (size_t)b * nn + i;
+    double l = NAN, h = NAN, vo = NAN;
+    if (var_status[b] == 0 && fit_status[b] >= 0) {
+        const double v = var[(size_t)b * ldv + i] * (cs[b] * cs[b]);
+        double sg = sqrt(v);
+        vo = v;
+        if (norm) { sg = sg / norm[i]; vo = v / (norm[i] * norm[i]); }
+        const double m = mu[o];
+        l = m + s_lo * sg;
+        h = m + s_hi * sg;
+    }
+    if (lo) lo[o] = l;
+    if (hi) hi[o] = h;
+    if (var_out) var_out[o] = vo;
+}
+
+void launch_dop_band(hipStream_t st, int B, int nn, const double* mu, const double* var, long long ldv, const double* cs,
+                     const double* norm, double s_lo, double s_hi, const int* var_status, const int* fit_status, double* lo,
+                     double* hi, double* var_out) {
+    hipLaunchKernelGGL(dop_band_kernel, dim3(B, (nn + 255) / 256), dim3(256), 0, st, B, nn, mu, var, ldv, cs, norm, s_lo, s_hi,
+                       var_status, fit_status, lo, hi, var_out);
 }
 
 }  // namespace hipdrt

@@ -430,6 +430,113 @@ class PostFitMixin:
                                          include_ideal=include_ideal)
         return (nu, dop[b]) if return_nu else dop[b]
 
+    # ---- the posterior of the distribution of phasances (drt1d.py:3153-3198, 3233-3258) on the prepared plan of the last fit --------
+    def _dop_grid(self):
+        """predict_dop's default grid (drt1d.py:3275-3280)"""
+        nu = np.unique(np.concatenate([self.basis_nu, np.linspace(-1, 1, 1001)]))
+        return np.unique(np.concatenate([nu, np.array([-1, 0, 1])]))
+
+    def _dop_posterior_request(self, what, nu, default_nu, normalize, normalize_tau, normalize_quantiles, order, delta_density,
+                               x=None, p_matrix=None):
+        """the checks of a DOP posterior request -> (plan, the ascending grid, the permutation that sorted the caller's nu,
+        get_dop_norm's vector on the grid or None, the area of one nu basis function); default_nu() is the grid of nu=None"""
+        if delta_density:
+            raise NotImplementedError(f'{what}: delta_density=True is not taken')
+        if order not in (0, 1, 2):
+            raise ValueError(f'Invalid order {order}. Options: 0, 1, 2')
+        plan, scales = self._predict_plan(what, x=x, p_matrix=p_matrix)
+        p0 = self._members()[0]
+        if scales is None or not p0['dop']:
+            raise RuntimeError(f'{what} needs a finished fit with fit_dop=True')
+        nu = np.asarray(default_nu() if nu is None else nu, dtype=float).ravel()
+        perm = np.argsort(nu, kind='stable')
+        nu = nu[perm]
+        normalize_by = None
+        if normalize:
+            if normalize_tau is None:
+                normalize_tau = pp.get_tau_lim(p0['frequencies'], p0.get('sample_times'), p0.get('step_times'))
+            normalize_by = response.dop_norm(nu, normalize_tau, self.nu_epsilon, normalize_quantiles)
+        self._set_predict_desc(plan)
+        return plan, nu, perm, normalize_by, np.sqrt(np.pi) / self.nu_epsilon
+
+    def predict_dop_ci_batch(self, nu=None, normalize=False, normalize_tau=None, quantiles=(0.025, 0.975), order=0,
+                             normalize_quantiles=(0.25, 0.75), delta_density=False, include_ideal=True, return_info=False):
+        """DRT.predict_dop_ci (drt1d.py:3233-3258) for every member of the last fit_dop fit -> (lo, hi, ok), each band (B, len(nu)):
+        the mean of derivative order 0, 1 or 2 plus the quantiles' numbers of posterior standard deviations, sigma^2 =
+        diag(E D inv(P) D E') coefficient_scale^2 / normalize_by^2 with D = diag(dop_scale_vector) of that member (under solve_rp
+        every member has its own).  Everything is formed on the device from the resident coefficients and the fit's own final
+        P (hipdrt_plan_dop_posterior): one Gram/L2 rebuild and one Cholesky factorisation per member.  ok (B,) bool is False where
+        the fit failed or P is not positive definite (rows NaN; upstream returns (None, None)).  return_info adds a dict: nu, mu,
+        sigma, status.
+
+        Where upstream is inconsistent: with nu=None its covariance is taken on basis_nu and its mean on predict_dop's
+        1034-point grid, so its own predict_dop_ci(nu=None) adds arrays of different lengths; here both use predict_dop's grid.
+        An unsorted nu is sorted by upstream for the mean only; here mean and sigma are both on the sorted grid, which is
+        info['nu'].  Upstream adds no variance for R_inf, the inductance and C_inv (include_ideal), and neither is any added here.
+        normalize_quantiles defaults to upstream's (0.25, 0.75) for this method, not predict_dop's (0, 1).  Last device batch only."""
+        what = 'predict_dop_ci'
+        plan, nu, _, normalize_by, area = self._dop_posterior_request(
+            what, nu, self._dop_grid, normalize, normalize_tau, normalize_quantiles, order, delta_density)
+        mu, lo, hi, var, status = plan.dop_posterior(nu, self.basis_nu, self.nu_epsilon, order=order, normalize_by=normalize_by,
+                                                     nu_basis_area=area, include_ideal=include_ideal,
+                                                     n_sigma=predict.n_sigma(quantiles), want_var=bool(return_info))
+        ok = status >= 0
+        if return_info:
+            return lo, hi, ok, dict(nu=nu, mu=mu, sigma=np.sqrt(var), status=status)
+        return lo, hi, ok
+
+    def predict_dop_ci(self, nu=None, x=None, normalize=False, normalize_tau=None, quantiles=(0.025, 0.975), order=0,
+                       normalize_quantiles=(0.25, 0.75), delta_density=False, include_ideal=True, b=0):
+        """DRT.predict_dop_ci (drt1d.py:3233-3258) of member ``b`` of the last fit_dop fit: (lo, hi) on the sorted grid, or
+        (None, None) with upstream's warning when P is not positive definite.  The choices of predict_dop_ci_batch hold."""
+        if x is not None:
+            raise NotImplementedError('predict_dop_ci: the x= override is not taken (predictions use the coefficients on the device)')
+        lo, hi, ok = self.predict_dop_ci_batch(nu=nu, normalize=normalize, normalize_tau=normalize_tau, quantiles=quantiles,
+                                               order=order, normalize_quantiles=normalize_quantiles, delta_density=delta_density,
+                                               include_ideal=include_ideal)
+        if not ok[b]:
+            warnings.warn('Singular P matrix - could not obtain covariance estimate')
+            return None, None
+        return lo[b], hi[b]
+
+    def estimate_dop_var_batch(self, nu=None, normalize=False, normalize_tau=None, normalize_quantiles=(0.25, 0.75), order=0,
+                               delta_density=False):
+        """np.diag(DRT.estimate_dop_cov(...)) (drt1d.py:3153-3198) for every member of the last fit_dop fit -> (var (B, len(nu)),
+        ok (B,) bool), from the device (hipdrt_plan_dop_posterior without a mean or a band).  nu=None is basis_nu, as upstream's
+        covariance takes it; the rows come back in the order of the caller's nu."""
+        plan, nu, perm, normalize_by, area = self._dop_posterior_request(
+            'estimate_dop_var', nu, lambda: self.basis_nu, normalize, normalize_tau, normalize_quantiles, order,
+            delta_density)
+        _, _, _, var, status = plan.dop_posterior(nu, self.basis_nu, self.nu_epsilon, order=order, normalize_by=normalize_by,
+                                                  nu_basis_area=area, include_ideal=False)
+        out = np.empty_like(var)
+        out[:, perm] = var
+        return out, status >= 0
+
+    def estimate_dop_cov(self, nu=None, p_matrix=None, normalize=False, normalize_tau=None, normalize_quantiles=(0.25, 0.75),
+                         var_floor=0.0, order=0, delta_density=False, b=0):
+        """DRT.estimate_dop_cov (drt1d.py:3153-3198) of member ``b`` of the last fit_dop fit: E x_cov[dop, dop] E' with x_cov =
+        estimate_param_cov's inv(P) coefficient_scale^2, rescaled on both sides by dop_scale_vector, formed on the device from
+        the Cholesky factor of the scaled P (hipdrt_plan_dop_cov).  nu=None is basis_nu as upstream; rows and columns follow the
+        caller's nu.  With normalize upstream divides by get_dop_norm's vector squared as a plain broadcast -- column j by
+        normalize_by[j]^2 -- so the matrix is not symmetric; exactly that is kept, and its diagonal is what the band uses.
+        var_floor is applied to the returned diagonal on the host, as upstream applies it.  None (with upstream's warning) when
+        P is not positive definite."""
+        plan, nu, perm, normalize_by, area = self._dop_posterior_request(
+            'estimate_dop_cov', nu, lambda: self.basis_nu, normalize, normalize_tau, normalize_quantiles, order,
+            delta_density, p_matrix=p_matrix)
+        cov, status = plan.dop_cov(b, nu, self.basis_nu, self.nu_epsilon, order=order, normalize_by=normalize_by, nu_basis_area=area)
+        if status < 0:
+            warnings.warn('Singular P matrix - could not obtain covariance estimate')
+            return None
+        out = np.empty_like(cov)
+        out[np.ix_(perm, perm)] = cov
+        if var_floor > 0:
+            var = np.diag(out).copy()
+            var[var < var_floor] = var_floor
+            np.fill_diagonal(out, var)
+        return out
+
     # ---- peak finding (drt1d.py:3753-3947; mapping/curvature.py, mapping/drtmd.py:1023-1106) on the last fitted batch ------------
     def _find_peaks_device(self, what, tau, ppd, normalize, sign, method, extend_var, want=None, **opt_kw):
         plan, scales = self._predict_plan(what)

@@ -184,3 +184,35 @@ def predict_dop_rows(basis_matrix, nu, fp, normalize_by=None, nu_basis_area=1.0,
             dop[idx] += e
             mag[idx] += np.abs(e)
     return (dop, mag) if return_abs else dop
+
+
+def dop_cov_rows(p_matrix, dop_start, dop_scale_vector, coefficient_scale, basis_matrix, normalize_by=None):
+    """DRT.estimate_dop_cov (drt1d.py:3153-3198; no delta_density, var_floor left to the caller) of one member -> (nn, nn), by
+    upstream's route: np.linalg.inv of the fit's P, the two-sided rescaling of its DOP block by dop_scale_vector and the factor
+    coefficient_scale^2 of estimate_param_cov (4126-4133), then basis_matrix @ x_cov[dop, dop] @ basis_matrix.T with basis_matrix
+    (nn, dop_size) = basis.construct_func_eval_matrix(basis_nu, nu, 'gaussian', nu_epsilon, order).  normalize_by (nn,) is
+    get_dop_norm's vector (dop_norm; None: not normalised): upstream divides by its square as a plain broadcast, so column j is
+    divided by normalize_by[j]^2 and the matrix is no longer symmetric; the diagonal is what the band uses.  A singular P raises
+    np.linalg.LinAlgError (upstream warns and returns None).  The device forms the same quantity from the Cholesky factor of
+    S P S, S = diag(1 / dop_scale_vector) on the DOP block (scale_p_kernel, csrc/predict.hip)."""
+    p_inv = np.linalg.inv(np.asarray(p_matrix, dtype=float))
+    dsv = np.asarray(dop_scale_vector, dtype=float)
+    a, e = int(dop_start), int(dop_start) + len(dsv)
+    dop_scale_mat = np.tile(dsv, (len(p_inv), 1))
+    p_inv[:, a:e] *= dop_scale_mat
+    p_inv[a:e, :] *= dop_scale_mat.T
+    x_cov = (p_inv * coefficient_scale ** 2)[a:e, a:e]
+    bm = np.asarray(basis_matrix, dtype=float)
+    cov = bm @ x_cov @ bm.T
+    if normalize_by is not None:
+        cov = cov / np.asarray(normalize_by, dtype=float) ** 2
+    return cov
+
+
+def dop_band(mu, var, quantiles=(0.025, 0.975)):
+    """DRT.predict_dop_ci (drt1d.py:3233-3258) from the mean and the diagonal of dop_cov_rows: (mu + s_lo sigma, mu + s_hi sigma),
+    sigma = var ** 0.5, s the quantiles' numbers of standard deviations (stats.std_normal_quantile)"""
+    from . import predict
+    s_lo, s_hi = predict.n_sigma(quantiles)
+    mu, sigma = np.asarray(mu, dtype=float), np.asarray(var, dtype=float) ** 0.5
+    return mu + s_lo * sigma, mu + s_hi * sigma

@@ -716,6 +716,36 @@ int hipdrt_plan_predict_z_model(hipdrt_plan* plan, const hipdrt_z_model_args* ar
 int hipdrt_plan_predict_dop(hipdrt_plan* plan, const double* nu, int nn, const double* basis_nu, double nu_epsilon,
                             const double* normalize_by, double nu_basis_area, int include_ideal, double* out, int* status);
 
+typedef struct {
+    const double* nu; int nn;                  /* evaluation grid, finite and ascending                                          */
+    const double* basis_nu; double nu_epsilon; /* [dop_size] the DOP basis grid and its Gaussian epsilon                         */
+    int order;                                 /* 0, 1, 2: the derivative of the basis that the rows evaluate                    */
+    const double* normalize_by;                /* [nn] get_dop_norm's vector, or NULL: not normalised                            */
+    double nu_basis_area;                      /* area of one basis function (read with normalize_by only)                       */
+    int include_ideal;                         /* R_inf, inductance and C_inv added to the mean at nu = 0, 1, -1                 */
+    double s_lo, s_hi;                         /* numbers of standard deviations of the band (stats.std_normal_quantile)         */
+} hipdrt_dop_args;
+/* DRT.predict_dop_ci (drt1d.py:3233-3258) and the diagonal of DRT.estimate_dop_cov (3153-3198) for every member of the fitted batch
+ * of a prepared plan with a DOP block, at derivative order 0, 1 or 2.  mu is hipdrt_plan_predict_dop's chain fed the order-k rows
+ * E = hipdrt_func_eval_matrix(basis_nu, nu, nu_epsilon, order) (order 0: the bits of hipdrt_plan_predict_dop).  The variance is
+ *   var[b][i] = e_i' D_b inv(P_b)[dop, dop] D_b e_i cs_b^2 / normalize_by[i]^2,   D_b = diag(dop_scale_vector_b)
+ * (estimate_param_cov's two-sided rescaling, 4126-4133): the packed image of every member's final P is scaled by 1 / dop_scale_vector_b
+ * on its DOP rows and columns (inv(S P S) = D inv(P) D), and the shared rows, placed over the DOP columns, go through the Cholesky
+ * kernel of hipdrt_plan_distribution_var: one Gram/L2 rebuild and one factorisation per member.  lo, hi = mu + s_lo sigma,
+ * mu + s_hi sigma with sigma = sqrt(var cs^2) / normalize_by; upstream adds no variance for the ideal elements, nor is any added here.
+ * mu, lo, hi, var: [B][nn], each may be NULL; with lo, hi and var all NULL nothing is factorised.  status [B] (may be NULL): the
+ * fit's status (< 0: NaN rows), or HIPDRT_PREDICT_NOT_PD when a variance was asked for and P is not positive definite (lo, hi, var
+ * NaN, mu valid).  Needs hipdrt_plan_set_predict_desc.  HIPDRT_E_INVALID for a plan without a DOP block, nu not ascending, order
+ * outside 0..2, n > 4096, or a dop_scale_vector entry of a member with a good fit that is not finite and positive.               */
+int hipdrt_plan_dop_posterior(hipdrt_plan* plan, const hipdrt_dop_args* args, double* mu, double* lo, double* hi, double* var,
+                              int* status);
+/* DRT.estimate_dop_cov (drt1d.py:3153-3198; var_floor is the caller's) of member b: out [nn][nn] =
+ * E D_b inv(P_b)[dop, dop] D_b E' cs_b^2, column j divided by normalize_by[j]^2 as upstream's broadcast divides it (the matrix is
+ * then not symmetric), from the same scaled image of P in the single-member form and rows_outer_kernel, as
+ * hipdrt_plan_distribution_cov.  include_ideal, s_lo and s_hi are not read.  *status (may be NULL): the fit's status, or
+ * HIPDRT_PREDICT_NOT_PD; out is NaN for either.  The refusals of hipdrt_plan_dop_posterior, and b outside the batch.                */
+int hipdrt_plan_dop_cov(hipdrt_plan* plan, int b, const hipdrt_dop_args* args, double* out, int* status);
+
 /* ---- peak finding for the fitted batch ---------------------------------------------------------------------------------------
  * Options of DRT.find_peaks (hybdrt/models/drt1d.py:3753-3947) and of the map's peak probabilities (curvature.peak_prob_1d,
  * hybdrt/mapping/curvature.py:12-58; DRTMD.predict_curv_prob, hybdrt/mapping/drtmd.py:1097-1104).                              */

@@ -264,6 +264,23 @@ typedef struct hipdrt_debug_posterior_args {
     double* var; int* status; double* cov; double* bex; double* tail;
 } hipdrt_debug_posterior_args;
 int hipdrt_debug_posterior(hipdrt_ctx* ctx, const hipdrt_debug_posterior_args* a);
+/* test hook (tests/test_gpu_dop_posterior.py): the same chain with the per-member congruence scaling of the packed P in front of it,
+ * as hipdrt_plan_dop_posterior / hipdrt_plan_dop_cov run it (scale_p_kernel between the packing of P and posterior_var_dev):
+ * entry (i, j) of every lower tile of member b is multiplied by s_i, then by s_j, with s = 1.0 / dop_scale_vector_b on the unknowns
+ * dop_start .. dop_start + dop_size - 1 and 1 elsewhere, so that var = rows_i' (S P S)^-1 rows_i.
+ *   post: hipdrt_debug_posterior's arguments, read as there (every member has its own image of P, a shared P is packed B times);
+ *   dop_scale_vector [dop_size], or [B][dop_size] when dop_scale_batched != 0.
+ * One more optional output: ppk [nb][nchp][nchp][256], the packed image after the scaling (tiles the kernels do not write are zero),
+ * of all B members or, with cov_member >= 0, of that member.  Borders and HIPDRT_E_NUMERIC as hipdrt_debug_posterior.
+ * HIPDRT_E_INVALID, and nothing is launched, for its refusals, dop_size < 1, a block outside [0, n), or a dop_scale_vector entry
+ * that is not finite and positive.                                                                                                */
+typedef struct hipdrt_debug_dop_posterior_args {
+    hipdrt_debug_posterior_args post;
+    int dop_start, dop_size;
+    const double* dop_scale_vector; int dop_scale_batched;
+    double* ppk;
+} hipdrt_debug_dop_posterior_args;
+int hipdrt_debug_dop_posterior(hipdrt_ctx* ctx, const hipdrt_debug_dop_posterior_args* a);
 
 /* test hook (tests/test_gpu_qp_loop.py): launch_qp (csrc/qp.hip) as it is, on host arrays, with its arguments filled the way the fit
  * loop fills them (loop_qp_args, csrc/plan_fit.hip) -- a form hipdrt_qp_batch cannot produce: P reaches the kernel as packed tiles only
@@ -306,7 +323,9 @@ int hipdrt_debug_lpt_order(hipdrt_ctx* ctx, int B, const int* iters, const int* 
  * of the last hipdrt_plan_llh_terms / _obs_llh_terms(_w) (ms[0] = ms[1]: its one launch), hipdrt_plan_score_candidates (ms[1]: all
  * launches),
  * hipdrt_plan_predict_drt / hipdrt_plan_predict_z / hipdrt_plan_find_peaks (ms[0]: the mean rows, ms[1]: all launches, peaks_kernel
- * included) or hipdrt_plan_predict_response / _z_model / _dop (ms[0] = ms[1]: all launches; _z_model with the upload of its grids and tables) of a plan of this context, by HIP
+ * included), hipdrt_plan_predict_response / _z_model / _dop (ms[0] = ms[1]: all launches; _z_model with the upload of its grids and
+ * tables) or hipdrt_plan_dop_posterior (ms[0]: the mean rows, ms[1]: with the Gram/L2 rebuild, the scaling, the factorisations and the
+ * band) of a plan of this context, by HIP
  * events around its launches (allocations and copies excluded): ms[0] up to the mean (predict_z: the whole prediction), ms[1] with
  * the credible band's factorisation included (equal to ms[0] without a band).                                                    */
 int hipdrt_debug_last_predict_ms(hipdrt_ctx* ctx, float* ms);
