@@ -203,7 +203,7 @@ int launch_cand_llh(hipStream_t st, const CandLlhArgs& a, int form) {
     if (form == 0) {
         HIPDRT_REQUIRE(cand_llh_fits_lds(a.m), "candidates: 16 rows of m doubles do not fit in LDS; use the scratch form");
         const size_t dyn = cand_dyn_lds(a.m);
-        if (int rc = set_lds_limit(reinterpret_cast<const void*>(cand_llh_kernel<0>), dyn, "cand_llh_kernel")) return rc;
+        if (int rc = set_lds(reinterpret_cast<const void*>(cand_llh_kernel<0>), dyn, "cand_llh_kernel")) return rc;
         hipLaunchKernelGGL(cand_llh_kernel<0>, grid, block, dyn, st, a);
     } else {
         HIPDRT_REQUIRE(a.scratch, "candidates: the scratch form needs its buffer");

@@ -8,6 +8,7 @@
 
 #include "../../include/hipdrt.h"
 #include "../../include/hipdrt_debug.h"
+#include "lds_layout.hpp"
 
 namespace hipdrt {
 
@@ -74,6 +75,10 @@ inline int set_lds_limit(const void* f, size_t bytes, const char* what) {
     const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e != hipSuccess) { set_error(std::string("hipFuncSetAttribute(") + what + "): " + hipGetErrorString(e)); return HIPDRT_E_HIP; }
     return HIPDRT_OK;
+}
+// the tail of every launcher with dynamic LDS: the attribute is raised only above the 64 KiB a kernel may have without it
+inline int set_lds(const void* f, size_t bytes, const char* what) {
+    return bytes <= 64 * 1024 ? 0 : set_lds_limit(f, bytes, what);
 }
 
 // per-workgroup LDS of a gfx950 CU, less the static part; and the refusal of a launch that needs more (dims: the sizes that decide it)
@@ -452,7 +457,6 @@ struct PeakResolveArgs {
     double* peak_gammas;                 // [B][max_peaks][nout]
 };
 int peak_resolve_check_opts(const hipdrt_peak_resolve_opts& o);
-int peak_resolve_ld(int nb);
 size_t peak_resolve_lds_bytes(int nfind, int nb, int nout, int max_peaks);
 // HIPDRT_E_INVALID, before any launch, when an option is out of range, an input the source needs is missing, or LDS cannot hold the shape
 int launch_peak_resolve(hipStream_t s, PeakResolveArgs a, int B);

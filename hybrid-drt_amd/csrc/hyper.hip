@@ -245,11 +245,8 @@ __global__ __launch_bounds__(HT) void init_weights_kernel(FitState st, int stage
     extern __shared__ double sm[];
     __shared__ double red[HNW];
     const int b = blockIdx.x, tid = threadIdx.x, n = st.n, m = st.m;
-    double* xs = sm;
-    double* tmp = xs + n;
-    double* tmp2 = tmp + m;
-    double* tmp3 = tmp2 + m;      // [2][m] present only when outlier_p is set
-    double* tmp4 = tmp3 + m;
+    const InitWeightsLds L = init_weights_lds(sm, n, m, st.opts.outlier_p > 0.0);
+    double *xs = L.xs, *tmp = L.tmp, *tmp2 = L.tmp2, *tmp3 = L.tmp3, *tmp4 = L.tmp4;
     if (st.qp_status[b] < 0) {
         if (tid == 0) { st.active[b] = 0; st.fit_status[b] = -1; }
         return;
@@ -479,19 +476,17 @@ __global__ __launch_bounds__(HT, 4) void hyper_kernel(FitState st, int it) {    
     if (!st.active[b]) return;
     HPROF_START();
     const int n = st.n, m = st.m, ns = st.ns, nd = n - ns;
-    double* xs = sm;              // [n]   new x
-    double* bsum = xs + n;        // [nd]  off-diagonal row sums of gamma @ diag(sqrt s)
-    double* gdia = bsum + nd;     // [nd]  diag(gamma)
-    double* sq = gdia + nd;       // [nd]  sqrt(s_k)
-    double* xh = sq + nd;         // [nd]  sign(x) sqrt|x|
-    double* tmp = xh + nd;        // [max(m, nd)]
-    const int tl = m > nd ? m : nd;
-    double* tmp2 = tmp + tl;      // [max(m, nd)]
+    const HyperLds L = hyper_lds(sm, n, m, ns, st.toeplitz_m, st.opts.outlier_p > 0.0);
+    double* xs = L.xs;            // [n]   new x
+    double* bsum = L.bsum;        // [nd]  off-diagonal row sums of gamma @ diag(sqrt s)
+    double* gdia = L.gdia;        // [nd]  diag(gamma)
+    double* sq = L.sq;            // [nd]  sqrt(s_k)
+    double* xh = L.xh;            // [nd]  sign(x) sqrt|x|
+    double* tmp = L.tmp;          // [max(m, nd)]
+    double* tmp2 = L.tmp2;        // [max(m, nd)]
     // [3][2 nd - 1] first columns of the Toeplitz penalty blocks (uniform ln-tau grids), mirrored around index nd - 1
     // so that entry (i, j) is cx[i - j + nd - 1] without an absolute value
-    // (toeplitz_m == 2, large joint fits: they start inside the second m-vector, behind the nd entries the Toeplitz phases use
-    // of it -- the weights phase, which needs all m, comes after the last use of the columns)
-    double* ctp = st.toeplitz_m == 2 ? tmp2 + nd : tmp2 + tl;
+    double* ctp = L.ctp;
     const int cw = 2 * nd - 1;
     const bool tpl = st.toeplitz_m != 0;
     if (tpl) {
@@ -737,7 +732,7 @@ __global__ __launch_bounds__(HT, 4) void hyper_kernel(FitState st, int it) {    
     HPROF(4);
     // weights
     double* wg = st.w + (size_t)b * m;
-    double* tmp3 = ctp + 3 * cw;       // [2][m], only present (and only touched) when outlier_p is set
+    double* tmp3 = L.tmp3;             // [2][m], only present (and only touched) when outlier_p is set
     estimate_weights_dev(st, b, st.vmm, xs, tmp, tmp2, tmp3, tmp3 + m, st.est_w + (size_t)b * m, wg, 0, -1, -1.0, st.premv);
     HPROF(5);
 
@@ -858,11 +853,7 @@ __global__ void make_h_kernel(double* h, int n, int ns, int nonneg) {
     h[i] = (nonneg || i < ns) ? 0.0 : 1e5;
 }
 
-size_t hyper_lds_bytes(int n, int m, int ns) {
-    const int nd = n - ns;
-    const int tl = m > nd ? m : nd;
-    return ((size_t)n + 4 * (size_t)nd + 2 * (size_t)tl + 3 * (size_t)(2 * nd - 1)) * sizeof(double);
-}
+size_t hyper_lds_bytes(int n, int m, int ns) { return hyper_lds(nullptr, n, m, ns, HYPER_ROWS, false).bytes; }
 
 int launch_prep(hipStream_t s, const FitState& st, int B) {
     if (st.prepared) hipLaunchKernelGGL(prep_prepared_kernel, dim3(B), dim3(HT), 0, s, st);
@@ -906,8 +897,7 @@ void launch_weight_method(hipStream_t s, const FitState& st, int B, double fixed
 }
 
 int launch_init_weights(hipStream_t s, const FitState& st, int B, int stage, int r0, int r1) {
-    // x + two row vectors, two more only for the outlier branch
-    const size_t lds = ((size_t)st.n + (st.opts.outlier_p > 0.0 ? 4 : 2) * (size_t)st.m) * sizeof(double);
+    const size_t lds = init_weights_lds(nullptr, st.n, st.m, st.opts.outlier_p > 0.0).bytes;
     if (lds > kLdsLimit) { set_error("initialize_weights: m too large for the LDS-resident kernel"); return HIPDRT_E_INVALID; }
     if (int rc = set_lds(reinterpret_cast<const void*>(init_weights_kernel), lds, "init_weights_kernel")) return rc;
     hipLaunchKernelGGL(init_weights_kernel, dim3(B), dim3(HT), lds, s, st, stage, r0, r1);
@@ -928,10 +918,8 @@ __global__ __launch_bounds__(HT) void llh_kernel(FitState st, double* __restrict
     extern __shared__ double sm[];
     __shared__ double red[HNW];
     const int b = blockIdx.x, tid = threadIdx.x, n = st.n, m = st.m;
-    double* xs = sm;
-    double* yh = xs + n;        // rm @ x
-    double* r2 = yh + m;        // residual^2
-    double* sh = r2 + m;        // vmm @ residual^2
+    const LlhLds L = llh_lds(sm, n, m);
+    double *xs = L.xs, *yh = L.yh, *r2 = L.r2, *sh = L.sh;      // x; rm @ x; residual^2; vmm @ residual^2
     const double* rv = st.rv + (size_t)b * m;
     for (int i = tid; i < n; i += HT) xs[i] = st.x[(size_t)b * n + i];
     __syncthreads();
@@ -975,7 +963,7 @@ __global__ __launch_bounds__(HT) void llh_kernel(FitState st, double* __restrict
 }
 
 int launch_llh(hipStream_t s, const FitState& st, int B, double* rss, double* slw, int stored, double scalar_w, double* w_out) {
-    const size_t lds = (size_t)(st.n + 3 * st.m) * sizeof(double);
+    const size_t lds = llh_lds(nullptr, st.n, st.m).bytes;
     if (int rc = set_lds(reinterpret_cast<const void*>(llh_kernel), lds, "llh_kernel")) return rc;
     hipLaunchKernelGGL(llh_kernel, dim3(B), dim3(HT), lds, s, st, rss, slw, stored, scalar_w, w_out);
     return 0;
@@ -1025,18 +1013,15 @@ void launch_scale_weights(hipStream_t s, const FitState& st, int B, double facto
 // two m-vectors, 2 = the columns inside the second m-vector (toeplitz_m == 2), 0 = the general row-streaming form (no columns in
 // LDS).  false: no layout fits.  The one place this is decided: launch_hyper and hipdrt_debug_hyper_form both ask here.
 bool hyper_lds_form(int n, int m, int ns, int toeplitz, bool outlier, int* form, size_t* lds_bytes) {
-    const size_t extra = outlier ? 2 * (size_t)m * sizeof(double) : 0;
-    size_t lds = hyper_lds_bytes(n, m, ns) + extra;
+    const auto bytes = [&](int layout) { return hyper_lds(nullptr, n, m, ns, layout, outlier).bytes; };
     int f = toeplitz ? 1 : 0;
-    if (lds > kLdsLimit && toeplitz && extra == 0) {
+    size_t lds = bytes(f);
+    if (lds > kLdsLimit && toeplitz && !outlier) {
         // large joint fits (config 5: m = 5120, n = 1078): no room for the mirrored Toeplitz columns NEXT to the two
-        // m-vectors -- they share the second one's space (see hyper_kernel); if even that does not fit, the general
+        // m-vectors -- they share the second one's space (HYPER_INSIDE); if even that does not fit, the general
         // row-streaming form of the same updates reads the penalty blocks from L2 instead
-        const size_t nd = (size_t)(n - ns), tl = (size_t)m > nd ? (size_t)m : nd, cols = 3 * (2 * nd - 1);
-        const size_t second = tl > nd + cols ? tl : nd + cols;
-        const size_t compact = ((size_t)n + 4 * nd + tl + second) * sizeof(double);
-        if (compact <= kLdsLimit) { f = 2; lds = compact; }
-        else { f = 0; lds -= cols * sizeof(double); }
+        if (bytes(HYPER_INSIDE) <= kLdsLimit) { f = 2; lds = bytes(HYPER_INSIDE); }
+        else { f = 0; lds = bytes(HYPER_DEMOTED); }
     }
     *form = f;
     *lds_bytes = lds;

@@ -1,6 +1,5 @@
 // Device helpers shared by the one-workgroup-per-spectrum kernels (hyper.hip, kk.hip, peaks.hip, peak_resolve.hip): 512-thread workgroups (peaks.hip,
-// peak_resolve.hip: 256, through the template argument), wavefront and block reductions, the bitonic sort, the row-slab matrix-vector product, and
-// the dynamic-LDS attribute of their launchers (the limit itself, kLdsLimit, is common.hpp's).
+// peak_resolve.hip: 256, through the template argument), wavefront and block reductions, the bitonic sort, and the row-slab matrix-vector product.
 #pragma once
 #include "common.hpp"
 
@@ -75,13 +74,7 @@ __device__ __forceinline__ double blk_min(double v, double* red) {
     return t;
 }
 
-// the length lds_sort needs for n values: the next power of two, at least 2
-static inline int next_pow2(int n) {
-    int p2 = 2;
-    while (p2 < n) p2 <<= 1;
-    return p2;
-}
-// ascending bitonic network over p2 (a power of two) doubles in LDS, NT threads
+// ascending bitonic network over p2 (a power of two, lds_layout.hpp: next_pow2) doubles in LDS, NT threads
 template <int NT = HT>
 __device__ __forceinline__ void lds_sort(double* __restrict__ v, int p2) {
     for (int k = 2; k <= p2; k <<= 1) {
@@ -155,10 +148,6 @@ __device__ __forceinline__ void rows_matvec(const double* __restrict__ M, int ld
         s = hw_sum(s);
         if (lane == 0) out[i] = s;
     }
-}
-
-static int set_lds(const void* f, size_t bytes, const char* what) {
-    return bytes <= 64 * 1024 ? 0 : set_lds_limit(f, bytes, what);
 }
 
 }  // namespace hipdrt

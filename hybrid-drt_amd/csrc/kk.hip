@@ -172,12 +172,9 @@ __global__ __launch_bounds__(HT) void kk_kernel(FitState st, KkArgs a, int stage
     extern __shared__ double sm[];
     __shared__ double red[HNW];
     const int b = blockIdx.x, tid = threadIdx.x, nf = a.nf;
-    double* er = sm;
-    double* ei = er + nf;
-    double* srt = ei + nf;
-    int* mask = reinterpret_cast<int*>(srt + a.p2);
-    double* xs = reinterpret_cast<double*>(mask + ((nf + 1) & ~1));
-    double* yh = xs + (stage_a ? st.n : 0);
+    const KkLds L = kk_lds(sm, nf, a.p2, st.n, stage_a);
+    double *er = L.er, *ei = L.ei, *srt = L.srt, *xs = L.xs, *yh = L.yh;
+    int* mask = L.mask;
     if (stage_a) {
         if (st.fit_status[b] < 0) {              // the fit of this spectrum failed: nothing to screen
             for (int k = tid; k < nf; k += HT) {
@@ -205,18 +202,7 @@ __global__ __launch_bounds__(HT) void kk_kernel(FitState st, KkArgs a, int stage
     kk_stats(a, b, er, ei, srt, mask, red);
 }
 
-static int kk_p2(int nf) {
-    int p2 = 2;
-    while (p2 < 2 * nf) p2 <<= 1;
-    return p2;
-}
-
-// LDS: residuals [2 nf], the sort buffer [p2], the mask [nf ints], and for stage A x [n] and the prediction [m = 2 nf]
-size_t kk_lds_bytes(int nf, int n, int stage_a) {
-    size_t d = 2 * (size_t)nf + (size_t)kk_p2(nf) + (size_t)((nf + 1) / 2);
-    if (stage_a) d += (size_t)n + 2 * (size_t)nf;
-    return d * sizeof(double);
-}
+size_t kk_lds_bytes(int nf, int n, int stage_a) { return kk_lds(nullptr, nf, kk_p2(nf), n, stage_a).bytes; }
 
 int launch_kk(hipStream_t s, const FitState* st, KkArgs a, int B) {
     const int stage_a = st != nullptr;

@@ -28,8 +28,6 @@
 namespace hipdrt {
 namespace {
 
-constexpr size_t MP_BYTES_PER_POINT = 5 * sizeof(double) + 3 * sizeof(int);
-
 // x[b][j] /= sum_abs[b] * area (predict_r_p(absolute=True), then x / rp[:, None]: drtmd.py:816-817)
 __global__ __launch_bounds__(256) void normalize_kernel(int rows, int nsup, const double* __restrict__ sum_abs, double area,
                                                         double* __restrict__ x) {
@@ -76,14 +74,9 @@ struct MapProbArgs {
 __global__ __launch_bounds__(PKT) void map_prob_kernel(MapProbArgs a) {
     extern __shared__ double sm[];
     const int b = blockIdx.x, tid = threadIdx.x, n = a.n;
-    double* f = sm;
-    double* fxx = f + n;
-    double* vf = fxx + n;
-    double* vxx = vf + n;
-    double* prom = vxx + n;
-    int* sgn = reinterpret_cast<int*>(prom + n);
-    int* lb = sgn + n;
-    int* rb = lb + n;
+    const MapProbLds L = map_prob_lds(sm, n);
+    double *f = L.f, *fxx = L.fxx, *vf = L.vf, *vxx = L.vxx, *prom = L.prom;
+    int *sgn = L.sgn, *lb = L.lb, *rb = L.rb;
     const size_t row = (size_t)b * n;
     for (int i = tid; i < n; i += PKT) {
         f[i] = a.f[row + i]; fxx[i] = a.fxx[row + i]; vf[i] = a.vf[row + i]; vxx[i] = a.vxx[row + i];
@@ -128,11 +121,12 @@ __global__ __launch_bounds__(256) void spread_sign_kernel(size_t n, const double
 
 // ---- stage 3's launches, shared by hipdrt_map_predict and its test hook hipdrt_debug_map_prob ----
 // what map_prob_kernel stages for rows of n points; HIPDRT_E_UNSUPPORTED with the limit in the message when LDS does not hold it
-int map_prob_lds(int n, size_t* lds) {
-    *lds = MP_BYTES_PER_POINT * (size_t)(n > 0 ? n : 0);
+int map_prob_lds_check(int n, size_t* lds) {
+    *lds = map_prob_lds(nullptr, n).bytes;
     if (*lds > kLdsLimit) {
-        set_error("unsupported: map_predict stages " + std::to_string(MP_BYTES_PER_POINT) + " bytes per evaluation point in LDS: neval <= " +
-                  std::to_string(kLdsLimit / MP_BYTES_PER_POINT) + ", got " + std::to_string(n));
+        const size_t per_point = map_prob_lds(nullptr, 1).bytes;
+        set_error("unsupported: map_predict stages " + std::to_string(per_point) + " bytes per evaluation point in LDS: neval <= " +
+                  std::to_string(kLdsLimit / per_point) + ", got " + std::to_string(n));
         return HIPDRT_E_UNSUPPORTED;
     }
     return HIPDRT_OK;
@@ -145,8 +139,8 @@ int launch_clamp(hipStream_t st, int rows, int n, double* vf, double* vxx, const
 }
 int launch_map_prob(hipStream_t st, int rows, const MapProbArgs& a) {
     size_t lds;
-    TRY(map_prob_lds(a.n, &lds));
-    if (lds > 65536) TRY(set_lds_limit(reinterpret_cast<const void*>(map_prob_kernel), lds, "map_prob_kernel"));
+    TRY(map_prob_lds_check(a.n, &lds));
+    TRY(set_lds(reinterpret_cast<const void*>(map_prob_kernel), lds, "map_prob_kernel"));
     hipLaunchKernelGGL(map_prob_kernel, dim3(rows), dim3(PKT), lds, st, a);
     LAUNCH_OK();
     return HIPDRT_OK;
@@ -194,7 +188,7 @@ extern "C" int hipdrt_map_predict(hipdrt_ctx* ctx, const hipdrt_map_predict_args
     const bool stored = have_var && g->var_stored != 0;
     if (stored && g->ext && (want_var || want_prob)) TRY(check_ext(g->ext, rows, neval));
     size_t lds;
-    if (want_prob) TRY(map_prob_lds(neval, &lds));
+    if (want_prob) TRY(map_prob_lds_check(neval, &lds));
     hipStream_t st; TRY(enter(ctx, &st));
 
     // ---- 1: x ----
@@ -304,7 +298,7 @@ extern "C" int hipdrt_debug_map_prob(hipdrt_ctx* ctx, int rows, int n, const dou
     HIPDRT_REQUIRE(std::isfinite(height) && std::isfinite(prominence), "height and prominence must be finite");
     if (ext) TRY(check_ext(ext, rows, n));
     size_t lds;
-    if (prob) TRY(map_prob_lds(n, &lds));
+    if (prob) TRY(map_prob_lds_check(n, &lds));
     hipStream_t st; TRY(enter(ctx, &st));
     const size_t bn = (size_t)rows * n;
     MapProbArgs a{};

@@ -29,8 +29,7 @@ namespace hipdrt {
 namespace {
 
 // ---- rank filter -----------------------------------------------------------------------------------------------------------
-constexpr int RT_R = 16, RT_C = 64;        // outputs of a tile: 4 per thread
-constexpr int RANK_MAX_WINDOW = 49;
+constexpr int RANK_MAX_WINDOW = 49;        // (the tile, RT_R x RT_C outputs, is lds_layout.hpp's)
 
 struct RankArgs {
     const double* in;
@@ -68,12 +67,14 @@ __device__ double ni_select(double* sel, int n, int rank) {
 
 template <int SR, int SC>
 __global__ __launch_bounds__(256) void rank_kernel(RankArgs a) {
-    extern __shared__ double lds[];
+    extern __shared__ double sm[];
     const int tid = threadIdx.x;
     const int sr = SR ? SR : a.sr, sc = SC ? SC : a.sc, n = sr * sc;
     const int r0 = blockIdx.x * RT_R, c0 = blockIdx.y * RT_C;
     const int WR = RT_R + sr - 1, WC = RT_C + sc - 1, WN = WR * WC;
-    double* sel = lds + WN + tid;
+    const RankLds L = rank_lds(sm, sr, sc);
+    double* lds = L.win;
+    double* sel = L.sel + tid;
     const double fill = a.fill ? *a.fill : 0.0;
     for (int e = tid; e < WN; e += 256) {
         const int gr = reflect_rank(r0 - sr / 2 + e / WC, a.R), gc = reflect_rank(c0 - sc / 2 + e % WC, a.C);
@@ -141,14 +142,12 @@ __global__ __launch_bounds__(256) void rank_kernel(RankArgs a) {
     }
 }
 
-size_t rank_lds_bytes(int sr, int sc) {
-    return ((size_t)(RT_R + sr - 1) * (RT_C + sc - 1) + (size_t)256 * sr * sc) * sizeof(double);
-}
+size_t rank_lds_bytes(int sr, int sc) { return rank_lds(nullptr, sr, sc).bytes; }
 
 template <int SR, int SC>
 int launch_rank(hipStream_t st, const RankArgs& a) {
     const size_t bytes = rank_lds_bytes(a.sr, a.sc);
-    if (bytes > 65536) TRY(set_lds_limit((const void*)rank_kernel<SR, SC>, bytes, "rank_kernel"));
+    TRY(set_lds((const void*)rank_kernel<SR, SC>, bytes, "rank_kernel"));
     const dim3 grid((a.R + RT_R - 1) / RT_R, (a.C + RT_C - 1) / RT_C);
     hipLaunchKernelGGL((rank_kernel<SR, SC>), grid, dim3(256), bytes, st, a);
     LAUNCH_OK();

@@ -70,9 +70,8 @@ __global__ __launch_bounds__(256) void lookup_kernel(double eps, int ngrid, int 
                                                      const double* __restrict__ wt_im, double* __restrict__ z_re,
                                                      double* __restrict__ z_im) {
     extern __shared__ double sm[];
-    double* ys = sm;
-    double* phis = sm + ny;
-    double* eys = sm + 2 * ny;
+    const YTablesLds L = y_tables_lds(sm, ny);
+    double *ys = L.ys, *phis = L.phis, *eys = L.eys;
     fill_y_tables(ys, phis, eys, ny, eps);
     __syncthreads();
     const int lane = threadIdx.x & 63;
@@ -177,19 +176,16 @@ __global__ __launch_bounds__(1024) void impedance_interp_kernel(
     const double* __restrict__ lut6, int rows_per_block, int tpr, double* __restrict__ a_re,
     double* __restrict__ a_im) {
     extern __shared__ double sm[];
-    // LDS: x_re[ng] x_im[ng] | fs_re[ng] fs_im[ng] (16-byte aligned: the dynamic segment starts aligned and 2 ng doubles
-    // precede the pairs only when ng is even; odd ng gets one pad double)
-    const int npad = ng + (ng & 1);
-    double* sx = sm;
-    double2* sfs = reinterpret_cast<double2*>(sm + 2 * npad);
-    const LutFS Tr = stage_lut_fs(sx, sfs, lut6, lut6 + ng, lut6 + 2 * ng, ng);
-    const LutFS Ti = stage_lut_fs(sx + npad, sfs + ng, lut6 + 3 * ng, lut6 + 4 * ng, lut6 + 5 * ng, ng);
+    static_assert(sizeof(LdsPair) == sizeof(double2) && alignof(LdsPair) == alignof(double2), "the layout's pair is a double2");
+    const ImpedanceInterpLds L = impedance_interp_lds(sm, ng, rows_per_block);
+    const LutFS Tr = stage_lut_fs(L.x_re, reinterpret_cast<double2*>(L.fs_re), lut6, lut6 + ng, lut6 + 2 * ng, ng);
+    const LutFS Ti = stage_lut_fs(L.x_im, reinterpret_cast<double2*>(L.fs_im), lut6 + 3 * ng, lut6 + 4 * ng, lut6 + 5 * ng, ng);
     const int b = blockIdx.y;
     const double* lwb = lw + (freq_batched ? (size_t)b * nf : 0);
     const int row0 = blockIdx.x * rows_per_block;
     const int rend = min(row0 + rows_per_block, nf);
     // ln(omega) of this workgroup's rows: an LDS read per row instead of a global load in front of every dependent chain
-    double* slw = sm + 6 * npad;
+    double* slw = L.slw;
     for (int i = threadIdx.x; i < rend - row0; i += blockDim.x) slw[i] = lwb[row0 + i];
     // Z' and Z'' tabulated on the same abscissae (generate_impedance_lookup gives both one grid): one bin search serves both
     int mine = 1;
@@ -255,7 +251,8 @@ __global__ __launch_bounds__(256) void toeplitz_cr_trapz_kernel(const double* __
                                                                 const double* __restrict__ tau, int ntau, double eps,
                                                                 int ny, double* __restrict__ cr) {
     extern __shared__ double sm[];
-    double* ys = sm; double* phis = sm + ny; double* eys = sm + 2 * ny;
+    const YTablesLds L = y_tables_lds(sm, ny);
+    double *ys = L.ys, *phis = L.phis, *eys = L.eys;
     fill_y_tables(ys, phis, eys, ny, eps);
     __syncthreads();
     const int lane = threadIdx.x & 63;
@@ -291,7 +288,8 @@ __global__ __launch_bounds__(256) void impedance_trapz_kernel(int freq_batched, 
                                                               const double* __restrict__ tau, int ntau, double eps, int ny,
                                                               double* __restrict__ a_re, double* __restrict__ a_im) {
     extern __shared__ double sm[];
-    double* ys = sm; double* phis = sm + ny; double* eys = sm + 2 * ny;
+    const YTablesLds L = y_tables_lds(sm, ny);
+    double *ys = L.ys, *phis = L.phis, *eys = L.eys;
     fill_y_tables(ys, phis, eys, ny, eps);
     __syncthreads();
     const int lane = threadIdx.x & 63;
@@ -366,7 +364,8 @@ __device__ __forceinline__ double trapz_response(const double* ys, const double*
 __global__ __launch_bounds__(256) void response_lookup_kernel(double eps, int ngrid, int ny,
                                                               const double* __restrict__ td, double* __restrict__ v) {
     extern __shared__ double sm[];
-    double* ys = sm; double* phis = sm + ny; double* eys = sm + 2 * ny;
+    const YTablesLds L = y_tables_lds(sm, ny);
+    double *ys = L.ys, *phis = L.phis, *eys = L.eys;
     fill_y_tables(ys, phis, eys, ny, eps);
     __syncthreads();
     const int lane = threadIdx.x & 63;
@@ -415,7 +414,8 @@ __global__ __launch_bounds__(256) void response_trapz_kernel(const double* __res
                                                              double eps, int ny, double* __restrict__ a,
                                                              double* __restrict__ layered) {
     extern __shared__ double sm[];
-    double* ys = sm; double* phis = sm + ny; double* eys = sm + 2 * ny;
+    const YTablesLds L = y_tables_lds(sm, ny);
+    double *ys = L.ys, *phis = L.phis, *eys = L.eys;
     fill_y_tables(ys, phis, eys, ny, eps);
     __syncthreads();
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -465,7 +465,8 @@ __global__ __launch_bounds__(256) void response_expdecay_kernel(const double* __
                                                                 double eps, int ny, double* __restrict__ a,
                                                                 double* __restrict__ layered) {
     extern __shared__ double sm[];
-    double* ys = sm; double* phis = sm + ny; double* eys = sm + 2 * ny;
+    const YTablesLds L = y_tables_lds(sm, ny);
+    double *ys = L.ys, *phis = L.phis, *eys = L.eys;
     fill_y_tables(ys, phis, eys, ny, eps);
     __syncthreads();
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -542,7 +543,7 @@ __global__ __launch_bounds__(256) void eis_vmm_kernel(const double* __restrict__
 void launch_lookup(hipStream_t st, double eps, int ngrid, int ny, const double* wt_re, const double* wt_im,
                    double* z_re, double* z_im) {
     const int blocks = (2 * ngrid + 3) / 4;
-    hipLaunchKernelGGL(lookup_kernel, dim3(blocks), dim3(256), 3 * ny * sizeof(double), st, eps, ngrid, ny, wt_re,
+    hipLaunchKernelGGL(lookup_kernel, dim3(blocks), dim3(256), y_tables_lds(nullptr, ny).bytes, st, eps, ngrid, ny, wt_re,
                        wt_im, z_re, z_im);
 }
 
@@ -559,7 +560,7 @@ void launch_impedance_matrix(hipStream_t st, int B, int freq_batched, const doub
             hipLaunchKernelGGL(toeplitz_cr_interp_kernel, dim3((tot + 255) / 256), dim3(256), 0, st, freq, nf, tau, ntau,
                                ngrid, lut6, cr_scratch);
         else
-            hipLaunchKernelGGL(toeplitz_cr_trapz_kernel, dim3((tot + 3) / 4), dim3(256), 3 * ny * sizeof(double), st,
+            hipLaunchKernelGGL(toeplitz_cr_trapz_kernel, dim3((tot + 3) / 4), dim3(256), y_tables_lds(nullptr, ny).bytes, st,
                                freq, nf, tau, ntau, eps, ny, cr_scratch);
         const int zb = B < 64 ? B : 64;
         hipLaunchKernelGGL(toeplitz_fill_kernel, dim3((ntau + 255) / 256, nf, zb), dim3(256), 0, st, B, nf, ntau,
@@ -579,10 +580,10 @@ void launch_impedance_matrix(hipStream_t st, int B, int freq_batched, const doub
         int rpb = 256;
         while (rpb > 4 && (long long)B * ((nf + rpb - 1) / rpb) < 1024) rpb /= 2;   // enough workgroups for 256 CUs
         const int bx = (nf + rpb - 1) / rpb;
-        hipLaunchKernelGGL(impedance_interp_kernel, dim3(bx, B), dim3(1024), (6 * (size_t)(ngrid + (ngrid & 1)) + rpb) * sizeof(double), st,
+        hipLaunchKernelGGL(impedance_interp_kernel, dim3(bx, B), dim3(1024), impedance_interp_lds(nullptr, ngrid, rpb).bytes, st,
                            freq_batched, lw, nf, lt, ntau, ngrid, lut6, rpb, tpr, a_re, a_im);
     } else {
-        hipLaunchKernelGGL(impedance_trapz_kernel, dim3((ntau + 15) / 16, nf, B), dim3(256), 3 * ny * sizeof(double),
+        hipLaunchKernelGGL(impedance_trapz_kernel, dim3((ntau + 15) / 16, nf, B), dim3(256), y_tables_lds(nullptr, ny).bytes,
                            st, freq_batched, freq, nf, tau, ntau, eps, ny, a_re, a_im);
     }
 }
@@ -708,7 +709,7 @@ void launch_chrono_vmm(hipStream_t st, const double* tt, int nt, const int* seg,
 }
 
 void launch_response_lookup(hipStream_t st, double eps, int ngrid, int ny, const double* td, double* v) {
-    hipLaunchKernelGGL(response_lookup_kernel, dim3((ngrid + 3) / 4), dim3(256), 3 * ny * sizeof(double), st, eps, ngrid, ny,
+    hipLaunchKernelGGL(response_lookup_kernel, dim3((ngrid + 3) / 4), dim3(256), y_tables_lds(nullptr, ny).bytes, st, eps, ngrid, ny,
                        td, v);
 }
 
@@ -722,7 +723,7 @@ void launch_response_matrix(hipStream_t st, const double* times, int nt, const d
                            3 * (size_t)ngrid * sizeof(double), st, times, nt, tau, ntau, step_times, step_sizes, nsteps,
                            ngrid, lut3, rpb, a, layered);
     } else {
-        hipLaunchKernelGGL(response_trapz_kernel, dim3((ntau + 15) / 16, nt), dim3(256), 3 * ny * sizeof(double), st,
+        hipLaunchKernelGGL(response_trapz_kernel, dim3((ntau + 15) / 16, nt), dim3(256), y_tables_lds(nullptr, ny).bytes, st,
                            times, nt, tau, ntau, step_times, step_sizes, nsteps, eps, ny, a, layered);
     }
 }
@@ -734,7 +735,7 @@ void launch_response_variant(hipStream_t st, const double* times, int nt, const 
         hipLaunchKernelGGL(response_pot_kernel, dim3((ntau + 255) / 256, nt), dim3(256), 0, st, times, nt, tau, ntau,
                            step_times, step_sizes, nsteps, a, layered);
     else
-        hipLaunchKernelGGL(response_expdecay_kernel, dim3((ntau + 15) / 16, nt), dim3(256), 3 * ny * sizeof(double), st,
+        hipLaunchKernelGGL(response_expdecay_kernel, dim3((ntau + 15) / 16, nt), dim3(256), y_tables_lds(nullptr, ny).bytes, st,
                            times, nt, tau, ntau, step_times, step_sizes, tau_rise, nsteps, eps, ny, a, layered);
 }
 

@@ -74,14 +74,9 @@ __global__ __launch_bounds__(PKT) void peak_trough_prob_kernel(PeakProbArgs a) {
     __shared__ int rpk[PP_MAX_RANGES];
     const int b = blockIdx.x, tid = threadIdx.x, n = a.neval, p2 = a.p2;
     const bool bayes = a.o.bayes_cov != 0, have_prob = a.prob_in != nullptr;
-    double* m0 = sm;
-    double* m1 = m0 + n;
-    double* m2 = m1 + n;
-    double* s0 = m2 + n;
-    double* w = s0 + 3 * (size_t)n;
-    int* sgn = reinterpret_cast<int*>(w + p2);
-    int* lb = sgn + n;
-    int* rb = lb + n;
+    const PeakProbLds L = peak_prob_lds(sm, n, p2);
+    double *m0 = L.m0, *m1 = L.m1, *m2 = L.m2, *s0 = L.s0, *w = L.w;
+    int *sgn = L.sgn, *lb = L.lb, *rb = L.rb;
     const size_t row = (size_t)b * n, bn = (size_t)gridDim.x * n;
 
     const bool dead = (a.fit_status && a.fit_status[b] < 0) || (bayes && a.var_status && a.var_status[b] != 0);
@@ -240,10 +235,7 @@ __global__ __launch_bounds__(PKT) void peak_trough_prob_kernel(PeakProbArgs a) {
     if (tid == 0 && a.count) a.count[b] = (int)kept;
 }
 
-size_t peak_prob_lds_bytes(int neval) {
-    const size_t n = (size_t)neval;
-    return (6 * n + (size_t)next_pow2(neval)) * sizeof(double) + 3 * n * sizeof(int);
-}
+size_t peak_prob_lds_bytes(int neval) { return peak_prob_lds(nullptr, neval, next_pow2(neval)).bytes; }
 
 int peak_prob_check(const hipdrt_peak_prob_opts& o, int neval, int nranges, const int* range_lo, const int* range_hi) {
     HIPDRT_REQUIRE(neval >= 1, "neval >= 1");

@@ -73,24 +73,9 @@ __device__ __forceinline__ ValIdx wave_arg_range(int s, int e, G g) {
     return wave_arg<MAX>(a);
 }
 
-int peak_resolve_ld(int nb) {
-    int ld = (nb + 3) & ~3;
-    while (ld % 32 != 4) ld += 4;
-    return ld;
-}
-static __host__ __device__ inline int pr_ldg(int nout) {
-    int l = (nout + 15) & ~15;
-    if (l % 32 == 0) l += 16;      // rows 32 banks apart: the four accumulator rows a wavefront writes at once alternate halves
-    return l;
-}
-
-// dynamic LDS: doubles f[nfind], fxx[nfind], xw[Pt * 16][ld], gam[16][ldg] (nout > 0), eps_l, eps_r, rco, rpk [mp each];
-// ints pk[mp], tr[mp], scan[RT]
+static_assert(RT == PR_THREADS, "the layout's scan row has one int per thread");
 size_t peak_resolve_lds_bytes(int nfind, int nb, int nout, int max_peaks) {
-    const size_t pt = (size_t)(max_peaks + 15) / 16;
-    const size_t d = 2 * (size_t)nfind + pt * 16 * (size_t)peak_resolve_ld(nb) + (nout > 0 ? 16 * (size_t)pr_ldg(nout) : 0) +
-                     4 * (size_t)max_peaks;
-    return d * sizeof(double) + (2 * (size_t)max_peaks + RT) * sizeof(int);
+    return peak_resolve_lds(nullptr, nfind, peak_resolve_ld(nb), pr_ldg(nout), nout, max_peaks).bytes;
 }
 
 // grid = B
@@ -100,18 +85,9 @@ __global__ __launch_bounds__(RT) void peak_resolve_kernel(PeakResolveArgs a) {
     __shared__ int s_cnt;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int n = a.nfind, nb = a.nb, nout = a.nout, mp = a.max_peaks, ld = a.ld, ldg = pr_ldg(nout);
-    const int ptiles = (mp + 15) / 16;
-    double* f = sm;
-    double* fxx = f + n;
-    double* xw = fxx + n;
-    double* gam = xw + (size_t)ptiles * 16 * ld;
-    double* epsl = gam + (nout > 0 ? 16 * ldg : 0);
-    double* epsr = epsl + mp;
-    double* rco = epsr + mp;
-    double* rpk = rco + mp;
-    int* pk = reinterpret_cast<int*>(rpk + mp);
-    int* tr = pk + mp;
-    int* scan = tr + mp;
+    const PeakResolveLds L = peak_resolve_lds(sm, n, ld, ldg, nout, mp);
+    double *f = L.f, *fxx = L.fxx, *xw = L.xw, *gam = L.gam, *epsl = L.epsl, *epsr = L.epsr, *rco = L.rco, *rpk = L.rpk;
+    int *pk = L.pk, *tr = L.tr, *scan = L.scan;
 
     // padded rows of one spectrum: NaN floats and -1 ints from peak slot `from` on
     auto pad_rows = [&](int from) {

@@ -24,31 +24,14 @@
 
 namespace hipdrt {
 
-// LDS rows of one spectrum: doubles fxx, prom, [f], [vxx, prob], [vf], [srt p2]; ints sgn, lb, rb
-struct PeakLds { int f, var, varf, sort; };
-static __host__ __device__ inline PeakLds peak_lds(int method, int need_f, int num_peaks) {
-    PeakLds l;
-    l.f = need_f; l.var = method >= 1; l.varf = method == 2; l.sort = method == 1 && num_peaks > 0;
-    return l;
-}
-
 // grid = B
 __global__ __launch_bounds__(PKT) void peaks_kernel(PeakArgs a) {
     extern __shared__ double sm[];
     __shared__ double red[PKT / 64];
     const int b = blockIdx.x, tid = threadIdx.x, n = a.neval, method = a.o.method;
-    const PeakLds l = peak_lds(method, a.f != nullptr, a.o.num_peaks);
-    double* fxx = sm;
-    double* prom = fxx + n;
-    double* p_ = prom + n;
-    double* f = p_;      p_ += l.f ? n : 0;
-    double* vxx = p_;    p_ += l.var ? n : 0;
-    double* prob = p_;   p_ += l.var ? n : 0;
-    double* vf = p_;     p_ += l.varf ? n : 0;
-    double* srt = p_;    p_ += l.sort ? a.p2 : 0;
-    int* sgn = reinterpret_cast<int*>(p_);
-    int* lb = sgn + n;
-    int* rb = lb + n;
+    const PeaksLds l = peaks_lds(sm, n, a.p2, method, a.f != nullptr, a.o.num_peaks);
+    double *fxx = l.fxx, *prom = l.prom, *f = l.frow, *vxx = l.vxx, *prob = l.prob, *vf = l.vf, *srt = l.srt;
+    int *sgn = l.sgn, *lb = l.lb, *rb = l.rb;
     const size_t row = (size_t)b * n;
 
     const bool dead = (a.fit_status && a.fit_status[b] < 0) || (l.var && a.var_status && a.var_status[b] != 0);
@@ -185,10 +168,7 @@ __global__ __launch_bounds__(PKT) void peaks_kernel(PeakArgs a) {
 }
 
 size_t peaks_lds_bytes(int neval, int method, int need_f, int num_peaks) {
-    const PeakLds l = peak_lds(method, need_f, num_peaks);
-    const size_t n = (size_t)neval;
-    size_t d = 2 * n + (l.f ? n : 0) + (l.var ? 2 * n : 0) + (l.varf ? n : 0) + (l.sort ? (size_t)next_pow2(neval) : 0);
-    return d * sizeof(double) + 3 * n * sizeof(int);
+    return peaks_lds(nullptr, neval, next_pow2(neval), method, need_f, num_peaks).bytes;
 }
 
 int peak_check_opts(const hipdrt_peak_opts& o, int neval) {

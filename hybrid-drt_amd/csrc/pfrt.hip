@@ -70,21 +70,15 @@ int launch_pfrt_step(hipStream_t s, const PfrtStepArgs& a, int B) {
     return HIPDRT_OK;
 }
 
-// LDS of pfrt_combine_kernel: the accumulator and ln(tau_pfrt) [np], ln(tau_out), the smoothed row and the integrated row [nout],
-// the steps' posterior weights [S]
-size_t pfrt_combine_lds_bytes(int S, int np, int nout) { return ((size_t)2 * np + (size_t)3 * nout + (size_t)S) * sizeof(double); }
+size_t pfrt_combine_lds_bytes(int S, int np, int nout) { return pfrt_combine_lds(nullptr, S, np, nout).bytes; }
 
 // grid = B
 __global__ __launch_bounds__(PKT) void pfrt_combine_kernel(PfrtCombineArgs a) {
     extern __shared__ double sm[];
     __shared__ double red[PKT];
     const int b = blockIdx.x, B = gridDim.x, tid = threadIdx.x, S = a.S, np = a.np, nout = a.nout;
-    double* acc = sm;
-    double* ltp = acc + np;
-    double* lto = ltp + np;
-    double* v = lto + nout;
-    double* res = v + nout;
-    double* post = res + nout;
+    const PfrtCombineLds L = pfrt_combine_lds(sm, S, np, nout);
+    double *acc = L.acc, *ltp = L.ltp, *lto = L.lto, *v = L.v, *res = L.res, *post = L.post;
 
     if ((a.fit_status && a.fit_status[b] < 0) || (a.bad && a.bad[b] != 0)) {
         for (int k = tid; k < nout; k += PKT) if (a.pfrt) a.pfrt[(size_t)b * nout + k] = NAN;
