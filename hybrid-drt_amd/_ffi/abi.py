@@ -326,6 +326,7 @@ SIGNATURES = {
     "hipdrt_debug_pack_p": [_vp, C.c_int, C.c_int, _dp, C.c_int, _dp],
     "hipdrt_debug_hyper_step": [_vp, C.POINTER(DebugHyperArgs)],
     "hipdrt_debug_hyper_form": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.POINTER(C.c_longlong)],
+    "hipdrt_debug_impedance_interp_form": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, C.POINTER(C.c_longlong)],
     "hipdrt_debug_kk_stats": [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(KkOpts), _dp, _ip, _dp, _ip, _ip],
     "hipdrt_default_kk_opts": [C.POINTER(KkOpts)],
     "hipdrt_plan_kk_screen": [_vp, C.POINTER(KkOpts), C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _ip, _ip],

@@ -61,10 +61,14 @@ class Context(DebugHooks):
                                                  _p(z_re), _p(z_im)))
         return z_re, z_im
 
-    def impedance_matrix(self, freq, tau, epsilon, mode=MODE_INTERP, toeplitz=False, lookups=None, ny=1000):
+    def impedance_matrix(self, freq, tau, epsilon, mode=MODE_INTERP, toeplitz=False, lookups=None, ny=1000, copies=None):
+        """freq [nf] -> (nf, ntau) pair; freq [B][nf] (per-spectrum grids) -> (B, nf, ntau); copies = B with a shared freq [nf]:
+        the B identical matrices a batch on one grid gets, (B, nf, ntau)"""
         freq, tau = _f64(freq), _f64(tau)
         batched = freq.ndim == 2
-        B = freq.shape[0] if batched else 1
+        if copies is not None and batched:
+            raise ValueError("copies goes with one shared frequency grid")
+        B = freq.shape[0] if batched else (1 if copies is None else int(copies))
         nf = freq.shape[-1]
         if lookups is not None:
             (lre, zre), (lim, zim) = lookups
@@ -78,7 +82,7 @@ class Context(DebugHooks):
         _check(self._lib.hipdrt_impedance_matrix(self._h, B, int(batched), _p(freq), nf, _p(tau), tau.size, int(mode),
                                                  int(bool(toeplitz)), float(epsilon), ng, _p(lre), _p(zre), _p(lim),
                                                  _p(zim), int(ny), _p(a_re), _p(a_im)))
-        if not batched:
+        if not batched and copies is None:
             return a_re[0], a_im[0]
         return a_re, a_im
 

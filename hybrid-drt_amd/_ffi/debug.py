@@ -113,6 +113,14 @@ class DebugHooks:
                                                  C.byref(form), C.byref(lds)))
         return form.value, lds.value
 
+    def debug_impedance_interp_form(self, B, nf, ntau, ngrid):
+        """tests: (tpr, rpb, lds_bytes) of the general interp build's launch -- threads per row, rows per workgroup, dynamic LDS;
+        raises for an ngrid the entry points refuse (hipdrt_debug_impedance_interp_form, include/hipdrt_debug.h)"""
+        tpr, rpb, lds = C.c_int(-1), C.c_int(-1), C.c_longlong(0)
+        _check(self._lib.hipdrt_debug_impedance_interp_form(self._h, int(B), int(nf), int(ntau), int(ngrid), C.byref(tpr),
+                                                            C.byref(rpb), C.byref(lds)))
+        return tpr.value, rpb.value, lds.value
+
     def debug_hyper_step(self, rm, vmm, mk, x, x_in, s, rho, xmx, rv, est_w, w, var_floor, coef_scale, opts: FitOpts, ns=0, n=None,
                          toeplitz=False, toep_reach=-1, qp_status=None, active=None, fit_status=None, outer_iters=None, n_active=0,
                          outlier_t=None, it=0, continue_mode=0, min_iter=1, basis_area=1.0, desc: PreparedDesc | None = None,

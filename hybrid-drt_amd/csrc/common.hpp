@@ -76,7 +76,8 @@ inline int set_lds_limit(const void* f, size_t bytes, const char* what) {
     if (e != hipSuccess) { set_error(std::string("hipFuncSetAttribute(") + what + "): " + hipGetErrorString(e)); return HIPDRT_E_HIP; }
     return HIPDRT_OK;
 }
-// the tail of every launcher with dynamic LDS: the attribute is raised only above the 64 KiB a kernel may have without it
+// the tail of a launcher with dynamic LDS: the attribute is raised only above the 64 KiB a kernel may have without it (the launchers
+// of matrices.hip do without it: their kernels launch at up to kLdsLimit all the same, tests/test_gpu_matrices_edges.py)
 inline int set_lds(const void* f, size_t bytes, const char* what) {
     return bytes <= 64 * 1024 ? 0 : set_lds_limit(f, bytes, what);
 }
@@ -88,6 +89,21 @@ inline int lds_check(size_t bytes, const char* who, const char* dims) {
     set_error(std::string("invalid argument: ") + who + ": " + std::to_string(bytes) + " bytes of LDS needed (" + dims + "), " +
               std::to_string(kLdsLimit) + " available");
     return HIPDRT_E_INVALID;
+}
+
+// What the matrix builders (matrices.hip) accept, each from the layout its kernel stages in LDS: trapezoid points (the interface's
+// 6000, which the y tables must hold), knots of the impedance lookups (at the fewest rows a workgroup of the general build takes --
+// launch_impedance_matrix gives up rows for a long table, so that an accepted table builds at every batch size) and knots of the
+// response lookup.  kGridDimMax: what a launch may put on gridDim.y or .z -- the kernels stride over rows, a longer batch is refused.
+static constexpr int kNyMax = 6000;
+static constexpr int kInterpMinRows = 4, kInterpMaxRows = 256;
+static constexpr int kGridDimMax = 65535;
+inline bool ny_ok(int ny) { return ny >= 2 && ny <= kNyMax && y_tables_lds(nullptr, ny).bytes <= kLdsLimit; }
+inline bool impedance_ngrid_ok(int ngrid) {
+    return ngrid >= 2 && ngrid <= (1 << 20) && impedance_interp_lds(nullptr, ngrid, kInterpMinRows).bytes <= kLdsLimit;
+}
+inline bool response_ngrid_ok(int ngrid) {
+    return ngrid >= 2 && ngrid <= (1 << 20) && response_interp_lds(nullptr, ngrid).bytes <= kLdsLimit;
 }
 
 // area of one tau basis function: sqrt(pi) / epsilon
@@ -139,6 +155,9 @@ void launch_lookup_slopes(hipStream_t st, int ngrid, const double* xp, const dou
 void launch_impedance_matrix(hipStream_t st, int B, int freq_batched, const double* freq, int nf, const double* tau,
                              int ntau, int mode, int toeplitz, double eps, int ngrid, const double* lut6, int ny,
                              double* a_re, double* a_im, double* cr_scratch);
+// the general interp build's launch form: threads per row, rows per workgroup and dynamic LDS (launch_impedance_matrix and
+// hipdrt_debug_impedance_interp_form both ask here)
+void impedance_interp_form(int B, int nf, int ntau, int ngrid, int* tpr, int* rpb, size_t* lds_bytes);
 void launch_phasor_z(hipStream_t st, const double* freq, int nf, const double* nu, int nnu, double eps, double* zre,
                      double* zim);
 void launch_phasor_v(hipStream_t st, const double* times, int nt, const double* nu, int nnu, double eps,

@@ -144,6 +144,17 @@ int hipdrt_debug_hyper_form(hipdrt_ctx* ctx, int n, int m, int ns, int toeplitz,
     return HIPDRT_OK;
 } HIPDRT_CATCH
 
+int hipdrt_debug_impedance_interp_form(hipdrt_ctx* ctx, int B, int nf, int ntau, int ngrid, int* tpr, int* rpb,
+                                       long long* lds_bytes) try {
+    HIPDRT_REQUIRE(ctx && tpr && rpb && lds_bytes, "NULL pointer");
+    HIPDRT_REQUIRE(B >= 1 && B <= kGridDimMax && nf >= 1 && ntau >= 1, "1 <= B <= 65535, nf, ntau >= 1");
+    HIPDRT_REQUIRE(impedance_ngrid_ok(ngrid), "interp needs lookups with ngrid >= 2 that one workgroup's LDS holds (2 <= ngrid <= 3406)");
+    size_t lds = 0;
+    impedance_interp_form(B, nf, ntau, ngrid, tpr, rpb, &lds);
+    *lds_bytes = (long long)lds;
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
 int hipdrt_debug_hyper_step(hipdrt_ctx* ctx, const hipdrt_debug_hyper_args* a) try {
     HIPDRT_REQUIRE(ctx && a, "NULL pointer");
     const int B = a->B, m = a->m, n = a->n, ns = a->ns, nd = n - ns;

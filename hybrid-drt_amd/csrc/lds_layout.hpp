@@ -309,5 +309,16 @@ HIPDRT_HD inline ImpedanceInterpLds impedance_interp_lds(void* sm, int ng, int r
     l.bytes = c.off;
     return l;
 }
+// response_interp_kernel: the response lookup {log_td, v, slope} [ng each], an image of lut3
+struct ResponseInterpLds { double *xp, *fp, *sl; size_t bytes; };
+HIPDRT_HD inline ResponseInterpLds response_interp_lds(void* sm, int ng) {
+    LdsCarver c = lds_carver(sm);
+    ResponseInterpLds l;
+    l.xp = c.take<double>((size_t)ng);
+    l.fp = c.take<double>((size_t)ng);
+    l.sl = c.take<double>((size_t)ng);
+    l.bytes = c.off;
+    return l;
+}
 
 }  // namespace hipdrt

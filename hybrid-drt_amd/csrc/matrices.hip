@@ -270,16 +270,17 @@ __global__ __launch_bounds__(256) void toeplitz_cr_trapz_kernel(const double* __
 __global__ void toeplitz_fill_kernel(int B, int nf, int ntau, const double* __restrict__ cr, double* __restrict__ a_re,
                                      double* __restrict__ a_im) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    const int i = blockIdx.y;
     if (j >= ntau) return;
     const double* c_re = cr; const double* r_re = cr + nf;
     const double* c_im = cr + nf + ntau; const double* r_im = c_im + nf;
-    const double vr = (i >= j) ? c_re[i - j] : r_re[j - i];
-    const double vi = (i >= j) ? c_im[i - j] : r_im[j - i];
-    for (int b = blockIdx.z; b < B; b += gridDim.z) {
-        const size_t o = ((size_t)b * nf + i) * ntau + j;
-        a_re[o] = vr;
-        a_im[o] = vi;
+    for (int i = blockIdx.y; i < nf; i += gridDim.y) {
+        const double vr = (i >= j) ? c_re[i - j] : r_re[j - i];
+        const double vi = (i >= j) ? c_im[i - j] : r_im[j - i];
+        for (int b = blockIdx.z; b < B; b += gridDim.z) {
+            const size_t o = ((size_t)b * nf + i) * ntau + j;
+            a_re[o] = vr;
+            a_im[o] = vi;
+        }
     }
 }
 
@@ -294,19 +295,21 @@ __global__ __launch_bounds__(256) void impedance_trapz_kernel(int freq_batched, 
     __syncthreads();
     const int lane = threadIdx.x & 63;
     const int wv = threadIdx.x >> 6;
-    const int r = blockIdx.y, b = blockIdx.z;
+    const int b = blockIdx.z;
     const double* fr = freq + (freq_batched ? (size_t)b * nf : 0);
-    const double w = fr[r] * 2.0 * 3.141592653589793;
-    // each block covers 16 consecutive tau columns
-    for (int k = 0; k < 4; ++k) {
-        const int c = blockIdx.x * 16 + k * 4 + wv;
-        if (c >= ntau) continue;
-        double zr, zi;
-        trapz_pair(ys, phis, eys, ny, w, tau[c], lane, zr, zi);
-        if (lane == 0) {
-            const size_t o = ((size_t)b * nf + r) * ntau + c;
-            a_re[o] = zr;
-            a_im[o] = zi;
+    for (int r = blockIdx.y; r < nf; r += gridDim.y) {
+        const double w = fr[r] * 2.0 * 3.141592653589793;
+        // each block covers 16 consecutive tau columns
+        for (int k = 0; k < 4; ++k) {
+            const int c = blockIdx.x * 16 + k * 4 + wv;
+            if (c >= ntau) continue;
+            double zr, zi;
+            trapz_pair(ys, phis, eys, ny, w, tau[c], lane, zr, zi);
+            if (lane == 0) {
+                const size_t o = ((size_t)b * nf + r) * ntau + c;
+                a_re[o] = zr;
+                a_im[o] = zi;
+            }
         }
     }
 }
@@ -384,9 +387,10 @@ __global__ __launch_bounds__(256) void response_interp_kernel(const double* __re
                                                               int ngrid, const double* __restrict__ lut3, int rpb,
                                                               double* __restrict__ a, double* __restrict__ layered) {
     extern __shared__ double sm[];
-    for (int i = threadIdx.x; i < 3 * ngrid; i += blockDim.x) sm[i] = lut3[i];
+    const ResponseInterpLds L = response_interp_lds(sm, ngrid);
+    for (int i = threadIdx.x; i < 3 * ngrid; i += blockDim.x) L.xp[i] = lut3[i];      // the three tables lie back to back
     __syncthreads();
-    const double* xp = sm; const double* fp = sm + ngrid; const double* sl = sm + 2 * ngrid;
+    const double* xp = L.xp; const double* fp = L.fp; const double* sl = L.sl;
     const double x0 = xp[0], inv_dx = (double)(ngrid - 1) / (xp[ngrid - 1] - xp[0]);
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= ntau) return;
@@ -419,20 +423,21 @@ __global__ __launch_bounds__(256) void response_trapz_kernel(const double* __res
     fill_y_tables(ys, phis, eys, ny, eps);
     __syncthreads();
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int r = blockIdx.y;
-    const double t = times[r];
-    for (int q = 0; q < 4; ++q) {
-        const int c = blockIdx.x * 16 + q * 4 + wv;
-        if (c >= ntau) continue;
-        double acc = 0.0;
-        for (int k = 0; k < nsteps; ++k) {
-            const double st = step_times[k];
-            double val = 0.0;
-            if (t > st) val = trapz_response(ys, phis, eys, ny, tau[c], t - st, lane) * step_sizes[k];
-            if (layered && lane == 0) layered[((size_t)k * nt + r) * ntau + c] = val;
-            acc += val;
+    for (int r = blockIdx.y; r < nt; r += gridDim.y) {      // a long record has more rows than a grid has y
+        const double t = times[r];
+        for (int q = 0; q < 4; ++q) {
+            const int c = blockIdx.x * 16 + q * 4 + wv;
+            if (c >= ntau) continue;
+            double acc = 0.0;
+            for (int k = 0; k < nsteps; ++k) {
+                const double st = step_times[k];
+                double val = 0.0;
+                if (t > st) val = trapz_response(ys, phis, eys, ny, tau[c], t - st, lane) * step_sizes[k];
+                if (layered && lane == 0) layered[((size_t)k * nt + r) * ntau + c] = val;
+                acc += val;
+            }
+            if (lane == 0) a[(size_t)r * ntau + c] = acc;
         }
-        if (lane == 0) a[(size_t)r * ntau + c] = acc;
     }
 }
 
@@ -470,20 +475,21 @@ __global__ __launch_bounds__(256) void response_expdecay_kernel(const double* __
     fill_y_tables(ys, phis, eys, ny, eps);
     __syncthreads();
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int r = blockIdx.y;
-    const double t = times[r];
-    for (int q = 0; q < 4; ++q) {
-        const int c = blockIdx.x * 16 + q * 4 + wv;
-        if (c >= ntau) continue;
-        double acc = 0.0;
-        for (int k = 0; k < nsteps; ++k) {
-            const double st = step_times[k];
-            double val = 0.0;
-            if (t > st) val = trapz_response_expdecay(ys, phis, eys, ny, tau[c], t - st, tau_rise[k], lane) * step_sizes[k];
-            if (layered && lane == 0) layered[((size_t)k * nt + r) * ntau + c] = val;
-            acc += val;
+    for (int r = blockIdx.y; r < nt; r += gridDim.y) {
+        const double t = times[r];
+        for (int q = 0; q < 4; ++q) {
+            const int c = blockIdx.x * 16 + q * 4 + wv;
+            if (c >= ntau) continue;
+            double acc = 0.0;
+            for (int k = 0; k < nsteps; ++k) {
+                const double st = step_times[k];
+                double val = 0.0;
+                if (t > st) val = trapz_response_expdecay(ys, phis, eys, ny, tau[c], t - st, tau_rise[k], lane) * step_sizes[k];
+                if (layered && lane == 0) layered[((size_t)k * nt + r) * ntau + c] = val;
+                acc += val;
+            }
+            if (lane == 0) a[(size_t)r * ntau + c] = acc;
         }
-        if (lane == 0) a[(size_t)r * ntau + c] = acc;
     }
 }
 
@@ -494,18 +500,21 @@ __global__ __launch_bounds__(256) void response_pot_kernel(const double* __restr
                                                            const double* __restrict__ step_times,
                                                            const double* __restrict__ step_sizes, int nsteps,
                                                            double* __restrict__ a, double* __restrict__ layered) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= ntau) return;
-    const double t = times[r], tc = tau[c];
-    double acc = 0.0;
-    for (int k = 0; k < nsteps; ++k) {
-        const double st = step_times[k];
-        double val = 0.0;
-        if (t >= st) val = exp(-(t - st) / tc) * step_sizes[k];
-        if (layered) layered[((size_t)k * nt + r) * ntau + c] = val;
-        acc += val;
+    const double tc = tau[c];
+    for (int r = blockIdx.y; r < nt; r += gridDim.y) {
+        const double t = times[r];
+        double acc = 0.0;
+        for (int k = 0; k < nsteps; ++k) {
+            const double st = step_times[k];
+            double val = 0.0;
+            if (t >= st) val = exp(-(t - st) / tc) * step_sizes[k];
+            if (layered) layered[((size_t)k * nt + r) * ntau + c] = val;
+            acc += val;
+        }
+        a[(size_t)r * ntau + c] = acc;
     }
-    a[(size_t)r * ntau + c] = acc;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -540,6 +549,9 @@ __global__ __launch_bounds__(256) void eis_vmm_kernel(const double* __restrict__
 // ---------------------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------------------
+// rows on gridDim.y: as many as a grid has, the kernels stride over the rest
+static inline int grid_rows(int rows) { return rows < kGridDimMax ? rows : kGridDimMax; }
+
 void launch_lookup(hipStream_t st, double eps, int ngrid, int ny, const double* wt_re, const double* wt_im,
                    double* z_re, double* z_im) {
     const int blocks = (2 * ngrid + 3) / 4;
@@ -563,7 +575,7 @@ void launch_impedance_matrix(hipStream_t st, int B, int freq_batched, const doub
             hipLaunchKernelGGL(toeplitz_cr_trapz_kernel, dim3((tot + 3) / 4), dim3(256), y_tables_lds(nullptr, ny).bytes, st,
                                freq, nf, tau, ntau, eps, ny, cr_scratch);
         const int zb = B < 64 ? B : 64;
-        hipLaunchKernelGGL(toeplitz_fill_kernel, dim3((ntau + 255) / 256, nf, zb), dim3(256), 0, st, B, nf, ntau,
+        hipLaunchKernelGGL(toeplitz_fill_kernel, dim3((ntau + 255) / 256, grid_rows(nf), zb), dim3(256), 0, st, B, nf, ntau,
                            cr_scratch, a_re, a_im);
         return;
     }
@@ -574,18 +586,29 @@ void launch_impedance_matrix(hipStream_t st, int B, int freq_batched, const doub
         double* lt = cr_scratch + count_f;
         const int cnt = count_f > ntau ? count_f : ntau;
         hipLaunchKernelGGL(log_grid_kernel, dim3((cnt + 255) / 256), dim3(256), 0, st, count_f, freq, ntau, tau, lw, lt);
-        int tpr = ((ntau + 1) / 2 + 63) / 64 * 64;           // threads per row (two columns each)
-        if (tpr > 1024) tpr = 1024;
-        while (1024 % tpr) tpr += 64;                         // 64,128,256,512,1024
-        int rpb = 256;
-        while (rpb > 4 && (long long)B * ((nf + rpb - 1) / rpb) < 1024) rpb /= 2;   // enough workgroups for 256 CUs
+        int tpr, rpb;
+        size_t lds;
+        impedance_interp_form(B, nf, ntau, ngrid, &tpr, &rpb, &lds);
         const int bx = (nf + rpb - 1) / rpb;
-        hipLaunchKernelGGL(impedance_interp_kernel, dim3(bx, B), dim3(1024), impedance_interp_lds(nullptr, ngrid, rpb).bytes, st,
+        hipLaunchKernelGGL(impedance_interp_kernel, dim3(bx, B), dim3(1024), lds, st,
                            freq_batched, lw, nf, lt, ntau, ngrid, lut6, rpb, tpr, a_re, a_im);
     } else {
-        hipLaunchKernelGGL(impedance_trapz_kernel, dim3((ntau + 15) / 16, nf, B), dim3(256), y_tables_lds(nullptr, ny).bytes,
+        hipLaunchKernelGGL(impedance_trapz_kernel, dim3((ntau + 15) / 16, grid_rows(nf), B), dim3(256), y_tables_lds(nullptr, ny).bytes,
                            st, freq_batched, freq, nf, tau, ntau, eps, ny, a_re, a_im);
     }
+}
+
+void impedance_interp_form(int B, int nf, int ntau, int ngrid, int* tpr_out, int* rpb_out, size_t* lds_bytes) {
+    int tpr = ((ntau + 1) / 2 + 63) / 64 * 64;           // threads per row (two columns each)
+    if (tpr > 1024) tpr = 1024;
+    while (1024 % tpr) tpr += 64;                         // 64,128,256,512,1024
+    int rpb = kInterpMaxRows;
+    while (rpb > kInterpMinRows && (long long)B * ((nf + rpb - 1) / rpb) < 1024) rpb /= 2;   // enough workgroups for 256 CUs
+    // a long table leaves fewer rows' ln(omega) beside it: every ngrid the entry points accept fits at kInterpMinRows
+    while (rpb > kInterpMinRows && impedance_interp_lds(nullptr, ngrid, rpb).bytes > kLdsLimit) rpb /= 2;
+    *tpr_out = tpr;
+    *rpb_out = rpb;
+    *lds_bytes = impedance_interp_lds(nullptr, ngrid, rpb).bytes;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -616,25 +639,28 @@ __device__ __forceinline__ void cerf(double x, double y, double& re, double& im)
 // (a, b) = (min(0, sgn nu_m), max(0, sgn nu_m))   (phasance.py:19-33, 62-82)
 __global__ void phasor_z_kernel(const double* __restrict__ freq, int nf, const double* __restrict__ nu, int nnu, double eps,
                                 double* __restrict__ zre, double* __restrict__ zim) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= nnu) return;
     const double PI = 3.141592653589793;
-    const double lw = log(2.0 * PI * freq[r]), num = nu[c];
+    const double num = nu[c];
     const double sg = (num > 0.0) ? 1.0 : ((num < 0.0) ? -1.0 : 0.0);
     const double a = fmin(0.0, sg), b = fmax(0.0, sg);
-    // prefactor exp(nu_m L + L^2 / (4 eps^2)), L = ln(j w) = lw + j pi/2
-    const double q = 1.0 / (4.0 * eps * eps);
-    const double e_re = num * lw + (lw * lw - 0.25 * PI * PI) * q;
-    const double e_im = num * 0.5 * PI + PI * lw * q;
-    const double mag = 0.5 * sqrt(PI) / eps * exp(e_re);
-    const double p_re = mag * cos(e_im), p_im = mag * sin(e_im);
-    const double y = -PI / (4.0 * eps), xoff = -lw / (2.0 * eps);
-    double br, bi, ar, ai;
-    cerf(eps * (b - num) + xoff, y, br, bi);
-    cerf(eps * (a - num) + xoff, y, ar, ai);
-    const double dr = br - ar, di = bi - ai;
-    zre[(size_t)r * nnu + c] = p_re * dr - p_im * di;
-    zim[(size_t)r * nnu + c] = p_re * di + p_im * dr;
+    for (int r = blockIdx.y; r < nf; r += gridDim.y) {
+        const double lw = log(2.0 * PI * freq[r]);
+        // prefactor exp(nu_m L + L^2 / (4 eps^2)), L = ln(j w) = lw + j pi/2
+        const double q = 1.0 / (4.0 * eps * eps);
+        const double e_re = num * lw + (lw * lw - 0.25 * PI * PI) * q;
+        const double e_im = num * 0.5 * PI + PI * lw * q;
+        const double mag = 0.5 * sqrt(PI) / eps * exp(e_re);
+        const double p_re = mag * cos(e_im), p_im = mag * sin(e_im);
+        const double y = -PI / (4.0 * eps), xoff = -lw / (2.0 * eps);
+        double br, bi, ar, ai;
+        cerf(eps * (b - num) + xoff, y, br, bi);
+        cerf(eps * (a - num) + xoff, y, ar, ai);
+        const double dr = br - ar, di = bi - ai;
+        zre[(size_t)r * nnu + c] = p_re * dr - p_im * di;
+        zim[(size_t)r * nnu + c] = p_re * di + p_im * dr;
+    }
 }
 
 // rm_layered[k][r][c] = size_k (G(b) - G(a)) for t_r > t_k, G(nu) = sqrt(pi)/2 dt^-nu_m / Gamma(1 - nu_m) / eps *
@@ -642,36 +668,39 @@ __global__ void phasor_z_kernel(const double* __restrict__ freq, int nf, const d
 __global__ void phasor_v_kernel(const double* __restrict__ times, int nt, const double* __restrict__ nu, int nnu, double eps,
                                 const double* __restrict__ step_times, const double* __restrict__ step_sizes, int nsteps,
                                 double* __restrict__ rm, double* __restrict__ layered) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= nnu) return;
     const double PI = 3.141592653589793;
-    const double num = nu[c], t = times[r];
+    const double num = nu[c];
     const double sg = (num > 0.0) ? 1.0 : ((num < 0.0) ? -1.0 : 0.0);
     const double a = fmin(0.0, sg), b = fmax(0.0, sg);
     const double gin = 1.0 / tgamma(1.0 - num);
-    double acc = 0.0;
-    for (int k = 0; k < nsteps; ++k) {
-        double val = 0.0;
-        if (t > step_times[k]) {
-            const double ldt = log(t - step_times[k]);
-            const double pre = 0.5 * sqrt(PI) * (exp(-num * ldt) * gin) / eps * exp(ldt * ldt / (4.0 * eps * eps));
-            const double xo = ldt / (2.0 * eps);
-            val = step_sizes[k] * (pre * erf(eps * (b - num) + xo) - pre * erf(eps * (a - num) + xo));
+    for (int r = blockIdx.y; r < nt; r += gridDim.y) {
+        const double t = times[r];
+        double acc = 0.0;
+        for (int k = 0; k < nsteps; ++k) {
+            double val = 0.0;
+            if (t > step_times[k]) {
+                const double ldt = log(t - step_times[k]);
+                const double pre = 0.5 * sqrt(PI) * (exp(-num * ldt) * gin) / eps * exp(ldt * ldt / (4.0 * eps * eps));
+                const double xo = ldt / (2.0 * eps);
+                val = step_sizes[k] * (pre * erf(eps * (b - num) + xo) - pre * erf(eps * (a - num) + xo));
+            }
+            if (layered) layered[((size_t)k * nt + r) * nnu + c] = val;
+            acc += val;
         }
-        if (layered) layered[((size_t)k * nt + r) * nnu + c] = val;
-        acc += val;
+        rm[(size_t)r * nnu + c] = acc;
     }
-    rm[(size_t)r * nnu + c] = acc;
 }
 
 void launch_phasor_z(hipStream_t st, const double* freq, int nf, const double* nu, int nnu, double eps, double* zre,
                      double* zim) {
-    hipLaunchKernelGGL(phasor_z_kernel, dim3((nnu + 63) / 64, nf), dim3(64), 0, st, freq, nf, nu, nnu, eps, zre, zim);
+    hipLaunchKernelGGL(phasor_z_kernel, dim3((nnu + 63) / 64, grid_rows(nf)), dim3(64), 0, st, freq, nf, nu, nnu, eps, zre, zim);
 }
 
 void launch_phasor_v(hipStream_t st, const double* times, int nt, const double* nu, int nnu, double eps,
                      const double* step_times, const double* step_sizes, int nsteps, double* rm, double* layered) {
-    hipLaunchKernelGGL(phasor_v_kernel, dim3((nnu + 63) / 64, nt), dim3(64), 0, st, times, nt, nu, nnu, eps, step_times,
+    hipLaunchKernelGGL(phasor_v_kernel, dim3((nnu + 63) / 64, grid_rows(nt)), dim3(64), 0, st, times, nt, nu, nnu, eps, step_times,
                        step_sizes, nsteps, rm, layered);
 }
 
@@ -720,10 +749,10 @@ void launch_response_matrix(hipStream_t st, const double* times, int nt, const d
         int rpb = 32;
         while (rpb > 1 && (long long)((ntau + 255) / 256) * ((nt + rpb - 1) / rpb) < 1024) rpb /= 2;
         hipLaunchKernelGGL(response_interp_kernel, dim3((ntau + 255) / 256, (nt + rpb - 1) / rpb), dim3(256),
-                           3 * (size_t)ngrid * sizeof(double), st, times, nt, tau, ntau, step_times, step_sizes, nsteps,
+                           response_interp_lds(nullptr, ngrid).bytes, st, times, nt, tau, ntau, step_times, step_sizes, nsteps,
                            ngrid, lut3, rpb, a, layered);
     } else {
-        hipLaunchKernelGGL(response_trapz_kernel, dim3((ntau + 15) / 16, nt), dim3(256), y_tables_lds(nullptr, ny).bytes, st,
+        hipLaunchKernelGGL(response_trapz_kernel, dim3((ntau + 15) / 16, grid_rows(nt)), dim3(256), y_tables_lds(nullptr, ny).bytes, st,
                            times, nt, tau, ntau, step_times, step_sizes, nsteps, eps, ny, a, layered);
     }
 }
@@ -732,10 +761,10 @@ void launch_response_variant(hipStream_t st, const double* times, int nt, const 
                              const double* step_times, const double* step_sizes, const double* tau_rise, int nsteps,
                              int variant, double eps, int ny, double* a, double* layered) {
     if (variant == HIPDRT_RESPONSE_POT)
-        hipLaunchKernelGGL(response_pot_kernel, dim3((ntau + 255) / 256, nt), dim3(256), 0, st, times, nt, tau, ntau,
+        hipLaunchKernelGGL(response_pot_kernel, dim3((ntau + 255) / 256, grid_rows(nt)), dim3(256), 0, st, times, nt, tau, ntau,
                            step_times, step_sizes, nsteps, a, layered);
     else
-        hipLaunchKernelGGL(response_expdecay_kernel, dim3((ntau + 15) / 16, nt), dim3(256), y_tables_lds(nullptr, ny).bytes, st,
+        hipLaunchKernelGGL(response_expdecay_kernel, dim3((ntau + 15) / 16, grid_rows(nt)), dim3(256), y_tables_lds(nullptr, ny).bytes, st,
                            times, nt, tau, ntau, step_times, step_sizes, tau_rise, nsteps, eps, ny, a, layered);
 }
 

@@ -22,7 +22,7 @@ extern "C" {
 int hipdrt_impedance_lookup(hipdrt_ctx* ctx, double epsilon, int ngrid, int ny, const double* wt_re,
                             const double* wt_im, double* z_re, double* z_im) try {
     HIPDRT_REQUIRE(ctx && wt_re && wt_im && z_re && z_im, "NULL pointer");
-    HIPDRT_REQUIRE(ngrid >= 2 && ny >= 2 && ny <= 6000, "ngrid >= 2, 2 <= ny <= 6000");
+    HIPDRT_REQUIRE(ngrid >= 2 && ny_ok(ny), "ngrid >= 2, 2 <= ny <= 6000");
     hipStream_t st; TRY(enter(ctx, &st));
     DevBuf dwr, dwi, dzr, dzi;
     const size_t gb = (size_t)ngrid * sizeof(double);
@@ -93,7 +93,7 @@ int hipdrt_chrono_var_matrix(hipdrt_ctx* ctx, const double* tt, int nt, const in
 
 int hipdrt_response_lookup(hipdrt_ctx* ctx, double epsilon, int ngrid, int ny, const double* td, double* v) try {
     HIPDRT_REQUIRE(ctx && td && v, "NULL pointer");
-    HIPDRT_REQUIRE(ngrid >= 2 && ny >= 2 && ny <= 6000, "ngrid >= 2, 2 <= ny <= 6000");
+    HIPDRT_REQUIRE(ngrid >= 2 && ny_ok(ny), "ngrid >= 2, 2 <= ny <= 6000");
     hipStream_t st; TRY(enter(ctx, &st));
     DevBuf dtd, dv;
     const size_t gb = (size_t)ngrid * sizeof(double);
@@ -114,9 +114,9 @@ int hipdrt_response_matrix(hipdrt_ctx* ctx, const double* times, int nt, const d
     HIPDRT_REQUIRE(mode == HIPDRT_MODE_INTERP || mode == HIPDRT_MODE_TRAPZ, "mode must be INTERP or TRAPZ");
     if (mode == HIPDRT_MODE_INTERP) {
         HIPDRT_REQUIRE(log_td && v && ngrid >= 2, "interpolate_grids must be provided for integrate_method 'interp'");
-        HIPDRT_REQUIRE(3 * (size_t)ngrid * sizeof(double) <= 150 * 1024, "lookup too long for LDS staging");
+        HIPDRT_REQUIRE(response_ngrid_ok(ngrid), "lookup too long for LDS staging");
     } else {
-        HIPDRT_REQUIRE(ny >= 2 && ny <= 6000, "2 <= ny <= 6000");
+        HIPDRT_REQUIRE(ny_ok(ny), "2 <= ny <= 6000");
     }
     hipStream_t st; TRY(enter(ctx, &st));
     DevBuf dt, dtau, dst, dsa, lut3, da, dl;
@@ -151,7 +151,7 @@ int hipdrt_response_matrix_variant(hipdrt_ctx* ctx, const double* times, int nt,
     HIPDRT_REQUIRE(variant == HIPDRT_RESPONSE_POT || variant == HIPDRT_RESPONSE_EXPDECAY, "variant must be POT or EXPDECAY");
     if (variant == HIPDRT_RESPONSE_EXPDECAY) {
         HIPDRT_REQUIRE(tau_rise, "the expdecay step model needs tau_rise");
-        HIPDRT_REQUIRE(ny >= 2 && ny <= 6000, "2 <= ny <= 6000");
+        HIPDRT_REQUIRE(ny_ok(ny), "2 <= ny <= 6000");
     }
     hipStream_t st; TRY(enter(ctx, &st));
     DevBuf dt, dtau, dst, dsa, dtr, da, dl;
@@ -198,10 +198,11 @@ static int impedance_matrix_common(hipdrt_ctx* ctx, int B, int freq_batched, con
     HIPDRT_REQUIRE(B >= 1 && nf >= 1 && ntau >= 1, "B, nf, ntau >= 1");
     HIPDRT_REQUIRE(mode == HIPDRT_MODE_INTERP || mode == HIPDRT_MODE_TRAPZ, "mode");
     HIPDRT_REQUIRE(!(toeplitz && freq_batched), "Toeplitz shortcut needs one shared frequency grid");
+    HIPDRT_REQUIRE(toeplitz || B <= kGridDimMax, "B <= 65535 spectra in one general build");
     if (mode == HIPDRT_MODE_INTERP)
-        HIPDRT_REQUIRE(log_wt_re && z_re && log_wt_im && z_im && ngrid >= 2 && ngrid <= 3400,
-                       "interp needs lookups with 2 <= ngrid <= 3400");
-    else HIPDRT_REQUIRE(ny >= 2 && ny <= 6000, "2 <= ny <= 6000");
+        HIPDRT_REQUIRE(log_wt_re && z_re && log_wt_im && z_im && impedance_ngrid_ok(ngrid),
+                       "interp needs lookups with ngrid >= 2 that one workgroup's LDS holds (2 <= ngrid <= 3406)");
+    else HIPDRT_REQUIRE(ny_ok(ny), "2 <= ny <= 6000");
     hipStream_t st; TRY(enter(ctx, &st));
     DevBuf dfreq, dtau, lut6, cr;
     TRY(upload(dfreq, freq, (size_t)(freq_batched ? B : 1) * nf * sizeof(double), st));

@@ -195,8 +195,8 @@ int hipdrt_plan_create(hipdrt_ctx* ctx, const double* freq, int nf, const double
     HIPDRT_REQUIRE(nf >= 2 && ntau >= 2 && capacity >= 1, "nf, ntau >= 2, capacity >= 1");
     HIPDRT_REQUIRE(mode == HIPDRT_MODE_INTERP || mode == HIPDRT_MODE_TRAPZ, "mode");
     if (mode == HIPDRT_MODE_INTERP)
-        HIPDRT_REQUIRE(wt_re && wt_im && log_wt_re && log_wt_im && ngrid >= 2 && ngrid <= 3400, "interp lookups");
-    HIPDRT_REQUIRE(ny >= 2 && ny <= 6000, "2 <= ny <= 6000");
+        HIPDRT_REQUIRE(wt_re && wt_im && log_wt_re && log_wt_im && impedance_ngrid_ok(ngrid), "interp lookups");
+    HIPDRT_REQUIRE(ny_ok(ny), "2 <= ny <= 6000");
     hipStream_t st; TRY(enter(ctx, &st));
     std::unique_ptr<hipdrt_plan> p(new hipdrt_plan());
     p->ctx = ctx;

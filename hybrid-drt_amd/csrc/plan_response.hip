@@ -176,9 +176,9 @@ int hipdrt_plan_predict_response(hipdrt_plan* p, const hipdrt_response_args* q, 
         HIPDRT_REQUIRE(q->mode == HIPDRT_MODE_INTERP || q->mode == HIPDRT_MODE_TRAPZ, "mode must be INTERP or TRAPZ");
         if (q->mode == HIPDRT_MODE_INTERP) {
             HIPDRT_REQUIRE(q->log_td && q->v && q->ngrid >= 2, "the response lookup table must be provided for mode INTERP");
-            HIPDRT_REQUIRE(3 * (size_t)q->ngrid * sizeof(double) <= 150 * 1024, "lookup too long for LDS staging");
+            HIPDRT_REQUIRE(response_ngrid_ok(q->ngrid), "lookup too long for LDS staging");
         } else {
-            HIPDRT_REQUIRE(q->ny >= 2 && q->ny <= 6000, "2 <= ny <= 6000");
+            HIPDRT_REQUIRE(ny_ok(q->ny), "2 <= ny <= 6000");
         }
     }
     if (want_dop) HIPDRT_REQUIRE(q->basis_nu && q->nu_epsilon > 0.0 && std::isfinite(q->nu_epsilon), "the DOP term needs basis_nu [dop_size] and nu_epsilon > 0");

@@ -128,6 +128,11 @@ int hipdrt_debug_hyper_step(hipdrt_ctx* ctx, const hipdrt_debug_hyper_args* a);
 /* test hook: the LDS form launch_hyper picks for a problem -- *form 1: Toeplitz columns beside the two m-vectors, 2: inside the
  * second m-vector, 0: the general row-streaming form -- and its dynamic LDS in bytes; HIPDRT_E_INVALID when none fits.        */
 int hipdrt_debug_hyper_form(hipdrt_ctx* ctx, int n, int m, int ns, int toeplitz, int outlier, int* form, long long* lds_bytes);
+/* test hook (tests/test_gpu_matrices_edges.py): the launch form of the general interp build of hipdrt_impedance_matrix for B
+ * spectra of nf frequencies, ntau columns and lookups of ngrid knots -- threads per matrix row, rows per workgroup and dynamic LDS
+ * in bytes; HIPDRT_E_INVALID for an ngrid the entry points refuse.  Nothing is launched.                                      */
+int hipdrt_debug_impedance_interp_form(hipdrt_ctx* ctx, int B, int nf, int ntau, int ngrid, int* tpr, int* rpb,
+                                       long long* lds_bytes);
 
 /* test hook (tests/test_gpu_kk.py): the statistics stage of hipdrt_plan_kk_screen's kernel as it is, on host residuals --
  * freq [nf] strictly ascending or descending, err_re / err_im [B][nf]; out (any may be NULL): std [B], outlier_mask [B][nf],

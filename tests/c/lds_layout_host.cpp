@@ -193,6 +193,11 @@ static void impedance_interp(int ng, int rpb) {
         });
 }
 
+static void response_interp(int ng) {
+    run("response_interp", 3 * (size_t)ng * 8, [&](void* b) { return response_interp_lds(b, ng); },
+        [&](const ResponseInterpLds& L) { return std::vector<Region>{R(L, xp, ng), R(L, fp, ng), R(L, sl, ng)}; });
+}
+
 int main() {
     // hyper_kernel: (n, m, ns) in the form hyper_lds_form gives a (toeplitz, outlier) problem of that shape
     hyper("hyper form 1", 66, 24, 2, HYPER_BESIDE, false, 6648);
@@ -241,6 +246,9 @@ int main() {
     y_tables(1000);
     impedance_interp(2000, 256);
     impedance_interp(1001, 4);
+    impedance_interp(3406, 4);
+    response_interp(2000);
+    response_interp(6816);
     if (failures) { std::printf("%d checks failed\n", failures); return 1; }
     std::printf("lds layouts ok\n");
     return 0;
