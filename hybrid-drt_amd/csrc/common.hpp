@@ -106,6 +106,27 @@ inline bool response_ngrid_ok(int ngrid) {
     return ngrid >= 2 && ngrid <= (1 << 20) && response_interp_lds(nullptr, ngrid).bytes <= kLdsLimit;
 }
 
+// A lookup buffer holds `ntables` tables back to back, each {x, f, slope}[ngrid]: lut6 = the impedance lookups {ln(omega tau), Z',
+// slope} then {ln(omega tau), Z'', slope}, lut3 = the response lookup {ln(t / tau), v, slope}.  Table k of buffer `base`:
+template <class T>
+struct LutPart { T *x, *f, *slope; };
+template <class T>
+HIPDRT_HD __forceinline__ LutPart<T> lut_part(T* base, int ngrid, int k) {
+    // ngrid <= 2^20 (impedance_ngrid_ok, response_ngrid_ok): int offsets, each formed on its own as the kernels always formed them
+    return LutPart<T>{base + 3 * k * ngrid, base + (3 * k + 1) * ngrid, base + (3 * k + 2) * ngrid};
+}
+HIPDRT_HD inline size_t lut_doubles(int ngrid, int ntables) { return (size_t)3 * ngrid * ntables; }
+// host side of table k: the buffer allocated on first use, then the host's abscissae and values copied in, each where given; the
+// slopes follow from launch_lut_slopes
+inline int stage_lut(hipStream_t st, DevBuf& lut, int ngrid, int ntables, int k, const double* x, const double* f) {
+    if (!lut.p) HIPDRT_CHECK(lut.alloc(lut_doubles(ngrid, ntables) * sizeof(double)));
+    const LutPart<double> T = lut_part(lut.d(), ngrid, k);
+    const size_t gb = (size_t)ngrid * sizeof(double);
+    if (x) HIPDRT_CHECK(hipMemcpyAsync(T.x, x, gb, hipMemcpyHostToDevice, st));
+    if (f) HIPDRT_CHECK(hipMemcpyAsync(T.f, f, gb, hipMemcpyHostToDevice, st));
+    return HIPDRT_OK;
+}
+
 // area of one tau basis function: sqrt(pi) / epsilon
 inline double basis_area(double eps) { return 1.7724538509055159 / eps; }
 
@@ -150,11 +171,13 @@ void ensure_stream_pool(int device);
 // matrices.hip
 void launch_lookup(hipStream_t st, double eps, int ngrid, int ny, const double* wt_re, const double* wt_im,
                    double* z_re, double* z_im);
-void launch_lookup_slopes(hipStream_t st, int ngrid, const double* xp, const double* fp, double* slopes);
-// lut = {log_wt_re, z_re, slope_re, log_wt_im, z_im, slope_im} each [ngrid], device
+// slope[j] = (f[j + 1] - f[j]) / (x[j + 1] - x[j]) of the first `ntables` tables of a lookup buffer (lut_part)
+void launch_lut_slopes(hipStream_t st, double* base, int ngrid, int ntables);
+// lut6: the two impedance lookups (lut_part), device; scratch: impedance_scratch_doubles(...) doubles of the same arguments
 void launch_impedance_matrix(hipStream_t st, int B, int freq_batched, const double* freq, int nf, const double* tau,
                              int ntau, int mode, int toeplitz, double eps, int ngrid, const double* lut6, int ny,
-                             double* a_re, double* a_im, double* cr_scratch);
+                             double* a_re, double* a_im, double* scratch);
+size_t impedance_scratch_doubles(int B, int freq_batched, int nf, int ntau, int mode, int toeplitz);
 // the general interp build's launch form: threads per row, rows per workgroup and dynamic LDS (launch_impedance_matrix and
 // hipdrt_debug_impedance_interp_form both ask here)
 void impedance_interp_form(int B, int nf, int ntau, int ngrid, int* tpr, int* rpb, size_t* lds_bytes);

@@ -280,7 +280,7 @@ HIPDRT_HD inline RankLds rank_lds(void* sm, int sr, int sc) {
 }
 
 // ---- matrices.hip ----
-// the trapezoid kernels' y tables (fill_y_tables): ys, phis, eys [ny each]
+// the trapezoid kernels' y tables (stage_y_tables): ys, phis, eys [ny each]
 struct YTablesLds { double *ys, *phis, *eys; size_t bytes; };
 HIPDRT_HD inline YTablesLds y_tables_lds(void* sm, int ny) {
     LdsCarver c = lds_carver(sm);

@@ -17,6 +17,27 @@ int func_eval_dev(hipStream_t st, const double* basis_dev, int nb, const double*
 }
 }  // namespace hipdrt
 
+// the tail of every entry point: the outputs on their way to the host, and the stream drained
+static int back_and_wait(const DevOuts& outs, hipStream_t st) {
+    TRY(outs.back(st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    return HIPDRT_OK;
+}
+
+// the device copies of what every step-response builder reads (col: the tau or nu grid; tau_rise only where the model has one)
+struct StepInputs {
+    DevBuf times, col, step_times, step_sizes, tau_rise;
+    int upload_all(hipStream_t st, const double* t, int nt, const double* c, int ncol, const double* stt, const double* sz, int nsteps,
+                   const double* rise = nullptr) {
+        TRY(upload(times, t, (size_t)nt * sizeof(double), st));
+        TRY(upload(col, c, (size_t)ncol * sizeof(double), st));
+        TRY(upload(step_times, stt, (size_t)nsteps * sizeof(double), st));
+        TRY(upload(step_sizes, sz, (size_t)nsteps * sizeof(double), st));
+        if (rise) TRY(upload(tau_rise, rise, (size_t)nsteps * sizeof(double), st));
+        return HIPDRT_OK;
+    }
+};
+
 extern "C" {
 
 int hipdrt_impedance_lookup(hipdrt_ctx* ctx, double epsilon, int ngrid, int ny, const double* wt_re,
@@ -24,16 +45,15 @@ int hipdrt_impedance_lookup(hipdrt_ctx* ctx, double epsilon, int ngrid, int ny, 
     HIPDRT_REQUIRE(ctx && wt_re && wt_im && z_re && z_im, "NULL pointer");
     HIPDRT_REQUIRE(ngrid >= 2 && ny_ok(ny), "ngrid >= 2, 2 <= ny <= 6000");
     hipStream_t st; TRY(enter(ctx, &st));
-    DevBuf dwr, dwi, dzr, dzi;
+    DevBuf dwr, dwi;
+    DevOuts outs;
+    double *dzr = nullptr, *dzi = nullptr;
     const size_t gb = (size_t)ngrid * sizeof(double);
     TRY(upload(dwr, wt_re, gb, st)); TRY(upload(dwi, wt_im, gb, st));
-    HIPDRT_CHECK(dzr.alloc(gb)); HIPDRT_CHECK(dzi.alloc(gb));
-    launch_lookup(st, epsilon, ngrid, ny, dwr.d(), dwi.d(), dzr.d(), dzi.d());
+    TRY(outs.want(z_re, (size_t)ngrid, dzr)); TRY(outs.want(z_im, (size_t)ngrid, dzi));
+    launch_lookup(st, epsilon, ngrid, ny, dwr.d(), dwi.d(), dzr, dzi);
     LAUNCH_OK();
-    HIPDRT_CHECK(hipMemcpyAsync(z_re, dzr.p, gb, hipMemcpyDeviceToHost, st));
-    HIPDRT_CHECK(hipMemcpyAsync(z_im, dzi.p, gb, hipMemcpyDeviceToHost, st));
-    HIPDRT_CHECK(hipStreamSynchronize(st));
-    return HIPDRT_OK;
+    return back_and_wait(outs, st);
 } HIPDRT_CATCH
 
 int hipdrt_phasor_z_matrix(hipdrt_ctx* ctx, const double* freq, int nf, const double* basis_nu, int n_nu, double nu_epsilon,
@@ -41,17 +61,15 @@ int hipdrt_phasor_z_matrix(hipdrt_ctx* ctx, const double* freq, int nf, const do
     HIPDRT_REQUIRE(ctx && freq && basis_nu && zm_re && zm_im, "NULL pointer");
     HIPDRT_REQUIRE(nf >= 1 && n_nu >= 1 && nu_epsilon > 0.0, "nf, n_nu >= 1, nu_epsilon > 0");
     hipStream_t st; TRY(enter(ctx, &st));
-    DevBuf df, dn, dr, di;
+    DevBuf df, dn;
+    DevOuts outs;
+    double *dr = nullptr, *di = nullptr;
     TRY(upload(df, freq, (size_t)nf * sizeof(double), st));
     TRY(upload(dn, basis_nu, (size_t)n_nu * sizeof(double), st));
-    const size_t ob = (size_t)nf * n_nu * sizeof(double);
-    HIPDRT_CHECK(dr.alloc(ob)); HIPDRT_CHECK(di.alloc(ob));
-    launch_phasor_z(st, df.d(), nf, dn.d(), n_nu, nu_epsilon, dr.d(), di.d());
+    TRY(outs.want(zm_re, (size_t)nf * n_nu, dr)); TRY(outs.want(zm_im, (size_t)nf * n_nu, di));
+    launch_phasor_z(st, df.d(), nf, dn.d(), n_nu, nu_epsilon, dr, di);
     LAUNCH_OK();
-    HIPDRT_CHECK(hipMemcpyAsync(zm_re, dr.p, ob, hipMemcpyDeviceToHost, st));
-    HIPDRT_CHECK(hipMemcpyAsync(zm_im, di.p, ob, hipMemcpyDeviceToHost, st));
-    HIPDRT_CHECK(hipStreamSynchronize(st));
-    return HIPDRT_OK;
+    return back_and_wait(outs, st);
 } HIPDRT_CATCH
 
 int hipdrt_phasor_v_matrix(hipdrt_ctx* ctx, const double* times, int nt, const double* basis_nu, int n_nu, double nu_epsilon,
@@ -59,20 +77,14 @@ int hipdrt_phasor_v_matrix(hipdrt_ctx* ctx, const double* times, int nt, const d
     HIPDRT_REQUIRE(ctx && times && basis_nu && step_times && step_sizes && rm, "NULL pointer");
     HIPDRT_REQUIRE(nt >= 1 && n_nu >= 1 && nsteps >= 1 && nu_epsilon > 0.0, "nt, n_nu, nsteps >= 1, nu_epsilon > 0");
     hipStream_t st; TRY(enter(ctx, &st));
-    DevBuf dt, dn, ds, da, dr, dl;
-    TRY(upload(dt, times, (size_t)nt * sizeof(double), st));
-    TRY(upload(dn, basis_nu, (size_t)n_nu * sizeof(double), st));
-    TRY(upload(ds, step_times, (size_t)nsteps * sizeof(double), st));
-    TRY(upload(da, step_sizes, (size_t)nsteps * sizeof(double), st));
-    const size_t ob = (size_t)nt * n_nu * sizeof(double);
-    HIPDRT_CHECK(dr.alloc(ob));
-    if (layered) HIPDRT_CHECK(dl.alloc(ob * nsteps));
-    launch_phasor_v(st, dt.d(), nt, dn.d(), n_nu, nu_epsilon, ds.d(), da.d(), nsteps, dr.d(), layered ? dl.d() : nullptr);
+    StepInputs in;
+    DevOuts outs;
+    double *dr = nullptr, *dl = nullptr;
+    TRY(in.upload_all(st, times, nt, basis_nu, n_nu, step_times, step_sizes, nsteps));
+    TRY(outs.want(rm, (size_t)nt * n_nu, dr)); TRY(outs.want(layered, (size_t)nt * n_nu * nsteps, dl));
+    launch_phasor_v(st, in.times.d(), nt, in.col.d(), n_nu, nu_epsilon, in.step_times.d(), in.step_sizes.d(), nsteps, dr, dl);
     LAUNCH_OK();
-    HIPDRT_CHECK(hipMemcpyAsync(rm, dr.p, ob, hipMemcpyDeviceToHost, st));
-    if (layered) HIPDRT_CHECK(hipMemcpyAsync(layered, dl.p, ob * nsteps, hipMemcpyDeviceToHost, st));
-    HIPDRT_CHECK(hipStreamSynchronize(st));
-    return HIPDRT_OK;
+    return back_and_wait(outs, st);
 } HIPDRT_CATCH
 
 int hipdrt_chrono_var_matrix(hipdrt_ctx* ctx, const double* tt, int nt, const int* seg, int nseg, double vmm_epsilon,
@@ -80,30 +92,29 @@ int hipdrt_chrono_var_matrix(hipdrt_ctx* ctx, const double* tt, int nt, const in
     HIPDRT_REQUIRE(ctx && tt && seg && vmm, "NULL pointer");
     HIPDRT_REQUIRE(nt >= 1 && nseg >= 1, "nt >= 1, nseg >= 1");
     hipStream_t st; TRY(enter(ctx, &st));
-    DevBuf dtt, dseg, dv;
+    DevBuf dtt, dseg;
+    DevOuts outs;
+    double* dv = nullptr;
     TRY(upload(dtt, tt, (size_t)nt * sizeof(double), st));
     TRY(upload(dseg, seg, (size_t)(nseg + 1) * sizeof(int), st));
-    HIPDRT_CHECK(dv.alloc((size_t)nt * nt * sizeof(double)));
-    launch_chrono_vmm(st, dtt.d(), nt, dseg.i(), nseg, vmm_epsilon, uniform, dv.d());
+    TRY(outs.want(vmm, (size_t)nt * nt, dv));
+    launch_chrono_vmm(st, dtt.d(), nt, dseg.i(), nseg, vmm_epsilon, uniform, dv);
     LAUNCH_OK();
-    HIPDRT_CHECK(hipMemcpyAsync(vmm, dv.p, (size_t)nt * nt * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPDRT_CHECK(hipStreamSynchronize(st));
-    return HIPDRT_OK;
+    return back_and_wait(outs, st);
 } HIPDRT_CATCH
 
 int hipdrt_response_lookup(hipdrt_ctx* ctx, double epsilon, int ngrid, int ny, const double* td, double* v) try {
     HIPDRT_REQUIRE(ctx && td && v, "NULL pointer");
     HIPDRT_REQUIRE(ngrid >= 2 && ny_ok(ny), "ngrid >= 2, 2 <= ny <= 6000");
     hipStream_t st; TRY(enter(ctx, &st));
-    DevBuf dtd, dv;
-    const size_t gb = (size_t)ngrid * sizeof(double);
-    TRY(upload(dtd, td, gb, st));
-    HIPDRT_CHECK(dv.alloc(gb));
-    launch_response_lookup(st, epsilon, ngrid, ny, dtd.d(), dv.d());
+    DevBuf dtd;
+    DevOuts outs;
+    double* dv = nullptr;
+    TRY(upload(dtd, td, (size_t)ngrid * sizeof(double), st));
+    TRY(outs.want(v, (size_t)ngrid, dv));
+    launch_response_lookup(st, epsilon, ngrid, ny, dtd.d(), dv);
     LAUNCH_OK();
-    HIPDRT_CHECK(hipMemcpyAsync(v, dv.p, gb, hipMemcpyDeviceToHost, st));
-    HIPDRT_CHECK(hipStreamSynchronize(st));
-    return HIPDRT_OK;
+    return back_and_wait(outs, st);
 } HIPDRT_CATCH
 
 int hipdrt_response_matrix(hipdrt_ctx* ctx, const double* times, int nt, const double* tau, int ntau,
@@ -119,28 +130,20 @@ int hipdrt_response_matrix(hipdrt_ctx* ctx, const double* times, int nt, const d
         HIPDRT_REQUIRE(ny_ok(ny), "2 <= ny <= 6000");
     }
     hipStream_t st; TRY(enter(ctx, &st));
-    DevBuf dt, dtau, dst, dsa, lut3, da, dl;
-    TRY(upload(dt, times, (size_t)nt * sizeof(double), st));
-    TRY(upload(dtau, tau, (size_t)ntau * sizeof(double), st));
-    TRY(upload(dst, step_times, (size_t)nsteps * sizeof(double), st));
-    TRY(upload(dsa, step_sizes, (size_t)nsteps * sizeof(double), st));
+    StepInputs in;
+    DevBuf lut3;
+    DevOuts outs;
+    double *da = nullptr, *dl = nullptr;
+    TRY(in.upload_all(st, times, nt, tau, ntau, step_times, step_sizes, nsteps));
     if (mode == HIPDRT_MODE_INTERP) {
-        const size_t gb = (size_t)ngrid * sizeof(double);
-        HIPDRT_CHECK(lut3.alloc(3 * gb));
-        HIPDRT_CHECK(hipMemcpyAsync(lut3.d(), log_td, gb, hipMemcpyHostToDevice, st));
-        HIPDRT_CHECK(hipMemcpyAsync(lut3.d() + ngrid, v, gb, hipMemcpyHostToDevice, st));
-        launch_lookup_slopes(st, ngrid, lut3.d(), lut3.d() + ngrid, lut3.d() + 2 * (size_t)ngrid);
+        TRY(stage_lut(st, lut3, ngrid, 1, 0, log_td, v));
+        launch_lut_slopes(st, lut3.d(), ngrid, 1);
     }
-    const size_t ab = (size_t)nt * ntau * sizeof(double);
-    HIPDRT_CHECK(da.alloc(ab));
-    if (layered) HIPDRT_CHECK(dl.alloc(ab * nsteps));
-    launch_response_matrix(st, dt.d(), nt, dtau.d(), ntau, dst.d(), dsa.d(), nsteps, mode, epsilon, ngrid, lut3.d(), ny,
-                           da.d(), layered ? dl.d() : nullptr);
+    TRY(outs.want(a, (size_t)nt * ntau, da)); TRY(outs.want(layered, (size_t)nt * ntau * nsteps, dl));
+    launch_response_matrix(st, in.times.d(), nt, in.col.d(), ntau, in.step_times.d(), in.step_sizes.d(), nsteps, mode, epsilon,
+                           ngrid, lut3.d(), ny, da, dl);
     LAUNCH_OK();
-    HIPDRT_CHECK(hipMemcpyAsync(a, da.p, ab, hipMemcpyDeviceToHost, st));
-    if (layered) HIPDRT_CHECK(hipMemcpyAsync(layered, dl.p, ab * nsteps, hipMemcpyDeviceToHost, st));
-    HIPDRT_CHECK(hipStreamSynchronize(st));
-    return HIPDRT_OK;
+    return back_and_wait(outs, st);
 } HIPDRT_CATCH
 
 int hipdrt_response_matrix_variant(hipdrt_ctx* ctx, const double* times, int nt, const double* tau, int ntau,
@@ -154,47 +157,25 @@ int hipdrt_response_matrix_variant(hipdrt_ctx* ctx, const double* times, int nt,
         HIPDRT_REQUIRE(ny_ok(ny), "2 <= ny <= 6000");
     }
     hipStream_t st; TRY(enter(ctx, &st));
-    DevBuf dt, dtau, dst, dsa, dtr, da, dl;
-    TRY(upload(dt, times, (size_t)nt * sizeof(double), st));
-    TRY(upload(dtau, tau, (size_t)ntau * sizeof(double), st));
-    TRY(upload(dst, step_times, (size_t)nsteps * sizeof(double), st));
-    TRY(upload(dsa, step_sizes, (size_t)nsteps * sizeof(double), st));
-    if (variant == HIPDRT_RESPONSE_EXPDECAY) TRY(upload(dtr, tau_rise, (size_t)nsteps * sizeof(double), st));
-    const size_t ab = (size_t)nt * ntau * sizeof(double);
-    HIPDRT_CHECK(da.alloc(ab));
-    if (layered) HIPDRT_CHECK(dl.alloc(ab * nsteps));
-    launch_response_variant(st, dt.d(), nt, dtau.d(), ntau, dst.d(), dsa.d(), dtr.d(), nsteps, variant, epsilon, ny, da.d(),
-                            layered ? dl.d() : nullptr);
+    StepInputs in;
+    DevOuts outs;
+    double *da = nullptr, *dl = nullptr;
+    TRY(in.upload_all(st, times, nt, tau, ntau, step_times, step_sizes, nsteps,
+                      variant == HIPDRT_RESPONSE_EXPDECAY ? tau_rise : nullptr));
+    TRY(outs.want(a, (size_t)nt * ntau, da)); TRY(outs.want(layered, (size_t)nt * ntau * nsteps, dl));
+    launch_response_variant(st, in.times.d(), nt, in.col.d(), ntau, in.step_times.d(), in.step_sizes.d(), in.tau_rise.d(), nsteps,
+                            variant, epsilon, ny, da, dl);
     LAUNCH_OK();
-    HIPDRT_CHECK(hipMemcpyAsync(a, da.p, ab, hipMemcpyDeviceToHost, st));
-    if (layered) HIPDRT_CHECK(hipMemcpyAsync(layered, dl.p, ab * nsteps, hipMemcpyDeviceToHost, st));
-    HIPDRT_CHECK(hipStreamSynchronize(st));
-    return HIPDRT_OK;
+    return back_and_wait(outs, st);
 } HIPDRT_CATCH
 
-// lut6 = {log_wt_re, z_re, slope_re, log_wt_im, z_im, slope_im}
-static int build_lut6(hipStream_t st, DevBuf& lut6, int ngrid, const double* log_wt_re, const double* z_re,
-                      const double* log_wt_im, const double* z_im, bool z_on_device) {
-    const size_t gb = (size_t)ngrid * sizeof(double);
-    if (!lut6.p) HIPDRT_CHECK(lut6.alloc(6 * gb));
-    double* base = lut6.d();
-    const hipMemcpyKind zk = z_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    HIPDRT_CHECK(hipMemcpyAsync(base, log_wt_re, gb, hipMemcpyHostToDevice, st));
-    HIPDRT_CHECK(hipMemcpyAsync(base + 3 * (size_t)ngrid, log_wt_im, gb, hipMemcpyHostToDevice, st));
-    if (z_re) HIPDRT_CHECK(hipMemcpyAsync(base + ngrid, z_re, gb, zk, st));
-    if (z_im) HIPDRT_CHECK(hipMemcpyAsync(base + 4 * (size_t)ngrid, z_im, gb, zk, st));
-    launch_lookup_slopes(st, ngrid, base, base + ngrid, base + 2 * (size_t)ngrid);
-    launch_lookup_slopes(st, ngrid, base + 3 * (size_t)ngrid, base + 4 * (size_t)ngrid, base + 5 * (size_t)ngrid);
-    LAUNCH_OK();
-    return 0;
-}
-
+// the body of both impedance entry points.  to_host: a_re / a_im are host arrays (device twins here, copied back), else device memory
 static int impedance_matrix_common(hipdrt_ctx* ctx, int B, int freq_batched, const double* freq, int nf,
                                    const double* tau, int ntau, int mode, int toeplitz, double epsilon, int ngrid,
                                    const double* log_wt_re, const double* z_re, const double* log_wt_im,
-                                   const double* z_im, int ny, double* a_re_dev, double* a_im_dev, int repeat,
+                                   const double* z_im, int ny, double* a_re, double* a_im, bool to_host, int repeat,
                                    float* elapsed_ms) {
-    HIPDRT_REQUIRE(ctx && freq && tau && a_re_dev && a_im_dev, "NULL pointer");
+    HIPDRT_REQUIRE(ctx && freq && tau && a_re && a_im, "NULL pointer");
     HIPDRT_REQUIRE(B >= 1 && nf >= 1 && ntau >= 1, "B, nf, ntau >= 1");
     HIPDRT_REQUIRE(mode == HIPDRT_MODE_INTERP || mode == HIPDRT_MODE_TRAPZ, "mode");
     HIPDRT_REQUIRE(!(toeplitz && freq_batched), "Toeplitz shortcut needs one shared frequency grid");
@@ -204,19 +185,27 @@ static int impedance_matrix_common(hipdrt_ctx* ctx, int B, int freq_batched, con
                        "interp needs lookups with ngrid >= 2 that one workgroup's LDS holds (2 <= ngrid <= 3406)");
     else HIPDRT_REQUIRE(ny_ok(ny), "2 <= ny <= 6000");
     hipStream_t st; TRY(enter(ctx, &st));
-    DevBuf dfreq, dtau, lut6, cr;
+    DevBuf dfreq, dtau, lut6, scratch;
+    DevOuts outs;
+    double *dre = a_re, *dim = a_im;
+    if (to_host) { TRY(outs.want(a_re, (size_t)B * nf * ntau, dre)); TRY(outs.want(a_im, (size_t)B * nf * ntau, dim)); }
     TRY(upload(dfreq, freq, (size_t)(freq_batched ? B : 1) * nf * sizeof(double), st));
     TRY(upload(dtau, tau, (size_t)ntau * sizeof(double), st));
-    if (mode == HIPDRT_MODE_INTERP) TRY(build_lut6(st, lut6, ngrid, log_wt_re, z_re, log_wt_im, z_im, false));
-    HIPDRT_CHECK(cr.alloc(((size_t)(freq_batched ? B : 1) * nf + 2 * (size_t)(nf + ntau)) * sizeof(double)));
+    if (mode == HIPDRT_MODE_INTERP) {
+        TRY(stage_lut(st, lut6, ngrid, 2, 0, log_wt_re, z_re));
+        TRY(stage_lut(st, lut6, ngrid, 2, 1, log_wt_im, z_im));
+        launch_lut_slopes(st, lut6.d(), ngrid, 2);
+        LAUNCH_OK();
+    }
+    HIPDRT_CHECK(scratch.alloc(impedance_scratch_doubles(B, freq_batched, nf, ntau, mode, toeplitz) * sizeof(double)));
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (elapsed_ms) { HIPDRT_CHECK(hipEventCreate(&e0)); HIPDRT_CHECK(hipEventCreate(&e1)); HIPDRT_CHECK(hipEventRecord(e0, st)); }
     for (int r = 0; r < (repeat < 1 ? 1 : repeat); ++r)
         launch_impedance_matrix(st, B, freq_batched, dfreq.d(), nf, dtau.d(), ntau, mode, toeplitz, epsilon, ngrid,
-                                lut6.d(), ny, a_re_dev, a_im_dev, cr.d());
+                                lut6.d(), ny, dre, dim, scratch.d());
     LAUNCH_OK();
     if (elapsed_ms) { HIPDRT_CHECK(hipEventRecord(e1, st)); }
-    HIPDRT_CHECK(hipStreamSynchronize(st));
+    TRY(back_and_wait(outs, st));
     if (elapsed_ms) {
         HIPDRT_CHECK(hipEventElapsedTime(elapsed_ms, e0, e1));
         (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
@@ -230,7 +219,7 @@ int hipdrt_impedance_matrix_dev(hipdrt_ctx* ctx, int B, int freq_batched, const 
                                 const double* z_im, int ny, void* a_re_dev, void* a_im_dev, int repeat,
                                 float* elapsed_ms) try {
     return impedance_matrix_common(ctx, B, freq_batched, freq, nf, tau, ntau, mode, toeplitz, epsilon, ngrid,
-                                   log_wt_re, z_re, log_wt_im, z_im, ny, (double*)a_re_dev, (double*)a_im_dev, repeat,
+                                   log_wt_re, z_re, log_wt_im, z_im, ny, (double*)a_re_dev, (double*)a_im_dev, false, repeat,
                                    elapsed_ms);
 } HIPDRT_CATCH
 
@@ -238,17 +227,8 @@ int hipdrt_impedance_matrix(hipdrt_ctx* ctx, int B, int freq_batched, const doub
                             int ntau, int mode, int toeplitz, double epsilon, int ngrid, const double* log_wt_re,
                             const double* z_re, const double* log_wt_im, const double* z_im, int ny, double* a_re,
                             double* a_im) try {
-    HIPDRT_REQUIRE(ctx && a_re && a_im, "NULL pointer");
-    HIPDRT_REQUIRE(B >= 1 && nf >= 1 && ntau >= 1, "B, nf, ntau >= 1");
-    TRY(enter(ctx));
-    DevBuf dre, dim;
-    const size_t bytes = (size_t)B * nf * ntau * sizeof(double);
-    HIPDRT_CHECK(dre.alloc(bytes)); HIPDRT_CHECK(dim.alloc(bytes));
-    TRY(impedance_matrix_common(ctx, B, freq_batched, freq, nf, tau, ntau, mode, toeplitz, epsilon, ngrid, log_wt_re,
-                                z_re, log_wt_im, z_im, ny, dre.d(), dim.d(), 1, nullptr));
-    HIPDRT_CHECK(hipMemcpy(a_re, dre.p, bytes, hipMemcpyDeviceToHost));
-    HIPDRT_CHECK(hipMemcpy(a_im, dim.p, bytes, hipMemcpyDeviceToHost));
-    return HIPDRT_OK;
+    return impedance_matrix_common(ctx, B, freq_batched, freq, nf, tau, ntau, mode, toeplitz, epsilon, ngrid, log_wt_re,
+                                   z_re, log_wt_im, z_im, ny, a_re, a_im, true, 1, nullptr);
 } HIPDRT_CATCH
 
 int hipdrt_nonuniform_gaussian_filter1d(hipdrt_ctx* ctx, const double* y, int n, const double* sigma, const int* seg, int nseg,
@@ -264,7 +244,9 @@ int hipdrt_nonuniform_gaussian_filter1d(hipdrt_ctx* ctx, const double* y, int n,
         HIPDRT_REQUIRE(seg[s_] >= 0 && seg[s_] <= seg[s_ + 1] && seg[s_ + 1] <= n, "segment bounds");
         if (filtered[s_]) for (int i = seg[s_]; i < seg[s_ + 1]; ++i) seg_of[i] = s_;
     }
-    DevBuf dy, dsg, dso, dseg, dnodes, dnd, dw, dwo, drad, dout;
+    DevBuf dy, dsg, dso, dseg, dnodes, dnd, dw, dwo, drad;
+    DevOuts outs;
+    double* dout = nullptr;
     TRY(upload(dy, y, (size_t)n * sizeof(double), st));
     TRY(upload(dsg, sigma, (size_t)n * sizeof(double), st));
     TRY(upload(dso, seg_of.data(), (size_t)n * sizeof(int), st));
@@ -274,13 +256,10 @@ int hipdrt_nonuniform_gaussian_filter1d(hipdrt_ctx* ctx, const double* y, int n,
     TRY(upload(dw, weights, (size_t)nweights * sizeof(double), st));
     TRY(upload(dwo, woff, (size_t)nseg * K * sizeof(int), st));
     TRY(upload(drad, radius, (size_t)nseg * K * sizeof(int), st));
-    HIPDRT_CHECK(dout.alloc((size_t)n * sizeof(double)));
-    launch_nonuniform_gauss(st, dy.d(), n, dsg.d(), dso.i(), dseg.i(), dnodes.d(), K, dnd.d(), dw.d(), dwo.i(), drad.i(),
-                            dout.d());
+    TRY(outs.want(out, (size_t)n, dout));
+    launch_nonuniform_gauss(st, dy.d(), n, dsg.d(), dso.i(), dseg.i(), dnodes.d(), K, dnd.d(), dw.d(), dwo.i(), drad.i(), dout);
     LAUNCH_OK();
-    HIPDRT_CHECK(hipMemcpyAsync(out, dout.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPDRT_CHECK(hipStreamSynchronize(st));
-    return HIPDRT_OK;
+    return back_and_wait(outs, st);
 } HIPDRT_CATCH
 
 int hipdrt_penalty_matrices(hipdrt_ctx* ctx, const double* ln_tau, int n, double epsilon, int toeplitz, double* m0,
@@ -288,17 +267,14 @@ int hipdrt_penalty_matrices(hipdrt_ctx* ctx, const double* ln_tau, int n, double
     HIPDRT_REQUIRE(ctx && ln_tau && m0 && m1 && m2, "NULL pointer");
     HIPDRT_REQUIRE(n >= 1, "n >= 1");
     hipStream_t st; TRY(enter(ctx, &st));
-    DevBuf dl, d0, d1, d2;
-    const size_t bytes = (size_t)n * n * sizeof(double);
+    DevBuf dl;
+    DevOuts outs;
+    double *d0 = nullptr, *d1 = nullptr, *d2 = nullptr;
     TRY(upload(dl, ln_tau, (size_t)n * sizeof(double), st));
-    HIPDRT_CHECK(d0.alloc(bytes)); HIPDRT_CHECK(d1.alloc(bytes)); HIPDRT_CHECK(d2.alloc(bytes));
-    launch_penalty(st, dl.d(), n, epsilon, toeplitz, d0.d(), d1.d(), d2.d(), n, 0);
+    TRY(outs.want(m0, (size_t)n * n, d0)); TRY(outs.want(m1, (size_t)n * n, d1)); TRY(outs.want(m2, (size_t)n * n, d2));
+    launch_penalty(st, dl.d(), n, epsilon, toeplitz, d0, d1, d2, n, 0);
     LAUNCH_OK();
-    HIPDRT_CHECK(hipMemcpyAsync(m0, d0.p, bytes, hipMemcpyDeviceToHost, st));
-    HIPDRT_CHECK(hipMemcpyAsync(m1, d1.p, bytes, hipMemcpyDeviceToHost, st));
-    HIPDRT_CHECK(hipMemcpyAsync(m2, d2.p, bytes, hipMemcpyDeviceToHost, st));
-    HIPDRT_CHECK(hipStreamSynchronize(st));
-    return HIPDRT_OK;
+    return back_and_wait(outs, st);
 } HIPDRT_CATCH
 
 int hipdrt_eis_var_matrix(hipdrt_ctx* ctx, const double* freq, int nf, double vmm_epsilon, double reim_cor,
@@ -306,15 +282,14 @@ int hipdrt_eis_var_matrix(hipdrt_ctx* ctx, const double* freq, int nf, double vm
     HIPDRT_REQUIRE(ctx && freq && vmm, "NULL pointer");
     HIPDRT_REQUIRE(nf >= 1, "nf >= 1");
     hipStream_t st; TRY(enter(ctx, &st));
-    DevBuf df, dv;
-    const size_t bytes = (size_t)4 * nf * nf * sizeof(double);
+    DevBuf df;
+    DevOuts outs;
+    double* dv = nullptr;
     TRY(upload(df, freq, (size_t)nf * sizeof(double), st));
-    HIPDRT_CHECK(dv.alloc(bytes));
-    launch_eis_vmm(st, df.d(), nf, vmm_epsilon, reim_cor, uniform, dv.d());
+    TRY(outs.want(vmm, (size_t)4 * nf * nf, dv));
+    launch_eis_vmm(st, df.d(), nf, vmm_epsilon, reim_cor, uniform, dv);
     LAUNCH_OK();
-    HIPDRT_CHECK(hipMemcpyAsync(vmm, dv.p, bytes, hipMemcpyDeviceToHost, st));
-    HIPDRT_CHECK(hipStreamSynchronize(st));
-    return HIPDRT_OK;
+    return back_and_wait(outs, st);
 } HIPDRT_CATCH
 
 int hipdrt_qp_batch(hipdrt_ctx* ctx, int B, int n, int p_batched, const double* P, const double* q, int h_batched,
@@ -322,7 +297,8 @@ int hipdrt_qp_batch(hipdrt_ctx* ctx, int B, int n, int p_batched, const double* 
     HIPDRT_REQUIRE(ctx && P && q && h && x && status, "NULL pointer");
     HIPDRT_REQUIRE(B >= 1 && n >= 1 && n <= 4096, "B >= 1, 1 <= n <= 4096");
     hipStream_t st; TRY(enter(ctx, &st));
-    DevBuf dP, dq, dh, dL, dx, dit, dpc, dst, dstate, dPpk, dgs;
+    DevBuf dP, dq, dh, dL, dstate, dPpk, dgs;
+    DevOuts outs;
     const int ldl = (int)qp_scratch_ld(n);
     const int G = qp_group_size(B, n, ctx->qp_force_group);           // 0: one workgroup per problem; >= 1: that many workgroups per problem
     // device copy of P with an even leading dimension (16-byte row-pair loads in the kernels), pad column zeroed
@@ -335,15 +311,13 @@ int hipdrt_qp_batch(hipdrt_ctx* ctx, int B, int n, int p_batched, const double* 
     TRY(upload(dq, q, (size_t)B * n * sizeof(double), st));
     TRY(upload(dh, h, (size_t)(h_batched ? B : 1) * n * sizeof(double), st));
     HIPDRT_CHECK(dL.alloc((size_t)B * qp_scratch_doubles(n, G) * sizeof(double)));
-    HIPDRT_CHECK(dx.alloc((size_t)B * n * sizeof(double)));
-    HIPDRT_CHECK(dit.alloc((size_t)B * sizeof(int)));
-    HIPDRT_CHECK(dpc.alloc((size_t)B * sizeof(double)));
-    HIPDRT_CHECK(dst.alloc((size_t)B * sizeof(int)));
     QpArgs a{};
+    // the kernel writes iteration counts and costs whether or not the caller wants them back
+    TRY(outs.want(x, (size_t)B * n, a.x)); TRY(outs.want(iters, (size_t)B, a.iters, true));
+    TRY(outs.want(pcost, (size_t)B, a.pcost, true)); TRY(outs.want(status, (size_t)B, a.status));
     a.B = B; a.n = n; a.P = dP.d(); a.p_stride = p_batched ? (long long)n * ldp : 0; a.ldp = ldp;
     a.q = dq.d(); a.h = dh.d(); a.h_stride = h_batched ? n : 0;
     a.L = dL.d(); a.ldl = ldl; a.l_stride = (long long)qp_scratch_doubles(n, G);
-    a.x = dx.d(); a.iters = dit.i(); a.pcost = dpc.d(); a.status = dst.i();
     a.active = nullptr; a.iters_accum = nullptr;
     a.G = G;
     a.waves = ctx->qp_waves;
@@ -358,12 +332,7 @@ int hipdrt_qp_batch(hipdrt_ctx* ctx, int B, int n, int p_batched, const double* 
     a.state = dstate.d(); a.state_ld = qp_state_ld(n); a.state_stride = (long long)qp_state_doubles(n);
     a.opts = opts ? *opts : default_qp_opts();
     TRY(launch_qp(st, a));
-    HIPDRT_CHECK(hipMemcpyAsync(x, dx.p, (size_t)B * n * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (iters) HIPDRT_CHECK(hipMemcpyAsync(iters, dit.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (pcost) HIPDRT_CHECK(hipMemcpyAsync(pcost, dpc.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPDRT_CHECK(hipMemcpyAsync(status, dst.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPDRT_CHECK(hipStreamSynchronize(st));
-    return HIPDRT_OK;
+    return back_and_wait(outs, st);
 } HIPDRT_CATCH
 
 int hipdrt_weighted_gram(hipdrt_ctx* ctx, int B, int m, int n, const double* A, const double* w, const double* b,
@@ -371,28 +340,25 @@ int hipdrt_weighted_gram(hipdrt_ctx* ctx, int B, int m, int n, const double* A, 
     HIPDRT_REQUIRE(ctx && A && w && b && P && q, "NULL pointer");
     HIPDRT_REQUIRE(B >= 1 && m >= 1 && n >= 1, "B, m, n >= 1");
     hipStream_t st; TRY(enter(ctx, &st));
-    DevBuf dA, dw, db, dl2, dl1, dP, dq;
+    DevBuf dA, dw, db, dl2, dl1;
+    DevOuts outs;
     TRY(upload(dA, A, (size_t)m * n * sizeof(double), st));
     TRY(upload(dw, w, (size_t)B * m * sizeof(double), st));
     TRY(upload(db, b, (size_t)B * m * sizeof(double), st));
     if (l2) TRY(upload(dl2, l2, (size_t)(l2_batched ? B : 1) * n * n * sizeof(double), st));
     if (l1) TRY(upload(dl1, l1, (size_t)n * sizeof(double), st));
-    HIPDRT_CHECK(dP.alloc((size_t)B * n * n * sizeof(double)));
-    HIPDRT_CHECK(dq.alloc((size_t)B * n * sizeof(double)));
     // one shared A, every problem, row-major P only; L2 as given (none: l2 = NULL)
     PqArgs pq{};
+    TRY(outs.want(P, (size_t)B * n * n, pq.P)); TRY(outs.want(q, (size_t)B * n, pq.q));
     pq.B = B; pq.m = m; pq.n = n; pq.A = dA.d(); pq.lda = n; pq.w = dw.d();
-    pq.P = dP.d(); pq.ldp = n; pq.p_stride = (long long)n * n;
-    pq.y = db.d(); pq.l1 = l1 ? dl1.d() : nullptr; pq.q = dq.d();
+    pq.ldp = n; pq.p_stride = (long long)n * n;
+    pq.y = db.d(); pq.l1 = l1 ? dl1.d() : nullptr;
     GramL2 g{};
     g.l2 = l2 ? dl2.d() : nullptr; g.l2_stride = l2_batched ? (long long)n * n : 0; g.ldl2 = n;
     launch_gram_l2(st, pq, g);
     launch_qvec(st, pq);
     LAUNCH_OK();
-    HIPDRT_CHECK(hipMemcpyAsync(P, dP.p, (size_t)B * n * n * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPDRT_CHECK(hipMemcpyAsync(q, dq.p, (size_t)B * n * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPDRT_CHECK(hipStreamSynchronize(st));
-    return HIPDRT_OK;
+    return back_and_wait(outs, st);
 } HIPDRT_CATCH
 
 int hipdrt_func_eval_matrix(hipdrt_ctx* ctx, const double* basis_grid, int nb, const double* eval_grid, int ne, double epsilon,
@@ -401,14 +367,14 @@ int hipdrt_func_eval_matrix(hipdrt_ctx* ctx, const double* basis_grid, int nb, c
     HIPDRT_REQUIRE(nb >= 1 && ne >= 1, "nb, ne >= 1");
     HIPDRT_REQUIRE(order >= 0 && order <= 2, "order must be 0, 1 or 2");
     hipStream_t st; TRY(enter(ctx, &st));
-    DevBuf db, de, dout;
+    DevBuf db, de;
+    DevOuts outs;
+    double* dout = nullptr;
     TRY(upload(db, basis_grid, (size_t)nb * sizeof(double), st));
     TRY(upload(de, eval_grid, (size_t)ne * sizeof(double), st));
-    HIPDRT_CHECK(dout.alloc((size_t)ne * nb * sizeof(double)));
-    TRY(func_eval_dev(st, db.d(), nb, de.d(), ne, epsilon, order, 1.0, dout.d(), nb));
-    HIPDRT_CHECK(hipMemcpyAsync(out, dout.p, (size_t)ne * nb * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPDRT_CHECK(hipStreamSynchronize(st));
-    return HIPDRT_OK;
+    TRY(outs.want(out, (size_t)ne * nb, dout));
+    TRY(func_eval_dev(st, db.d(), nb, de.d(), ne, epsilon, order, 1.0, dout, nb));
+    return back_and_wait(outs, st);
 } HIPDRT_CATCH
 
 }  // extern "C"

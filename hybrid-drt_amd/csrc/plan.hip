@@ -119,15 +119,11 @@ void hipdrt_default_fit_opts(hipdrt_fit_opts* o) {
 static int plan_build_matrices(hipdrt_plan* p, bool build_lookup) {
     hipStream_t st = p->ctx->stream;
     if (p->mode == HIPDRT_MODE_INTERP && build_lookup) {
-        double* base = p->lut6.d();
-        launch_lookup(st, p->eps, p->ngrid, p->ny, p->wt_re.d(), p->wt_im.d(), base + p->ngrid, base + 4 * (size_t)p->ngrid);
+        launch_lookup(st, p->eps, p->ngrid, p->ny, p->wt_re.d(), p->wt_im.d(), lut_part(p->lut6.d(), p->ngrid, 0).f,
+                      lut_part(p->lut6.d(), p->ngrid, 1).f);
         LAUNCH_OK();
     }
-    if (p->mode == HIPDRT_MODE_INTERP) {
-        double* base = p->lut6.d();
-        launch_lookup_slopes(st, p->ngrid, base, base + p->ngrid, base + 2 * (size_t)p->ngrid);
-        launch_lookup_slopes(st, p->ngrid, base + 3 * (size_t)p->ngrid, base + 4 * (size_t)p->ngrid, base + 5 * (size_t)p->ngrid);
-    }
+    if (p->mode == HIPDRT_MODE_INTERP) launch_lut_slopes(st, p->lut6.d(), p->ngrid, 2);
     launch_impedance_matrix(st, 1, 0, p->freq.d(), p->nf, p->tau.d(), p->ntau, p->mode, p->toeplitz_a, p->eps, p->ngrid,
                             p->lut6.d(), p->ny, p->a_re.d(), p->a_im.d(), p->cr.d());
     LAUNCH_OK();
@@ -220,13 +216,12 @@ int hipdrt_plan_create(hipdrt_ctx* ctx, const double* freq, int nf, const double
     const size_t gb = (size_t)(ngrid > 0 ? ngrid : 1) * sizeof(double);
     if (mode == HIPDRT_MODE_INTERP) {
         TRY(upload(p->wt_re, wt_re, gb, st)); TRY(upload(p->wt_im, wt_im, gb, st));
-        HIPDRT_CHECK(p->lut6.alloc(6 * gb));
-        HIPDRT_CHECK(hipMemcpyAsync(p->lut6.d(), log_wt_re, gb, hipMemcpyHostToDevice, st));
-        HIPDRT_CHECK(hipMemcpyAsync(p->lut6.d() + 3 * (size_t)ngrid, log_wt_im, gb, hipMemcpyHostToDevice, st));
+        TRY(stage_lut(st, p->lut6, ngrid, 2, 0, log_wt_re, nullptr));
+        TRY(stage_lut(st, p->lut6, ngrid, 2, 1, log_wt_im, nullptr));
     }
     HIPDRT_CHECK(p->a_re.alloc((size_t)nf * ntau * sizeof(double)));
     HIPDRT_CHECK(p->a_im.alloc((size_t)nf * ntau * sizeof(double)));
-    HIPDRT_CHECK(p->cr.alloc(2 * (size_t)(nf + ntau) * sizeof(double)));
+    HIPDRT_CHECK(p->cr.alloc(impedance_scratch_doubles(1, 0, nf, ntau, mode, toeplitz_a) * sizeof(double)));
     HIPDRT_CHECK(p->rm.alloc((size_t)m * p->ldrm * sizeof(double)));
     HIPDRT_CHECK(hipMemsetAsync(p->rm.p, 0, p->rm.bytes, st));
     for (int k = 0; k < 3; ++k) {
@@ -379,8 +374,8 @@ int hipdrt_plan_get(hipdrt_plan* p, const char* which, double* out, long long co
     hipStream_t st; TRY(enter(p->ctx, &st));
     const std::string w = which;
     const double* src = nullptr; int rows = 0, cols = 0, ld = 0;
-    if (w == "lut_z_re") { src = p->lut6.d() + p->ngrid; rows = 1; cols = ld = p->ngrid; }
-    else if (w == "lut_z_im") { src = p->lut6.d() + 4 * (size_t)p->ngrid; rows = 1; cols = ld = p->ngrid; }
+    if (w == "lut_z_re") { src = lut_part(p->lut6.d(), p->ngrid, 0).f; rows = 1; cols = ld = p->ngrid; }
+    else if (w == "lut_z_im") { src = lut_part(p->lut6.d(), p->ngrid, 1).f; rows = 1; cols = ld = p->ngrid; }
     else if (w == "a_re") { src = p->a_re.d(); rows = p->nf; cols = ld = p->ntau; }
     else if (w == "a_im") { src = p->a_im.d(); rows = p->nf; cols = ld = p->ntau; }
     else if (w == "rm") { src = p->rm.d(); rows = p->m; cols = p->n; ld = p->ldrm; }
@@ -410,9 +405,8 @@ int hipdrt_plan_set_lookup(hipdrt_plan* p, const double* z_re, const double* z_i
     HIPDRT_REQUIRE(p && z_re && z_im, "NULL pointer");
     HIPDRT_REQUIRE(p->mode == HIPDRT_MODE_INTERP, "plan is not in interp mode");
     hipStream_t st; TRY(enter(p->ctx, &st));
-    const size_t gb = (size_t)p->ngrid * sizeof(double);
-    HIPDRT_CHECK(hipMemcpyAsync(p->lut6.d() + p->ngrid, z_re, gb, hipMemcpyHostToDevice, st));
-    HIPDRT_CHECK(hipMemcpyAsync(p->lut6.d() + 4 * (size_t)p->ngrid, z_im, gb, hipMemcpyHostToDevice, st));
+    TRY(stage_lut(st, p->lut6, p->ngrid, 2, 0, nullptr, z_re));
+    TRY(stage_lut(st, p->lut6, p->ngrid, 2, 1, nullptr, z_im));
     TRY(plan_build_matrices(p, false));
     HIPDRT_CHECK(hipStreamSynchronize(st));
     return HIPDRT_OK;

@@ -301,7 +301,7 @@ int hipdrt_plan_predict_z(hipdrt_plan* p, const double* freq, int nf, int includ
     HIPDRT_CHECK(dzr.alloc((size_t)B * nf * sizeof(double))); HIPDRT_CHECK(dzi.alloc((size_t)B * nf * sizeof(double)));
     if (include_mask & 1) {
         HIPDRT_CHECK(dA.alloc((size_t)2 * nf * ntau * sizeof(double)));
-        HIPDRT_CHECK(cr.alloc(((size_t)nf + 2 * (size_t)(nf + ntau)) * sizeof(double)));
+        HIPDRT_CHECK(cr.alloc(impedance_scratch_doubles(1, 0, nf, ntau, p->mode, 0) * sizeof(double)));
         HIPDRT_CHECK(dy.alloc((size_t)B * 2 * nf * sizeof(double)));
     }
     PredictTimer tm(p->ctx, st);

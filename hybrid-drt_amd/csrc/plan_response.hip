@@ -205,12 +205,7 @@ int hipdrt_plan_predict_response(hipdrt_plan* p, const hipdrt_response_args* q, 
     a.out = dout.d();
     if (want_drt) {
         TRY(upload(dtau, q->basis_tau, (size_t)ntau * sizeof(double), st));
-        if (q->mode == HIPDRT_MODE_INTERP) {
-            const size_t gb = (size_t)q->ngrid * sizeof(double);
-            HIPDRT_CHECK(lut3.alloc(3 * gb));
-            HIPDRT_CHECK(hipMemcpyAsync(lut3.d(), q->log_td, gb, hipMemcpyHostToDevice, st));
-            HIPDRT_CHECK(hipMemcpyAsync(lut3.d() + q->ngrid, q->v, gb, hipMemcpyHostToDevice, st));
-        }
+        if (q->mode == HIPDRT_MODE_INTERP) TRY(stage_lut(st, lut3, q->ngrid, 1, 0, q->log_td, q->v));
         HIPDRT_CHECK(dsum.alloc(tb * ntau));
         HIPDRT_CHECK(dU.alloc(tb * ntau * S));
     }
@@ -223,7 +218,7 @@ int hipdrt_plan_predict_response(hipdrt_plan* p, const hipdrt_response_args* q, 
     PredictTimer tm(p->ctx, st);
     if (want_drt) {
         // the unit-step layers, once for the batch: the members' step sizes enter in the assembly
-        if (q->mode == HIPDRT_MODE_INTERP) launch_lookup_slopes(st, q->ngrid, lut3.d(), lut3.d() + q->ngrid, lut3.d() + 2 * (size_t)q->ngrid);
+        if (q->mode == HIPDRT_MODE_INTERP) launch_lut_slopes(st, lut3.d(), q->ngrid, 1);
         launch_response_matrix(st, dt.d(), nt, dtau.d(), ntau, dst.d(), dones.d(), S, q->mode, p->basis_eps, q->ngrid, lut3.d(),
                                q->ny, dsum.d(), dU.d());
         LAUNCH_OK();

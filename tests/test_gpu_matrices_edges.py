@@ -220,6 +220,40 @@ def test_trapz_response_and_expdecay(ctx, ny, nt, ntau, nsteps):
     check("response_pot", a, ref, scale=float(np.abs(ref_lay).max()))
 
 
+@pytest.mark.parametrize("nt,ntau,nsteps", [(5, 3, 3), (5, 257, 3)])
+def test_interp_response_at_the_step_rule(ctx, nt, ntau, nsteps):
+    """the interp build with more than one step, a sample before the first step and one exactly on a step (t > t_k: that sample
+    belongs to the layer before); 257 columns: one past a 256-column block"""
+    table, tau = mu.response_table(1999), mu.tau_grid(ntau)
+    times, st, sz, _ = mu.response_inputs(nt, nsteps)
+    a, lay = ctx.response_matrix(times, tau, st, sz, 1.0, INTERP, lookup=table)
+    ref, ref_lay = mu.response_interp(times, tau, st, sz, table)
+    zero = ~(times[None, :] > st[:, None])
+    assert zero.any() and (times[None, :] == st[:, None]).any() and not lay[zero].any()
+    assert same(lay == 0, np.asarray(ref_lay, dtype=float) == 0)              # and nowhere else
+    check("response_interp", lay, ref_lay)
+    check("response_interp", a, ref, scale=float(np.abs(ref_lay).max()))
+
+
+def test_layered_false_agrees_with_layered_true(ctx):
+    """the sum is the same matrix whether or not the layers are kept (the shared step loop's null-pointer branch)"""
+    from hipdrt import _ffi
+    nt, ntau, nsteps = 5, 3, 3
+    tau, table = mu.tau_grid(ntau), mu.response_table(1999)
+    times, st, sz, tr = mu.response_inputs(nt, nsteps)
+    eps = mu.eps_of(65)
+    builds = {
+        "interp": lambda layered: ctx.response_matrix(times, tau, st, sz, 1.0, INTERP, lookup=table, layered=layered),
+        "trapz": lambda layered: ctx.response_matrix(times, tau, st, sz, eps, TRAPZ, ny=65, layered=layered),
+        "expdecay": lambda layered: ctx.response_matrix_variant(times, tau, st, sz, _ffi.RESPONSE_EXPDECAY, tr, eps, 65, layered=layered),
+        "pot": lambda layered: ctx.response_matrix_variant(times, tau, st, sz, _ffi.RESPONSE_POT, layered=layered),
+    }
+    for name, build in builds.items():
+        (a, lay), (b, none) = build(True), build(False)
+        assert none is None and lay.shape == (nsteps, nt, ntau), name
+        assert a.any() and same(a, b), name
+
+
 def test_trapz_points_beyond_the_maximum_are_refused(ctx):
     from hipdrt import _ffi
     ny, one = mu.NY_MAX + 1, np.array([1.0])
