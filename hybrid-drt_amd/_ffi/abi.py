@@ -126,6 +126,22 @@ class CandidatesOut(C.Structure):
                 ("status", _ip)]
 
 
+class LmlIn(C.Structure):
+    """hipdrt_lml_in (include/hipdrt.h)"""
+    _fields_ = [("step", C.c_int), ("x", _dp), ("rho", _dp), ("s", _dp), ("dop_rho", _dp), ("weights", _dp),
+                ("override_hypers", C.c_int), ("l2_lambda_0", C.c_double), ("derivative_weights", C.c_double * 3),
+                ("dop_l2_lambda_0", C.c_double), ("dop_derivative_weights", C.c_double * 3)]
+
+
+class LmlOut(C.Structure):
+    """hipdrt_lml_out (include/hipdrt.h)"""
+    _fields_ = [("logdet_p", _dp), ("logdet_prior", _dp), ("wy2", _dp), ("fit2", _dp), ("cross", _dp), ("slw", _dp), ("xox", _dp),
+                ("l1x", _dp), ("status", _ip)]
+
+
+LML_TERMS = ("logdet_p", "logdet_prior", "wy2", "fit2", "cross", "slw", "xox", "l1x")
+
+
 class DebugPeakResolveArgs(C.Structure):
     """hipdrt_debug_peak_resolve_args (include/hipdrt_debug.h)"""
     _fields_ = [("B", C.c_int), ("nfind", C.c_int), ("nb", C.c_int), ("nout", C.c_int), ("copies", C.c_int), ("source", C.c_int),
@@ -357,6 +373,9 @@ SIGNATURES = {
     "hipdrt_plan_integrate_drt": [_vp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _ip, _ip, C.c_int, _dp, _ip],
     "hipdrt_debug_peak_resolve": [_vp, C.POINTER(DebugPeakResolveArgs)],
     "hipdrt_plan_score_candidates": [_vp, C.POINTER(CandidatesIn), C.POINTER(CandidatesOut)],
+    "hipdrt_default_lml_in": [C.POINTER(LmlIn)],
+    "hipdrt_plan_lml_terms": [_vp, C.POINTER(LmlIn), C.POINTER(LmlOut)],
+    "hipdrt_debug_logdet": [_vp, C.c_int, C.c_int, _dp, _dp, _ip],
     "hipdrt_debug_candidate_llh": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp],
     "hipdrt_debug_candidate_form": [_vp, C.c_int],
     "hipdrt_debug_posterior": [_vp, C.POINTER(DebugPosteriorArgs)],
@@ -434,7 +453,7 @@ SIGNATURES = {
                              _dp, _dp, _dp, _dp, _ip, _ip],
 }
 _RESTYPES = {"hipdrt_last_error": C.c_char_p, "hipdrt_stream": C.c_void_p, "hipdrt_default_fit_opts": None,
-             "hipdrt_default_kk_opts": None, "hipdrt_peak_opts_default": None, "hipdrt_peak_prob_opts_default": None,
+             "hipdrt_default_kk_opts": None, "hipdrt_default_lml_in": None, "hipdrt_peak_opts_default": None, "hipdrt_peak_prob_opts_default": None,
              "hipdrt_peak_resolve_opts_default": None, "hipdrt_pfrt_opts_default": None}
 
 _lib = None

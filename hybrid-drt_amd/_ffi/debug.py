@@ -545,6 +545,17 @@ class DebugHooks:
         _check(self._lib.hipdrt_debug_pack_p(self._h, B, n, _p(P), ldp, _p(Ppk)))
         return Ppk
 
+    def debug_logdet(self, P):
+        """tests: the log-determinant kernel of Plan.lml_terms alone on symmetric matrices P (B, n, n) (hipdrt_debug_logdet,
+        include/hipdrt_debug.h) -> (logdet (B,), status (B,)): 2 sum log L_ii, or NaN and -1 where P is not positive definite"""
+        P = _f64(P)
+        if P.ndim != 3 or P.shape[1] != P.shape[2]:
+            raise ValueError("P: [B][n][n]")
+        B, n = P.shape[:2]
+        logdet, status = np.full(B, 7e77), np.full(B, -77, dtype=np.int32)
+        _check(self._lib.hipdrt_debug_logdet(self._h, B, n, _p(P), _p(logdet), _pi(status)))
+        return logdet, status
+
     def qp_profile(self, reset=True):
         buf = (C.c_ulonglong * 64)()        # 0..47 the QP kernel's phases, 48..63 hyper_kernel's (PROFILE=1 builds)
         _check(self._lib.hipdrt_qp_profile(self._h, buf, 64, int(reset)))

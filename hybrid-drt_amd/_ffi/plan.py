@@ -108,6 +108,40 @@ class Plan:
             _check(self._lib.hipdrt_plan_obs_llh_terms_w(self._h, 3, float(weights), _p(rss), _p(slw)))
         return rss, slw
 
+    def lml_terms(self, x=None, rho=None, s_vectors=None, dop_rho=None, step=None, weights=None, hypers=None, want=None):
+        """hipdrt_plan_lml_terms for the fitted batch: the eight terms of DRT.evaluate_lml per spectrum -> dict of logdet_p,
+        logdet_prior, wy2, fit2, cross, slw, xox, l1x and status, each (B,).  State: x (B, n), rho (B, 3), s_vectors (B, 3, n) and,
+        for a plan with a DOP block, dop_rho (B, 3) together; or step = a recorded step; or neither: the live fit.  weights (B, m):
+        None = the fit's est_weights.  hypers: None = the plan's own, else a dict with l2_lambda_0, derivative_weights and, for a
+        DOP plan, dop_l2_lambda_0, dop_derivative_weights.  want: the terms to form and download (None: all); status always comes."""
+        B, n, m = self.B, self.n, self.m
+        lib = self._lib
+        b = Bound(LmlIn())
+        i = b.c
+        lib.hipdrt_default_lml_in(C.byref(i))
+        i.step = -1 if step is None else int(step)
+        if step is not None and i.step < 0:
+            raise ValueError("step must be >= 0")
+        b.array("x", x, (B, n)); b.array("rho", rho, (B, 3)); b.array("s", s_vectors, (B, 3, n)); b.array("dop_rho", dop_rho, (B, 3))
+        b.array("weights", weights, (B, m))
+        if hypers is not None:
+            i.override_hypers = 1
+            i.l2_lambda_0 = float(hypers["l2_lambda_0"])
+            for k, v in enumerate(np.broadcast_to(np.asarray(hypers["derivative_weights"], dtype=float), (3,))):
+                i.derivative_weights[k] = float(v)
+            if hypers.get("dop_l2_lambda_0") is not None:
+                i.dop_l2_lambda_0 = float(hypers["dop_l2_lambda_0"])
+                for k, v in enumerate(np.broadcast_to(np.asarray(hypers["dop_derivative_weights"], dtype=float), (3,))):
+                    i.dop_derivative_weights[k] = float(v)
+        out = {k: np.full(B, 7e77) for k in LML_TERMS if want is None or k in want}
+        out["status"] = np.full(B, -77, dtype=np.int32)
+        u = LmlOut()
+        for k in LML_TERMS:
+            setattr(u, k, _p(out.get(k)))
+        u.status = _pi(out["status"])
+        _check(lib.hipdrt_plan_lml_terms(self._h, C.byref(i), C.byref(u)))
+        return out
+
     def set_state(self, x=None, rho=None, s=None, weights=None, dop_rho=None):
         arrs = [None if a is None else _f64(a) for a in (x, rho, s, weights)]
         _check(self._lib.hipdrt_plan_set_state(self._h, *[None if a is None else _p(a) for a in arrs]))

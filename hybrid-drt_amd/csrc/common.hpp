@@ -579,6 +579,22 @@ struct CandPeakArgs {
 };
 void launch_cand_compact(hipStream_t st, const CandPeakArgs& a);
 
+// lml.hip: the sums of the log marginal likelihood (qphb.py:1279-1344), one workgroup per spectrum (all pointers device memory; an
+// output may be null).  With r = rm_b x_b: wy2 = |w y|^2, fit2 = |w r|^2, cross = sum w^2 r y, slw = sum log w, xox = x' Omega x
+// for the Omega that launch_gram_l2 forms from `g` (the lower triangle of every M_k, mirrored), l1x = l1' x.
+struct LmlSumsArgs {
+    int m, n, ldrm;
+    const double* rm; long long rm_stride;   // [m][ldrm]; doubles between consecutive spectra (0 = shared)
+    const double *rv, *w;                    // [B][m]
+    const double* x;                         // [B][n]
+    GramL2 g;                                // mk, ldm, s, rho, dfac, ns and the DOP block; l2 is not read
+    const double* l1;                        // [n] or null (l1x = 0)
+    const int* fit_status;                   // [B] or null: a negative status gives NaN in every sum
+    double *wy2, *fit2, *cross, *slw, *xox, *l1x;   // [B]
+};
+size_t lml_sums_lds_bytes(int n, int m);
+int launch_lml_sums(hipStream_t st, const LmlSumsArgs& a, int B);
+
 // qp.hip
 struct QpArgs {
     int B, n;
@@ -622,6 +638,10 @@ size_t qp_gsync_ints();
 int launch_dist_var(hipStream_t st, int B, int n, const double* Ppk, long long ppk_stride, const double* Bex, int nex,
                     double* L, long long l_stride, double* out, long long out_stride, int* status);
 size_t dist_var_scratch_doubles(int n, int nex);
+// logdet[b] = 2 sum log diag chol(M_b) of B packed matrices, status[b] = -1 and NaN where M_b is not positive definite
+// (qp_resident.hpp: logdet_kernel_resident); L: dist_var_scratch_doubles(n, 0) doubles of scratch per matrix
+int launch_logdet(hipStream_t st, int B, int n, const double* Ppk, long long ppk_stride, double* L, long long l_stride,
+                  double* logdet, int* status);
 void launch_rows_outer(hipStream_t st, const double* Y, int nch, int ncol, int nex, int nrow, double scale, double* out, int ld);
 void launch_pack_rows(hipStream_t st, int nrow, int ncol, int col_offset, const double* M, int ldm, int ntile_rows,
                       double* tiles, int nchp);

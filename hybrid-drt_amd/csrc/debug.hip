@@ -132,6 +132,27 @@ int hipdrt_debug_pack_p(hipdrt_ctx* ctx, int B, int n, const double* P, int ldp,
     return HIPDRT_OK;
 } HIPDRT_CATCH
 
+int hipdrt_debug_logdet(hipdrt_ctx* ctx, int B, int n, const double* P, double* logdet, int* status) try {
+    HIPDRT_REQUIRE(ctx && P && logdet && status, "NULL pointer");
+    HIPDRT_REQUIRE(B >= 1 && B <= 4096 && n >= 1 && n <= 4096, "1 <= B <= 4096, 1 <= n <= 4096");
+    hipStream_t st; TRY(enter(ctx, &st));
+    const size_t ppk = qp_ppk_doubles(n);
+    DevBuf dP, dPpk, scratch, dld, dst;
+    TRY(upload(dP, P, (size_t)B * n * n * sizeof(double), st));
+    // (tiles above the diagonal and tile rows of pure padding are neither written by the packing nor read by the factorisation)
+    HIPDRT_CHECK(dPpk.alloc((size_t)B * ppk * sizeof(double)));
+    HIPDRT_CHECK(hipMemsetAsync(dPpk.p, 0, (size_t)B * ppk * sizeof(double), st));
+    HIPDRT_CHECK(dld.alloc((size_t)B * sizeof(double))); HIPDRT_CHECK(dst.alloc((size_t)B * sizeof(int)));
+    launch_pack_p(st, B, n, dP.d(), n, dPpk.d());
+    LAUNCH_OK();
+    TRY(logdet_dev(st, B, n, dPpk.d(), (long long)ppk, scratch, dld.d(), dst.i()));
+    LAUNCH_OK();
+    HIPDRT_CHECK(hipMemcpyAsync(logdet, dld.p, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipMemcpyAsync(status, dst.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
 // test hook (include/hipdrt_debug.h): launch_hyper as the fit loop calls it, on host arrays.  Every extent a kernel derives an
 // address from is checked here.  In/out arrays live on the device between two borders of marker bytes (Guarded).
 int hipdrt_debug_hyper_form(hipdrt_ctx* ctx, int n, int m, int ns, int toeplitz, int outlier, int* form, long long* lds_bytes) try {

@@ -141,6 +141,19 @@ HIPDRT_HD inline LlhLds llh_lds(void* sm, int n, int m) {
     return l;
 }
 
+// ---- lml.hip ----
+// lml_sums_kernel: x [n], sqrt(s_k) x of the order at hand [n], rm @ x [m]
+struct LmlLds { double *xs, *vs, *yh; size_t bytes; };
+HIPDRT_HD inline LmlLds lml_lds(void* sm, int n, int m) {
+    LdsCarver c = lds_carver(sm);
+    LmlLds l;
+    l.xs = c.take<double>((size_t)n);
+    l.vs = c.take<double>((size_t)n);
+    l.yh = c.take<double>((size_t)m);
+    l.bytes = c.off;
+    return l;
+}
+
 // ---- kk.hip ----
 // kk_kernel: residuals [nf each], the sort buffer [p2 = kk_p2(nf)], the mask [nf ints; the doubles behind it start on the next
 // even count], and for stage A x [n] and the prediction [m = 2 nf]

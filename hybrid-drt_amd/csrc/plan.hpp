@@ -246,7 +246,9 @@ namespace hipdrt {
 int make_view(hipdrt_plan* p, hipdrt_subfit& sf, int idx, int b0, int nb);
 int plan_hist_reserve(hipdrt_plan* p, int rows);
 // plan_fit.hip: L2 part of P in hyper-parameter form for the plan's current state
-GramL2 plan_l2(const hipdrt_plan* p, double l2_lambda_0, const double* derivative_weights, double dop_l2_lambda_0);
+// (dop_derivative_weights null: the plan's own)
+GramL2 plan_l2(const hipdrt_plan* p, double l2_lambda_0, const double* derivative_weights, double dop_l2_lambda_0,
+               const double* dop_derivative_weights = nullptr);
 
 // ---- Kramers-Kronig screening: plan_post.hip (hipdrt_plan_kk_screen) and its stage-B test hook in debug.hip --------------------
 int kk_check_opts(const hipdrt_kk_opts& o);
@@ -294,6 +296,9 @@ struct PosteriorChain {
     int nex() const { return (neval + 15) / 16; }
 };
 int posterior_var_dev(hipStream_t st, const PosteriorChain& c, DevBuf& scratch);
+// logdet[nb], status[nb] (device) of nb packed matrices, through launch_logdet in chunks of at most 256 with one factor scratch per
+// matrix of a chunk; `scratch` is grown when it is too small and otherwise reused, so that a second call costs no allocation
+int logdet_dev(hipStream_t st, int nb, int n, const double* ppk, long long pstr, DevBuf& scratch, double* logdet, int* status);
 // scale * Y Y' of the rows Y = rows L^-T that the chain left behind ONE spectrum's factor (scratch_b: that spectrum's scratch)
 // -> dcov[neval][neval] on the device
 void posterior_cov_dev(hipStream_t st, const double* scratch_b, int n, int neval, double scale, double* dcov);

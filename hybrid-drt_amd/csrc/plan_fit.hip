@@ -10,7 +10,8 @@
 
 namespace hipdrt {
 // L2 part of P in hyper-parameter form (calculate_qp_l2_matrix, qphb.py:53-120) for the plan's current state
-GramL2 plan_l2(const hipdrt_plan* p, double l2_lambda_0, const double* derivative_weights, double dop_l2_lambda_0) {
+GramL2 plan_l2(const hipdrt_plan* p, double l2_lambda_0, const double* derivative_weights, double dop_l2_lambda_0,
+               const double* dop_derivative_weights) {
     GramL2 g{};
     g.l2 = nullptr; g.ldm = p->ldm; g.ns = p->ns; g.use_rho = 1;
     g.sym = p->prepared ? 0 : p->toeplitz_m;      // caller-supplied matrices are not assumed bitwise symmetric
@@ -21,7 +22,8 @@ GramL2 plan_l2(const hipdrt_plan* p, double l2_lambda_0, const double* derivativ
     g.s = p->s.d(); g.rho = p->rho.d();
     if (p->prepared && p->desc.dop_size > 0) {
         g.dop_start = p->desc.dop_start; g.dop_size = p->desc.dop_size; g.dop_rho = p->dop_rho.d();
-        for (int k = 0; k < 3; ++k) g.dop_dfac[k] = dop_l2_lambda_0 * p->desc.dop_derivative_weights[k];
+        const double* ddw = dop_derivative_weights ? dop_derivative_weights : p->desc.dop_derivative_weights;
+        for (int k = 0; k < 3; ++k) g.dop_dfac[k] = dop_l2_lambda_0 * ddw[k];
     }
     return g;
 }

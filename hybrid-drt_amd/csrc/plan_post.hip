@@ -1,6 +1,6 @@
 // What reads a finished fit of a plan (include/hipdrt.h) apart from the DRT chain of plan_drt.hip: log-likelihood terms, the
-// final P, the posterior covariance and variance, Kramers-Kronig screening (csrc/kk.hip), impedance and resistances
-// (csrc/predict.hip).
+// final P, the posterior covariance and variance, the terms of the log marginal likelihood (csrc/lml.hip), Kramers-Kronig screening
+// (csrc/kk.hip), impedance and resistances (csrc/predict.hip).
 #include <cmath>
 #include <cstring>
 
@@ -88,6 +88,17 @@ int posterior_var_dev(hipStream_t st, const PosteriorChain& c, DevBuf& scratch) 
         const int nc = (nb - b0) < chunk ? (nb - b0) : chunk;
         TRY(launch_dist_var(st, nc, n, c.ppk + (size_t)b0 * c.pstr, c.pstr, c.bex, nex, scratch.d() + c.guard, c.single ? 0 : lsz,
                             c.var + (size_t)b0 * nex * 16, c.single ? 0 : (long long)nex * 16, c.status + b0));
+    }
+    return HIPDRT_OK;
+}
+
+int logdet_dev(hipStream_t st, int nb, int n, const double* ppk, long long pstr, DevBuf& scratch, double* logdet, int* status) {
+    const long long lsz = (long long)dist_var_scratch_doubles(n, 0);
+    const int chunk = nb < 256 ? nb : 256;
+    if (scratch.bytes < (size_t)chunk * lsz * sizeof(double)) HIPDRT_CHECK(scratch.alloc((size_t)chunk * lsz * sizeof(double)));
+    for (int b0 = 0; b0 < nb; b0 += chunk) {
+        const int nc = (nb - b0) < chunk ? (nb - b0) : chunk;
+        TRY(launch_logdet(st, nc, n, ppk + (size_t)b0 * pstr, pstr, scratch.d(), lsz, logdet + b0, status + b0));
     }
     return HIPDRT_OK;
 }
@@ -216,6 +227,110 @@ int hipdrt_plan_param_var(hipdrt_plan* p, double* out, int* status) try {
     HIPDRT_REQUIRE(p && out, "NULL pointer");
     const int n = p->n;
     return plan_quadratic_forms(p, host_identity(n).data(), n, n, 0, out, status);
+} HIPDRT_CATCH
+
+// ---- the log marginal likelihood (csrc/lml.hip, qp_resident.hpp: logdet_kernel_resident) ---------------------------------------
+void hipdrt_default_lml_in(hipdrt_lml_in* in) {
+    if (!in) return;
+    std::memset(in, 0, sizeof(*in));
+    in->step = -1;
+    // get_default_hypers (qphb.py:208-255); read only with override_hypers
+    in->l2_lambda_0 = 142.0; in->dop_l2_lambda_0 = 10.0;
+    const double dw[3] = {1.5, 1.0, 0.5}, ddw[3] = {0.5, 1.0, 0.5};
+    for (int k = 0; k < 3; ++k) { in->derivative_weights[k] = dw[k]; in->dop_derivative_weights[k] = ddw[k]; }
+}
+
+int hipdrt_plan_lml_terms(hipdrt_plan* p, const hipdrt_lml_in* in_, hipdrt_lml_out* out) try {
+    HIPDRT_REQUIRE(p && out, "NULL pointer");
+    const hipdrt_lml_in in = opts_or(in_, hipdrt_default_lml_in);
+    HIPDRT_REQUIRE(p->B >= 1 && p->prepped, "no fitted batch in the plan");
+    HIPDRT_REQUIRE(p->n <= 4096, "log marginal likelihood: n <= 4096");
+    const int B = p->B, n = p->n, m = p->m;
+    const bool dop = p->prepared && p->desc.dop_size > 0;
+    const bool uploaded = in.x || in.rho || in.s || in.dop_rho;
+    // every check comes before the first launch
+    if (uploaded) {
+        HIPDRT_REQUIRE(in.x && in.rho && in.s, "an uploaded state needs x, rho and s together");
+        HIPDRT_REQUIRE(in.step < 0, "an uploaded state and a recorded step exclude each other");
+        HIPDRT_REQUIRE(dop == (in.dop_rho != nullptr), "dop_rho is required exactly when the plan has a DOP block");
+    }
+    HIPDRT_REQUIRE(in.step < p->pf_steps, "step out of range of the recorded steps");
+    if (in.weights)
+        for (size_t i = 0; i < (size_t)B * m; ++i)
+            HIPDRT_REQUIRE(in.weights[i] > 0.0 && std::isfinite(in.weights[i]), "weights must be positive and finite");
+    double l2 = p->opts.l2_lambda_0, dop_l2 = dop ? p->desc.dop_l2_lambda_0 : 0.0, dw[3], ddw[3];
+    for (int k = 0; k < 3; ++k) { dw[k] = p->opts.derivative_weights[k]; ddw[k] = dop ? p->desc.dop_derivative_weights[k] : 0.0; }
+    if (in.override_hypers) {
+        l2 = in.l2_lambda_0; dop_l2 = in.dop_l2_lambda_0;
+        for (int k = 0; k < 3; ++k) { dw[k] = in.derivative_weights[k]; ddw[k] = in.dop_derivative_weights[k]; }
+        HIPDRT_REQUIRE(std::isfinite(l2) && (!dop || std::isfinite(dop_l2)), "hyper override: l2_lambda_0 and dop_l2_lambda_0 must be finite");
+        for (int k = 0; k < 3; ++k)
+            HIPDRT_REQUIRE(std::isfinite(dw[k]) && (!dop || std::isfinite(ddw[k])), "hyper override: derivative weights must be finite");
+    }
+    TRY(lds_check(lml_sums_lds_bytes(n, m), "lml sums", "n, m"));
+    hipStream_t st; TRY(enter(p->ctx, &st));
+
+    const size_t D = sizeof(double);
+    DevBuf dx, drho, ds, ddop, dwt, dzero, scratch, dst;
+    PostSource src = live_source(p);
+    if (uploaded) {
+        TRY(upload(dx, in.x, (size_t)B * n * D, st)); TRY(upload(drho, in.rho, (size_t)B * 3 * D, st));
+        TRY(upload(ds, in.s, (size_t)B * 3 * n * D, st));
+        if (dop) TRY(upload(ddop, in.dop_rho, (size_t)B * 3 * D, st));
+        src = PostSource{dx.d(), ds.d(), drho.d(), dop ? ddop.d() : nullptr, nullptr, p->fit_status.i()};
+    } else if (in.step >= 0) {
+        src = step_source(p, in.step, nullptr, p->pf_status.i() + p->pf_layout().scalar(in.step));
+    }
+    // upstream's default is qphb_params['est_weights'], never the scaled weights of the last calculate_pq
+    if (in.weights) TRY(upload(dwt, in.weights, (size_t)B * m * D, st));
+    src.w = in.weights ? dwt.d() : p->est_w.d();
+    HIPDRT_CHECK(dzero.alloc((size_t)B * m * D));
+    HIPDRT_CHECK(hipMemsetAsync(dzero.p, 0, (size_t)B * m * D, st));
+    HIPDRT_CHECK(dst.alloc((size_t)2 * B * sizeof(int)));
+
+    GramL2 g = plan_l2(p, l2, dw, dop_l2, ddw);
+    g.s = src.s; g.rho = src.rho;
+    if (g.dop_size > 0) g.dop_rho = src.dop_rho;
+
+    LmlSumsArgs sa{};
+    sa.m = m; sa.n = n; sa.ldrm = p->ldrm; sa.rm = p->rm.d(); sa.rm_stride = p->rm_stride; sa.rv = p->rv.d(); sa.w = src.w;
+    sa.x = src.x; sa.g = g; sa.l1 = p->l1.d(); sa.fit_status = src.fit_status;
+    double *dlp = nullptr, *dlo = nullptr;
+    DevOuts outs;
+    TRY(outs.want(out->logdet_p, B, dlp, true)); TRY(outs.want(out->logdet_prior, B, dlo, true));
+    TRY(outs.want(out->wy2, B, sa.wy2)); TRY(outs.want(out->fit2, B, sa.fit2)); TRY(outs.want(out->cross, B, sa.cross));
+    TRY(outs.want(out->slw, B, sa.slw)); TRY(outs.want(out->xox, B, sa.xox)); TRY(outs.want(out->l1x, B, sa.l1x));
+
+    PredictTimer tm(p->ctx, st);
+    // P, packed tiles only, of every member whether still active or not; then Omega into the same place
+    PqArgs pq = p->pq(src.w);
+    pq.active = nullptr;
+    launch_gram_l2(st, pq, g);
+    LAUNCH_OK();
+    TRY(logdet_dev(st, B, n, pq.Ppk, pq.ppk_stride, scratch, dlp, dst.i()));
+    pq.w = dzero.d();
+    launch_gram_l2(st, pq, g);
+    LAUNCH_OK();
+    TRY(logdet_dev(st, B, n, pq.Ppk, pq.ppk_stride, scratch, dlo, dst.i() + B));
+    TRY(launch_lml_sums(st, sa, B));
+    LAUNCH_OK();
+    tm.mark();
+
+    std::vector<int> hfit(B), hdet(2 * (size_t)B), hstat(B);
+    HIPDRT_CHECK(hipMemcpyAsync(hfit.data(), src.fit_status, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipMemcpyAsync(hdet.data(), dst.p, (size_t)2 * B * sizeof(int), hipMemcpyDeviceToHost, st));
+    TRY(outs.back(st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    for (int b = 0; b < B; ++b) hdet[b] = (hdet[b] != 0 || hdet[(size_t)B + b] != 0) ? -1 : 0;
+    merge_status(B, hfit.data(), hdet.data(), hstat.data());
+    // a member whose fit failed: every row NaN (the sums are, by the kernel; the determinants of whatever its state held are not)
+    for (int b = 0; b < B; ++b)
+        if (hfit[b] < 0) {
+            if (out->logdet_p) out->logdet_p[b] = __builtin_nan("");
+            if (out->logdet_prior) out->logdet_prior[b] = __builtin_nan("");
+        }
+    if (out->status) std::memcpy(out->status, hstat.data(), (size_t)B * sizeof(int));
+    return HIPDRT_OK;
 } HIPDRT_CATCH
 
 // ---- Kramers-Kronig screening (csrc/kk.hip) ---------------------------------------------------------------------------------

@@ -161,6 +161,18 @@ size_t dist_var_scratch_doubles(int n, int nex) {
     return (nch + (size_t)nex) * nch * TSZ + (n > RNP_MAX ? (size_t)round_up(n, 32) * PLD : 0);   // + U when it lives outside LDS
 }
 
+// log-determinants of B packed matrices (qp_resident.hpp: logdet_kernel_resident); scratch per matrix: dist_var_scratch_doubles(n, 0)
+int launch_logdet(hipStream_t st, int B, int n, const double* Ppk, long long ppk_stride, double* L, long long l_stride,
+                  double* logdet, int* status) {
+    if (n > GRP_NMAX) { set_error("log-determinant: n > 4096 not supported"); return HIPDRT_E_INVALID; }
+    const int NP = round_up(n, 32);
+    LogdetArgs a;
+    a.B = B; a.n = n; a.Ppk = Ppk; a.ppk_stride = ppk_stride; a.nchp = qp_nchp(n);
+    a.L = L; a.l_stride = l_stride; a.logdet = logdet; a.status = status;
+    if (n > RNP_MAX) return launch_lds(logdet_kernel_resident<true>, "logdet", dim3(B), dim3(RT), logdet_lds_bytes<true>(NP), st, a, NP);
+    return launch_lds(logdet_kernel_resident<false>, "logdet", dim3(B), dim3(RT), logdet_lds_bytes<false>(NP), st, a, NP);
+}
+
 // diagnostic (tools/): resident workgroups per CU the runtime reports for the coneqp kernel of n unknowns
 int qp_occupancy(int threads, int n) {
     const int NP = round_up(n, 32);

@@ -2167,6 +2167,53 @@ __global__ __launch_bounds__(RTT) void cov_kernel_resident(CovArgs a, int NP) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Log-determinant of a symmetric positive definite matrix given as packed lower tiles, for the log marginal likelihood
+// (hybdrt/models/qphb.py:1301, 1313: np.linalg.slogdet of P and of the prior precision):
+//     logdet = 2 sum_i log L_ii ,   M = L L'
+// factor() as the posterior-variance kernel runs it -- no diagonal shift, no appended rows.  It never stores a diagonal block of
+// L: what survives is U, the inverse of every 32 x 32 diagonal block, whose own diagonal is 1 / L_ii exactly as the pivot chain
+// formed it (cholinv16_blocked: row i of the inverse at U[i * PLD + (i mod 32)]).  So the kernel returns
+//     logdet = -2 sum_{i < n} log U_ii
+// over the n real unknowns; the identity rows that pad n up to NP are not read.  Wavefront 0 sums: lane l takes i = l, l + 64, ...
+// in ascending order, then one butterfly over the lanes -- an order that depends on n alone, never on the batch.
+// ---------------------------------------------------------------------------------------------------------
+struct LogdetArgs {
+    int B, n;
+    const double* Ppk; long long ppk_stride; int nchp;   // the matrices, packed lower tiles
+    double* L; long long l_stride;                       // scratch per matrix: dist_var_scratch_doubles(n, 0)
+    double* logdet;                                      // [B]; NaN where status is -1
+    int* status;                                         // [B]: 0 ok, -1 not positive definite
+};
+
+template <bool GU, int RTT = 512>
+__global__ __launch_bounds__(RTT) void logdet_kernel_resident(LogdetArgs a, int NP) {
+    constexpr int RT = RTT;
+    const int b = blockIdx.x;
+    extern __shared__ double smem[];
+    OpsResidentT<GU, RTT> ops;
+    ops.L = a.L + (size_t)b * a.l_stride; ops.nch = NP / 16; ops.n = a.n;
+    ops.Ppk = a.Ppk + (size_t)b * a.ppk_stride; ops.nchp = a.nchp;
+    constexpr int VEC = ResSmemT<GU, RTT>::VEC;
+    ops.sm.carve(smem);
+    if (GU) ops.sm.U = ops.L + (size_t)(NP / 16) * (NP / 16) * TSZ;      // behind the nch x nch tiles, as in cov_kernel_resident
+    for (int i = threadIdx.x; i < NP * PLD; i += RT) ops.sm.U[i] = 0.0;
+    for (int i = threadIdx.x; i < VEC; i += RT) { ops.sm.vec[i] = 0.0; ops.sm.dvec[i] = 0.0; }   // no diagonal shift
+    __syncthreads();
+    const bool ok = ops.factor();          // every role leaves after the same barrier: U is complete and visible
+    if (threadIdx.x >= 64) return;
+    const int lane = threadIdx.x;
+    double s_ = 0.0;
+    if (ok)
+        for (int i = lane; i < a.n; i += 64) s_ += log(ops.sm.U[(size_t)i * PLD + (i & 31)]);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) s_ += __shfl_xor(s_, o, 64);
+    if (lane == 0) {
+        a.logdet[b] = ok ? -2.0 * s_ : __builtin_nan("");
+        a.status[b] = ok ? 0 : -1;
+    }
+}
+
 // The QP kernel: 64-column passes over the history (factor64), in both forms below.
 // (the second launch-bound argument is waves per SIMD: 2 in both forms, i.e. one 512-thread or two 256-thread workgroups per
 // CU and at most 256 registers per lane; without it hipcc gives the 256-thread form 393 registers and one workgroup per CU)
@@ -2205,6 +2252,9 @@ template <bool GU>
 static size_t cov_lds_bytes(int NP) {
     return ((GU ? 0 : (size_t)NP * PLD) + ResSmemT<GU, 512, false>::FIXED) * sizeof(double);
 }
+// logdet_kernel_resident carves the posterior-variance kernel's layout (the 32-column factorisation's)
+template <bool GU>
+static size_t logdet_lds_bytes(int NP) { return cov_lds_bytes<GU>(NP); }
 // per-problem scratch doubles of the U-outside form: the tile-packed factor (NP^2) followed by U (NP x 33)
 static size_t resident_gu_doubles(int n) {
     const size_t NP = (size_t)round_up(n, 32);

@@ -37,6 +37,23 @@ def marginal_llh(rss, m, alpha_0=2, beta_0=1):
     return alpha_0 * np.log(beta_0) - alpha_n * np.log(beta_n) + loggamma(alpha_n) - loggamma(alpha_0)
 
 
+def evaluate_lml(x_hat, penalty_matrices, penalty_type, hypers, l1_lambda_vector, rho_vector, dop_rho_vector, s_vectors,
+                 weights, rm, rv, special_qp_params, alpha_0=1, beta_0=1):
+    """qphb.evaluate_lml (hybdrt/models/qphb.py:1279-1344), same arguments: the log marginal likelihood of one state under fixed
+    s and rho.  This is the numpy STATEMENT (models/lml.py) that the device path -- DRT.evaluate_lml / evaluate_lml_batch over
+    hipdrt_plan_lml_terms -- is tested against; it runs on the host and serves arrays that are not a plan's.  The determinants
+    are Cholesky sums where upstream calls slogdet, and a matrix that is not positive definite raises upstream's ValueError."""
+    from . import lml
+    if penalty_type != 'integral':
+        raise NotImplementedError("penalty_type 'discrete' is deprecated in the reference and not built")
+    terms, status = lml.lml_terms(x_hat, rho_vector, s_vectors, dop_rho_vector, weights, rm, rv, penalty_matrices, hypers,
+                                  special_qp_params, l1=l1_lambda_vector)
+    if status:
+        which = 'posterior' if np.isnan(terms['logdet_p']) else 'prior'
+        raise ValueError(f'Determinant of {which} covariance matrix is negative - not PSD')
+    return lml.lml_from_terms(terms, len(rv), alpha_0, beta_0)
+
+
 def get_num_special(special_qp_params):
     """qphb.py:44-48."""
     if len(special_qp_params) == 0:

@@ -6,7 +6,7 @@ a prepared plan, what is collected -- the difference is one named piece."""
 import numpy as np
 
 from .. import _ffi
-from . import candidates, qphb
+from . import candidates, lml, qphb
 
 
 def combine_status(so_far, step):
@@ -45,6 +45,12 @@ def pfrt_schedule(factors, kw):
     def step_hypers(f):
         return dict(s_0=s_0 * f, l2_lambda_0=base['l2_lambda_0'] / f)
     return factors, step_hypers
+
+
+def _no_column(criterion):
+    """the candidate tables hold bic only, like upstream's continuous tables: 'lml' and 'lml-bic' have nothing to read"""
+    return (f"criterion {criterion!r}: the candidate tables have no such column (nor have upstream's continuous tables); "
+            "evaluate_lml / evaluate_lml_batch score a fit, not a table of candidates")
 
 
 class RestartMixin:
@@ -356,6 +362,71 @@ class RestartMixin:
         """DRT.evaluate_bic of member ``b`` of the last fit"""
         return float(self.evaluate_bic_batch(find_peaks_kw=find_peaks_kw, **llh_kw)[b])
 
+    # ---- the log marginal likelihood (drt1d.py:4513-4543) -------------------------------------------------------------------
+    def evaluate_lml_batch(self, weights=None, update_hypers=None, state=None, step=None, alpha_0=1, beta_0=1, return_terms=False):
+        """DRT.evaluate_lml (drt1d.py:4513-4543 over qphb.py:1279-1344) for every spectrum of the last batch -> (B,): both
+        log-determinants and the sums on the device (hipdrt_plan_lml_terms), upstream's last two lines here (models/lml.py).
+        state: dict of batch arrays x (B, n), rho_vector (B, 3), s_vectors (B, 3, n), plus dop_rho_vector (B, 3) for a fit with
+        fit_dop -- what upstream takes from a history entry; step: a recorded step of the step store (PFRT steps, candidates);
+        neither: the live fit.  weights (B, m) or (m,): None = the fit's est_weights, as upstream.  update_hypers: of the keys of
+        a hyper dict, l2_lambda_0, derivative_weights, dop_l2_lambda_0 and dop_derivative_weights reach the formula, the others
+        are accepted without effect, as upstream; a key no hyper dict has is a ValueError.  A member whose fit failed, or whose
+        P or prior precision is not positive definite, gives NaN (status: the fit's, or PREDICT_NOT_PD); so does a negative
+        beta, as upstream.  return_terms: (lml, dict of the eight terms and status)."""
+        plan = self._plan
+        if plan is None or not plan.B:
+            raise ValueError('evaluate_lml needs a finished fit')
+        if state is not None and step is not None:
+            raise ValueError('state and step exclude each other')
+        has_dop = 'x_dop' in (self.special_qp_params or {})
+        hypers = None
+        if update_hypers:
+            hypers = lml.updated_hypers({k: self.fit_kwargs[k] for k in lml.LML_HYPERS if k in self.fit_kwargs}, update_hypers,
+                                        known=qphb.get_default_hypers(fit_dop=True))
+        kw = {}
+        if state is not None:
+            x, rho, s, dop_rho = lml.entry_state(state)
+            if has_dop and dop_rho is None:
+                raise ValueError('state lacks dop_rho_vector: this fit has a DOP block')
+            kw = dict(x=x, rho=rho, s_vectors=np.asarray(s, dtype=float), dop_rho=dop_rho if has_dop else None)
+        if weights is not None:
+            weights = np.broadcast_to(np.asarray(weights, dtype=float), (plan.B, plan.m))
+            if not np.all(weights > 0):
+                raise ValueError('weights must be positive')
+        terms = plan.lml_terms(step=step, weights=weights, hypers=hypers, **kw)
+        out = np.asarray(lml.lml_from_terms(terms, plan.m, alpha_0, beta_0), dtype=float)
+        out = np.where(terms['status'] < 0, np.nan, out)
+        return (out, terms) if return_terms else out
+
+    def evaluate_lml(self, history_entry=None, weights=None, update_hypers=None, b=0):
+        """DRT.evaluate_lml of member ``b`` of the last fit, upstream's signature.  history_entry: a dict with x, rho_vector,
+        s_vectors (and dop_rho_vector), as upstream's history entries are; this project's own qphb_history entries carry no
+        s_vectors and are refused with a pointer to evaluate_lml_batch(step=...) / (state=...).  Where upstream raises
+        'Determinant of ... is negative - not PSD', a failed factorisation raises the same text."""
+        plan = self._plan
+        if plan is None or not plan.B:
+            raise ValueError('evaluate_lml needs a finished fit')
+        state = None
+        if history_entry is not None:
+            x, rho, s, dop_rho = lml.entry_state(history_entry)
+            live = plan.download(s_vectors=True)                       # the other members keep their own state
+            state = dict(x=live['x'].copy(), rho_vector=live['rho'].copy(), s_vectors=live['s_vectors'].copy())
+            state['x'][b], state['rho_vector'][b], state['s_vectors'][b] = x, rho, np.asarray(s, dtype=float)
+            if 'x_dop' in (self.special_qp_params or {}):
+                if dop_rho is None:
+                    raise ValueError('history_entry lacks dop_rho_vector: this fit has a DOP block')
+                state['dop_rho_vector'] = plan.get('dop_rho').copy()
+                state['dop_rho_vector'][b] = dop_rho
+        if weights is not None and plan.B > 1:
+            w = plan.get('est_weights').copy()
+            w[b] = weights
+            weights = w
+        out, terms = self.evaluate_lml_batch(weights=weights, update_hypers=update_hypers, state=state, return_terms=True)
+        if terms['status'][b] == _ffi.PREDICT_NOT_PD:
+            which = 'posterior' if np.isnan(terms['logdet_p'][b]) else 'prior'
+            raise ValueError(f'Determinant of {which} covariance matrix is negative - not PSD')
+        return float(out[b])
+
     # the tables generate_candidates left (drt1d.py:2383-2500); discrete element models are not built
     def get_candidate_df(self, candidate_type):
         if candidate_type == 'continuous':
@@ -383,7 +454,7 @@ class RestartMixin:
         criterion = 'bic' if criterion is None else criterion
         if criterion not in df:
             candidates.norm_bayes_factors(np.zeros(1), criterion)        # (an invalid criterion is stats' ValueError)
-            raise NotImplementedError(f'criterion {criterion!r}: evaluate_lml is not built')
+            raise NotImplementedError(_no_column(criterion))
         bf = candidates.norm_bayes_factors(df[criterion], criterion)
         if candidate_id is None:
             return bf
@@ -399,7 +470,7 @@ class RestartMixin:
         c1, c2 = self.get_candidate(candidate_id_1, candidate_type), self.get_candidate(candidate_id_2, candidate_type)
         if criterion not in c1:
             candidates.bayes_factor(0.0, 0.0, criterion)
-            raise NotImplementedError(f'criterion {criterion!r}: evaluate_lml is not built')
+            raise NotImplementedError(_no_column(criterion))
         return candidates.bayes_factor(c1[criterion], c2[criterion], criterion)
 
     def get_best_candidate_id(self, candidate_type, criterion=None):
@@ -415,7 +486,7 @@ class RestartMixin:
         if df is None:
             raise ValueError('Candidates must be first be generated using generate_candidates')
         if criterion not in df:
-            raise NotImplementedError(f'criterion {criterion!r}: evaluate_lml is not built')
+            raise NotImplementedError(_no_column(criterion))
         values = df[criterion] * directions[criterion]
         return df['model_id'][np.argmax(values)]
 

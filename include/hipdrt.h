@@ -1000,6 +1000,49 @@ typedef struct {                      /* host arrays, any may be NULL; [C][B] le
  * peaks).  The result of a candidate depends neither on C or B nor on its position among the candidates or in the batch.         */
 int hipdrt_plan_score_candidates(hipdrt_plan* plan, const hipdrt_candidates_in* in, hipdrt_candidates_out* out);
 
+/* ---- log marginal likelihood (evidence) of the fitted batch -----------------------------------------------------------------------
+ * The ingredients of DRT.evaluate_lml (hybdrt/models/drt1d.py:4513-4543 over qphb.evaluate_lml, hybdrt/models/qphb.py:1279-1344)
+ * for every spectrum of the fitted batch.  With Omega = calculate_qp_l2_matrix(...) (qphb.py:53-120, special diagonal included),
+ * P = Omega + (W rm)'(W rm) (calculate_pq, qphb.py:1154-1183), y = rv and r = rm x:
+ *     logdet_p = ln det P, logdet_prior = ln det Omega, wy2 = |W y|^2, fit2 = |W r|^2, cross = sum w^2 r y, slw = sum ln w,
+ *     xox = x' Omega x, l1x = l1' x
+ * from which upstream's last lines follow on the host (hipdrt/models/lml.py: lml_from_terms):
+ *     beta = 0.5 (wy2 - fit2 - xox) + beta_0,  alpha = m / 2 + alpha_0,
+ *     lml  = 0.5 (logdet_prior - logdet_p) + slw + lgamma(alpha) - lgamma(alpha_0) + alpha_0 ln beta_0 - alpha ln beta
+ * (cross and l1x are not in the LML: wy2 - 2 cross + fit2 is the residual sum of squares, and with xox they give x'Px and q'x).
+ * State: the live fit (step < 0, no arrays), recorded step `step` of the step store (hipdrt_plan_pfrt_begin / _record), or the
+ * uploaded arrays x, rho, s (and dop_rho exactly when the plan has a DOP block).  Weights: NULL = the fit's own est_weights, which
+ * is upstream's default -- never the scaled weights the fit's last P was formed with, nor the row factors of a KK pass.
+ * A determinant is 2 sum ln L_ii of the Cholesky factor (csrc/qp_resident.hpp: logdet_kernel_resident); P's packed image is formed,
+ * reduced, and Omega's image then formed in the same place.                                                                          */
+typedef struct {
+    int step;                         /* >= 0: that recorded step's x, rho, s, dop_rho; -1: the live fit or the arrays below          */
+    const double* x;                  /* [B][n] scaled unknowns; x, rho and s come together or not at all                             */
+    const double* rho;                /* [B][3]                                                                                       */
+    const double* s;                  /* [B][3][n]                                                                                    */
+    const double* dop_rho;            /* [B][3]; with the arrays above, required exactly when the plan has a DOP block                */
+    const double* weights;            /* [B][m], every entry > 0; NULL: the plan's est_weights                                        */
+    int override_hypers;              /* 0: the plan's own hyper-parameters; 1: the four below (update_hypers)                        */
+    double l2_lambda_0;
+    double derivative_weights[3];     /* a weight of 0 skips that order                                                               */
+    double dop_l2_lambda_0;           /* read only when the plan has a DOP block, as the next                                         */
+    double dop_derivative_weights[3];
+} hipdrt_lml_in;
+typedef struct {                      /* host arrays [B], any may be NULL                                                             */
+    double *logdet_p, *logdet_prior;  /* NaN where that factorisation failed                                                          */
+    double *wy2, *fit2, *cross, *slw, *xox, *l1x;
+    int* status;                      /* the fit's (a recorded step: the step's) status where negative: every row of that member is
+                                         NaN; else HIPDRT_PREDICT_NOT_PD where either matrix is not positive definite; else that status */
+} hipdrt_lml_out;
+/* step -1, no arrays, no override; the hyper fields hold get_default_hypers' values (qphb.py:208-255)                                */
+void hipdrt_default_lml_in(hipdrt_lml_in* in);
+/* in NULL: the defaults.  HIPDRT_E_INVALID before any launch: no fitted batch, n > 4096, a step outside the store, a step together
+ * with arrays, arrays without x, rho or s, dop_rho missing or superfluous, a weight that is not positive and finite, an override that
+ * is not finite, m and n beyond one workgroup's LDS.  The last device batch only.  The call rebuilds the packed image of P, which
+ * every outer iteration of a fit rebuilds too, and writes nothing else that the fit or a later call reads.  Plain and prepared
+ * plans; a vz_offset column is taken as the fit left it.  A spectrum's result depends neither on B nor on its position.              */
+int hipdrt_plan_lml_terms(hipdrt_plan* plan, const hipdrt_lml_in* in, hipdrt_lml_out* out);
+
 /* kernel-time breakdown of the last hipdrt_plan_fit in ms (HIP events on the ctx stream):
  * t[0]=total, t[1]=gram, t[2]=qp, t[3]=hyper, t[4]=setup/other; launches[5] same order                 */
 int hipdrt_plan_timings(hipdrt_plan* plan, float* t, int* launches);

@@ -85,6 +85,10 @@ typedef struct hipdrt_debug_gram_args {
 int hipdrt_debug_gram_l2(hipdrt_ctx* ctx, const hipdrt_debug_gram_args* a);
 /* test hook: launch_pack_p -- row-major symmetric P [B][n][ldp] (host) -> Ppk [B][nchp * nchp * 256] (host, in/out as above) */
 int hipdrt_debug_pack_p(hipdrt_ctx* ctx, int B, int n, const double* P, int ldp, double* Ppk);
+/* test hook (tests/test_gpu_lml.py): the log-determinant kernel of hipdrt_plan_lml_terms alone -- launch_pack_p, then launch_logdet in
+ * that entry's chunks -- on B row-major symmetric matrices P [B][n][n] (host; the lower triangle is read).  logdet [B] = 2 sum ln L_ii
+ * of the Cholesky factor, status [B] = 0; a matrix that is not positive definite gives NaN and -1.  1 <= B <= 4096, 1 <= n <= 4096. */
+int hipdrt_debug_logdet(hipdrt_ctx* ctx, int B, int n, const double* P, double* logdet, int* status);
 
 /* test hook (tests/test_gpu_hyper.py): one hyper-parameter step -- launch_hyper (csrc/hyper.hip) as it is: hyper_kernel, with the
  * products of estimate_weights inside it, from premv_kernel or from batch_products_kernel<0> / <1> -- on host arrays.  The hook
