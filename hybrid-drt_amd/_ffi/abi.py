@@ -139,6 +139,13 @@ class LmlOut(C.Structure):
                 ("l1x", _dp), ("status", _ip)]
 
 
+class ResolveArgs(C.Structure):
+    """hipdrt_resolve_args (include/hipdrt.h)"""
+    _fields_ = [("nb", C.c_int), ("nr", C.c_int), ("num_remove", C.c_int), ("so", C.c_int), ("lambda_psi", C.c_double),
+                ("tau_filter_sigma", C.c_double), ("special_filter_sigma", C.c_double), ("first", _ip), ("match", _ip),
+                ("tau_indices", _ip), ("my", _dp), ("param_scale", _dp), ("x_remove", _dp), ("h", _dp)]
+
+
 LML_TERMS = ("logdet_p", "logdet_prior", "wy2", "fit2", "cross", "slw", "xox", "l1x")
 
 
@@ -376,6 +383,8 @@ SIGNATURES = {
     "hipdrt_default_lml_in": [C.POINTER(LmlIn)],
     "hipdrt_plan_lml_terms": [_vp, C.POINTER(LmlIn), C.POINTER(LmlOut)],
     "hipdrt_debug_logdet": [_vp, C.c_int, C.c_int, _dp, _dp, _ip],
+    "hipdrt_plan_resolve_group": [_vp, C.POINTER(ResolveArgs), _dp, _ip, _ip],
+    "hipdrt_debug_resolve_assemble": [_vp, C.POINTER(ResolveArgs), C.c_int, _dp, _dp, _dp, _dp],
     "hipdrt_debug_candidate_llh": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp],
     "hipdrt_debug_candidate_form": [_vp, C.c_int],
     "hipdrt_debug_posterior": [_vp, C.POINTER(DebugPosteriorArgs)],

@@ -4,7 +4,7 @@ A ctypes pointer field does not keep its array alive, so every array goes throug
 the entry point takes, stored in the field and held in ``keep`` for as long as the Bound lives."""
 import numpy as np
 
-from .abi import _p, _pi
+from .abi import ResolveArgs, _p, _pi
 
 
 class Bound:
@@ -56,3 +56,25 @@ class Bound:
             slot.radius = r
             if w is not None:
                 slot.w = w
+
+
+def resolve_bound(args, num_members):
+    """a description of coupled batches (mapping.resolve.resolve_args) as hipdrt_resolve_args, with the sizes it implies:
+    -> (Bound, [nc_k], [doubles before batch k in x and h])"""
+    b = Bound(ResolveArgs())
+    c = b.c
+    nb, nr, nrm = int(args["nb"]), int(args["nr"]), int(args["num_remove"])
+    c.nb, c.nr, c.num_remove, c.so, c.lambda_psi = nb, nr, nrm, int(args["so"]), float(args["lambda_psi"])
+    c.tau_filter_sigma, c.special_filter_sigma = float(args["tau_filter_sigma"]), float(args["special_filter_sigma"])
+    b.array("first", args["first"], (nb,), dtype=np.int32)
+    match = b.array("match", args["match"], (nb, 2), dtype=np.int32)
+    b.array("tau_indices", args["tau_indices"], (num_members, 2), dtype=np.int32)
+    b.array("my", args["my"], (nb, nr, nr))
+    if nrm > 0:
+        b.array("x_remove", args["x_remove"], (num_members, nrm))
+    nc = [int(c.so + m[1] - m[0]) for m in match]
+    if [len(v) for v in args["param_scale"]] != nc or [len(v) for v in args["h"]] != [nr * v for v in nc]:
+        raise ValueError("param_scale: so + match width entries per batch; h: nr times as many")
+    b.array("param_scale", np.concatenate([np.asarray(v, dtype=np.float64) for v in args["param_scale"]]))
+    b.array("h", np.concatenate([np.asarray(v, dtype=np.float64) for v in args["h"]]))
+    return b, nc, np.concatenate([[0], np.cumsum([nr * v for v in nc])]).astype(int)

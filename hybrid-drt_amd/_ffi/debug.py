@@ -7,7 +7,7 @@ import numpy as np
 
 from .abi import *            # noqa: F401,F403 (the constants and structures)
 from .abi import _check, _dp, _f64, _i32, _p, _pi
-from .args import Bound
+from .args import Bound, resolve_bound
 from .opts import (_index_windows, _kk_outputs, _peak_out_args, _peak_outputs, _peak_prob_out_args, _peak_prob_outputs,
                    _resolve_out_struct, _resolve_outputs, peak_opts, peak_prob_opts, peak_resolve_opts, pfrt_opts)
 
@@ -555,6 +555,28 @@ class DebugHooks:
         logdet, status = np.full(B, 7e77), np.full(B, -77, dtype=np.int32)
         _check(self._lib.hipdrt_debug_logdet(self._h, B, n, _p(P), _p(logdet), _pi(status)))
         return logdet, status
+
+    def debug_resolve_assemble(self, args, p_list, q_list):
+        """tests: the assembly kernels of Plan.resolve_group alone (hipdrt_debug_resolve_assemble, include/hipdrt_debug.h) on host
+        arrays: args as mapping.resolve.resolve_args gives it (h is not read), member b's own P (n_b, n_b) and q (n_b,) -> one
+        (P_k, q_k) per batch, P_k dense and symmetric from the lower tiles the kernel wrote.  Raises when a kernel wrote outside an
+        array or left a padding entry of a tile non-zero."""
+        if len(p_list) != len(q_list):
+            raise ValueError("one q per P")
+        b, nc, off = resolve_bound(args, len(p_list))
+        nb, nr = b.c.nb, b.c.nr
+        for m, (p, v, (left, right)) in enumerate(zip(p_list, q_list, np.asarray(args["tau_indices"]).reshape(-1, 2))):
+            n = b.c.num_remove + b.c.so + int(right) - int(left)          # the hook reads this many rows, whatever it is handed
+            if np.shape(p) != (n, n) or np.shape(v) != (n,):
+                raise ValueError(f"member {m}: P ({n}, {n}) and q ({n},) for its tau range, got {np.shape(p)} and {np.shape(v)}")
+        P = np.concatenate([_f64(p).ravel() for p in p_list])
+        q = np.concatenate([_f64(v).ravel() for v in q_list])
+        p_out = np.full(int(sum((nr * v) ** 2 for v in nc)), 7e77)
+        q_out = np.full(off[-1], 7e77)
+        _check(self._lib.hipdrt_debug_resolve_assemble(self._h, C.byref(b.c), len(p_list), _p(P), _p(q), _p(p_out), _p(q_out)),
+               {E_UNSUPPORTED: NotImplementedError})
+        poff = np.concatenate([[0], np.cumsum([(nr * v) ** 2 for v in nc])]).astype(int)
+        return [(p_out[poff[k]:poff[k + 1]].reshape(nr * nc[k], nr * nc[k]), q_out[off[k]:off[k + 1]]) for k in range(nb)]
 
     def qp_profile(self, reset=True):
         buf = (C.c_ulonglong * 64)()        # 0..47 the QP kernel's phases, 48..63 hyper_kernel's (PROFILE=1 builds)

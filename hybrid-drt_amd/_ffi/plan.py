@@ -8,7 +8,7 @@ import numpy as np
 
 from .abi import *            # noqa: F401,F403 (the constants and structures)
 from .abi import _check, _f64, _i32, _p, _pi, _vp, load_library
-from .args import Bound
+from .args import Bound, resolve_bound
 from .opts import (_index_windows, _kk_outputs, _peak_out_args, _peak_outputs, _peak_prob_out_args, _peak_prob_outputs, _resolve_out_struct, _resolve_outputs, default_fit_opts, peak_opts,
                    peak_resolve_opts, pfrt_opts)
 
@@ -637,6 +637,17 @@ class PreparedPlan(Plan):
         status = C.c_int(0)
         _check(self._lib.hipdrt_plan_dop_cov(self._h, int(member), C.byref(b.c), _p(out), C.byref(status)))
         return out, int(status.value)
+
+    def resolve_group(self, args):
+        """hipdrt_plan_resolve_group: the coupled QPs of DRTMD.resolve_group over members of the fitted batch, assembled from the final
+        P and q on the device and solved there.  args: mapping.resolve.resolve_args' description -> dict of x (one (nr, nc_k) array
+        per batch), iterations (nb,), status (nb,).  tau_filter_sigma / special_filter_sigma > 0: NotImplementedError."""
+        b, nc, off = resolve_bound(args, self.B)
+        nb, nr = b.c.nb, b.c.nr
+        x = np.full(off[-1], 7e77)
+        iters, status = np.full(nb, -7, dtype=np.int32), np.full(nb, -7, dtype=np.int32)
+        _check(self._lib.hipdrt_plan_resolve_group(self._h, C.byref(b.c), _p(x), _pi(iters), _pi(status)), {E_UNSUPPORTED: NotImplementedError})
+        return dict(x=[x[off[k]:off[k + 1]].reshape(nr, nc[k]) for k in range(nb)], iterations=iters, status=status)
 
     def get(self, which):
         B = self.batch

@@ -14,10 +14,9 @@ from .. import _ffi
 from ..matrices.basis import construct_func_eval_matrix
 
 
-def get_offset_pq(drt):
-    """resolve.get_offset_pq (hybdrt/mapping/resolve.py:11-64): P, q of a fitted DRT without the v_baseline / vz_offset
-    unknowns, their fitted values folded into q."""
-    p, q = drt.fit_parameters['p_matrix'], drt.fit_parameters['q_vector']
+def removed_values(drt):
+    """the fitted values of the v_baseline / vz_offset unknowns in the QP's own scaling (resolve.py:23-47): what get_offset_pq folds
+    into q.  Needs no P."""
     sp = drt.special_qp_params
     num_remove = sum(sp[k]['size'] for k in ('v_baseline', 'vz_offset'))     # KeyError on non-hybrid fits, as upstream
     x_remove = np.empty(num_remove)
@@ -27,6 +26,15 @@ def get_offset_pq(drt):
     coef[0] += drt.scaled_response_offset
     x_remove[vb['index']:vb['index'] + vb['size']] = coef * drt.v_baseline_scale
     x_remove[sp['vz_offset']['index']] = drt.fit_parameters['vz_offset']
+    return x_remove
+
+
+def get_offset_pq(drt):
+    """resolve.get_offset_pq (hybdrt/mapping/resolve.py:11-64): P, q of a fitted DRT without the v_baseline / vz_offset
+    unknowns, their fitted values folded into q."""
+    p, q = drt.fit_parameters['p_matrix'], drt.fit_parameters['q_vector']
+    x_remove = removed_values(drt)
+    num_remove = len(x_remove)
     return p[num_remove:, num_remove:], q[num_remove:] + x_remove @ p[:num_remove, num_remove:]
 
 
@@ -71,16 +79,11 @@ def get_tau_indices(obs_tau_indices, truncate=False):
     return (max(lefts), min(rights)) if truncate else (min(lefts), max(rights))
 
 
-def resolve_observations(obs_drt_list, obs_tau_indices, nonneg, obs_psi=None, truncate=False, sigma=1, lambda_psi=1,
-                         unpack=False, tau_filter_sigma=0, special_filter_sigma=0, device=0, _assemble_only=False):
-    """resolve.resolve_observations (189-341).  Returns (x_opt (nr, nc), match_tau_indices), or the unpacked
-    (x_drt, x_special, match_tau_indices).  Raises ValueError when the QP breaks down (cvxopt's error)."""
-    match = get_tau_indices(obs_tau_indices, truncate=truncate)
-    special = offset_special_dict(obs_drt_list[0].special_qp_params)
-    so = int(sum(v.get('size', 1) for v in special.values()))
-    pq = [resize_pq(*get_offset_pq(drt), so, obs_tau_indices[i], match) for i, drt in enumerate(obs_drt_list)]
-    nr, nc = len(pq), len(pq[0][1])
-
+def coupling(obs_drt_list, special, nc, sigma):
+    """the coupling of one batch across its observations (resolve.py:232-272): my (nr, nr), the second-derivative Gaussian filter
+    applied to the coefficients at their true scale, and param_scale (nc,), which brings R_inf and x_dop to the spread they have
+    over the batch.  Also the x_dop slice (or None)."""
+    nr = len(obs_drt_list)
     # smoothness across observations, applied to the coefficients at their true scale (resolve.py:232-245, 271-272)
     ly = gaussian_filter1d(np.eye(nr), sigma=sigma, mode='reflect', order=2)
     scale_vec = np.array([drt.coefficient_scale for drt in obs_drt_list])
@@ -96,6 +99,30 @@ def resolve_observations(obs_drt_list, obs_tau_indices, nonneg, obs_psi=None, tr
                           for drt in obs_drt_list])
         dop = (special['x_dop']['index'], special['x_dop']['index'] + special['x_dop'].get('size', 1))
         param_scale[dop[0]:dop[1]] = (np.std(x_dop, axis=0) + 0.1 * np.std(x_dop)) ** -2
+    return my, param_scale, dop
+
+
+def bound_vector(special, nonneg, nr, nc):
+    """h of G x <= h with G = -I (resolve.py:301-317): 0 for unknowns that may not be negative, 10 for the others"""
+    h = np.zeros(nr * nc) if nonneg else 10 * np.ones(nr * nc)
+    for v in special.values():
+        if v['nonneg']:
+            for i in range(nr):
+                h[v['index'] + i * nc:v['index'] + v.get('size', 1) + i * nc] = 0
+    return h
+
+
+def resolve_observations(obs_drt_list, obs_tau_indices, nonneg, obs_psi=None, truncate=False, sigma=1, lambda_psi=1,
+                         unpack=False, tau_filter_sigma=0, special_filter_sigma=0, device=0, _assemble_only=False):
+    """resolve.resolve_observations (189-341).  Returns (x_opt (nr, nc), match_tau_indices), or the unpacked
+    (x_drt, x_special, match_tau_indices).  Raises ValueError when the QP breaks down (cvxopt's error)."""
+    match = get_tau_indices(obs_tau_indices, truncate=truncate)
+    special = offset_special_dict(obs_drt_list[0].special_qp_params)
+    so = int(sum(v.get('size', 1) for v in special.values()))
+    pq = [resize_pq(*get_offset_pq(drt), so, obs_tau_indices[i], match) for i, drt in enumerate(obs_drt_list)]
+    nr, nc = len(pq), len(pq[0][1])
+
+    my, param_scale, dop = coupling(obs_drt_list, special, nc, sigma)
     m_full = np.zeros((nr * nc, nr * nc))
     diag = np.arange(nc)
     for i in range(nr):
@@ -115,11 +142,7 @@ def resolve_observations(obs_drt_list, obs_tau_indices, nonneg, obs_psi=None, tr
     for i, (p, _) in enumerate(pq):
         p_matrix[i * nc:(i + 1) * nc, i * nc:(i + 1) * nc] += p
     q_vector = np.concatenate([q for _, q in pq])
-    h = np.zeros(nr * nc) if nonneg else 10 * np.ones(nr * nc)
-    for v in special.values():
-        if v['nonneg']:
-            for i in range(nr):
-                h[v['index'] + i * nc:v['index'] + v.get('size', 1) + i * nc] = 0
+    h = bound_vector(special, nonneg, nr, nc)
 
     if _assemble_only:
         return p_matrix, q_vector, h, special, match, nr, nc
@@ -150,16 +173,11 @@ def unpack_resolved_x(x, obs_drt_list, special_dict):
     return x_drt, x_special
 
 
-def resolve_group(obs_drt_list, obs_tau_indices, nonneg, num_tau_super, batch_size=7, overlap=2, truncate=False, sigma=1,
-                  lambda_psi=1, tau_filter_sigma=0, special_filter_sigma=0, device=0):
-    """DRTMD.resolve_group (hybdrt/mapping/drtmd.py:486-559) for observations already sorted along psi: overlapping batches
-    of `batch_size` observations are re-optimised coherently (resolve_observations each) and the overlaps averaged with
-    weights growing with the distance from the batch edge.  The batches are independent QPs: all of one size go to the device as
-    ONE batched launch (one size when every observation was fitted on the same tau range).  Returns (obs_x_resolved (num_obs, num_tau_super), obs_special_resolved dict)."""
-    num_obs = len(obs_drt_list)
+def group_batch_starts(num_obs, batch_size=7, overlap=2):
+    """the batches of DRTMD.resolve_group (drtmd.py:510-537) over num_obs sorted observations -> (batch size, capped at num_obs; the
+    first observation of every batch): a stride of batch_size - overlap, and a full batch for the last one"""
     batch_size = min(batch_size, num_obs)
     stride = max(batch_size - overlap, 1)
-    num_batches = 1 + int(np.ceil((num_obs - batch_size) / stride))
     starts = []
     for start in range(0, num_obs, stride):
         if num_obs - start < batch_size:
@@ -167,6 +185,50 @@ def resolve_group(obs_drt_list, obs_tau_indices, nonneg, num_tau_super, batch_si
         starts.append(start)
         if start + batch_size >= num_obs:
             break
+    return batch_size, starts
+
+
+def average_batches(obs_drt_list, starts, batch_size, overlap, num_tau_super, x_sol, matches, special):
+    """drtmd.py:516-559: the batches' solutions x_sol[i] (nr, nc_i) on their common ranges matches[i], unpacked to data units and
+    averaged over the overlaps with weights growing with the distance from the batch edge.  Returns (obs_x_resolved
+    (num_obs, num_tau_super), obs_special_resolved dict)."""
+    num_obs = len(obs_drt_list)
+    x_batch = np.zeros((len(starts), num_obs, num_tau_super))
+    sp_batch = {k: np.zeros((len(starts), num_obs) + ((v.get('size', 1),) if v.get('size', 1) > 1 else ()))
+                for k, v in special.items()}
+    margins = -np.ones((len(starts), num_obs))
+    # The reference runs the batches one after the other on ONE array: a batch overwrites its observations' rows inside its own
+    # common tau range only (drtmd.py:476) and then records a copy of those rows (drtmd.py:531) -- where a later batch's range is
+    # shorter, the copy still holds what the earlier batch wrote outside it.  Same here, on the solutions of the batched launch.
+    rows = np.zeros((num_obs, num_tau_super))
+    for i, (a, match) in enumerate(zip(starts, matches)):
+        x_drt, x_special = unpack_resolved_x(np.asarray(x_sol[i]).reshape(batch_size, -1), obs_drt_list[a:a + batch_size], special)
+        rows[a:a + batch_size, match[0]:match[1]] = x_drt
+        x_batch[i, a:a + batch_size] = rows[a:a + batch_size]
+        for k, v in x_special.items():
+            sp_batch[k][i, a:a + batch_size] = v
+        margins[i, a:a + batch_size] = np.minimum(np.arange(batch_size), np.arange(batch_size)[::-1])
+    if overlap > 0 and num_obs > 1:
+        w = margins + 0.1                          # drtmd.py:541-546: edge observations still count a little
+        w[w < 0] = 0
+        x_res = np.average(x_batch, axis=0, weights=np.repeat(w[:, :, None], num_tau_super, axis=2))
+        sp_res = {k: np.average(v, axis=0, weights=w if v.ndim == 2 else np.repeat(w[:, :, None], v.shape[-1], axis=2))
+                  for k, v in sp_batch.items()}
+    else:
+        # without overlap every observation is written by exactly one batch
+        x_res = x_batch.sum(axis=0)
+        sp_res = {k: v.sum(axis=0) for k, v in sp_batch.items()}
+    return x_res, sp_res
+
+
+def resolve_group(obs_drt_list, obs_tau_indices, nonneg, num_tau_super, batch_size=7, overlap=2, truncate=False, sigma=1,
+                  lambda_psi=1, tau_filter_sigma=0, special_filter_sigma=0, device=0):
+    """DRTMD.resolve_group (hybdrt/mapping/drtmd.py:486-559) for observations already sorted along psi: overlapping batches
+    of `batch_size` observations are re-optimised coherently (resolve_observations each) and the overlaps averaged with
+    weights growing with the distance from the batch edge.  The batches are independent QPs: all of one size go to the device as
+    ONE batched launch (one size when every observation was fitted on the same tau range).  Returns (obs_x_resolved (num_obs, num_tau_super), obs_special_resolved dict)."""
+    num_obs = len(obs_drt_list)
+    batch_size, starts = group_batch_starts(num_obs, batch_size, overlap)
     if num_obs == 1:
         raise ValueError("Only one observation included in resolution group")
     probs = [resolve_observations(obs_drt_list[a:a + batch_size], obs_tau_indices[a:a + batch_size], nonneg,
@@ -186,31 +248,86 @@ def resolve_group(obs_drt_list, obs_tau_indices, nonneg, num_tau_super, batch_si
         for j, i in enumerate(members):
             x_sol[i], iterations[i] = res['x'][j], int(res['iterations'][j])
     resolve_group.last_qp = dict(iterations=iterations, launches=len(by_size))
-    special = probs[0][3]
-    x_batch = np.zeros((len(starts), num_obs, num_tau_super))
-    sp_batch = {k: np.zeros((len(starts), num_obs) + ((v.get('size', 1),) if v.get('size', 1) > 1 else ()))
-                for k, v in special.items()}
-    margins = -np.ones((len(starts), num_obs))
-    # The reference runs the batches one after the other on ONE array: a batch overwrites its observations' rows inside its own
-    # common tau range only (drtmd.py:476) and then records a copy of those rows (drtmd.py:531) -- where a later batch's range is
-    # shorter, the copy still holds what the earlier batch wrote outside it.  Same here, on the solutions of the batched launch.
-    rows = np.zeros((num_obs, num_tau_super))
-    for i, (a, pr) in enumerate(zip(starts, probs)):
-        _, _, _, sp_, match, nr, nc = pr
-        x_drt, x_special = unpack_resolved_x(x_sol[i].reshape(nr, nc), obs_drt_list[a:a + batch_size], sp_)
-        rows[a:a + batch_size, match[0]:match[1]] = x_drt
-        x_batch[i, a:a + batch_size] = rows[a:a + batch_size]
-        for k, v in x_special.items():
-            sp_batch[k][i, a:a + batch_size] = v
-        margins[i, a:a + batch_size] = np.minimum(np.arange(batch_size), np.arange(batch_size)[::-1])
-    if overlap > 0 and num_obs > 1:
-        w = margins + 0.1                          # drtmd.py:541-546: edge observations still count a little
-        w[w < 0] = 0
-        x_res = np.average(x_batch, axis=0, weights=np.repeat(w[:, :, None], num_tau_super, axis=2))
-        sp_res = {k: np.average(v, axis=0, weights=w if v.ndim == 2 else np.repeat(w[:, :, None], v.shape[-1], axis=2))
-                  for k, v in sp_batch.items()}
-    else:
-        # without overlap every observation is written by exactly one batch
-        x_res = x_batch.sum(axis=0)
-        sp_res = {k: v.sum(axis=0) for k, v in sp_batch.items()}
-    return x_res, sp_res
+    return average_batches(obs_drt_list, starts, batch_size, overlap, num_tau_super, x_sol, [pr[4] for pr in probs], probs[0][3])
+
+
+# ---- the same coupled problems from what a fitted device batch already holds (csrc/resolve.hip) -----------------------------------
+def resolve_args(obs_drt_list, obs_tau_indices, nonneg, starts, batch_size, truncate=False, sigma=1, lambda_psi=1,
+                 tau_filter_sigma=0, special_filter_sigma=0):
+    """The description hipdrt_plan_resolve_group takes (include/hipdrt.h) for the batches starts[k] .. starts[k] + batch_size - 1 of
+    the sorted observations: everything resolve_observations derives from a fitted observation EXCEPT its P and q -- the special
+    table, the scales, the tau indices, the fitted R_inf / x_dop / v_baseline / vz_offset.  obs_drt_list: objects that carry
+    fit_parameters (no p_matrix needed), special_qp_params and the scale attributes (DRT.batch_fits(with_p=False)).  Returns a dict:
+    nb, nr, num_remove, so, lambda_psi, tau_filter_sigma, special_filter_sigma; first (nb,), match (nb, 2), tau_indices (B, 2),
+    x_remove (B, num_remove), my (nb, nr, nr); param_scale and h, one array per batch; special, the table after the removal."""
+    special = offset_special_dict(obs_drt_list[0].special_qp_params)
+    so = int(sum(v.get('size', 1) for v in special.values()))
+    x_remove = np.array([removed_values(drt) for drt in obs_drt_list]).reshape(len(obs_drt_list), -1)
+    nr = int(batch_size)
+    match, my, param_scale, h = [], [], [], []
+    for a in starts:
+        members = obs_drt_list[a:a + nr]
+        m = get_tau_indices(obs_tau_indices[a:a + nr], truncate=truncate)
+        nc = so + m[1] - m[0]
+        my_k, ps_k, _ = coupling(members, special, nc, sigma)
+        match.append(m); my.append(my_k); param_scale.append(ps_k); h.append(bound_vector(special, nonneg, nr, nc))
+    return dict(nb=len(starts), nr=nr, num_remove=x_remove.shape[1], so=so, lambda_psi=float(lambda_psi),
+                tau_filter_sigma=float(tau_filter_sigma), special_filter_sigma=float(special_filter_sigma),
+                first=np.asarray(starts, dtype=np.int32), match=np.asarray(match, dtype=np.int32).reshape(-1, 2),
+                tau_indices=np.asarray(obs_tau_indices, dtype=np.int32).reshape(-1, 2), x_remove=x_remove,
+                my=np.asarray(my, dtype=float).reshape(-1, nr, nr), param_scale=param_scale, h=h, special=special)
+
+
+def member_columns(args, k, b):
+    """for batch k of a description and its member b: the member's own unknown behind every column of its block (nc_k,), -1 where
+    the member has no basis function (resize_pq's four cases as one index rule: the special unknowns keep their place, the DRT
+    block is shifted by the distance between the two left ends and cut at either end)"""
+    so, nrm = args['so'], args['num_remove']
+    left, right = (int(v) for v in args['tau_indices'][b])
+    ml, mr = (int(v) for v in args['match'][k])
+    s = np.arange(mr - ml) + ml - left
+    drt = np.where((s >= 0) & (s < right - left), nrm + so + s, -1)
+    return np.concatenate([nrm + np.arange(so), drt]).astype(int)
+
+
+def assemble_statement(args, p_list, q_list):
+    """The numpy statement of csrc/resolve.hip: for every batch of the description `args` (resolve_args) the coupled (P_k, q_k) from
+    the members' own P (n_b, n_b) and q (n_b,).  Entry by entry what resolve_observations(_assemble_only=True) builds for
+    tau_filter_sigma = special_filter_sigma = 0: P bit for bit, q up to the order of its num_remove + 1 term sum."""
+    if args['tau_filter_sigma'] > 0 or args['special_filter_sigma'] > 0:
+        raise NotImplementedError('tau_filter_sigma / special_filter_sigma > 0: the blocks are dense, see resolve_observations')
+    nr, nrm, lam = args['nr'], args['num_remove'], args['lambda_psi']
+    out = []
+    for k in range(args['nb']):
+        my, ps = args['my'][k], np.asarray(args['param_scale'][k], dtype=float)
+        nc = len(ps)
+        p_k, q_k = np.zeros((nr * nc, nr * nc)), np.zeros(nr * nc)
+        diag = np.arange(nc)
+        for i in range(nr):
+            for j in range(nr):
+                p_k[i * nc + diag, j * nc + diag] = ps * my[i, j] * lam
+        for i in range(nr):
+            b = int(args['first'][k]) + i
+            p, q = np.asarray(p_list[b], dtype=float), np.asarray(q_list[b], dtype=float)
+            src = member_columns(args, k, b)
+            there = src >= 0
+            block = np.zeros((nc, nc))
+            block[np.ix_(there, there)] = p[np.ix_(src[there], src[there])]
+            p_k[i * nc:(i + 1) * nc, i * nc:(i + 1) * nc] += block
+            q_off = q[nrm:] + args['x_remove'][b] @ p[:nrm, nrm:]
+            q_k[i * nc + np.where(there)[0]] = q_off[src[there] - nrm]
+        out.append((p_k, q_k))
+    return out
+
+
+def resolve_batches_on_plan(plan, obs_drt_list, obs_tau_indices, nonneg, starts, batch_size, truncate=False, sigma=1, lambda_psi=1):
+    """The batches of resolve_group solved from a fitted prepared plan (hipdrt_plan_resolve_group): nothing but the description goes
+    up, nothing but the solutions comes back.  Returns (x_sol: one (nr, nc_k) array per batch, their common tau ranges, the special
+    table after the removal, the QPs' iteration counts).  Raises ValueError when a QP breaks down (cvxopt's error)."""
+    args = resolve_args(obs_drt_list, obs_tau_indices, nonneg, starts, batch_size, truncate=truncate, sigma=sigma,
+                        lambda_psi=lambda_psi)
+    res = plan.resolve_group(args)
+    if np.any(res['status'] < 0):
+        raise ValueError("Rank(A) < p or Rank([P; A; G]) < n")
+    matches = [tuple(int(v) for v in m) for m in args['match']]
+    return res['x'], matches, args['special'], [int(v) for v in res['iterations']]

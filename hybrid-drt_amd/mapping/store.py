@@ -25,7 +25,12 @@ The fitted map is read through the prediction block (drtmd.py:788-1106): ``predi
 mapping.predict, the same arithmetic in numpy).  The store keeps no fits and no covariances: with ``store_eval_var=True`` every
 device batch also leaves the raw variances of the DRT and of its curvature on get_tau_eval(10) in ``obs_f_var`` / ``obs_fxx_var``.
 
-Not here (out of scope): file readers, psi interpolation, resolve bookkeeping, pickling."""
+Neighbouring observations can be re-optimised coherently: ``resolve_observations`` / ``resolve_group`` (drtmd.py:432-559) write
+``obs_x_resolved`` / ``obs_special_resolved``, which ``filter_observations(resolved=True)`` then reads.  The store keeps no fits, so a
+resolve refits its observations as ONE prepared device batch and hands that plan to mapping.resolve.resolve_batches_on_plan: the
+coupled QPs are assembled from the members' final P and q where they lie (csrc/resolve.hip) and solved there.
+
+Not here (out of scope): file readers, psi interpolation, pickling."""
 import warnings
 
 import numpy as np
@@ -34,6 +39,7 @@ from . import drtmd as _driver
 from . import nddata
 from . import predict as _predict
 from .ndx import filter_ndx
+from . import resolve as _resolve
 from .resolve import get_tau_indices
 from .table import new_special, tau_slots
 
@@ -67,7 +73,7 @@ class DRTMD:
         self.obs_x_filt = np.zeros_like(self.obs_x)
         self.obs_special = None
         self.obs_special_filt = {}
-        # the store keeps no resolve bookkeeping: a caller that resolves (mapping.resolve) may set these for filter_observations
+        # None until the first resolve_observations / resolve_group (or until a caller that resolved elsewhere sets them)
         self.obs_x_resolved, self.obs_special_resolved = None, None
         self.obs_llh, self.obs_rss = np.zeros(0), np.zeros(0)
         self.obs_data_badness, self.obs_fit_badness = np.zeros(0), np.zeros(0)                   # drtmd.py:121-122
@@ -104,6 +110,10 @@ class DRTMD:
         self.obs_x_filt = np.concatenate([self.obs_x_filt, np.zeros((1,) + self.obs_x_filt.shape[1:])])
         for key, val in self.obs_special_filt.items():
             self.obs_special_filt[key] = np.concatenate([val, np.zeros((1,) + val.shape[1:])])
+        if self.obs_x_resolved is not None:
+            self.obs_x_resolved = np.concatenate([self.obs_x_resolved, np.zeros((1,) + self.obs_x_resolved.shape[1:])])
+        for key, val in (self.obs_special_resolved or {}).items():
+            self.obs_special_resolved[key] = np.concatenate([val, np.zeros((1,) + val.shape[1:])])
         self.obs_llh, self.obs_rss = np.append(self.obs_llh, 0.0), np.append(self.obs_rss, 0.0)
         self.obs_data_badness, self.obs_fit_badness = np.append(self.obs_data_badness, 0.0), np.append(self.obs_fit_badness, 0.0)
         if self.obs_special is not None:
@@ -188,6 +198,115 @@ class DRTMD:
             obs_index = obs_index[~self.obs_ignore_flag[obs_index]]
         return obs_index
 
+    # ---- resolution (drtmd.py:432-559) ----
+    def _resolve_selection(self, obs_index, psi_sort_dims):
+        """fitted and not ignored, in the order of psi_sort_dims (drtmd.py:436-443, 492-505)"""
+        obs_index = np.asarray(obs_index, dtype=int).ravel()
+        obs_index = obs_index[self.obs_fit_status[obs_index] & ~self.obs_ignore_flag[obs_index]]
+        if psi_sort_dims is not None:
+            sort_vals = [self.obs_psi[obs_index, self.psi_dim_names.index(d)] for d in psi_sort_dims][::-1]
+            obs_index = obs_index[np.lexsort(sort_vals)]
+        return obs_index
+
+    def _resolved_arrays(self):
+        if self.fit_type == 'pfrt':
+            raise NotImplementedError("fit_type='pfrt': resolve takes one DRT per observation")
+        if self.obs_x_resolved is None:
+            self.obs_x_resolved = np.zeros_like(self.obs_x)
+        if self.obs_special_resolved is None:
+            # initialize_obs_special (drtmd.py:1160-1166): zeros under every fitted special parameter -- v_baseline and vz_offset,
+            # which a resolve eliminates, keep them
+            self.obs_special_resolved = {key: np.zeros_like(val) for key, val in (self.obs_special or {}).items()}
+
+    def _write_resolved_special(self, obs_index, special):
+        for key, val in special.items():
+            if key not in self.obs_special_resolved:
+                self.obs_special_resolved[key] = new_special(self.num_obs, val)
+            self.obs_special_resolved[key][obs_index] = val
+
+    def _refit_members(self, obs_index):
+        """The store keeps no fits: the selected observations once more, as ONE prepared device batch through the driver.  Returns
+        the plan, still holding that batch, and one view per observation of what resolve reads from a fit beside P and q
+        (DRT.batch_fits).  Nothing of the store is written.  EIS-only observations raise upstream's KeyError: get_offset_pq needs
+        the v_baseline / vz_offset of a joint fit."""
+        observations = [self.obs_data[i] for i in obs_index]
+        if all(kind == 'eis' for kind, _ in _driver.observation_groups(observations)):
+            raise KeyError('v_baseline')
+        _, _, res = _driver.fit_observations(self.drt1d, observations=observations, tau_supergrid=self.tau_supergrid, drt_var=False,
+                                             ignore_errors=True, llh_kw=self.llh_kw, rss_kw=self.rss_kw, **self.fit_kw)
+        if len(res['groups']) != 1:
+            raise NotImplementedError("resolve on the store takes observations that share one protocol (data type, sampling grids): "
+                                      f"these fall into {len(res['groups'])} device batches; use mapping.resolve.resolve_group on "
+                                      "their fits")
+        if not np.all(res['obs_fit_status']):
+            raise RuntimeError(f"observation {obs_index[int(np.argmin(res['obs_fit_status']))]} was fitted before and failed now")
+        return self.drt1d._plan, self.drt1d.batch_fits(with_p=False)
+
+    def _resolve_batches(self, obs_index, starts, batch_size, overlap, truncate, sigma, lambda_psi, tau_filter_sigma,
+                         special_filter_sigma):
+        """the batches of sorted observations obs_index -> (obs_x_resolved rows (len(obs_index), num_tau), specials) averaged over the
+        overlaps.  Assembled and solved on the device from the refitted plan; with a tau or special filter the coupled P is dense
+        across its blocks, which the device assembly does not build: those go through the host-assembled path
+        (mapping.resolve.resolve_group on the members' downloaded P)."""
+        tau_indices = [self.obs_tau_indices[i] for i in obs_index]
+        nonneg, nsup = self.fit_kw['nonneg'], len(self.tau_supergrid)
+        plan, members = self._refit_members(obs_index)
+        if tau_filter_sigma > 0 or special_filter_sigma > 0:
+            fits = self.drt1d.batch_fits()
+            out = _resolve.resolve_group(fits, tau_indices, nonneg, nsup, batch_size=batch_size, overlap=overlap, truncate=truncate,
+                                         sigma=sigma, lambda_psi=lambda_psi, tau_filter_sigma=tau_filter_sigma,
+                                         special_filter_sigma=special_filter_sigma, device=self.drt1d.device)
+            self.last_resolve = dict(_resolve.resolve_group.last_qp, path='host')
+            return out
+        x_sol, matches, special, iterations = _resolve.resolve_batches_on_plan(
+            plan, members, tau_indices, nonneg, starts, batch_size, truncate=truncate, sigma=sigma, lambda_psi=lambda_psi)
+        self.last_resolve = dict(iterations=iterations, path='device')
+        return _resolve.average_batches(members, starts, batch_size, overlap, nsup, x_sol, matches, special)
+
+    def resolve_observations(self, obs_index, psi_sort_dims=None, truncate=False, sigma=1, lambda_psi=1, tau_filter_sigma=0,
+                             special_filter_sigma=0):
+        """drtmd.py:432-484: the listed observations (fitted, not ignored, sorted along psi_sort_dims) re-optimised as ONE coupled
+        problem, into obs_x_resolved (inside their common tau range) and obs_special_resolved.  One observation: its raw parameters
+        are copied, with upstream's warning.  tau_filter_sigma / special_filter_sigma > 0 fall back to the host-assembled path
+        (_resolve_batches).  Raises ValueError when the QP breaks down (cvxopt's error), KeyError for EIS-only observations."""
+        obs_index = self._resolve_selection(obs_index, psi_sort_dims)
+        if len(obs_index) == 0:
+            warnings.warn("No valid observations included in resolution group")
+            return
+        self._resolved_arrays()
+        if len(obs_index) == 1:
+            warnings.warn("Only one observation included in resolution group; raw parameters will be copied")
+            left, right = self.obs_tau_indices[obs_index[0]]
+            self.obs_x_resolved[obs_index, left:right] = self.obs_x[obs_index, left:right]
+            self._write_resolved_special(obs_index, {k: v[obs_index] for k, v in (self.obs_special or {}).items()})
+            return
+        left, right = get_tau_indices([self.obs_tau_indices[i] for i in obs_index], truncate=truncate)
+        x_res, sp_res = self._resolve_batches(obs_index, [0], len(obs_index), 0, truncate, sigma, lambda_psi, tau_filter_sigma,
+                                              special_filter_sigma)
+        self.obs_x_resolved[obs_index, left:right] = x_res[:, left:right]
+        self._write_resolved_special(obs_index, sp_res)
+
+    def resolve_group(self, group_id, batch_size=7, overlap=2, psi_sort_dims=None, truncate=False, sigma=1, lambda_psi=1,
+                      tau_filter_sigma=0, special_filter_sigma=0):
+        """drtmd.py:486-559: the group's observations (fitted, not ignored, sorted along psi_sort_dims) in overlapping batches of
+        batch_size, every batch one coupled problem, the overlaps averaged with weights growing with the distance from the batch
+        edge (mapping.resolve.group_batch_starts, average_batches); obs_x_resolved rows of the group are cleared first.  All batches
+        are assembled on the device from one refit of the group and solved there, one launch per problem size.  Raises ValueError
+        for a group of one observation and when a QP breaks down, KeyError for EIS-only observations."""
+        obs_index = self._resolve_selection(self.get_group_index(group_id), psi_sort_dims)
+        if len(obs_index) == 0:
+            warnings.warn("No valid observations included in resolution group")
+            return
+        self._resolved_arrays()
+        self.obs_x_resolved[obs_index] = 0
+        if len(obs_index) == 1:
+            raise ValueError("Only one observation included in resolution group")
+        batch_size, starts = _resolve.group_batch_starts(len(obs_index), batch_size, overlap)
+        x_res, sp_res = self._resolve_batches(obs_index, starts, batch_size, overlap, truncate, sigma, lambda_psi, tau_filter_sigma,
+                                              special_filter_sigma)
+        self.obs_x_resolved[obs_index] = x_res
+        self._write_resolved_special(obs_index, sp_res)
+
     def filter_observations(self, obs_index, psi_sort_dims=None, truncate=False, resolved=True, special_kw=None, **kw):
         """drtmd.py:561-628: smooth the fitted coefficients of the listed observations across psi (rows, in the order of
         psi_sort_dims) and tau with mapping.ndx.filter_ndx(**kw) on the device, into obs_x_filt / obs_special_filt.  x_dop is
@@ -199,8 +318,8 @@ class DRTMD:
             sort_vals = [self.obs_psi[obs_index, self.psi_dim_names.index(d)] for d in psi_sort_dims][::-1]
             obs_index = obs_index[np.lexsort(sort_vals)]
         if resolved and (self.obs_x_resolved is None or self.obs_special_resolved is None):
-            raise ValueError("resolved=True needs obs_x_resolved / obs_special_resolved, which this store does not fill: set them, "
-                             "or pass resolved=False to filter the fitted parameters")
+            raise ValueError("resolved=True needs obs_x_resolved / obs_special_resolved: run resolve_group / resolve_observations "
+                             "first (or set them), or pass resolved=False to filter the fitted parameters")
         x_drt_in = self.obs_x_resolved if resolved else self.obs_x
         special_in = (self.obs_special_resolved if resolved else self.obs_special) or {}
         if special_kw is None:

@@ -683,15 +683,16 @@ class PreparedFitMixin:
         meas = [(times, i_batch[b], v_batch[b], frequencies, z_batch[b]) for b in range(len(z_batch))]
         return self._fit_prepared_batch(meas, kw)
 
-    def batch_fits(self):
+    def batch_fits(self, with_p=True):
         """Per-observation views of the last prepared batch fit, carrying what the mapping step reads from a fitted DRT
         (fit_parameters incl. p_matrix / q_vector, special_qp_params, the scale attributes): feed them to
-        hipdrt.mapping.resolve.resolve_observations / resolve_group."""
+        hipdrt.mapping.resolve.resolve_observations / resolve_group.  with_p=False downloads no P: what
+        mapping.resolve.resolve_args needs beside the plan itself."""
         import types
         preps, fps = self._last_prepared
         fits = []
         for b, (pr, fp) in enumerate(zip(preps, fps)):
-            fp = dict(fp, p_matrix=self._plan.p_matrix(b))
+            fp = dict(fp, p_matrix=self._plan.p_matrix(b)) if with_p else dict(fp)
             fits.append(types.SimpleNamespace(
                 fit_parameters=fp, special_qp_params=pr['special'], coefficient_scale=pr['coefficient_scale'],
                 impedance_scale=pr['impedance_scale'], response_signal_scale=pr['response_signal_scale'],

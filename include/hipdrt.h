@@ -1043,6 +1043,39 @@ void hipdrt_default_lml_in(hipdrt_lml_in* in);
  * plans; a vz_offset column is taken as the fit left it.  A spectrum's result depends neither on B nor on its position.              */
 int hipdrt_plan_lml_terms(hipdrt_plan* plan, const hipdrt_lml_in* in, hipdrt_lml_out* out);
 
+/* ---- coherent re-optimisation of neighbouring observations, assembled on the device --------------------------------------------------
+ * DRTMD.resolve_observations / resolve_group (hybdrt/mapping/drtmd.py:432-559) over resolve.resolve_observations
+ * (hybdrt/mapping/resolve.py:176-341) for the members of a fitted PREPARED batch: every coupled batch k takes the nr consecutive
+ * members first[k] .. first[k] + nr - 1; their final P (what hipdrt_plan_get_p_matrix returns) and q never leave the device.  With
+ * nc_k = so + match[k][1] - match[k][0] unknowns per member, P_k (nr nc_k square) and q_k are written in the form the coneqp
+ * launchers read (lower 16 x 16 tiles):
+ *     block (i, i)   member i's P without its leading num_remove data-dependent unknowns (v_baseline, vz_offset; get_offset_pq,
+ *                    resolve.py:11-64), its tau range tau_indices[b] moved into match[k] (resize_pq's four cases, resolve.py:67-134;
+ *                    zero where the member has no basis function), plus param_scale[c] * my[i][i] * lambda_psi on the diagonal;
+ *     block (i, j)   the diagonal matrix param_scale[c] * my[i][j] * lambda_psi;
+ *     q_k block i    q_trim + x_remove_i @ P_i[:num_remove, num_remove:], resized alike.
+ * Products and the single add round as numpy's (no fused multiply-add); q's short sum runs in index order.  All batches of one size
+ * are then solved in one coneqp launch, with the kernel choice and default options of hipdrt_qp_batch for that many problems of that
+ * size.                                                                                                                              */
+typedef struct {
+    int nb, nr;                       /* coupled batches; members of every batch (>= 1)                                               */
+    int num_remove, so;               /* leading unknowns dropped from every member; special unknowns kept behind them                */
+    double lambda_psi;
+    double tau_filter_sigma, special_filter_sigma;   /* > 0 makes P dense across blocks: HIPDRT_E_UNSUPPORTED                         */
+    const int* first;                 /* [nb] first member of batch k                                                                 */
+    const int* match;                 /* [nb][2] the batch's common tau range (left, right) on the supergrid                          */
+    const int* tau_indices;           /* [B][2] every member's own range; right - left = n - num_remove - so                          */
+    const double* my;                 /* [nb][nr][nr] coupling across the members of a batch (exactly symmetric)                      */
+    const double* param_scale;        /* nc_k entries for batch k, batch after batch                                                  */
+    const double* x_remove;           /* [B][num_remove] fitted values of the dropped unknowns; NULL with num_remove = 0              */
+    const double* h;                  /* nr * nc_k entries for batch k, batch after batch (the QP's bound; read by the solve only)    */
+} hipdrt_resolve_args;
+/* x_out: batch k's nr * nc_k unknowns, batch after batch; iters_out (may be NULL) and status_out [nb]: as hipdrt_qp_batch returns them.
+ * HIPDRT_E_INVALID before any launch: a plan that is not prepared or holds no fitted batch, a member outside the batch, a range that
+ * is empty or does not match n, nr * nc_k > 4096, nb > 65535.  HIPDRT_E_UNSUPPORTED for either filter sigma > 0 (the caller assembles
+ * those on the host and uses hipdrt_qp_batch).  Reads the fitted state only: the plan can be fitted, read or resolved again.          */
+int hipdrt_plan_resolve_group(hipdrt_plan* plan, const hipdrt_resolve_args* args, double* x_out, int* iters_out, int* status_out);
+
 /* kernel-time breakdown of the last hipdrt_plan_fit in ms (HIP events on the ctx stream):
  * t[0]=total, t[1]=gram, t[2]=qp, t[3]=hyper, t[4]=setup/other; launches[5] same order                 */
 int hipdrt_plan_timings(hipdrt_plan* plan, float* t, int* launches);

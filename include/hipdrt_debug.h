@@ -13,6 +13,7 @@
  * hipdrt_debug_lpt_order (the dispatch-order kernel alone).  The map kernels have hipdrt_debug_map_gaussian (the separable filter
  * passes in their LDS and uncached forms), hipdrt_debug_map_reduce (the fixed-order mean, std and min / max) and hipdrt_debug_map_prob
  * (the clamp and probability kernels of a map's rows, fed f and fxx directly); the rank filters are reached through their entry point.
+ * The assembly kernels of hipdrt_plan_resolve_group have hipdrt_debug_resolve_assemble (members of their own sizes in, dense P_k out).
  */
 #ifndef HIPDRT_DEBUG_H
 #define HIPDRT_DEBUG_H
@@ -375,6 +376,16 @@ int hipdrt_debug_map_reduce(hipdrt_ctx* ctx, const double* x, long long n, int m
 int hipdrt_debug_map_prob(hipdrt_ctx* ctx, int rows, int n, const double* f, const double* fxx, const double* vf, const double* vxx,
                           const int* ext, int clamp_first, int search, double height, double prominence, int sign_now, double* pk,
                           double* curv, double* vf_out, double* vxx_out);
+
+/* test hook (tests/test_gpu_store_resolve.py): the assembly kernels of hipdrt_plan_resolve_group (csrc/resolve.hip) alone, on host
+ * arrays -- args as there (h is not read), B members of their own sizes n_b = num_remove + so + right_b - left_b:
+ *   P: member b's row-major n_b x n_b matrix, member after member; q: its n_b entries, member after member.
+ * Out: P_out, batch k's dense (nr nc_k) square matrix, batch after batch, unpacked from the lower tiles the kernel wrote (the upper
+ * triangle is the mirror image, as the QP reads it); q_out, batch k's nr nc_k entries, batch after batch.  The packed image, q and
+ * every input sit between borders of marker bytes: HIPDRT_E_NUMERIC when a kernel changed one, when a padding entry of a tile is not
+ * zero, or when a diagonal tile is not symmetric.  HIPDRT_E_INVALID / HIPDRT_E_UNSUPPORTED, and nothing is launched, as the entry point. */
+int hipdrt_debug_resolve_assemble(hipdrt_ctx* ctx, const hipdrt_resolve_args* args, int B, const double* P, const double* q,
+                                  double* P_out, double* q_out);
 
 #ifdef __cplusplus
 }
