@@ -7,8 +7,8 @@ module holds what (debug: the DebugHooks that Context mixes in).  Callers write 
 from . import abi
 from .abi import *                                                   # noqa: F401,F403 (every public name of the headers' mirror)
 from .abi import _HERE, _RESTYPES, _check, _dp, _f64, _i32, _ip, _lock, _p, _pi, _vp      # noqa: F401
-from .args import Bound                                              # noqa: F401
-from .opts import (default_fit_opts, kk_opts, PEAK_METHODS, peak_opts, pfrt_opts, pfrt_bytes_per_spectrum,    # noqa: F401
+from .args import Bound, pfrt_select_bound                                              # noqa: F401
+from .opts import (default_fit_opts, kk_opts, PEAK_METHODS, peak_opts, pfrt_opts, pfrt_select_opts, pfrt_bytes_per_spectrum,    # noqa: F401
                    peak_resolve_opts, _resolve_outputs, _resolve_out_struct, _PEAK_INT, _PEAK_F64, _peak_outputs, _peak_out_args,
                    _kk_outputs, PEAK_PROB_SEARCH, peak_prob_opts, _peak_prob_outputs, _peak_prob_out_args, _index_windows)
 from .context import Context, _default_ctx, device_usable, get_context      # noqa: F401

@@ -95,6 +95,12 @@ class PfrtOpts(C.Structure):
                 ("smooth_epsilon", C.c_double), ("integrate", C.c_int), ("integrate_threshold", C.c_double), ("normalize", C.c_int)]
 
 
+class PfrtSelectOpts(C.Structure):
+    """hipdrt_pfrt_select_opts (include/hipdrt.h)"""
+    _fields_ = [("start_thresh", C.c_double), ("end_thresh", C.c_double), ("peak_thresh", C.c_double), ("max_peaks", C.c_int),
+                ("ln_tau_out", _dp), ("neval_out", C.c_int)]
+
+
 class PeakResolveOpts(C.Structure):
     """hipdrt_peak_resolve_opts (include/hipdrt.h)"""
     _fields_ = [("sign", C.c_int), ("max_peaks", C.c_int), ("epsilon_factor", C.c_double), ("max_epsilon", C.c_double),
@@ -124,6 +130,13 @@ class CandidatesOut(C.Structure):
     """hipdrt_candidates_out (include/hipdrt.h)"""
     _fields_ = [("rss", _dp), ("sum_log_w", _dp), ("count", _ip), ("peak_index", _ip), ("heights", _dp), ("prominences", _dp),
                 ("status", _ip)]
+
+
+class PfrtSelectOut(C.Structure):
+    """hipdrt_pfrt_select_out (include/hipdrt.h)"""
+    _fields_ = [("num_peaks", _ip), ("ranked_index", _ip), ("first", _ip), ("num_candidates", _ip), ("step_index", _ip),
+                ("magnitude", _dp), ("match_quality", _dp), ("raw_pfrt", _dp), ("step_pfrt", _dp), ("post_prob", _dp),
+                ("pfrt", _dp)]
 
 
 class LmlIn(C.Structure):
@@ -299,6 +312,9 @@ PEAKS_FROM_FIND, PEAKS_FROM_INDICES, PEAKS_FROM_WINDOWS = 0, 1, 2
 CANDIDATES_FROM_STEPS, CANDIDATES_FROM_HOST = 0, 1
 CANDIDATE_ABSENT = -6                               # status of a slot at or past the spectrum's ncand (hipdrt_plan_score_candidates)
 CANDIDATE_OUTPUTS = ("rss", "sum_log_w", "count", "peak_index", "heights", "prominences", "status")
+PFRT_NO_PEAK, PFRT_TOO_MANY_PEAKS = 16, 17           # per-spectrum statuses of hipdrt_plan_pfrt_select
+PFRT_SELECT_COMPACT = ("num_peaks", "ranked_index", "first", "num_candidates", "step_index", "magnitude", "match_quality")
+PFRT_SELECT_ROWS = ("raw_pfrt", "step_pfrt", "post_prob", "pfrt")
 RESOLVE_OUTPUTS = ("count", "peak_index", "trough_index", "eps_l", "eps_r", "r_peaks", "r_coef", "x_peaks", "peak_gammas", "status")
 
 # include_mask bits of hipdrt_plan_predict_response and hipdrt_plan_predict_z_model (HIPDRT_INCLUDE_*)
@@ -400,6 +416,11 @@ SIGNATURES = {
     "hipdrt_plan_get_step_p_matrix": [_vp, C.c_int, C.c_int, _dp],
     "hipdrt_pfrt_opts_default": [C.POINTER(PfrtOpts)],
     "hipdrt_plan_predict_pfrt": [_vp, _dp, _dp, C.c_int, _dp, C.c_int, C.POINTER(PfrtOpts), _dp, _dp, _dp, _dp, _ip],
+    "hipdrt_pfrt_select_opts_default": [C.POINTER(PfrtSelectOpts)],
+    "hipdrt_plan_pfrt_select": [_vp, _dp, _dp, C.c_int, C.POINTER(PfrtOpts), C.POINTER(PfrtSelectOpts), C.POINTER(PfrtSelectOut),
+                                _ip],
+    "hipdrt_debug_pfrt_select": [_vp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.POINTER(PfrtSelectOpts),
+                                 C.POINTER(PfrtSelectOut), _ip],
     "hipdrt_debug_pfrt_step": [_vp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.c_double, C.c_int, C.c_int, _dp],
     "hipdrt_debug_pfrt_combine": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.POINTER(PfrtOpts), _dp, _dp,
                                   _dp, _dp, _dp],
@@ -463,7 +484,8 @@ SIGNATURES = {
 }
 _RESTYPES = {"hipdrt_last_error": C.c_char_p, "hipdrt_stream": C.c_void_p, "hipdrt_default_fit_opts": None,
              "hipdrt_default_kk_opts": None, "hipdrt_default_lml_in": None, "hipdrt_peak_opts_default": None, "hipdrt_peak_prob_opts_default": None,
-             "hipdrt_peak_resolve_opts_default": None, "hipdrt_pfrt_opts_default": None}
+             "hipdrt_peak_resolve_opts_default": None, "hipdrt_pfrt_opts_default": None,
+             "hipdrt_pfrt_select_opts_default": None}
 
 _lib = None
 _lock = threading.Lock()

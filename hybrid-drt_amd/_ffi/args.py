@@ -4,7 +4,7 @@ A ctypes pointer field does not keep its array alive, so every array goes throug
 the entry point takes, stored in the field and held in ``keep`` for as long as the Bound lives."""
 import numpy as np
 
-from .abi import ResolveArgs, _p, _pi
+from .abi import PFRT_SELECT_COMPACT, PFRT_SELECT_ROWS, PfrtSelectOut, ResolveArgs, _p, _pi
 
 
 class Bound:
@@ -78,3 +78,22 @@ def resolve_bound(args, num_members):
     b.array("param_scale", np.concatenate([np.asarray(v, dtype=np.float64) for v in args["param_scale"]]))
     b.array("h", np.concatenate([np.asarray(v, dtype=np.float64) for v in args["h"]]))
     return b, nc, np.concatenate([[0], np.cumsum([nr * v for v in nc])]).astype(int)
+
+
+def pfrt_select_bound(B, S, npf, max_peaks, want=None, rows=True, nout=0):
+    """hipdrt_pfrt_select_out with its host arrays, poisoned so that anything the kernel leaves unwritten shows (-77 / 7e77: -1
+    and NaN are the padding of unused slots): the compact form (num_peaks, first, num_candidates (B,); ranked_index, step_index,
+    magnitude, match_quality (B, max_peaks)) and, with `rows`, raw_pfrt (B, np), step_pfrt (S, B, np), post_prob (S, B); pfrt
+    (B, nout) only when `want` names it.  want: the names to form and download (None: all but pfrt) -> (Bound, dict of the arrays)"""
+    mp = max(1, min(int(max_peaks), 4096))          # (a count the library refuses still gets arrays to point at)
+    shapes = dict(num_peaks=(B,), ranked_index=(B, mp), first=(B,), num_candidates=(B,), step_index=(B, mp), magnitude=(B, mp),
+                  match_quality=(B, mp), raw_pfrt=(B, npf), step_pfrt=(S, B, npf), post_prob=(S, B), pfrt=(B, nout))
+    b = Bound(PfrtSelectOut())
+    out = {}
+    for k in PFRT_SELECT_COMPACT + (PFRT_SELECT_ROWS if rows else ()):
+        if (want is None and k == "pfrt") or (want is not None and k not in want):
+            continue
+        integer = k in PFRT_SELECT_COMPACT[:5]
+        out[k] = b.array(k, np.full(shapes[k], -77, dtype=np.int32) if integer else np.full(shapes[k], 7e77), shapes[k],
+                         dtype=np.int32 if integer else np.float64)
+    return b, out

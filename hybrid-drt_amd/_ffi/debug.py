@@ -7,9 +7,9 @@ import numpy as np
 
 from .abi import *            # noqa: F401,F403 (the constants and structures)
 from .abi import _check, _dp, _f64, _i32, _p, _pi
-from .args import Bound, resolve_bound
+from .args import Bound, pfrt_select_bound, resolve_bound
 from .opts import (_index_windows, _kk_outputs, _peak_out_args, _peak_outputs, _peak_prob_out_args, _peak_prob_outputs,
-                   _resolve_out_struct, _resolve_outputs, peak_opts, peak_prob_opts, peak_resolve_opts, pfrt_opts)
+                   _resolve_out_struct, _resolve_outputs, peak_opts, peak_prob_opts, peak_resolve_opts, pfrt_opts, pfrt_select_opts)
 
 
 class DebugHooks:
@@ -353,6 +353,21 @@ class DebugHooks:
         out = dict(pfrt=np.full((B, nout), 7e77), raw_pfrt=np.full((B, npf), 7e77), post_prob=np.full((S, B), 7e77))
         _check(self._lib.hipdrt_debug_pfrt_combine(self._h, B, S, npf, nout, _p(sp), _p(rss), _p(slw), _p(fac), int(m), C.byref(opts),
                                                    _p(ltp), _p(lto), _p(out["pfrt"]), _p(out["raw_pfrt"]), _p(out["post_prob"])))
+        return out
+
+    def debug_pfrt_select(self, raw_pfrt, step_pfrt, rss, sum_log_w, m, sel: PfrtSelectOpts | None = None):
+        """tests: pfrt_select_kernel on host arrays (hipdrt_debug_pfrt_select): raw_pfrt (B, np), step_pfrt (S, B, np), rss and
+        sum_log_w (S, B) -> dict of the compact form (see Plan.pfrt_select) and status (B,).  Raises when the kernel wrote outside
+        an output."""
+        raw, sp, rss, slw = _f64(raw_pfrt), _f64(step_pfrt), _f64(rss), _f64(sum_log_w)
+        if sp.ndim != 3 or raw.shape != sp.shape[1:] or rss.shape != sp.shape[:2] or slw.shape != sp.shape[:2]:
+            raise ValueError("shapes: raw_pfrt (B, np); step_pfrt (S, B, np); rss, sum_log_w (S, B)")
+        S, B, npf = sp.shape
+        sel = sel if sel is not None else pfrt_select_opts()
+        b, out = pfrt_select_bound(B, S, npf, sel.max_peaks, rows=False)
+        out["status"] = np.full(B, -77, dtype=np.int32)
+        _check(self._lib.hipdrt_debug_pfrt_select(self._h, B, S, npf, _p(raw), _p(sp), _p(rss), _p(slw), int(m), C.byref(sel),
+                                                  C.byref(b.c), _pi(out["status"])))
         return out
 
     def debug_candidate_llh(self, x, rm, rv, vmm, var_floor):

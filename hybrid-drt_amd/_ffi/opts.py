@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from .abi import (FitOpts, KkOpts, PeakOpts, PeakProbOpts, PeakResolveOpts, PeakResolveOut, PfrtOpts, RESOLVE_OUTPUTS, _check, _p, _pi,
+from .abi import (FitOpts, KkOpts, PeakOpts, PeakProbOpts, PeakResolveOpts, PeakResolveOut, PfrtOpts, PfrtSelectOpts, RESOLVE_OUTPUTS, _check, _p, _pi,
                   load_library)
 
 
@@ -76,6 +76,14 @@ def pfrt_opts(**kw) -> PfrtOpts:
         if k not in names:
             raise TypeError(f"hipdrt_pfrt_opts has no field {k!r}")
         setattr(o, k, type(getattr(o, k))(v))
+    return o
+
+
+def pfrt_select_opts(start_thresh=0.99, end_thresh=0.01, peak_thresh=1e-6, max_peaks=16) -> PfrtSelectOpts:
+    """hipdrt_pfrt_select_opts from the keywords of DRT.select_pfrt_candidates"""
+    o = PfrtSelectOpts()
+    load_library().hipdrt_pfrt_select_opts_default(C.byref(o))
+    o.start_thresh, o.end_thresh, o.peak_thresh, o.max_peaks = float(start_thresh), float(end_thresh), float(peak_thresh), int(max_peaks)
     return o
 
 

@@ -8,9 +8,9 @@ import numpy as np
 
 from .abi import *            # noqa: F401,F403 (the constants and structures)
 from .abi import _check, _f64, _i32, _p, _pi, _vp, load_library
-from .args import Bound, resolve_bound
+from .args import Bound, pfrt_select_bound, resolve_bound
 from .opts import (_index_windows, _kk_outputs, _peak_out_args, _peak_outputs, _peak_prob_out_args, _peak_prob_outputs, _resolve_out_struct, _resolve_outputs, default_fit_opts, peak_opts,
-                   peak_resolve_opts, pfrt_opts)
+                   peak_resolve_opts, pfrt_opts, pfrt_select_opts)
 
 
 class Plan:
@@ -379,6 +379,29 @@ class Plan:
         g = out.get
         _check(self._lib.hipdrt_plan_predict_pfrt(self._h, _p(fac), _p(ltp), npf, _p(lto), nout, C.byref(opts), _p(g("pfrt")),
                                                   _p(g("raw_pfrt")), _p(g("step_pfrt")), _p(g("post_prob")), _pi(out["status"])))
+        return out
+
+    def pfrt_select(self, factors, ln_tau_pfrt, opts: PfrtOpts | None = None, sel: PfrtSelectOpts | None = None, want=None,
+                    ln_tau_out=None):
+        """hipdrt_plan_pfrt_select over the recorded steps -> dict of the compact form (num_peaks, first, num_candidates (B,);
+        ranked_index, step_index, magnitude, match_quality (B, max_peaks); unused slots -1 / NaN), raw_pfrt (B, np), step_pfrt
+        (S, B, np), post_prob (S, B) and status (B,); want: the names to form and download (None: all of these); status always
+        comes.  'pfrt' in want: also the finished PFRT (B, nout) of the same pass, as predict_pfrt gives it for opts, on
+        ln_tau_out (None: the tau_pfrt grid)."""
+        fac, ltp = _f64(factors).ravel(), _f64(ln_tau_pfrt).ravel()
+        S = fac.size
+        if S != self.pfrt_steps():
+            raise ValueError(f"factors has {S} entries, the plan has recorded {self.pfrt_steps()} PFRT steps")
+        opts = opts if opts is not None else pfrt_opts()
+        sel = sel if sel is not None else pfrt_select_opts()
+        lto = None
+        if want is not None and "pfrt" in want:
+            lto = ltp if ln_tau_out is None else _f64(ln_tau_out).ravel()
+            sel.ln_tau_out, sel.neval_out = _p(lto), lto.size
+        b, out = pfrt_select_bound(self.B, S, ltp.size, sel.max_peaks, want, nout=0 if lto is None else lto.size)
+        out["status"] = np.empty(self.B, dtype=np.int32)
+        _check(self._lib.hipdrt_plan_pfrt_select(self._h, _p(fac), _p(ltp), ltp.size, C.byref(opts), C.byref(sel), C.byref(b.c),
+                                                 _pi(out["status"])))
         return out
 
     def set_init_h(self, h_init):

@@ -545,6 +545,24 @@ int pfrt_check(const hipdrt_pfrt_opts& o, int S, int np, int nout);
 int launch_pfrt_combine(hipStream_t s, const PfrtCombineArgs& a, int B);
 // c, alpha_n and beta_0 of PfrtCombineArgs for m data rows (evaluate_llh's defaults alpha_0 = 2, beta_0 = 1)
 void pfrt_llh_consts(int m, double* c, double* alpha_n, double* beta_0);
+// pfrt_select_kernel: pfrt.select_candidates (hybdrt/models/pfrt.py:164-213) on the raw PFRT and the steps' rows of every spectrum
+struct PfrtSelectArgs {
+    int S, np, max_peaks;
+    long long ld_step, ld_sum;           // as PfrtCombineArgs
+    const double* raw;                   // [B][np]
+    const double* step_pfrt;             // [S][B][np]
+    const double *rss, *slw;             // [S][ld_sum]
+    double c, alpha_n, beta_0;           // llh = (c - alpha_n ln(beta_0 + rss / 2)) + slw
+    double start_thresh, end_thresh, peak_thresh;
+    const int *fit_status, *bad;         // [B] or null: a negative status / a non-zero flag leaves every slot unused
+    int *num_peaks, *first, *num_candidates;       // [B] each; any output may be null
+    int *ranked_index, *step_index;      // [B][max_peaks]: unused slots hold -1
+    double *magnitude, *match_quality;   // [B][max_peaks]: unused slots hold NaN
+    int* status;                         // [B]: 0, HIPDRT_PFRT_NO_PEAK or HIPDRT_PFRT_TOO_MANY_PEAKS (required)
+};
+// the limits of hipdrt_plan_pfrt_select beyond pfrt_check's: thresholds that are numbers, 1 <= max_peaks <= 64
+int pfrt_select_check(const hipdrt_pfrt_select_opts& o);
+int launch_pfrt_select(hipStream_t s, const PfrtSelectArgs& a, int B);
 
 // candidates.hip: the likelihood sums of C candidate solutions per spectrum, 16 candidates of a spectrum per workgroup on the
 // matrix pipe, and the compaction of peaks_kernel's dense rows (all pointers device memory)

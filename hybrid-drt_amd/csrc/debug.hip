@@ -488,6 +488,38 @@ int hipdrt_debug_pfrt_combine(hipdrt_ctx* ctx, int B, int S, int neval_pfrt, int
     return outs.back(st);
 } HIPDRT_CATCH
 
+int hipdrt_debug_pfrt_select(hipdrt_ctx* ctx, int B, int S, int neval_pfrt, const double* raw_pfrt, const double* step_pfrt,
+                             const double* rss, const double* sum_log_w, int m, const hipdrt_pfrt_select_opts* sel,
+                             hipdrt_pfrt_select_out* out, int* status) try {
+    HIPDRT_REQUIRE(ctx && raw_pfrt && step_pfrt && rss && sum_log_w && out && status, "NULL pointer");
+    HIPDRT_REQUIRE(B >= 1 && B <= 65535 && m >= 1, "1 <= B <= 65535, m >= 1");
+    const hipdrt_pfrt_select_opts so = opts_or(sel, hipdrt_pfrt_select_opts_default);
+    // every check comes before the first launch (and the first upload)
+    HIPDRT_REQUIRE(S >= 1 && S <= 1024, "1 <= steps <= 1024");
+    HIPDRT_REQUIRE(neval_pfrt >= 1 && neval_pfrt <= 2048, "pfrt_select: at most 2048 points on the tau_pfrt grid");
+    TRY(pfrt_select_check(so));
+    const int np = neval_pfrt, mp = so.max_peaks;
+    const size_t bn = (size_t)B * np, bm = (size_t)B * mp;
+    TRY(require_finite(raw_pfrt, bn)); TRY(require_finite(step_pfrt, (size_t)S * bn));
+    hipStream_t st; TRY(enter(ctx, &st));
+    DevBuf draw, dstep, drss, dslw;
+    TRY(upload(draw, raw_pfrt, bn * sizeof(double), st)); TRY(upload(dstep, step_pfrt, (size_t)S * bn * sizeof(double), st));
+    TRY(upload(drss, rss, (size_t)S * B * sizeof(double), st)); TRY(upload(dslw, sum_log_w, (size_t)S * B * sizeof(double), st));
+    PfrtSelectArgs a{};
+    a.S = S; a.np = np; a.max_peaks = mp; a.ld_step = (long long)bn; a.ld_sum = B;
+    a.raw = draw.d(); a.step_pfrt = dstep.d(); a.rss = drss.d(); a.slw = dslw.d();
+    pfrt_llh_consts(m, &a.c, &a.alpha_n, &a.beta_0);
+    a.start_thresh = so.start_thresh; a.end_thresh = so.end_thresh; a.peak_thresh = so.peak_thresh;
+    GuardedOuts outs;
+    TRY(outs.want("num_peaks", out->num_peaks, (size_t)B, a.num_peaks, st)); TRY(outs.want("ranked_index", out->ranked_index, bm, a.ranked_index, st));
+    TRY(outs.want("first", out->first, (size_t)B, a.first, st)); TRY(outs.want("num_candidates", out->num_candidates, (size_t)B, a.num_candidates, st));
+    TRY(outs.want("step_index", out->step_index, bm, a.step_index, st)); TRY(outs.want("magnitude", out->magnitude, bm, a.magnitude, st));
+    TRY(outs.want("match_quality", out->match_quality, bm, a.match_quality, st)); TRY(outs.want("status", status, (size_t)B, a.status, st));
+    TRY(launch_pfrt_select(st, a, B));
+    LAUNCH_OK();
+    return outs.back(st);
+} HIPDRT_CATCH
+
 // test hook (include/hipdrt_debug.h): response_chain (plan_response.hip) as it is, on host arrays; out between borders of marker bytes
 int hipdrt_debug_response(hipdrt_ctx* ctx, const hipdrt_debug_response_args* q) try {
     HIPDRT_REQUIRE(ctx && q && q->X && q->step_sizes && q->coefficient_scale && q->out, "NULL pointer");

@@ -259,6 +259,39 @@ HIPDRT_HD inline PfrtCombineLds pfrt_combine_lds(void* sm, int S, int np, int no
     return l;
 }
 
+// pfrt_select_kernel: the raw PFRT, one step row and its shifted image [np each]; per range its area, its magnitude and the
+// running best match_quality [max_peaks each]; ints: per grid point the range it belongs to (its end included) and rank_at [np
+// each] -- rank_at first holds the flag "a range starts here" for the count of the ranges, and from then on the rank of the peak
+// that sits at the point (INT_MAX: none); per range start, end, peak, rank -> range and the running best step [max_peaks each],
+// and the counts {ranges, first, candidates}
+static constexpr int PFS_MAX_PEAKS = 64;
+struct PfrtSelectLds {
+    double *raw, *row, *sh, *area, *mag, *best;
+    int *rng, *rank_at, *start, *end, *peak, *order, *best_step, *counts;
+    size_t bytes;
+};
+HIPDRT_HD inline PfrtSelectLds pfrt_select_lds(void* sm, int np, int max_peaks) {
+    const size_t n = (size_t)np, mp = (size_t)max_peaks;
+    LdsCarver c = lds_carver(sm);
+    PfrtSelectLds l;
+    l.raw = c.take<double>(n);
+    l.row = c.take<double>(n);
+    l.sh = c.take<double>(n);
+    l.area = c.take<double>(mp);
+    l.mag = c.take<double>(mp);
+    l.best = c.take<double>(mp);
+    l.rng = c.take<int>(n);
+    l.rank_at = c.take<int>(n);
+    l.start = c.take<int>(mp);
+    l.end = c.take<int>(mp);
+    l.peak = c.take<int>(mp);
+    l.order = c.take<int>(mp);
+    l.best_step = c.take<int>(mp);
+    l.counts = c.take<int>(4);
+    l.bytes = c.off;
+    return l;
+}
+
 // ---- map_predict.hip ----
 // map_prob_kernel: five double rows and three int rows of n evaluation points
 struct MapProbLds { double *f, *fxx, *vf, *vxx, *prom; int *sgn, *lb, *rb; size_t bytes; };

@@ -5,6 +5,7 @@
 // final P and the variance path come from plan_post.hip (plan.hpp).
 #include <cmath>
 #include <cstring>
+#include <optional>
 
 #include "plan.hpp"
 
@@ -497,34 +498,41 @@ int hipdrt_plan_pfrt_get_step(hipdrt_plan* p, int step, double* x, double* rho, 
     return HIPDRT_OK;
 } HIPDRT_CATCH
 
-int hipdrt_plan_predict_pfrt(hipdrt_plan* p, const double* factors, const double* ln_tau_pfrt, int neval_pfrt,
-                             const double* ln_tau_out, int neval_out, const hipdrt_pfrt_opts* opts, double* pfrt, double* raw_pfrt,
-                             double* step_pfrt, double* post_prob, int* status) try {
+// What hipdrt_plan_predict_pfrt and hipdrt_plan_pfrt_select share.  pfrt_request: every check of the plan, the factors and the
+// options (o already holds the caller's or the defaults; np, nout the two grids), before the first launch.  pfrt_steps_dev: the
+// loop over the recorded steps -- the step weights, the rows, one factorisation per step, launch_peaks and launch_pfrt_step --
+// which leaves the steps' rows and the status vectors on the device.
+struct PfrtSteps {
+    DevBuf dev, dfs, dbad, dlnf, dstep;      // ln(tau_pfrt) [np], merged fit status [B], variance flag [B], ln(factors) [S], [S][B][np]
+    std::vector<int> comb;                   // host image of dfs: a spectrum whose fit failed in any step is dead in every step
+    size_t bn = 0;                           // B * np
+    std::optional<PredictTimer> tm;          // started before the first step; the caller marks it after its last launch
+};
+static int pfrt_request(hipdrt_plan* p, const double* factors, const double* ln_tau_pfrt, const hipdrt_pfrt_opts& o, int np,
+                        int nout, PredictBasis& pb, hipdrt_peak_opts& po) {
     HIPDRT_REQUIRE(p && factors && ln_tau_pfrt, "NULL pointer");
     if (p->prepared) {
         set_error("not supported: predict_pfrt is built for plain EIS plans (hipdrt_plan_create); a prepared plan records its steps "
                   "and gives their P matrices only");
         return HIPDRT_E_UNSUPPORTED;
     }
-    PredictBasis pb;
     TRY(predict_basis(p, pb));
-    hipdrt_pfrt_opts o = opts_or(opts, hipdrt_pfrt_opts_default);
-    const int S = p->pf_steps, B = p->B, np = neval_pfrt, nout = neval_out, width = p->n - p->ns;
-    // every check comes before the first launch
+    const int S = p->pf_steps;
     HIPDRT_REQUIRE(S >= 1, "no recorded PFRT steps in the plan (hipdrt_plan_pfrt_begin / _record around the fit's steps)");
     TRY(pfrt_check(o, S, np, nout));
-    HIPDRT_REQUIRE(!o.smooth || ln_tau_out, "smoothing needs the output grid");
     HIPDRT_REQUIRE(o.eval_sign == 1, "eval_sign must be 1 (the DRT block of a plain EIS plan holds one copy of the basis)");
     for (int i = 0; i < S; ++i) HIPDRT_REQUIRE(factors[i] > 0.0 && std::isfinite(factors[i]), "factors must be positive and finite");
-    hipdrt_peak_opts po;
     hipdrt_peak_opts_default(&po);
     po.eval_sign = 1; po.search = o.search; po.normalize = 1; po.method = 0; po.height = o.height; po.prominence = o.prominence;
     TRY(peak_check_opts(po, np));
     HIPDRT_REQUIRE(peaks_lds_bytes(np, 0, 1, 0) <= kLdsLimit, "predict_pfrt: neval_pfrt too large for one workgroup's LDS");
-    hipStream_t st; TRY(enter(p->ctx, &st));
-
-    // a spectrum whose fit failed in any step is dead in every step
-    std::vector<int> hs((size_t)S * B), comb(B, 0), hbad(B, 0);
+    return HIPDRT_OK;
+}
+static int pfrt_steps_dev(hipdrt_plan* p, const PredictBasis& pb, const hipdrt_pfrt_opts& o, const hipdrt_peak_opts& po,
+                          const double* factors, const double* ln_tau_pfrt, int np, hipStream_t st, PfrtSteps& W) {
+    const int S = p->pf_steps, B = p->B, width = p->n - p->ns;
+    std::vector<int> hs((size_t)S * B);
+    W.comb.assign(B, 0);
     for (int i = 0; i < S; ++i)
         HIPDRT_CHECK(hipMemcpyAsync(hs.data() + (size_t)i * B, p->pf_status.i() + p->pf_layout().scalar(i), (size_t)B * sizeof(int),
                                     hipMemcpyDeviceToHost, st));
@@ -532,39 +540,38 @@ int hipdrt_plan_predict_pfrt(hipdrt_plan* p, const double* factors, const double
     for (int b = 0; b < B; ++b)
         for (int i = 0; i < S; ++i) {
             const int v = hs[(size_t)i * B + b];
-            if (comb[b] >= 0 && (v < 0 || v > comb[b])) comb[b] = v;
+            if (W.comb[b] >= 0 && (v < 0 || v > W.comb[b])) W.comb[b] = v;
         }
     std::vector<double> lnf(S);
     for (int i = 0; i < S; ++i) lnf[i] = std::log(factors[i]);
 
-    const size_t bn = (size_t)B * np;
-    DevBuf dev, dout_grid, dfs, dbad, dlnf, dw, dscratch, dnorm0, dsg, dht, dpr, dstep, dE;
-    TRY(upload(dev, ln_tau_pfrt, (size_t)np * sizeof(double), st));
-    if (o.smooth) TRY(upload(dout_grid, ln_tau_out, (size_t)nout * sizeof(double), st));
-    TRY(upload(dfs, comb.data(), (size_t)B * sizeof(int), st));
-    TRY(upload(dlnf, lnf.data(), (size_t)S * sizeof(double), st));
-    HIPDRT_CHECK(dbad.alloc((size_t)B * sizeof(int)));
-    HIPDRT_CHECK(hipMemsetAsync(dbad.p, 0, (size_t)B * sizeof(int), st));
+    const size_t bn = W.bn = (size_t)B * np;
+    DevBuf dw, dscratch, dnorm0, dsg, dht, dpr, dE;
+    TRY(upload(W.dev, ln_tau_pfrt, (size_t)np * sizeof(double), st));
+    TRY(upload(W.dfs, W.comb.data(), (size_t)B * sizeof(int), st));
+    TRY(upload(W.dlnf, lnf.data(), (size_t)S * sizeof(double), st));
+    HIPDRT_CHECK(W.dbad.alloc((size_t)B * sizeof(int)));
+    HIPDRT_CHECK(hipMemsetAsync(W.dbad.p, 0, (size_t)B * sizeof(int), st));
     HIPDRT_CHECK(dnorm0.alloc((size_t)B * sizeof(double)));
     HIPDRT_CHECK(dsg.alloc(bn * sizeof(int))); HIPDRT_CHECK(dht.alloc(bn * sizeof(double))); HIPDRT_CHECK(dpr.alloc(bn * sizeof(double)));
-    HIPDRT_CHECK(dstep.alloc((size_t)S * bn * sizeof(double)));
+    HIPDRT_CHECK(W.dstep.alloc((size_t)S * bn * sizeof(double)));
     HIPDRT_CHECK(dE.alloc((size_t)2 * np * width * sizeof(double)));
     HIPDRT_CHECK(hipStreamSynchronize(st));          // (the host vectors above may go out of use)
     const int orders[2] = {2, 0};
-    PredictTimer tm(p->ctx, st);
+    PredictTimer& tm = W.tm.emplace(p->ctx, st);
     for (int i = 0; i < S; ++i) {
         // step P = calculate_pq with the step's s / rho and the raw re-estimated weights (drt1d.py:2611-2632)
         TRY(step_weights(p, i, st, dw, dscratch));
-        const PostSource src = step_source(p, i, dw.d(), dfs.i());
+        const PostSource src = step_source(p, i, dw.d(), W.dfs.i());
         // f and fxx normalised by the R_p of the step's own x; sigma^2 of both orders from one factorisation of the step P
         DrtRows R;
-        TRY(R.begin(p, dev.d(), dE, np, 2));
+        TRY(R.begin(p, W.dev.d(), dE, np, 2));
         TRY(plan_drt_rows_dev(p, src, pb, orders, 1, 1, nullptr, true, st, R, tm, i > 0));
         // ... but every step's variances are divided by the squared R_p of the FIRST step (estimate_distribution_cov takes
         // get_drt_norm() of fit_parameters, which the warm restarts never update: drt1d.py:3081)
         if (i == 0) HIPDRT_CHECK(hipMemcpyAsync(dnorm0.p, R.dnorm.p, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, st));
         PeakArgs pa{};
-        peak_args_rows(pa, R, po, true, false, dfs.i());
+        peak_args_rows(pa, R, po, true, false, W.dfs.i());
         pa.peak_sign = dsg.i(); pa.heights = dht.d(); pa.prominences = dpr.d();
         TRY(launch_peaks(st, pa, B));
         LAUNCH_OK();
@@ -572,26 +579,126 @@ int hipdrt_plan_predict_pfrt(hipdrt_plan* p, const double* factors, const double
         sa.neval = np; sa.floor = o.fxx_var_floor; sa.ext_left = o.ext_left; sa.ext_right = o.ext_right;
         sa.peak_sign = dsg.i(); sa.heights = dht.d(); sa.prominences = dpr.d(); sa.f = R.mu(1);
         sa.var_fxx = R.var(0); sa.var_f = R.var(1); sa.ldv = R.ldv(); sa.cs = R.cs; sa.norm = dnorm0.d();
-        sa.fit_status = dfs.i(); sa.var_status = R.dvstat.i(); sa.out = dstep.d() + (size_t)i * bn; sa.bad = dbad.i();
+        sa.fit_status = W.dfs.i(); sa.var_status = R.dvstat.i(); sa.out = W.dstep.d() + (size_t)i * bn; sa.bad = W.dbad.i();
         TRY(launch_pfrt_step(st, sa, B));
         LAUNCH_OK();
         HIPDRT_CHECK(hipStreamSynchronize(st));      // R's buffers are released at the end of the iteration
     }
+    return HIPDRT_OK;
+}
+// the combination of the steps W holds; sizes, the output grid and the output pointers are the caller's
+static PfrtCombineArgs pfrt_combine_of(const hipdrt_plan* p, const hipdrt_pfrt_opts& o, const PfrtSteps& W, int np, int nout) {
     PfrtCombineArgs ca = pfrt_combine_args(o, p->m);
-    ca.S = S; ca.np = np; ca.nout = nout; ca.ld_step = (long long)bn; ca.ld_sum = p->capacity;
-    ca.step_pfrt = dstep.d(); ca.rss = p->pf_rss.d(); ca.slw = p->pf_slw.d(); ca.ln_factors = dlnf.d();
-    ca.ltp = dev.d(); ca.lto = dout_grid.d(); ca.fit_status = dfs.i(); ca.bad = dbad.i();
+    ca.S = p->pf_steps; ca.np = np; ca.nout = nout; ca.ld_step = (long long)W.bn; ca.ld_sum = p->capacity;
+    ca.step_pfrt = W.dstep.d(); ca.rss = p->pf_rss.d(); ca.slw = p->pf_slw.d(); ca.ln_factors = W.dlnf.d();
+    ca.ltp = W.dev.d(); ca.fit_status = W.dfs.i(); ca.bad = W.dbad.i();
+    return ca;
+}
+
+int hipdrt_plan_predict_pfrt(hipdrt_plan* p, const double* factors, const double* ln_tau_pfrt, int neval_pfrt,
+                             const double* ln_tau_out, int neval_out, const hipdrt_pfrt_opts* opts, double* pfrt, double* raw_pfrt,
+                             double* step_pfrt, double* post_prob, int* status) try {
+    const hipdrt_pfrt_opts o = opts_or(opts, hipdrt_pfrt_opts_default);
+    const int np = neval_pfrt, nout = neval_out;
+    PredictBasis pb;
+    hipdrt_peak_opts po;
+    // every check comes before the first launch
+    TRY(pfrt_request(p, factors, ln_tau_pfrt, o, np, nout, pb, po));
+    HIPDRT_REQUIRE(!o.smooth || ln_tau_out, "smoothing needs the output grid");
+    const int S = p->pf_steps, B = p->B;
+    hipStream_t st; TRY(enter(p->ctx, &st));
+    DevBuf dout_grid;
+    if (o.smooth) TRY(upload(dout_grid, ln_tau_out, (size_t)nout * sizeof(double), st));
+    PfrtSteps W;
+    TRY(pfrt_steps_dev(p, pb, o, po, factors, ln_tau_pfrt, np, st, W));
+    PfrtCombineArgs ca = pfrt_combine_of(p, o, W, np, nout);
+    ca.lto = dout_grid.d();
     DevOuts outs;
-    TRY(outs.want(pfrt, (size_t)B * nout, ca.pfrt)); TRY(outs.want(raw_pfrt, bn, ca.raw)); TRY(outs.want(post_prob, (size_t)S * B, ca.post));
+    TRY(outs.want(pfrt, (size_t)B * nout, ca.pfrt)); TRY(outs.want(raw_pfrt, W.bn, ca.raw)); TRY(outs.want(post_prob, (size_t)S * B, ca.post));
     TRY(launch_pfrt_combine(st, ca, B));
     LAUNCH_OK();
-    tm.mark();
+    W.tm->mark();
     TRY(outs.back(st));
     // (the steps' rows are formed whatever the caller asked for: the combination reads them)
-    if (step_pfrt) HIPDRT_CHECK(hipMemcpyAsync(step_pfrt, dstep.p, dstep.bytes, hipMemcpyDeviceToHost, st));
-    HIPDRT_CHECK(hipMemcpyAsync(hbad.data(), dbad.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (step_pfrt) HIPDRT_CHECK(hipMemcpyAsync(step_pfrt, W.dstep.p, W.dstep.bytes, hipMemcpyDeviceToHost, st));
+    std::vector<int> hbad(B, 0);
+    HIPDRT_CHECK(hipMemcpyAsync(hbad.data(), W.dbad.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
     HIPDRT_CHECK(hipStreamSynchronize(st));
-    if (status) merge_status(B, comb.data(), hbad.data(), status);
+    if (status) merge_status(B, W.comb.data(), hbad.data(), status);
+    return HIPDRT_OK;
+} HIPDRT_CATCH
+
+// ---- DRT.select_pfrt_candidates on the device (pfrt_select_kernel, csrc/pfrt.hip) -------------------------------------------------
+void hipdrt_pfrt_select_opts_default(hipdrt_pfrt_select_opts* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->start_thresh = 0.99; o->end_thresh = 0.01; o->peak_thresh = 1e-6; o->max_peaks = 16;
+}
+
+int hipdrt_plan_pfrt_select(hipdrt_plan* p, const double* factors, const double* ln_tau_pfrt, int neval_pfrt,
+                            const hipdrt_pfrt_opts* opts, const hipdrt_pfrt_select_opts* sel, hipdrt_pfrt_select_out* out,
+                            int* status) try {
+    HIPDRT_REQUIRE(out, "NULL pointer");
+    const hipdrt_pfrt_opts of = opts_or(opts, hipdrt_pfrt_opts_default);      // as given: the finished row out->pfrt
+    hipdrt_pfrt_opts o = of;
+    o.smooth = 0; o.integrate = 0; o.normalize = 0;          // upstream selects on the raw PFRT
+    const hipdrt_pfrt_select_opts so = opts_or(sel, hipdrt_pfrt_select_opts_default);
+    const int np = neval_pfrt, nout = so.neval_out;
+    PredictBasis pb;
+    hipdrt_peak_opts po;
+    // every check comes before the first launch
+    TRY(pfrt_request(p, factors, ln_tau_pfrt, o, np, np, pb, po));
+    TRY(pfrt_select_check(so));
+    if (out->pfrt) {
+        TRY(pfrt_check(of, p->pf_steps, np, nout));
+        HIPDRT_REQUIRE(!of.smooth || so.ln_tau_out, "smoothing needs the output grid");
+    }
+    const int S = p->pf_steps, B = p->B, mp = so.max_peaks;
+    hipStream_t st; TRY(enter(p->ctx, &st));
+    PfrtSteps W;
+    TRY(pfrt_steps_dev(p, pb, o, po, factors, ln_tau_pfrt, np, st, W));
+    PfrtCombineArgs ca = pfrt_combine_of(p, o, W, np, np);
+    DevOuts outs;
+    TRY(outs.want(out->raw_pfrt, W.bn, ca.raw, true)); TRY(outs.want(out->post_prob, (size_t)S * B, ca.post));
+    TRY(launch_pfrt_combine(st, ca, B));
+    LAUNCH_OK();
+    PfrtSelectArgs sa{};
+    sa.S = S; sa.np = np; sa.max_peaks = mp; sa.ld_step = ca.ld_step; sa.ld_sum = ca.ld_sum;
+    sa.raw = ca.raw; sa.step_pfrt = ca.step_pfrt; sa.rss = ca.rss; sa.slw = ca.slw;
+    sa.c = ca.c; sa.alpha_n = ca.alpha_n; sa.beta_0 = ca.beta_0;
+    sa.start_thresh = so.start_thresh; sa.end_thresh = so.end_thresh; sa.peak_thresh = so.peak_thresh;
+    sa.fit_status = W.dfs.i(); sa.bad = W.dbad.i();
+    const size_t bm = (size_t)B * mp;
+    int* dsel = nullptr;
+    TRY(outs.want(out->num_peaks, (size_t)B, sa.num_peaks)); TRY(outs.want(out->ranked_index, bm, sa.ranked_index));
+    TRY(outs.want(out->first, (size_t)B, sa.first)); TRY(outs.want(out->num_candidates, (size_t)B, sa.num_candidates));
+    TRY(outs.want(out->step_index, bm, sa.step_index)); TRY(outs.want(out->magnitude, bm, sa.magnitude));
+    TRY(outs.want(out->match_quality, bm, sa.match_quality));
+    std::vector<int> hsel(B, 0), hbad(B, 0);
+    TRY(outs.want(hsel.data(), (size_t)B, dsel));
+    sa.status = dsel;
+    TRY(launch_pfrt_select(st, sa, B));
+    LAUNCH_OK();
+    // the finished row: the combination once more with the caller's smoothing, integration and normalisation
+    DevBuf dout_grid;
+    if (out->pfrt) {
+        if (of.smooth) TRY(upload(dout_grid, so.ln_tau_out, (size_t)nout * sizeof(double), st));
+        PfrtCombineArgs cf = pfrt_combine_of(p, of, W, np, nout);
+        cf.lto = dout_grid.d();
+        TRY(outs.want(out->pfrt, (size_t)B * nout, cf.pfrt));
+        TRY(launch_pfrt_combine(st, cf, B));
+        LAUNCH_OK();
+    }
+    W.tm->mark();
+    TRY(outs.back(st));
+    if (out->step_pfrt) HIPDRT_CHECK(hipMemcpyAsync(out->step_pfrt, W.dstep.p, W.dstep.bytes, hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipMemcpyAsync(hbad.data(), W.dbad.p, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPDRT_CHECK(hipStreamSynchronize(st));
+    if (status) {
+        merge_status(B, W.comb.data(), hbad.data(), status);
+        // a live row's own outcome (no peak, too many peaks) goes before a non-negative fit status
+        for (int b = 0; b < B; ++b) if (status[b] >= 0 && hsel[b] != 0) status[b] = hsel[b];
+    }
     return HIPDRT_OK;
 } HIPDRT_CATCH
 

@@ -294,7 +294,7 @@ def fit_observation_list(drt, observations, tau_supergrid, drt_var=False, ignore
 
 
 def fit_observations_pfrt(drt, observations, tau_supergrid, pfrt_factors=None, drt_var=False, ignore_errors=False,
-                          llh_kw=None, rss_kw=None, predict_pfrt_kw=None, **fit_kw):
+                          llh_kw=None, rss_kw=None, predict_pfrt_kw=None, select_pfrt_kw=None, **fit_kw):
     """DRTMD with fit_type='pfrt' (drtmd.py:98-100, 1136-1158, 1338-1342): every observation through _pfrt_fit_core
     (drt1d.py:2558-2700) -- one full fit at the first regularisation factor, one warm restart per further factor -- with one
     solution PER FACTOR recorded.  Factors: ``pfrt_factors`` (or ``factors=`` among the fit keywords, which is where upstream
@@ -310,7 +310,11 @@ def fit_observations_pfrt(drt, observations, tau_supergrid, pfrt_factors=None, d
     Also returned per observation: step_llh (num, S), step_iters (num, S).  ``predict_pfrt_kw`` (a dict, may be empty): EIS groups
     also fill res['obs_pfrt'] and res['obs_raw_pfrt'] (num, len(tau_supergrid)) from DRT.predict_pfrt_batch(**predict_pfrt_kw) with
     tau_pfrt = tau = tau_supergrid unless the dict says otherwise (rows of other groups and of failed fits are NaN); None leaves
-    every returned object as it is without it."""
+    every returned object as it is without it.  ``select_pfrt_kw`` (a dict of start_thresh, end_thresh, peak_thresh, max_peaks,
+    may be empty; needs predict_pfrt_kw): EIS groups make ONE device pass, DRT.select_pfrt_candidates_batch(pfrt_kw=...), which
+    yields the candidates, the raw PFRT and the finished PFRT (the bits predict_pfrt_batch gives); res['obs_pfrt_candidates'] is
+    a list with (target_peak_indices, step_indices) per observation, None for other groups, failed fits and rows without an
+    answer.  None leaves every result as it is without it."""
     tau_supergrid = np.asarray(tau_supergrid, dtype=float)
     if 'factors' in fit_kw:
         pfrt_factors = fit_kw.pop('factors')
@@ -327,6 +331,14 @@ def fit_observations_pfrt(drt, observations, tau_supergrid, pfrt_factors=None, d
         if len(ppk['tau']) != nsup or len(ppk['tau_pfrt']) != nsup:
             raise ValueError('predict_pfrt_kw: tau and tau_pfrt must have the length of tau_supergrid')
         res['obs_pfrt'], res['obs_raw_pfrt'] = np.full((num, nsup), np.nan), np.full((num, nsup), np.nan)
+    if select_pfrt_kw is not None:
+        if predict_pfrt_kw is None:
+            raise ValueError('select_pfrt_kw needs predict_pfrt_kw (a dict, may be empty): the candidates come from the PFRT pass')
+        spk = dict(select_pfrt_kw)
+        if set(spk) - {'start_thresh', 'end_thresh', 'peak_thresh', 'max_peaks'}:
+            raise TypeError(f"unexpected select_pfrt_kw {sorted(set(spk) - {'start_thresh', 'end_thresh', 'peak_thresh', 'max_peaks'})}")
+        finish_kw = {k: ppk.pop(k) for k in ('tau', 'smooth', 'smooth_kw', 'integrate', 'integrate_threshold', 'normalize') if k in ppk}
+        res['obs_pfrt_candidates'] = [None] * num
     pf_kw = {k: fit_kw.pop(k) for k in ('max_iter_per_step', 'max_init_iter', 'xtol', 'nonneg') if k in fit_kw}
     for kind, idx in observation_groups(observations):
         first = {}
@@ -350,7 +362,12 @@ def fit_observations_pfrt(drt, observations, tau_supergrid, pfrt_factors=None, d
                 specials['R_inf'] = pr['step_x'][:, :, sp['R_inf']['index']] * cs[None, :]
             if 'inductance' in sp:
                 specials['inductance'] = pr['step_x'][:, :, sp['inductance']['index']] * cs[None, :] * drt.inductance_scale
-            if predict_pfrt_kw is not None:
+            if select_pfrt_kw is not None:
+                pairs, info = drt.select_pfrt_candidates_batch(return_info=True, pfrt_kw=finish_kw, **spk, **ppk)
+                for k, pair in zip(idx, pairs):
+                    res['obs_pfrt_candidates'][k] = pair
+                res['obs_pfrt'][idx], res['obs_raw_pfrt'][idx] = info['pfrt'], info['raw_pfrt']
+            elif predict_pfrt_kw is not None:
                 tot, info = drt.predict_pfrt_batch(return_info=True, **ppk)
                 res['obs_pfrt'][idx], res['obs_raw_pfrt'][idx] = tot, info['raw_pfrt']
         else:

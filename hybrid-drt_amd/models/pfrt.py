@@ -7,6 +7,10 @@ evaluation.get_similarity_function('gaussian') (2840-2848), pfrt.integrate_peaks
 utils.array.find_contiguous_ranges) and the normalisation by the maximum.  Everything acts on rows that are already evaluated: per
 step f (order 0), fxx (order 2) and their posterior variances before extend_var and the floor.  No scipy.
 
+DRT.select_pfrt_candidates (drt1d.py:2860-2865 over hybdrt/models/pfrt.py:49-213) on the raw PFRT, the steps' rows and the step
+likelihoods: rank_peaks, shift_candidate, candidate_corr, select_candidates and the compact result form that pfrt_select_kernel
+writes (select_compact / candidates_from_compact).
+
 Sums run in the order the kernels use (over the steps ascending, over the grid ascending); where upstream lets numpy choose the
 order (np.trapezoid, the matrix product) the difference is a reordering of non-negative terms.
 """
@@ -151,3 +155,96 @@ def predict_pfrt_rows(factors, llh, f, fxx, var_f, var_fxx, ln_tau_pfrt, ln_tau_
     raw = combine(post, steps)
     out = finish(raw, ln_tau_pfrt, ln_tau_out, smooth, smooth_order, smooth_epsilon, integrate, integrate_threshold, normalize)
     return dict(pfrt=out, raw_pfrt=raw, step_pfrt=steps, post_prob=post)
+
+
+# ---- select_pfrt_candidates (hybdrt/models/pfrt.py:49-213) ------------------------------------------------------------------------
+def rank_peaks(pf, min_prob):
+    """pfrt.rank_peaks(integrate=True): (peak indices, areas) by descending area.  Equal areas put the higher index first: what
+    np.argsort(areas)[::-1] gives for the at most 16 entries numpy sorts by insertion, made the rule for any count."""
+    idx, area = integrate_peaks(pf, min_prob)
+    order = np.array(sorted(range(len(area)), key=lambda r: (-area[r], -r)), dtype=np.intp)
+    return idx[order], area[order]
+
+
+def shift_candidate(cand_pf, ranges, peak_indices):
+    """pfrt.shift_candidate_pfrt: every entry > 0 at ti moves to the peak index of the one range with start <= ti <= end (end is
+    the exclusive end, so the point one past a range still belongs to it) and stays where it is otherwise.  Entries that land on
+    the same peak: the highest ti wins, as numpy's fancy assignment in ascending ti leaves it."""
+    cand_pf = np.asarray(cand_pf, dtype=float)
+    starts, ends = ranges
+    out = np.zeros(len(cand_pf))
+    for ti in np.where(cand_pf > 0)[0]:
+        match = [r for r in range(len(starts)) if starts[r] <= ti <= ends[r]]
+        out[peak_indices[match[0]] if len(match) == 1 else ti] = cand_pf[ti]
+    return out
+
+
+def _corr(target, cand):
+    """np.corrcoef(target, cand)[0, 1] with np.cov's steps in one fixed order: both rows centred by their means, the three sums of
+    products in ascending index order, each times 1 / (n - 1), the covariance divided by the two standard deviations in turn,
+    the result clipped to [-1, 1]"""
+    n = len(cand)
+    seq = lambda v: np.cumsum(v)[-1]          # (np.cumsum adds one term after the other: the sum in ascending index order)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        target, cand = np.asarray(target, dtype=float), np.asarray(cand, dtype=float)
+        dt, dc = target - seq(target) / np.float64(n), cand - seq(cand) / np.float64(n)
+        stt, scc, stc = seq(dt * dt), seq(dc * dc), seq(dt * dc)
+        fac = np.float64(1.0) / np.float64(n - 1)
+        r = ((stc * fac) / np.sqrt(stt * fac)) / np.sqrt(scc * fac)
+    if r > 1.0:
+        r = np.float64(1.0)
+    if r < -1.0:
+        r = np.float64(-1.0)
+    return r
+
+
+def candidate_corr(target_indices, cand_pf):
+    """pfrt.candidate_corr: the correlation of the 0/1 row with ones at target_indices and the (shifted) candidate row; an
+    all-zero candidate row gives NaN"""
+    cand_pf = np.asarray(cand_pf, dtype=float)
+    target = np.zeros(len(cand_pf))
+    target[np.asarray(target_indices, dtype=np.intp)] = 1.0
+    return _corr(target, cand_pf)
+
+
+def select_compact(tot_pf, step_pfs, step_llh, start_thresh=0.99, end_thresh=0.01, peak_thresh=1e-6):
+    """pfrt.select_candidates in the compact form the device writes -> dict(num_peaks K, ranked_index (K,), magnitude (K,)
+    normalised by the largest, first (the prefix length minus one of the first target), num_candidates, step_index and
+    match_quality (num_candidates,)).  Candidate j has target ranked_index[:first + j + 1] and step step_index[j], the np.argmax
+    of corr * llh over the steps (the first NaN wins); match_quality[j] is that winning value.  K peaks give at most K - 1
+    candidates.  A row with no value at or above peak_thresh raises ValueError."""
+    tot_pf, step_llh = np.asarray(tot_pf, dtype=float), np.asarray(step_llh, dtype=float)
+    ranges = get_peak_ranges(tot_pf, peak_thresh)
+    if len(ranges[0]) == 0:
+        raise ValueError('select_candidates: no value of the PFRT at or above peak_thresh')
+    peak_indices = identify_peaks(tot_pf, peak_thresh)
+    shifted = [shift_candidate(c, ranges, peak_indices) for c in step_pfs]
+    ranked, mag = rank_peaks(tot_pf, peak_thresh)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        mag = mag / np.max(mag)
+    K = len(mag)
+    inc = np.where(mag >= start_thresh)[0]
+    first = inc = int(inc[-1]) if len(inc) > 0 else 0
+    step_index, quality = [], []
+    while inc < K - 1:
+        mq = np.array([candidate_corr(ranked[:inc + 1], sh) * llh for sh, llh in zip(shifted, step_llh)])
+        step_index.append(int(np.argmax(mq)))
+        quality.append(mq[step_index[-1]])
+        inc += 1
+        if mag[inc] < end_thresh:
+            break
+    return dict(num_peaks=K, ranked_index=np.asarray(ranked, dtype=np.intp), magnitude=mag, first=first,
+                num_candidates=len(step_index), step_index=np.array(step_index, dtype=np.intp),
+                match_quality=np.array(quality, dtype=float))
+
+
+def candidates_from_compact(c):
+    """the compact form -> upstream's (target_peak_indices, candidate_indices): a list of index arrays and a list of step indices"""
+    ranked, first = np.asarray(c['ranked_index'], dtype=np.intp), int(c['first'])
+    n = int(c['num_candidates'])
+    return [ranked[:first + j + 1].copy() for j in range(n)], [int(s) for s in np.asarray(c['step_index'])[:n]]
+
+
+def select_candidates(tot_pf, step_pfs, step_llh, start_thresh=0.99, end_thresh=0.01, peak_thresh=1e-6):
+    """pfrt.select_candidates (hybdrt/models/pfrt.py:164-213, without its print) -> (target_peak_indices, candidate_indices)"""
+    return candidates_from_compact(select_compact(tot_pf, step_pfs, step_llh, start_thresh, end_thresh, peak_thresh))

@@ -7,7 +7,7 @@ import numpy as np
 
 from .. import _ffi, preprocessing as pp
 from ..matrices import basis, mat1d
-from . import background, peaks, predict, response
+from . import background, peaks, pfrt as pfrt_rule, predict, response
 
 
 class PostFitMixin:
@@ -917,6 +917,40 @@ class PostFitMixin:
         final s / rho and the raw weights re-estimated from the step's x, formed on the device (hipdrt_plan_get_step_p_matrix)"""
         return self._pfrt_plan('step_p_matrix').step_p_matrix(step, b)
 
+    def _pfrt_chain(self, what, tau_pfrt, sign, prior_mu, prior_sigma, find_peaks_kw, n_eff_factor, fxx_var_floor, extend_var):
+        """what predict_pfrt_batch and select_pfrt_candidates_batch ask of the chain up to the raw PFRT, with its refusals ->
+        (plan, tau_pfrt, the fields of hipdrt_pfrt_opts the chain reads, factors)"""
+        if self.series_neg:
+            raise NotImplementedError(f'{what}: series_neg fits are not taken (upstream\'s normalize=True raises for them)')
+        if isinstance(self._plan, _ffi.PreparedPlan):
+            raise NotImplementedError(f'{what} is built for plain EIS fits; a prepared plan records its steps and gives '
+                                      'step_p_matrix only')
+        plan = self._pfrt_plan(what)
+        fkw = dict(find_peaks_kw or {'height': 1e-3, 'prominence': 5e-3})
+        for name in fkw:
+            if name not in ('height', 'prominence'):
+                raise NotImplementedError(f'{what}: the {name}= condition of scipy.signal.find_peaks is not built '
+                                          f'(only height and prominence)')
+        sign = self._drt_sign(plan, sign)
+        tau_pfrt = self.get_tau_eval(10) if tau_pfrt is None else np.asarray(tau_pfrt, dtype=float)
+        search, ext = self._peak_search(sign), self._peak_ext(tau_pfrt, extend_var)
+        chain = dict(eval_sign=sign, search=search, height=fkw.get('height', 0), prominence=fkw.get('prominence', 0),
+                     prior_mu=prior_mu, prior_sigma=prior_sigma, n_eff_factor=n_eff_factor, fxx_var_floor=fxx_var_floor,
+                     ext_left=ext[0], ext_right=ext[1])
+        factors = np.asarray(self.pfrt_result['factors'], dtype=float)
+        if len(factors) != plan.pfrt_steps():
+            raise ValueError(f"pfrt_result['factors'] has {len(factors)} entries, the plan recorded {plan.pfrt_steps()} steps")
+        return plan, tau_pfrt, chain, factors
+
+    @staticmethod
+    def _pfrt_finish(smooth=True, smooth_kw=None, integrate=False, integrate_threshold=1e-6, normalize=True):
+        """the fields of hipdrt_pfrt_opts behind predict_pfrt's last stage (drt1d.py:2840-2858), from its keywords"""
+        skw = dict(smooth_kw or {'order': 2, 'epsilon': 5})
+        if set(skw) - {'order', 'epsilon'}:
+            raise TypeError(f"unexpected smooth_kw {sorted(set(skw) - {'order', 'epsilon'})}")
+        return dict(smooth=bool(smooth), smooth_order=skw.get('order', 2), smooth_epsilon=skw.get('epsilon', 5),
+                    integrate=bool(integrate), integrate_threshold=integrate_threshold, normalize=bool(normalize))
+
     def predict_pfrt_batch(self, tau=None, tau_pfrt=None, sign=None, prior_mu=-4, prior_sigma=0.5, find_peaks_kw=None,
                            n_eff_factor=0.5, fxx_var_floor=1e-5, extend_var=True, smooth=True, smooth_kw=None, integrate=False,
                            integrate_threshold=1e-6, normalize=True, return_info=False):
@@ -925,34 +959,13 @@ class PostFitMixin:
         is tau_pfrt (without smooth the result stays on tau_pfrt, as upstream).  With return_info also a dict with tau_pfrt,
         raw_pfrt (B, n), step_pfrt (S, B, n), post_prob (S, B) and status (B,), the first three also stored into pfrt_result under
         upstream's keys.  Rows of spectra whose fit failed in any step, or whose step P is not positive definite, are NaN.  Of
-        find_peaks_kw only height and prominence are built; plain EIS fits only.  select_pfrt_candidates and the discrete-model
-        conversion stay with the reference's Python on these arrays."""
-        if self.series_neg:
-            raise NotImplementedError('predict_pfrt: series_neg fits are not taken (upstream\'s normalize=True raises for them)')
-        if isinstance(self._plan, _ffi.PreparedPlan):
-            raise NotImplementedError('predict_pfrt is built for plain EIS fits; a prepared plan records its steps and gives '
-                                      'step_p_matrix only')
-        plan = self._pfrt_plan('predict_pfrt')
-        fkw = dict(find_peaks_kw or {'height': 1e-3, 'prominence': 5e-3})
-        for name in fkw:
-            if name not in ('height', 'prominence'):
-                raise NotImplementedError(f'predict_pfrt: the {name}= condition of scipy.signal.find_peaks is not built '
-                                          f'(only height and prominence)')
-        skw = dict(smooth_kw or {'order': 2, 'epsilon': 5})
-        if set(skw) - {'order', 'epsilon'}:
-            raise TypeError(f"unexpected smooth_kw {sorted(set(skw) - {'order', 'epsilon'})}")
-        sign = self._drt_sign(plan, sign)
-        tau_pfrt = self.get_tau_eval(10) if tau_pfrt is None else np.asarray(tau_pfrt, dtype=float)
+        find_peaks_kw only height and prominence are built; plain EIS fits only.  select_pfrt_candidates has its own device pass
+        (select_pfrt_candidates_batch); the discrete-model conversion stays with the reference's Python on these arrays."""
+        finish = self._pfrt_finish(smooth, smooth_kw, integrate, integrate_threshold, normalize)
+        plan, tau_pfrt, chain, factors = self._pfrt_chain('predict_pfrt', tau_pfrt, sign, prior_mu, prior_sigma, find_peaks_kw,
+                                                          n_eff_factor, fxx_var_floor, extend_var)
         tau_out = tau_pfrt if (tau is None or not smooth) else np.asarray(tau, dtype=float)
-        search, ext = self._peak_search(sign), self._peak_ext(tau_pfrt, extend_var)
-        opts = _ffi.pfrt_opts(eval_sign=sign, search=search, height=fkw.get('height', 0), prominence=fkw.get('prominence', 0),
-                              prior_mu=prior_mu, prior_sigma=prior_sigma, n_eff_factor=n_eff_factor, fxx_var_floor=fxx_var_floor,
-                              ext_left=ext[0], ext_right=ext[1], smooth=bool(smooth), smooth_order=skw.get('order', 2),
-                              smooth_epsilon=skw.get('epsilon', 5), integrate=bool(integrate),
-                              integrate_threshold=integrate_threshold, normalize=bool(normalize))
-        factors = np.asarray(self.pfrt_result['factors'], dtype=float)
-        if len(factors) != plan.pfrt_steps():
-            raise ValueError(f"pfrt_result['factors'] has {len(factors)} entries, the plan recorded {plan.pfrt_steps()} steps")
+        opts = _ffi.pfrt_opts(**finish, **chain)
         out = plan.predict_pfrt(factors, np.log(tau_pfrt), np.log(tau_out) if smooth else None, opts,
                                 want=None if return_info else ('pfrt',))
         if not return_info:
@@ -973,6 +986,66 @@ class PostFitMixin:
                                             integrate_threshold=integrate_threshold, normalize=normalize, return_info=True)
         self.pfrt_result.update(raw_pfrt=info['raw_pfrt'][b], step_pfrt=info['step_pfrt'][:, b])
         return tot[b]
+
+    # ---- DRT.select_pfrt_candidates (drt1d.py:2860-2865 over hybdrt/models/pfrt.py:164-213) on the device ----------------------
+    def select_pfrt_candidates_batch(self, start_thresh=0.99, end_thresh=0.01, peak_thresh=1e-6, max_peaks=16, return_info=False,
+                                     tau_pfrt=None, sign=None, prior_mu=-4, prior_sigma=0.5, find_peaks_kw=None, n_eff_factor=0.5,
+                                     fxx_var_floor=1e-5, extend_var=True, pfrt_kw=None):
+        """DRT.select_pfrt_candidates for every spectrum of the last PFRT fit, in one device pass over the recorded steps
+        (hipdrt_plan_pfrt_select; models/pfrt.py select_compact is the rule in numpy) -> a list of B pairs (target_peak_indices,
+        step_indices) in upstream's form: candidate j is the set of the first + j + 1 most probable peaks of the raw PFRT (indices
+        into tau_pfrt) and the recorded step whose own PFRT matches it best.  Entry b is None where member b has no answer: a
+        negative status (a failed fit, a step P that is not positive definite), _ffi.PFRT_NO_PEAK (nothing at or above
+        peak_thresh; upstream raises) or _ffi.PFRT_TOO_MANY_PEAKS (more ranges than max_peaks).  The fit's own non-negative
+        statuses are live, as in predict_pfrt_batch: 1, a step that ended at its iteration limit, is how PFRT steps usually
+        end.  Peaks of equal area rank the higher index first; np.argmax picks the step, so the first NaN (an all-zero shifted
+        row) wins.  tau_pfrt ... extend_var are predict_pfrt_batch's keywords for the chain up to the raw PFRT, with the same
+        refusals.
+        Without return_info only the compact arrays and the status come down (a few numbers per spectrum; none of the rows),
+        and pfrt_result stays as it is.  With return_info also a dict with the compact arrays (num_peaks, ranked_index,
+        magnitude, first, num_candidates, step_index, match_quality), raw_pfrt, step_pfrt, post_prob, tau_pfrt and status;
+        tau_pfrt, raw_pfrt and step_pfrt are then stored into pfrt_result, as predict_pfrt_batch does with return_info.
+        pfrt_kw (with return_info; a dict of predict_pfrt_batch's tau, smooth, smooth_kw, integrate, integrate_threshold,
+        normalize; may be empty): the dict also holds 'pfrt', that method's result from the same pass, the same bits."""
+        plan, tau_pfrt, chain, factors = self._pfrt_chain('select_pfrt_candidates', tau_pfrt, sign, prior_mu, prior_sigma,
+                                                          find_peaks_kw, n_eff_factor, fxx_var_floor, extend_var)
+        want, finish, ln_tau_out = _ffi.PFRT_SELECT_COMPACT, {}, None
+        if return_info:
+            want = want + _ffi.PFRT_SELECT_ROWS[:3]
+            if pfrt_kw is not None:
+                fkw = dict(pfrt_kw)
+                tau = fkw.pop('tau', None)
+                finish = self._pfrt_finish(**fkw)
+                want = want + ('pfrt',)
+                if tau is not None and finish['smooth']:
+                    ln_tau_out = np.log(np.asarray(tau, dtype=float))
+        elif pfrt_kw is not None:
+            raise ValueError('select_pfrt_candidates_batch: pfrt_kw goes with return_info=True')
+        out = plan.pfrt_select(factors, np.log(tau_pfrt), _ffi.pfrt_opts(**finish, **chain),
+                               _ffi.pfrt_select_opts(start_thresh, end_thresh, peak_thresh, max_peaks), want=want,
+                               ln_tau_out=ln_tau_out)
+        no_answer = (out['status'] < 0) | np.isin(out['status'], (_ffi.PFRT_NO_PEAK, _ffi.PFRT_TOO_MANY_PEAKS))
+        pairs = [None if no_answer[b] else pfrt_rule.candidates_from_compact({k: out[k][b] for k in _ffi.PFRT_SELECT_COMPACT})
+                 for b in range(len(no_answer))]
+        if not return_info:
+            return pairs
+        self.pfrt_result.update(tau_pfrt=tau_pfrt, raw_pfrt=out['raw_pfrt'], step_pfrt=out['step_pfrt'])
+        return pairs, dict(out, tau_pfrt=tau_pfrt)
+
+    def select_pfrt_candidates(self, start_thresh=0.99, end_thresh=0.01, peak_thresh=1e-6, b=0):
+        """DRT.select_pfrt_candidates (drt1d.py:2860-2865) of member ``b`` of the last PFRT fit, from the device ->
+        (target_peak_indices, step_indices).  Upstream reads pfrt_result here and writes nothing to it; neither does this, and
+        no row comes down.  ValueError where the raw PFRT has nothing at or above peak_thresh (upstream fails there inside
+        find_contiguous_ranges)."""
+        plan, tau_pfrt, chain, factors = self._pfrt_chain('select_pfrt_candidates', None, None, -4, 0.5, None, 0.5, 1e-5, True)
+        out = plan.pfrt_select(factors, np.log(tau_pfrt), _ffi.pfrt_opts(**chain),
+                               _ffi.pfrt_select_opts(start_thresh, end_thresh, peak_thresh), want=_ffi.PFRT_SELECT_COMPACT)
+        status = int(out['status'][b])
+        if status == _ffi.PFRT_NO_PEAK:
+            raise ValueError(f'select_pfrt_candidates: no value of the raw PFRT at or above peak_thresh={peak_thresh}')
+        if status < 0 or status == _ffi.PFRT_TOO_MANY_PEAKS:
+            raise RuntimeError(f'select_pfrt_candidates: member {b} has status {status}')
+        return pfrt_rule.candidates_from_compact({k: out[k][b] for k in _ffi.PFRT_SELECT_COMPACT})
 
     # ---- what DRTMD takes from a finished fit (mapping/drtmd.py:258-279) ----------------------------------------
     def _signed_basis(self, bm, sign):

@@ -959,6 +959,57 @@ int hipdrt_plan_predict_pfrt(hipdrt_plan* plan, const double* factors, const dou
                              const double* ln_tau_out, int neval_out, const hipdrt_pfrt_opts* opts, double* pfrt, double* raw_pfrt,
                              double* step_pfrt, double* post_prob, int* status);
 
+/* DRT.select_pfrt_candidates (hybdrt/models/drt1d.py:2860-2865 over hybdrt/models/pfrt.py:164-213) for every spectrum of the
+ * fitted batch, on the device: the chain of hipdrt_plan_predict_pfrt up to raw_pfrt (opts as there; upstream selects on the raw
+ * PFRT, so its smooth, integrate and normalize fields act on the optional finished row `pfrt` alone), then per spectrum the
+ * contiguous ranges of raw_pfrt >= peak_thresh, their peaks ranked by integrated area (equal areas: the higher index first),
+ * every step's row shifted onto those peaks (an entry at ti moves to the peak of the range with start <= ti <= end, end being
+ * the exclusive end; of several entries that land on one peak the one from the highest index stays), and for each growing set
+ * of best peaks the step with the largest corrcoef(target, shifted row) * step likelihood, by np.argmax's rule (the first
+ * maximum; the first NaN, which an all-zero row gives, beats everything).  The first target holds the peaks whose magnitude
+ * (area / largest area) reaches start_thresh (at least one); targets grow by one peak until the next magnitude is below
+ * end_thresh; the full set is never a target, so K peaks give at most K - 1 candidates.
+ * out (host; any may be NULL), the compact form: num_peaks [B] = K; ranked_index, magnitude [B][max_peaks]; first [B], the
+ * prefix length minus one of the first target; num_candidates [B]; step_index, match_quality [B][max_peaks] -- candidate j has
+ * target ranked_index[0 .. first + j] and step step_index[j], match_quality[j] is the winning value.  Unused slots hold -1 and
+ * NaN.  raw_pfrt, step_pfrt, post_prob: as hipdrt_plan_predict_pfrt.  pfrt [B][neval_out]: the finished PFRT of the same pass,
+ * the bits hipdrt_plan_predict_pfrt gives for the same opts and grids (sel->ln_tau_out, sel->neval_out; without smooth
+ * neval_out == neval_pfrt and the grid is not read); it costs one more launch of the combination, no second pass over the steps.
+ * status [B]: the fit's or the variance path's status as in hipdrt_plan_predict_pfrt.  A negative one leaves every slot unused
+ * and the three counts -1; 0 and 1, a step that ended at its iteration limit, are live fits.  A live fit has
+ * HIPDRT_PFRT_NO_PEAK for a row with nothing at or above peak_thresh (num_peaks 0, upstream raises there) and
+ * HIPDRT_PFRT_TOO_MANY_PEAKS for more ranges than max_peaks (num_peaks holds their number, nothing is ranked).
+ * HIPDRT_E_INVALID before any launch: as hipdrt_plan_predict_pfrt (the smoothing options and the output grid only when pfrt is
+ * asked for), max_peaks outside 1 ... 64, a threshold that is NaN.  HIPDRT_E_UNSUPPORTED for a prepared plan.  The result of a
+ * spectrum depends neither on B nor on its position.                                                                            */
+#define HIPDRT_PFRT_NO_PEAK 16
+#define HIPDRT_PFRT_TOO_MANY_PEAKS 17
+typedef struct {
+    double start_thresh;        /* 0.99                                                                                        */
+    double end_thresh;          /* 0.01                                                                                        */
+    double peak_thresh;         /* 1e-6                                                                                        */
+    int max_peaks;              /* 16; 1 ... 64                                                                                 */
+    const double* ln_tau_out;   /* NULL; [neval_out] the grid of out->pfrt (read with out->pfrt and opts->smooth only)          */
+    int neval_out;              /* 0; points of out->pfrt                                                                       */
+} hipdrt_pfrt_select_opts;
+void hipdrt_pfrt_select_opts_default(hipdrt_pfrt_select_opts* o);
+typedef struct {
+    int* num_peaks;             /* [B]                                                                                          */
+    int* ranked_index;          /* [B][max_peaks]                                                                               */
+    int* first;                 /* [B]                                                                                          */
+    int* num_candidates;        /* [B]                                                                                          */
+    int* step_index;            /* [B][max_peaks]                                                                               */
+    double* magnitude;          /* [B][max_peaks]                                                                               */
+    double* match_quality;      /* [B][max_peaks]                                                                               */
+    double* raw_pfrt;           /* [B][neval_pfrt]                                                                              */
+    double* step_pfrt;          /* [S][B][neval_pfrt]                                                                           */
+    double* post_prob;          /* [S][B]                                                                                       */
+    double* pfrt;               /* [B][sel->neval_out]                                                                          */
+} hipdrt_pfrt_select_out;
+int hipdrt_plan_pfrt_select(hipdrt_plan* plan, const double* factors, const double* ln_tau_pfrt, int neval_pfrt,
+                            const hipdrt_pfrt_opts* opts, const hipdrt_pfrt_select_opts* sel, hipdrt_pfrt_select_out* out,
+                            int* status);
+
 /* ---- candidate models of the fitted batch, scored on the device -----------------------------------------------------------------
  * What DRT.generate_candidates (hybdrt/models/drt1d.py:1632-1821) computes per candidate before it ranks them (1690-1729): the
  * log-likelihood under weights re-estimated from the candidate alone (evaluate_llh(weights=None, x=x), 4457-4496 over

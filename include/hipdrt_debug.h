@@ -213,6 +213,13 @@ int hipdrt_debug_pfrt_combine(hipdrt_ctx* ctx, int B, int S, int neval_pfrt, int
                               const double* rss, const double* sum_log_w, const double* factors, int m,
                               const hipdrt_pfrt_opts* opts, const double* ln_tau_pfrt, const double* ln_tau_out, double* pfrt,
                               double* raw_pfrt, double* post_prob);
+/* test hook (tests/test_gpu_pfrt_select.py): pfrt_select_kernel of csrc/pfrt.hip as it is, on host arrays: raw_pfrt [B][neval_pfrt],
+ * step_pfrt [S][B][neval_pfrt], rss and sum_log_w [S][B], m the number of data rows behind the sums.  out: the compact form of
+ * hipdrt_plan_pfrt_select (its raw_pfrt, step_pfrt, post_prob and pfrt are not written, sel's output grid is not read); status [B]: 0, HIPDRT_PFRT_NO_PEAK or
+ * HIPDRT_PFRT_TOO_MANY_PEAKS.  Every device output has a border of marker bytes: HIPDRT_E_NUMERIC when the kernel wrote outside.   */
+int hipdrt_debug_pfrt_select(hipdrt_ctx* ctx, int B, int S, int neval_pfrt, const double* raw_pfrt, const double* step_pfrt,
+                             const double* rss, const double* sum_log_w, int m, const hipdrt_pfrt_select_opts* sel,
+                             hipdrt_pfrt_select_out* out, int* status);
 
 /* test hook (tests/test_gpu_response.py): the device chain of hipdrt_plan_predict_response behind its layer builders -- the DOP
  * blocks times their scale vectors, the row-application kernel on the S nt stacked rows of U (both copies of a two-copy block) and
