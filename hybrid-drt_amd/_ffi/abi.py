@@ -197,6 +197,26 @@ class DebugHyperArgs(C.Structure):
     ]
 
 
+class DebugSetupArgs(C.Structure):
+    """hipdrt_debug_setup_args (include/hipdrt_debug.h)"""
+    _fields_ = [
+        ("B", C.c_int), ("nf", C.c_int), ("m", C.c_int), ("n", C.c_int), ("ldrm", C.c_int), ("opts", C.POINTER(FitOpts)),
+        ("desc", C.POINTER(PreparedDesc)), ("z_re", _dp), ("z_im", _dp), ("rm", _dp), ("rm_batched", C.c_int), ("vmm", _dp),
+        ("vmm_iw", _dp), ("qp_status", _ip), ("rv", _dp), ("w", _dp), ("est_w", _dp), ("x", _dp), ("x_in", _dp), ("s", _dp),
+        ("rho", _dp), ("xmx", _dp), ("dop_rho", _dp), ("dop_xmx", _dp), ("coef_scale", _dp), ("var_floor", _dp), ("active", _ip),
+        ("outer_iters", _ip), ("fit_status", _ip), ("qp_iters_total", _ip), ("outlier_t", _dp), ("stage", C.c_int), ("r0", C.c_int),
+        ("r1", C.c_int), ("row_mask", C.c_int), ("fixed_chrono", C.c_double), ("fixed_eis", C.c_double), ("wrow", _dp), ("wfac", _dp),
+        ("stored", C.c_int), ("scalar_w", C.c_double), ("rss", _dp), ("slw", _dp), ("w_out", _dp),
+    ]
+
+
+class DebugRowopArgs(C.Structure):
+    """hipdrt_debug_rowop_args (include/hipdrt_debug.h)"""
+    _fields_ = [(k, C.c_int) for k in ("op", "B", "m", "n", "ns", "nf", "ld", "col", "idx_rinf", "idx_induc", "nonneg", "batched")] + [
+        ("factor", C.c_double), ("pen_r", C.c_double), ("pen_l", C.c_double), ("in0", _dp), ("in1", _dp), ("in2", _dp),
+        ("active", _ip), ("out0", _dp), ("out1", _dp), ("out2", _dp)]
+
+
 class DebugPosteriorArgs(C.Structure):
     """hipdrt_debug_posterior_args (include/hipdrt_debug.h)"""
     _fields_ = [("B", C.c_int), ("n", C.c_int), ("P", _dp), ("p_batched", C.c_int), ("ldp", C.c_int), ("rows", _dp),
@@ -364,6 +384,11 @@ SIGNATURES = {
     "hipdrt_debug_gram_l2": [_vp, C.POINTER(DebugGramArgs)],
     "hipdrt_debug_pack_p": [_vp, C.c_int, C.c_int, _dp, C.c_int, _dp],
     "hipdrt_debug_hyper_step": [_vp, C.POINTER(DebugHyperArgs)],
+    "hipdrt_debug_prep": [_vp, C.POINTER(DebugSetupArgs)],
+    "hipdrt_debug_init_weights": [_vp, C.POINTER(DebugSetupArgs)],
+    "hipdrt_debug_weight_method": [_vp, C.POINTER(DebugSetupArgs)],
+    "hipdrt_debug_llh": [_vp, C.POINTER(DebugSetupArgs)],
+    "hipdrt_debug_rowop": [_vp, C.POINTER(DebugRowopArgs)],
     "hipdrt_debug_hyper_form": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.POINTER(C.c_longlong)],
     "hipdrt_debug_impedance_interp_form": [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, C.POINTER(C.c_longlong)],
     "hipdrt_debug_kk_stats": [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(KkOpts), _dp, _ip, _dp, _ip, _ip],

@@ -176,6 +176,58 @@ class DebugHooks:
         out["n_active"] = int(out["n_active"][0])
         return out
 
+    _SETUP_F64 = dict(rv="Bm", w="Bm", est_w="Bm", x="Bn", x_in="Bn", s="B3n", rho="B3", xmx="B3", dop_rho="B3", dop_xmx="B3",
+                      coef_scale="B", var_floor="B", outlier_t="Bm", wrow="Bm", wfac="B2", rss="B", slw="B", w_out="Bm")
+    _SETUP_I32 = ("active", "outer_iters", "fit_status", "qp_iters_total")
+
+    def debug_setup(self, hook, B, m, n, opts: FitOpts, desc: PreparedDesc | None = None, nf=0, z_re=None, z_im=None, rm=None,
+                    vmm=None, vmm_iw=None, qp_status=None, stage=0, r0=0, r1=0, row_mask=False, fixed_chrono=0.0, fixed_eis=0.0,
+                    stored=0, scalar_w=1.0, **state):
+        """tests: one of the setup hooks of include/hipdrt_debug.h -- hook = 'prep' | 'init_weights' | 'weight_method' | 'llh' -- on
+        host arrays.  rm (m, ldrm) shared or (B, m, ldrm); vmm, vmm_iw (m, m).  `state`: the per-spectrum arrays by their names in
+        hipdrt_debug_setup_args, as they are BEFORE the launch (poison where a kernel is to write without reading); they are copied,
+        and the copies come back in a dict as the device holds them AFTER it.  Raises when a kernel wrote outside an array."""
+        b = Bound(DebugSetupArgs())
+        a = b.c
+        a.B, a.nf, a.m, a.n = int(B), int(nf), int(m), int(n)
+        a.opts = C.pointer(b.hold(opts))
+        if desc is not None:
+            a.desc = C.pointer(b.hold(desc))
+        b.array("z_re", z_re, (B, nf)), b.array("z_im", z_im, (B, nf))
+        rm = b.array("rm", rm, [(m, rm.shape[-1]), (B, m, rm.shape[-1])] if rm is not None else None)
+        a.ldrm, a.rm_batched = (rm.shape[-1], int(rm.ndim == 3)) if rm is not None else (n, 0)
+        b.array("vmm", vmm, (m, m)), b.array("vmm_iw", vmm_iw, (m, m))
+        b.array("qp_status", qp_status, (B,), np.int32)
+        a.stage, a.r0, a.r1, a.row_mask = int(stage), int(r0), int(r1), int(bool(row_mask))
+        a.fixed_chrono, a.fixed_eis, a.stored, a.scalar_w = float(fixed_chrono), float(fixed_eis), int(stored), float(scalar_w)
+        dims = dict(B=(B,), Bm=(B, m), Bn=(B, n), B3n=(B, 3, n), B3=(B, 3), B2=(B, 2))
+        out = {}
+        for name, v in state.items():
+            if name in self._SETUP_I32:
+                out[name] = b.array(name, v, (B,), np.int32, copy=True)
+            elif name in self._SETUP_F64:
+                out[name] = b.array(name, v, dims[self._SETUP_F64[name]], copy=True)
+            else:
+                raise ValueError(f"unknown state array {name}")
+        _check(getattr(self._lib, "hipdrt_debug_" + hook)(self._h, C.byref(a)))
+        return out
+
+    def debug_rowop(self, op, out, in0=None, in1=None, in2=None, active=None, B=0, m=0, n=0, ns=0, nf=0, ld=0, col=0, idx_rinf=-1,
+                    idx_induc=-1, nonneg=0, batched=False, factor=1.0, pen_r=0.0, pen_l=0.0):
+        """tests: one element-wise launcher of csrc/hyper.hip on host arrays (hipdrt_debug_rowop, include/hipdrt_debug.h; `op` as
+        numbered there).  out: one array, or the three matrices of op 2, as they are BEFORE the launch; copies come back as the device
+        holds them AFTER it (one array, or a list of three).  Raises when a kernel wrote outside an array."""
+        b = Bound(DebugRowopArgs())
+        a = b.c
+        a.op, a.B, a.m, a.n, a.ns, a.nf, a.ld, a.col = int(op), int(B), int(m), int(n), int(ns), int(nf), int(ld), int(col)
+        a.idx_rinf, a.idx_induc, a.nonneg, a.batched = int(idx_rinf), int(idx_induc), int(nonneg), int(bool(batched))
+        a.factor, a.pen_r, a.pen_l = float(factor), float(pen_r), float(pen_l)
+        b.array("in0", in0), b.array("in1", in1), b.array("in2", in2), b.array("active", active, None, np.int32)
+        outs = list(out) if isinstance(out, (list, tuple)) else [out]
+        res = [b.array(f"out{k}", v, copy=True) for k, v in enumerate(outs)]
+        _check(self._lib.hipdrt_debug_rowop(self._h, C.byref(a)))
+        return res if isinstance(out, (list, tuple)) else res[0]
+
     def debug_kk_stats(self, freq, err, opts: KkOpts | None = None):
         """tests: the statistics stage of the KK screen kernel on host residuals err (B, nf) complex
         (hipdrt_debug_kk_stats, include/hipdrt_debug.h) -> dict(std, outlier_mask, f_lim, i_lim, status)"""

@@ -1,7 +1,7 @@
 // Test and diagnostic hooks of include/hipdrt_debug.h: context switches, and single launchers run on host arrays exactly as
 // the fit loop runs them.  (hipdrt_debug_stream_pool sits with the pool in api.hip; hipdrt_debug_map_gaussian, _map_reduce and
-// _map_prob sit in map_filter.hip and map_predict.hip, next to kernels no other file can name.  debug_guard.hpp holds the bordered
-// device arrays all of them use.)
+// _map_prob sit in map_filter.hip and map_predict.hip, next to kernels no other file can name; the hooks of the launchers that run
+// before the fit loop and after it sit in debug_setup.hip.  debug_guard.hpp holds the bordered device arrays all of them use.)
 #include <cmath>
 #include <cstring>
 
@@ -240,7 +240,7 @@ int hipdrt_debug_hyper_step(hipdrt_ctx* ctx, const hipdrt_debug_hyper_args* a) t
     DevBuf dvmm, dmk[3], dx, dqs, dvs, dve, dpremv;
     std::vector<double> rm_copy(a->rm, a->rm + nrm);
     const size_t bn = (size_t)B * n, bm = (size_t)B * m, b3 = (size_t)B * 3;
-    FitState fs{};
+    FitState fs = debug_fit_state(0, m, n, ns, a->ldrm, a->ldm, a->rm_batched != 0, *a->opts, prep ? &desc : nullptr);
     GuardedOuts g;
     TRY(g.want("rm", rm_copy.data(), nrm, fs.rm_rw, st));
     TRY(upload(dvmm, a->vmm, (size_t)m * m * D, st));
@@ -257,17 +257,14 @@ int hipdrt_debug_hyper_step(hipdrt_ctx* ctx, const hipdrt_debug_hyper_args* a) t
     TRY(g.want("outer_iters", a->outer_iters, B, fs.outer_iters, st)); TRY(g.want("n_active", a->n_active, 1, fs.n_active, st));
     TRY(g.want("outlier_t", a->outlier_t, bm, fs.outlier_t, st));
     TRY(g.want("dop_rho", prep ? a->dop_rho : nullptr, b3, fs.dop_rho, st)); TRY(g.want("dop_xmx", prep ? a->dop_xmx : nullptr, b3, fs.dop_xmx, st));
-    fs.nf = 0; fs.m = m; fs.n = n; fs.ns = ns; fs.ldrm = a->ldrm; fs.ldm = a->ldm;
     fs.toeplitz_m = a->toeplitz ? 1 : 0; fs.toep_reach = a->toeplitz ? a->toep_reach : -1;
-    fs.continue_mode = a->continue_mode; fs.min_iter = a->min_iter; fs.basis_area = a->basis_area; fs.opts = *a->opts;
-    fs.prepared = prep ? 1 : 0; fs.desc = desc;
-    fs.rm_stride = a->rm_batched ? (long long)m * a->ldrm : 0;
+    fs.continue_mode = a->continue_mode; fs.min_iter = a->min_iter; fs.basis_area = a->basis_area;
+    fs.desc = desc;          // (not a prepared step: vz_index -1, the rest zero, as before)
     fs.rm = fs.rm_rw;
     fs.vz_strength = vz ? dvs.d() : nullptr; fs.vz_entry = a->vz_entry ? dve.d() : nullptr;
     fs.vmm = dvmm.d(); fs.vmm_iw = dvmm.d();
     for (int k = 0; k < 3; ++k) fs.mk[k] = dmk[k].d();
     fs.x = dx.d(); fs.qp_status = dqs.i();
-    fs.hist_b = -1; fs.hist_cap = 0;
     if (a->products) {
         HIPDRT_CHECK(dpremv.alloc(3 * (size_t)B * m * D));
         HIPDRT_CHECK(hipMemsetAsync(dpremv.p, 0xFF, 3 * (size_t)B * m * D, st));       // NaN where no product kernel wrote

@@ -46,7 +46,7 @@ struct Guarded {
 // The guarded outputs of one hook, as DevOuts (plan.hpp) holds the plain ones of an entry point: one want() per output, one
 // back() after the launch that fetches every array and then checks every border.
 struct GuardedOuts {
-    static constexpr int MAX = 17;         // hipdrt_debug_hyper_step has 17
+    static constexpr int MAX = 24;         // hipdrt_debug_hyper_step has 17, the setup hooks (debug_setup.hip) up to 22
     Guarded g[MAX];
     int n = 0;
     template <class T>
@@ -101,5 +101,20 @@ struct GuardedBlocks {
         return 0;
     }
 };
+
+// The fields of a FitState that are not arrays, as hipdrt_plan::state() fills them for a problem of these sizes: what
+// hipdrt_debug_hyper_step and the setup hooks (debug_setup.hip) share.  desc null: not a prepared plan.  No history, no product scratch.
+inline FitState debug_fit_state(int nf, int m, int n, int ns, int ldrm, int ldm, bool rm_batched, const hipdrt_fit_opts& opts,
+                                const hipdrt_prepared_desc* desc) {
+    FitState fs{};
+    fs.nf = nf; fs.m = m; fs.n = n; fs.ns = ns; fs.ldrm = ldrm; fs.ldm = ldm;
+    fs.toeplitz_m = 0; fs.toep_reach = -1; fs.continue_mode = 0; fs.min_iter = 1; fs.opts = opts;
+    fs.prepared = desc ? 1 : 0;
+    if (desc) fs.desc = *desc; else fs.desc.vz_index = -1;
+    fs.rm_stride = rm_batched ? (long long)m * ldrm : 0;
+    fs.hist_b = -1; fs.hist_cap = 0;
+    fs.premv = nullptr; fs.premv_batched = 0;
+    return fs;
+}
 
 }  // namespace hipdrt

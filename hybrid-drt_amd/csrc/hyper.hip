@@ -898,7 +898,7 @@ void launch_weight_method(hipStream_t s, const FitState& st, int B, double fixed
 
 int launch_init_weights(hipStream_t s, const FitState& st, int B, int stage, int r0, int r1) {
     const size_t lds = init_weights_lds(nullptr, st.n, st.m, st.opts.outlier_p > 0.0).bytes;
-    if (lds > kLdsLimit) { set_error("initialize_weights: m too large for the LDS-resident kernel"); return HIPDRT_E_INVALID; }
+    if (int rc = lds_check(lds, "initialize_weights", "n + 2 m doubles, n + 4 m with outlier_p")) return rc;
     if (int rc = set_lds(reinterpret_cast<const void*>(init_weights_kernel), lds, "init_weights_kernel")) return rc;
     hipLaunchKernelGGL(init_weights_kernel, dim3(B), dim3(HT), lds, s, st, stage, r0, r1);
     if (stage == 1 || stage == 3) hipLaunchKernelGGL(record_init_qp_kernel, dim3(1), dim3(64), 0, s, st);
@@ -964,6 +964,7 @@ __global__ __launch_bounds__(HT) void llh_kernel(FitState st, double* __restrict
 
 int launch_llh(hipStream_t s, const FitState& st, int B, double* rss, double* slw, int stored, double scalar_w, double* w_out) {
     const size_t lds = llh_lds(nullptr, st.n, st.m).bytes;
+    if (int rc = lds_check(lds, "llh_kernel", "n + 3 m doubles")) return rc;
     if (int rc = set_lds(reinterpret_cast<const void*>(llh_kernel), lds, "llh_kernel")) return rc;
     hipLaunchKernelGGL(llh_kernel, dim3(B), dim3(HT), lds, s, st, rss, slw, stored, scalar_w, w_out);
     return 0;

@@ -270,6 +270,17 @@ int hipdrt_plan_create_prepared(hipdrt_ctx* ctx, const hipdrt_prepared_desc* d, 
     HIPDRT_REQUIRE(d->vb_size >= 0 && d->vb_start >= 0 && d->vb_start + d->vb_size <= d->ns, "v_baseline columns");
     HIPDRT_REQUIRE(d->num_chrono >= 0 && d->num_chrono <= d->m, "num_chrono");
     HIPDRT_REQUIRE(!(opts && opts->update_scale) || d->basis_area > 0.0, "update_scale needs desc.basis_area");
+    if (d->init_weights_separately && d->num_chrono > 0 && d->num_chrono < d->m) {
+        // stage 2 of init_weights_kernel multiplies the whole of V by the residuals of all rows where the reference takes
+        // vmm[sl, sl] (drt1d.py:648-672): the two agree only while no chrono row reads an impedance residual, or the reverse
+        const int nc = d->num_chrono;
+        for (int i = 0; i < d->m; ++i) {
+            const int j0 = i < nc ? nc : 0, j1 = i < nc ? d->m : nc;
+            for (int j = j0; j < j1; ++j)
+                HIPDRT_REQUIRE(vmm[(size_t)i * d->m + j] == 0.0,
+                               "init_weights_separately: vmm must be zero outside its chrono and impedance blocks");
+        }
+    }
     hipStream_t st; TRY(enter(ctx, &st));
     std::unique_ptr<hipdrt_plan> p(new hipdrt_plan());
     p->ctx = ctx;

@@ -14,6 +14,8 @@
  * passes in their LDS and uncached forms), hipdrt_debug_map_reduce (the fixed-order mean, std and min / max) and hipdrt_debug_map_prob
  * (the clamp and probability kernels of a map's rows, fed f and fxx directly); the rank filters are reached through their entry point.
  * The assembly kernels of hipdrt_plan_resolve_group have hipdrt_debug_resolve_assemble (members of their own sizes in, dense P_k out).
+ * What runs before the loop and after it has hipdrt_debug_prep, hipdrt_debug_init_weights, hipdrt_debug_weight_method, hipdrt_debug_llh
+ * and hipdrt_debug_rowop (the element-wise launchers), csrc/debug_setup.hip.
  */
 #ifndef HIPDRT_DEBUG_H
 #define HIPDRT_DEBUG_H
@@ -393,6 +395,70 @@ int hipdrt_debug_map_prob(hipdrt_ctx* ctx, int rows, int n, const double* f, con
  * zero, or when a diagonal tile is not symmetric.  HIPDRT_E_INVALID / HIPDRT_E_UNSUPPORTED, and nothing is launched, as the entry point. */
 int hipdrt_debug_resolve_assemble(hipdrt_ctx* ctx, const hipdrt_resolve_args* args, int B, const double* P, const double* q,
                                   double* P_out, double* q_out);
+
+/* test hooks (tests/test_gpu_setup.py, csrc/debug_setup.hip): what runs before the fit loop and after it -- launch_prep,
+ * launch_row_mask + launch_init_weights, launch_weight_method and launch_llh (csrc/hyper.hip) as they are, on host arrays, with a
+ * FitState filled as hipdrt_plan::state() fills it (hist_b = -1).  One structure serves the four hooks; each names below what it
+ * needs, and refuses a NULL among those.  Arrays are host memory, row-major.  Every per-spectrum array that is given is in/out: its host
+ * contents are uploaded between two borders of marker bytes, the launcher runs, and it is overwritten with what the device holds
+ * afterwards, so it differs from what went in only where a kernel wrote.  HIPDRT_E_NUMERIC when a border changed.  Non-finite
+ * entries of z, rm, vmm, vmm_iw, x, rv, est_w and var_floor are refused where the hook's kernels read them.
+ * Limits: 1 <= B <= 4096, 1 <= m <= 8192, 1 <= n <= 4096, ldrm >= n, 0 <= num_chrono <= m.                                        */
+typedef struct hipdrt_debug_setup_args {
+    int B, nf, m, n, ldrm;
+    const hipdrt_fit_opts* opts;
+    const hipdrt_prepared_desc* desc;      /* or NULL: a plain plan.  Used: num_chrono, chrono_vmm_uniform, dop_rho_0             */
+    const double *z_re, *z_im;             /* [B][nf]: prep of a plain plan (m = 2 nf)                                            */
+    const double* rm;                      /* [rm_batched ? B : 1][m][ldrm]                                                       */
+    int rm_batched;
+    const double *vmm, *vmm_iw;            /* [m][m] each: two uploads, so a read of the wrong one shows                          */
+    const int* qp_status;                  /* [B]                                                                                 */
+    double *rv, *w, *est_w;                /* [B][m]                                                                              */
+    double *x, *x_in;                      /* [B][n]                                                                              */
+    double* s;                             /* [B][3][n]                                                                           */
+    double *rho, *xmx, *dop_rho, *dop_xmx; /* [B][3]                                                                              */
+    double *coef_scale, *var_floor;        /* [B]                                                                                 */
+    int *active, *outer_iters, *fit_status, *qp_iters_total;      /* [B]                                                          */
+    double* outlier_t;                     /* [B][m] or NULL                                                                      */
+    int stage, r0, r1, row_mask;           /* init_weights: stage 0..3; 0 <= r0 < r1 <= m (stage 2, row_mask)                     */
+    double fixed_chrono, fixed_eis;        /* weight rule: > 0 overrides                                                          */
+    double *wrow, *wfac;                   /* weight rule out: [B][m], [B][2]                                                     */
+    int stored;                            /* llh: weight mode 0..3                                                               */
+    double scalar_w;
+    double *rss, *slw;                     /* llh out: [B] each                                                                   */
+    double* w_out;                         /* llh out: [B][m] or NULL                                                             */
+} hipdrt_debug_setup_args;
+/* launch_prep.  Plain (desc NULL): z_re, z_im, nf >= 1, m == 2 nf.  Prepared: rv (read), dop_rho, dop_xmx.  Both: rv, w, s, x, x_in,
+ * rho, xmx, coef_scale, var_floor, active, outer_iters, fit_status, qp_iters_total.                                              */
+int hipdrt_debug_prep(hipdrt_ctx* ctx, const hipdrt_debug_setup_args* a);
+/* row_mask != 0: launch_row_mask(r0, r1) on w first; then launch_init_weights(stage, r0, r1).  Needs rm, vmm, vmm_iw, qp_status, x,
+ * rv, w, est_w, var_floor, active, fit_status.  HIPDRT_E_INVALID, and nothing launched, when (n, m) do not fit one workgroup's LDS. */
+int hipdrt_debug_init_weights(hipdrt_ctx* ctx, const hipdrt_debug_setup_args* a);
+/* launch_weight_method: needs desc with 0 < num_chrono < m (the condition under which the fit launches it), est_w, wrow, wfac.    */
+int hipdrt_debug_weight_method(hipdrt_ctx* ctx, const hipdrt_debug_setup_args* a);
+/* launch_llh(stored, scalar_w, w_out): needs rm, vmm, x, rv, est_w, var_floor, rss, slw.  HIPDRT_E_INVALID, and nothing launched,
+ * when n + 3 m doubles do not fit one workgroup's LDS.                                                                            */
+int hipdrt_debug_llh(hipdrt_ctx* ctx, const hipdrt_debug_setup_args* a);
+
+/* test hook: the element-wise launchers of csrc/hyper.hip, one per call, chosen by `op`.  in0..in2 are read, out0..out2 are in/out
+ * between marker borders as above.  Non-finite inputs are refused.
+ *   0 launch_vmm_exclude_self   in0 vmm [m][m] -> out0 [m][m]
+ *   1 launch_assemble_rm        in0 a_re, in1 a_im [nf][n - ns], in2 freq [nf]; idx_rinf, idx_induc in [-1, ns); factor = the
+ *                               inductance scale -> out0 rm [2 nf][ld], ld >= n (m is not read: the rows are 2 nf)
+ *   2 launch_special_penalty    out0..out2 the three [n][ld] matrices; idx_rinf, idx_induc in [-1, n); pen_r, pen_l
+ *   3 launch_make_h             n, ns, nonneg -> out0 [n]
+ *   4 launch_scale_rows         in0 w [B][m], or NULL: in place on out0; in1 rows [batched ? B : 1][m] or NULL; active [B] or NULL;
+ *                               factor -> out0 [B][m]
+ *   5 launch_scale_weights      out0 w [B][m] in place; active [B]; factor
+ *   6 launch_copy_column        in0 rm [batched ? B : 1][m][ld], 0 <= col < ld -> out0 [B][m]                                      */
+typedef struct hipdrt_debug_rowop_args {
+    int op, B, m, n, ns, nf, ld, col, idx_rinf, idx_induc, nonneg, batched;
+    double factor, pen_r, pen_l;
+    const double *in0, *in1, *in2;
+    const int* active;
+    double *out0, *out1, *out2;
+} hipdrt_debug_rowop_args;
+int hipdrt_debug_rowop(hipdrt_ctx* ctx, const hipdrt_debug_rowop_args* a);
 
 #ifdef __cplusplus
 }
